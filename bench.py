@@ -13,6 +13,11 @@ over independent problems with no data-path collective -> weak sc
 Everything that is timed runs in the PRODUCT library (libdefslam_hip.so); the kernel duration comes from two HIP events
 this script records on the library's launch stream (dsh_stream).  Only the isolated-assembly leg uses the lab build.
 
+A plain run sets up, warms up, times the K steps and prints the line (with the figures derived from those steps).  `--full` adds
+everything that takes runs of its own: the shared-camera and connected-mesh legs, the batch curve, the latency and end-to-end legs, the
+lab build's per-phase and isolated-assembly figures, the CPU baseline and the parity check against the oracle.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+
 Rank 0 prints ONE JSON line; `value` = LM iterations of all ranks / max-over-ranks wall time.
 """
 import argparse
@@ -32,6 +37,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6    # FP64 vector == matrix peak
 PROFILE_ROUND = "r06"
+DUMP_BYTES = 48_000_000    # --dump-outputs: all ranks' arrays together stay below 64 MB
+DUMP_SEED = 20260101       # the fixed sample of problems whose arrays are written when the whole batch does not fit
 
 
 def kernel_source_hash() -> str:
@@ -408,6 +415,43 @@ def connected_leg(local_rank, tmpl, fr, regs):
             c.close()
 
 
+def dump_sample_ids(frames, world):
+    """Local ids of the problems whose arrays --dump-outputs writes: the whole batch when it fits this rank's share of DUMP_BYTES,
+    otherwise a fixed seeded sample of it (the same ids for the same arguments)."""
+    B = len(frames)
+    M, n = frames[0].obs_nodes.shape[0], frames[0].nodes_xyz.shape[0]
+    per_problem = 8 * 3 * n + 8 * M + 4 * M + 4 * 3 * M + 8 * 7 + 4 * 16 + 8 + 8   # xyz, chi2, outlier, map points, pose7, Tcw, rep_error, id
+    fit = max(1, (DUMP_BYTES // world - 4 * 8 * B) // per_problem)
+    if B <= fit:
+        return list(range(B))
+    return sorted(int(i) for i in np.random.default_rng(DUMP_SEED).choice(B, fit, replace=False))
+
+
+def dump_outputs(out_dir, frames, inliers, ids, first_id, rank, world):
+    """What a caller of the timed path receives from the last timed step (dsh_sft_batch_download into the Frame objects): the
+    per-problem counters of every problem, the arrays of the problems `ids` (float64, float32 where the interface is float).  With
+    several ranks every rank writes its own problems, the file names end in _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    sel = [frames[i] for i in ids]
+    arrays = {
+        "iters": np.array([f.iters for f in frames], np.float64),
+        "trials": np.array([f.trials for f in frames], np.float64),
+        "status": np.array([f.status for f in frames], np.float64),
+        "inliers": np.array(inliers, np.float64),
+        "sample_problem_ids": np.array([first_id + i for i in ids], np.float64),
+        "sample_nodes_xyz": np.stack([f.nodes_xyz for f in sel]).astype(np.float64),
+        "sample_pose7": np.stack([f.pose7 for f in sel]).astype(np.float64),
+        "sample_Tcw": np.stack([f.Tcw for f in sel]).astype(np.float32),
+        "sample_rep_error": np.array([f.rep_error_f64 for f in sel], np.float64),
+        "sample_chi2_obs": np.stack([f.chi2_obs for f in sel]).astype(np.float64),
+        "sample_outlier": np.stack([f.mvbOutlier for f in sel]).astype(np.float32),
+        "sample_mappoints": np.stack([f.mappoints for f in sel]).astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,16 +460,21 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="independent problems per GPU per step (default: 16384 for C2 = 64 per CU, 42 GB of HBM: problems need 7-35 damping "
                                                          "trials and a launch ends with its slowest one, so a deep batch amortises the tail; 16 for C5 = BASELINE configs[4])")
     ap.add_argument("--config", default="C2", choices=["smoke", "C2", "C5"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip latency / end-to-end / isolated-assembly legs (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the other legs (batch curve, latency, end-to-end, shared camera, "
+                                                        "connected mesh, lab per-phase and isolated-assembly figures) and the CPU baseline with the parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the results of the last timed step as DIR/<name>.npy (float32 / float64, "
+                                                                        "< 64 MB: counters of every problem, arrays of a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip latency / end-to-end / isolated-assembly legs (profiling runs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one GPU per rank); gloo only to exercise the multi-rank path on a single GPU")
     ap.add_argument("--all-ranks-on-device", type=int, default=-1, help="testing aid: every rank uses this device index instead of LOCAL_RANK")
     ap.add_argument("--dry-ranks", type=int, default=0, help="rehearsal of the N-rank launch on however many GPUs exist: N ranks, rank r on device r mod #GPUs, the real "
                                                              "nccl (RCCL) backend when every rank has its own GPU and gloo otherwise (RCCL refuses two ranks of one communicator "
                                                              "on one device); a per-rank memory guard shrinks the batch to what the shared device holds; the line says dry_ranks")
-    ap.add_argument("--shared-camera", default="auto", choices=["auto", "on", "off"], help="the optional joint-problem leg (library-owned RCCL communicator): auto = on with one "
-                                                                                            "rank, off with several (a collective that has not run on this node yet must not cost the replica line)")
+    ap.add_argument("--shared-camera", default="auto", choices=["auto", "on", "off"], help="the optional joint-problem leg of --full (library-owned RCCL communicator): auto = on "
+                                                                                            "with one rank, off with several (a collective that has not run on this node yet must "
+                                                                                            "not cost the replica line)")
     args = ap.parse_args()
     if args.dry_ranks > 0:
         args.gpus = args.dry_ranks
@@ -434,6 +483,11 @@ def main():
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         sys.exit(2)
+    if args.steps < 1:
+        print("bench.py: --steps must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    extra_legs = args.full and not args.no_extra_legs
+    cpu_leg = args.full and not args.no_cpu_baseline
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, dry=args.dry_ranks > 0))
@@ -492,13 +546,18 @@ def main():
     wall = time.perf_counter() - t0
     iters, trials = ctx.batch_counts()              # per step (every step restarts from the uploaded state)
     parity_ids = [i for i in (0, 1, args.batch // 2, args.batch - 1) if 0 <= i < args.batch]
-    parity_ids = sorted(set(parity_ids)) if (rank == 0 and world == 1 and not args.no_cpu_baseline and args.config != "C5") else []
+    parity_ids = sorted(set(parity_ids)) if (rank == 0 and world == 1 and cpu_leg and args.config != "C5") else []
+    dump_ids = dump_sample_ids(frames, world) if args.dump_outputs else []
+    got = sorted(set(parity_ids) | set(dump_ids))
     gpu_sample = []
-    if parity_ids:                                  # the results of the last timed launch, before any other leg re-uploads
-        ctx.batch_download(only=parity_ids)         # writes the results into the Frame objects (the reference mutates its frame in place) ...
+    if got:                                         # the results of the last timed launch, before any other leg re-uploads
+        inliers = ctx.batch_download(only=got)      # writes the results into the Frame objects (the reference mutates its frame in place) ...
         gpu_sample = [(rank * args.batch + i, frames[i]) for i in parity_ids]
-        for i in parity_ids:                        # ... so the legs below get fresh inputs for these ids
-            frames[i] = sft.frame_from_synth(synth.make_frame(tmpl, m, rank * args.batch + i))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frames, inliers, dump_ids, rank * args.batch, rank, world)
+        if args.full:
+            for i in got:                           # ... so the legs below get fresh inputs for these ids
+                frames[i] = sft.frame_from_synth(synth.make_frame(tmpl, m, rank * args.batch + i))
     infos = [ctx.problem_info(b) for b in range(args.batch)]
     alg_bytes = sum(i[0] for i in infos)
     _, counts = infos[0]
@@ -523,7 +582,7 @@ def main():
     # RCCL all-reduce of the camera block (collective: every rank takes part)
     shared = None
     shared_hung = False
-    if plan["shared_camera"] and not args.no_extra_legs and args.config == "C2":
+    if plan["shared_camera"] and extra_legs and args.config == "C2":
         # The leg is a collective of the library's own RCCL communicator: with several ranks it runs under a watchdog, so that a rank
         # that fails (or a communicator that cannot be formed on this node) costs this optional object, never the replica line above.
         box = {}
@@ -640,7 +699,7 @@ def main():
         if shared is not None:
             out["shared_camera"] = shared
         curve = None
-        if not args.no_extra_legs and not shared_hung and int(counts[7]) == 1 and world == 1:
+        if extra_legs and not shared_hung and int(counts[7]) == 1 and world == 1:
             # The throughput claim at the batch sizes a multi-template / multi-keyframe user would actually have: the PRODUCT library on prefixes of
             # the same batch, HIP events on its stream (3 steps after a warm-up step); the rounds per step are added from the lab build below
             curve = {"what": "product library, prefixes of the benched batch, HIP events on dsh_stream(), 3 timed steps after one warm-up; rounds_per_step = "
@@ -665,7 +724,7 @@ def main():
             rates = [pt["iters_per_s"] for pt in curve["points"]]
             curve["monotone"] = bool(all(b >= a for a, b in zip(rates, rates[1:])))
             out["batch_curve"] = curve
-        if not args.no_extra_legs and not shared_hung:   # (a context stuck in a hung collective cannot run the other legs)
+        if extra_legs and not shared_hung:   # (a context stuck in a hung collective cannot run the other legs)
             # single-problem latency leg (the >=200 iters/s target of BASELINE.json is for ONE problem on one GPU)
             ctx.batch_upload(frames[:1], *regs, 1, 50)
             ctx.batch_run()
@@ -741,7 +800,7 @@ def main():
                 "ms_per_pass": asm_ms, "algorithmic_bytes_per_pass": alg_bytes, "traffic": traffic_asm, "traffic_source": traffic_source,
                 "measured_traffic_GBps": (traffic_asm / (asm_ms * 1e-3) / 1e9) if traffic_asm else None,
                 "library": "libdefslam_hip_lab.so (dsh_lab_sft_assemble_timed -> sft_assembly_kernel)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_leg:
             out["cpu_baseline"], parity = cpu_baseline(tmpl, m, args.cpu_seconds, gpu_sample)
             if parity is not None:
                 out["parity_check"] = parity

@@ -148,3 +148,50 @@ def test_rank_plan_keeps_the_shared_camera_leg_off_with_several_ranks():
         assert b.rank_plan(n, 0, -1, "nccl", env, 8, "on")["shared_camera"] is True            # asked for
         assert b.rank_plan(n, n, -1, "nccl", env, 1, "on")["shared_camera"] is False           # rehearsal on one device: gloo
     assert b.rank_plan(1, 0, -1, "nccl", {}, 1, "off")["shared_camera"] is False
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    """--dump-outputs: the whole batch when it fits, otherwise the same seeded sample for the same arguments; every rank's arrays together
+    stay below 64 MB."""
+    from defslam_amd import sft, synth
+    b = _bench_module()
+    for cfg, B in (("C2", 16384), ("C5", 16), ("smoke", 512)):
+        rows, cols, m = synth.CONFIGS[cfg]
+        fr = sft.frame_from_synth(synth.make_frame(synth.make_grid_template(rows, cols), m, 0))
+        M, n = fr.obs_nodes.shape[0], fr.nodes_xyz.shape[0]
+        for world in (1, 8):
+            ids = b.dump_sample_ids([fr] * B, world)
+            assert ids == b.dump_sample_ids([fr] * B, world)
+            assert ids == sorted(set(ids)) and 0 <= ids[0] and ids[-1] < B
+            per_problem = 8 * 3 * n + 8 * M + 4 * M + 4 * 3 * M + 8 * 7 + 4 * 16 + 8 + 8
+            assert world * (len(ids) * per_problem + 4 * 8 * B) < 64e6
+        if cfg == "C2":
+            assert 1000 < len(b.dump_sample_ids([fr] * B, 1)) < B       # 16384 C2 problems do not fit: a sample of them
+        else:
+            assert b.dump_sample_ids([fr] * B, 1) == list(range(B))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run: the headline fields, none of the --full legs, and with --dump-outputs the results of the last timed step -- float
+    arrays below 64 MB whose per-problem counters add up to what the line reports."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "smoke", "--batch", "64", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    for k in ("cpu_baseline", "parity_check", "batch_curve", "latency", "e2e", "shared_camera", "connected_mesh"):
+        assert k not in d
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert "iters.npy" in files and "sample_nodes_xyz.npy" in files
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) < 64e6
+    a = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["iters"].shape == (64,) and np.array_equal(a["sample_problem_ids"], np.arange(64.0))
+    assert abs(a["iters"].sum() - d["iters_per_frame"] * 64) < 1e-6 * a["iters"].sum()
+    assert a["sample_nodes_xyz"].shape == (64, 100, 3) and np.isfinite(a["sample_nodes_xyz"]).all()

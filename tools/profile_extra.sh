@@ -8,7 +8,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof_${TAG}x
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --config C5 --batch 16 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_c5_b16.log 2> $OUT/bench_c5_b16.err
+python bench.py --full --config C5 --batch 16 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_c5_b16.log 2> $OUT/bench_c5_b16.err
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c5_stats -- python $ROOT/bench.py --config C5 --batch 16 --steps 5 --warmup 1 --no-cpu-baseline --no-extra-legs > $OUT/bench_c5_b16_rocprof.log 2>&1)
 (cd /tmp && rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/c5_fetch -- python $ROOT/bench.py --config C5 --batch 16 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs > $OUT/c5_fetch.log 2>&1)
 (cd /tmp && rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/c5_write -- python $ROOT/bench.py --config C5 --batch 16 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs > $OUT/c5_write.log 2>&1)

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 (hostname; rocm-smi --showuniqueid --showserial --showproductname 2>/dev/null | grep -i "unique\|serial\|Card Model\|Node ID"; lscpu | grep "^Model name"; date -u) > $OUT/box.txt
-python bench.py > $OUT/bench_plain.log 2> $OUT/bench_plain.err
+python bench.py --full > $OUT/bench_plain.log 2> $OUT/bench_plain.err
 cd /tmp
 BA="--no-cpu-baseline --no-extra-legs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $ROOT/bench.py $BA --steps 5 --warmup 1 > $OUT/bench_under_rocprof.log 2>&1
@@ -54,8 +54,8 @@ f=$(find $OUT/c5_stats -name "*kernel_stats.csv" | head -1); cp $f $OUT/c5_b16_k
 for n in pmc_fetch pmc_write asm_fetch asm_write c5_fetch c5_write; do f=$(find $OUT/$n -name "*_counter_collection.csv" | head -1); [ -n "$f" ] && cp $f $OUT/$n.csv; done
 # the traffic file is in place now: the bench lines that carry roofline.traffic
 mkdir -p profiles/r06; cp $OUT/traffic.json profiles/r06/traffic.json
-python bench.py > $OUT/bench_final.log 2> $OUT/bench_final.err
-python bench.py $C5 --steps 10 --warmup 2 > $OUT/bench_c5_b16.log 2> $OUT/bench_c5_b16.err
+python bench.py --full > $OUT/bench_final.log 2> $OUT/bench_final.err
+python bench.py $C5 --full --steps 10 --warmup 2 > $OUT/bench_c5_b16.log 2> $OUT/bench_c5_b16.err
 python tools/bench_nrsfm.py > $OUT/nrsfm_plain.log 2>&1
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/nrsfm_stats -- python $ROOT/tools/bench_nrsfm.py --no-cpu > $OUT/nrsfm_under_rocprof.log 2>&1)
 f=$(find $OUT/nrsfm_stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/nrsfm_kernel_stats.csv

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "${ASM_ONLY:-}" ]; then
-python bench.py "$@" > $OUT/bench_plain.log 2> $OUT/bench_plain.err
+python bench.py --full "$@" > $OUT/bench_plain.log 2> $OUT/bench_plain.err
 fi
 cd /tmp
 if [ -z "${ASM_ONLY:-}" ]; then
