@@ -84,6 +84,22 @@ class SchwarpStoreC(C.Structure):
     _fields_ = [("point_id", C.c_void_p), ("idx2", C.c_void_p), ("tag", C.c_int32)]
 
 
+class TrackFrameC(C.Structure):
+    _fields_ = [("Tcw", c_float_p), ("Ow", C.c_float * 3), ("K", C.c_float * 4), ("bounds", C.c_float * 4), ("grid_cols", C.c_int32),
+                ("grid_rows", C.c_int32), ("levels", C.c_int32), ("scale_factors", c_float_p), ("log_scale_factor", C.c_float), ("N", C.c_int32),
+                ("kp", c_float_p), ("octave", c_i32_p), ("desc", c_u8_p), ("state", c_u8_p)]
+
+
+class TrackProblemC(C.Structure):
+    _fields_ = [("frame", TrackFrameC), ("mode", C.c_int32), ("th", C.c_float), ("Q", C.c_int32), ("xyz", c_float_p), ("octave", c_i32_p),
+                ("normal", c_float_p), ("max_distance", c_float_p), ("desc", c_u8_p), ("skip", c_u8_p), ("match", c_i32_p), ("in_view", c_u8_p),
+                ("level", c_i32_p), ("uv", c_float_p), ("view_cos", c_float_p), ("nmatches", C.c_int32), ("rescans", C.c_int32)]
+
+
+DSH_TRACK_FRAME = 0
+DSH_TRACK_LOCAL = 1
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -100,6 +116,7 @@ EXPORTED_SYMBOLS = [
     "dsh_comm_unique_id", "dsh_comm_create", "dsh_comm_destroy", "dsh_sft_shared_solve", "dsh_sft_shared_solve_group", "dsh_sft_connected_solve", "dsh_sft_connected_solve_group",
     "dsh_diffdb_create", "dsh_diffdb_destroy", "dsh_diffdb_clear", "dsh_diffdb_count", "dsh_diffdb_append", "dsh_schwarp_fit_batch_store",
     "dsh_normals_estimate_db", "dsh_sfn_estimate_db",
+    "dsh_search_by_projection_batch", "dsh_search_by_projection_frame", "dsh_search_by_projection_local",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -191,6 +208,10 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_sft_shared_solve_group.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(SftFrameC), C.POINTER(SftResultC)]
     L.dsh_sft_connected_solve.argtypes = [vp, vp, C.POINTER(SftFrameC), C.POINTER(SftResultC)]
     L.dsh_sft_connected_solve_group.argtypes = [vp, vp, C.POINTER(SftFrameC), C.POINTER(SftResultC)]
+    L.dsh_search_by_projection_batch.argtypes = [vp, C.c_int, C.POINTER(TrackProblemC)]
+    L.dsh_search_by_projection_frame.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_float_p, c_i32_p, c_u8_p, C.c_float, c_i32_p, c_i32_p]
+    L.dsh_search_by_projection_local.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p, C.c_float,
+                                                 c_i32_p, c_u8_p, c_i32_p, c_i32_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

@@ -1,0 +1,252 @@
+// Host side of the tracking searches (include/defslam_hip.h: dsh_search_by_projection_*): validation, one packed upload, the three
+// launches of track_kernels.hip, one download.
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/defslam_hip.h"
+#include "dsh_ctx.h"
+#include "track_problem.h"
+
+namespace {
+
+#define TRK_HIPCHK(c, call)                                                                                   \
+  do {                                                                                                        \
+    hipError_t e__ = (call);                                                                                  \
+    if (e__ != hipSuccess) {                                                                                  \
+      (void)hipStreamSynchronize((c)->stream);                                                                \
+      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                     \
+    }                                                                                                         \
+  } while (0)
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+std::string frame_error(const dsh_track_frame& f) {
+  if (!f.Tcw) return "Tcw is NULL";
+  for (int k = 0; k < 4; k++)
+    if (!std::isfinite(f.K[k]) || !std::isfinite(f.bounds[k])) return "K / bounds not finite";
+  if (!(f.bounds[1] > f.bounds[0]) || !(f.bounds[3] > f.bounds[2])) return "empty image bounds";
+  if (f.grid_cols <= 0 || f.grid_rows <= 0 || (long long)f.grid_cols * f.grid_rows > TRK_MAX_CELLS) return "grid size outside 1 .. 8192 cells";
+  if (f.levels <= 0 || f.levels > TRK_MAX_LEVELS || !f.scale_factors) return "levels outside 1 .. 32 or no scale factors";
+  if (f.N < 0 || f.N > TRK_MAX_KEYPOINTS) return "N outside 0 .. 8192";
+  if (f.N > 0 && (!f.kp || !f.octave || !f.desc || !f.state)) return "key point arrays are NULL";
+  for (int j = 0; j < f.N; j++) {
+    if (f.octave[j] < 0 || f.octave[j] > 127) return "key point octave outside 0 .. 127";
+    if (f.state[j] > 2) return "key point state not 0, 1 or 2";
+  }
+  return "";
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* problems) {
+  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  if (!c) return DSH_ERR_ARG;
+  if (B < 0 || (B > 0 && !problems)) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: bad batch");
+  // validation, sizes and offsets
+  long long Nt = 0, Qt = 0, Ct = 0;
+  for (int p = 0; p < B; p++) {
+    dsh_track_problem& pr = problems[p];
+    const std::string fe = frame_error(pr.frame);
+    auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(p) + ": " + m); };
+    if (!fe.empty()) return bad(fe);
+    if (pr.mode != DSH_TRACK_FRAME && pr.mode != DSH_TRACK_LOCAL) return bad("mode is neither DSH_TRACK_FRAME nor DSH_TRACK_LOCAL");
+    if (!(pr.th > 0.0f) || !std::isfinite(pr.th)) return bad("th must be a positive finite number");
+    if (pr.Q < 0) return bad("Q < 0");
+    if (pr.Q > 0 && (!pr.xyz || !pr.desc || !pr.match)) return bad("query arrays are NULL");
+    if (pr.Q > 0 && pr.mode == DSH_TRACK_FRAME) {
+      if (!pr.octave) return bad("frame to frame needs the query octaves");
+      for (int q = 0; q < pr.Q; q++)
+        if (pr.octave[q] < 0 || pr.octave[q] >= pr.frame.levels) return bad("query octave outside 0 .. levels-1");
+    }
+    if (pr.Q > 0 && pr.mode == DSH_TRACK_LOCAL && (!pr.normal || !pr.max_distance)) return bad("the local map needs normals and max distances");
+    Nt += pr.frame.N;
+    Qt += pr.Q;
+    Ct += (long long)pr.frame.grid_cols * pr.frame.grid_rows + 1;
+  }
+  if (Qt > (1LL << 28) || Nt > (1LL << 28)) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: batch too large");
+  for (int p = 0; p < B; p++) problems[p].nmatches = problems[p].rescans = 0;
+  // arguments first, so that a host-only context reports bad ones too
+  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_search_by_projection: host-only context, no GPU (there is no CPU fallback)");
+  if (B == 0) return DSH_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_search_by_projection: hipSetDevice failed");
+
+  // one host buffer, one copy up: problem descriptors, key points, queries
+  const size_t o_prob = 0, o_kp = align256(sizeof(TrkProb) * B), o_km = o_kp + align256(8 * Nt), o_kd = o_km + align256(4 * Nt),
+               o_qpid = o_kd + align256(32 * Nt), o_qxyz = o_qpid + align256(4 * Qt), o_qnrm = o_qxyz + align256(12 * Qt),
+               o_qmaxd = o_qnrm + align256(12 * Qt), o_qmeta = o_qmaxd + align256(4 * Qt), o_qdesc = o_qmeta + align256(4 * Qt),
+               up_bytes = o_qdesc + align256(32 * Qt);
+  // downloads: match, level, in view, uv, view cos, per-problem counters
+  const size_t d_match = 0, d_level = align256(4 * Qt), d_inview = d_level + align256(4 * Qt), d_uv = d_inview + align256(4 * Qt),
+               d_vcos = d_uv + align256(8 * Qt), d_pstat = d_vcos + align256(4 * Qt), down_bytes = d_pstat + align256(16 * (size_t)B);
+  TRK_HIPCHK(c, c->pin_in.ensure(up_bytes));
+  TRK_HIPCHK(c, c->pin_out.ensure(down_bytes));
+  char* h = c->pin_in.p;
+  long long kp_off = 0, q_off = 0, cell_off = 0;
+  for (int p = 0; p < B; p++) {
+    const dsh_track_problem& pr = problems[p];
+    const dsh_track_frame& f = pr.frame;
+    TrkProb P;
+    std::memset(&P, 0, sizeof(P));
+    for (int i = 0; i < 3; i++) {
+      for (int k = 0; k < 3; k++) P.R[3 * i + k] = f.Tcw[4 * i + k];
+      P.t[i] = f.Tcw[4 * i + 3];
+      P.Ow[i] = f.Ow[i];
+    }
+    P.fx = f.K[0]; P.fy = f.K[1]; P.cx = f.K[2]; P.cy = f.K[3];
+    P.minX = f.bounds[0]; P.maxX = f.bounds[1]; P.minY = f.bounds[2]; P.maxY = f.bounds[3];
+    // Frame.cc:97-98: mfGridElementWidthInv = float(FRAME_GRID_COLS) / (mnMaxX - mnMinX)
+    P.winv = (float)f.grid_cols / (P.maxX - P.minX);
+    P.hinv = (float)f.grid_rows / (P.maxY - P.minY);
+    P.logsf = f.log_scale_factor;
+    P.th = pr.th;
+    for (int l = 0; l < f.levels; l++) P.sf[l] = f.scale_factors[l];
+    P.cols = f.grid_cols; P.rows = f.grid_rows; P.levels = f.levels; P.mode = pr.mode;
+    P.N = f.N; P.Q = pr.Q; P.kp_off = (int32_t)kp_off; P.q_off = (int32_t)q_off; P.cell_off = (int32_t)cell_off;
+    std::memcpy(h + o_prob + sizeof(TrkProb) * p, &P, sizeof(P));
+    if (f.N > 0) {
+      std::memcpy(h + o_kp + 8 * kp_off, f.kp, 8 * (size_t)f.N);
+      int32_t* km = reinterpret_cast<int32_t*>(h + o_km) + kp_off;
+      for (int j = 0; j < f.N; j++) km[j] = f.octave[j] | ((int32_t)f.state[j] << 8);
+      std::memcpy(h + o_kd + 32 * kp_off, f.desc, 32 * (size_t)f.N);
+    }
+    if (pr.Q > 0) {
+      int32_t* qpid = reinterpret_cast<int32_t*>(h + o_qpid) + q_off;
+      int32_t* qmeta = reinterpret_cast<int32_t*>(h + o_qmeta) + q_off;
+      for (int q = 0; q < pr.Q; q++) {
+        qpid[q] = p;
+        qmeta[q] = pr.mode == DSH_TRACK_FRAME ? pr.octave[q] : (pr.skip && pr.skip[q] ? 1 : 0);
+      }
+      std::memcpy(h + o_qxyz + 12 * q_off, pr.xyz, 12 * (size_t)pr.Q);
+      if (pr.mode == DSH_TRACK_LOCAL) {
+        std::memcpy(h + o_qnrm + 12 * q_off, pr.normal, 12 * (size_t)pr.Q);
+        std::memcpy(h + o_qmaxd + 4 * q_off, pr.max_distance, 4 * (size_t)pr.Q);
+      }
+      std::memcpy(h + o_qdesc + 32 * q_off, pr.desc, 32 * (size_t)pr.Q);
+    }
+    kp_off += f.N;
+    q_off += pr.Q;
+    cell_off += (long long)f.grid_cols * f.grid_rows + 1;
+  }
+
+  c->scratch.reset();
+  hipStream_t st = c->stream;
+  void *dup = nullptr, *dcell = nullptr, *dskp = nullptr, *dsmeta = nullptr, *dsdesc = nullptr, *dkeys = nullptr, *dncand = nullptr, *dwin = nullptr,
+       *ddown = nullptr;
+  TRK_HIPCHK(c, c->scratch.take(up_bytes, &dup));
+  TRK_HIPCHK(c, c->scratch.take(4 * (size_t)Ct, &dcell));
+  TRK_HIPCHK(c, c->scratch.take(8 * (size_t)Nt, &dskp));
+  TRK_HIPCHK(c, c->scratch.take(4 * (size_t)Nt, &dsmeta));
+  TRK_HIPCHK(c, c->scratch.take(32 * (size_t)Nt, &dsdesc));
+  TRK_HIPCHK(c, c->scratch.take(8 * (size_t)TRK_K * Qt, &dkeys));
+  TRK_HIPCHK(c, c->scratch.take(4 * (size_t)Qt, &dncand));
+  TRK_HIPCHK(c, c->scratch.take(sizeof(TrkWin) * (size_t)Qt, &dwin));
+  TRK_HIPCHK(c, c->scratch.take(down_bytes, &ddown));
+  TRK_HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
+  char* du = static_cast<char*>(dup);
+  char* dd = static_cast<char*>(ddown);
+  TRK_HIPCHK(c, hipMemsetAsync(dd + d_pstat, 0, 16 * (size_t)B, st));
+  TrkBufs b;
+  b.prob = reinterpret_cast<const TrkProb*>(du + o_prob);
+  b.kp = reinterpret_cast<const float2*>(du + o_kp);
+  b.kmeta = reinterpret_cast<const int32_t*>(du + o_km);
+  b.kdesc = reinterpret_cast<const uint4*>(du + o_kd);
+  b.cell_start = static_cast<int32_t*>(dcell);
+  b.skp = static_cast<float2*>(dskp);
+  b.smeta = static_cast<int32_t*>(dsmeta);
+  b.sdesc = static_cast<uint4*>(dsdesc);
+  b.qpid = reinterpret_cast<const int32_t*>(du + o_qpid);
+  b.qxyz = reinterpret_cast<const float*>(du + o_qxyz);
+  b.qnrm = reinterpret_cast<const float*>(du + o_qnrm);
+  b.qmaxd = reinterpret_cast<const float*>(du + o_qmaxd);
+  b.qmeta = reinterpret_cast<const int32_t*>(du + o_qmeta);
+  b.qdesc = reinterpret_cast<const uint4*>(du + o_qdesc);
+  b.keys = static_cast<unsigned long long*>(dkeys);
+  b.ncand = static_cast<int32_t*>(dncand);
+  b.win = static_cast<TrkWin*>(dwin);
+  b.match = reinterpret_cast<int32_t*>(dd + d_match);
+  b.level = reinterpret_cast<int32_t*>(dd + d_level);
+  b.inview = reinterpret_cast<int32_t*>(dd + d_inview);
+  b.uv = reinterpret_cast<float*>(dd + d_uv);
+  b.vcos = reinterpret_cast<float*>(dd + d_vcos);
+  b.pstat = reinterpret_cast<int32_t*>(dd + d_pstat);
+  TRK_HIPCHK(c, trk_launch(b, B, (int)Qt, st));
+  TRK_HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  TRK_HIPCHK(c, hipStreamSynchronize(st));
+
+  const char* o = c->pin_out.p;
+  const int32_t* pstat = reinterpret_cast<const int32_t*>(o + d_pstat);
+  for (int p = 0; p < B; p++)
+    if (pstat[4 * p + 2])
+      return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(p) + ": a query window holds more than 4096 candidates");
+  q_off = 0;
+  for (int p = 0; p < B; p++) {
+    dsh_track_problem& pr = problems[p];
+    const size_t Q = (size_t)pr.Q;
+    if (Q > 0) {
+      std::memcpy(pr.match, o + d_match + 4 * q_off, 4 * Q);
+      if (pr.mode == DSH_TRACK_LOCAL) {
+        const int32_t* iv = reinterpret_cast<const int32_t*>(o + d_inview) + q_off;
+        if (pr.in_view)
+          for (size_t q = 0; q < Q; q++) pr.in_view[q] = (uint8_t)iv[q];
+        if (pr.level) std::memcpy(pr.level, o + d_level + 4 * q_off, 4 * Q);
+        if (pr.uv) std::memcpy(pr.uv, o + d_uv + 8 * q_off, 8 * Q);
+        if (pr.view_cos) std::memcpy(pr.view_cos, o + d_vcos + 4 * q_off, 4 * Q);
+      }
+    }
+    pr.nmatches = pstat[4 * p];
+    pr.rescans = pstat[4 * p + 1];
+    q_off += pr.Q;
+  }
+  return DSH_OK;
+}
+
+int dsh_search_by_projection_frame(dsh_ctx* ctx, const dsh_track_frame* frame, int Q, const float* xyz, const int32_t* octave,
+                                   const uint8_t* desc, float th, int32_t* match, int32_t* nmatches) {
+  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  if (!c) return DSH_ERR_ARG;
+  if (!frame) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection_frame: frame is NULL");
+  dsh_track_problem pr;
+  std::memset(&pr, 0, sizeof(pr));
+  pr.frame = *frame;
+  pr.mode = DSH_TRACK_FRAME;
+  pr.th = th;
+  pr.Q = Q;
+  pr.xyz = xyz;
+  pr.octave = octave;
+  pr.desc = desc;
+  pr.match = match;
+  const int rc = dsh_search_by_projection_batch(ctx, 1, &pr);
+  if (rc == DSH_OK && nmatches) *nmatches = pr.nmatches;
+  return rc;
+}
+
+int dsh_search_by_projection_local(dsh_ctx* ctx, const dsh_track_frame* frame, int Q, const float* xyz, const float* normal,
+                                   const float* max_distance, const uint8_t* desc, const uint8_t* skip, float th, int32_t* match,
+                                   uint8_t* in_view, int32_t* level, int32_t* nmatches) {
+  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  if (!c) return DSH_ERR_ARG;
+  if (!frame) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection_local: frame is NULL");
+  dsh_track_problem pr;
+  std::memset(&pr, 0, sizeof(pr));
+  pr.frame = *frame;
+  pr.mode = DSH_TRACK_LOCAL;
+  pr.th = th;
+  pr.Q = Q;
+  pr.xyz = xyz;
+  pr.normal = normal;
+  pr.max_distance = max_distance;
+  pr.desc = desc;
+  pr.skip = skip;
+  pr.match = match;
+  pr.in_view = in_view;
+  pr.level = level;
+  const int rc = dsh_search_by_projection_batch(ctx, 1, &pr);
+  if (rc == DSH_OK && nmatches) *nmatches = pr.nmatches;
+  return rc;
+}
+
+}  // extern "C"

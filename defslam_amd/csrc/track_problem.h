@@ -1,0 +1,60 @@
+// Device-side layout of the tracking searches (dsh_search_by_projection_*, dsh_track.cpp -> track_kernels.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define TRK_K 4                 // keys (distance, visiting order) phase A keeps per query
+#define TRK_MAX_LEVELS 32
+#define TRK_MAX_KEYPOINTS 8192  // the "taken" bitmap of phase B: 1 KB of LDS
+#define TRK_MAX_CELLS 8192      // FRAME_GRID_COLS x FRAME_GRID_ROWS (64 x 48 in the reference)
+#define TRK_MAX_CANDIDATES 4096 // key points in one query's window; more is DSH_ERR_ARG (bounds phase B's serial re-scan)
+#define TRK_TH_HIGH 75          // ORBmatcher::TH_HIGH of this reference (ORBmatcher.cc:35)
+#define TRK_NO_KEY 0xFFFFFFFFFFFFFFFFull
+
+// one frame of the batch: its pose, camera, grid, pyramid and where its arrays start in the concatenated buffers
+struct TrkProb {
+  float R[9], t[3], Ow[3];
+  float fx, fy, cx, cy, minX, maxX, minY, maxY, winv, hinv, logsf, th;
+  float sf[TRK_MAX_LEVELS];
+  int32_t cols, rows, levels, mode, N, Q, kp_off, q_off, cell_off, pad;
+};
+
+// what phase B needs to walk a query's window again
+struct TrkWin {
+  float u, v, r;
+  int32_t lmin, lmax, pad[3];
+};
+
+struct TrkBufs {
+  const TrkProb* prob;
+  // key points of every frame, concatenated (TrkProb::kp_off): mvKeysUn x y, octave | state << 8, 32-byte descriptor
+  const float2* kp;
+  const int32_t* kmeta;
+  const uint4* kdesc;
+  // grid cells: CSR start per frame at cell_off (cols * rows + 1 entries), key points in cell order (index order within a
+  // cell is not kept: the search orders candidates by the explicit key (cell, index))
+  int32_t* cell_start;
+  float2* skp;
+  int32_t* smeta;   // index | octave << 16 | state << 24
+  uint4* sdesc;
+  // queries of every frame, concatenated (TrkProb::q_off)
+  const int32_t* qpid;
+  const float* qxyz;
+  const float* qnrm;
+  const float* qmaxd;
+  const int32_t* qmeta;   // frame to frame: the last frame's octave; local map: the skip flag
+  const uint4* qdesc;
+  // phase A -> phase B
+  unsigned long long* keys;   // TRK_K per query
+  int32_t* ncand;
+  TrkWin* win;
+  // outputs
+  int32_t* match;
+  int32_t* level;
+  int32_t* inview;
+  float* uv;
+  float* vcos;
+  int32_t* pstat;   // 4 per frame: matches, queries re-scanned in phase B, window over TRK_MAX_CANDIDATES, unused
+};
+
+extern "C" hipError_t trk_launch(const TrkBufs& b, int B, int Qt, hipStream_t st);

@@ -535,3 +535,129 @@ def make_interleaved_sequence(n_frames: int = 41, kf_every: int = 10, n_points: 
                 invsig=invsig, depth=depth, X0=X0, frames=frames, kfs=kfs, n_tracked=n_tracked, cam=np.array([fx, fy, cx, cy], np.float32),
                 bounds=np.array([0.0, 640.0, 0.0, 480.0], np.float32), Twc=Twc, scale_true=scale_true, nodes0=nodes0, mesh=mesh, grid_uv=(gu, gv),
                 facets=regular_triangulation(rows, cols), noise=noise, n_frames=n_frames, kf_every=kf_every)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Tracking searches (defslam_amd/track.py): a current frame with ORB-like key points around the projections of map points
+# embedded in a deformed template, the last frame's map points (frame-to-frame queries) and local map points with normals.
+# ---------------------------------------------------------------------------------------------------------
+def _flip_bits(rng, d, n):
+    d = d.copy()
+    for f in rng.choice(256, size=int(n), replace=False):
+        d[f // 8] ^= np.uint8(1 << (f % 8))
+    return d
+
+
+def make_track_scene(seed: int = 0, n_kp: int = 1200, n_frame_q: int = 400, n_local_q: int = 300, mappoint_xyz=None, Tcw=None,
+                     levels: int = 8, adversarial: bool = True, state_mix: bool = False, n_clusters: int = 6):
+    """One current frame and the queries of both searches (returns dict(frame=track.TrackFrame, fq=FrameQueries, lq=LocalQueries,
+    point_xyz, kp_of_point)).  Map points: float32 positions on a bent 10 x 10 template (or mappoint_xyz, e.g. a
+    dsh_sft_result.mappoint_xyz, so that SfT(t) -> search(t+1) -> SfT(t+1) can be chained); the current pose moves slightly away
+    from Tcw (identity when None), which is the pose the searches project with.  Key points: one per map point near its projection
+    (descriptor = the point's with a few flipped bits, octave drawn around the point's), distractors, exact duplicates (distance
+    ties) and, with adversarial, clusters of near-identical key points that several queries want (in-call conflicts that exhaust a
+    query's stored keys).  Local points get normals with viewCos spread over [0.3, 1] and max distances that put the predicted level
+    0.1 .. 0.9 of a level away from a boundary; viewCos is kept 1e-3 away from 0.5 and 0.998.  state_mix draws key point states
+    0 / 1 / 2 (otherwise all 0)."""
+    from . import track
+    rng = np.random.default_rng(1000 + seed)
+    fx, fy, cx, cy = CAMERA_K
+    K = np.array(CAMERA_K, np.float32)
+    bounds = np.array([0.0, 640.0, 0.0, 480.0], np.float32)
+    sf, logsf = track.orb_pyramid(levels)
+    T0 = np.eye(4, dtype=np.float32) if Tcw is None else np.asarray(Tcw, np.float32)
+    if mappoint_xyz is None:
+        tmpl = make_grid_template(10, 10, seed=1234 + seed)
+        n_pts = max(n_frame_q, n_local_q) + 50
+        fac = rng.integers(0, tmpl.facets.shape[0], n_pts)
+        bary = rng.dirichlet((1.0, 1.0, 1.0), n_pts)
+        gt = tmpl.xyz0.copy()
+        gt[:, 2] += 0.05 * np.sin(2 * np.pi * (gt[:, 0] - gt[:, 0].min()) / np.ptp(gt[:, 0]) + 0.3 * seed)
+        pts = (bary[:, :, None] * gt[tmpl.facets[fac]]).sum(1).astype(np.float32)
+    else:
+        pts = np.asarray(mappoint_xyz, np.float32).reshape(-1, 3)
+    P = pts.shape[0]
+    # the current frame's pose: a small motion away from T0 (float32, as cv::Mat mTcw)
+    dT = np.eye(4)
+    dT[:3, :3] = _rodrigues(rng.normal(size=3) * 0.004)
+    dT[:3, 3] = rng.uniform(-0.004, 0.004, 3)
+    Tc = (dT @ T0.astype(np.float64)).astype(np.float32)
+    Ow = track.camera_center(Tc)
+    Xc = pts.astype(np.float64) @ Tc[:3, :3].astype(np.float64).T + Tc[:3, 3].astype(np.float64)
+    uv = np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
+    pdesc = rng.integers(0, 256, (P, 32), dtype=np.uint8)
+    poct = rng.integers(0, levels - 2, P)
+    kp, koct, kdesc, kp_of_point = [], [], [], np.full(P, -1, np.int64)
+    for i in range(P):
+        if rng.uniform() < 0.1:                                   # not detected in this frame
+            continue
+        kp_of_point[i] = len(kp)
+        kp.append(uv[i] + rng.uniform(-1.5, 1.5, 2))
+        koct.append(int(np.clip(poct[i] + rng.integers(-1, 2), 0, levels - 1)))
+        kdesc.append(_flip_bits(rng, pdesc[i], rng.integers(0, 40)))
+        if rng.uniform() < 0.15:                                  # a near-identical second detection: distance tie
+            kp.append(kp[-1] + rng.uniform(-0.5, 0.5, 2))
+            koct.append(koct[-1])
+            kdesc.append(kdesc[-1].copy())
+        if rng.uniform() < 0.3:                                   # a close distractor
+            kp.append(uv[i] + rng.uniform(-6, 6, 2))
+            koct.append(int(rng.integers(0, levels)))
+            kdesc.append(_flip_bits(rng, pdesc[i], rng.integers(10, 90)))
+    clusters = []
+    if adversarial:
+        for c in range(n_clusters):                               # several queries want the same few key points
+            i = int(rng.integers(0, P))
+            clusters.append(i)
+            for _ in range(8):
+                kp.append(uv[i] + rng.uniform(-1.0, 1.0, 2))
+                koct.append(int(np.clip(poct[i], 0, levels - 1)))
+                kdesc.append(_flip_bits(rng, pdesc[i], rng.integers(0, 12)))
+    n_extra = max(0, n_kp - len(kp))
+    kp += list(np.stack([rng.uniform(-5, 645, n_extra), rng.uniform(-5, 485, n_extra)], 1))
+    koct += list(rng.integers(0, levels, n_extra))
+    kdesc += list(rng.integers(0, 256, (n_extra, 32), dtype=np.uint8))
+    kp = np.asarray(kp, np.float32)
+    koct = np.asarray(koct, np.int32)
+    kdesc = np.asarray(kdesc, np.uint8)
+    perm = rng.permutation(kp.shape[0])
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(perm.shape[0])
+    kp, koct, kdesc = kp[perm], koct[perm], kdesc[perm]
+    kp_of_point = np.where(kp_of_point >= 0, inv[np.maximum(kp_of_point, 0)], -1)
+    N = kp.shape[0]
+    state = np.zeros(N, np.uint8)
+    if state_mix:
+        state = rng.choice(np.array([0, 1, 2], np.uint8), N, p=[0.7, 0.15, 0.15])
+    frame = track.TrackFrame(Tcw=Tc, K=K, bounds=bounds, kp=kp, octave=koct, desc=kdesc, scale_factors=sf, log_scale_factor=float(logsf),
+                             state=state, Ow=Ow)
+    # frame-to-frame queries: map points in the last frame's index order, conflicts included (the cluster points repeat)
+    order = rng.permutation(P)
+    qi = np.concatenate([order[:n_frame_q], np.repeat(np.asarray(clusters, np.int64), 3)]) if n_frame_q else np.zeros(0, np.int64)
+    rng.shuffle(qi)
+    fq = track.FrameQueries(xyz=pts[qi], octave=np.clip(poct[qi], 0, levels - 1).astype(np.int32), desc=pdesc[qi])
+    # local points: normals and max distances around the thresholds' safe sides
+    li = np.concatenate([order[::-1][:n_local_q], np.repeat(np.asarray(clusters, np.int64), 3)]) if n_local_q else np.zeros(0, np.int64)
+    rng.shuffle(li)
+    L = li.shape[0]
+    PO = pts[li].astype(np.float64) - Ow.astype(np.float64)
+    dist = np.linalg.norm(PO, axis=1) if L else np.zeros(0)
+    dirn = PO / np.maximum(dist[:, None], 1e-12)
+    normals = np.zeros((L, 3), np.float32)
+    maxd = np.zeros(L, np.float32)
+    for k in range(L):
+        while True:
+            target = rng.choice([rng.uniform(0.3, 0.997), rng.uniform(0.9985, 1.0)])
+            w = rng.normal(size=3)
+            w -= w.dot(dirn[k]) * dirn[k]
+            w /= np.linalg.norm(w)
+            n = target * dirn[k] + np.sqrt(max(0.0, 1 - target * target)) * w
+            n = n.astype(np.float32)
+            vc = float(PO[k].dot(n.astype(np.float64)) / dist[k])
+            if abs(vc - 0.5) > 1e-3 and abs(vc - 0.998) > 1e-3:
+                break
+        normals[k] = n
+        lev = rng.integers(-1, levels + 1) + rng.uniform(0.1, 0.9)
+        maxd[k] = np.float32(dist[k] * 1.2 ** lev)
+    skip = (rng.uniform(size=L) < 0.05).astype(np.uint8)
+    lq = track.LocalQueries(xyz=pts[li], normal=normals, max_distance=maxd, desc=pdesc[li], skip=skip)
+    return dict(frame=frame, fq=fq, lq=lq, point_xyz=pts, kp_of_point=kp_of_point, frame_points=qi, local_points=li)

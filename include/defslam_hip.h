@@ -392,6 +392,91 @@ int dsh_surface_register(dsh_ctx* ctx, int n, const float* cloud_surface /* n*3 
                          int64_t nu, const float* Twc /* 16 */, double chi_limit, int check_chi, int32_t* registered, double* sim3 /* 8 */,
                          double* s22, float* Tcw_new /* 16 */, double* info /* 8 */);
 
+/* ---- tracking: search by projection (the observations of the SfT problem) ----------------------------------------------
+ * DefTracking::TrackWithMotionModel (Modules/Tracking/DefTracking.cc:342-375) and DefTracking::TrackLocalMap -> SearchLocalPoints
+ * (DefTracking.cc:234-250, Thirdparty/ORBSLAM_2/src/Tracking.cc:1405-1470) match map points to the key points of the current frame:
+ *   frame to frame  ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)        ORBmatcher.cc:1360-1510
+ *   local map       Frame::isInFrustum(pMP, 0.5) (Frame.cc:338-390), MapPoint::PredictScale (MapPoint.cc:422-437),
+ *                   ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th), nn-ratio 0.8 (ORBmatcher.cc:42-143)
+ * Both are the monocular paths DefSLAM runs: no stereo branch (mvuRight, bForward / bBackward) and no rotation histogram
+ * (compiled out by `if (false)` in the reference).  TH_HIGH is this reference's 75 (ORBmatcher.cc:35).  Candidates come from
+ * Frame::GetFeaturesInArea (Frame.cc:421-480) over the grid of Frame::PosInGrid (Frame.cc:484-496): |dx| < r and |dy| < r, octave in
+ * [min level, max level], visiting order column, row, index; the best is the first strictly smaller Hamming distance in that order.
+ * Queries interact within a call exactly as in the reference: a key point assigned to an earlier query holds a map point with
+ * observations and is no candidate for a later one.  match[] is bit-exact.
+ * Key point state on input (state[j]): 0 no map point, 1 a map point with observations (never a candidate), 2 a map point without
+ * observations (a candidate; frame to frame drops a best that lands on it, ORBmatcher.cc:1462; the local map overwrites it).
+ * DefTracking.cc:358 calls DefORBmatcher's copy of the frame-to-frame search (Modules/Matching/DefORBmatcher.cc:296-420): it also
+ * skips bad points and points without a facet (the caller leaves them out of the queries) and overwrites instead of dropping; the
+ * two agree whenever no key point enters in state 2, which TrackWithMotionModel guarantees by clearing mvpMapPoints first (:353).
+ * Arithmetic (OpenCV internals restated): Rcw * x + tcw is three float32 products summed in row order with tcw added in double and
+ * rounded once; frame to frame forms invzc = 1.0 / z in double and rounds it to float; isInFrustum forms invz = 1.0f / z in float,
+ * dist = cv::norm(P - Ow) as the double square root of the double sum of squares rounded to float, viewCos = float(double dot(PO, Pn)
+ * / dist); PredictScale takes ::log(double) of the float ratio mfMaxDistance / dist.  No FMA contraction anywhere.  isInFrustum has
+ * no distance-range test in DefSLAM (min / max distance are computed and never used) and none is applied here.  A projection that is
+ * NaN (a point exactly on the camera plane) is not in view and matches nothing.  The reference's NaN bounds tests pass, so its
+ * isInFrustum reports such a point in view (in_view / level / uv / view_cos differ there), and its window arithmetic on NaN is undefined
+ * behaviour; no other input is affected.
+ * Limits: N <= 8192 key points, grid_cols * grid_rows <= 8192, levels <= 32, octaves < 128, at most 4096 candidates in one query's
+ * window; beyond them DSH_ERR_ARG.  A host-only context returns DSH_ERR_NO_DEVICE (no CPU fallback). */
+typedef struct dsh_track_frame {
+  const float* Tcw;            /* 4x4 row-major float32 (CurrentFrame.mTcw) */
+  float Ow[3];                 /* camera centre (Frame::mOw, float32); read by the local-map search only */
+  float K[4];                  /* Frame::fx, fy, cx, cy */
+  float bounds[4];             /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+  int32_t grid_cols, grid_rows;/* FRAME_GRID_COLS, FRAME_GRID_ROWS (64, 48) */
+  int32_t levels;              /* mnScaleLevels */
+  const float* scale_factors;  /* mvScaleFactors[levels] */
+  float log_scale_factor;      /* mfLogScaleFactor */
+  int32_t N;                   /* key points */
+  const float* kp;             /* N x 2 mvKeysUn pixel positions */
+  const int32_t* octave;       /* N  mvKeysUn[j].octave */
+  const uint8_t* desc;         /* N x 32 mDescriptors rows */
+  const uint8_t* state;        /* N  0 / 1 / 2 as above */
+} dsh_track_frame;
+
+#define DSH_TRACK_FRAME 0      /* frame to frame (motion model) */
+#define DSH_TRACK_LOCAL 1      /* local map */
+/* One search of a batch.  Inputs: the frame, the mode, th and the Q queries in the reference's order.
+ *   frame to frame  the last frame's map points that are present and not outliers, in last-frame index order: xyz (world position,
+ *                   float32, e.g. dsh_sft_result.mappoint_xyz), octave (LastFrame.mvKeys[i].octave), desc (GetDescriptor)
+ *   local map       mvpLocalMapPoints in its order (DefTracking::UpdateLocalPoints copies a std::set<MapPoint*>): xyz, normal
+ *                   (GetNormal), max_distance (mfMaxDistance), desc, skip (may be NULL: points already matched in this frame or bad,
+ *                   Tracking.cc:1446-1451)
+ * Outputs: match[Q] = key point index or -1; local map also (each may be NULL) in_view (mbTrackInView), level (mnTrackScaleLevel),
+ * uv (Q x 2 mTrackProjX, mTrackProjY) and view_cos (mTrackViewCos), zero where not in view; nmatches (the function's return value)
+ * and rescans (queries whose matches phase B had to search again: a measurement, not a result). */
+typedef struct dsh_track_problem {
+  dsh_track_frame frame;
+  int32_t mode;                /* DSH_TRACK_FRAME or DSH_TRACK_LOCAL */
+  float th;                    /* frame to frame: 20, then 25 (DefTracking.cc:358,368); local map: 3 (5 after a relocalisation) */
+  int32_t Q;
+  const float* xyz;            /* Q x 3 */
+  const int32_t* octave;       /* Q, frame to frame */
+  const float* normal;         /* Q x 3, local map */
+  const float* max_distance;   /* Q, local map */
+  const uint8_t* desc;         /* Q x 32 */
+  const uint8_t* skip;         /* Q, local map, may be NULL */
+  int32_t* match;              /* out Q */
+  uint8_t* in_view;            /* out Q, local map */
+  int32_t* level;              /* out Q, local map */
+  float* uv;                   /* out Q x 2, local map */
+  float* view_cos;             /* out Q, local map */
+  int32_t nmatches;            /* out */
+  int32_t rescans;             /* out */
+} dsh_track_problem;
+/* B independent searches (different frames, sizes and modes) in one upload, three launches and one download; a search's result does
+ * not depend on the rest of the batch. */
+int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* problems);
+/* ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, true) (ORBmatcher.cc:1360-1510): the batch of one. */
+int dsh_search_by_projection_frame(dsh_ctx* ctx, const dsh_track_frame* frame, int Q, const float* xyz, const int32_t* octave,
+                                   const uint8_t* desc, float th, int32_t* match, int32_t* nmatches);
+/* Tracking::SearchLocalPoints after its bookkeeping (Tracking.cc:1440-1468): isInFrustum(pMP, 0.5) of every query that is not
+ * skipped, then ORBmatcher(0.8).SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cc:42-136).  The batch of one. */
+int dsh_search_by_projection_local(dsh_ctx* ctx, const dsh_track_frame* frame, int Q, const float* xyz, const float* normal,
+                                   const float* max_distance, const uint8_t* desc, const uint8_t* skip, float th, int32_t* match,
+                                   uint8_t* in_view, int32_t* level, int32_t* nmatches);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

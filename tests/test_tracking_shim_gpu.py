@@ -1,0 +1,104 @@
+"""The tracking-search shim (integration/tracking_search_hip.h) compiled against stand-in Frame / MapPoint types and run on the device:
+TrackWithMotionModel's SearchByProjectionHIP sequence and SearchLocalPointsHIP fill mvpMapPoints and the map points' tracking members
+exactly as the sequential restatement (tests/track_search_ref.py) of the reference's calls does."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import track_search_ref as R
+from conftest import ROOT
+
+INTEG = os.path.join(ROOT, "integration")
+
+
+def test_tracking_shim_compiles_against_the_c_abi():
+    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
+    assert os.path.exists(os.path.join(INTEG, "build", "tracking_shim_test"))
+    src = open(os.path.join(INTEG, "tracking_search_hip.h")).read()
+    assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
+
+
+def _first_unique(ids):
+    _, first = np.unique(ids, return_index=True)
+    return ids[np.sort(first)]
+
+
+@pytest.mark.gpu
+def test_tracking_shim_follows_the_reference_flow(tmp_path):
+    from defslam_amd import synth, track
+    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
+    exe = os.path.join(INTEG, "build", "tracking_shim_test")
+    rng = np.random.default_rng(5)
+    sc = synth.make_track_scene(41, n_kp=1200, n_frame_q=400, n_local_q=300, n_clusters=8)
+    tf, fq, lq = sc["frame"], sc["fq"], sc["lq"]
+    pts = sc["point_xyz"]
+    P = pts.shape[0]
+    desc = np.zeros((P, 32), np.uint8)
+    normal = np.tile(np.array([0, 0, 1], np.float32), (P, 1))
+    maxd = np.ones(P, np.float32)
+    octave_of = np.zeros(P, np.int32)
+    desc[sc["frame_points"]] = fq.desc
+    octave_of[sc["frame_points"]] = fq.octave
+    desc[sc["local_points"]] = lq.desc
+    normal[sc["local_points"]] = lq.normal
+    maxd[sc["local_points"]] = lq.max_distance
+    bad = rng.uniform(size=P) < 0.04
+    # the last frame: its map points (one key point each), a few outliers and key points without a map point
+    last_ids = _first_unique(sc["frame_points"])
+    entries = []
+    for i in last_ids:
+        if rng.uniform() < 0.05:
+            entries.append((-1, 0, int(rng.integers(0, 8))))
+        entries.append((int(i), int(rng.uniform() < 0.05), int(octave_of[i])))
+    local_ids = _first_unique(sc["local_points"])
+    N = tf.kp.shape[0]
+    with open(tmp_path / "in.txt", "w") as f:
+        f.write(f"{tf.scale_factors.shape[0]} {float(np.float32(tf.log_scale_factor))!r}\n" + " ".join(repr(float(s)) for s in tf.scale_factors) + "\n")
+        f.write(f"{P}\n")
+        for p in range(P):
+            f.write(" ".join(repr(float(v)) for v in (*pts[p], *normal[p], maxd[p])) + f" 1 {int(bad[p])} " + " ".join(str(int(b)) for b in desc[p]) + "\n")
+        cam = " ".join(repr(float(v)) for v in (*tf.K, *tf.bounds)) + "\n"
+        f.write(cam + " ".join(repr(float(v)) for v in np.asarray(tf.Tcw, np.float32).ravel()) + "\n" + " ".join(repr(float(v)) for v in tf.Ow) + "\n")
+        f.write(f"{N}\n")
+        for j in range(N):
+            f.write(f"{float(tf.kp[j, 0])!r} {float(tf.kp[j, 1])!r} {int(tf.octave[j])} " + " ".join(str(int(b)) for b in tf.desc[j]) + "\n")
+        f.write(cam + " ".join(repr(float(v)) for v in np.eye(4, dtype=np.float32).ravel()) + "\n0 0 0\n")
+        f.write(f"{len(entries)}\n" + "".join(f"{a} {b} {c}\n" for a, b, c in entries))
+        f.write(f"{len(local_ids)}\n" + " ".join(str(int(i)) for i in local_ids) + "\n")
+    r = subprocess.run(["timeout", "-k", "10", "120", exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "0"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    tok = iter(open(tmp_path / "out.txt").read().split())
+    n1, th = int(next(tok)), int(next(tok))
+    after_motion = np.array([int(next(tok)) for _ in range(N)])
+    n2 = int(next(tok))
+    loc = [(int(next(tok)), int(next(tok)), float(next(tok)), float(next(tok)), float(next(tok)), int(next(tok)), int(next(tok))) for _ in local_ids]
+    final = np.array([int(next(tok)) for _ in range(N)])
+
+    # the restatement: TrackWithMotionModel on the queries ORBmatcher.cc:1384-1390 takes
+    q_ids = np.array([a for a, b, _ in entries if a >= 0 and not b], np.int64)
+    q_oct = np.array([c for a, b, c in entries if a >= 0 and not b], np.int32)
+    m, n, th_ref, _ = R.motion_model(tf, pts[q_ids], q_oct, desc[q_ids])
+    assert (n1, th) == (n, th_ref) and n > 100
+    exp_motion = np.full(N, -1)
+    exp_motion[m[m >= 0]] = q_ids[m >= 0]
+    np.testing.assert_array_equal(after_motion, exp_motion)
+    # Tracking::SearchLocalPoints: bad points leave the frame, the others are "seen"; the local search on that state
+    frame_mp = np.where((exp_motion >= 0) & ~bad[np.maximum(exp_motion, 0)], exp_motion, -1)
+    seen = np.zeros(P, bool)
+    seen[frame_mp[frame_mp >= 0]] = True
+    skip = (seen[local_ids] | bad[local_ids]).astype(np.uint8)
+    state = (frame_mp >= 0).astype(np.uint8)
+    ml, nl, _, iv, lev, uv, vc = R.search_local(R.ref_frame(track.TrackFrame(**{**tf.__dict__, "state": state})), state, pts[local_ids],
+                                                normal[local_ids], maxd[local_ids], desc[local_ids], skip, 3)
+    assert n2 == nl and nl > 0
+    for q, (inv, lv, u, v, c, vis, seen_id) in enumerate(loc):
+        assert inv == int(iv[q])
+        if iv[q]:
+            assert (lv, np.float32(u), np.float32(v), np.float32(c)) == (lev[q], uv[q, 0], uv[q, 1], vc[q])
+        assert vis == int(seen[local_ids[q]]) + int(iv[q])                  # IncreaseVisible: Tracking.cc:1422 and :1456
+        assert seen_id == (2 if seen[local_ids[q]] else 0)
+    exp_final = frame_mp.copy()
+    exp_final[ml[ml >= 0]] = local_ids[ml >= 0]
+    np.testing.assert_array_equal(final, exp_final)
