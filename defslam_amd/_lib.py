@@ -122,7 +122,8 @@ DSH_COMM_ID_BYTES = 128
 
 # include/defslam_hip_debug.h: only libdefslam_hip_lab.so exports these
 LAB_SYMBOLS = ["dsh_lab_set_option", "dsh_lab_sft_run_timed", "dsh_lab_sft_assemble_timed", "dsh_lab_sft_phase_ms", "dsh_lab_sft_step_trace",
-               "dsh_lab_sft_system", "dsh_lab_sft_solver_info", "dsh_lab_sft_wave_check", "dsh_lab_sft_dump", "dsh_lab_sft_rounds_timed"]
+               "dsh_lab_sft_system", "dsh_lab_sft_solver_info", "dsh_lab_sft_wave_check", "dsh_lab_sft_dump", "dsh_lab_sft_rounds_timed",
+               "dsh_lab_sft_factor_check"]
 
 _lib = None
 _lab = None
@@ -227,6 +228,7 @@ def _bind(path: str, lab: bool) -> C.CDLL:
         L.dsh_lab_sft_wave_check.argtypes = [vp, C.c_double, C.c_int, C.c_int, c_double_p, c_double_p, c_i32_p, c_double_p]
         L.dsh_lab_sft_dump.argtypes = [vp, C.c_int, C.c_int, C.c_int64, c_double_p]
         L.dsh_lab_sft_rounds_timed.argtypes = [vp, c_double_p, c_i32_p]
+        L.dsh_lab_sft_factor_check.argtypes = [vp, c_double_p, c_u8_p, C.c_int, c_double_p, c_i32_p]
         for name in LAB_SYMBOLS:
             getattr(L, name).restype = C.c_int
     return L
@@ -264,3 +266,16 @@ class HipEvents:
             if e:
                 self._hip.hipEventDestroy(e)
         self.e0 = self.e1 = None
+
+
+HIP_DEVICE_ATTRIBUTE_MULTIPROCESSOR_COUNT = 63   # hipDeviceAttributeMultiprocessorCount (hip_runtime_api.h)
+
+
+def device_cus(device: int = 0) -> int:
+    """Compute units of a HIP device (libamdhip64 through ctypes): what the library sizes its launches by (dsh_create)."""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipDeviceGetAttribute.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int]
+    n = C.c_int(0)
+    if hip.hipDeviceGetAttribute(C.byref(n), HIP_DEVICE_ATTRIBUTE_MULTIPROCESSOR_COUNT, int(device)) != 0 or n.value <= 0:
+        raise OSError("hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount) failed")
+    return int(n.value)

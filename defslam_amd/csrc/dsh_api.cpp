@@ -45,6 +45,7 @@ extern "C" hipError_t sft_vec_sum2(const double* a, const double* b, double* out
 #ifdef DSH_LAB
 extern "C" hipError_t sft_wave_lab_launch(const SftDev* d_probs, int B, int which, double rel, int max_kd, size_t jl_doubles, hipStream_t stream);
 extern "C" hipError_t sft_assembly_launch(const SftDev* d_probs, int B, int max_kd, size_t jl_doubles, int nw, hipStream_t stream);
+extern "C" hipError_t sftb_factor_lab_launch(const SftDev* d_probs, SftRun* d_runs, int* d_counters, int B, int grid, hipStream_t stream);
 #endif
 
 namespace {
@@ -887,9 +888,11 @@ int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) {
   HIPCHK(c, hipEventRecord(c->stage_free, c->stream));
   c->stage_busy = true;
   // The kernel initialises everything it reads (state, H with its zero padding, border, x, counters).  A fresh allocation
-  // is cleared once so that no tile of L / Lt that a masked lane may touch holds a NaN pattern; after that the workspace
-  // only ever holds finite numbers this library wrote.  The result region is always cleared (a caller that downloads
-  // without running gets zeros, not the previous batch).
+  // is cleared once; after that the workspace holds whatever the previous batch left -- including the NaN tiles of L of a
+  // failed factorisation (every pivot behind a non-positive one is NaN, and the factorisation goes on storing).  So no
+  // result may depend on what a tile held before this batch wrote it: tests/test_factor_waves_gpu.py runs a healthy batch on
+  // the workspace of a failing one and compares it with a fresh context bit for bit.  The result region is always cleared
+  // (a caller that downloads without running gets zeros, not the previous batch).
   if (fresh_arena) HIPCHK(c, hipMemsetAsync(base + ws_off, 0, a.size - ws_off, c->stream));
   HIPCHK(c, hipMemsetAsync(base + c->res_off, 0, c->res_bytes, c->stream));
   c->d_probs = (SftDev*)(base + o_tab);
@@ -1449,6 +1452,44 @@ int dsh_lab_sft_wave_check(dsh_ctx* c, double rel, int launches, int only, doubl
     }
   }
   return DSH_OK;   // (H stays assembled at the initial state: the check can be repeated; the results of the last full run are stale)
+}
+
+int dsh_lab_sft_factor_check(dsh_ctx* c, const double* lambda, const uint8_t* factor, int grid, double* x, int32_t* ok) {
+  if (!c || !lambda || grid < 0) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_factor_check: bad argument");
+  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_factor_check: host-only context, no GPU (there is no CPU fallback)");
+  if (c->B <= 0 || !c->ran) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_factor_check: needs an uploaded batch that has run once");
+  for (int b = 0; b < c->B; b++)
+    if (c->h_probs[b].tile_mode != 1) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_factor_check: register-window problems (half-bandwidth <= 128) only");
+  (void)hipSetDevice(c->device);
+  const int B = c->B;
+  // run records and counters of its own: the batch need not be in the throughput shape (the records of the rounds exist only there)
+  struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } } runs, counters;
+  HIPCHK(c, hipMalloc(&runs.p, sizeof(SftRun) * (size_t)B));
+  HIPCHK(c, hipMalloc(&counters.p, 16 * sizeof(int)));
+  std::vector<SftRun> h_runs(B);
+  for (int b = 0; b < B; b++) {
+    SftRun& R = h_runs[b];
+    std::memset(&R, 0, sizeof(R));
+    R.lambda = lambda[b];
+    R.state = (!factor || factor[b]) ? SFTB_TRIAL : SFTB_DONE;
+    R.fact_ok = -1;   // stays -1 where the problem was left out
+  }
+  HIPCHK(c, sft_assembly_launch(c->d_probs, B, c->max_kd, c->jl_doubles, c->rounds_mode ? 8 : c->nw, c->stream));   // H of the initial state
+  for (int b = 0; b < B; b++) HIPCHK(c, hipMemcpyAsync(c->h_probs[b].dbg + 1, &lambda[b], sizeof(double), hipMemcpyHostToDevice, c->stream));   // for wave_check(only = 2)
+  HIPCHK(c, hipMemcpyAsync(runs.p, h_runs.data(), sizeof(SftRun) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(counters.p, 0, 16 * sizeof(int), c->stream));
+  HIPCHK(c, sftb_factor_lab_launch(c->d_probs, (SftRun*)runs.p, (int*)counters.p, B, grid ? grid : std::min(B, 4 * c->num_cus), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h_runs.data(), runs.p, sizeof(SftRun) * (size_t)B, hipMemcpyDeviceToHost));
+  size_t off = 0;
+  for (int b = 0; b < B; b++) {
+    const SftDev& h = c->h_probs[b];
+    const size_t Dnp = (size_t)((h.Dn + kNB - 1) / kNB) * kNB;
+    if (x) HIPCHK(c, hipMemcpy(x + off, h.x, 8 * (Dnp + 6), hipMemcpyDeviceToHost));
+    off += Dnp + 6;
+    if (ok) ok[b] = h_runs[b].fact_ok;
+  }
+  return DSH_OK;   // (H stays assembled at the initial state, as after dsh_lab_sft_wave_check; the results of the last full run are stale)
 }
 
 int dsh_lab_sft_rounds_timed(dsh_ctx* c, double* ms4, int32_t* rounds) {

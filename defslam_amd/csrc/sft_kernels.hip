@@ -3472,3 +3472,12 @@ extern "C" hipError_t sftb_launch(const SftDev* d_probs, SftRun* d_runs, int* d_
   }
   return hipGetLastError();
 }
+
+#ifdef DSH_LAB
+// The FACTOR kernel of the rounds alone (dsh_lab_sft_factor_check): `grid` persistent wavefronts pull the problems whose run record says
+// SFTB_TRIAL from counters[1] (the caller zeroes the counters); grid = 1: one wave solves them all in index order.
+extern "C" hipError_t sftb_factor_lab_launch(const SftDev* d_probs, SftRun* d_runs, int* d_counters, int B, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(sftb_factor_kernel, dim3(grid), dim3(64), WV_LDS_DOUBLES * sizeof(double), stream, d_probs, d_runs, d_counters, B);
+  return hipGetLastError();
+}
+#endif

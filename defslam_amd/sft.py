@@ -242,6 +242,30 @@ class Context:
         offs = np.concatenate([[0], np.cumsum(dims)])
         return [xr[offs[b]:offs[b + 1]] for b in range(B)], [xn[offs[b]:offs[b + 1]] for b in range(B)], ok, ms
 
+    def factor_check(self, lam, factor=None, grid: int = 0):
+        """The FACTOR kernel of the throughput shape alone on the normal equations of every uploaded problem at its initial state
+        (dsh_lab_sft_factor_check): problem b factored with damping lam[b] (left out where factor[b] is false) by `grid` persistent
+        wavefronts (0: the launch shape of the rounds, 1: one wavefront in index order).  Returns (x, ok): x a list of per-problem
+        solutions (Dnp + 6, as wave_check), ok[b] the "all pivots positive" flag (-1: left out)."""
+        self._need_lab("dsh_lab_sft_factor_check")
+        B = len(self._frames)
+        lam = np.ascontiguousarray(lam, np.float64)
+        if lam.shape != (B,):
+            raise ValueError(f"factor_check: lam must have one damping per problem ({B})")
+        fac = None if factor is None else np.ascontiguousarray(np.asarray(factor, bool).astype(np.uint8))
+        if fac is not None and fac.shape != (B,):
+            raise ValueError(f"factor_check: factor must have one flag per problem ({B})")
+        dims = []
+        for b in range(B):
+            Dn = int(self.problem_info(b)[1][5]) - 6
+            dims.append(((Dn + 31) // 32) * 32 + 6)
+        x = np.zeros(int(sum(dims)))
+        ok = np.zeros(B, np.int32)
+        self._check(self._L.dsh_lab_sft_factor_check(self._h, _ptr(lam, C.c_double), _ptr(fac, C.c_uint8), int(grid), _ptr(x, C.c_double),
+                                                     _ptr(ok, C.c_int32)), "dsh_lab_sft_factor_check")
+        offs = np.concatenate([[0], np.cumsum(dims)])
+        return [x[offs[b]:offs[b + 1]] for b in range(B)], ok
+
     def rounds_timed(self):
         """One run of the uploaded batch as rounds of phase kernels with events around every launch (lab): (dict of total ms per phase, rounds)."""
         self._need_lab("dsh_lab_sft_rounds_timed")

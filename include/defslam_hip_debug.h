@@ -64,6 +64,14 @@ int dsh_lab_sft_assemble_timed(dsh_ctx* ctx, int launches, double* total_ms);
  * camera), ok2[2 b + which] the "all pivots positive" flags, ms2[which] the device time of one launch (average over `launches`);
  * only = 0: both, 1: the four-wavefront solver alone, 2: the one-wavefront solver alone (with the lambda the last reference run left). */
 int dsh_lab_sft_wave_check(dsh_ctx* ctx, double rel, int launches, int only, double* x_ref, double* x_new, int32_t* ok2, double* ms2);
+/* The FACTOR kernel of the throughput shape (sftb_factor_kernel: persistent wavefronts, the back substitution of a wave's previous problem
+ * deferred into the factor steps of its next one) alone, on the normal equations of every problem at its uploaded state (assembled as for
+ * dsh_lab_sft_wave_check): problem b is factored with damping lambda[b] -- or left out where factor (may be NULL) has factor[b] == 0 --
+ * by `grid` wavefronts (0: the launch shape of the rounds, min(B, 4 x CUs); 1: one wavefront solves every problem in index order).
+ * x (may be NULL) receives the solutions as dsh_lab_sft_wave_check lays them out, ok (may be NULL) the "all pivots positive" flags
+ * (-1: left out).  lambda[b] is also left in the problem's debug slot, so that dsh_lab_sft_wave_check(only = 2) afterwards solves the same
+ * systems with one kernel per problem.  Needs a batch of register-window problems that has run once; the results of that run are stale. */
+int dsh_lab_sft_factor_check(dsh_ctx* ctx, const double* lambda, const uint8_t* factor, int grid, double* x, int32_t* ok);
 /* One run of the uploaded batch in the throughput shape (rounds of phase kernels, sft_batch.h) with a HIP event in front of and behind
  * every launch: ms7[0..4] = total device milliseconds of the INIT, LIN, FACTOR, TRIAL and tail-kernel launches, ms7[5] = factorisations the FACTOR
  * launches performed, ms7[6] = linearisations the LIN launches performed (the last problems' are the tail kernel's); *rounds (may be NULL) = rounds of phase kernels launched.

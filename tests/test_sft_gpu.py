@@ -143,12 +143,26 @@ def test_benched_shape_matches_oracle_under_load(gpu_ctx, oracle_mod):
         assert frames[p].trials == r.trials
 
 
-@pytest.mark.parametrize("B,waves", [(65, 8), (86, 8), (129, 1), (300, 1)])
-def test_launch_shapes_between_latency_mode_and_rounds(gpu_ctx, oracle_mod, B, waves):
-    """The hand-over points of r06 in the PRODUCT library (DESIGN 4.0, 256 CUs): 65 problems = three speculative lanes per problem (the device
-    holds 3 x 65 workgroups, not 4 x), 86 = two lanes, 129 and 300 = the throughput shape with the tail kernel alone (until r05: one workgroup
-    per problem of the persistent kernel).  A ragged batch on the 9 x 14 mesh, sampled ids against the oracle, two runs bit-identical."""
-    from defslam_amd import sft, synth
+# batch sizes at the hand-over points, from the device's CU count (on 256 CUs: 65, 86, 129 and 300 problems -- the test ids)
+LAUNCH_SHAPES = {
+    "three_lanes": (lambda cus: cus // 4 + 1, 8),
+    "two_lanes": (lambda cus: cus // 3 + 1, 8),
+    "rounds_just_above_half": (lambda cus: cus // 2 + 1, 1),
+    "rounds_tail_alone": (lambda cus: (cus * 75 + 63) // 64, 1),
+}
+
+
+@pytest.mark.parametrize("shape", list(LAUNCH_SHAPES), ids=["65-8", "86-8", "129-1", "300-1"])
+def test_launch_shapes_between_latency_mode_and_rounds(gpu_ctx, oracle_mod, shape):
+    """The hand-over points of r06 in the PRODUCT library, from the device's CU count: CUs / 4 + 1 problems = three speculative
+    lanes per problem (the device holds 3 x B workgroups, not 4 x), CUs / 3 + 1 = two lanes, CUs / 2 + 1 and about 1.17 x CUs = the throughput
+    shape with the tail kernel alone (until r05: one workgroup per problem of the persistent kernel).  A ragged batch on the 9 x 14 mesh,
+    sampled ids against the oracle, two runs bit-identical."""
+    from defslam_amd import _lib, sft, synth
+    cus = _lib.device_cus(0)
+    B, waves = LAUNCH_SHAPES[shape][0](cus), LAUNCH_SHAPES[shape][1]
+    lanes = 4 if 4 * B <= cus else (3 if 3 * B <= cus else (2 if 2 * B <= cus else 1))
+    assert lanes == {"three_lanes": 3, "two_lanes": 2}.get(shape, 1)
     tmpl = synth.make_grid_template(9, 14)
     gpu_ctx.template_build(tmpl.xyz0, tmpl.facets)
     regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
@@ -332,7 +346,9 @@ def test_rounds_of_phase_kernels_with_failing_factorisations(rounds_ctx, oracle_
     """Problems whose normal equations are not positive definite (observations with NEGATIVE information: H = sum w J^T J is indefinite) among
     healthy ones in one batch of the throughput shape: the one-wavefront Cholesky reports the non-positive pivot, the trial counts as failed
     (g2o: `_solver->solve` returns false, the step is rejected, optimization_algorithm_levenberg.cpp:103-113), the state is restored, status
-    bit 0 is set -- and the neighbours of such a problem in the batch (same factor wave before and after it) are solved as if it were not there."""
+    bit 0 is set -- and the neighbours of such a problem in the batch index are solved as if it were not there.  (With 512 problems every FACTOR
+    wave of a 256-CU device gets one problem per launch, and which wave pulls which problem is decided at run time: the sequences inside one
+    wave -- a failed problem behind and in front of healthy ones -- are test_factor_waves_gpu.py's.)"""
     from defslam_amd import sft, synth
     B = 512
     tmpl = synth.make_grid_template(10, 10)
