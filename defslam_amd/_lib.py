@@ -100,6 +100,18 @@ DSH_TRACK_FRAME = 0
 DSH_TRACK_LOCAL = 1
 
 
+class MpKeyFrameC(C.Structure):
+    _fields_ = [("Ow", C.c_float * 3), ("N", C.c_int32), ("desc", c_u8_p), ("octave", c_i32_p), ("levels", C.c_int32),
+                ("scale_factors", c_float_p), ("bad", C.c_int32)]
+
+
+DSH_MP_DESCRIPTOR = 1
+DSH_MP_NORMAL_DEPTH = 2
+DSH_MP_NO_OBS = 1
+DSH_MP_NO_GOOD_DESC = 2
+DSH_MP_MAX_OBS = 65535
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -117,6 +129,7 @@ EXPORTED_SYMBOLS = [
     "dsh_diffdb_create", "dsh_diffdb_destroy", "dsh_diffdb_clear", "dsh_diffdb_count", "dsh_diffdb_append", "dsh_schwarp_fit_batch_store",
     "dsh_normals_estimate_db", "dsh_sfn_estimate_db",
     "dsh_search_by_projection_batch", "dsh_search_by_projection_frame", "dsh_search_by_projection_local",
+    "dsh_kfdb_create", "dsh_kfdb_destroy", "dsh_kfdb_clear", "dsh_kfdb_add", "dsh_kfdb_set_bad", "dsh_kfdb_count", "dsh_mappoint_update",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -213,6 +226,14 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_search_by_projection_frame.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_float_p, c_i32_p, c_u8_p, C.c_float, c_i32_p, c_i32_p]
     L.dsh_search_by_projection_local.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p, C.c_float,
                                                  c_i32_p, c_u8_p, c_i32_p, c_i32_p]
+    L.dsh_kfdb_create.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    L.dsh_kfdb_destroy.argtypes = [vp]
+    L.dsh_kfdb_clear.argtypes = [vp]
+    L.dsh_kfdb_add.argtypes = [vp, C.POINTER(MpKeyFrameC), c_i32_p]
+    L.dsh_kfdb_set_bad.argtypes = [vp, C.c_int32, C.c_int32]
+    L.dsh_kfdb_count.argtypes = [vp]
+    L.dsh_mappoint_update.argtypes = [vp, vp, C.c_int, c_float_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, C.c_int32, c_u8_p, c_i32_p, c_float_p,
+                                      c_float_p, c_float_p, c_i32_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

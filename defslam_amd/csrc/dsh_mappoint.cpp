@@ -1,0 +1,342 @@
+// Host side of the map point upkeep (include/defslam_hip.h: dsh_kfdb_*, dsh_mappoint_update): the keyframe store in HBM, validation,
+// one packed upload, the launches of mappoint_kernels.hip, one download.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/defslam_hip.h"
+#include "dsh_ctx.h"
+#include "mappoint_problem.h"
+
+// The store: descriptor rows and camera centres on the device; what validation and the election lists need on the host.
+struct dsh_kfdb {
+  dsh_ctx_base* ctx = nullptr;   // the owning context; null after dsh_destroy of that context (the store can then only be destroyed)
+  int device = 0;
+  int32_t cap = 0, count = 0;    // keyframes
+  long long row_cap = 0, rows = 0;
+  MpuSlot* d_slots = nullptr;
+  uint4* d_rows = nullptr;       // two uint4 per descriptor row
+  struct Kf {
+    long long row_off;
+    int32_t N, levels, bad;
+    float sf[MPU_MAX_LEVELS];
+    std::vector<int8_t> octave;
+  };
+  std::vector<Kf> kf;
+};
+
+namespace {
+
+#define MPU_HIPCHK(c, call)                                                                                   \
+  do {                                                                                                        \
+    hipError_t e__ = (call);                                                                                  \
+    if (e__ != hipSuccess) {                                                                                  \
+      (void)hipStreamSynchronize((c)->stream);                                                                \
+      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                     \
+    }                                                                                                         \
+  } while (0)
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// grow-on-demand device arrays: a new allocation of at least twice the capacity, the stored part copied device to device
+hipError_t grow(void** p, size_t used, size_t need_bytes) {
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, need_bytes);
+  if (e != hipSuccess) return e;
+  (void)hipDeviceSynchronize();   // nothing of this device may still read the old array
+  if (used) e = hipMemcpy(q, *p, used, hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) { (void)hipFree(q); return e; }
+  if (*p) (void)hipFree(*p);
+  *p = q;
+  return hipSuccess;
+}
+
+int width_class(int M) { return M <= 8 ? 0 : M <= 16 ? 1 : M <= 32 ? 2 : 3; }
+
+}  // namespace
+
+void kfdb_detach_all(dsh_ctx_base* c) {
+  for (dsh_kfdb* db : c->kfdbs) db->ctx = nullptr;
+  c->kfdbs.clear();
+}
+
+extern "C" {
+
+int dsh_kfdb_create(dsh_ctx* ctx, int32_t capacity, dsh_kfdb** out) {
+  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  if (!c) return DSH_ERR_ARG;
+  if (!out || capacity <= 0 || capacity > (1 << 24)) return dsh_fail(c, DSH_ERR_ARG, "dsh_kfdb_create: bad argument");
+  *out = nullptr;
+  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_kfdb_create: host-only context, no GPU (there is no CPU fallback)");
+  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_create: hipSetDevice failed");
+  dsh_kfdb* db = new dsh_kfdb();
+  db->ctx = c;
+  db->device = c->device;
+  db->row_cap = (long long)capacity * 1024;
+  if (hipMalloc((void**)&db->d_slots, sizeof(MpuSlot) * (size_t)capacity) != hipSuccess ||
+      hipMalloc((void**)&db->d_rows, 32 * (size_t)db->row_cap) != hipSuccess) {
+    if (db->d_slots) (void)hipFree(db->d_slots);
+    delete db;
+    return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_create: out of device memory");
+  }
+  db->cap = capacity;
+  c->kfdbs.push_back(db);
+  *out = db;
+  return DSH_OK;
+}
+
+int dsh_kfdb_destroy(dsh_kfdb* db) {
+  if (!db) return DSH_ERR_ARG;
+  (void)hipSetDevice(db->device);
+  (void)hipDeviceSynchronize();
+  if (db->ctx) {
+    auto& v = db->ctx->kfdbs;
+    v.erase(std::remove(v.begin(), v.end(), db), v.end());
+  }
+  if (db->d_slots) (void)hipFree(db->d_slots);
+  if (db->d_rows) (void)hipFree(db->d_rows);
+  delete db;
+  return DSH_OK;
+}
+
+int dsh_kfdb_clear(dsh_kfdb* db) {
+  if (!db || !db->ctx) return DSH_ERR_ARG;
+  db->count = 0;
+  db->rows = 0;
+  db->kf.clear();
+  return DSH_OK;
+}
+
+int32_t dsh_kfdb_count(const dsh_kfdb* db) { return db ? db->count : -1; }
+
+int dsh_kfdb_set_bad(dsh_kfdb* db, int32_t slot, int32_t bad) {
+  if (!db || !db->ctx) return DSH_ERR_ARG;
+  if (slot < 0 || slot >= db->count) return dsh_fail(db->ctx, DSH_ERR_ARG, "dsh_kfdb_set_bad: slot outside the store");
+  db->kf[slot].bad = bad ? 1 : 0;   // read by the host when it lists a call's election rows
+  return DSH_OK;
+}
+
+int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
+  if (!db || !db->ctx) return DSH_ERR_ARG;
+  dsh_ctx_base* c = db->ctx;
+  auto bad = [&](const char* m) { return dsh_fail(c, DSH_ERR_ARG, std::string("dsh_kfdb_add: ") + m); };
+  if (!kf) return bad("keyframe is NULL");
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(kf->Ow[k])) return bad("camera centre not finite");
+  if (kf->N < 0 || kf->N > (1 << 20)) return bad("N outside 0 .. 2^20");
+  if (kf->N > 0 && (!kf->desc || !kf->octave)) return bad("key point arrays are NULL");
+  if (kf->levels <= 0 || kf->levels > MPU_MAX_LEVELS || !kf->scale_factors) return bad("levels outside 1 .. 32 or no scale factors");
+  for (int j = 0; j < kf->N; j++)
+    if (kf->octave[j] < 0 || kf->octave[j] > 127) return bad("key point octave outside 0 .. 127");
+  if (db->count == INT32_MAX || db->rows + kf->N > INT32_MAX) return bad("store full");
+  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: hipSetDevice failed");
+  if (db->count + 1 > db->cap) {
+    const int32_t ncap = (int32_t)std::min<long long>(2ll * db->cap, INT32_MAX);
+    if (grow((void**)&db->d_slots, sizeof(MpuSlot) * (size_t)db->count, sizeof(MpuSlot) * (size_t)ncap) != hipSuccess)
+      return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
+    db->cap = ncap;
+  }
+  if (db->rows + kf->N > db->row_cap) {
+    const long long ncap = std::max(db->rows + kf->N, 2 * db->row_cap);
+    if (grow((void**)&db->d_rows, 32 * (size_t)db->rows, 32 * (size_t)ncap) != hipSuccess)
+      return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
+    db->row_cap = ncap;
+  }
+  MpuSlot s;
+  s.Ow[0] = kf->Ow[0]; s.Ow[1] = kf->Ow[1]; s.Ow[2] = kf->Ow[2];
+  s.row_off = (int32_t)db->rows;
+  hipStream_t st = c->stream;
+  MPU_HIPCHK(c, hipMemcpyAsync(db->d_slots + db->count, &s, sizeof(s), hipMemcpyHostToDevice, st));
+  if (kf->N > 0) MPU_HIPCHK(c, hipMemcpyAsync(db->d_rows + 2 * db->rows, kf->desc, 32 * (size_t)kf->N, hipMemcpyHostToDevice, st));
+  MPU_HIPCHK(c, hipStreamSynchronize(st));
+  dsh_kfdb::Kf h;
+  h.row_off = db->rows;
+  h.N = kf->N;
+  h.levels = kf->levels;
+  h.bad = kf->bad ? 1 : 0;
+  std::memset(h.sf, 0, sizeof(h.sf));
+  for (int l = 0; l < kf->levels; l++) h.sf[l] = kf->scale_factors[l];
+  h.octave.assign(kf->octave, kf->octave + kf->N);
+  db->kf.push_back(std::move(h));
+  if (slot) *slot = db->count;
+  db->count++;
+  db->rows += kf->N;
+  return DSH_OK;
+}
+
+int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, const int32_t* obs_ptr, const int32_t* obs_kf,
+                        const int32_t* obs_idx, const int32_t* ref_kf, int32_t what, uint8_t* desc, int32_t* best, float* normal,
+                        float* max_distance, float* min_distance, int32_t* status) {
+  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  if (!c) return DSH_ERR_ARG;
+  auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, "dsh_mappoint_update: " + m); };
+  // arguments that need no store
+  if (P < 0) return bad("P < 0");
+  if (what < 1 || what > (DSH_MP_DESCRIPTOR | DSH_MP_NORMAL_DEPTH)) return bad("what is not a non-empty mask of DSH_MP_DESCRIPTOR, DSH_MP_NORMAL_DEPTH");
+  const bool want_d = (what & DSH_MP_DESCRIPTOR) != 0, want_g = (what & DSH_MP_NORMAL_DEPTH) != 0;
+  if (P > 0 && (!xyz || !obs_ptr)) return bad("xyz or obs_ptr is NULL");
+  if (P > 0 && want_d && !desc) return bad("DSH_MP_DESCRIPTOR needs desc");
+  if (P > 0 && want_g && (!ref_kf || !normal || !max_distance || !min_distance)) return bad("DSH_MP_NORMAL_DEPTH needs ref_kf, normal, max_distance, min_distance");
+  if (P > 0 && obs_ptr[0] != 0) return bad("obs_ptr[0] != 0");
+  for (int p = 0; p < P; p++) {
+    const long long m = (long long)obs_ptr[p + 1] - obs_ptr[p];
+    if (m < 0) return bad("obs_ptr decreases at point " + std::to_string(p));
+    if (m > DSH_MP_MAX_OBS) return bad("point " + std::to_string(p) + " has more than 65535 observations");
+  }
+  const long long Mt = P > 0 ? obs_ptr[P] : 0;
+  if (Mt > 0 && (!obs_kf || !obs_idx)) return bad("obs_kf or obs_idx is NULL");
+  if (db && db->ctx != c) return bad("the store belongs to another context or was detached");
+  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_mappoint_update: host-only context, no GPU (there is no CPU fallback)");
+  if (!db) return bad("store is NULL");
+
+  // arguments against the store; the election lists and the reference levels on the way
+  std::vector<int32_t> stamp(db->count, 0), el_obs;   // el_obs: observation index of each election row
+  std::vector<MpuPoint> pts(P);
+  std::vector<int32_t> el_row;
+  std::vector<uint8_t> no_good(P, 0);
+  el_row.reserve(want_d ? Mt : 0);
+  el_obs.reserve(want_d ? Mt : 0);
+  for (int p = 0; p < P; p++) {
+    MpuPoint& q = pts[p];
+    std::memset(&q, 0, sizeof(q));
+    q.x = xyz[3 * p]; q.y = xyz[3 * p + 1]; q.z = xyz[3 * p + 2];
+    q.obs_off = obs_ptr[p];
+    q.M = obs_ptr[p + 1] - obs_ptr[p];
+    q.el_off = (int32_t)el_row.size();
+    q.ref_slot = -1;
+    q.what = what;
+    const std::string at = "point " + std::to_string(p) + ": ";
+    const int32_t ref = want_g && q.M > 0 ? ref_kf[p] : -1;
+    if (want_g && q.M > 0 && (ref < 0 || ref >= db->count)) return bad(at + "reference keyframe slot outside the store");
+    int32_t ref_idx = 0;   // observations[pRefKF] of a copy that lacks pRefKF inserts and yields 0
+    int ngood = 0;
+    for (int m = 0; m < q.M; m++) {
+      const int32_t s = obs_kf[q.obs_off + m], j = obs_idx[q.obs_off + m];
+      if (s < 0 || s >= db->count) return bad(at + "keyframe slot outside the store");
+      if (stamp[s] == p + 1) return bad(at + "keyframe slot " + std::to_string(s) + " repeated");
+      stamp[s] = p + 1;
+      const dsh_kfdb::Kf& k = db->kf[s];
+      if (j < 0 || j >= k.N) return bad(at + "obs_idx outside the keyframe's key points");
+      if (s == ref) ref_idx = j;
+      ngood += !k.bad;
+      if (want_d && !k.bad) {
+        el_row.push_back((int32_t)(k.row_off + j));
+        el_obs.push_back(m);
+      }
+    }
+    q.Me = (int32_t)el_row.size() - q.el_off;
+    if (q.M > 0 && ngood == 0) no_good[p] = 1;
+    if (want_g && q.M > 0) {
+      const dsh_kfdb::Kf& k = db->kf[ref];
+      if (ref_idx >= k.N) return bad(at + "the reference keyframe has no key point 0");
+      const int level = k.octave[ref_idx];
+      if (level >= k.levels) return bad(at + "reference octave >= levels");
+      q.ref_slot = ref;
+      q.sf_level = k.sf[level];
+      q.sf_last = k.sf[k.levels - 1];
+    }
+  }
+  if (P == 0) return DSH_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_mappoint_update: hipSetDevice failed");
+
+  // work lists: small points by width class; large points biggest first, each a normal block and its election row blocks
+  std::vector<int32_t> small_order, large_pts;
+  std::vector<int32_t> cls_n(4, 0);
+  for (int p = 0; p < P; p++) {
+    const int M = pts[p].M;
+    if (M == 0) continue;
+    if (M <= MPU_SMALL) cls_n[width_class(M)]++;
+    else large_pts.push_back(p);
+  }
+  int32_t small_off[5] = {0, 0, 0, 0, 0};
+  for (int k = 0; k < 4; k++) small_off[k + 1] = small_off[k] + cls_n[k];
+  small_order.resize(small_off[4]);
+  {
+    int32_t cur[4] = {small_off[0], small_off[1], small_off[2], small_off[3]};
+    for (int p = 0; p < P; p++)
+      if (pts[p].M > 0 && pts[p].M <= MPU_SMALL) small_order[cur[width_class(pts[p].M)]++] = p;
+  }
+  std::stable_sort(large_pts.begin(), large_pts.end(), [&](int a, int b) { return pts[a].M > pts[b].M; });
+  std::vector<int32_t> blocks;   // pairs (point, first row or -1)
+  for (int p : large_pts) {
+    if (want_g) { blocks.push_back(p); blocks.push_back(-1); }
+    if (want_d)
+      for (int r = 0; r < pts[p].Me; r += MPU_ROWS) { blocks.push_back(p); blocks.push_back(r); }
+  }
+  const int NB = (int)blocks.size() / 2, NL = (int)large_pts.size();
+  const size_t Met = el_row.size();
+
+  // one host buffer, one copy up
+  const size_t o_pts = 0, o_oslot = align256(sizeof(MpuPoint) * P), o_el = o_oslot + align256(4 * (size_t)Mt),
+               o_small = o_el + align256(4 * Met), o_blk = o_small + align256(4 * small_order.size()),
+               o_lpts = o_blk + align256(4 * blocks.size()), up_bytes = o_lpts + align256(4 * (size_t)NL);
+  const size_t d_best = 0, d_desc = align256(4 * (size_t)P), d_nrm = d_desc + align256(32 * (size_t)P), d_dist = d_nrm + align256(12 * (size_t)P),
+               down_bytes = d_dist + align256(8 * (size_t)P);
+  MPU_HIPCHK(c, c->pin_in.ensure(up_bytes));
+  MPU_HIPCHK(c, c->pin_out.ensure(down_bytes));
+  char* h = c->pin_in.p;
+  std::memcpy(h + o_pts, pts.data(), sizeof(MpuPoint) * P);
+  if (Mt > 0) std::memcpy(h + o_oslot, obs_kf, 4 * (size_t)Mt);
+  if (Met > 0) std::memcpy(h + o_el, el_row.data(), 4 * Met);
+  if (!small_order.empty()) std::memcpy(h + o_small, small_order.data(), 4 * small_order.size());
+  if (!blocks.empty()) std::memcpy(h + o_blk, blocks.data(), 4 * blocks.size());
+  if (NL > 0) std::memcpy(h + o_lpts, large_pts.data(), 4 * (size_t)NL);
+
+  c->scratch.reset();
+  hipStream_t st = c->stream;
+  void *dup = nullptr, *ddown = nullptr, *dkey = nullptr;
+  MPU_HIPCHK(c, c->scratch.take(up_bytes, &dup));
+  MPU_HIPCHK(c, c->scratch.take(down_bytes, &ddown));
+  MPU_HIPCHK(c, c->scratch.take(4 * (size_t)P, &dkey));
+  MPU_HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
+  if (NL > 0) MPU_HIPCHK(c, hipMemsetAsync(dkey, 0xFF, 4 * (size_t)P, st));
+  char* du = static_cast<char*>(dup);
+  char* dd = static_cast<char*>(ddown);
+  MpuBufs b;
+  b.slots = db->d_slots;
+  b.rows = db->d_rows;
+  b.pts = reinterpret_cast<const MpuPoint*>(du + o_pts);
+  b.obs_slot = reinterpret_cast<const int32_t*>(du + o_oslot);
+  b.el_row = reinterpret_cast<const int32_t*>(du + o_el);
+  b.small_order = reinterpret_cast<const int32_t*>(du + o_small);
+  b.large_blocks = reinterpret_cast<const int2*>(du + o_blk);
+  b.large_key = static_cast<uint32_t*>(dkey);
+  b.large_pts = reinterpret_cast<const int32_t*>(du + o_lpts);
+  b.best = reinterpret_cast<int32_t*>(dd + d_best);
+  b.desc = reinterpret_cast<uint4*>(dd + d_desc);
+  b.normal = reinterpret_cast<float*>(dd + d_nrm);
+  b.dist = reinterpret_cast<float*>(dd + d_dist);
+  MPU_HIPCHK(c, mpu_launch(b, small_off, NB, NL, st));
+  MPU_HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  MPU_HIPCHK(c, hipStreamSynchronize(st));
+
+  // outputs: only what was asked for, only where the reference writes
+  const char* o = c->pin_out.p;
+  const int32_t* obest = reinterpret_cast<const int32_t*>(o + d_best);
+  const float* onrm = reinterpret_cast<const float*>(o + d_nrm);
+  const float* odist = reinterpret_cast<const float*>(o + d_dist);
+  for (int p = 0; p < P; p++) {
+    const MpuPoint& q = pts[p];
+    int32_t flags = 0;
+    if (q.M == 0) flags |= DSH_MP_NO_OBS;
+    if (no_good[p]) flags |= DSH_MP_NO_GOOD_DESC;
+    if (want_d) {
+      const bool elected = q.Me > 0;
+      if (best) best[p] = elected ? el_obs[q.el_off + obest[p]] : -1;
+      if (elected) std::memcpy(desc + 32 * (size_t)p, o + d_desc + 32 * (size_t)p, 32);
+    }
+    if (want_g && q.M > 0) {
+      std::memcpy(normal + 3 * (size_t)p, onrm + 3 * (size_t)p, 12);
+      max_distance[p] = odist[2 * (size_t)p];
+      min_distance[p] = odist[2 * (size_t)p + 1];
+    }
+    if (status) status[p] = flags;
+  }
+  return DSH_OK;
+}
+
+}  // extern "C"

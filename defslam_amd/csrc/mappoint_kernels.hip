@@ -1,0 +1,211 @@
+// Map point upkeep (dsh_mappoint_update): MapPoint::ComputeDistinctiveDescriptors (Thirdparty/ORBSLAM_2/src/MapPoint.cc:257-325) and
+// MapPoint::UpdateNormalAndDepth (MapPoint.cc:348-391) of a batch of independent map points, on the descriptor rows dsh_kfdb keeps in
+// HBM.  Observation counts are very uneven, so a call has two kinds of work, all on the context's stream:
+//   small   points with M <= 64 observations: lane groups of 8, 16, 32 or 64 lanes (the host bins points by M), one lane per row.  The
+//           group stages its election rows in LDS, every lane forms its row of Hamming distances (16-bit, in registers) and finds the
+//           element of rank floor((Me-1)/2) by a 9-step bisection on the distance value (0 .. 256); the winner is the (median, row)
+//           minimum over the group.  The same lanes form the terms of the normal, summed in observation order.
+//   large   points with more: one wavefront per block of 64 election rows.  Each lane owns a row and counts its distances to every
+//           election row (read with wave-uniform addresses) into its own 257-bin histogram in LDS (16-bit counts, two to a word), then
+//           walks it to the median; blocks publish (median << 16 | row) with atomicMin.  One more wavefront per point forms the
+//           normal's terms 64 at a time and sums them in order.  The host starts the biggest points first.
+//   finish  one thread per large point: the winner's descriptor row.
+// Compiled without FMA contraction: the reference's float32 expression order is kept (see include/defslam_hip.h).
+#pragma clang fp contract(off)
+#include <hip/hip_runtime.h>
+
+#include "mappoint_problem.h"
+
+namespace {
+
+__device__ __forceinline__ int hamming(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
+  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
+         __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// one term of UpdateNormalAndDepth's loop (MapPoint.cc:370-374): normali = mWorldPos - Owi, alpha = (float)(1.0 / cv::norm(normali));
+// cv::scaleAdd adds normali * alpha to the running sum
+__device__ __forceinline__ void normal_term(const MpuSlot& s, float x, float y, float z, float& tx, float& ty, float& tz) {
+  const float nx = x - s.Ow[0], ny = y - s.Ow[1], nz = z - s.Ow[2];
+  const double nrm = sqrt((double)nx * (double)nx + (double)ny * (double)ny + (double)nz * (double)nz);
+  const float a = (float)(1.0 / nrm);
+  tx = nx * a;
+  ty = ny * a;
+  tz = nz * a;
+}
+
+// mNormalVector = normal / n (MapPoint.cc:389) and the depth range (:379-388), written by one lane
+__device__ __forceinline__ void write_geometry(const MpuBufs& b, const MpuPoint& pt, int p, float sx, float sy, float sz) {
+  float* nv = b.normal + 3 * (size_t)p;
+  if (pt.M > 1) {
+    const float a = (float)(1.0 / (double)pt.M);   // Mat::convertTo(scale 1.0 / n): cvt_32f's src * a + b with b = 0
+    nv[0] = sx * a + 0.0f;
+    nv[1] = sy * a + 0.0f;
+    nv[2] = sz * a + 0.0f;
+  } else {   // n == 1: cv::add(normal, Scalar(0))
+    nv[0] = sx + 0.0f;
+    nv[1] = sy + 0.0f;
+    nv[2] = sz + 0.0f;
+  }
+  const MpuSlot r = b.slots[pt.ref_slot];
+  const float px = pt.x - r.Ow[0], py = pt.y - r.Ow[1], pz = pt.z - r.Ow[2];
+  const float dist = (float)sqrt((double)px * (double)px + (double)py * (double)py + (double)pz * (double)pz);
+  const float mx = dist * pt.sf_level;
+  b.dist[2 * (size_t)p] = mx;
+  b.dist[2 * (size_t)p + 1] = mx / pt.sf_last;
+}
+
+// W lanes per point; a block of 256 threads serves 256 / W points of one width class
+template <int W>
+__global__ __launch_bounds__(256) void mpu_small_kernel(MpuBufs b, int off, int n) {
+  __shared__ uint4 sd[2 * 256];
+  const int t = threadIdx.x, r = t % W, g = t / W, gbase = (t & 63) - r;   // gbase: the group's first lane in the wavefront
+  const int k = blockIdx.x * (256 / W) + g;
+  const bool has = k < n;
+  const int p = has ? b.small_order[off + k] : 0;
+  MpuPoint pt;
+  if (has) pt = b.pts[p];
+  else { pt.M = pt.Me = 0; pt.what = 0; pt.x = pt.y = pt.z = 0.f; }
+  const bool elect = (pt.what & 1) && pt.Me > 0, geom = (pt.what & 2) && pt.M > 0;
+  uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
+  if (elect && r < pt.Me) {
+    const int row = b.el_row[pt.el_off + r];
+    d0 = b.rows[2 * (size_t)row];
+    d1 = b.rows[2 * (size_t)row + 1];
+  }
+  sd[2 * t] = d0;
+  sd[2 * t + 1] = d1;
+  __syncthreads();
+  if (elect) {
+    // row r of D as 16-bit distances; columns past Me hold 511, above every value the bisection tests
+    uint32_t dd[W / 2];
+    const uint4* gd = sd + 2 * (t - r);
+#pragma unroll
+    for (int j = 0; j < W; j += 2) {
+      const int a = j < pt.Me ? hamming(d0, d1, gd[2 * j], gd[2 * j + 1]) : 511;
+      const int c = j + 1 < pt.Me ? hamming(d0, d1, gd[2 * j + 2], gd[2 * j + 3]) : 511;
+      dd[j / 2] = (uint32_t)a | ((uint32_t)c << 16);
+    }
+    // the smallest v with #{j : D[r][j] <= v} > floor((Me-1)/2): sorted(row)[(size_t)(0.5 * (Me - 1))] (MapPoint.cc:311-313)
+    const int kth = (pt.Me - 1) / 2;
+    int lo = 0, hi = 256;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < W / 2; j++) cnt += (int)((dd[j] & 0xFFFF) <= (uint32_t)mid) + (int)((dd[j] >> 16) <= (uint32_t)mid);
+      if (cnt > kth) hi = mid;
+      else lo = mid + 1;
+    }
+    uint32_t key = r < pt.Me ? ((uint32_t)lo << 16) | (uint32_t)r : 0xFFFFFFFFu;
+    // the first row with a strictly smaller median (MapPoint.cc:315-319): the (median, row) minimum of the group
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+      const uint32_t other = (uint32_t)__shfl_xor((int)key, o, 64);
+      key = other < key ? other : key;
+    }
+    if (r == 0) {
+      const int e = (int)(key & 0xFFFF);
+      b.best[p] = e;
+      b.desc[2 * (size_t)p] = sd[2 * (t + e)];
+      b.desc[2 * (size_t)p + 1] = sd[2 * (t + e) + 1];
+    }
+  }
+  // the normal: lane r forms the term of observation r, every lane of the group sums the group's terms in observation order
+  float tx = 0.f, ty = 0.f, tz = 0.f;
+  if (geom && r < pt.M) normal_term(b.slots[b.obs_slot[pt.obs_off + r]], pt.x, pt.y, pt.z, tx, ty, tz);
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    const float ux = __shfl(tx, gbase + j, 64), uy = __shfl(ty, gbase + j, 64), uz = __shfl(tz, gbase + j, 64);
+    if (j < pt.M) {
+      sx = ux + sx;
+      sy = uy + sy;
+      sz = uz + sz;
+    }
+  }
+  if (geom && r == 0) write_geometry(b, pt, p, sx, sy, sz);
+}
+
+// one wavefront per block: (p, first election row) or (p, -1) for the point's normal and depth
+__global__ __launch_bounds__(64) void mpu_large_kernel(MpuBufs b) {
+  __shared__ uint32_t hist[64 * MPU_HIST_WORDS];
+  const int2 blk = b.large_blocks[blockIdx.x];
+  const int p = blk.x, row0 = blk.y, lane = threadIdx.x;
+  const MpuPoint pt = b.pts[p];
+  if (row0 < 0) {
+    // UpdateNormalAndDepth: 64 terms at a time, summed in observation order by every lane (the same value in each)
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int base = 0; base < pt.M; base += 64) {
+      float tx = 0.f, ty = 0.f, tz = 0.f;
+      if (base + lane < pt.M) normal_term(b.slots[b.obs_slot[pt.obs_off + base + lane]], pt.x, pt.y, pt.z, tx, ty, tz);
+      const int cnt = min(64, pt.M - base);
+      for (int l = 0; l < cnt; l++) {
+        sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tx), l)) + sx;
+        sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ty), l)) + sy;
+        sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tz), l)) + sz;
+      }
+    }
+    if (lane == 0) write_geometry(b, pt, p, sx, sy, sz);
+    return;
+  }
+  const int i = row0 + lane;
+  const bool valid = i < pt.Me;
+  uint32_t* h = hist + lane * MPU_HIST_WORDS;
+  for (int w = 0; w < MPU_HIST_WORDS; w++) h[w] = 0;
+  uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
+  if (valid) {
+    const int row = b.el_row[pt.el_off + i];
+    d0 = b.rows[2 * (size_t)row];
+    d1 = b.rows[2 * (size_t)row + 1];
+  }
+  // each lane's histogram is its own: plain read-modify-write, no atomics.  Counts <= Me <= 65535 fit their 16 bits.
+  for (int j = 0; j < pt.Me; j++) {
+    const int row = b.el_row[pt.el_off + j];
+    const int dist = hamming(d0, d1, b.rows[2 * (size_t)row], b.rows[2 * (size_t)row + 1]);
+    if (valid) h[dist >> 1] += 1u << ((dist & 1) << 4);
+  }
+  const int kth = (pt.Me - 1) / 2;
+  int med = 256, cum = 0;
+  for (int w = 0; w < MPU_HIST_WORDS; w++) {
+    const uint32_t v = h[w];
+    const int lo = (int)(v & 0xFFFF), hi = (int)(v >> 16);
+    if (cum + lo > kth) { med = 2 * w; break; }
+    cum += lo;
+    if (cum + hi > kth) { med = 2 * w + 1; break; }
+    cum += hi;
+  }
+  uint32_t key = valid ? ((uint32_t)med << 16) | (uint32_t)i : 0xFFFFFFFFu;
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t other = (uint32_t)__shfl_xor((int)key, o, 64);
+    key = other < key ? other : key;
+  }
+  if (lane == 0) atomicMin(&b.large_key[p], key);
+}
+
+__global__ __launch_bounds__(64) void mpu_finish_kernel(MpuBufs b, int n_large) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n_large) return;
+  const int p = b.large_pts[k];
+  const MpuPoint pt = b.pts[p];
+  if (!(pt.what & 1) || pt.Me <= 0) return;
+  const int e = (int)(b.large_key[p] & 0xFFFF);
+  const int row = b.el_row[pt.el_off + e];
+  b.best[p] = e;
+  b.desc[2 * (size_t)p] = b.rows[2 * (size_t)row];
+  b.desc[2 * (size_t)p + 1] = b.rows[2 * (size_t)row + 1];
+}
+
+}  // namespace
+
+// small_off[5]: the small points of width class c (8, 16, 32, 64 lanes) are small_order[small_off[c] .. small_off[c + 1])
+extern "C" hipError_t mpu_launch(const MpuBufs& b, const int32_t* small_off, int n_large_blocks, int n_large, hipStream_t st) {
+  if (n_large_blocks > 0) hipLaunchKernelGGL(mpu_large_kernel, dim3(n_large_blocks), dim3(64), 0, st, b);
+  if (n_large > 0) hipLaunchKernelGGL(mpu_finish_kernel, dim3((n_large + 63) / 64), dim3(64), 0, st, b, n_large);
+  const int n8 = small_off[1] - small_off[0], n16 = small_off[2] - small_off[1], n32 = small_off[3] - small_off[2], n64 = small_off[4] - small_off[3];
+  if (n8 > 0) hipLaunchKernelGGL(mpu_small_kernel<8>, dim3((n8 + 31) / 32), dim3(256), 0, st, b, small_off[0], n8);
+  if (n16 > 0) hipLaunchKernelGGL(mpu_small_kernel<16>, dim3((n16 + 15) / 16), dim3(256), 0, st, b, small_off[1], n16);
+  if (n32 > 0) hipLaunchKernelGGL(mpu_small_kernel<32>, dim3((n32 + 7) / 8), dim3(256), 0, st, b, small_off[2], n32);
+  if (n64 > 0) hipLaunchKernelGGL(mpu_small_kernel<64>, dim3((n64 + 3) / 4), dim3(256), 0, st, b, small_off[3], n64);
+  return hipGetLastError();
+}

@@ -477,6 +477,78 @@ int dsh_search_by_projection_local(dsh_ctx* ctx, const dsh_track_frame* frame, i
                                    const float* max_distance, const uint8_t* desc, const uint8_t* skip, float th, int32_t* match,
                                    uint8_t* in_view, int32_t* level, int32_t* nmatches);
 
+/* ---- map point upkeep: distinctive descriptor, normal and depth range ----------------------------------------------------
+ * Two MapPoint methods keep the inputs of the local-map search current:
+ *   descriptor      MapPoint::ComputeDistinctiveDescriptors   Thirdparty/ORBSLAM_2/src/MapPoint.cc:257-325
+ *   normal, depth   MapPoint::UpdateNormalAndDepth            MapPoint.cc:348-391
+ * called from LocalMapping::ProcessNewKeyFrame (LocalMapping.cc:142-161, via DefLocalMapping.cc:160-164: both, for every map point of
+ * the new keyframe that it does not yet observe), DefLocalMapping::CreateNewMapPoints (DefLocalMapping.cc:340-341: both),
+ * DefTracking::MonocularInitialization (DefTracking.cc:610-611: both) and DefMapPoint::Repose (DefMapPoint.cc:122-126, from
+ * TriangularMesh.cc:192: normal and depth only).
+ * dsh_kfdb keeps what these read of every keyframe resident in HBM: the descriptor rows, the octaves of mvKeysUn, the camera centre,
+ * the scale pyramid and the bad flag.  A keyframe is copied up once, when it is added; keyframe poses do not change after insertion in
+ * DefSLAM (there is no keyframe bundle adjustment), so the store has no pose update.  Lifetime as dsh_diffdb: a store belongs to the
+ * context it was created on; dsh_destroy of that context detaches it -- every call on it then returns DSH_ERR_ARG -- and
+ * dsh_kfdb_destroy works before or after dsh_destroy. */
+typedef struct dsh_kfdb dsh_kfdb;
+typedef struct dsh_mp_keyframe {
+  float Ow[3];                 /* GetCameraCenter(), float32 */
+  int32_t N;                   /* key points */
+  const uint8_t* desc;         /* N x 32 mDescriptors rows */
+  const int32_t* octave;       /* N  mvKeysUn[j].octave, 0 .. 127 */
+  int32_t levels;              /* mnScaleLevels, 1 .. 32 */
+  const float* scale_factors;  /* mvScaleFactors[levels] */
+  int32_t bad;                 /* isBad() */
+} dsh_mp_keyframe;
+/* capacity is the initial number of keyframes; the store grows on demand (descriptor rows too). */
+int dsh_kfdb_create(dsh_ctx* ctx, int32_t capacity, dsh_kfdb** out);
+int dsh_kfdb_destroy(dsh_kfdb* db);
+int dsh_kfdb_clear(dsh_kfdb* db);                                       /* forget every keyframe (DefMap::clear on a reset) */
+int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot);/* copy one keyframe up; *slot = its index, 0, 1, 2 ... */
+int dsh_kfdb_set_bad(dsh_kfdb* db, int32_t slot, int32_t bad);           /* KeyFrame::SetBadFlag */
+int32_t dsh_kfdb_count(const dsh_kfdb* db);                             /* keyframes stored; -1 for NULL */
+
+#define DSH_MP_DESCRIPTOR 1    /* what: ComputeDistinctiveDescriptors */
+#define DSH_MP_NORMAL_DEPTH 2  /* what: UpdateNormalAndDepth */
+#define DSH_MP_NO_OBS 1        /* status: no observations -- nothing changed, no output written but best (-1) and status */
+#define DSH_MP_NO_GOOD_DESC 2  /* status: observations, none in a keyframe that is not bad -- descriptor unchanged (set whatever `what` asks) */
+#define DSH_MP_MAX_OBS 65535
+/* Updates P independent map points (the points of ProcessNewKeyFrame's loop do not interact, so one batch is exact).  The caller leaves
+ * out bad points (both methods return at once on mbBad).
+ * Inputs: xyz[P x 3] (mWorldPos, float32); the observations as CSR in the reference's iteration order (std::map<KeyFrame*, size_t>, so
+ * the caller supplies that order): obs_ptr[P + 1], obs_kf[] (store slots), obs_idx[] (the key point index in that keyframe); ref_kf[P]
+ * (the slot of mpRefKF; read only with DSH_MP_NORMAL_DEPTH); what = DSH_MP_DESCRIPTOR | DSH_MP_NORMAL_DEPTH.
+ * Outputs (each may be NULL when `what` does not ask for it; a part not asked for is never written): desc[P x 32] in/out, left as it
+ * was where the reference returns early; best[P] the index into the point's observations of the elected descriptor, or -1; normal[P x
+ * 3], max_distance[P], min_distance[P]; status[P] (may be NULL) DSH_MP_* flags above.
+ * Election (MapPoint.cc:257-325): only observations whose keyframe is not bad take part (:279-283); D is the full M x M Hamming matrix
+ * with 0 on the diagonal (:292-304); the median of row i is sorted(row)[(size_t)(0.5 * (M - 1))], the element of rank floor((M-1)/2)
+ * (:311-313); the winner is the first i with a strictly smaller median, ties go to the earliest observation (:315-319).  M = 1 elects
+ * that descriptor; M = 2 has both medians 0 and elects index 0.  Integer valued: best and desc are bit-exact.
+ * Normal (MapPoint.cc:366-377): the sum runs over ALL observations, bad keyframes included (UpdateNormalAndDepth does not test isBad),
+ * in observation order, n counts every observation.  The sum is sequential: the order is part of the result.
+ * Depth (MapPoint.cc:379-390): dist = cv::norm(Pos - Ow_ref) rounded to float; level = pRefKF->mvKeysUn[observations[pRefKF]].octave;
+ * max = dist * scale_factors[level], min = max / scale_factors[levels - 1], both float.  Quirk, reproduced: operator[] on the copied map
+ * yields index 0 when the reference keyframe is not among the observations, so key point 0 of the reference keyframe gives the octave.
+ * Arithmetic (OpenCV 4 internals restated -- a reading of OpenCV's sources; no OpenCV build was available to check against):
+ *   normali = mWorldPos - Owi                float32, per element
+ *   cv::norm(normali)                        sqrt in double of the double sum ((x*x + y*y) + z*z) (normL2_32f)
+ *   normal + normali / norm                  MatExpr builds AddEx(normal, normali, 1, 1.0/norm), assigned as
+ *                                            cv::scaleAdd(normali, 1.0/norm, normal): alpha rounded to float, then per element
+ *                                            normali * alpha + normal in float32 (scaleAdd_32f's scalar tail: 3 elements never reach
+ *                                            its vector loop), product and sum rounded separately
+ *   normal / n                               n > 1: Mat::convertTo with scale 1.0/n: a = (float)(1.0/n), normal * a + 0.0f in float32
+ *                                            (cvt_32f's scalar path); n = 1: cv::add(normal, 0), which leaves it as it is
+ *   dist, max, min                           (float)sqrt(double sum), then float products / quotient as above
+ * No FMA contraction anywhere.  A point that coincides with a keyframe centre gives the reference's NaN (0 * inf), not a guard.
+ * Limits: at most DSH_MP_MAX_OBS observations per point.  A point with more, a slot outside the store, a slot repeated within one point
+ * (the reference's map holds a keyframe once), obs_idx >= N of its keyframe, or a reference octave >= levels (checked only where it is
+ * read) makes the call return DSH_ERR_ARG without writing any output.  Arguments are checked first: a host-only context (which has no
+ * store) reports bad ones with DSH_ERR_ARG and then returns DSH_ERR_NO_DEVICE (no CPU fallback). */
+int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, const int32_t* obs_ptr, const int32_t* obs_kf,
+                        const int32_t* obs_idx, const int32_t* ref_kf, int32_t what, uint8_t* desc, int32_t* best, float* normal,
+                        float* max_distance, float* min_distance, int32_t* status);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
