@@ -12,6 +12,8 @@
 
 #include <cstdint>
 
+#include "mapping_launch.h"
+
 namespace {
 
 __global__ void ddb_keep_kernel(int n, const uint8_t* __restrict__ drop, const int32_t* __restrict__ pid, int32_t* __restrict__ keep) {

@@ -20,15 +20,11 @@
 #include "sft_pack.h"
 #include "sft_problem.h"
 
+#include "mapping_launch.h"
+
 #ifdef DSH_LAB
 #include "../../include/defslam_hip_debug.h"
 #endif
-
-extern "C" hipError_t sft_lm_launch(const SftDev* d_probs, int B, int max_kd, size_t jl_doubles, int nw, size_t* configured, hipStream_t stream);
-extern "C" size_t sft_lm_kernel_lds_bytes(int kd, size_t jl_doubles);
-extern "C" hipError_t sftb_launch(const SftDev* d_probs, SftRun* d_runs, int* d_counters, int* d_list, int B, int phase, size_t jl_doubles, size_t xyz_doubles, size_t* configured, int num_cus, int tail_below, hipStream_t stream);
-extern "C" hipError_t sftb_tail_launch(const SftDev* d_probs, SftRun* d_runs, int* d_counters, int B, int max_kd, size_t jl_doubles, size_t* configured, int num_cus, int tail_below, hipStream_t stream);
-extern "C" hipError_t sft_spec_launch(const SftDev* d_probs, SftSpec* d_spec, int B, int K, int phase, int nh, int owner_waves, int max_kd, size_t jl_doubles, size_t* configured, hipStream_t stream);
 
 // The dynamic LDS size a kernel has been enabled for (hipFuncSetAttribute) is a property of the (device, kernel) pair, not of a context: two
 // contexts on one GPU -- tracking and mapping, say -- must not lower each other's setting.  One high-water mark per device and kernel for the
@@ -38,15 +34,6 @@ static LdsMarks g_lds_marks[64];
 static std::mutex g_lds_mu;
 #define LDS_MARKS(c) (g_lds_marks[(c)->device & 63])
 #define LDS_LOCK() std::lock_guard<std::mutex> lds_lock__(g_lds_mu)
-extern "C" hipError_t sft_sc_launch(const SftDev* d_probs, SftSc* d_sc, int B, int phase, int max_kd, size_t jl_doubles, size_t* configured, hipStream_t stream);
-extern "C" hipError_t sft_sc_local_reduce(SftSc* const* d_ptrs, int G, hipStream_t stream);
-extern "C" hipError_t sft_cn_launch(const SftDev* d_probs, SftSc* d_sc, int phase, int max_kd, size_t jl_doubles, size_t* configured, hipStream_t stream);
-extern "C" hipError_t sft_vec_sum2(const double* a, const double* b, double* out_a, double* out_b, int n, hipStream_t stream);
-#ifdef DSH_LAB
-extern "C" hipError_t sft_wave_lab_launch(const SftDev* d_probs, int B, int which, double rel, int max_kd, size_t jl_doubles, hipStream_t stream);
-extern "C" hipError_t sft_assembly_launch(const SftDev* d_probs, int B, int max_kd, size_t jl_doubles, int nw, hipStream_t stream);
-extern "C" hipError_t sftb_factor_lab_launch(const SftDev* d_probs, SftRun* d_runs, int* d_counters, int B, int grid, hipStream_t stream);
-#endif
 
 namespace {
 
@@ -62,46 +49,7 @@ struct Packed {
   dsh::SftFramePack f;
 };
 
-// Host buffer of a context that the copy engine reads / writes directly: page-locked for a GPU context (hipMemcpyAsync
-// from pageable memory is staged and synchronous), plain memory for a host-only one.  Grow-only.
-struct HostBuf {
-  char* p = nullptr;
-  size_t cap = 0;
-  bool pinned = false;
-  hipError_t ensure(size_t bytes, bool want_pinned) {
-    if (bytes <= cap) return hipSuccess;
-    release();
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (want_pinned) {
-      const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
-      if (e != hipSuccess) { p = nullptr; return e; }
-      pinned = true;
-    } else {
-      p = static_cast<char*>(std::malloc(want));
-      if (!p) return hipErrorOutOfMemory;
-      pinned = false;
-    }
-    cap = want;
-    return hipSuccess;
-  }
-  void release() {
-    if (p) { if (pinned) (void)hipHostFree(p); else std::free(p); }
-    p = nullptr; cap = 0;
-  }
-};
-
-struct Arena {  // byte layout of a device allocation, 256-byte aligned slices
-  size_t size = 0;
-  size_t take(size_t bytes) {
-    const size_t off = size;
-    size += (bytes + 255) & ~size_t(255);
-    return off;
-  }
-};
-
 }  // namespace
-
-extern "C" hipError_t reg_embed(int, const float*, int, const double*, const int32_t*, const int32_t*, const int32_t*, int32_t*, int32_t*, float*, hipStream_t);
 
 struct dsh_ctx : dsh_ctx_base {
   dsh::TemplateHost tmpl;
@@ -169,17 +117,9 @@ struct dsh_ctx : dsh_ctx_base {
   bool any_split = false;              // some problem of the batch runs the two-sided factorisation (SftPart): a FACTOR launch precedes every trial launch
 };
 
-namespace {
+dsh_ctx_base* dsh_base(dsh_ctx* ctx) { return static_cast<dsh_ctx_base*>(ctx); }
 
-int fail(dsh_ctx* c, int code, const std::string& m) {
-  if (c) c->err = m;
-  return code;
-}
-#define HIPCHK(c, call)                                                                              \
-  do {                                                                                               \
-    hipError_t e__ = (call);                                                                         \
-    if (e__ != hipSuccess) return fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-  } while (0)
+namespace {
 
 void drop_graphs(dsh_ctx* c) {
   if (!c->host_only && c->stream) (void)hipStreamSynchronize(c->stream);   // a batch in flight may still read them
@@ -379,7 +319,7 @@ int run_rounds_enqueue(dsh_ctx* c) {
     for (int s = 0; s < S; s++) done += *reinterpret_cast<const int*>(c->spec_done.p + 64 * s);
     const int* c0 = reinterpret_cast<const int*>(c->spec_done.p);
     if (done >= B) { c->rounds_hint = (tail_below >= 0 && c0[6]) ? std::max(1, c0[7]) : rounds; break; }
-    if (rounds >= worst) { rc = fail(c, DSH_ERR_STATE, "batched rounds: a problem did not terminate within its trial budget"); break; }
+    if (rounds >= worst) { rc = dsh_fail(c, DSH_ERR_STATE, "batched rounds: a problem did not terminate within its trial budget"); break; }
     group = 2;
   }
   return rc;   // (every stream is idle here: what the caller enqueues on the context's stream is ordered behind all of them)
@@ -422,7 +362,7 @@ int run_once(dsh_ctx* c) {
     int needed = 0;
     for (int b = 0; b < B; b++) { all_done = all_done && sp[b].done; needed = std::max(needed, sp[b].launches); }
     if (all_done) { c->spec_hint = needed; break; }
-    if (rounds >= worst) return fail(c, DSH_ERR_STATE, "speculative trials: a problem did not terminate within its launch budget");
+    if (rounds >= worst) return dsh_fail(c, DSH_ERR_STATE, "speculative trials: a problem did not terminate within its launch budget");
     group = 2;
   }
   return DSH_OK;
@@ -470,8 +410,7 @@ int dsh_create(dsh_ctx** out, int device) {
 
 int dsh_destroy(dsh_ctx* c) {
   if (!c) return DSH_ERR_ARG;
-  ddb_detach_all(c);   // databases of this context stay valid objects (dsh_diffdb_destroy still frees them) but no longer name it
-  kfdb_detach_all(c);  // keyframe stores likewise (dsh_kfdb_destroy)
+  dsh_detach_stores(c);   // its stores stay valid objects (dsh_diffdb_destroy / dsh_kfdb_destroy still free them) but no longer name it
   if (c->host_only) { c->stage.release(); c->results.release(); delete c; return DSH_OK; }
   (void)hipSetDevice(c->device);
   drop_graphs(c);
@@ -495,16 +434,15 @@ int dsh_destroy(dsh_ctx* c) {
 const char* dsh_last_error(const dsh_ctx* c) { return c ? c->err.c_str() : "null context"; }
 void* dsh_stream(dsh_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int dsh_synchronize(dsh_ctx* c) {
-  if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return DSH_ERR_NO_DEVICE;
+  if (const int rc = dsh_enter(c, "dsh_synchronize")) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return DSH_OK;
 }
 
 int dsh_template_build(dsh_ctx* c, int n, const double* xyz0, int F, const int32_t* facets) {
-  if (!c || n <= 0 || F <= 0 || !xyz0 || !facets) return fail(c, DSH_ERR_ARG, "dsh_template_build: bad argument");
+  if (!c || n <= 0 || F <= 0 || !xyz0 || !facets) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_build: bad argument");
   for (int i = 0; i < 3 * F; i++)
-    if (facets[i] < 0 || facets[i] >= n) return fail(c, DSH_ERR_ARG, "dsh_template_build: facet index out of range");
+    if (facets[i] < 0 || facets[i] >= n) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_build: facet index out of range");
   if (!c->host_only) (void)hipSetDevice(c->device);
   c->tmpl.build(n, xyz0, F, facets);
   return upload_template(c);
@@ -512,19 +450,19 @@ int dsh_template_build(dsh_ctx* c, int n, const double* xyz0, int F, const int32
 
 int dsh_template_set(dsh_ctx* c, int n, const double* xyz0, const uint8_t* boundary, const int32_t* rp, const int32_t* col, const double* w,
                      const double* k0, int E, const int32_t* en, const double* eL, double median_L) {
-  if (!c || n <= 0 || E < 0 || !xyz0 || !boundary || !rp || !col || !w || !k0 || !en || !eL) return fail(c, DSH_ERR_ARG, "dsh_template_set: bad argument");
+  if (!c || n <= 0 || E < 0 || !xyz0 || !boundary || !rp || !col || !w || !k0 || !en || !eL) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: bad argument");
   // The arrays become indices of the packer (inc[edge_nodes[..]], opt[nbr_col[..]]): a malformed CSR or edge list must be
   // refused here, not turn into an out-of-bounds write later.
-  if (rp[0] != 0) return fail(c, DSH_ERR_ARG, "dsh_template_set: nbr_rowptr[0] != 0");
+  if (rp[0] != 0) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: nbr_rowptr[0] != 0");
   for (int i = 0; i < n; i++)
-    if (rp[i + 1] < rp[i]) return fail(c, DSH_ERR_ARG, "dsh_template_set: nbr_rowptr is not non-decreasing");
+    if (rp[i + 1] < rp[i]) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: nbr_rowptr is not non-decreasing");
   for (int p = 0; p < rp[n]; p++)
-    if (col[p] < 0 || col[p] >= n) return fail(c, DSH_ERR_ARG, "dsh_template_set: neighbour index out of range");
+    if (col[p] < 0 || col[p] >= n) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: neighbour index out of range");
   for (int e = 0; e < E; e++) {
-    if (en[2 * e] < 0 || en[2 * e] >= n || en[2 * e + 1] < 0 || en[2 * e + 1] >= n) return fail(c, DSH_ERR_ARG, "dsh_template_set: edge node out of range");
-    if (!(eL[e] > 0.0)) return fail(c, DSH_ERR_ARG, "dsh_template_set: edge rest length must be positive");
+    if (en[2 * e] < 0 || en[2 * e] >= n || en[2 * e + 1] < 0 || en[2 * e + 1] >= n) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: edge node out of range");
+    if (!(eL[e] > 0.0)) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: edge rest length must be positive");
   }
-  if (!(median_L > 0.0)) return fail(c, DSH_ERR_ARG, "dsh_template_set: median edge length must be positive");
+  if (!(median_L > 0.0)) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_set: median edge length must be positive");
   if (!c->host_only) (void)hipSetDevice(c->device);
   c->tmpl.set(n, xyz0, boundary, rp, col, w, k0, E, en, eL, median_L);
   return upload_template(c);
@@ -561,26 +499,25 @@ int dsh_template_embed(const dsh_ctx* c, int P, const float* pts, int32_t* facet
 
 int dsh_template_embed_device(dsh_ctx* c, int P, const float* pts, int32_t* facet_id, int32_t* nodes, float* bary) {
   if (!c) return DSH_ERR_ARG;
-  if (!c->tmpl.valid || c->tmpl.F <= 0) return fail(c, DSH_ERR_STATE, "dsh_template_embed_device: needs a template built from facets");
-  if (P < 0 || (P > 0 && (!pts || !facet_id || !nodes || !bary))) return fail(c, DSH_ERR_ARG, "dsh_template_embed_device: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_template_embed_device: host-only context, no GPU (dsh_template_embed is the host routine)");
+  if (!c->tmpl.valid || c->tmpl.F <= 0) return dsh_fail(c, DSH_ERR_STATE, "dsh_template_embed_device: needs a template built from facets");
+  if (P < 0 || (P > 0 && (!pts || !facet_id || !nodes || !bary))) return dsh_fail(c, DSH_ERR_ARG, "dsh_template_embed_device: bad argument");
+  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_template_embed_device: host-only context, no GPU (dsh_template_embed is the host routine)");
   if (P == 0) return DSH_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return fail(c, DSH_ERR_HIP, "dsh_template_embed_device: hipSetDevice failed");
+  if (const int rc = dsh_enter(c, "dsh_template_embed_device")) return rc;
   const dsh::TemplateHost& t = c->tmpl;
-  c->scratch.reset();
   hipStream_t st = c->stream;
   struct Item { const void* src; size_t bytes; void* dev; };
   Item in[5] = {{pts, 12 * (size_t)P, nullptr}, {t.xyz0.data(), 24 * (size_t)t.n, nullptr}, {t.facets.data(), 12 * (size_t)t.F, nullptr},
                 {t.nf_ptr.data(), 4 * (size_t)(t.n + 1), nullptr}, {t.nf_idx.data(), 4 * t.nf_idx.size(), nullptr}};
   for (Item& it : in) {
-    if (c->scratch.take(it.bytes, &it.dev) != hipSuccess) return fail(c, DSH_ERR_HIP, "dsh_template_embed_device: out of device memory");
+    if (c->scratch.take(it.bytes, &it.dev) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_template_embed_device: out of device memory");
     if (it.bytes && hipMemcpyAsync(it.dev, it.src, it.bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-      return fail(c, DSH_ERR_HIP, "dsh_template_embed_device: upload failed");
+      return dsh_fail(c, DSH_ERR_HIP, "dsh_template_embed_device: upload failed");
   }
   void *d_fid = nullptr, *d_nodes = nullptr, *d_bary = nullptr;
   if (c->scratch.take(4 * (size_t)P, &d_fid) != hipSuccess || c->scratch.take(12 * (size_t)P, &d_nodes) != hipSuccess ||
       c->scratch.take(12 * (size_t)P, &d_bary) != hipSuccess)
-    return fail(c, DSH_ERR_HIP, "dsh_template_embed_device: out of device memory");
+    return dsh_fail(c, DSH_ERR_HIP, "dsh_template_embed_device: out of device memory");
   hipError_t e = reg_embed(P, static_cast<const float*>(in[0].dev), t.n, static_cast<const double*>(in[1].dev), static_cast<const int32_t*>(in[2].dev),
                            static_cast<const int32_t*>(in[3].dev), static_cast<const int32_t*>(in[4].dev), static_cast<int32_t*>(d_fid),
                            static_cast<int32_t*>(d_nodes), static_cast<float*>(d_bary), st);
@@ -588,13 +525,13 @@ int dsh_template_embed_device(dsh_ctx* c, int P, const float* pts, int32_t* face
   if (e == hipSuccess) e = hipMemcpyAsync(nodes, d_nodes, 12 * (size_t)P, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(bary, d_bary, 12 * (size_t)P, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(c, DSH_ERR_HIP, std::string("dsh_template_embed_device: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, std::string("dsh_template_embed_device: ") + hipGetErrorString(e));
   return DSH_OK;
 }
 
 int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) {
-  if (!c || B <= 0 || !frames) return fail(c, DSH_ERR_ARG, "dsh_sft_batch_upload: bad argument");
-  if (!c->tmpl.valid) return fail(c, DSH_ERR_STATE, "dsh_sft_batch_upload: no template");
+  if (!c || B <= 0 || !frames) return dsh_fail(c, DSH_ERR_ARG, "dsh_sft_batch_upload: bad argument");
+  if (!c->tmpl.valid) return dsh_fail(c, DSH_ERR_STATE, "dsh_sft_batch_upload: no template");
   if (!c->host_only) (void)hipSetDevice(c->device);
   c->B = 0;
   c->ran = false;
@@ -603,7 +540,7 @@ int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) {
   for (int b = 0; b < B; b++) {
     std::string e;
     const int rc = pack_problem(c, frames[b], c->opt.wide_off != 0, c->packed[b], e);
-    if (rc != DSH_OK) return fail(c, rc, "problem " + std::to_string(b) + ": " + e);
+    if (rc != DSH_OK) return dsh_fail(c, rc, "problem " + std::to_string(b) + ": " + e);
   }
   // Launch shape: 8 wavefronts per problem give the lowest latency; with at least two problems per CU, 4 wavefronts
   // per problem (two problems resident per CU, <= 80 KB of LDS each) give the higher throughput.  Band mode needs 8.
@@ -764,7 +701,7 @@ int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) {
   if (nh > 0)
     for (int e = 0; e < B * K; e++) {
       const SftDev& h = c->packed[e % B].h;
-      if (h.split) for (int g = 0; g < 2; g++) sync_total += ((size_t)4 * (16 + h.part[g].nT) + 255) & ~(size_t)255;
+      if (h.split) for (int g = 0; g < 2; g++) sync_total += Arena::round((size_t)4 * (16 + h.part[g].nT));
     }
   const size_t o_sync = a.take(sync_total);
   size_t sync_used = 0;
@@ -801,11 +738,11 @@ int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) {
         const bool helped = nh > 0 && g < 2;
         po.Pf = a.take(helped ? tiles : 0); po.PfB = a.take(helped ? col : 0);
         po.sync = o_sync + sync_used;
-        if (helped) sync_used += ((size_t)4 * (16 + q.nT) + 255) & ~(size_t)255;
+        if (helped) sync_used += Arena::round((size_t)4 * (16 + q.nT));
       }
   }
   if (sft_lm_kernel_lds_bytes(max_kd, jl_doubles) > 160 * 1024 || max_kd + kNB + SFT_BORDER > SFT_NT)
-    return fail(c, DSH_ERR_ARG, "half-bandwidth too large for the LDS panel / workgroup");
+    return dsh_fail(c, DSH_ERR_ARG, "half-bandwidth too large for the LDS panel / workgroup");
   bool fresh_arena = false;
   if (a.size > c->d_batch_cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -920,9 +857,8 @@ int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) {
 
 int dsh_sft_batch_run(dsh_ctx* c) {
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_sft_batch_run: host-only context, no GPU (there is no CPU fallback)");
-  if (c->B <= 0) return fail(c, DSH_ERR_STATE, "dsh_sft_batch_run: nothing uploaded");
-  (void)hipSetDevice(c->device);
+  if (const int rc = dsh_enter(c, "dsh_sft_batch_run")) return rc;
+  if (c->B <= 0) return dsh_fail(c, DSH_ERR_STATE, "dsh_sft_batch_run: nothing uploaded");
   const int rc = run_once(c);
   if (rc != DSH_OK) return rc;
   c->ran = true;
@@ -931,8 +867,7 @@ int dsh_sft_batch_run(dsh_ctx* c) {
 
 int dsh_sft_batch_counts(dsh_ctx* c, int64_t* iters, int64_t* trials) {
   if (!c || c->B <= 0 || !c->ran) return DSH_ERR_STATE;
-  if (c->host_only) return DSH_ERR_NO_DEVICE;
-  (void)hipSetDevice(c->device);
+  if (const int rc = dsh_enter(c, "dsh_sft_batch_counts")) return rc;
   // one copy of the B result headers (they are contiguous), ordered behind the run on the context's stream
   const size_t bytes = sizeof(SftResHdr) * (size_t)c->B;
   HIPCHK(c, c->results.ensure(std::max(bytes, c->results.cap), true));
@@ -960,10 +895,9 @@ int dsh_sft_batch_problem_info(dsh_ctx* c, int b, int64_t* bytes, int32_t* count
 }
 
 int dsh_sft_batch_download(dsh_ctx* c, int B, dsh_sft_result* res) {
-  if (!c || !res || B != c->B) return fail(c, DSH_ERR_ARG, "dsh_sft_batch_download: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_sft_batch_download: host-only context");
-  if (!c->ran) return fail(c, DSH_ERR_STATE, "dsh_sft_batch_download: no run");
-  (void)hipSetDevice(c->device);
+  if (!c || !res || B != c->B) return dsh_fail(c, DSH_ERR_ARG, "dsh_sft_batch_download: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_sft_batch_download")) return rc;
+  if (!c->ran) return dsh_fail(c, DSH_ERR_STATE, "dsh_sft_batch_download: no run");
   // the whole result region (headers + bodies of every problem) in ONE copy into page-locked memory
   HIPCHK(c, c->results.ensure(c->res_bytes, true));
   HIPCHK(c, hipMemcpyAsync(c->results.p, c->d_batch + c->res_off, c->res_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -998,7 +932,7 @@ int dsh_sft_batch_download(dsh_ctx* c, int B, dsh_sft_result* res) {
 }
 
 int dsh_sft_solve(dsh_ctx* c, const dsh_sft_frame* frame, dsh_sft_result* result) {
-  if (!c || !frame || !result) return fail(c, DSH_ERR_ARG, "dsh_sft_solve: bad argument");
+  if (!c || !frame || !result) return dsh_fail(c, DSH_ERR_ARG, "dsh_sft_solve: bad argument");
   int rc = dsh_sft_batch_upload(c, 1, frame);
   if (rc != DSH_OK) return rc;
   rc = dsh_sft_batch_run(c);
@@ -1168,18 +1102,17 @@ int dsh_comm_unique_id(void* id) {
 }
 
 int dsh_comm_create(dsh_ctx* c, int nranks, int rank, const void* id, dsh_comm** out) {
-  if (!c || !out || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(c, DSH_ERR_ARG, "dsh_comm_create: bad argument");
+  if (!c || !out || !id || nranks < 1 || rank < 0 || rank >= nranks) return dsh_fail(c, DSH_ERR_ARG, "dsh_comm_create: bad argument");
   *out = nullptr;
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_comm_create: host-only context");
+  if (const int rc = dsh_enter(c, "dsh_comm_create")) return rc;
   std::string err;
-  if (!g_rccl.load(err)) return fail(c, DSH_ERR_HIP, "dsh_comm_create: " + err);
-  (void)hipSetDevice(c->device);
+  if (!g_rccl.load(err)) return dsh_fail(c, DSH_ERR_HIP, "dsh_comm_create: " + err);
   RcclUniqueId uid;
   std::memcpy(&uid, id, sizeof(uid));
   std::unique_ptr<dsh_comm> cm(new dsh_comm());
   cm->nranks = nranks; cm->rank = rank; cm->ctx = c;
   const int rc = g_rccl.CommInitRank(&cm->comm, nranks, uid, rank);
-  if (rc != 0) return fail(c, DSH_ERR_HIP, std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error"));
+  if (rc != 0) return dsh_fail(c, DSH_ERR_HIP, std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error"));
   *out = cm.release();
   return DSH_OK;
 }
@@ -1192,13 +1125,13 @@ int dsh_comm_destroy(dsh_comm* cm) {
 }
 
 int dsh_sft_shared_solve(dsh_ctx* c, dsh_comm* cm, const dsh_sft_frame* frame, dsh_sft_result* result) {
-  if (!c || !cm || !frame || !result || cm->ctx != c) return fail(c, DSH_ERR_ARG, "dsh_sft_shared_solve: bad argument");
+  if (!c || !cm || !frame || !result || cm->ctx != c) return dsh_fail(c, DSH_ERR_ARG, "dsh_sft_shared_solve: bad argument");
   std::vector<ScRank> R{ScRank{c}};
   ScReducer red;
   red.comm = cm;
   std::string err;
   const int rc = sc_solve(R, red, cm->rank, cm->nranks, frame, result, err);
-  return rc == DSH_OK ? rc : fail(c, rc, "dsh_sft_shared_solve: " + err);
+  return rc == DSH_OK ? rc : dsh_fail(c, rc, "dsh_sft_shared_solve: " + err);
 }
 
 int dsh_sft_shared_solve_group(int G, dsh_ctx* const* ctxs, const dsh_sft_frame* frames, dsh_sft_result* results) {
@@ -1209,21 +1142,21 @@ int dsh_sft_shared_solve_group(int G, dsh_ctx* const* ctxs, const dsh_sft_frame*
   std::vector<ScRank> R;
   for (int g = 0; g < G; g++) R.push_back(ScRank{ctxs[g]});
   for (int g = 0; g < G; g++) {   // the state blocks must exist before their addresses are collected
-    if (ctxs[g]->host_only) return fail(c0, DSH_ERR_NO_DEVICE, "dsh_sft_shared_solve_group: host-only context, no GPU (there is no CPU fallback)");
+    if (ctxs[g]->host_only) return dsh_fail(c0, DSH_ERR_NO_DEVICE, "dsh_sft_shared_solve_group: host-only context, no GPU (there is no CPU fallback)");
     (void)hipSetDevice(ctxs[g]->device);
-    if (!ctxs[g]->d_sc && hipMalloc((void**)&ctxs[g]->d_sc, sizeof(SftSc)) != hipSuccess) return fail(c0, DSH_ERR_HIP, "dsh_sft_shared_solve_group: out of device memory");
+    if (!ctxs[g]->d_sc && hipMalloc((void**)&ctxs[g]->d_sc, sizeof(SftSc)) != hipSuccess) return dsh_fail(c0, DSH_ERR_HIP, "dsh_sft_shared_solve_group: out of device memory");
   }
   std::vector<SftSc*> ptrs;
   for (int g = 0; g < G; g++) ptrs.push_back(ctxs[g]->d_sc);
   ScReducer red;
   (void)hipSetDevice(c0->device);
-  if (hipMalloc((void**)&red.d_ptrs, sizeof(SftSc*) * G) != hipSuccess) return fail(c0, DSH_ERR_HIP, "dsh_sft_shared_solve_group: out of device memory");
+  if (hipMalloc((void**)&red.d_ptrs, sizeof(SftSc*) * G) != hipSuccess) return dsh_fail(c0, DSH_ERR_HIP, "dsh_sft_shared_solve_group: out of device memory");
   int rc = DSH_OK;
   std::string err;
   if (hipMemcpy(red.d_ptrs, ptrs.data(), sizeof(SftSc*) * G, hipMemcpyHostToDevice) != hipSuccess) { rc = DSH_ERR_HIP; err = "pointer table upload failed"; }
   if (rc == DSH_OK) rc = sc_solve(R, red, 0, G, frames, results, err);
   (void)hipFree(red.d_ptrs);
-  return rc == DSH_OK ? rc : fail(c0, rc, "dsh_sft_shared_solve_group: " + err);
+  return rc == DSH_OK ? rc : dsh_fail(c0, rc, "dsh_sft_shared_solve_group: " + err);
 }
 
 
@@ -1334,12 +1267,12 @@ int cn_solve(std::vector<ScRank>& R, dsh_comm* comm, int rank0, const dsh_sft_fr
 }  // namespace
 
 int dsh_sft_connected_solve(dsh_ctx* c, dsh_comm* cm, const dsh_sft_frame* frame, dsh_sft_result* result) {
-  if (!c || !cm || !frame || !result || cm->ctx != c) return fail(c, DSH_ERR_ARG, "dsh_sft_connected_solve: bad argument");
-  if (cm->nranks != 2) return fail(c, DSH_ERR_ARG, "dsh_sft_connected_solve: the cut has two parts: the communicator must have exactly two ranks");
+  if (!c || !cm || !frame || !result || cm->ctx != c) return dsh_fail(c, DSH_ERR_ARG, "dsh_sft_connected_solve: bad argument");
+  if (cm->nranks != 2) return dsh_fail(c, DSH_ERR_ARG, "dsh_sft_connected_solve: the cut has two parts: the communicator must have exactly two ranks");
   std::vector<ScRank> R{ScRank{c}};
   std::string err;
   const int rc = cn_solve(R, cm, cm->rank, frame, result, err);
-  return rc == DSH_OK ? rc : fail(c, rc, "dsh_sft_connected_solve: " + err);
+  return rc == DSH_OK ? rc : dsh_fail(c, rc, "dsh_sft_connected_solve: " + err);
 }
 
 int dsh_sft_connected_solve_group(dsh_ctx* c0, dsh_ctx* c1, const dsh_sft_frame* frame, dsh_sft_result* results) {
@@ -1347,7 +1280,7 @@ int dsh_sft_connected_solve_group(dsh_ctx* c0, dsh_ctx* c1, const dsh_sft_frame*
   std::vector<ScRank> R{ScRank{c0}, ScRank{c1}};
   std::string err;
   const int rc = cn_solve(R, nullptr, 0, frame, results, err);
-  return rc == DSH_OK ? rc : fail(c0, rc, "dsh_sft_connected_solve_group: " + err);
+  return rc == DSH_OK ? rc : dsh_fail(c0, rc, "dsh_sft_connected_solve_group: " + err);
 }
 
 #ifdef DSH_LAB
@@ -1363,33 +1296,32 @@ struct EventPair {   // destroyed on every path
 int dsh_lab_set_option(dsh_ctx* c, const char* name, int value) {
   if (!c || !name) return DSH_ERR_ARG;
   const std::string k(name);
-  if (k == "waves") { if (value != 0 && value != 4 && value != 8) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: waves is 0 (automatic), 4 or 8"); c->opt.waves = value; }
+  if (k == "waves") { if (value != 0 && value != 4 && value != 8) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: waves is 0 (automatic), 4 or 8"); c->opt.waves = value; }
   else if (k == "dataflow") c->opt.dataflow = value != 0;
   else if (k == "wide_off") c->opt.wide_off = value != 0;
   else if (k == "rounds") c->opt.rounds = value != 0;
-  else if (k == "streams") { if (value < 0 || value > dsh_ctx::kMaxSub) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: streams is 0 (automatic) or 1..4 sub-batches"); c->opt.streams = value; }
-  else if (k == "split") { if (value < 0 || value > 2) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: split is 0 (off), 1 (wide bands only) or 2 (every band long enough)"); c->opt.split = value; }
-  else if (k == "helpers_wbt") { if (value < 1 || value > 16) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: helpers_wbt is 1..16 (tiles of half-bandwidth from which parts get helper workgroups)"); c->opt.helpers_wbt = value; }
-  else if (k == "owner_waves") { if (value != 8 && value != 16) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: owner_waves is 8 or 16 (wavefronts of a FACTOR workgroup with helpers)"); c->opt.owner_waves = value; }
-  else if (k == "helpers") { if (value < -1 || value > 3) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: helpers is -1 (automatic) or 0..3 workgroups per part"); c->opt.helpers = value; }
-  else if (k == "tail") { if (value < -1 || value > 8) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: tail is -1 (automatic), 0 (rounds to the end) or the number of problems per CU from which downwards the last problems go to the tail kernel"); c->opt.tail = value; }
-  else if (k == "speculate") { if (value < 0 || value > SFT_SPEC_MAXK) return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: speculate is 0 (automatic) or 1..4 lanes"); c->opt.speculate = value; }
-  else return fail(c, DSH_ERR_ARG, "dsh_lab_set_option: unknown option " + k);
+  else if (k == "streams") { if (value < 0 || value > dsh_ctx::kMaxSub) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: streams is 0 (automatic) or 1..4 sub-batches"); c->opt.streams = value; }
+  else if (k == "split") { if (value < 0 || value > 2) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: split is 0 (off), 1 (wide bands only) or 2 (every band long enough)"); c->opt.split = value; }
+  else if (k == "helpers_wbt") { if (value < 1 || value > 16) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: helpers_wbt is 1..16 (tiles of half-bandwidth from which parts get helper workgroups)"); c->opt.helpers_wbt = value; }
+  else if (k == "owner_waves") { if (value != 8 && value != 16) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: owner_waves is 8 or 16 (wavefronts of a FACTOR workgroup with helpers)"); c->opt.owner_waves = value; }
+  else if (k == "helpers") { if (value < -1 || value > 3) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: helpers is -1 (automatic) or 0..3 workgroups per part"); c->opt.helpers = value; }
+  else if (k == "tail") { if (value < -1 || value > 8) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: tail is -1 (automatic), 0 (rounds to the end) or the number of problems per CU from which downwards the last problems go to the tail kernel"); c->opt.tail = value; }
+  else if (k == "speculate") { if (value < 0 || value > SFT_SPEC_MAXK) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: speculate is 0 (automatic) or 1..4 lanes"); c->opt.speculate = value; }
+  else return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_set_option: unknown option " + k);
   return DSH_OK;
 }
 
 int dsh_lab_sft_solver_info(dsh_ctx* c, int b, int32_t* out8) {
-  if (!c || !out8 || b < 0 || b >= c->B) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_solver_info: bad argument");
+  if (!c || !out8 || b < 0 || b >= c->B) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_solver_info: bad argument");
   const SftDev& h = c->h_probs[b];
   out8[0] = h.split; out8[1] = h.sp_c0; out8[2] = h.sp_s; out8[3] = h.sp_n1p; out8[4] = h.sp_pad; out8[5] = c->spec_k; out8[6] = h.tile_mode; out8[7] = c->nw;
   return DSH_OK;
 }
 
 int dsh_lab_sft_run_timed(dsh_ctx* c, int launches, double* total_ms) {
-  if (!c || launches <= 0 || !total_ms) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_run_timed: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_run_timed: host-only context, no GPU (there is no CPU fallback)");
-  if (c->B <= 0) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_run_timed: nothing uploaded");
-  (void)hipSetDevice(c->device);
+  if (!c || launches <= 0 || !total_ms) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_run_timed: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_run_timed")) return rc;
+  if (c->B <= 0) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_run_timed: nothing uploaded");
   EventPair ev;
   HIPCHK(c, ev.create());
   HIPCHK(c, hipEventRecord(ev.e0, c->stream));
@@ -1404,10 +1336,9 @@ int dsh_lab_sft_run_timed(dsh_ctx* c, int launches, double* total_ms) {
 }
 
 int dsh_lab_sft_assemble_timed(dsh_ctx* c, int launches, double* total_ms) {
-  if (!c || launches <= 0 || !total_ms) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_assemble_timed: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_assemble_timed: host-only context, no GPU (there is no CPU fallback)");
-  if (c->B <= 0 || !c->ran) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_assemble_timed: needs an uploaded batch that has run once");
-  (void)hipSetDevice(c->device);
+  if (!c || launches <= 0 || !total_ms) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_assemble_timed: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_assemble_timed")) return rc;
+  if (c->B <= 0 || !c->ran) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_assemble_timed: needs an uploaded batch that has run once");
   EventPair ev;
   HIPCHK(c, ev.create());
   HIPCHK(c, hipEventRecord(ev.e0, c->stream));
@@ -1422,12 +1353,11 @@ int dsh_lab_sft_assemble_timed(dsh_ctx* c, int launches, double* total_ms) {
 }
 
 int dsh_lab_sft_wave_check(dsh_ctx* c, double rel, int launches, int only, double* x_ref, double* x_new, int32_t* ok2, double* ms2) {
-  if (!c || launches <= 0 || !ms2) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_wave_check: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_wave_check: host-only context, no GPU (there is no CPU fallback)");
-  if (c->B <= 0 || !c->ran) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_wave_check: needs an uploaded batch that has run once");
+  if (!c || launches <= 0 || !ms2) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_wave_check: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_wave_check")) return rc;
+  if (c->B <= 0 || !c->ran) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_wave_check: needs an uploaded batch that has run once");
   for (int b = 0; b < c->B; b++)
-    if (c->h_probs[b].tile_mode != 1) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_wave_check: register-window problems (half-bandwidth <= 128) only");
-  (void)hipSetDevice(c->device);
+    if (c->h_probs[b].tile_mode != 1) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_wave_check: register-window problems (half-bandwidth <= 128) only");
   HIPCHK(c, sft_assembly_launch(c->d_probs, c->B, c->max_kd, c->jl_doubles, c->rounds_mode ? 8 : c->nw, c->stream));   // H of the initial state
   EventPair ev;
   HIPCHK(c, ev.create());
@@ -1456,15 +1386,14 @@ int dsh_lab_sft_wave_check(dsh_ctx* c, double rel, int launches, int only, doubl
 }
 
 int dsh_lab_sft_factor_check(dsh_ctx* c, const double* lambda, const uint8_t* factor, int grid, double* x, int32_t* ok) {
-  if (!c || !lambda || grid < 0) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_factor_check: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_factor_check: host-only context, no GPU (there is no CPU fallback)");
-  if (c->B <= 0 || !c->ran) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_factor_check: needs an uploaded batch that has run once");
+  if (!c || !lambda || grid < 0) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_factor_check: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_factor_check")) return rc;
+  if (c->B <= 0 || !c->ran) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_factor_check: needs an uploaded batch that has run once");
   for (int b = 0; b < c->B; b++)
-    if (c->h_probs[b].tile_mode != 1) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_factor_check: register-window problems (half-bandwidth <= 128) only");
-  (void)hipSetDevice(c->device);
+    if (c->h_probs[b].tile_mode != 1) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_factor_check: register-window problems (half-bandwidth <= 128) only");
   const int B = c->B;
   // run records and counters of its own: the batch need not be in the throughput shape (the records of the rounds exist only there)
-  struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } } runs, counters;
+  struct OwnedDevBuf { void* p = nullptr; ~OwnedDevBuf() { if (p) (void)hipFree(p); } } runs, counters;
   HIPCHK(c, hipMalloc(&runs.p, sizeof(SftRun) * (size_t)B));
   HIPCHK(c, hipMalloc(&counters.p, 16 * sizeof(int)));
   std::vector<SftRun> h_runs(B);
@@ -1494,10 +1423,9 @@ int dsh_lab_sft_factor_check(dsh_ctx* c, const double* lambda, const uint8_t* fa
 }
 
 int dsh_lab_sft_rounds_timed(dsh_ctx* c, double* ms4, int32_t* rounds) {
-  if (!c || !ms4) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_rounds_timed: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_rounds_timed: host-only context, no GPU (there is no CPU fallback)");
-  if (c->B <= 0 || !c->rounds_mode) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_rounds_timed: needs an uploaded batch that runs as rounds of phase kernels");
-  (void)hipSetDevice(c->device);
+  if (!c || !ms4) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_rounds_timed: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_rounds_timed")) return rc;
+  if (c->B <= 0 || !c->rounds_mode) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_rounds_timed: needs an uploaded batch that runs as rounds of phase kernels");
   std::vector<hipEvent_t> ev;
   c->phase_events = &ev;
   c->phase_ids.clear();
@@ -1522,26 +1450,24 @@ int dsh_lab_sft_rounds_timed(dsh_ctx* c, double* ms4, int32_t* rounds) {
 }
 
 int dsh_lab_sft_dump(dsh_ctx* c, int b, int what, int64_t n, double* out) {
-  if (!c || !out || b < 0 || b >= c->B || n <= 0) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_dump: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_dump: host-only context");
+  if (!c || !out || b < 0 || b >= c->B || n <= 0) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_dump: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_dump")) return rc;
   const SftDev& h = c->h_probs[b];
   const double* src = what == 0 ? h.Lb : what == 1 ? h.Linv : what == 2 ? h.Lbord : what == 3 ? h.Hc : what == 4 ? h.Hbord : what == 5 ? h.x : what == 6 ? h.Hcorner :
                       (what == 8 || what == 9) ? (const double*)h.part[what - 8].sync : h.dbg;   // 8, 9: the helper statistics of part 0 / 1 (int32 words)
-  if (!src) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_dump: the problem has no such buffer");
-  (void)hipSetDevice(c->device);
+  if (!src) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_dump: the problem has no such buffer");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, src, 8 * (size_t)n, hipMemcpyDeviceToHost));
   return DSH_OK;
 }
 
 int dsh_lab_sft_phase_ms(dsh_ctx* c, int b, double* out8) {
-  if (!c || !out8 || b < 0 || b >= c->B) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_phase_ms: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_phase_ms: host-only context");
-  if (!c->ran) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_phase_ms: no run");
+  if (!c || !out8 || b < 0 || b >= c->B) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_phase_ms: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_phase_ms")) return rc;
+  if (!c->ran) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_phase_ms: no run");
 #ifndef SFT_PHASE_TIMERS
-  return fail(c, DSH_ERR_STATE, "dsh_lab_sft_phase_ms: this build has no phase timers (make lab EXTRA=-DSFT_PHASE_TIMERS)");
+  return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_phase_ms: this build has no phase timers (make lab EXTRA=-DSFT_PHASE_TIMERS)");
 #else
-  (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out8, c->h_probs[b].dbg, 8 * sizeof(double), hipMemcpyDeviceToHost));
   for (int i = 0; i < 8; i++) out8[i] *= 1e-5;  // 100 MHz ticks -> ms
@@ -1556,13 +1482,12 @@ int dsh_lab_sft_phase_ms(dsh_ctx* c, int b, double* out8) {
 }
 
 int dsh_lab_sft_step_trace(dsh_ctx* c, int b, double* out64) {
-  if (!c || !out64 || b < 0 || b >= c->B) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_step_trace: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_step_trace: host-only context");
-  if (!c->ran) return fail(c, DSH_ERR_STATE, "dsh_lab_sft_step_trace: no run");
+  if (!c || !out64 || b < 0 || b >= c->B) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_step_trace: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_step_trace")) return rc;
+  if (!c->ran) return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_step_trace: no run");
 #ifndef SFT_STEP_TRACE
-  return fail(c, DSH_ERR_STATE, "dsh_lab_sft_step_trace: this build has no step trace (make lab EXTRA=-DSFT_STEP_TRACE)");
+  return dsh_fail(c, DSH_ERR_STATE, "dsh_lab_sft_step_trace: this build has no step trace (make lab EXTRA=-DSFT_STEP_TRACE)");
 #else
-  (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out64, c->h_probs[b].dbg + 16, 64 * sizeof(double), hipMemcpyDeviceToHost));
   return DSH_OK;
@@ -1570,12 +1495,11 @@ int dsh_lab_sft_step_trace(dsh_ctx* c, int b, double* out64) {
 }
 
 int dsh_lab_sft_system(dsh_ctx* c, int b, int32_t D, double* H, double* bvec, double* chi2) {
-  if (!c || b < 0 || b >= c->B) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_system: bad argument");
-  if (c->host_only) return fail(c, DSH_ERR_NO_DEVICE, "dsh_lab_sft_system: host-only context");
-  (void)hipSetDevice(c->device);
+  if (!c || b < 0 || b >= c->B) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_system: bad argument");
+  if (const int rc = dsh_enter(c, "dsh_lab_sft_system")) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));   // an asynchronous run may still be using the problem table
   SftDev h = c->h_probs[b];
-  if (D != 6 + h.Dn) return fail(c, DSH_ERR_ARG, "dsh_lab_sft_system: D mismatch");
+  if (D != 6 + h.Dn) return dsh_fail(c, DSH_ERR_ARG, "dsh_lab_sft_system: D mismatch");
   // flip the mode of this one problem, run it alone, restore
   const int32_t mode_saved = h.mode, split_saved = h.split;
   h.mode = 1;

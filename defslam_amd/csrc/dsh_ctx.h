@@ -1,17 +1,16 @@
-// Internal definition of the opaque dsh_ctx (shared by the translation units of libdefslam_hip.so).
+// Internal definition of the opaque dsh_ctx (shared by the translation units of libdefslam_hip.so) and the host-side plumbing every
+// C ABI module uses: error reporting (dsh_fail, HIPCHK), the device gate (dsh_enter), scratch slices (DevBuf), block layout (Arena),
+// page-locked host buffers (HostBuf) and the life cycle of the device-resident stores (dsh_store).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdlib>
 #include <string>
 #include <utility>
 #include <vector>
 
-#include "dsh_template.h"
-#include "sft_problem.h"
-
-namespace dsh {
-struct PackedSft;   // defined in dsh_api.cpp
-}
+#include "../../include/defslam_hip.h"
 
 // Grow-only device scratch of a context: the one-shot calls (BBS, normals, Schwarp) carve their temporaries out of it
 // instead of paying a dozen hipMalloc/hipFree per call.  reset() at the start of a call, release() in dsh_destroy.
@@ -46,37 +45,133 @@ struct dsh_scratch {
   }
 };
 
-// Page-locked host buffer for the one-copy-in / one-copy-out calls (grow-only; plain memory for a host-only context).
-struct dsh_pinned {
+// Host buffer of a context that the copy engine reads / writes directly: page-locked for a GPU context (hipMemcpyAsync
+// from pageable memory is staged and synchronous), plain memory for a host-only one.  Grow-only.
+struct HostBuf {
   char* p = nullptr;
   size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
+  bool pinned = false;
+  hipError_t ensure(size_t bytes, bool want_pinned) {
     if (bytes <= cap) return hipSuccess;
     release();
     const size_t want = bytes + bytes / 4 + 4096;
-    const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
-    if (e != hipSuccess) { p = nullptr; return e; }
+    if (want_pinned) {
+      const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
+      if (e != hipSuccess) { p = nullptr; return e; }
+      pinned = true;
+    } else {
+      p = static_cast<char*>(std::malloc(want));
+      if (!p) return hipErrorOutOfMemory;
+      pinned = false;
+    }
     cap = want;
     return hipSuccess;
   }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+  void release() {
+    if (p) { if (pinned) (void)hipHostFree(p); else std::free(p); }
+    p = nullptr; cap = 0;
+  }
 };
+
+// Byte layout of a block that moves in one copy (or one device allocation): 256-byte aligned slices.
+struct Arena {
+  size_t size = 0;
+  static size_t round(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+  size_t take(size_t bytes) {
+    const size_t off = size;
+    size += round(bytes);
+    return off;
+  }
+};
+
+struct dsh_store;
 
 struct dsh_ctx_base {
   dsh_scratch scratch;
-  dsh_pinned pin_in, pin_out;
+  HostBuf pin_in, pin_out;   // one-copy-in / one-copy-out blocks (Schwarp fits, tracking searches, map point update)
   int device = 0;
   bool host_only = false;   // device == -1: template + packer only (CPU tests of the host logic)
   hipStream_t stream = nullptr;
   std::string err;
-  std::vector<struct dsh_diffdb*> diffdbs;   // databases created on this context: dsh_destroy detaches them (dsh_diffdb.cpp: ddb_detach_all)
-  std::vector<struct dsh_kfdb*> kfdbs;       // keyframe stores likewise (dsh_mappoint.cpp: kfdb_detach_all)
+  std::vector<dsh_store*> stores;   // device-resident stores created on this context: dsh_destroy detaches them (dsh_detach_stores)
 };
-void ddb_detach_all(dsh_ctx_base* c);
-void kfdb_detach_all(dsh_ctx_base* c);
+dsh_ctx_base* dsh_base(dsh_ctx* ctx);   // the opaque handle of the ABI as its base (dsh_api.cpp, where dsh_ctx is complete)
+
+// What the device-resident stores (dsh_diffdb, dsh_kfdb) share: the owning context and the device of their allocations.  A store works
+// in either order with dsh_destroy of its context: dsh_destroy detaches it (every call on it but its destroy then returns DSH_ERR_ARG),
+// and destroying it needs nothing of the context.
+struct dsh_store {
+  dsh_ctx_base* ctx = nullptr;   // the owning context; null after dsh_destroy of that context
+  int device = 0;                // HIP device of the allocations
+};
+inline void dsh_attach_store(dsh_ctx_base* c, dsh_store* s) {
+  s->ctx = c;
+  s->device = c->device;
+  c->stores.push_back(s);
+}
+inline void dsh_detach_stores(dsh_ctx_base* c) {
+  for (dsh_store* s : c->stores) s->ctx = nullptr;
+  c->stores.clear();
+}
+// First half of a store's destroy: wait for the whole device (the context's stream may be gone), unregister.  The store frees its arrays.
+inline void dsh_store_unregister(dsh_store* s) {
+  (void)hipSetDevice(s->device);
+  (void)hipDeviceSynchronize();
+  if (s->ctx) {
+    auto& v = s->ctx->stores;
+    v.erase(std::remove(v.begin(), v.end(), s), v.end());
+  }
+}
+// Grow-by-copy of a store's device allocation *p: a new allocation of `bytes`, then -- with nothing of the device still reading or
+// writing the old one -- copy(new) moves the stored part device to device, and the old allocation is freed.  *p is unchanged on failure.
+template <class Copy>
+hipError_t dsh_store_grow(void** p, size_t bytes, Copy copy) {
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess) return e;
+  (void)hipDeviceSynchronize();
+  e = copy(static_cast<char*>(q));
+  if (e != hipSuccess) { (void)hipFree(q); return e; }
+  if (*p) (void)hipFree(*p);
+  *p = q;
+  return hipSuccess;
+}
 
 // error helper usable from every translation unit
 inline int dsh_fail(dsh_ctx_base* c, int code, const std::string& m) {
   if (c) c->err = m;
   return code;
 }
+
+// A failed HIP call: drain the context's stream first (copies from local host buffers may still be in flight), then DSH_ERR_HIP.
+inline int dsh_fail_hip(dsh_ctx_base* c, hipError_t e, const char* call) {
+  if (c && !c->host_only && c->stream) (void)hipStreamSynchronize(c->stream);
+  return dsh_fail(c, DSH_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
+}
+#define HIPCHK(c, call)                                           \
+  do {                                                            \
+    const hipError_t e__ = (call);                                \
+    if (e__ != hipSuccess) return dsh_fail_hip(c, e__, #call);    \
+  } while (0)
+
+// The gate of an entry point that needs the device; it sits where the entry point's host-only check belongs in its order of checks.
+// A host-only context is DSH_ERR_NO_DEVICE (there is no CPU fallback); then the context's device is made current and its scratch reset.
+inline int dsh_enter(dsh_ctx_base* c, const char* who) {
+  if (!c) return DSH_ERR_ARG;
+  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, std::string(who) + ": host-only context, no GPU (there is no CPU fallback)");
+  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, std::string(who) + ": hipSetDevice failed");
+  c->scratch.reset();   // temporaries of this call come out of the context's scratch
+  return DSH_OK;
+}
+
+// A slice of the context's scratch: nothing to free.
+struct DevBuf {
+  void* p = nullptr;
+  hipError_t alloc(dsh_ctx_base* c, size_t bytes) { return c->scratch.take(bytes, &p); }
+  template <class T> T* as() { return static_cast<T*>(p); }
+};
+
+namespace dsh {
+// Dense bending matrix of a B-spline (dsh_sfn.cpp; the warp initialisation of dsh_schwarp.cpp uses it too).
+void bbs_bending_dense(const dsh_bbs* b, double lambda, double* Bm);
+}  // namespace dsh

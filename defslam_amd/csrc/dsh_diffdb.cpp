@@ -11,40 +11,16 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
-
-extern "C" hipError_t ddb_group(long long, const int32_t*, int, const int32_t*, int, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, void*, int32_t*, hipStream_t);
-extern "C" hipError_t ddb_gather(int, const int32_t*, const float*, const int32_t*, const int32_t*, float*, int32_t*, int32_t*, hipStream_t);
-extern "C" size_t ddb_group_tmp_bytes(int);
-extern "C" hipError_t nrsfm_launch_normals(int, int, const int32_t*, const int32_t*, const float*, const uint8_t*, const float*, const uint8_t*, const float*,
-                                           const uint8_t*, const float*, double*, double*, double*, int32_t*, float*, float*, uint8_t*, int32_t*, hipStream_t);
-
-namespace {
-#define HIPCHK(c, call)                                                                                        \
-  do {                                                                                                         \
-    hipError_t e__ = (call);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      (void)hipStreamSynchronize((c)->stream);                                                                  \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                      \
-    }                                                                                                           \
-  } while (0)
-struct DevBuf {
-  void* p = nullptr;
-  hipError_t alloc(dsh_ctx_base* c, size_t bytes) { return c->scratch.take(bytes, &p); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
-}  // namespace
+#include "mapping_launch.h"
 
 extern "C" {
 
 int dsh_diffdb_create(dsh_ctx* ctx, int64_t capacity, dsh_diffdb** out) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c || !out || capacity <= 0 || capacity > (int64_t)1 << 30) return dsh_fail(c, DSH_ERR_ARG, "dsh_diffdb_create: bad argument");
   *out = nullptr;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_diffdb_create: host-only context, no GPU (there is no CPU fallback)");
-  (void)hipSetDevice(c->device);
+  if (const int rc = dsh_enter(c, "dsh_diffdb_create")) return rc;
   dsh_diffdb* db = new dsh_diffdb();
-  db->ctx = c;
-  db->device = c->device;
   db->cap = capacity;
   char* base = nullptr;
   const size_t bytes = (size_t)capacity * (72 + 12);
@@ -53,21 +29,14 @@ int dsh_diffdb_create(dsh_ctx* ctx, int64_t capacity, dsh_diffdb** out) {
   db->pid = reinterpret_cast<int32_t*>(base + (size_t)capacity * 72);
   db->tag = db->pid + capacity;
   db->idx2 = db->tag + capacity;
-  c->diffdbs.push_back(db);
+  dsh_attach_store(c, db);
   *out = db;
   return DSH_OK;
 }
 
-// Works in either order with dsh_destroy of the context: the database remembers its device, waits for the whole device (the context's
-// stream may be gone) and never dereferences a context that has been destroyed (dsh_destroy detaches its databases).
 int dsh_diffdb_destroy(dsh_diffdb* db) {
   if (!db) return DSH_ERR_ARG;
-  (void)hipSetDevice(db->device);
-  (void)hipDeviceSynchronize();
-  if (db->ctx) {
-    auto& v = db->ctx->diffdbs;
-    v.erase(std::remove(v.begin(), v.end(), db), v.end());
-  }
+  dsh_store_unregister(db);
   if (db->rec) (void)hipFree(db->rec);
   if (db->last_normals) (void)hipFree(db->last_normals);
   delete db;
@@ -76,33 +45,29 @@ int dsh_diffdb_destroy(dsh_diffdb* db) {
 
 }  // extern "C"
 
-void ddb_detach_all(dsh_ctx_base* c) {
-  for (dsh_diffdb* db : c->diffdbs) db->ctx = nullptr;
-  c->diffdbs.clear();
-}
-
 int ddb_reserve(dsh_diffdb* db, long long need) {
   if (need <= db->cap) return 0;
   if (need > (1ll << 30)) return (int)hipErrorOutOfMemory;
   const long long ncap = std::min<long long>(std::max(need, 2 * db->cap), 1ll << 30);
   (void)hipSetDevice(db->device);
-  char* base = nullptr;
-  hipError_t e = hipMalloc((void**)&base, (size_t)ncap * (72 + 12));
+  void* base = db->rec;
+  int32_t *pid = nullptr, *tag = nullptr, *idx2 = nullptr;
+  const hipError_t e = dsh_store_grow(&base, (size_t)ncap * (72 + 12), [&](char* q) {
+    pid = reinterpret_cast<int32_t*>(q + (size_t)ncap * 72);
+    tag = pid + ncap;
+    idx2 = tag + ncap;
+    const size_t n = (size_t)db->count;
+    hipError_t r = hipSuccess;
+    if (n) {
+      r = hipMemcpy(q, db->rec, 72 * n, hipMemcpyDeviceToDevice);
+      if (r == hipSuccess) r = hipMemcpy(pid, db->pid, 4 * n, hipMemcpyDeviceToDevice);
+      if (r == hipSuccess) r = hipMemcpy(tag, db->tag, 4 * n, hipMemcpyDeviceToDevice);
+      if (r == hipSuccess) r = hipMemcpy(idx2, db->idx2, 4 * n, hipMemcpyDeviceToDevice);
+    }
+    return r;
+  });
   if (e != hipSuccess) return (int)e;
-  float* rec = reinterpret_cast<float*>(base);
-  int32_t* pid = reinterpret_cast<int32_t*>(base + (size_t)ncap * 72);
-  int32_t *tag = pid + ncap, *idx2 = tag + ncap;
-  (void)hipDeviceSynchronize();   // nothing of this device may still read or write the old arrays
-  const size_t n = (size_t)db->count;
-  if (n) {
-    e = hipMemcpy(rec, db->rec, 72 * n, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pid, db->pid, 4 * n, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tag, db->tag, 4 * n, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(idx2, db->idx2, 4 * n, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { (void)hipFree(base); return (int)e; }
-  }
-  (void)hipFree(db->rec);
-  db->rec = rec; db->pid = pid; db->tag = tag; db->idx2 = idx2; db->cap = ncap;
+  db->rec = static_cast<float*>(base); db->pid = pid; db->tag = tag; db->idx2 = idx2; db->cap = ncap;
   return 0;
 }
 
@@ -142,16 +107,14 @@ int dsh_diffdb_append(dsh_diffdb* db, int n, const dsh_diffprop* recs, const int
 int dsh_normals_estimate_db(dsh_ctx* ctx, dsh_diffdb* db, int P, const int32_t* point_ids, const float* x0, const uint8_t* has_x0, const float* ref_uv,
                             double* k1k2, double* cov, int32_t* status, float* normal_ref, int32_t* iters, int32_t max_rec, int32_t* n_rec, int32_t* rec_point,
                             int32_t* rec_tag, int32_t* rec_idx2, float* normal_rec, uint8_t* rec_written) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_normals_estimate_db: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_normals_estimate_db")) return rc;
   if (!db || db->ctx != c || P < 0 || (P > 0 && (!point_ids || !x0 || !has_x0 || !ref_uv || !k1k2 || !status)) || max_rec < 0)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_normals_estimate_db: bad argument");
   if (n_rec) *n_rec = 0;
   db->last_P = db->last_R = 0;
   if (P == 0) return DSH_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_normals_estimate_db: hipSetDevice failed");
-  c->scratch.reset();
   hipStream_t st = c->stream;
   const long long n = db->count;
   const size_t nn = n > 0 ? (size_t)n : 1;

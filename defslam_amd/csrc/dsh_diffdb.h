@@ -2,10 +2,9 @@
 #pragma once
 #include <cstdint>
 
-struct dsh_ctx_base;
-struct dsh_diffdb {
-  dsh_ctx_base* ctx = nullptr;   // the owning context; set to null by dsh_destroy of that context (the database can then only be destroyed)
-  int device = 0;                // HIP device of the allocation: dsh_diffdb_destroy needs nothing else
+#include "dsh_ctx.h"
+
+struct dsh_diffdb : dsh_store {
   long long cap = 0, count = 0;
   int32_t max_pid = -1;          // largest point id stored so far (size of the lookup table of a grouping)
   float* rec = nullptr;          // cap x 18 float32: the DiffProp fields in the order of dsh_diffprop

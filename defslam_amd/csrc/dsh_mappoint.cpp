@@ -13,9 +13,7 @@
 #include "mappoint_problem.h"
 
 // The store: descriptor rows and camera centres on the device; what validation and the election lists need on the host.
-struct dsh_kfdb {
-  dsh_ctx_base* ctx = nullptr;   // the owning context; null after dsh_destroy of that context (the store can then only be destroyed)
-  int device = 0;
+struct dsh_kfdb : dsh_store {
   int32_t cap = 0, count = 0;    // keyframes
   long long row_cap = 0, rows = 0;
   MpuSlot* d_slots = nullptr;
@@ -31,51 +29,24 @@ struct dsh_kfdb {
 
 namespace {
 
-#define MPU_HIPCHK(c, call)                                                                                   \
-  do {                                                                                                        \
-    hipError_t e__ = (call);                                                                                  \
-    if (e__ != hipSuccess) {                                                                                  \
-      (void)hipStreamSynchronize((c)->stream);                                                                \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                     \
-    }                                                                                                         \
-  } while (0)
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // grow-on-demand device arrays: a new allocation of at least twice the capacity, the stored part copied device to device
 hipError_t grow(void** p, size_t used, size_t need_bytes) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, need_bytes);
-  if (e != hipSuccess) return e;
-  (void)hipDeviceSynchronize();   // nothing of this device may still read the old array
-  if (used) e = hipMemcpy(q, *p, used, hipMemcpyDeviceToDevice);
-  if (e != hipSuccess) { (void)hipFree(q); return e; }
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  return hipSuccess;
+  return dsh_store_grow(p, need_bytes, [&](char* q) { return used ? hipMemcpy(q, *p, used, hipMemcpyDeviceToDevice) : hipSuccess; });
 }
 
 int width_class(int M) { return M <= 8 ? 0 : M <= 16 ? 1 : M <= 32 ? 2 : 3; }
 
 }  // namespace
 
-void kfdb_detach_all(dsh_ctx_base* c) {
-  for (dsh_kfdb* db : c->kfdbs) db->ctx = nullptr;
-  c->kfdbs.clear();
-}
-
 extern "C" {
 
 int dsh_kfdb_create(dsh_ctx* ctx, int32_t capacity, dsh_kfdb** out) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (!out || capacity <= 0 || capacity > (1 << 24)) return dsh_fail(c, DSH_ERR_ARG, "dsh_kfdb_create: bad argument");
   *out = nullptr;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_kfdb_create: host-only context, no GPU (there is no CPU fallback)");
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_create: hipSetDevice failed");
+  if (const int rc = dsh_enter(c, "dsh_kfdb_create")) return rc;
   dsh_kfdb* db = new dsh_kfdb();
-  db->ctx = c;
-  db->device = c->device;
   db->row_cap = (long long)capacity * 1024;
   if (hipMalloc((void**)&db->d_slots, sizeof(MpuSlot) * (size_t)capacity) != hipSuccess ||
       hipMalloc((void**)&db->d_rows, 32 * (size_t)db->row_cap) != hipSuccess) {
@@ -84,19 +55,14 @@ int dsh_kfdb_create(dsh_ctx* ctx, int32_t capacity, dsh_kfdb** out) {
     return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_create: out of device memory");
   }
   db->cap = capacity;
-  c->kfdbs.push_back(db);
+  dsh_attach_store(c, db);
   *out = db;
   return DSH_OK;
 }
 
 int dsh_kfdb_destroy(dsh_kfdb* db) {
   if (!db) return DSH_ERR_ARG;
-  (void)hipSetDevice(db->device);
-  (void)hipDeviceSynchronize();
-  if (db->ctx) {
-    auto& v = db->ctx->kfdbs;
-    v.erase(std::remove(v.begin(), v.end(), db), v.end());
-  }
+  dsh_store_unregister(db);
   if (db->d_slots) (void)hipFree(db->d_slots);
   if (db->d_rows) (void)hipFree(db->d_rows);
   delete db;
@@ -150,9 +116,9 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
   s.Ow[0] = kf->Ow[0]; s.Ow[1] = kf->Ow[1]; s.Ow[2] = kf->Ow[2];
   s.row_off = (int32_t)db->rows;
   hipStream_t st = c->stream;
-  MPU_HIPCHK(c, hipMemcpyAsync(db->d_slots + db->count, &s, sizeof(s), hipMemcpyHostToDevice, st));
-  if (kf->N > 0) MPU_HIPCHK(c, hipMemcpyAsync(db->d_rows + 2 * db->rows, kf->desc, 32 * (size_t)kf->N, hipMemcpyHostToDevice, st));
-  MPU_HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipMemcpyAsync(db->d_slots + db->count, &s, sizeof(s), hipMemcpyHostToDevice, st));
+  if (kf->N > 0) HIPCHK(c, hipMemcpyAsync(db->d_rows + 2 * db->rows, kf->desc, 32 * (size_t)kf->N, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   dsh_kfdb::Kf h;
   h.row_off = db->rows;
   h.N = kf->N;
@@ -171,7 +137,7 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
 int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, const int32_t* obs_ptr, const int32_t* obs_kf,
                         const int32_t* obs_idx, const int32_t* ref_kf, int32_t what, uint8_t* desc, int32_t* best, float* normal,
                         float* max_distance, float* min_distance, int32_t* status) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, "dsh_mappoint_update: " + m); };
   // arguments that need no store
@@ -190,7 +156,7 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   const long long Mt = P > 0 ? obs_ptr[P] : 0;
   if (Mt > 0 && (!obs_kf || !obs_idx)) return bad("obs_kf or obs_idx is NULL");
   if (db && db->ctx != c) return bad("the store belongs to another context or was detached");
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_mappoint_update: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_mappoint_update")) return rc;
   if (!db) return bad("store is NULL");
 
   // arguments against the store; the election lists and the reference levels on the way
@@ -241,7 +207,6 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
     }
   }
   if (P == 0) return DSH_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_mappoint_update: hipSetDevice failed");
 
   // work lists: small points by width class; large points biggest first, each a normal block and its election row blocks
   std::vector<int32_t> small_order, large_pts;
@@ -271,13 +236,13 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   const size_t Met = el_row.size();
 
   // one host buffer, one copy up
-  const size_t o_pts = 0, o_oslot = align256(sizeof(MpuPoint) * P), o_el = o_oslot + align256(4 * (size_t)Mt),
-               o_small = o_el + align256(4 * Met), o_blk = o_small + align256(4 * small_order.size()),
-               o_lpts = o_blk + align256(4 * blocks.size()), up_bytes = o_lpts + align256(4 * (size_t)NL);
-  const size_t d_best = 0, d_desc = align256(4 * (size_t)P), d_nrm = d_desc + align256(32 * (size_t)P), d_dist = d_nrm + align256(12 * (size_t)P),
-               down_bytes = d_dist + align256(8 * (size_t)P);
-  MPU_HIPCHK(c, c->pin_in.ensure(up_bytes));
-  MPU_HIPCHK(c, c->pin_out.ensure(down_bytes));
+  Arena up, down;
+  const size_t o_pts = up.take(sizeof(MpuPoint) * P), o_oslot = up.take(4 * (size_t)Mt), o_el = up.take(4 * Met), o_small = up.take(4 * small_order.size()),
+               o_blk = up.take(4 * blocks.size()), o_lpts = up.take(4 * (size_t)NL), up_bytes = up.size;
+  const size_t d_best = down.take(4 * (size_t)P), d_desc = down.take(32 * (size_t)P), d_nrm = down.take(12 * (size_t)P), d_dist = down.take(8 * (size_t)P),
+               down_bytes = down.size;
+  HIPCHK(c, c->pin_in.ensure(up_bytes, true));
+  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
   char* h = c->pin_in.p;
   std::memcpy(h + o_pts, pts.data(), sizeof(MpuPoint) * P);
   if (Mt > 0) std::memcpy(h + o_oslot, obs_kf, 4 * (size_t)Mt);
@@ -286,14 +251,13 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   if (!blocks.empty()) std::memcpy(h + o_blk, blocks.data(), 4 * blocks.size());
   if (NL > 0) std::memcpy(h + o_lpts, large_pts.data(), 4 * (size_t)NL);
 
-  c->scratch.reset();
   hipStream_t st = c->stream;
   void *dup = nullptr, *ddown = nullptr, *dkey = nullptr;
-  MPU_HIPCHK(c, c->scratch.take(up_bytes, &dup));
-  MPU_HIPCHK(c, c->scratch.take(down_bytes, &ddown));
-  MPU_HIPCHK(c, c->scratch.take(4 * (size_t)P, &dkey));
-  MPU_HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
-  if (NL > 0) MPU_HIPCHK(c, hipMemsetAsync(dkey, 0xFF, 4 * (size_t)P, st));
+  HIPCHK(c, c->scratch.take(up_bytes, &dup));
+  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
+  HIPCHK(c, c->scratch.take(4 * (size_t)P, &dkey));
+  HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
+  if (NL > 0) HIPCHK(c, hipMemsetAsync(dkey, 0xFF, 4 * (size_t)P, st));
   char* du = static_cast<char*>(dup);
   char* dd = static_cast<char*>(ddown);
   MpuBufs b;
@@ -310,9 +274,9 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   b.desc = reinterpret_cast<uint4*>(dd + d_desc);
   b.normal = reinterpret_cast<float*>(dd + d_nrm);
   b.dist = reinterpret_cast<float*>(dd + d_dist);
-  MPU_HIPCHK(c, mpu_launch(b, small_off, NB, NL, st));
-  MPU_HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
-  MPU_HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, mpu_launch(b, small_off, NB, NL, st));
+  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
 
   // outputs: only what was asked for, only where the reference writes
   const char* o = c->pin_out.p;

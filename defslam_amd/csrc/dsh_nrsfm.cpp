@@ -8,39 +8,9 @@
 
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
-
-extern "C" hipError_t nrsfm_launch_bbs_eval(double, double, int, double, double, int, int, const double*, const double*, const double*, int, int, int, double*,
-                                            uint8_t*, hipStream_t);
-extern "C" hipError_t nrsfm_launch_bbs_coloc(double, double, int, double, double, int, const double*, const double*, int, int, int, int32_t*, double*,
-                                             int32_t*, hipStream_t);
-extern "C" hipError_t nrsfm_launch_normals(int, int, const int32_t*, const int32_t*, const float*, const uint8_t*, const float*, const uint8_t*, const float*,
-                                           const uint8_t*, const float*, double*, double*, double*, int32_t*, float*, float*, uint8_t*, int32_t*, hipStream_t);
+#include "mapping_launch.h"
 
 namespace {
-
-#define HIPCHK(c, call)                                                                                        \
-  do {                                                                                                         \
-    hipError_t e__ = (call);                                                                                   \
-    if (e__ != hipSuccess) {   /* copies from local host buffers may be in flight: drain the stream before they go away */    \
-      (void)hipStreamSynchronize((c)->stream);                                                                  \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                      \
-    }                                                                                                           \
-  } while (0)
-
-// scoped device buffer
-struct DevBuf {   // a slice of the context's scratch (dsh_ctx.h); nothing to free
-  void* p = nullptr;
-  hipError_t alloc(dsh_ctx_base* c, size_t bytes) { return c->scratch.take(bytes, &p); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-int gpu_ready(dsh_ctx_base* c, const char* who) {
-  if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, std::string(who) + ": host-only context, no GPU (there is no CPU fallback)");
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, std::string(who) + ": hipSetDevice failed");
-  c->scratch.reset();   // temporaries of this call come out of the context's scratch
-  return DSH_OK;
-}
 
 bool bbs_ok(const dsh_bbs* b) { return b && b->nptsu >= 4 && b->nptsv >= 4 && b->valdim >= 1 && b->umax > b->umin && b->vmax > b->vmin; }
 
@@ -49,8 +19,8 @@ bool bbs_ok(const dsh_bbs* b) { return b && b->nptsu >= 4 && b->nptsv >= 4 && b-
 extern "C" {
 
 int dsh_bbs_eval(dsh_ctx* ctx, const dsh_bbs* bbs, const double* ctrl, const double* u, const double* v, int n, int du, int dv, double* val, uint8_t* outside) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
-  int rc = gpu_ready(c, "dsh_bbs_eval");
+  dsh_ctx_base* c = dsh_base(ctx);
+  int rc = dsh_enter(c, "dsh_bbs_eval");
   if (rc != DSH_OK) return rc;
   if (!bbs_ok(bbs) || !ctrl || n < 0 || (n > 0 && (!u || !v || !val)) || du < 0 || du > 2 || dv < 0 || dv > 2) return dsh_fail(c, DSH_ERR_ARG, "dsh_bbs_eval: bad argument");
   if (n == 0) return DSH_OK;
@@ -70,8 +40,8 @@ int dsh_bbs_eval(dsh_ctx* ctx, const dsh_bbs* bbs, const double* ctrl, const dou
 }
 
 int dsh_bbs_coloc(dsh_ctx* ctx, const dsh_bbs* bbs, const double* u, const double* v, int n, int du, int dv, int32_t* cols, double* w, int32_t* n_outside) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
-  int rc = gpu_ready(c, "dsh_bbs_coloc");
+  dsh_ctx_base* c = dsh_base(ctx);
+  int rc = dsh_enter(c, "dsh_bbs_coloc");
   if (rc != DSH_OK) return rc;
   if (!bbs_ok(bbs) || n < 0 || (n > 0 && (!u || !v || !cols || !w)) || du < 0 || du > 2 || dv < 0 || dv > 2) return dsh_fail(c, DSH_ERR_ARG, "dsh_bbs_coloc: bad argument");
   if (n_outside) *n_outside = 0;
@@ -96,8 +66,8 @@ int dsh_bbs_coloc(dsh_ctx* ctx, const dsh_bbs* bbs, const double* u, const doubl
 int dsh_normals_estimate(dsh_ctx* ctx, int P, const int32_t* rec_ptr, const dsh_diffprop* recs, const uint8_t* rec_is_ref, const float* rec_first_normal,
                          const uint8_t* rec_has_first_normal, const float* x0, const uint8_t* has_x0, const float* ref_uv, double* k1k2, double* cov,
                          int32_t* status, float* normal_ref, float* normal_rec, uint8_t* rec_written, int32_t* iters) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
-  int rc = gpu_ready(c, "dsh_normals_estimate");
+  dsh_ctx_base* c = dsh_base(ctx);
+  int rc = dsh_enter(c, "dsh_normals_estimate");
   if (rc != DSH_OK) return rc;
   if (P < 0 || (P > 0 && (!rec_ptr || !x0 || !has_x0 || !ref_uv || !k1k2 || !status))) return dsh_fail(c, DSH_ERR_ARG, "dsh_normals_estimate: bad argument");
   if (P == 0) return DSH_OK;

@@ -11,20 +11,9 @@
 
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
-
-extern "C" hipError_t reg_scale_min_median(int, int, const float*, const float*, const double*, const int32_t*, const int64_t*, float*, double*, double*,
-                                           hipStream_t);
-extern "C" hipError_t reg_horn(int, const float*, const float*, const double*, double, double, double*, double*, hipStream_t);
+#include "mapping_launch.h"
 
 namespace {
-#define HIPCHK(c, call)                                                                                        \
-  do {                                                                                                         \
-    hipError_t e__ = (call);                                                                                   \
-    if (e__ != hipSuccess) {   /* copies from local host buffers may be in flight: drain the stream before they go away */    \
-      (void)hipStreamSynchronize((c)->stream);                                                                  \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                      \
-    }                                                                                                           \
-  } while (0)
 
 constexpr int kMaxPairs = 8000;   // the finishing kernel keeps two floats per pair in LDS
 
@@ -146,24 +135,17 @@ void compose(const double* sim3, const float* Twc, double* s22_out, float* Tcw) 
   Tcw[12] = Tcw[13] = Tcw[14] = 0.f;
   Tcw[15] = 1.f;
 }
-
-int enter(dsh_ctx_base* c, const char* what) {
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, std::string(what) + ": host-only context, no GPU (there is no CPU fallback)");
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, std::string(what) + ": hipSetDevice failed");
-  c->scratch.reset();
-  return DSH_OK;
-}
 }  // namespace
 
 extern "C" {
 
 int dsh_scale_min_median(dsh_ctx* ctx, int n, const float* pos_mono, const float* pos_stereo, const double* u, int64_t nu, float* scale,
                          int64_t* consumed, int32_t* status) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (n <= 0 || n > kMaxPairs || !pos_mono || !pos_stereo || nu < 0 || (nu > 0 && !u) || !scale || !status)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_scale_min_median: bad argument (1 <= n <= 8000)");
-  int rc = enter(c, "dsh_scale_min_median");
+  int rc = dsh_enter(c, "dsh_scale_min_median");
   if (rc != DSH_OK) return rc;
   Clouds d;
   rc = upload_clouds(c, n, pos_mono, pos_stereo, d);
@@ -173,10 +155,10 @@ int dsh_scale_min_median(dsh_ctx* ctx, int n, const float* pos_mono, const float
 
 int dsh_optimize_horn(dsh_ctx* ctx, int n, const float* pts1, const float* pts2, double* sim3, double chi, double huber, int32_t* acceptable,
                       double* info) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (n <= 0 || !pts1 || !pts2 || !sim3 || !acceptable || !(huber >= 0.0)) return dsh_fail(c, DSH_ERR_ARG, "dsh_optimize_horn: bad argument");
-  int rc = enter(c, "dsh_optimize_horn");
+  int rc = dsh_enter(c, "dsh_optimize_horn");
   if (rc != DSH_OK) return rc;
   Clouds d;
   rc = upload_clouds(c, n, pts1, pts2, d);
@@ -186,14 +168,14 @@ int dsh_optimize_horn(dsh_ctx* ctx, int n, const float* pts1, const float* pts2,
 
 int dsh_surface_register(dsh_ctx* ctx, int n, const float* cloud_surface, const float* cloud_map, const double* u, int64_t nu, const float* Twc,
                          double chi_limit, int check_chi, int32_t* registered, double* sim3, double* s22, float* Tcw_new, double* info) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (n < 0 || n > kMaxPairs || (n > 0 && (!cloud_surface || !cloud_map)) || nu < 0 || (nu > 0 && !u) || !Twc || !registered || !sim3 || !s22 || !Tcw_new)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_surface_register: bad argument (n <= 8000)");
   *registered = 0;
   if (info) std::memset(info, 0, 8 * sizeof(double));
   if (n < 15) return DSH_OK;   // SurfaceRegistration.cc:108-109
-  int rc = enter(c, "dsh_surface_register");
+  int rc = dsh_enter(c, "dsh_surface_register");
   if (rc != DSH_OK) return rc;
   Clouds d;
   rc = upload_clouds(c, n, cloud_surface, cloud_map, d);

@@ -12,44 +12,9 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
-
-extern "C" hipError_t ddb_append(int, const uint8_t*, const float*, const int32_t*, const int32_t*, const int32_t*, int32_t*, int32_t*, void*, size_t, long long, long long,
-                                 float*, int32_t*, int32_t*, int32_t*, hipStream_t);
-extern "C" size_t ddb_scan_tmp_bytes(int);
-
-extern "C" hipError_t nrsfm_swp_eval(double, double, int, double, double, int, int, double, double, double, const float*, const float*, const float*,
-                                     const double*, double*, double*, int, hipStream_t);
-extern "C" hipError_t nrsfm_swp_loss(int, int, const double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_swp_normal(int, int, int, double*, double*, const double*, const double*, double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_swp_colscale(int, const double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_swp_solve(int, const double*, const double*, double, double*, double*, double*, double*, int, int, hipStream_t);
-extern "C" int nrsfm_swp_solve_np(int);
-extern "C" hipError_t nrsfm_swp_step(int, const double*, const double*, const double*, const double*, double*, double*, hipStream_t);
-extern "C" size_t nrsfm_swp_fit_bytes();
-extern "C" void nrsfm_swp_fit_fill(void*, double, double, int, double, double, int, int, double, double, double, float, float, int, const float*, const float*, const float*,
-                                   double*, double*, double*, double*, double*, double*, double*, double*, double*, double*, double*, float*, uint8_t*, int32_t*, double*,
-                                   const double*, void*);
-extern "C" size_t nrsfm_swp_compact_bytes(int, int, int);
-extern "C" hipError_t nrsfm_swp_fit_batch(void*, int, int, int, int, int, hipStream_t);
-namespace dsh { void bbs_bending_dense(const dsh_bbs* b, double lambda, double* Bm); }
-extern "C" hipError_t nrsfm_swp_diffprop(double, double, int, double, double, int, int, const float*, const float*, const double*, float, float, float*,
-                                         uint8_t*, hipStream_t);
+#include "mapping_launch.h"
 
 namespace {
-#define HIPCHK(c, call)                                                                                        \
-  do {                                                                                                         \
-    hipError_t e__ = (call);                                                                                   \
-    if (e__ != hipSuccess) {   /* copies from local host buffers may be in flight: drain the stream before they go away */    \
-      (void)hipStreamSynchronize((c)->stream);                                                                  \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                      \
-    }                                                                                                           \
-  } while (0)
-
-struct DevBuf {   // a slice of the context's scratch (dsh_ctx.h); nothing to free
-  void* p = nullptr;
-  hipError_t alloc(dsh_ctx_base* c, size_t bytes) { return c->scratch.take(bytes, &p); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
 
 struct Fit {
   dsh_ctx_base* c;
@@ -107,11 +72,10 @@ extern "C" {
 
 int dsh_schwarp_eval(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, const float* invsig, double fx_slot, double fy_slot,
                      double lambda, const double* x, double* residuals, double* jacobian) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_schwarp_eval: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_schwarp_eval")) return rc;
   if (!args_ok(bbs, P, kp1, kp2, invsig, x) || !residuals) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_eval: bad argument");
-  (void)hipSetDevice(c->device);
   Fit f;
   int rc = setup(f, c, bbs, P, kp1, kp2, invsig, fx_slot, fy_slot, lambda, x);
   if (rc != DSH_OK) return rc;
@@ -130,9 +94,9 @@ int dsh_schwarp_eval(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, 
 // stores / db (both or neither): the DiffProp records of the matches that are kept go into the device-resident database instead of
 // (or besides) the host -- dsh_schwarp_fit_batch_store.
 static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_schwarp_store* stores, dsh_diffdb* db) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_schwarp_fit_batch: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_schwarp_fit_batch")) return rc;
   if (B <= 0 || !probs) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit_batch: bad argument");
   if (db && (db->ctx != c || !stores)) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit_batch_store: the database belongs to another context / no store descriptors");
   if (db) {   // room for every record this call can add, BEFORE anything is launched: a call stores all of its records or fails untouched
@@ -150,63 +114,61 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     if (db && !stores[b].point_id) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit_batch_store: point_id missing in problem " + std::to_string(b));
     maxP = std::max(maxP, q.P); maxN = std::max(maxN, q.bbs.nptsu * q.bbs.nptsv); max_it = std::max(max_it, q.max_iters);
   }
-  (void)hipSetDevice(c->device);
   hipStream_t st = c->stream;
-  c->scratch.reset();
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // ---- layout of the input block (host-staged) and of the output block
   const size_t fit_bytes = nrsfm_swp_fit_bytes();
-  size_t in_bytes = al(fit_bytes * (size_t)B), out_bytes = 0;
+  Arena in, out;
+  in.take(fit_bytes * (size_t)B);   // the fit descriptors
   int with_init = 0;
   struct Off { size_t kp1, kp2, isg, x0, cs, xo, diff, drop, info, costs, bend; };
   std::vector<Off> off(B);
   // x lives at the head of the output block (in/out): only that part is uploaded with the start values
-  for (int b = 0; b < B; b++) { off[b].xo = out_bytes; out_bytes += al(8 * 2 * (size_t)probs[b].bbs.nptsu * probs[b].bbs.nptsv); }
-  const size_t x_bytes = out_bytes;
+  for (int b = 0; b < B; b++) off[b].xo = out.take(8 * 2 * (size_t)probs[b].bbs.nptsu * probs[b].bbs.nptsv);
+  const size_t x_bytes = out.size;
   for (int b = 0; b < B; b++) {
     const dsh_schwarp_problem& q = probs[b];
     const size_t n2 = 2 * (size_t)q.bbs.nptsu * q.bbs.nptsv;
     Off& o = off[b];
-    o.kp1 = in_bytes; in_bytes += al(8 * (size_t)q.P);
-    o.kp2 = in_bytes; in_bytes += al(8 * (size_t)q.P);
-    o.isg = in_bytes; in_bytes += al(4 * (size_t)q.P);
-    o.cs = in_bytes; in_bytes += al(8 * n2);
+    o.kp1 = in.take(8 * (size_t)q.P);
+    o.kp2 = in.take(8 * (size_t)q.P);
+    o.isg = in.take(4 * (size_t)q.P);
+    o.cs = in.take(8 * n2);
     // bending matrix of the Warp::initialize stage: one per run of problems with the same grid and weight
     o.bend = 0;
     if (q.init_lambda > 0.0) {
       const bool same = b > 0 && probs[b - 1].init_lambda == q.init_lambda && std::memcmp(&probs[b - 1].bbs, &q.bbs, sizeof(dsh_bbs)) == 0 && off[b - 1].bend;
       if (same) o.bend = off[b - 1].bend;
-      else { o.bend = in_bytes; in_bytes += al(8 * (n2 / 2) * (n2 / 2)); }
+      else { o.bend = in.take(8 * (n2 / 2) * (n2 / 2)); }
       with_init = 1;
     }
-    o.diff = out_bytes; out_bytes += al(!db && q.diff ? 72 * (size_t)q.P : 0);     // store mode: records and flags live in one strided block (below)
-    o.drop = out_bytes; out_bytes += al(!db && q.drop ? (size_t)q.P : 0);
-    o.info = out_bytes; out_bytes += 256;
-    o.costs = out_bytes; out_bytes += 256;
+    o.diff = out.take(!db && q.diff ? 72 * (size_t)q.P : 0);     // store mode: records and flags live in one strided block (below)
+    o.drop = out.take(!db && q.drop ? (size_t)q.P : 0);
+    o.info = out.take(256);
+    o.costs = out.take(256);
   }
   // store mode: DiffProp records / drop flags / point ids / tags / second-keyframe indices of all fits, problem b at stride maxP
   DevBuf sdiff, sdrop, skeep, spos, stmp;
   const size_t nall = (size_t)B * maxP;
   size_t o_pid = 0, o_tag = 0, o_idx2 = 0;
   if (db) {
-    o_pid = in_bytes; in_bytes += al(4 * nall);
-    o_tag = in_bytes; in_bytes += al(4 * nall);
-    o_idx2 = in_bytes; in_bytes += al(4 * nall);
+    o_pid = in.take(4 * nall);
+    o_tag = in.take(4 * nall);
+    o_idx2 = in.take(4 * nall);
     HIPCHK(c, sdiff.alloc(c, 72 * nall)); HIPCHK(c, sdrop.alloc(c, nall)); HIPCHK(c, skeep.alloc(c, 4 * nall)); HIPCHK(c, spos.alloc(c, 4 * nall));
     HIPCHK(c, stmp.alloc(c, ddb_scan_tmp_bytes((int)nall)));
   }
   DevBuf din, dout;
-  HIPCHK(c, din.alloc(c, in_bytes)); HIPCHK(c, dout.alloc(c, out_bytes));
-  HIPCHK(c, c->pin_in.ensure(in_bytes + x_bytes)); HIPCHK(c, c->pin_out.ensure(out_bytes));
+  HIPCHK(c, din.alloc(c, in.size)); HIPCHK(c, dout.alloc(c, out.size));
+  HIPCHK(c, c->pin_in.ensure(in.size + x_bytes, true)); HIPCHK(c, c->pin_out.ensure(out.size, true));
   char* hin = c->pin_in.p;
-  char* hx = c->pin_in.p + in_bytes;   // start values of x, laid out like the head of the output block
+  char* hx = c->pin_in.p + in.size;   // start values of x, laid out like the head of the output block
   std::memset(hx, 0, x_bytes);
   char* dib = din.as<char>();
   char* dob = dout.as<char>();
   // what has to start at zero (scalars of the controller, the step vector) lies in one block: one memset for the whole batch
   DevBuf dzero;
   size_t zero_bytes = 0;
-  for (int b = 0; b < B; b++) zero_bytes += 128 + al(8 * 2 * (size_t)probs[b].bbs.nptsu * probs[b].bbs.nptsv);
+  for (int b = 0; b < B; b++) zero_bytes += 128 + Arena::round(8 * 2 * (size_t)probs[b].bbs.nptsu * probs[b].bbs.nptsv);
   HIPCHK(c, dzero.alloc(c, zero_bytes));
   HIPCHK(c, hipMemsetAsync(dzero.p, 0, zero_bytes, st));
   size_t zoff = 0;
@@ -225,7 +187,7 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     DevBuf xn, g, r, J, A, M, W, compact;
     double* scal = reinterpret_cast<double*>(dzero.as<char>() + zoff);
     double* dx = reinterpret_cast<double*>(dzero.as<char>() + zoff + 128);
-    zoff += 128 + al(8 * (size_t)n2);
+    zoff += 128 + Arena::round(8 * (size_t)n2);
     const size_t np = (size_t)nrsfm_swp_solve_np(n2);
     HIPCHK(c, xn.alloc(c, 8 * (size_t)n2)); HIPCHK(c, g.alloc(c, 8 * (size_t)n2)); HIPCHK(c, r.alloc(c, 8 * (size_t)m));
     // the dense (2P+4N) x 2N buffer only serves the Warp::initialize stage (its colocation matrix); the fit keeps its Jacobian structured
@@ -255,11 +217,11 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
         max_pid = std::max(max_pid, id);
       }
   }
-  HIPCHK(c, hipMemcpyAsync(dib, hin, in_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dib, hin, in.size, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(dob, hx, x_bytes, hipMemcpyHostToDevice, st));
-  if (out_bytes > x_bytes) HIPCHK(c, hipMemsetAsync(dob + x_bytes, 0, out_bytes - x_bytes, st));
+  if (out.size > x_bytes) HIPCHK(c, hipMemsetAsync(dob + x_bytes, 0, out.size - x_bytes, st));
   HIPCHK(c, nrsfm_swp_fit_batch(dib, B, maxP, maxN, max_it, with_init, st));
-  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, dob, out_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, dob, out.size, hipMemcpyDeviceToHost, st));
   std::vector<uint8_t> hdrop;
   std::vector<float> hdiff;
   int32_t added = 0;
@@ -306,13 +268,13 @@ extern "C" {
 int dsh_schwarp_fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs) { return fit_batch(ctx, B, probs, nullptr, nullptr); }
 
 int dsh_schwarp_fit_batch_store(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_schwarp_store* stores, dsh_diffdb* db) {
-  if (!db || !stores) return dsh_fail(reinterpret_cast<dsh_ctx_base*>(ctx), DSH_ERR_ARG, "dsh_schwarp_fit_batch_store: bad argument");
+  if (!db || !stores) return dsh_fail(dsh_base(ctx), DSH_ERR_ARG, "dsh_schwarp_fit_batch_store: bad argument");
   return fit_batch(ctx, B, probs, stores, db);
 }
 
 int dsh_schwarp_fit(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, const float* invsig, double fx_slot, double fy_slot,
                     double lambda, float fx, float fy, int max_iters, double* x, dsh_diffprop* diff, uint8_t* drop, int32_t* info, double* costs) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_schwarp_fit: host-only context, no GPU (there is no CPU fallback)");
   if (!args_ok(bbs, P, kp1, kp2, invsig, x) || max_iters < 0) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit: bad argument");

@@ -13,36 +13,9 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
-
-extern "C" hipError_t nrsfm_swp_normal(int, int, int, double*, double*, const double*, const double*, double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_swp_solve(int, const double*, const double*, double, double*, double*, double*, double*, int, int, hipStream_t);
-extern "C" hipError_t nrsfm_swp_resolve(int, const double*, const double*, const double*, double*, int, int, hipStream_t);
-extern "C" int nrsfm_swp_solve_np(int);
-extern "C" hipError_t nrsfm_sfn_rows(double, double, int, double, double, int, int, const double*, const double*, const float*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_sfn_residual(int, int, const double*, const double*, const double*, double, double*, hipStream_t);
-extern "C" hipError_t nrsfm_sfn_axpy(int, const double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_warp_coloc(double, double, int, double, double, int, int, const float*, const float*, double*, double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_mat_add(size_t, const double*, double*, hipStream_t);
-extern "C" hipError_t nrsfm_match_search(double, double, int, double, double, int, const double*, int, const float*, const uint32_t*, const float*, const float*, int, int,
-                                         int, const float*, const uint32_t*, const uint8_t*, float, int, int32_t*, int32_t*, hipStream_t);
-extern "C" hipError_t ddb_pick_normals(int, const int32_t*, const float*, const float*, float*, hipStream_t);
-extern "C" hipError_t nrsfm_sfn_points(double, double, int, double, double, int, const double*, int, const double*, const double*, float*, hipStream_t);
+#include "mapping_launch.h"
 
 namespace {
-#define HIPCHK(c, call)                                                                                        \
-  do {                                                                                                         \
-    hipError_t e__ = (call);                                                                                   \
-    if (e__ != hipSuccess) {   /* copies from local host buffers may be in flight: drain the stream before they go away */    \
-      (void)hipStreamSynchronize((c)->stream);                                                                  \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                      \
-    }                                                                                                           \
-  } while (0)
-
-struct DevBuf {   // a slice of the context's scratch (dsh_ctx.h); nothing to free
-  void* p = nullptr;
-  hipError_t alloc(dsh_ctx_base* c, size_t bytes) { return c->scratch.take(bytes, &p); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
 
 // int_0^1 b_p^(k) b_q^(k) dt for the four cubic B-spline pieces on a knot interval, k = 0, 1, 2: the three coefficient
 // tables of the reference's bending code are products of these numbers.
@@ -111,9 +84,9 @@ int dsh_bbs_bending(const dsh_bbs* bbs, double lambda, double* bending) {
 static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u, const double* v, const float* normals, const dsh_diffdb* ndb, const int32_t* sel,
                         double bending_weight, double mean_depth, int n_all, const double* u_all, const double* v_all, double* ctrl_raw, double* ctrl, float* pts,
                         int32_t* ok) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_sfn_estimate: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_sfn_estimate")) return rc;
   if (!bbs_ok(bbs) || n < 0 || n_all < 0 || (n > 0 && (!u || !v || (!normals && !(ndb && sel)))) || (n_all > 0 && (!u_all || !v_all || !pts)) || !ctrl || !ok)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_sfn_estimate: bad argument");
   if (ndb) {
@@ -125,8 +98,6 @@ static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u
   const int N = bbs->nptsu * bbs->nptsv;
   if (N > 512) return dsh_fail(c, DSH_ERR_ARG, "dsh_sfn_estimate: more than 512 control points (one-workgroup solve)");
   *ok = 0;
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_sfn_estimate: hipSetDevice failed");
-  c->scratch.reset();
   hipStream_t st = c->stream;
   const int m = 2 * n + N + 1, np = nrsfm_swp_solve_np(N);
   DevBuf dA, db, dr, dx, ddx, dG, dg, dM, dW, dones, dscal, du, dv, dn, dua, dva, dctrl, dpts;
@@ -204,22 +175,20 @@ int dsh_sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u, c
 
 int dsh_sfn_estimate_db(dsh_ctx* ctx, const dsh_bbs* bbs, const dsh_diffdb* db, int n, const int32_t* sel, const double* u, const double* v, double bending_weight,
                         double mean_depth, int n_all, const double* u_all, const double* v_all, double* ctrl_raw, double* ctrl, float* pts, int32_t* ok) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (!db || (n > 0 && !sel)) return dsh_fail(c, DSH_ERR_ARG, "dsh_sfn_estimate_db: bad argument");
   return sfn_estimate(ctx, bbs, n, u, v, nullptr, db, sel, bending_weight, mean_depth, n_all, u_all, v_all, ctrl_raw, ctrl, pts, ok);
 }
 
 int dsh_warp_initialize(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, double lambda, double* x, int32_t* ok) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_warp_initialize: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_warp_initialize")) return rc;
   if (!bbs_ok(bbs) || P <= 0 || !kp1 || !kp2 || !x || !ok) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: bad argument");
   const int N = bbs->nptsu * bbs->nptsv;
   if (N > 512) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: more than 512 control points (one-workgroup solve)");
   *ok = 0;
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_warp_initialize: hipSetDevice failed");
-  c->scratch.reset();
   hipStream_t st = c->stream;
   const int np = nrsfm_swp_solve_np(N);
   DevBuf dC, dr0, dr1, dG, dB, dg0, dg1, dM, dW, dx, dones, dscal, dk1, dk2;
@@ -257,16 +226,14 @@ int dsh_warp_initialize(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp
 int dsh_search_by_schwarp(dsh_ctx* ctx, const dsh_bbs* bbs, const double* x, int Q, const float* kp1, const uint8_t* desc1, const float* cam2,
                           const float* bounds2, int grid_cols, int grid_rows, int N2, const float* kp2, const uint8_t* desc2, const uint8_t* has_mp2,
                           float radius, int th_low, int32_t* match, int32_t* nmatches) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_search_by_schwarp: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_search_by_schwarp")) return rc;
   if (!bbs_ok(bbs) || !x || Q < 0 || N2 < 0 || (Q > 0 && (!kp1 || !desc1 || !match)) || (N2 > 0 && (!kp2 || !desc2 || !has_mp2)) || !cam2 || !bounds2 ||
       grid_cols <= 0 || grid_rows <= 0 || grid_cols * grid_rows > 8192 || !(bounds2[1] > bounds2[0]) || !(bounds2[3] > bounds2[2]) || th_low > 256)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_schwarp: bad argument");
   if (nmatches) *nmatches = 0;
   if (Q == 0) return DSH_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_search_by_schwarp: hipSetDevice failed");
-  c->scratch.reset();
   hipStream_t st = c->stream;
   const int N = bbs->nptsu * bbs->nptsv;
   DevBuf dx, dk1, dd1, dk2, dd2, dmp, dcell, dmatch;

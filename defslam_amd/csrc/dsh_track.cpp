@@ -11,17 +11,6 @@
 
 namespace {
 
-#define TRK_HIPCHK(c, call)                                                                                   \
-  do {                                                                                                        \
-    hipError_t e__ = (call);                                                                                  \
-    if (e__ != hipSuccess) {                                                                                  \
-      (void)hipStreamSynchronize((c)->stream);                                                                \
-      return dsh_fail(c, DSH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                     \
-    }                                                                                                         \
-  } while (0)
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 std::string frame_error(const dsh_track_frame& f) {
   if (!f.Tcw) return "Tcw is NULL";
   for (int k = 0; k < 4; k++)
@@ -43,7 +32,7 @@ std::string frame_error(const dsh_track_frame& f) {
 extern "C" {
 
 int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* problems) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (B < 0 || (B > 0 && !problems)) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: bad batch");
   // validation, sizes and offsets
@@ -70,20 +59,20 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   if (Qt > (1LL << 28) || Nt > (1LL << 28)) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: batch too large");
   for (int p = 0; p < B; p++) problems[p].nmatches = problems[p].rescans = 0;
   // arguments first, so that a host-only context reports bad ones too
-  if (c->host_only) return dsh_fail(c, DSH_ERR_NO_DEVICE, "dsh_search_by_projection: host-only context, no GPU (there is no CPU fallback)");
+  if (const int rc = dsh_enter(c, "dsh_search_by_projection")) return rc;
   if (B == 0) return DSH_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_search_by_projection: hipSetDevice failed");
 
   // one host buffer, one copy up: problem descriptors, key points, queries
-  const size_t o_prob = 0, o_kp = align256(sizeof(TrkProb) * B), o_km = o_kp + align256(8 * Nt), o_kd = o_km + align256(4 * Nt),
-               o_qpid = o_kd + align256(32 * Nt), o_qxyz = o_qpid + align256(4 * Qt), o_qnrm = o_qxyz + align256(12 * Qt),
-               o_qmaxd = o_qnrm + align256(12 * Qt), o_qmeta = o_qmaxd + align256(4 * Qt), o_qdesc = o_qmeta + align256(4 * Qt),
-               up_bytes = o_qdesc + align256(32 * Qt);
+  Arena up;
+  const size_t o_prob = up.take(sizeof(TrkProb) * B), o_kp = up.take(8 * Nt), o_km = up.take(4 * Nt), o_kd = up.take(32 * Nt), o_qpid = up.take(4 * Qt),
+               o_qxyz = up.take(12 * Qt), o_qnrm = up.take(12 * Qt), o_qmaxd = up.take(4 * Qt), o_qmeta = up.take(4 * Qt), o_qdesc = up.take(32 * Qt),
+               up_bytes = up.size;
   // downloads: match, level, in view, uv, view cos, per-problem counters
-  const size_t d_match = 0, d_level = align256(4 * Qt), d_inview = d_level + align256(4 * Qt), d_uv = d_inview + align256(4 * Qt),
-               d_vcos = d_uv + align256(8 * Qt), d_pstat = d_vcos + align256(4 * Qt), down_bytes = d_pstat + align256(16 * (size_t)B);
-  TRK_HIPCHK(c, c->pin_in.ensure(up_bytes));
-  TRK_HIPCHK(c, c->pin_out.ensure(down_bytes));
+  Arena down;
+  const size_t d_match = down.take(4 * Qt), d_level = down.take(4 * Qt), d_inview = down.take(4 * Qt), d_uv = down.take(8 * Qt), d_vcos = down.take(4 * Qt),
+               d_pstat = down.take(16 * (size_t)B), down_bytes = down.size;
+  HIPCHK(c, c->pin_in.ensure(up_bytes, true));
+  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
   char* h = c->pin_in.p;
   long long kp_off = 0, q_off = 0, cell_off = 0;
   for (int p = 0; p < B; p++) {
@@ -132,23 +121,22 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
     cell_off += (long long)f.grid_cols * f.grid_rows + 1;
   }
 
-  c->scratch.reset();
   hipStream_t st = c->stream;
   void *dup = nullptr, *dcell = nullptr, *dskp = nullptr, *dsmeta = nullptr, *dsdesc = nullptr, *dkeys = nullptr, *dncand = nullptr, *dwin = nullptr,
        *ddown = nullptr;
-  TRK_HIPCHK(c, c->scratch.take(up_bytes, &dup));
-  TRK_HIPCHK(c, c->scratch.take(4 * (size_t)Ct, &dcell));
-  TRK_HIPCHK(c, c->scratch.take(8 * (size_t)Nt, &dskp));
-  TRK_HIPCHK(c, c->scratch.take(4 * (size_t)Nt, &dsmeta));
-  TRK_HIPCHK(c, c->scratch.take(32 * (size_t)Nt, &dsdesc));
-  TRK_HIPCHK(c, c->scratch.take(8 * (size_t)TRK_K * Qt, &dkeys));
-  TRK_HIPCHK(c, c->scratch.take(4 * (size_t)Qt, &dncand));
-  TRK_HIPCHK(c, c->scratch.take(sizeof(TrkWin) * (size_t)Qt, &dwin));
-  TRK_HIPCHK(c, c->scratch.take(down_bytes, &ddown));
-  TRK_HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(c, c->scratch.take(up_bytes, &dup));
+  HIPCHK(c, c->scratch.take(4 * (size_t)Ct, &dcell));
+  HIPCHK(c, c->scratch.take(8 * (size_t)Nt, &dskp));
+  HIPCHK(c, c->scratch.take(4 * (size_t)Nt, &dsmeta));
+  HIPCHK(c, c->scratch.take(32 * (size_t)Nt, &dsdesc));
+  HIPCHK(c, c->scratch.take(8 * (size_t)TRK_K * Qt, &dkeys));
+  HIPCHK(c, c->scratch.take(4 * (size_t)Qt, &dncand));
+  HIPCHK(c, c->scratch.take(sizeof(TrkWin) * (size_t)Qt, &dwin));
+  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
+  HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
   char* du = static_cast<char*>(dup);
   char* dd = static_cast<char*>(ddown);
-  TRK_HIPCHK(c, hipMemsetAsync(dd + d_pstat, 0, 16 * (size_t)B, st));
+  HIPCHK(c, hipMemsetAsync(dd + d_pstat, 0, 16 * (size_t)B, st));
   TrkBufs b;
   b.prob = reinterpret_cast<const TrkProb*>(du + o_prob);
   b.kp = reinterpret_cast<const float2*>(du + o_kp);
@@ -173,9 +161,9 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   b.uv = reinterpret_cast<float*>(dd + d_uv);
   b.vcos = reinterpret_cast<float*>(dd + d_vcos);
   b.pstat = reinterpret_cast<int32_t*>(dd + d_pstat);
-  TRK_HIPCHK(c, trk_launch(b, B, (int)Qt, st));
-  TRK_HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
-  TRK_HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, trk_launch(b, B, (int)Qt, st));
+  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
 
   const char* o = c->pin_out.p;
   const int32_t* pstat = reinterpret_cast<const int32_t*>(o + d_pstat);
@@ -206,7 +194,7 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
 
 int dsh_search_by_projection_frame(dsh_ctx* ctx, const dsh_track_frame* frame, int Q, const float* xyz, const int32_t* octave,
                                    const uint8_t* desc, float th, int32_t* match, int32_t* nmatches) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (!frame) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection_frame: frame is NULL");
   dsh_track_problem pr;
@@ -227,7 +215,7 @@ int dsh_search_by_projection_frame(dsh_ctx* ctx, const dsh_track_frame* frame, i
 int dsh_search_by_projection_local(dsh_ctx* ctx, const dsh_track_frame* frame, int Q, const float* xyz, const float* normal,
                                    const float* max_distance, const uint8_t* desc, const uint8_t* skip, float th, int32_t* match,
                                    uint8_t* in_view, int32_t* level, int32_t* nmatches) {
-  dsh_ctx_base* c = reinterpret_cast<dsh_ctx_base*>(ctx);
+  dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (!frame) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection_local: frame is NULL");
   dsh_track_problem pr;

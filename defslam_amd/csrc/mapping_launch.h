@@ -1,0 +1,70 @@
+// Launchers of the mapping-side kernels (nrsfm_kernels.hip, diffdb_kernels.hip, register_kernels.hip), declared once: the kernel
+// files include this header too, so the compiler checks every declaration against its definition.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+// ---- nrsfm_kernels.hip: B-spline evaluation / colocation, normals (dsh_nrsfm.cpp, dsh_diffdb.cpp)
+extern "C" hipError_t nrsfm_launch_bbs_eval(double umin, double umax, int nptsu, double vmin, double vmax, int nptsv, int valdim, const double* ctrl,
+                                            const double* u, const double* v, int n, int du, int dv, double* val, uint8_t* outside, hipStream_t st);
+extern "C" hipError_t nrsfm_launch_bbs_coloc(double umin, double umax, int nptsu, double vmin, double vmax, int nptsv, const double* u, const double* v,
+                                             int n, int du, int dv, int32_t* cols, double* w, int32_t* n_outside, hipStream_t st);
+extern "C" hipError_t nrsfm_launch_normals(int P, int R, const int32_t* rec_ptr, const int32_t* rec_point, const float* recs, const uint8_t* is_ref,
+                                           const float* first_n, const uint8_t* has_first_n, const float* x0, const uint8_t* has_x0, const float* ref_uv,
+                                           double* Q, double* k1k2, double* cov, int32_t* status, float* normal_ref, float* normal_rec, uint8_t* written,
+                                           int32_t* iters, hipStream_t st);
+
+// ---- nrsfm_kernels.hip: Schwarp fit (dsh_schwarp.cpp) and the dense solver it shares with Shape from Normals (dsh_sfn.cpp)
+extern "C" hipError_t nrsfm_swp_eval(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
+                                     const float* kp1, const float* kp2, const float* invsig, const double* x, double* r, double* J, int with_j, hipStream_t st);
+extern "C" hipError_t nrsfm_swp_loss(int P2, int m, const double* r, double* scal, hipStream_t st);
+extern "C" hipError_t nrsfm_swp_normal(int P2, int m, int n2, double* J, double* r, const double* cs, const double* scal, double* A, double* g, hipStream_t st);
+extern "C" hipError_t nrsfm_swp_colscale(int n2, const double* A, double* cs, hipStream_t st);
+extern "C" int nrsfm_swp_solve_np(int n2);
+extern "C" hipError_t nrsfm_swp_solve(int n2, const double* A, const double* g, double radius, double* M, double* Winv, double* dx, double* out, int interleave,
+                                      int kd, hipStream_t st);
+extern "C" hipError_t nrsfm_swp_resolve(int n2, const double* g, const double* M, const double* Winv, double* dx, int interleave, int kd, hipStream_t st);
+extern "C" hipError_t nrsfm_swp_step(int n2, const double* x, const double* dx, const double* cs, const double* g, double* xn, double* out, hipStream_t st);
+extern "C" hipError_t nrsfm_swp_diffprop(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, const float* kp1, const float* kp2,
+                                         const double* x, float fx_true, float fy_true, float* diff, uint8_t* drop, hipStream_t st);
+extern "C" size_t nrsfm_swp_fit_bytes();
+extern "C" void nrsfm_swp_fit_fill(void* host_slot, double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
+                                   float fx, float fy, int max_iters, const float* kp1, const float* kp2, const float* isg, double* x, double* xn, double* cs,
+                                   double* g, double* dx, double* r, double* J, double* A, double* M, double* W, double* scal, float* diff, uint8_t* drop,
+                                   int32_t* info, double* costs, const double* bend, void* compact);
+extern "C" size_t nrsfm_swp_compact_bytes(int P, int nu, int nv);
+extern "C" hipError_t nrsfm_swp_fit_batch(void* d_fits_v, int B, int maxP, int maxN, int max_iters, int with_init, hipStream_t st);
+
+// ---- nrsfm_kernels.hip: Shape from Normals, warp initialisation, search by Schwarp (dsh_sfn.cpp)
+extern "C" hipError_t nrsfm_sfn_rows(double umin, double umax, int nu, double vmin, double vmax, int nv, int n, const double* u, const double* v,
+                                     const float* normals, double* A, hipStream_t st);
+extern "C" hipError_t nrsfm_sfn_residual(int m, int N, const double* A, const double* x, const double* b, double sign, double* out, hipStream_t st);
+extern "C" hipError_t nrsfm_sfn_axpy(int n, const double* dx, double* x, hipStream_t st);
+extern "C" hipError_t nrsfm_sfn_points(double umin, double umax, int nu, double vmin, double vmax, int nv, const double* ctrl, int n, const double* u,
+                                       const double* v, float* pts, hipStream_t st);
+extern "C" hipError_t nrsfm_warp_coloc(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, const float* kp1, const float* kp2, double* Cm,
+                                       double* rhs0, double* rhs1, hipStream_t st);
+extern "C" hipError_t nrsfm_mat_add(size_t n, const double* B, double* A, hipStream_t st);
+extern "C" hipError_t nrsfm_match_search(double umin, double umax, int nu, double vmin, double vmax, int nv, const double* x, int Q, const float* kp1,
+                                         const uint32_t* desc1, const float* cam2, const float* bounds2, int cols, int rows, int N2, const float* kp2,
+                                         const uint32_t* desc2, const uint8_t* has_mp2, float radius, int th_low, int32_t* cell, int32_t* match, hipStream_t st);
+
+// ---- diffdb_kernels.hip: the DiffProp database (dsh_diffdb.cpp, dsh_schwarp.cpp, dsh_sfn.cpp)
+extern "C" hipError_t ddb_pick_normals(int n, const int32_t* sel, const float* nref, const float* nrec, float* out, hipStream_t st);
+extern "C" hipError_t ddb_append(int n, const uint8_t* drop, const float* diff, const int32_t* pid, const int32_t* tag, const int32_t* idx2, int32_t* keep, int32_t* pos,
+                                 void* tmp, size_t tmp_bytes, long long base, long long cap, float* rec, int32_t* dpid, int32_t* dtag, int32_t* didx2, hipStream_t st);
+extern "C" size_t ddb_scan_tmp_bytes(int n);
+extern "C" size_t ddb_group_tmp_bytes(int P);
+extern "C" hipError_t ddb_group(long long n, const int32_t* dpid, int P, const int32_t* point_ids, int nlook, int32_t* lookup, int32_t* key, int32_t* count,
+                                int32_t* cursor, int32_t* perm, int32_t* owner, void* tmp, int32_t* rec_ptr, hipStream_t st);
+extern "C" hipError_t ddb_gather(int R, const int32_t* perm, const float* rec, const int32_t* dtag, const int32_t* didx2, float* soa, int32_t* otag, int32_t* oidx2,
+                                 hipStream_t st);
+
+// ---- register_kernels.hip: embedding (dsh_api.cpp), surface registration (dsh_register.cpp)
+extern "C" hipError_t reg_embed(int P, const float* pts, int n, const double* xyz0, const int32_t* facets, const int32_t* nf_ptr, const int32_t* nf_idx,
+                                int32_t* facet_id, int32_t* nodes, float* bary, hipStream_t st);
+extern "C" hipError_t reg_scale_min_median(int n, int ncand, const float* mono, const float* stereo, const double* u, const int32_t* cand,
+                                           const int64_t* cand_off, float* medians, double* scales, double* out, hipStream_t st);
+extern "C" hipError_t reg_horn(int n, const float* p1, const float* p2, const double* sim3_in, double chi, double huber_delta, double* err, double* out,
+                               hipStream_t st);

@@ -16,6 +16,7 @@
 #include "tile_chol.h"
 #include <math.h>
 #include <stdint.h>
+#include "mapping_launch.h"
 
 namespace {
 

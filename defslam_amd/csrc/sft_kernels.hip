@@ -3426,7 +3426,6 @@ extern "C" hipError_t sft_lm_launch(const SftDev* d_probs, int B, int max_kd, si
   return hipGetLastError();
 }
 
-extern "C" size_t sft_lm_kernel_lds_bytes(int kd, size_t jl_doubles);
 #ifdef DSH_LAB
 extern "C" hipError_t sft_wave_lab_launch(const SftDev* d_probs, int B, int which, double rel, int max_kd, size_t jl_doubles, hipStream_t stream) {
   if (which == 0) {

@@ -256,3 +256,182 @@ def test_graph_cache_survives_more_active_sets_than_it_holds(host_ctx):
         assert nb == ref[v][0]
         np.testing.assert_array_equal(counts[:7], ref[v][1][:7])
         assert counts[8] == ref[v][1][8]
+
+
+DSH_OK, ARG, STATE, NODEV = 0, 1, 3, 4   # DSH_ERR_ARG, DSH_ERR_STATE, DSH_ERR_NO_DEVICE
+_HOST_ONLY_MESSAGE_EMPTY = ("dsh_synchronize",)   # returns DSH_ERR_NO_DEVICE without a message
+
+
+def _host_only_rows(keep):
+    """One row per product entry point that takes a context, store or communicator: (name, well-formed call, its status, call with one
+    malformed argument, its status).  Arguments are raw ctypes values; `None` is a null pointer, the context goes in as "ctx"."""
+    from defslam_amd import _lib
+
+    def buf(nbytes=4096, fill=None):
+        b = (C.c_uint8 * nbytes)()
+        if fill is not None:
+            C.memmove(b, fill.ctypes.data, fill.nbytes)
+        keep.append(b)
+        return C.cast(b, C.c_void_p)
+
+    def ref(s):
+        keep.append(s)
+        return C.cast(C.byref(s), C.c_void_p)
+
+    I, L64, D, F = C.c_int, C.c_int64, C.c_double, C.c_float
+    eye = buf(fill=np.eye(4, dtype=np.float32))
+    one = buf(fill=np.ones(1, np.float32))
+    bbs = ref(_lib.BbsC(0.0, 1.0, 5, 0.0, 1.0, 5, 1))
+    bad_bbs = ref(_lib.BbsC(0.0, 1.0, 3, 0.0, 1.0, 5, 1))   # fewer than 4 control points
+
+    def frame(**over):
+        f = _lib.SftFrameC(Tcw=C.cast(eye, _lib.c_float_p), n_frame=1, M=1, reg_lap=1.0, reg_inex=1.0, reg_temp=1.0, neighbour_layers=1, max_iters=50,
+                           obs_nodes=C.cast(buf(fill=np.array([0, 1, 2], np.int32)), _lib.c_i32_p), obs_bary=C.cast(buf(fill=np.full(3, 1 / 3)), _lib.c_double_p),
+                           obs_uv=C.cast(buf(fill=np.array([320.0, 240.0])), _lib.c_double_p), obs_invsig2=C.cast(buf(fill=np.ones(1)), _lib.c_double_p),
+                           xyz=C.cast(buf(fill=np.array([0, 0, 1, 1, 0, 1, 0, 1, 1], np.float64)), _lib.c_double_p))
+        f.K[:] = (500.0, 500.0, 320.0, 240.0)
+        for k, v in over.items():
+            setattr(f, k, v)
+        return ref(f)
+
+    def track_frame(**over):
+        f = _lib.TrackFrameC(Tcw=C.cast(eye, _lib.c_float_p), grid_cols=64, grid_rows=48, levels=1, scale_factors=C.cast(one, _lib.c_float_p),
+                             log_scale_factor=0.18, N=0)
+        f.K[:] = (500.0, 500.0, 320.0, 240.0)
+        f.bounds[:] = (0.0, 640.0, 0.0, 480.0)
+        for k, v in over.items():
+            setattr(f, k, v)
+        keep.append(f)
+        return f
+
+    def track_problem(**over):
+        p = _lib.TrackProblemC(frame=track_frame(), mode=_lib.DSH_TRACK_FRAME, th=20.0, Q=0)
+        for k, v in over.items():
+            setattr(p, k, v)
+        return ref(p)
+
+    def schwarp_problem(**over):
+        p = _lib.SchwarpProblemC(bbs=_lib.BbsC(0.0, 1.0, 5, 0.0, 1.0, 5, 2), P=0, fx_slot=1.0, fy_slot=1.0, lam=1.0, fx=500.0, fy=500.0, max_iters=10,
+                                 x=buf().value)
+        for k, v in over.items():
+            setattr(p, k, v)
+        return ref(p)
+
+    def kf(**over):
+        k = _lib.MpKeyFrameC(N=0, levels=1, scale_factors=C.cast(one, _lib.c_float_p))
+        for n, v in over.items():
+            setattr(k, n, v)
+        return ref(k)
+
+    out = C.c_void_p()
+    o = ref(out)
+    i64 = buf()
+    P = buf   # an output / input array large enough for every minimal call below
+    ctx = "ctx"
+    return [
+        ("dsh_synchronize", (ctx,), NODEV, (None,), ARG),
+        ("dsh_template_build", (ctx, I(3), P(), I(1), buf(fill=np.array([0, 1, 2], np.int32))), DSH_OK,
+         (ctx, I(3), P(), I(1), buf(fill=np.array([0, 1, 3], np.int32))), ARG),
+        ("dsh_template_dims", (ctx, P(), P(), P()), DSH_OK, (None, P(), P(), P()), STATE),
+        ("dsh_template_get", (ctx,) + tuple(P() for _ in range(8)), DSH_OK, (None,) + tuple(P() for _ in range(8)), STATE),
+        ("dsh_template_embed", (ctx, I(1), P(), P(), P(), P()), DSH_OK, (ctx, I(1), None, P(), P(), P()), ARG),
+        ("dsh_template_embed_device", (ctx, I(1), P(), P(), P(), P()), NODEV, (ctx, I(1), None, P(), P(), P()), ARG),
+        ("dsh_sft_solve", (ctx, frame(), P()), NODEV, (ctx, None, P()), ARG),
+        ("dsh_sft_batch_upload", (ctx, I(1), frame()), DSH_OK, (ctx, I(0), frame()), ARG),
+        ("dsh_sft_batch_run", (ctx,), NODEV, (None,), ARG),
+        ("dsh_sft_batch_download", (ctx, I(0), P()), NODEV, (ctx, I(0), None), ARG),
+        ("dsh_sft_batch_counts", (ctx, i64, i64), STATE, (None, i64, i64), STATE),
+        ("dsh_sft_batch_problem_info", (ctx, I(0), P(), P()), ARG, (ctx, I(-1), P(), P()), ARG),
+        ("dsh_comm_create", (ctx, I(1), I(0), P(), o), NODEV, (ctx, I(1), I(1), P(), o), ARG),
+        ("dsh_comm_destroy", (None,), ARG, (None,), ARG),
+        ("dsh_sft_shared_solve", (ctx, None, frame(), P()), ARG, (ctx, None, None, P()), ARG),
+        ("dsh_sft_shared_solve_group", (I(1), "ctxs", frame(), P()), NODEV, (I(0), None, frame(), P()), ARG),
+        ("dsh_sft_connected_solve", (ctx, None, frame(), P()), ARG, (ctx, None, None, P()), ARG),
+        ("dsh_sft_connected_solve_group", (ctx, ctx, frame(), P()), ARG, (ctx, None, frame(), P()), ARG),
+        ("dsh_bbs_eval", (ctx, bbs, P(), None, None, I(0), I(0), I(0), None, None), NODEV, (ctx, bad_bbs, P(), None, None, I(0), I(0), I(0), None, None), NODEV),
+        ("dsh_bbs_coloc", (ctx, bbs, None, None, I(0), I(0), I(0), None, None, None), NODEV, (ctx, bbs, None, None, I(0), I(3), I(0), None, None, None), NODEV),
+        ("dsh_normals_estimate", (ctx, I(0), buf(fill=np.zeros(1, np.int32))) + (None,) * 7 + (P(),) + (None,) * 6, NODEV,
+         (ctx, I(-1), buf(fill=np.zeros(1, np.int32))) + (None,) * 7 + (P(),) + (None,) * 6, NODEV),
+        ("dsh_schwarp_eval", (ctx, bbs, I(0), None, None, None, D(1), D(1), D(1), P(), None, None), NODEV,
+         (ctx, bad_bbs, I(0), None, None, None, D(1), D(1), D(1), P(), None, None), NODEV),
+        ("dsh_schwarp_fit", (ctx, bbs, I(0), None, None, None, D(1), D(1), D(1), F(500), F(500), I(10), P(), None, None, P(), P()), NODEV,
+         (ctx, bbs, I(0), None, None, None, D(1), D(1), D(1), F(500), F(500), I(10), None, None, None, P(), P()), NODEV),
+        ("dsh_schwarp_fit_batch", (ctx, I(1), schwarp_problem()), NODEV, (ctx, I(-1), schwarp_problem()), NODEV),
+        ("dsh_diffdb_create", (ctx, L64(16), o), NODEV, (ctx, L64(-1), o), ARG),
+        ("dsh_diffdb_destroy", (None,), ARG, (None,), ARG),
+        ("dsh_diffdb_clear", (None,), ARG, (None,), ARG),
+        ("dsh_diffdb_append", (None, I(0), None, None, None, None), ARG, (None, I(-1), None, None, None, None), ARG),
+        ("dsh_schwarp_fit_batch_store", (ctx, I(1), schwarp_problem(), P(), None), ARG, (ctx, I(-1), schwarp_problem(), P(), None), ARG),
+        ("dsh_normals_estimate_db", (ctx, None, I(0)) + (None,) * 9 + (I(0), P()) + (None,) * 5, NODEV,
+         (ctx, None, I(-1)) + (None,) * 9 + (I(0), P()) + (None,) * 5, NODEV),
+        ("dsh_sfn_estimate", (ctx, bbs, I(0), None, None, None, D(1e-3), D(1), I(0), None, None, P(), P(), None, P()), NODEV,
+         (ctx, bad_bbs, I(0), None, None, None, D(1e-3), D(1), I(0), None, None, P(), P(), None, P()), NODEV),
+        ("dsh_sfn_estimate_db", (ctx, bbs, None, I(0), None, None, None, D(1e-3), D(1), I(0), None, None, P(), P(), None, P()), ARG,
+         (ctx, bad_bbs, None, I(0), None, None, None, D(1e-3), D(1), I(0), None, None, P(), P(), None, P()), ARG),
+        ("dsh_warp_initialize", (ctx, bbs, I(0), None, None, D(1), P(), P()), NODEV, (ctx, bbs, I(-1), None, None, D(1), P(), P()), NODEV),
+        ("dsh_search_by_schwarp", (ctx, bbs, P(), I(0), None, None, P(), P(), I(64), I(48), I(0), None, None, None, F(10), I(50), None, P()), NODEV,
+         (ctx, bbs, P(), I(-1), None, None, P(), P(), I(64), I(48), I(0), None, None, None, F(10), I(50), None, P()), NODEV),
+        ("dsh_scale_min_median", (ctx, I(1), P(), P(), None, L64(0), P(), P(), P()), NODEV, (ctx, I(0), P(), P(), None, L64(0), P(), P(), P()), ARG),
+        ("dsh_optimize_horn", (ctx, I(1), P(), P(), P(), D(1), D(0.01), P(), P()), NODEV, (ctx, I(1), P(), P(), P(), D(1), D(-1), P(), P()), ARG),
+        ("dsh_surface_register", (ctx, I(15), P(), P(), None, L64(0), eye, D(0.05), I(1), P(), P(), P(), P(), P()), NODEV,
+         (ctx, I(15), P(), P(), None, L64(0), None, D(0.05), I(1), P(), P(), P(), P(), P()), ARG),
+        ("dsh_search_by_projection_batch", (ctx, I(1), track_problem()), NODEV, (ctx, I(1), track_problem(mode=2)), ARG),
+        ("dsh_search_by_projection_frame", (ctx, ref(track_frame()), I(0), None, None, None, F(20), None, P()), NODEV,
+         (ctx, ref(track_frame(levels=0)), I(0), None, None, None, F(20), None, P()), ARG),
+        ("dsh_search_by_projection_local", (ctx, ref(track_frame()), I(0), None, None, None, None, None, F(3), None, None, None, P()), NODEV,
+         (ctx, ref(track_frame()), I(-1), None, None, None, None, None, F(3), None, None, None, P()), ARG),
+        ("dsh_kfdb_create", (ctx, I(16), o), NODEV, (ctx, I(0), o), ARG),
+        ("dsh_kfdb_destroy", (None,), ARG, (None,), ARG),
+        ("dsh_kfdb_clear", (None,), ARG, (None,), ARG),
+        ("dsh_kfdb_add", (None, kf(), P()), ARG, (None, None, P()), ARG),
+        ("dsh_kfdb_set_bad", (None, I(0), I(1)), ARG, (None, I(-1), I(1)), ARG),
+        ("dsh_mappoint_update", (ctx, None, I(0), None, buf(fill=np.zeros(1, np.int32)), None, None, None, I(1), P(), P(), None, None, None, P()), NODEV,
+         (ctx, None, I(0), None, buf(fill=np.zeros(1, np.int32)), None, None, None, I(0), P(), P(), None, None, None, P()), ARG),
+    ]
+
+
+def _host_only_call(name, args):
+    """Status and dsh_last_error of one call on a fresh host-only context (a fresh one: the message is the call's own)."""
+    from defslam_amd import _lib
+    L = C.CDLL(_lib.LIB_PATH)   # its own function objects: untyped, the rows pass ctypes values
+    L.dsh_last_error.restype = C.c_char_p
+    ctx = C.c_void_p()
+    assert L.dsh_create(C.byref(ctx), -1) == 0
+    try:   # a template built from one facet: the calls that need one get past that check
+        xyz = np.array([[0, 0, 1], [1, 0, 1], [0, 1, 1]], np.float64)
+        assert L.dsh_template_build(ctx, 3, C.c_void_p(xyz.ctypes.data), 1, C.c_void_p(np.array([0, 1, 2], np.int32).ctypes.data)) == 0
+        ctxs = (C.c_void_p * 1)(ctx)
+        rc = getattr(L, name)(*[ctx if a == "ctx" else ctxs if a == "ctxs" else a for a in args])
+        return rc, (L.dsh_last_error(ctx) or b"").decode()
+    finally:
+        assert L.dsh_destroy(ctx) == 0
+
+
+def test_host_only_status_of_every_entry_point():
+    """Order of checks on a host-only context: every product entry point that takes a context, store or communicator, once with
+    minimal well-formed arguments and once with one malformed argument.  Which of argument checks and the device gate comes first is
+    part of the contract (e.g. dsh_mappoint_update: arguments first); a refusal for want of a device says "host-only"."""
+    keep = []
+    rows = _host_only_rows(keep)
+    header = open(os.path.join(ROOT, "include", "defslam_hip.h")).read()
+    takes = set(re.findall(r"\b(dsh_[a-z0-9_]+)\s*\((?:[^)]*\b(?:dsh_ctx|dsh_diffdb|dsh_kfdb|dsh_comm)\b)", header))
+    # not in the table: the context's life cycle, the calls that return no status, dsh_template_set (its malformed arrays: above)
+    assert {r[0] for r in rows} == takes - {"dsh_create", "dsh_destroy", "dsh_last_error", "dsh_stream", "dsh_diffdb_count", "dsh_kfdb_count",
+                                            "dsh_template_set"}
+    for name, good, good_rc, bad, bad_rc in rows:
+        for args, want in ((good, good_rc), (bad, bad_rc)):
+            rc, msg = _host_only_call(name, args)
+            assert rc == want, (name, args is bad, rc, msg)
+            if rc == NODEV and name not in _HOST_ONLY_MESSAGE_EMPTY:
+                assert "host-only" in msg, (name, msg)
+
+
+def test_host_files_declare_no_launcher_prototypes():
+    """A kernel launcher is declared once, in a header that its .hip file includes too, so the compiler checks the declaration
+    against the definition (an extern "C" name carries no parameter types: a drifted prototype would still link).  No host file
+    declares an extern "C" function it does not define; `extern "C" {` blocks and definitions are fine."""
+    import glob
+    for path in sorted(glob.glob(os.path.join(ROOT, "defslam_amd", "csrc", "*.cpp"))):
+        src = re.sub(r"//[^\n]*", "", open(path).read())
+        for m in re.finditer(r'extern\s+"C"\s*([^{;]*)([{;])', src):
+            assert not (m.group(2) == ";" and m.group(1).strip()), f"{os.path.basename(path)}: extern \"C\" {' '.join(m.group(1).split())[:80]}"
