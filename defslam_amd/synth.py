@@ -306,7 +306,8 @@ def make_warp_problem(n_matches: int = 400, seed: int = 3, nu: int = 13, nv: int
 # ---------------------------------------------------------------------------------------------------------
 # Shape from Normals: a smooth depth surface z(u, v) over the normalised image plane; key points with the true
 # surface normals (plus noise) as NRSfM would hand them over.  X(u, v) = z (u, v, 1): normal ~ X_u x X_v.
-def make_sfn_scene(n_points: int = 600, seed: int = 4, noise: float = 0.01, with_normal_frac: float = 0.8):
+def make_sfn_scene(n_points: int = 600, seed: int = 4, noise: float = 0.01, with_normal_frac: float = 0.8, nu: int = 13, nv: int = 15):
+    """nu x nv: the control grid of the depth spline (the reference's 13 x 15 unless a test asks for another one)."""
     rng = np.random.default_rng(seed)
     u = rng.uniform(-0.55, 0.55, n_points)
     v = rng.uniform(-0.42, 0.42, n_points)
@@ -329,7 +330,7 @@ def make_sfn_scene(n_points: int = 600, seed: int = 4, noise: float = 0.01, with
     has = rng.uniform(size=n_points) < with_normal_frac
     umin, umax = float(u.min() - 0.10), float(u.max() + 0.10)
     vmin, vmax = float(v.min() - 0.10), float(v.max() + 0.10)
-    return dict(bbs=(umin, umax, 13, vmin, vmax, 15, 1), u_all=u, v_all=v, depth_true=d, u=u[has], v=v[has], normals=nrm[has].astype(np.float32),
+    return dict(bbs=(umin, umax, nu, vmin, vmax, nv, 1), u_all=u, v_all=v, depth_true=d, u=u[has], v=v[has], normals=nrm[has].astype(np.float32),
                 mean_depth=float(d.mean()))
 
 
@@ -337,9 +338,10 @@ def make_sfn_scene(n_points: int = 600, seed: int = 4, noise: float = 0.01, with
 # Warp-guided match search: keyframe 1 key points (normalised) with ORB-like 256-bit descriptors, a warp, and keyframe 2
 # key points scattered around the predictions (pixels) with noisy copies of the descriptors, distractors, exact duplicates
 # (distance ties), points that already carry a map point and points outside the image / the grid.
-def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2):
+def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2, nu: int = 13, nv: int = 15):
+    """nu x nv: the control grid of the warp that predicts the matches."""
     rng = np.random.default_rng(seed)
-    pr = make_warp_problem(400, seed + 1)
+    pr = make_warp_problem(400, seed + 1, nu, nv)
     bbs = pr["bbs"][:6] + (2,)
     x = pr["x0"]
     cam2 = np.array([520.0, 515.0, 322.5, 241.25], np.float32)

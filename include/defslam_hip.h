@@ -195,7 +195,14 @@ int dsh_sft_connected_solve(dsh_ctx* ctx, dsh_comm* comm, const dsh_sft_frame* f
 int dsh_sft_connected_solve_group(dsh_ctx* ctx0, dsh_ctx* ctx1, const dsh_sft_frame* frame, dsh_sft_result* results);
 
 /* ---- NRSfM mapping side ----------------------------------------------------------------------- */
-/* Uniform bicubic B-spline (BBS::bbs_t, Thirdparty/BBS/bbs.h:41-50). */
+/* Uniform bicubic B-spline (BBS::bbs_t, Thirdparty/BBS/bbs.h:41-50).  The control grid is an argument of every call (in the reference it
+ * is a compile-time constant, 13 x 15).  Every entry point that takes one wants nptsu >= 4, nptsv >= 4, umax > umin and vmax > vmin and
+ * returns DSH_ERR_ARG otherwise; the entry points that solve for the control points also limit N = nptsu*nptsv, because one workgroup
+ * factors the padded system (at most 512 unknowns).  A refused call changes nothing: the context stays usable.
+ *   dsh_schwarp_eval                                                N <= 4096
+ *   dsh_schwarp_fit, dsh_schwarp_fit_batch, .._fit_batch_store      N <= 256   (2 N unknowns)
+ *   dsh_sfn_estimate, dsh_sfn_estimate_db, dsh_warp_initialize      N <= 512
+ *   dsh_bbs_eval, dsh_bbs_coloc, dsh_search_by_schwarp              no limit on N */
 typedef struct dsh_bbs {
   double umin, umax;
   int32_t nptsu;
@@ -251,7 +258,8 @@ int dsh_schwarp_eval(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, 
 /* SchwarpDatabase::calculateSchwarps (SchwarpDatabase.cc:145-349): HuberLoss(5.77) on the warp block, Levenberg-Marquardt
  * (max_iters = 3 in the reference), then the DiffProp record of every match (diff[P], may be NULL together with drop) and
  * drop[p] = 1 when its reprojection error exceeds 10 px (fx, fy = KF->fx, KF->fy).  x is in/out.
- * info[0] = iterations, info[1] = accepted steps; costs[0] initial, costs[1] final cost (both may be NULL). */
+ * info[0] = iterations, info[1] = accepted steps; costs[0] initial, costs[1] final cost (both may be NULL).
+ * At most 256 control points (nptsu*nptsv <= 256, e.g. 16 x 16): beyond them DSH_ERR_ARG, here and in the batched calls below. */
 int dsh_schwarp_fit(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, const float* invsig, double fx_slot,
                     double fy_slot, double lambda, float fx, float fy, int max_iters, double* x, dsh_diffprop* diff, uint8_t* drop,
                     int32_t* info, double* costs);
@@ -329,7 +337,8 @@ int dsh_normals_estimate_db(dsh_ctx* ctx, dsh_diffdb* db, int P, const int32_t* 
  * Least squares  min |M x|^2 + |Bend x|^2 + (sum x - N mean_depth)^2  over the N = nptsu*nptsv control points, then the
  * reference's scale: ctrl = x / float(median of float(x)) (Surface::saveArray), pts[3 n_all] = float (u d, v d, d) with
  * d = BBS eval of ctrl (Surface::set3DSurfacePoint).  ctrl_raw (may be NULL) receives x before the scaling.
- * *ok = 0 (and DSH_OK) when the reference's estimate() would return false: no key points, rank-deficient system, NaN/Inf. */
+ * *ok = 0 (and DSH_OK) when the reference's estimate() would return false: no key points, rank-deficient system, NaN/Inf.
+ * At most 512 control points (nptsu*nptsv <= 512, e.g. 16 x 32): beyond them DSH_ERR_ARG, also in dsh_sfn_estimate_db. */
 int dsh_sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u, const double* v, const float* normals, double bending_weight,
                      double mean_depth, int n_all, const double* u_all, const double* v_all, double* ctrl_raw, double* ctrl, float* pts, int32_t* ok);
 /* The same with the normals taken on the device from the last dsh_normals_estimate_db of db (they never visit the host): sel[n] >= 0 is
@@ -341,7 +350,8 @@ int dsh_sfn_estimate_db(dsh_ctx* ctx, const dsh_bbs* bbs, const dsh_diffdb* db, 
 /* Warps::Warp::initialize (Modules/Mapping/Schwarp.cc:99-160): the control points of the warp kp1 -> kp2 that start the
  * Schwarzian fit, (C^T C + Bending(lambda)) X = C^T kp2 with C the colocation matrix of the P key points kp1 (float32 x,y
  * pairs, normalised coordinates).  x[2N]: first coordinate of the N control points, then the second (the layout
- * dsh_schwarp_fit takes).  *ok = 0 when the matrix is not positive definite (too few matches for this lambda). */
+ * dsh_schwarp_fit takes).  *ok = 0 when the matrix is not positive definite (too few matches for this lambda).
+ * At most 512 control points (nptsu*nptsv <= 512): beyond them DSH_ERR_ARG. */
 int dsh_warp_initialize(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, double lambda, double* x, int32_t* ok);
 /* DefORBmatcher::searchBySchwarp (Modules/Matching/DefORBmatcher.cc:189-294): for each of the Q query key points of keyframe
  * 1 (the caller keeps the reference's filter :200-211: map point present, not bad, not yet in keyframe 2; kp1 = mpKeypointNorm,

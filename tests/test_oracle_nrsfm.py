@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+import grid_cases
+
 BBS_GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "bbs_*.npz")))
 ORDERS = [(0, 0), (1, 0), (0, 1), (1, 1), (2, 0), (0, 2)]
 
@@ -161,26 +163,8 @@ def test_normals_status_codes_and_propagation(oracle_mod):
 
 
 def test_schwarp_oracle_schwarzian_jacobian_is_exact_and_warp_rows_follow_the_reference_quirks(oracle_mod):
-    from defslam_amd import synth
-    pr = synth.make_warp_problem(120, 4)
-    P, N = 120, 195
-    x = pr["x0"] + np.random.default_rng(4).normal(scale=5e-3, size=390)
-    r, J = oracle_mod.schwarp_eval(pr["bbs"], pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], 0.7, x)
-    for k in [0, 97, 194, 195, 300, 389]:
-        d = np.zeros(390)
-        d[k] = 1e-6
-        fd = (oracle_mod.schwarp_eval(pr["bbs"], pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], 0.7, x + d, False)[0] -
-              oracle_mod.schwarp_eval(pr["bbs"], pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], 0.7, x - d, False)[0]) / 2e-6
-        np.testing.assert_allclose(fd[2 * P:], J[2 * P:, k], rtol=1e-5, atol=1e-7)     # Schwarzian: true derivative
-        if k < N:   # warp x rows: -coloc*fx_slot, i.e. the true derivative divided by invSigma (the constant Jacobian has no invSigma)
-            np.testing.assert_allclose(fd[:P], J[:P, k] * pr["invsig"], rtol=1e-5, atol=1e-6)
-    np.testing.assert_array_equal(J[:P], J[P:2 * P])            # Schwarp.cc:291-298 copies the x rows over the y rows
-    assert (J[:2 * P, N:] == 0).all()
-    # an affine warp has zero Schwarzian derivative
-    iu, iv = np.meshgrid(np.arange(13), np.arange(15), indexing="ij")
-    aff = np.concatenate([(0.3 + 1.1 * iu - 0.2 * iv).ravel(), (-0.1 + 0.4 * iu + 0.9 * iv).ravel()])
-    ra, _ = oracle_mod.schwarp_eval(pr["bbs"], pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], 0.7, aff, False)
-    assert np.abs(ra[2 * P:]).max() < 1e-9
+    """(the body, with P and the control grid as parameters, lives in tests/grid_cases.py: test_mapping_grids_cpu.py runs it on other grids)"""
+    grid_cases.check_schwarp_oracle_jacobian(oracle_mod, 120, 13, 15)
 
 
 def test_initial_schwarp_residuals_are_loss_corrected_like_ceres_evaluate(oracle_mod):
@@ -217,34 +201,6 @@ def test_schwarp_fit_never_increases_the_cost(oracle_mod):
 
 def test_match_search_oracle_equals_brute_force(oracle_mod):
     """The grid-walking oracle of searchBySchwarp against an independent numpy brute force with the explicit tie-break key
-    (distance, grid column, grid row, index)."""
+    (distance, grid column, grid row, index); tests/grid_cases.py holds the brute force."""
     from defslam_amd import synth
-    sc = synth.make_match_scene(300, 500, seed=4)
-    m = oracle_mod.search_by_schwarp(sc["bbs"], sc["x"], sc["kp1"], sc["desc1"], sc["cam2"], sc["bounds2"], sc["kp2"], sc["desc2"], sc["has_mp2"])
-    assert (m >= 0).sum() > 50
-    bbs = sc["bbs"]
-    N = bbs[2] * bbs[5]
-    ctrl = np.stack([sc["x"][:N], sc["x"][N:]], 1).reshape(-1)
-    val, _ = oracle_mod.bbs_eval(bbs, ctrl, sc["kp1"][:, 0].astype(float), sc["kp1"][:, 1].astype(float))
-    e = val.astype(np.float32)
-    px = e[:, 0] * sc["cam2"][0] + sc["cam2"][2]
-    py = e[:, 1] * sc["cam2"][1] + sc["cam2"][3]
-    winv, hinv = np.float32(64) / np.float32(640), np.float32(48) / np.float32(480)
-    k2 = sc["kp2"]
-    cx = np.floor(k2[:, 0] * winv + np.float32(0.5)).astype(int)      # roundf for non-negative values; negatives fall outside anyway
-    cy = np.floor(k2[:, 1] * hinv + np.float32(0.5)).astype(int)
-    ingrid = (k2[:, 0] * winv > -0.5) & (cx < 64) & (k2[:, 1] * hinv > -0.5) & (cy < 48)
-    bits = np.unpackbits(sc["desc2"], axis=1)
-    for q in range(sc["kp1"].shape[0]):
-        exp = -1
-        if 0 <= px[q] < 640 and 0 <= py[q] < 480:
-            dx, dy = np.abs(k2[:, 0] - px[q]), np.abs(k2[:, 1] - py[q])
-            c0 = max(0, int(np.floor((px[q] - np.float32(2)) * winv))); c1 = min(63, int(np.ceil((px[q] + np.float32(2)) * winv)))
-            r0 = max(0, int(np.floor((py[q] - np.float32(2)) * hinv))); r1 = min(47, int(np.ceil((py[q] + np.float32(2)) * hinv)))
-            cand = np.where(ingrid & (dx < 2) & (dy < 2) & (sc["has_mp2"] == 0) & (cx >= c0) & (cx <= c1) & (cy >= r0) & (cy <= r1))[0]
-            if cand.size:
-                dist = (bits[cand] != np.unpackbits(sc["desc1"][q])[None, :]).sum(1)
-                keys = [(int(d), int(cx[j]), int(cy[j]), int(j)) for d, j in zip(dist, cand) if d < 50]
-                if keys:
-                    exp = min(keys)[3]
-        assert m[q] == exp, q
+    grid_cases.check_match_search_brute_force(oracle_mod, synth.make_match_scene(300, 500, seed=4))
