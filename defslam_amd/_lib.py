@@ -112,6 +112,15 @@ DSH_MP_NO_GOOD_DESC = 2
 DSH_MP_MAX_OBS = 65535
 
 
+class MpdbDescC(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("point_capacity", C.c_int32), ("keyframe_capacity", C.c_int32), ("observation_capacity", C.c_int64)]
+
+
+DSH_MPDB_POSITION = 1
+DSH_MPDB_NORMAL_DEPTH = 2
+DSH_MPDB_DESCRIPTOR = 4
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -130,6 +139,10 @@ EXPORTED_SYMBOLS = [
     "dsh_normals_estimate_db", "dsh_sfn_estimate_db",
     "dsh_search_by_projection_batch", "dsh_search_by_projection_frame", "dsh_search_by_projection_local",
     "dsh_kfdb_create", "dsh_kfdb_destroy", "dsh_kfdb_clear", "dsh_kfdb_add", "dsh_kfdb_set_bad", "dsh_kfdb_count", "dsh_mappoint_update",
+    "dsh_mpdb_create", "dsh_mpdb_destroy", "dsh_mpdb_clear", "dsh_mpdb_point_count", "dsh_mpdb_keyframe_count", "dsh_mpdb_add_points",
+    "dsh_mpdb_update_points", "dsh_mpdb_set_points_bad", "dsh_mpdb_add_observations", "dsh_mpdb_erase_observations", "dsh_mpdb_add_keyframe",
+    "dsh_mpdb_set_keyframe_point", "dsh_mpdb_set_keyframe_parent", "dsh_mpdb_set_keyframe_bad",
+    "dsh_local_map_update", "dsh_local_map_points", "dsh_local_map_search",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -234,6 +247,24 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_kfdb_count.argtypes = [vp]
     L.dsh_mappoint_update.argtypes = [vp, vp, C.c_int, c_float_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, C.c_int32, c_u8_p, c_i32_p, c_float_p,
                                       c_float_p, c_float_p, c_i32_p]
+    i32 = C.c_int32
+    L.dsh_mpdb_create.argtypes = [C.POINTER(MpdbDescC), C.POINTER(vp)]
+    L.dsh_mpdb_destroy.argtypes = [vp]
+    L.dsh_mpdb_clear.argtypes = [vp]
+    L.dsh_mpdb_point_count.argtypes = [vp]
+    L.dsh_mpdb_keyframe_count.argtypes = [vp]
+    L.dsh_mpdb_add_points.argtypes = [vp, C.c_int, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p, c_i32_p]
+    L.dsh_mpdb_update_points.argtypes = [vp, C.c_int, c_i32_p, i32, c_float_p, c_float_p, c_float_p, c_u8_p]
+    L.dsh_mpdb_set_points_bad.argtypes = [vp, C.c_int, c_i32_p, c_u8_p]
+    L.dsh_mpdb_add_observations.argtypes = [vp, C.c_int, c_i32_p, c_i32_p]
+    L.dsh_mpdb_erase_observations.argtypes = [vp, C.c_int, c_i32_p, c_i32_p]
+    L.dsh_mpdb_add_keyframe.argtypes = [vp, i32, c_i32_p, i32, i32, c_i32_p]
+    L.dsh_mpdb_set_keyframe_point.argtypes = [vp, i32, i32, i32]
+    L.dsh_mpdb_set_keyframe_parent.argtypes = [vp, i32, i32]
+    L.dsh_mpdb_set_keyframe_bad.argtypes = [vp, i32, i32]
+    L.dsh_local_map_update.argtypes = [vp, C.c_int, c_i32_p, c_u8_p, i32, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p]
+    L.dsh_local_map_points.argtypes = [vp, i32, c_i32_p, c_i32_p]
+    L.dsh_local_map_search.argtypes = [vp, C.POINTER(TrackFrameC), C.c_float, i32, c_i32_p, c_i32_p, c_u8_p, c_i32_p, c_float_p, c_float_p, c_i32_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

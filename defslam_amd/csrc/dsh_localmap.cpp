@@ -1,0 +1,539 @@
+// Host side of the map point store and the local map (include/defslam_hip.h: dsh_mpdb_*, dsh_local_map_*): the store's arrays in HBM,
+// the host mirror that validates (who observes whom, the keyframes' sizes), and per call one upload, the launches of
+// localmap_kernels.hip (and, for the search, of track_kernels.hip) and one download.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "../../include/defslam_hip.h"
+#include "dsh_ctx.h"
+#include "localmap_problem.h"
+#include "track_problem.h"
+
+struct dsh_mpdb : dsh_store {
+  int32_t P = 0, Pcap = 0, K = 0, Kcap = 0;
+  long long R = 0, Rcap = 0, T = 0, Tcap = 0;   // log records, table entries
+  // points
+  float *d_xyz = nullptr, *d_nrm = nullptr, *d_maxd = nullptr;
+  uint4* d_desc = nullptr;
+  int32_t *d_bad = nullptr, *d_cnt = nullptr, *d_local_ids = nullptr;
+  // observations, keyframes, the resident local map
+  int2* d_log = nullptr;
+  LmKf* d_kf = nullptr;
+  int32_t *d_table = nullptr, *d_local_kf = nullptr;
+  LmHdr* d_hdr = nullptr;
+  // host mirror
+  std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
+  std::vector<LmKf> kf;
+  int32_t n_local_points = 0;
+
+  void free_all() {
+    for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_log, (void*)d_kf,
+                    (void*)d_table, (void*)d_local_kf, (void*)d_hdr})
+      if (p) (void)hipFree(p);
+  }
+};
+
+namespace {
+
+uint64_t obs_key(int32_t point, int32_t slot) { return ((uint64_t)(uint32_t)point << 32) | (uint32_t)slot; }
+
+// grow-on-demand device array of T: a new allocation, the `used` leading elements copied device to device
+template <class T>
+hipError_t grow(T** p, size_t used, size_t cap) {
+  return dsh_store_grow((void**)p, sizeof(T) * cap, [&](char* q) { return used ? hipMemcpy(q, *p, sizeof(T) * used, hipMemcpyDeviceToDevice) : hipSuccess; });
+}
+
+hipError_t reserve_points(dsh_mpdb* db, long long need) {
+  if (need <= db->Pcap) return hipSuccess;
+  const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Pcap), INT32_MAX), P = (size_t)db->P;
+  hipError_t e;
+  if ((e = grow(&db->d_xyz, 3 * P, 3 * cap)) != hipSuccess || (e = grow(&db->d_nrm, 3 * P, 3 * cap)) != hipSuccess ||
+      (e = grow(&db->d_maxd, P, cap)) != hipSuccess || (e = grow(&db->d_desc, 2 * P, 2 * cap)) != hipSuccess ||
+      (e = grow(&db->d_bad, P, cap)) != hipSuccess || (e = grow(&db->d_cnt, P, cap)) != hipSuccess ||
+      (e = grow(&db->d_local_ids, P, cap)) != hipSuccess)
+    return e;
+  db->Pcap = (int32_t)cap;
+  return hipSuccess;
+}
+
+hipError_t reserve_keyframes(dsh_mpdb* db, long long need) {
+  if (need <= db->Kcap) return hipSuccess;
+  const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Kcap), INT32_MAX), K = (size_t)db->K;
+  hipError_t e;
+  if ((e = grow(&db->d_kf, K, cap)) != hipSuccess || (e = grow(&db->d_local_kf, K, cap)) != hipSuccess) return e;
+  db->Kcap = (int32_t)cap;
+  return hipSuccess;
+}
+
+// the first checks of every entry point: a store that is alive and attached
+#define MPDB_ENTER(who)                              \
+  if (!db || !db->ctx) return DSH_ERR_ARG;           \
+  dsh_ctx_base* c = db->ctx;                         \
+  auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, std::string(who) + ": " + m); }
+
+// n distinct ids inside [0, count)
+std::string ids_error(int n, const int32_t* ids, int32_t count, const char* what) {
+  if (n < 0) return "n < 0";
+  if (n > 0 && !ids) return std::string(what) + " array is NULL";
+  std::vector<int32_t> s(ids, ids + n);
+  std::sort(s.begin(), s.end());
+  for (int i = 0; i < n; i++) {
+    if (s[i] < 0 || s[i] >= count) return std::string(what) + " " + std::to_string(s[i]) + " outside the store";
+    if (i > 0 && s[i] == s[i - 1]) return std::string(what) + " " + std::to_string(s[i]) + " repeated in the batch";
+  }
+  return "";
+}
+
+// one int32 of the store, written in stream order
+int put_i32(dsh_ctx_base* c, int32_t* dst, int32_t v) {
+  HIPCHK(c, hipMemcpyAsync(dst, &v, 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return DSH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsh_mpdb_create(const dsh_mpdb_desc* desc, dsh_mpdb** out) {
+  if (!desc) return DSH_ERR_ARG;
+  dsh_ctx_base* c = dsh_base(desc->ctx);
+  if (!c) return DSH_ERR_ARG;
+  if (!out) return dsh_fail(c, DSH_ERR_ARG, "dsh_mpdb_create: out is NULL");
+  *out = nullptr;
+  if (desc->point_capacity <= 0 || desc->keyframe_capacity <= 0 || desc->observation_capacity <= 0 || desc->observation_capacity > (1ll << 40))
+    return dsh_fail(c, DSH_ERR_ARG, "dsh_mpdb_create: capacities must be positive");
+  dsh_mpdb* db = new dsh_mpdb();
+  if (!c->host_only) {
+    // a host-only context gets a store without arrays: its entry points check arguments and refuse (dsh_enter)
+    if (const int rc = dsh_enter(c, "dsh_mpdb_create")) { delete db; return rc; }
+    db->Tcap = (long long)desc->keyframe_capacity * 1024;
+    db->Rcap = desc->observation_capacity;
+    if (reserve_points(db, desc->point_capacity) != hipSuccess || reserve_keyframes(db, desc->keyframe_capacity) != hipSuccess ||
+        hipMalloc((void**)&db->d_log, sizeof(int2) * (size_t)db->Rcap) != hipSuccess ||
+        hipMalloc((void**)&db->d_table, 4 * (size_t)db->Tcap) != hipSuccess || hipMalloc((void**)&db->d_hdr, sizeof(LmHdr)) != hipSuccess ||
+        hipMemset(db->d_hdr, 0, sizeof(LmHdr)) != hipSuccess) {
+      db->free_all();
+      delete db;
+      return dsh_fail(c, DSH_ERR_HIP, "dsh_mpdb_create: out of device memory");
+    }
+  }
+  dsh_attach_store(c, db);
+  *out = db;
+  return DSH_OK;
+}
+
+int dsh_mpdb_destroy(dsh_mpdb* db) {
+  if (!db) return DSH_ERR_ARG;
+  if (db->d_hdr) dsh_store_unregister(db);
+  else if (db->ctx) db->ctx->stores.erase(std::remove(db->ctx->stores.begin(), db->ctx->stores.end(), (dsh_store*)db), db->ctx->stores.end());
+  db->free_all();
+  delete db;
+  return DSH_OK;
+}
+
+int dsh_mpdb_clear(dsh_mpdb* db) {
+  MPDB_ENTER("dsh_mpdb_clear");
+  (void)bad;
+  if (db->d_hdr) {
+    if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_mpdb_clear: hipSetDevice failed");
+    HIPCHK(c, hipMemsetAsync(db->d_hdr, 0, sizeof(LmHdr), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  db->P = db->K = 0;
+  db->R = db->T = 0;
+  db->n_local_points = 0;
+  db->obs.clear();
+  db->kf.clear();
+  return DSH_OK;
+}
+
+int32_t dsh_mpdb_point_count(const dsh_mpdb* db) { return db ? db->P : -1; }
+int32_t dsh_mpdb_keyframe_count(const dsh_mpdb* db) { return db ? db->K : -1; }
+
+int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* normal, const float* max_distance, const uint8_t* desc,
+                        const uint8_t* bad_flags, int32_t* first_id) {
+  MPDB_ENTER("dsh_mpdb_add_points");
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!xyz || !normal || !max_distance || !desc)) return bad("a point array is NULL");
+  if ((long long)db->P + n > INT32_MAX) return bad("store full");
+  if (const int rc = dsh_enter(c, "dsh_mpdb_add_points")) return rc;
+  if (first_id) *first_id = db->P;
+  if (n == 0) return DSH_OK;
+  HIPCHK(c, reserve_points(db, (long long)db->P + n));
+  std::vector<int32_t> b32(n, 0);
+  if (bad_flags)
+    for (int i = 0; i < n; i++) b32[i] = bad_flags[i] ? 1 : 0;
+  hipStream_t st = c->stream;
+  const size_t P = (size_t)db->P;
+  HIPCHK(c, hipMemcpyAsync(db->d_xyz + 3 * P, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(db->d_nrm + 3 * P, normal, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(db->d_maxd + P, max_distance, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(db->d_desc + 2 * P, desc, 32 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(db->d_bad + P, b32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  db->P += n;
+  return DSH_OK;
+}
+
+int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what, const float* xyz, const float* normal,
+                           const float* max_distance, const uint8_t* desc) {
+  MPDB_ENTER("dsh_mpdb_update_points");
+  if (what < 1 || what > (DSH_MPDB_POSITION | DSH_MPDB_NORMAL_DEPTH | DSH_MPDB_DESCRIPTOR))
+    return bad("what is not a non-empty mask of DSH_MPDB_POSITION, DSH_MPDB_NORMAL_DEPTH, DSH_MPDB_DESCRIPTOR");
+  const std::string ie = ids_error(n, ids, db->P, "point id");
+  if (!ie.empty()) return bad(ie);
+  const bool wp = (what & DSH_MPDB_POSITION) != 0, wn = (what & DSH_MPDB_NORMAL_DEPTH) != 0, wd = (what & DSH_MPDB_DESCRIPTOR) != 0;
+  if (n > 0 && ((wp && !xyz) || (wn && (!normal || !max_distance)) || (wd && !desc))) return bad("an array that `what` selects is NULL");
+  if (const int rc = dsh_enter(c, "dsh_mpdb_update_points")) return rc;
+  if (n == 0) return DSH_OK;
+  Arena up;
+  const size_t m = (size_t)n, o_ids = up.take(4 * m), o_xyz = up.take(wp ? 12 * m : 0), o_nrm = up.take(wn ? 12 * m : 0), o_maxd = up.take(wn ? 4 * m : 0),
+               o_desc = up.take(wd ? 32 * m : 0);
+  HIPCHK(c, c->pin_in.ensure(up.size, true));
+  char* h = c->pin_in.p;
+  std::memcpy(h + o_ids, ids, 4 * m);
+  if (wp) std::memcpy(h + o_xyz, xyz, 12 * m);
+  if (wn) { std::memcpy(h + o_nrm, normal, 12 * m); std::memcpy(h + o_maxd, max_distance, 4 * m); }
+  if (wd) std::memcpy(h + o_desc, desc, 32 * m);
+  void* dup = nullptr;
+  HIPCHK(c, c->scratch.take(up.size, &dup));
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(dup, h, up.size, hipMemcpyHostToDevice, st));
+  const char* du = static_cast<const char*>(dup);
+  LmWriteBufs w;
+  w.ids = reinterpret_cast<const int32_t*>(du + o_ids);
+  w.src_xyz = reinterpret_cast<const float*>(du + o_xyz);
+  w.src_normal = reinterpret_cast<const float*>(du + o_nrm);
+  w.src_max_distance = reinterpret_cast<const float*>(du + o_maxd);
+  w.src_desc = reinterpret_cast<const uint4*>(du + o_desc);
+  w.xyz = db->d_xyz; w.normal = db->d_nrm; w.max_distance = db->d_maxd; w.desc = db->d_desc;
+  HIPCHK(c, lm_write_points_launch(w, n, what, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return DSH_OK;
+}
+
+int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8_t* bad_flags) {
+  MPDB_ENTER("dsh_mpdb_set_points_bad");
+  const std::string ie = ids_error(n, ids, db->P, "point id");
+  if (!ie.empty()) return bad(ie);
+  if (const int rc = dsh_enter(c, "dsh_mpdb_set_points_bad")) return rc;
+  if (n == 0) return DSH_OK;
+  Arena up;
+  const size_t m = (size_t)n, o_ids = up.take(4 * m), o_val = up.take(4 * m);
+  HIPCHK(c, c->pin_in.ensure(up.size, true));
+  char* h = c->pin_in.p;
+  std::memcpy(h + o_ids, ids, 4 * m);
+  int32_t* v = reinterpret_cast<int32_t*>(h + o_val);
+  for (int i = 0; i < n; i++) v[i] = !bad_flags || bad_flags[i] ? 1 : 0;
+  void* dup = nullptr;
+  HIPCHK(c, c->scratch.take(up.size, &dup));
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(dup, h, up.size, hipMemcpyHostToDevice, st));
+  const char* du = static_cast<const char*>(dup);
+  HIPCHK(c, lm_scatter_i32_launch(db->d_bad, reinterpret_cast<const int32_t*>(du + o_ids), reinterpret_cast<const int32_t*>(du + o_val), 0, n, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return DSH_OK;
+}
+
+int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots) {
+  MPDB_ENTER("dsh_mpdb_add_observations");
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!point_ids || !keyframe_slots)) return bad("point_ids or keyframe_slots is NULL");
+  std::unordered_set<uint64_t> batch;
+  for (int i = 0; i < n; i++) {
+    const int32_t p = point_ids[i], s = keyframe_slots[i];
+    const std::string at = "pair " + std::to_string(i) + ": ";
+    if (p < 0 || p >= db->P) return bad(at + "point id outside the store");
+    if (s < 0 || s >= db->K) return bad(at + "keyframe slot outside the store");
+    if (db->obs.count(obs_key(p, s))) return bad(at + "the point already observes this keyframe");
+    if (!batch.insert(obs_key(p, s)).second) return bad(at + "repeated in the batch");
+  }
+  if (const int rc = dsh_enter(c, "dsh_mpdb_add_observations")) return rc;
+  if (n == 0) return DSH_OK;
+  if (db->R + n > db->Rcap) {
+    const long long cap = std::max(db->R + n, 2 * db->Rcap);
+    HIPCHK(c, grow(&db->d_log, (size_t)db->R, (size_t)cap));
+    db->Rcap = cap;
+  }
+  HIPCHK(c, c->pin_in.ensure(8 * (size_t)n, true));
+  int2* h = reinterpret_cast<int2*>(c->pin_in.p);
+  for (int i = 0; i < n; i++) h[i] = make_int2(point_ids[i], keyframe_slots[i]);
+  HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; i++) db->obs[obs_key(point_ids[i], keyframe_slots[i])] = db->R + i;
+  db->R += n;
+  return DSH_OK;
+}
+
+int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots) {
+  MPDB_ENTER("dsh_mpdb_erase_observations");
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!point_ids || !keyframe_slots)) return bad("point_ids or keyframe_slots is NULL");
+  for (int i = 0; i < n; i++) {
+    const std::string at = "pair " + std::to_string(i) + ": ";
+    if (point_ids[i] < 0 || point_ids[i] >= db->P) return bad(at + "point id outside the store");
+    if (keyframe_slots[i] < 0 || keyframe_slots[i] >= db->K) return bad(at + "keyframe slot outside the store");
+  }
+  if (const int rc = dsh_enter(c, "dsh_mpdb_erase_observations")) return rc;
+  // the records to blank: 2 * record is the point field of the log seen as int32 pairs
+  std::vector<int32_t> idx;
+  std::vector<uint64_t> keys;
+  for (int i = 0; i < n; i++) {
+    const uint64_t k = obs_key(point_ids[i], keyframe_slots[i]);
+    const auto it = db->obs.find(k);
+    if (it == db->obs.end() || std::find(keys.begin(), keys.end(), k) != keys.end()) continue;
+    if (it->second > (INT32_MAX >> 1)) return bad("log too long to erase from");
+    idx.push_back((int32_t)(2 * it->second));
+    keys.push_back(k);
+  }
+  if (idx.empty()) return DSH_OK;
+  const size_t bytes = 4 * idx.size();
+  HIPCHK(c, c->pin_in.ensure(bytes, true));
+  std::memcpy(c->pin_in.p, idx.data(), bytes);
+  void* dup = nullptr;
+  HIPCHK(c, c->scratch.take(bytes, &dup));
+  HIPCHK(c, hipMemcpyAsync(dup, c->pin_in.p, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, lm_scatter_i32_launch(reinterpret_cast<int32_t*>(db->d_log), static_cast<const int32_t*>(dup), nullptr, -1, (int)idx.size(), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (const uint64_t k : keys) db->obs.erase(k);
+  return DSH_OK;
+}
+
+int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_t parent, int32_t bad_flag, int32_t* slot) {
+  MPDB_ENTER("dsh_mpdb_add_keyframe");
+  if (N < 0 || N > (1 << 20)) return bad("N outside 0 .. 2^20");
+  if (N > 0 && !points) return bad("the table is NULL");
+  for (int j = 0; j < N; j++)
+    if (points[j] < -1 || points[j] >= db->P) return bad("table entry " + std::to_string(j) + " is neither -1 nor a point of the store");
+  if (parent < -1 || parent >= db->K) return bad("parent is neither -1 nor a slot of the store");
+  if (db->K == INT32_MAX || db->T + N > INT32_MAX) return bad("store full");
+  if (const int rc = dsh_enter(c, "dsh_mpdb_add_keyframe")) return rc;
+  HIPCHK(c, reserve_keyframes(db, (long long)db->K + 1));
+  if (db->T + N > db->Tcap) {
+    const long long cap = std::max(db->T + N, 2 * db->Tcap);
+    HIPCHK(c, grow(&db->d_table, (size_t)db->T, (size_t)cap));
+    db->Tcap = cap;
+  }
+  LmKf k;
+  k.tab_off = (int32_t)db->T; k.N = N; k.parent = parent; k.bad = bad_flag ? 1 : 0;
+  HIPCHK(c, hipMemcpyAsync(db->d_kf + db->K, &k, sizeof(k), hipMemcpyHostToDevice, c->stream));
+  if (N > 0) HIPCHK(c, hipMemcpyAsync(db->d_table + db->T, points, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  db->kf.push_back(k);
+  if (slot) *slot = db->K;
+  db->K++;
+  db->T += N;
+  return DSH_OK;
+}
+
+int dsh_mpdb_set_keyframe_point(dsh_mpdb* db, int32_t slot, int32_t idx, int32_t point_id) {
+  MPDB_ENTER("dsh_mpdb_set_keyframe_point");
+  if (slot < 0 || slot >= db->K) return bad("slot outside the store");
+  if (idx < 0 || idx >= db->kf[slot].N) return bad("index outside the keyframe's key points");
+  if (point_id < -1 || point_id >= db->P) return bad("point_id is neither -1 nor a point of the store");
+  if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_point")) return rc;
+  return put_i32(c, db->d_table + db->kf[slot].tab_off + idx, point_id);
+}
+
+int dsh_mpdb_set_keyframe_parent(dsh_mpdb* db, int32_t slot, int32_t parent) {
+  MPDB_ENTER("dsh_mpdb_set_keyframe_parent");
+  if (slot < 0 || slot >= db->K) return bad("slot outside the store");
+  if (parent < -1 || parent >= db->K || parent == slot) return bad("parent is neither -1 nor another slot of the store");
+  if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_parent")) return rc;
+  db->kf[slot].parent = parent;
+  return put_i32(c, &db->d_kf[slot].parent, parent);
+}
+
+int dsh_mpdb_set_keyframe_bad(dsh_mpdb* db, int32_t slot, int32_t bad_flag) {
+  MPDB_ENTER("dsh_mpdb_set_keyframe_bad");
+  if (slot < 0 || slot >= db->K) return bad("slot outside the store");
+  if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_bad")) return rc;
+  db->kf[slot].bad = bad_flag ? 1 : 0;
+  return put_i32(c, &db->d_kf[slot].bad, bad_flag ? 1 : 0);
+}
+
+int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8_t* frame_bad, int32_t kf_capacity, int32_t* local_kf,
+                         int32_t* local_votes, int32_t* n_voted, int32_t* n_local_kf, int32_t* ref_kf, int32_t* n_local_points) {
+  MPDB_ENTER("dsh_local_map_update");
+  if (N < 0 || N > (1 << 20)) return bad("N outside 0 .. 2^20");
+  if (N > 0 && !frame_points) return bad("frame_points is NULL");
+  for (int i = 0; i < N; i++)
+    if (frame_points[i] < -1 || frame_points[i] >= db->P) return bad("frame_points[" + std::to_string(i) + "] is neither -1 nor a point of the store");
+  if ((local_kf || local_votes) && kf_capacity < db->K) return bad("kf_capacity is smaller than the store's keyframe count");
+  if (const int rc = dsh_enter(c, "dsh_local_map_update")) return rc;
+
+  const size_t P = (size_t)db->P, K = (size_t)db->K, nb = (P + LM_CHUNK - 1) / LM_CHUNK;
+  Arena down;
+  const size_t d_hdr = down.take(sizeof(LmHdr)), d_kf = down.take(4 * K), d_votes = down.take(4 * K), d_fbad = down.take((size_t)N), down_bytes = down.size;
+  HIPCHK(c, c->pin_in.ensure(4 * (size_t)N, true));
+  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
+  if (N > 0) std::memcpy(c->pin_in.p, frame_points, 4 * (size_t)N);
+  hipStream_t st = c->stream;
+  void *dup = nullptr, *dvotes = nullptr, *dmark = nullptr, *dflag = nullptr, *dblk = nullptr, *ddown = nullptr;
+  HIPCHK(c, c->scratch.take(4 * (size_t)N, &dup));
+  HIPCHK(c, c->scratch.take(4 * K, &dvotes));
+  HIPCHK(c, c->scratch.take(4 * K, &dmark));
+  HIPCHK(c, c->scratch.take(4 * P, &dflag));
+  HIPCHK(c, c->scratch.take(4 * nb, &dblk));
+  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
+  if (N > 0) HIPCHK(c, hipMemcpyAsync(dup, c->pin_in.p, 4 * (size_t)N, hipMemcpyHostToDevice, st));
+  char* dd = static_cast<char*>(ddown);
+  LmBufs b;
+  b.P = db->P; b.K = db->K; b.N = N; b.R = db->R;
+  b.bad = db->d_bad; b.log = db->d_log; b.kf = db->d_kf; b.table = db->d_table;
+  b.frame_points = static_cast<const int32_t*>(dup);
+  b.cnt = db->d_cnt;
+  b.votes = static_cast<int32_t*>(dvotes);
+  b.mark = static_cast<int32_t*>(dmark);
+  b.flag = static_cast<int32_t*>(dflag);
+  b.block_cnt = static_cast<int32_t*>(dblk);
+  b.local_kf = db->d_local_kf; b.local_ids = db->d_local_ids; b.hdr = db->d_hdr;
+  b.out_hdr = reinterpret_cast<LmHdr*>(dd + d_hdr);
+  b.out_kf = reinterpret_cast<int32_t*>(dd + d_kf);
+  b.out_votes = reinterpret_cast<int32_t*>(dd + d_votes);
+  b.out_frame_bad = reinterpret_cast<uint8_t*>(dd + d_fbad);
+  HIPCHK(c, lm_update_launch(b, st));
+  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+
+  const char* o = c->pin_out.p;
+  const LmHdr h = *reinterpret_cast<const LmHdr*>(o + d_hdr);
+  db->n_local_points = h.n_local_points;
+  if (frame_bad && N > 0) std::memcpy(frame_bad, o + d_fbad, (size_t)N);
+  if (local_kf) std::memcpy(local_kf, o + d_kf, 4 * (size_t)h.n_local_kf);
+  if (local_votes) std::memcpy(local_votes, o + d_votes, 4 * (size_t)h.n_voted);
+  if (n_voted) *n_voted = h.n_voted;
+  if (n_local_kf) *n_local_kf = h.n_local_kf;
+  if (ref_kf) *ref_kf = h.ref_kf;
+  if (n_local_points) *n_local_points = h.n_local_points;
+  return DSH_OK;
+}
+
+int dsh_local_map_points(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* n) {
+  MPDB_ENTER("dsh_local_map_points");
+  if (capacity < db->n_local_points) return bad("capacity is smaller than the number of local points");
+  if (db->n_local_points > 0 && !ids) return bad("ids is NULL");
+  if (const int rc = dsh_enter(c, "dsh_local_map_points")) return rc;
+  if (db->n_local_points > 0) {
+    HIPCHK(c, hipMemcpyAsync(ids, db->d_local_ids, 4 * (size_t)db->n_local_points, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (n) *n = db->n_local_points;
+  return DSH_OK;
+}
+
+int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, int32_t capacity, int32_t* local_ids, int32_t* match,
+                         uint8_t* in_view, int32_t* level, float* uv, float* view_cos, int32_t* nmatches) {
+  MPDB_ENTER("dsh_local_map_search");
+  if (!frame) return bad("frame is NULL");
+  const std::string fe = trk_frame_error(*frame);
+  if (!fe.empty()) return bad(fe);
+  if (!(th > 0.0f) || !std::isfinite(th)) return bad("th must be a positive finite number");
+  const int Q = db->n_local_points;
+  if (capacity < Q) return bad("capacity is smaller than the number of local points");
+  if (Q > 0 && !match) return bad("match is NULL");
+  if (Q > (1 << 28)) return bad("too many local points");
+  if (const int rc = dsh_enter(c, "dsh_local_map_search")) return rc;
+  if (nmatches) *nmatches = 0;
+  if (Q == 0) return DSH_OK;
+
+  // up: the frame and its key points; the queries are gathered from the store on the device
+  const dsh_track_frame& f = *frame;
+  const size_t N = (size_t)f.N, q = (size_t)Q, cells = (size_t)f.grid_cols * f.grid_rows + 1;
+  Arena up, down;
+  const size_t o_prob = up.take(sizeof(TrkProb)), o_kp = up.take(8 * N), o_km = up.take(4 * N), o_kd = up.take(32 * N), up_bytes = up.size;
+  const size_t d_match = down.take(4 * q), d_level = down.take(4 * q), d_inview = down.take(4 * q), d_uv = down.take(8 * q), d_vcos = down.take(4 * q),
+               d_pstat = down.take(16), d_ids = down.take(4 * q), down_bytes = down.size;
+  HIPCHK(c, c->pin_in.ensure(up_bytes, true));
+  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
+  char* h = c->pin_in.p;
+  TrkProb pr;
+  trk_fill_prob(pr, f, DSH_TRACK_LOCAL, th, Q);
+  std::memcpy(h + o_prob, &pr, sizeof(pr));
+  if (N > 0) {
+    std::memcpy(h + o_kp, f.kp, 8 * N);
+    int32_t* km = reinterpret_cast<int32_t*>(h + o_km);
+    for (size_t j = 0; j < N; j++) km[j] = f.octave[j] | ((int32_t)f.state[j] << 8);
+    std::memcpy(h + o_kd, f.desc, 32 * N);
+  }
+  hipStream_t st = c->stream;
+  void *dup = nullptr, *dcell = nullptr, *dskp = nullptr, *dsmeta = nullptr, *dsdesc = nullptr, *dkeys = nullptr, *dncand = nullptr, *dwin = nullptr,
+       *ddown = nullptr, *dqpid = nullptr, *dqxyz = nullptr, *dqnrm = nullptr, *dqmaxd = nullptr, *dqmeta = nullptr, *dqdesc = nullptr;
+  HIPCHK(c, c->scratch.take(up_bytes, &dup));
+  HIPCHK(c, c->scratch.take(4 * cells, &dcell));
+  HIPCHK(c, c->scratch.take(8 * N, &dskp));
+  HIPCHK(c, c->scratch.take(4 * N, &dsmeta));
+  HIPCHK(c, c->scratch.take(32 * N, &dsdesc));
+  HIPCHK(c, c->scratch.take(8 * (size_t)TRK_K * q, &dkeys));
+  HIPCHK(c, c->scratch.take(4 * q, &dncand));
+  HIPCHK(c, c->scratch.take(sizeof(TrkWin) * q, &dwin));
+  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
+  HIPCHK(c, c->scratch.take(4 * q, &dqpid));
+  HIPCHK(c, c->scratch.take(12 * q, &dqxyz));
+  HIPCHK(c, c->scratch.take(12 * q, &dqnrm));
+  HIPCHK(c, c->scratch.take(4 * q, &dqmaxd));
+  HIPCHK(c, c->scratch.take(4 * q, &dqmeta));
+  HIPCHK(c, c->scratch.take(32 * q, &dqdesc));
+  HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
+  char* du = static_cast<char*>(dup);
+  char* dd = static_cast<char*>(ddown);
+  HIPCHK(c, hipMemsetAsync(dd + d_pstat, 0, 16, st));
+  LmQueryBufs g;
+  g.xyz = db->d_xyz; g.normal = db->d_nrm; g.max_distance = db->d_maxd; g.desc = db->d_desc; g.bad = db->d_bad; g.cnt = db->d_cnt;
+  g.local_ids = db->d_local_ids;
+  g.qpid = static_cast<int32_t*>(dqpid);
+  g.qxyz = static_cast<float*>(dqxyz);
+  g.qnrm = static_cast<float*>(dqnrm);
+  g.qmaxd = static_cast<float*>(dqmaxd);
+  g.qmeta = static_cast<int32_t*>(dqmeta);
+  g.qdesc = static_cast<uint4*>(dqdesc);
+  g.out_ids = reinterpret_cast<int32_t*>(dd + d_ids);
+  HIPCHK(c, lm_gather_launch(g, Q, st));
+  TrkBufs b;
+  b.prob = reinterpret_cast<const TrkProb*>(du + o_prob);
+  b.kp = reinterpret_cast<const float2*>(du + o_kp);
+  b.kmeta = reinterpret_cast<const int32_t*>(du + o_km);
+  b.kdesc = reinterpret_cast<const uint4*>(du + o_kd);
+  b.cell_start = static_cast<int32_t*>(dcell);
+  b.skp = static_cast<float2*>(dskp);
+  b.smeta = static_cast<int32_t*>(dsmeta);
+  b.sdesc = static_cast<uint4*>(dsdesc);
+  b.qpid = g.qpid; b.qxyz = g.qxyz; b.qnrm = g.qnrm; b.qmaxd = g.qmaxd; b.qmeta = g.qmeta; b.qdesc = g.qdesc;
+  b.keys = static_cast<unsigned long long*>(dkeys);
+  b.ncand = static_cast<int32_t*>(dncand);
+  b.win = static_cast<TrkWin*>(dwin);
+  b.match = reinterpret_cast<int32_t*>(dd + d_match);
+  b.level = reinterpret_cast<int32_t*>(dd + d_level);
+  b.inview = reinterpret_cast<int32_t*>(dd + d_inview);
+  b.uv = reinterpret_cast<float*>(dd + d_uv);
+  b.vcos = reinterpret_cast<float*>(dd + d_vcos);
+  b.pstat = reinterpret_cast<int32_t*>(dd + d_pstat);
+  HIPCHK(c, trk_launch(b, 1, Q, st));
+  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+
+  const char* o = c->pin_out.p;
+  const int32_t* pstat = reinterpret_cast<const int32_t*>(o + d_pstat);
+  if (pstat[2]) return bad("a query window holds more than 4096 candidates");
+  std::memcpy(match, o + d_match, 4 * q);
+  if (local_ids) std::memcpy(local_ids, o + d_ids, 4 * q);
+  if (in_view) {
+    const int32_t* iv = reinterpret_cast<const int32_t*>(o + d_inview);
+    for (size_t i = 0; i < q; i++) in_view[i] = (uint8_t)iv[i];
+  }
+  if (level) std::memcpy(level, o + d_level, 4 * q);
+  if (uv) std::memcpy(uv, o + d_uv, 8 * q);
+  if (view_cos) std::memcpy(view_cos, o + d_vcos, 4 * q);
+  if (nmatches) *nmatches = pstat[0];
+  return DSH_OK;
+}
+
+}  // extern "C"

@@ -9,9 +9,7 @@
 #include "dsh_ctx.h"
 #include "track_problem.h"
 
-namespace {
-
-std::string frame_error(const dsh_track_frame& f) {
+std::string trk_frame_error(const dsh_track_frame& f) {
   if (!f.Tcw) return "Tcw is NULL";
   for (int k = 0; k < 4; k++)
     if (!std::isfinite(f.K[k]) || !std::isfinite(f.bounds[k])) return "K / bounds not finite";
@@ -27,7 +25,24 @@ std::string frame_error(const dsh_track_frame& f) {
   return "";
 }
 
-}  // namespace
+void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int Q) {
+  std::memset(&P, 0, sizeof(P));
+  for (int i = 0; i < 3; i++) {
+    for (int k = 0; k < 3; k++) P.R[3 * i + k] = f.Tcw[4 * i + k];
+    P.t[i] = f.Tcw[4 * i + 3];
+    P.Ow[i] = f.Ow[i];
+  }
+  P.fx = f.K[0]; P.fy = f.K[1]; P.cx = f.K[2]; P.cy = f.K[3];
+  P.minX = f.bounds[0]; P.maxX = f.bounds[1]; P.minY = f.bounds[2]; P.maxY = f.bounds[3];
+  // Frame.cc:97-98: mfGridElementWidthInv = float(FRAME_GRID_COLS) / (mnMaxX - mnMinX)
+  P.winv = (float)f.grid_cols / (P.maxX - P.minX);
+  P.hinv = (float)f.grid_rows / (P.maxY - P.minY);
+  P.logsf = f.log_scale_factor;
+  P.th = th;
+  for (int l = 0; l < f.levels; l++) P.sf[l] = f.scale_factors[l];
+  P.cols = f.grid_cols; P.rows = f.grid_rows; P.levels = f.levels; P.mode = mode;
+  P.N = f.N; P.Q = Q;
+}
 
 extern "C" {
 
@@ -39,7 +54,7 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   long long Nt = 0, Qt = 0, Ct = 0;
   for (int p = 0; p < B; p++) {
     dsh_track_problem& pr = problems[p];
-    const std::string fe = frame_error(pr.frame);
+    const std::string fe = trk_frame_error(pr.frame);
     auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(p) + ": " + m); };
     if (!fe.empty()) return bad(fe);
     if (pr.mode != DSH_TRACK_FRAME && pr.mode != DSH_TRACK_LOCAL) return bad("mode is neither DSH_TRACK_FRAME nor DSH_TRACK_LOCAL");
@@ -79,22 +94,8 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
     const dsh_track_problem& pr = problems[p];
     const dsh_track_frame& f = pr.frame;
     TrkProb P;
-    std::memset(&P, 0, sizeof(P));
-    for (int i = 0; i < 3; i++) {
-      for (int k = 0; k < 3; k++) P.R[3 * i + k] = f.Tcw[4 * i + k];
-      P.t[i] = f.Tcw[4 * i + 3];
-      P.Ow[i] = f.Ow[i];
-    }
-    P.fx = f.K[0]; P.fy = f.K[1]; P.cx = f.K[2]; P.cy = f.K[3];
-    P.minX = f.bounds[0]; P.maxX = f.bounds[1]; P.minY = f.bounds[2]; P.maxY = f.bounds[3];
-    // Frame.cc:97-98: mfGridElementWidthInv = float(FRAME_GRID_COLS) / (mnMaxX - mnMinX)
-    P.winv = (float)f.grid_cols / (P.maxX - P.minX);
-    P.hinv = (float)f.grid_rows / (P.maxY - P.minY);
-    P.logsf = f.log_scale_factor;
-    P.th = pr.th;
-    for (int l = 0; l < f.levels; l++) P.sf[l] = f.scale_factors[l];
-    P.cols = f.grid_cols; P.rows = f.grid_rows; P.levels = f.levels; P.mode = pr.mode;
-    P.N = f.N; P.Q = pr.Q; P.kp_off = (int32_t)kp_off; P.q_off = (int32_t)q_off; P.cell_off = (int32_t)cell_off;
+    trk_fill_prob(P, f, pr.mode, pr.th, pr.Q);
+    P.kp_off = (int32_t)kp_off; P.q_off = (int32_t)q_off; P.cell_off = (int32_t)cell_off;
     std::memcpy(h + o_prob + sizeof(TrkProb) * p, &P, sizeof(P));
     if (f.N > 0) {
       std::memcpy(h + o_kp + 8 * kp_off, f.kp, 8 * (size_t)f.N);

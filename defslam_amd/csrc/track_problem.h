@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
+#include "../../include/defslam_hip.h"
+
 #define TRK_K 4                 // keys (distance, visiting order) phase A keeps per query
 #define TRK_MAX_LEVELS 32
 #define TRK_MAX_KEYPOINTS 8192  // the "taken" bitmap of phase B: 1 KB of LDS
@@ -58,3 +62,8 @@ struct TrkBufs {
 };
 
 extern "C" hipError_t trk_launch(const TrkBufs& b, int B, int Qt, hipStream_t st);
+
+// Host side shared by the entry points that run these kernels (dsh_track.cpp; dsh_localmap.cpp takes its queries from the store):
+// what is wrong with a frame ("" when nothing is), and a frame as a TrkProb -- everything but the offsets into the concatenated buffers.
+std::string trk_frame_error(const dsh_track_frame& f);
+void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int Q);

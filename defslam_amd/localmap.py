@@ -1,0 +1,173 @@
+"""Host-side mirror of the map point store and the local map (include/defslam_hip.h: dsh_mpdb_*, dsh_local_map_*):
+
+  * Tracking::UpdateLocalMap = Tracking::UpdateLocalKeyFrames (Thirdparty/ORBSLAM_2/src/Tracking.cc:1510-1629) +
+    DefTracking::UpdateLocalPoints (Modules/Tracking/DefTracking.cc:426-454);
+  * Tracking::SearchLocalPoints (Tracking.cc:1405-1470) with the resident local points as queries.
+
+The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
+device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
+order here is the index: keyframes by ascending slot, points by ascending id.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from .sft import Context, _ptr
+from .track import TrackFrame
+
+POSITION = _lib.DSH_MPDB_POSITION
+NORMAL_DEPTH = _lib.DSH_MPDB_NORMAL_DEPTH
+DESCRIPTOR = _lib.DSH_MPDB_DESCRIPTOR
+
+
+@dataclass
+class LocalMap:
+    """What dsh_local_map_update returns."""
+    frame_bad: np.ndarray               # (N,) bool: the frame held a bad point there (the reference nulls the entry)
+    local_kf: np.ndarray                # mvpLocalKeyFrames as slots
+    votes: np.ndarray                   # the votes of its first n_voted entries
+    ref_kf: int                         # pKFmax, or -1: leave mpReferenceKF as it is
+    n_local_points: int                 # len(mvpLocalMapPoints); the ids stay on the device (MapPointStore.local_points)
+
+
+@dataclass
+class LocalSearch:
+    """What dsh_local_map_search returns, per local point in ascending id."""
+    local_ids: np.ndarray
+    match: np.ndarray                   # key point index or -1
+    in_view: np.ndarray                 # mbTrackInView
+    level: np.ndarray                   # mnTrackScaleLevel
+    uv: np.ndarray                      # (Q,2) mTrackProjX, mTrackProjY
+    view_cos: np.ndarray                # mTrackViewCos
+    nmatches: int
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+class MapPointStore:
+    """dsh_mpdb: map points, observations and keyframe tables resident in HBM."""
+
+    def __init__(self, ctx: Context, points: int = 4096, keyframes: int = 64, observations: int = 1 << 16):
+        self._ctx, self._h = ctx, None
+        d = _lib.MpdbDescC(ctx._h, int(points), int(keyframes), int(observations))
+        h = C.c_void_p()
+        ctx._check(ctx._L.dsh_mpdb_create(C.byref(d), C.byref(h)), "dsh_mpdb_create")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            self._ctx._L.dsh_mpdb_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _call(self, name, *args):
+        self._ctx._check(getattr(self._ctx._L, name)(self._h, *args), name)
+
+    def clear(self):
+        self._call("dsh_mpdb_clear")
+
+    @property
+    def n_points(self) -> int:
+        return int(self._ctx._L.dsh_mpdb_point_count(self._h))
+
+    @property
+    def n_keyframes(self) -> int:
+        return int(self._ctx._L.dsh_mpdb_keyframe_count(self._h))
+
+    # ---- points ----
+    def add_points(self, xyz, normal, max_distance, desc, bad=None) -> int:
+        """Returns the id of the first new point; the others follow."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        nrm = np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+        md = np.ascontiguousarray(max_distance, np.float32).reshape(n)
+        ds = np.ascontiguousarray(desc, np.uint8).reshape(n, 32)
+        b = None if bad is None else np.ascontiguousarray(bad, np.uint8).reshape(n)
+        first = C.c_int32(-1)
+        self._call("dsh_mpdb_add_points", n, _ptr(xyz, C.c_float), _ptr(nrm, C.c_float), _ptr(md, C.c_float), _ptr(ds, C.c_uint8), _ptr(b, C.c_uint8),
+                   C.byref(first))
+        return int(first.value)
+
+    def update_points(self, ids, xyz=None, normal=None, max_distance=None, desc=None):
+        """Overwrite what is given: xyz (the RecalculatePosition write-back), normal with max_distance, desc."""
+        ids = _i32(ids)
+        n = ids.shape[0]
+        what = (POSITION if xyz is not None else 0) | (NORMAL_DEPTH if normal is not None else 0) | (DESCRIPTOR if desc is not None else 0)
+        xyz = None if xyz is None else np.ascontiguousarray(xyz, np.float32).reshape(n, 3)
+        nrm = None if normal is None else np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+        md = None if max_distance is None else np.ascontiguousarray(max_distance, np.float32).reshape(n)
+        ds = None if desc is None else np.ascontiguousarray(desc, np.uint8).reshape(n, 32)
+        self._call("dsh_mpdb_update_points", n, _ptr(ids, C.c_int32), what, _ptr(xyz, C.c_float), _ptr(nrm, C.c_float), _ptr(md, C.c_float),
+                   _ptr(ds, C.c_uint8))
+
+    def set_points_bad(self, ids, bad=None):
+        ids = _i32(ids)
+        b = None if bad is None else np.ascontiguousarray(bad, np.uint8).reshape(ids.shape[0])
+        self._call("dsh_mpdb_set_points_bad", ids.shape[0], _ptr(ids, C.c_int32), _ptr(b, C.c_uint8))
+
+    # ---- observations ----
+    def add_observations(self, point_ids, keyframe_slots):
+        p, k = _i32(point_ids), _i32(keyframe_slots)
+        self._call("dsh_mpdb_add_observations", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32))
+
+    def erase_observations(self, point_ids, keyframe_slots):
+        p, k = _i32(point_ids), _i32(keyframe_slots)
+        self._call("dsh_mpdb_erase_observations", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32))
+
+    # ---- keyframes ----
+    def add_keyframe(self, points, parent: int = -1, bad: bool = False) -> int:
+        t = _i32(points)
+        slot = C.c_int32(-1)
+        self._call("dsh_mpdb_add_keyframe", t.shape[0], _ptr(t, C.c_int32), int(parent), 1 if bad else 0, C.byref(slot))
+        return int(slot.value)
+
+    def set_keyframe_point(self, slot: int, idx: int, point_id: int):
+        self._call("dsh_mpdb_set_keyframe_point", int(slot), int(idx), int(point_id))
+
+    def set_keyframe_parent(self, slot: int, parent: int):
+        self._call("dsh_mpdb_set_keyframe_parent", int(slot), int(parent))
+
+    def set_keyframe_bad(self, slot: int, bad: bool = True):
+        self._call("dsh_mpdb_set_keyframe_bad", int(slot), 1 if bad else 0)
+
+    # ---- the local map ----
+    def update_local_map(self, frame_points) -> LocalMap:
+        """Tracking::UpdateLocalMap for a frame whose mvpMapPoints are frame_points (ids or -1)."""
+        fp = _i32(frame_points)
+        N, K = fp.shape[0], max(self.n_keyframes, 1)
+        fb = np.zeros(N, np.uint8)
+        kf, votes = np.full(K, -1, np.int32), np.zeros(K, np.int32)
+        nv, nk, ref, npts = C.c_int32(0), C.c_int32(0), C.c_int32(-1), C.c_int32(0)
+        self._call("dsh_local_map_update", N, _ptr(fp, C.c_int32), _ptr(fb, C.c_uint8), K, _ptr(kf, C.c_int32), _ptr(votes, C.c_int32), C.byref(nv),
+                   C.byref(nk), C.byref(ref), C.byref(npts))
+        return LocalMap(frame_bad=fb.astype(bool), local_kf=kf[:nk.value].copy(), votes=votes[:nv.value].copy(), ref_kf=int(ref.value),
+                        n_local_points=int(npts.value))
+
+    def local_points(self, n: int) -> np.ndarray:
+        """The resident local point ids of the last update (n = LocalMap.n_local_points)."""
+        ids = np.zeros(max(int(n), 1), np.int32)
+        got = C.c_int32(0)
+        self._call("dsh_local_map_points", int(n), _ptr(ids, C.c_int32), C.byref(got))
+        return ids[:got.value].copy()
+
+    def search_local_points(self, frame: TrackFrame, n_local_points: int, th: float = 3.0) -> LocalSearch:
+        """Tracking::SearchLocalPoints from the store; frame.state as for the local-map search (track.local_points_search)."""
+        keep = []
+        f = frame.c(keep)
+        Q = int(n_local_points)
+        m = max(Q, 1)
+        ids, match = np.zeros(m, np.int32), np.full(m, -1, np.int32)
+        iv, lev, uv, vc = np.zeros(m, np.uint8), np.zeros(m, np.int32), np.zeros((m, 2), np.float32), np.zeros(m, np.float32)
+        nm = C.c_int32(0)
+        self._call("dsh_local_map_search", C.byref(f), float(th), Q, _ptr(ids, C.c_int32), _ptr(match, C.c_int32), _ptr(iv, C.c_uint8),
+                   _ptr(lev, C.c_int32), _ptr(uv, C.c_float), _ptr(vc, C.c_float), C.byref(nm))
+        return LocalSearch(local_ids=ids[:Q], match=match[:Q], in_view=iv[:Q].astype(bool), level=lev[:Q], uv=uv[:Q], view_cos=vc[:Q],
+                           nmatches=int(nm.value))

@@ -663,3 +663,108 @@ def make_track_scene(seed: int = 0, n_kp: int = 1200, n_frame_q: int = 400, n_lo
     skip = (rng.uniform(size=L) < 0.05).astype(np.uint8)
     lq = track.LocalQueries(xyz=pts[li], normal=normals, max_distance=maxd, desc=pdesc[li], skip=skip)
     return dict(frame=frame, fq=fq, lq=lq, point_xyz=pts, kp_of_point=kp_of_point, frame_points=qi, local_points=li)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Local map (defslam_amd/localmap.py): a map of keyframes along a camera path over a surface -- point tables, observations, a
+# spanning tree, bad flags -- and a current frame that already holds the matches of the frame-to-frame search.
+# ---------------------------------------------------------------------------------------------------------
+def make_local_map_scene(seed: int = 0, n_kf: int = 30, n_kp: int = 1200, obs_per_point: int = 8, n_frame_kp: int = 1200, fill: float = 0.7,
+                         bad_kf_frac: float = 0.07, bad_point_frac: float = 0.02):
+    """A map and a current frame (returns a dict).  Map: P = n_kf * n_kp * fill / obs_per_point points on a bent template (xyz, normal,
+    max_distance, desc, bad); point p is seen by a run of about obs_per_point consecutive keyframes of the path, in each at a random
+    key point: tables[k] (n_kp ids or -1) and the observation pairs (obs_point, obs_kf), shuffled.  parents: a chain with branches
+    (parents[0] = -1); kf_bad / bad: a few bad keyframes and points.  The LAST keyframe is in the window between CreateNewKeyFrame and
+    ProcessNewKeyFrame: its table is filled, its observations are not there yet.  Frame: a track.TrackFrame near the end of the path whose
+    key points were generated around the projections of the most recently seen points; frame_points (N ids or -1) holds what the
+    frame-to-frame search would have matched -- most of those points at their own key point, a few of them at a second key point as
+    well (they vote twice), some bad points among them -- and frame.state is 1 where a point is held."""
+    from . import track
+    rng = np.random.default_rng(7000 + seed)
+    P = max(8, int(n_kf * n_kp * fill / obs_per_point))
+    tmpl = make_grid_template(10, 10, seed=1234 + seed)
+    gt = tmpl.xyz0.copy()
+    gt[:, 2] += 0.05 * np.sin(2 * np.pi * (gt[:, 0] - gt[:, 0].min()) / np.ptp(gt[:, 0]) + 0.3 * seed)
+    fac = rng.integers(0, tmpl.facets.shape[0], P)
+    bary = rng.dirichlet((1.0, 1.0, 1.0), P)
+    xyz = (bary[:, :, None] * gt[tmpl.facets[fac]]).sum(1).astype(np.float32)
+    # who sees whom: point p by keyframes first[p] .. first[p] + run[p] - 1; points sorted by first so that ids follow the path
+    run = np.clip(rng.integers(max(1, obs_per_point // 2), obs_per_point + obs_per_point // 2 + 1, P), 1, n_kf)
+    first = np.sort(rng.integers(0, np.maximum(n_kf - run // 2, 1), P))
+    first = np.minimum(first, n_kf - 1)
+    tables = np.full((n_kf, n_kp), -1, np.int32)
+    obs_point, obs_kf = [], []
+    for k in range(n_kf):
+        seen = np.nonzero((first <= k) & (k < first + run))[0]
+        if seen.shape[0] > int(0.9 * n_kp):
+            seen = np.sort(rng.choice(seen, int(0.9 * n_kp), replace=False))
+        tables[k, rng.choice(n_kp, seen.shape[0], replace=False)] = seen
+        if k < n_kf - 1:                                           # the last keyframe's observations are still to come
+            obs_point.append(seen)
+            obs_kf.append(np.full(seen.shape[0], k))
+    obs_point = np.concatenate(obs_point).astype(np.int32) if obs_point else np.zeros(0, np.int32)
+    obs_kf = np.concatenate(obs_kf).astype(np.int32) if obs_kf else np.zeros(0, np.int32)
+    perm = rng.permutation(obs_point.shape[0])
+    obs_point, obs_kf = obs_point[perm], obs_kf[perm]
+    parents = np.arange(-1, n_kf - 1, dtype=np.int32)
+    for k in range(2, n_kf):
+        if rng.uniform() < 0.15:
+            parents[k] = rng.integers(0, k - 1)
+    kf_bad = np.zeros(n_kf, bool)                                  # a few of each, at least one (never the root keyframe)
+    if n_kf > 1:
+        kf_bad[rng.choice(np.arange(1, n_kf), min(n_kf - 1, max(1, int(round(bad_kf_frac * n_kf)))), replace=False)] = True
+    bad = np.zeros(P, bool)
+    bad[rng.choice(P, max(1, int(round(bad_point_frac * P))), replace=False)] = True
+    # the current frame: key points around the most recently seen points
+    recent = np.nonzero(first + run >= n_kf - 2)[0]
+    n_vis = max(4, min(recent.shape[0], int(0.45 * n_frame_kp)))
+    vis = np.sort(rng.choice(recent, n_vis, replace=False)) if recent.shape[0] > n_vis else (recent if recent.shape[0] >= 4 else np.arange(P - 4, P))
+    ts = make_track_scene(seed, n_kp=n_frame_kp, n_frame_q=0, n_local_q=vis.shape[0], mappoint_xyz=xyz[vis], adversarial=False)
+    frame = ts["frame"]
+    Ow = np.asarray(frame.Ow, np.float64)
+    PO = xyz.astype(np.float64) - Ow
+    dist = np.linalg.norm(PO, axis=1)
+    nrm = PO / dist[:, None] + 0.3 * rng.normal(size=(P, 3))
+    normal = (nrm / np.linalg.norm(nrm, axis=1)[:, None]).astype(np.float32)
+    max_distance = (dist * 1.2 ** rng.uniform(0.1, 6.9, P)).astype(np.float32)
+    desc = rng.integers(0, 256, (P, 32), dtype=np.uint8)
+    lq, li = ts["lq"], ts["local_points"]
+    for q in range(li.shape[0]):                                   # the visible points take the scene's normals, depths and descriptors
+        p = vis[li[q]]
+        normal[p], max_distance[p], desc[p] = lq.normal[q], lq.max_distance[q], lq.desc[q]
+    N = np.asarray(frame.kp).reshape(-1, 2).shape[0]
+    frame_points = np.full(N, -1, np.int32)
+    kp_of = ts["kp_of_point"]
+    for i in range(vis.shape[0]):
+        if kp_of[i] >= 0 and rng.uniform() < 0.6:                  # matched by the frame-to-frame search
+            frame_points[kp_of[i]] = vis[i]
+    free = np.nonzero(frame_points < 0)[0]
+    held = frame_points[frame_points >= 0]
+    if held.shape[0] and free.shape[0]:
+        twice = rng.choice(held, min(5, held.shape[0]), replace=False)
+        frame_points[rng.choice(free, twice.shape[0], replace=False)] = twice
+        bad[rng.choice(held, min(3, held.shape[0]), replace=False)] = True
+    state = (frame_points >= 0).astype(np.uint8)
+    frame = track.TrackFrame(**{**frame.__dict__, "state": state})
+    return dict(xyz=xyz, normal=normal, max_distance=max_distance, desc=desc, bad=bad, tables=tables, parents=parents, kf_bad=kf_bad,
+                obs_point=obs_point, obs_kf=obs_kf, frame=frame, frame_points=frame_points)
+
+
+def write_local_map_scene(sc, path):
+    """A make_local_map_scene dict as the text file integration/localmap_shim_test_main.cc reads (floats by repr: they round-trip)."""
+    tf = sc["frame"]
+    a = tf.arrays()
+    fl = lambda vs: " ".join(repr(float(v)) for v in vs)
+    by = lambda row: " ".join(str(int(b)) for b in row)
+    P, K, N = sc["xyz"].shape[0], sc["tables"].shape[0], a["kp"].shape[0]
+    with open(path, "w") as f:
+        f.write(f"{a['sf'].shape[0]} {float(np.float32(tf.log_scale_factor))!r}\n{fl(a['sf'])}\n{P}\n")
+        for p in range(P):
+            f.write(f"{fl(sc['xyz'][p])} {fl(sc['normal'][p])} {float(sc['max_distance'][p])!r} {int(sc['bad'][p])} {by(sc['desc'][p])}\n")
+        f.write(f"{K}\n")
+        for k in range(K):
+            f.write(f"{int(sc['parents'][k])} {int(sc['kf_bad'][k])} {sc['tables'].shape[1]} {by(sc['tables'][k])}\n")
+        f.write(f"{sc['obs_point'].shape[0]}\n" + "".join(f"{int(p)} {int(k)}\n" for p, k in zip(sc["obs_point"], sc["obs_kf"])))
+        f.write(f"{fl(a['K'])} {fl(a['bounds'])}\n{fl(a['Tcw'].ravel())}\n{fl(a['Ow'])}\n{N}\n")
+        for j in range(N):
+            f.write(f"{float(a['kp'][j, 0])!r} {float(a['kp'][j, 1])!r} {int(a['octave'][j])} {int(sc['frame_points'][j])} {by(a['desc'][j])}\n")

@@ -559,6 +559,94 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
                         const int32_t* obs_idx, const int32_t* ref_kf, int32_t what, uint8_t* desc, int32_t* best, float* normal,
                         float* max_distance, float* min_distance, int32_t* status);
 
+/* ---- tracking: the local map from a resident map point store ---------------------------------------------------------------
+ * Tracking::UpdateLocalMap (Thirdparty/ORBSLAM_2/src/Tracking.cc:1472-1480) = Tracking::UpdateLocalKeyFrames (:1510-1629) +
+ * DefTracking::UpdateLocalPoints (Modules/Tracking/DefTracking.cc:426-454), and Tracking::SearchLocalPoints (:1405-1470) fed from it.
+ * dsh_mpdb keeps in HBM what these read of the map:
+ *   points      id 0, 1, 2 ... in creation order: mWorldPos (float32), the normal, mfMaxDistance, the 32-byte descriptor, the bad flag
+ *   observations  MapPoint::mObservations, the point-side relation, as an append-only log of (point id, keyframe slot) records; an
+ *               erased record is blanked in place.  A host mirror finds a pair's record and refuses a pair that is already there
+ *               (MapPoint::AddObservation, MapPoint.cc:88-91).  The key point index of an observation is not read here and not stored
+ *   keyframes   slot 0, 1, 2 ... in insertion order -- add keyframes to dsh_kfdb and to this store in the same order and the numbers
+ *               agree: N, the keyframe-side table mvpMapPoints (a point id or -1 per key point), the parent in the spanning tree (a
+ *               slot or -1, KeyFrame::GetParent; the children of a keyframe are the slots whose parent it is) and the bad flag
+ * Both relations are stored because the reference reads both -- votes go through the points' observations, local points through the
+ * keyframes' tables -- and between CreateNewKeyFrame and LocalMapping::ProcessNewKeyFrame they disagree.
+ * ORDER.  The reference iterates std::map<KeyFrame*, int>, std::set<KeyFrame*> and std::set<MapPoint*> in pointer order.  Here, as
+ * everywhere in this library, index order stands for pointer order: keyframes by ascending slot, points by ascending id.
+ * Lifetime as dsh_kfdb: a store belongs to the context of its descriptor; dsh_destroy of that context detaches it -- every call on it
+ * then returns DSH_ERR_ARG -- and the store's own destroy works before or after.  Every entry point takes the store alone (it remembers
+ * its context, runs on that context's stream and reports through that context's dsh_last_error).  Arguments are checked on the host
+ * before any device work: ids and slots outside the store, an index >= N, a NULL array with n > 0 or an id repeated within one batch
+ * give DSH_ERR_ARG, and nothing is stored or written.  A store can be created on a host-only context: it checks arguments (against
+ * an empty store) and then returns DSH_ERR_NO_DEVICE -- there is no CPU fallback. */
+typedef struct dsh_mpdb dsh_mpdb;
+typedef struct dsh_mpdb_desc {
+  dsh_ctx* ctx;                /* the owning context */
+  int32_t point_capacity;      /* initial capacities (> 0); the store grows on demand */
+  int32_t keyframe_capacity;
+  int64_t observation_capacity;
+} dsh_mpdb_desc;
+int dsh_mpdb_create(const dsh_mpdb_desc* desc, dsh_mpdb** out);
+int dsh_mpdb_destroy(dsh_mpdb* db);
+int dsh_mpdb_clear(dsh_mpdb* db);                         /* forget everything, the local map included (DefMap::clear on a reset) */
+int32_t dsh_mpdb_point_count(const dsh_mpdb* db);         /* points stored; -1 for NULL */
+int32_t dsh_mpdb_keyframe_count(const dsh_mpdb* db);      /* keyframes stored; -1 for NULL */
+/* n new points: xyz[n x 3], normal[n x 3], max_distance[n], desc[n x 32], bad[n] (may be NULL: none is bad); *first_id (may be NULL) =
+ * the id of the first one, the others follow. */
+int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* normal, const float* max_distance, const uint8_t* desc,
+                        const uint8_t* bad, int32_t* first_id);
+#define DSH_MPDB_POSITION 1      /* what: xyz */
+#define DSH_MPDB_NORMAL_DEPTH 2  /* what: normal and max_distance (the outputs of dsh_mappoint_update) */
+#define DSH_MPDB_DESCRIPTOR 4    /* what: desc */
+/* Overwrite the parts `what` selects of the n distinct points ids[n]; arrays of parts not selected are not read.  The per-frame use is
+ * the write-back of DefMapPoint::RecalculatePosition after the pose optimisation (dsh_sft_result.mappoint_xyz, DSH_MPDB_POSITION). */
+int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what, const float* xyz, const float* normal,
+                           const float* max_distance, const uint8_t* desc);
+/* MapPoint::SetBadFlag of n distinct points; bad[n] may be NULL (all become bad). */
+int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8_t* bad);
+/* MapPoint::AddObservation / EraseObservation for n (point, keyframe) pairs.  Adding a pair that is stored, or twice in one batch, is
+ * DSH_ERR_ARG; erasing a pair that is not stored changes nothing, like the reference. */
+int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots);
+int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots);
+/* A keyframe with its table points[N] (ids or -1) and its parent (an existing slot or -1); *slot (may be NULL) = its slot. */
+int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_t parent, int32_t bad, int32_t* slot);
+/* KeyFrame::AddMapPoint / EraseMapPointMatch: table entry idx of the keyframe becomes point_id (or -1). */
+int dsh_mpdb_set_keyframe_point(dsh_mpdb* db, int32_t slot, int32_t idx, int32_t point_id);
+int dsh_mpdb_set_keyframe_parent(dsh_mpdb* db, int32_t slot, int32_t parent);   /* KeyFrame::ChangeParent; parent != slot, or -1 */
+int dsh_mpdb_set_keyframe_bad(dsh_mpdb* db, int32_t slot, int32_t bad);         /* KeyFrame::SetBadFlag */
+
+/* Tracking::UpdateLocalMap for the frame whose mvpMapPoints are frame_points[N] (ids or -1).  Integer valued: every output is exact.
+ * Outputs (each may be NULL): frame_bad[N] = 1 where the frame holds a bad point (the reference nulls that entry, Tracking.cc:1527-1530);
+ * local_kf[] = mvpLocalKeyFrames as slots and local_votes[] = the votes of its first *n_voted entries, both of kf_capacity entries, which
+ * must be at least the store's keyframe count when either is given (the list holds a keyframe at most once); *n_local_kf its length;
+ * *ref_kf = the slot of pKFmax, or -1: leave mpReferenceKF as it is; *n_local_points = the size of mvpLocalMapPoints.  The two lists
+ * stay resident in the store for the next call and for dsh_local_map_search.
+ * Votes (:1513-1532): a frame entry votes once for every keyframe among its point's observations, so a point held by k key points of
+ * the frame votes k times; bad points do not vote; erased observations do not count.
+ * No vote at all (:1534): the previous local keyframe list stays, *n_voted = 0, *ref_kf = -1; the local points are still rebuilt from
+ * that list (UpdateLocalMap calls UpdateLocalPoints regardless).
+ * Local keyframes (:1545-1562): the voted keyframes that are not bad, by ascending slot; pKFmax is the first of them with a strictly
+ * larger vote (a tie goes to the lower slot).  When every voted keyframe is bad the list is empty and *ref_kf = -1.
+ * Expansion (:1566-1622), literally: the loop visits the voted entries only (its end iterator is taken before the pushes) and stops
+ * once the list holds more than 80; per visited keyframe it appends at most three: the first keyframe of the whole map, by ascending
+ * slot, that is not bad and not yet listed (the reference iterates Map::GetAllKeyFrames there; its covisibility call is commented
+ * out, :1576-1577); the first child that is not bad and not yet listed; and the parent when it is not yet listed -- without a test of
+ * its bad flag, and appending it ends the whole loop (the break at :1619 leaves the outer for).
+ * Local points (DefTracking.cc:426-454): the points in the tables of the local keyframes that are not bad, by ascending id. */
+int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8_t* frame_bad, int32_t kf_capacity, int32_t* local_kf,
+                         int32_t* local_votes, int32_t* n_voted, int32_t* n_local_kf, int32_t* ref_kf, int32_t* n_local_points);
+/* The resident local point list of the last update: ids[capacity] receives *n ids (DSH_ERR_ARG when capacity is smaller). */
+int dsh_local_map_points(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* n);
+/* Tracking::SearchLocalPoints (:1440-1468) with the resident local points as queries, in ascending id: position, normal, max distance
+ * and descriptor are gathered from the store on the device, only the frame's key points travel up, and the kernels of
+ * dsh_search_by_projection_local run on them.  A query is skipped when its point is bad or was held by a key point of the frame of the
+ * preceding dsh_local_map_update (mnLastFrameSeen == mnId after the loop at :1408-1425 says exactly that, :1449-1451).
+ * frame->state[] as for DSH_TRACK_LOCAL.  Outputs of Q = n_local_points entries, capacity >= Q: local_ids (may be NULL), match, and
+ * (each may be NULL) in_view, level, uv[Q x 2], view_cos, *nmatches.  Limits and refusals as dsh_search_by_projection_batch. */
+int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, int32_t capacity, int32_t* local_ids, int32_t* match,
+                         uint8_t* in_view, int32_t* level, float* uv, float* view_cos, int32_t* nmatches);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

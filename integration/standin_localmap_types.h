@@ -1,0 +1,69 @@
+// Stand-ins of the members of ORB_SLAM2::KeyFrame, ORB_SLAM2::MapPoint and ORB_SLAM2::Frame that integration/local_map_hip.h touches
+// (reference declaration behind each), for the repository's CI: OpenCV is not in the build image.  Inside DefSLAM these are not used.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <set>
+#include <vector>
+
+#include "standin_types.h"   // standin::KeyPoint (cv::KeyPoint: pt, octave)
+
+namespace standin {
+
+class LmKeyFrame;
+
+class LmMapPoint {                             // Thirdparty/ORBSLAM_2/include/MapPoint.h
+ public:
+  std::map<LmKeyFrame*, size_t> GetObservations() { return mObservations; }   // :54 (a copy, as in the reference)
+  int Observations() { return (int)mObservations.size(); }              // :55
+  bool isBad() { return bad; }                                          // :64
+  void IncreaseVisible(int n = 1) { nVisible += n; }                    // :69
+  float pos[3] = {0, 0, 0};                                             // GetWorldPos() :49 (cv::Mat 3x1 float)
+  float normal[3] = {0, 0, 1};                                          // GetNormal() :51
+  uint8_t desc[32] = {};                                                // GetDescriptor() :76 (1x32 CV_8U)
+  float mfMaxDistance = 1.f;                                            // :152
+  // tracking members written by Frame::isInFrustum (MapPoint.h:103-108)
+  float mTrackProjX = 0, mTrackProjY = 0, mTrackViewCos = 0;
+  int mnTrackScaleLevel = 0;
+  bool mbTrackInView = false;
+  unsigned long mnTrackReferenceForFrame = 0;                           // :109
+  unsigned long mnLastFrameSeen = 0;                                    // :110
+  std::map<LmKeyFrame*, size_t> mObservations;                          // :127
+  int nVisible = 0;
+  bool bad = false;
+};
+
+class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/KeyFrame.h
+ public:
+  std::vector<LmMapPoint*> GetMapPointMatches() { return mvpMapPoints; }    // :89 (a copy)
+  std::set<LmKeyFrame*> GetChilds() { return mspChildrens; }            // :80
+  LmKeyFrame* GetParent() { return mpParent; }                          // :81
+  bool isBad() { return bad; }                                          // :108
+  unsigned long mnId = 0;                                               // :126
+  unsigned long mnTrackReferenceForFrame = 0;                           // :141
+  std::vector<LmMapPoint*> mvpMapPoints;                                // :199
+  LmKeyFrame* mpParent = nullptr;                                       // :217
+  std::set<LmKeyFrame*> mspChildrens;                                   // :218
+  bool bad = false;
+};
+
+class LmFrame {                                // Thirdparty/ORBSLAM_2/include/Frame.h
+ public:
+  float mTcw[16];                                                       // :180 cv::Mat 4x4 float
+  float mOw[3];                                                         // :231 camera centre
+  float fx, fy, cx, cy;                                                 // :121-124 (static in the reference)
+  float mnMinX, mnMaxX, mnMinY, mnMaxY;                                 // :199-202 (static)
+  int N = 0;                                                            // :140
+  std::vector<KeyPoint> mvKeys, mvKeysUn;                               // :148-149
+  std::vector<uint8_t> mDescriptors;                                    // :163 N rows of 32 bytes (cv::Mat CV_8U)
+  std::vector<LmMapPoint*> mvpMapPoints;                                // :166
+  std::vector<bool> mvbOutlier;                                         // :172
+  int mnScaleLevels = 8;                                                // :190
+  float mfLogScaleFactor = 0;                                           // :192
+  std::vector<float> mvScaleFactors;                                    // :193
+  unsigned long mnId = 0;                                               // :184
+  LmKeyFrame* mpReferenceKF = nullptr;                                  // :187
+};
+
+}  // namespace standin
