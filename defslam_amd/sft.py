@@ -56,6 +56,9 @@ class Frame:
     half_bandwidth: int = 0
     status: int = 0
     trace: np.ndarray = field(default=None)
+    # (RegLap, RegInex, RegTemp) of this frame alone; None: the weights of the call.  One batch may hold frames with different weights
+    # (dsh_sft_frame carries them per frame: a keyframe switch solves with RegTemp = 0 next to ordinary frames).
+    regs: Optional[tuple] = None
 
 
 class Context:
@@ -166,12 +169,15 @@ class Context:
         fc.obs_uv = _ptr(uv, C.c_double)
         fc.obs_invsig2 = _ptr(isg, C.c_double)
         fc.xyz = _ptr(xyz, C.c_double)
+        if f.regs is not None:
+            reg_lap, reg_inex, reg_temp = f.regs
         fc.reg_lap, fc.reg_inex, fc.reg_temp = float(reg_lap), float(reg_inex), float(reg_temp)
         fc.neighbour_layers = int(layers)
         fc.max_iters = int(max_iters)
         return fc
 
     def batch_upload(self, frames: Sequence[Frame], RegLap=5000.0, RegInex=5000.0, RegTemp=0.0, NeighboursLayers=1, max_iters=50):
+        """A frame whose `regs` is set is solved with its own (RegLap, RegInex, RegTemp); every other frame with the call's."""
         keep: list = []
         arr = (_lib.SftFrameC * len(frames))()
         for i, f in enumerate(frames):

@@ -21,6 +21,7 @@ REG_INEX = 12000.0
 REG_TEMP = 0.05
 N_FRAME_KEYPOINTS = 1200
 CAMERA_K = (500.0, 500.0, 320.0, 240.0)  # fx, fy, cx, cy for a 640x480 frame
+IMAGE_SIZE = (640, 480)                  # width, height
 
 CONFIGS = {
     # name: (rows, cols, matches)
@@ -73,16 +74,19 @@ def regular_triangulation(rows: int, cols: int) -> np.ndarray:
     return np.asarray(f, dtype=np.int32)
 
 
-def make_grid_template(rows: int, cols: int, seed: int = 1234, z0: float = 1.0) -> GridTemplate:
+def make_grid_template(rows: int, cols: int, seed: int = 1234, z0: float = 1.0, *, camera=CAMERA_K, image_size=IMAGE_SIZE) -> GridTemplate:
+    """camera = (fx, fy, cx, cy) and image_size = (width, height) place the grid in the frustum; z0 is the scene scale (depth of the
+    template, and its bump scales with it)."""
     rng = np.random.default_rng(seed)
-    fx, fy, cx, cy = CAMERA_K
+    fx, fy, cx, cy = camera
+    width, height = image_size
     # cover 80% of the frustum at depth z0
-    xs = np.linspace(-0.8 * cx / fx, 0.8 * (640 - cx) / fx, cols) * z0
-    ys = np.linspace(-0.8 * cy / fy, 0.8 * (480 - cy) / fy, rows) * z0
+    xs = np.linspace(-0.8 * cx / fx, 0.8 * (width - cx) / fx, cols) * z0
+    ys = np.linspace(-0.8 * cy / fy, 0.8 * (height - cy) / fy, rows) * z0
     X, Y = np.meshgrid(xs, ys)  # row-major: node id = col + cols*row
     ph = rng.uniform(0, 2 * np.pi, size=2)
-    # low-frequency bump, amplitude 0.02, so the rest mean curvature is non-zero
-    Z = z0 + 0.02 * np.sin(2 * np.pi * X / (xs[-1] - xs[0]) + ph[0]) * np.cos(2 * np.pi * Y / (ys[-1] - ys[0]) + ph[1])
+    # low-frequency bump, amplitude 0.02 z0, so the rest mean curvature is non-zero
+    Z = z0 + (0.02 * z0) * np.sin(2 * np.pi * X / (xs[-1] - xs[0]) + ph[0]) * np.cos(2 * np.pi * Y / (ys[-1] - ys[0]) + ph[1])
     xyz0 = np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1)
     # the reference builds nodes from float32 vertices (TriangularMesh.cc:109-123)
     xyz0 = xyz0.astype(np.float32).astype(np.float64)
@@ -102,22 +106,25 @@ def make_frame(tmpl: GridTemplate, n_matches: int, problem_id: int = 0, *,
                bend: float = 0.05, rot_deg: float = 3.0, trans: float = 0.02,
                noise_px: float = 0.5, outlier_frac: float = 0.05,
                n_frame: int = N_FRAME_KEYPOINTS, init_xyz: np.ndarray | None = None,
-               init_Tcw: np.ndarray | None = None, phase: float = 0.0, gt_pose: tuple | None = None) -> SftFrame:
+               init_Tcw: np.ndarray | None = None, phase: float = 0.0, gt_pose: tuple | None = None,
+               camera=CAMERA_K, image_size=IMAGE_SIZE, scale: float = 1.0) -> SftFrame:
     """gt_pose = (rotation vector, translation) fixes the ground-truth camera (sequences: a smooth trajectory) instead of
-    drawing it from the problem's random stream; the stream is consumed identically either way."""
+    drawing it from the problem's random stream; the stream is consumed identically either way.  camera = (fx, fy, cx, cy) and
+    image_size = (width, height) are the frame's pinhole and the area the outliers fall in; scale is the scene scale (the z0 of the
+    template): bend and ground-truth translation are multiplied by it."""
     rng = np.random.default_rng(42 + problem_id)
-    fx, fy, cx, cy = CAMERA_K
+    fx, fy, cx, cy = camera
     xyz0 = tmpl.xyz0
     width = xyz0[:, 0].max() - xyz0[:, 0].min()
     # smooth, roughly isometric bend: sinusoid with wavelength = mesh width
     gt = xyz0.copy()
-    gt[:, 2] += bend * np.sin(2 * np.pi * (xyz0[:, 0] - xyz0[:, 0].min()) / width + phase + 0.3 * problem_id)
+    gt[:, 2] += (bend * scale) * np.sin(2 * np.pi * (xyz0[:, 0] - xyz0[:, 0].min()) / width + phase + 0.3 * problem_id)
     # ground-truth camera: small SE3 offset
     axis = rng.normal(size=3)
     axis /= np.linalg.norm(axis)
     ang = np.deg2rad(rot_deg) * rng.uniform(0.3, 1.0)
     R = _rodrigues(axis * ang)
-    t = rng.uniform(-trans, trans, size=3)
+    t = rng.uniform(-trans, trans, size=3) * scale
     if gt_pose is not None:
         R = _rodrigues(np.asarray(gt_pose[0], dtype=np.float64))
         t = np.asarray(gt_pose[1], dtype=np.float64)
@@ -134,7 +141,7 @@ def make_frame(tmpl: GridTemplate, n_matches: int, problem_id: int = 0, *,
     uv = np.stack([fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy], axis=1)
     uv += rng.normal(scale=noise_px, size=uv.shape)
     is_out = rng.uniform(size=n_matches) < outlier_frac
-    uv_out = np.stack([rng.uniform(0, 640, size=n_matches), rng.uniform(0, 480, size=n_matches)], axis=1)
+    uv_out = np.stack([rng.uniform(0, image_size[0], size=n_matches), rng.uniform(0, image_size[1], size=n_matches)], axis=1)
     uv = np.where(is_out[:, None], uv_out, uv)
     uv = uv.astype(np.float32).astype(np.float64)
     octave = rng.integers(0, 6, size=n_matches)
@@ -142,7 +149,7 @@ def make_frame(tmpl: GridTemplate, n_matches: int, problem_id: int = 0, *,
 
     Tcw = np.eye(4, dtype=np.float32) if init_Tcw is None else np.asarray(init_Tcw, dtype=np.float32)
     xyz = xyz0.copy() if init_xyz is None else np.asarray(init_xyz, dtype=np.float64).copy()
-    return SftFrame(Tcw=Tcw, K=np.asarray(CAMERA_K, dtype=np.float64), n_frame=n_frame,
+    return SftFrame(Tcw=Tcw, K=np.asarray(camera, dtype=np.float64), n_frame=n_frame,
                     obs_facet=fac, obs_nodes=nodes, obs_bary=bary, obs_uv=uv, obs_invsig2=invsig2,
                     xyz=xyz, gt_xyz=gt, gt_Tcw=gtT, is_outlier_gt=is_out)
 
@@ -551,7 +558,8 @@ def _flip_bits(rng, d, n):
 
 
 def make_track_scene(seed: int = 0, n_kp: int = 1200, n_frame_q: int = 400, n_local_q: int = 300, mappoint_xyz=None, Tcw=None,
-                     levels: int = 8, adversarial: bool = True, state_mix: bool = False, n_clusters: int = 6):
+                     levels: int = 8, adversarial: bool = True, state_mix: bool = False, n_clusters: int = 6,
+                     camera=CAMERA_K, bounds=(0.0, IMAGE_SIZE[0], 0.0, IMAGE_SIZE[1]), scale: float = 1.0):
     """One current frame and the queries of both searches (returns dict(frame=track.TrackFrame, fq=FrameQueries, lq=LocalQueries,
     point_xyz, kp_of_point)).  Map points: float32 positions on a bent 10 x 10 template (or mappoint_xyz, e.g. a
     dsh_sft_result.mappoint_xyz, so that SfT(t) -> search(t+1) -> SfT(t+1) can be chained); the current pose moves slightly away
@@ -560,21 +568,23 @@ def make_track_scene(seed: int = 0, n_kp: int = 1200, n_frame_q: int = 400, n_lo
     ties) and, with adversarial, clusters of near-identical key points that several queries want (in-call conflicts that exhaust a
     query's stored keys).  Local points get normals with viewCos spread over [0.3, 1] and max distances that put the predicted level
     0.1 .. 0.9 of a level away from a boundary; viewCos is kept 1e-3 away from 0.5 and 0.998.  state_mix draws key point states
-    0 / 1 / 2 (otherwise all 0)."""
+    0 / 1 / 2 (otherwise all 0).  camera = (fx, fy, cx, cy); bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), the undistorted image area (its
+    minima may be negative); scale is the scene scale: depth and bend of the template and the camera's translation."""
     from . import track
     rng = np.random.default_rng(1000 + seed)
-    fx, fy, cx, cy = CAMERA_K
-    K = np.array(CAMERA_K, np.float32)
-    bounds = np.array([0.0, 640.0, 0.0, 480.0], np.float32)
+    fx, fy, cx, cy = camera
+    K = np.array(camera, np.float32)
+    x_lo, x_hi, y_lo, y_hi = (float(b) for b in bounds)
+    bounds = np.array([x_lo, x_hi, y_lo, y_hi], np.float32)
     sf, logsf = track.orb_pyramid(levels)
     T0 = np.eye(4, dtype=np.float32) if Tcw is None else np.asarray(Tcw, np.float32)
     if mappoint_xyz is None:
-        tmpl = make_grid_template(10, 10, seed=1234 + seed)
+        tmpl = make_grid_template(10, 10, seed=1234 + seed, z0=scale, camera=(fx, fy, cx - x_lo, cy - y_lo), image_size=(x_hi - x_lo, y_hi - y_lo))
         n_pts = max(n_frame_q, n_local_q) + 50
         fac = rng.integers(0, tmpl.facets.shape[0], n_pts)
         bary = rng.dirichlet((1.0, 1.0, 1.0), n_pts)
         gt = tmpl.xyz0.copy()
-        gt[:, 2] += 0.05 * np.sin(2 * np.pi * (gt[:, 0] - gt[:, 0].min()) / np.ptp(gt[:, 0]) + 0.3 * seed)
+        gt[:, 2] += (0.05 * scale) * np.sin(2 * np.pi * (gt[:, 0] - gt[:, 0].min()) / np.ptp(gt[:, 0]) + 0.3 * seed)
         pts = (bary[:, :, None] * gt[tmpl.facets[fac]]).sum(1).astype(np.float32)
     else:
         pts = np.asarray(mappoint_xyz, np.float32).reshape(-1, 3)
@@ -582,7 +592,7 @@ def make_track_scene(seed: int = 0, n_kp: int = 1200, n_frame_q: int = 400, n_lo
     # the current frame's pose: a small motion away from T0 (float32, as cv::Mat mTcw)
     dT = np.eye(4)
     dT[:3, :3] = _rodrigues(rng.normal(size=3) * 0.004)
-    dT[:3, 3] = rng.uniform(-0.004, 0.004, 3)
+    dT[:3, 3] = rng.uniform(-0.004, 0.004, 3) * scale
     Tc = (dT @ T0.astype(np.float64)).astype(np.float32)
     Ow = track.camera_center(Tc)
     Xc = pts.astype(np.float64) @ Tc[:3, :3].astype(np.float64).T + Tc[:3, 3].astype(np.float64)
@@ -615,7 +625,7 @@ def make_track_scene(seed: int = 0, n_kp: int = 1200, n_frame_q: int = 400, n_lo
                 koct.append(int(np.clip(poct[i], 0, levels - 1)))
                 kdesc.append(_flip_bits(rng, pdesc[i], rng.integers(0, 12)))
     n_extra = max(0, n_kp - len(kp))
-    kp += list(np.stack([rng.uniform(-5, 645, n_extra), rng.uniform(-5, 485, n_extra)], 1))
+    kp += list(np.stack([rng.uniform(x_lo - 5, x_hi + 5, n_extra), rng.uniform(y_lo - 5, y_hi + 5, n_extra)], 1))
     koct += list(rng.integers(0, levels, n_extra))
     kdesc += list(rng.integers(0, 256, (n_extra, 32), dtype=np.uint8))
     kp = np.asarray(kp, np.float32)

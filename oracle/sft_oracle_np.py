@@ -40,6 +40,27 @@ def se3_exp(u):
     return R, V @ up
 
 
+def rotation_from_f32_pose(R):
+    """The rotation the reference starts from: Converter::toSE3Quat hands the (float32-valued, hence only nearly orthonormal) matrix to
+    Eigen::Quaterniond(R) -- from the trace when it is positive, else from the largest diagonal entry -- and SE3Quat normalises the result.
+    For an orthonormal R every rule gives the same rotation; for a float32 one they differ by 1e-7, which a comparison to 1e-11 sees."""
+    R = np.asarray(R, float)
+    d = np.diag(R)
+    skew = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    if d.sum() > 0:
+        s = np.sqrt(d.sum() + 1.0)
+        q = np.append(skew * (0.5 / s), 0.5 * s)
+    else:
+        i = 0 if d[0] >= d[1] else 1
+        i = 2 if d[2] > d[i] else i
+        s = np.sqrt(2.0 * d[i] - d.sum() + 1.0)
+        q = np.append((R[i, :3] + R[:3, i]) * (0.5 / s), skew[i] * (0.5 / s))
+        q[i] = 0.5 * s
+    if q[3] < 0:
+        q = -q
+    return Rotation.from_quat(q / np.linalg.norm(q)).as_matrix()
+
+
 class Graph:
     def __init__(self, tc, Tcw, K, n_frame, obs_nodes, obs_bary, obs_uv, obs_invsig2, xyz, reg_lap, reg_inex, reg_temp, layers=1):
         self.tc = tc
@@ -47,7 +68,7 @@ class Graph:
         self.n = n
         self.K = np.asarray(K, float)
         T = np.asarray(Tcw, np.float32).astype(float)
-        self.R = Rotation.from_matrix(T[:3, :3]).as_matrix()
+        self.R = rotation_from_f32_pose(T[:3, :3])
         self.t = T[:3, 3].copy()
         self.xyz = np.array(xyz, float)
         self.obs_nodes = np.asarray(obs_nodes)

@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import irregular_meshes  # noqa: E402
+import operating_points  # noqa: E402
 import oracle  # noqa: E402
 from oracle import sft_oracle_np as onp  # noqa: E402
 from defslam_amd import synth  # noqa: E402
@@ -22,10 +23,14 @@ from defslam_amd import synth  # noqa: E402
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def case(name, rows, cols, m, pid, regs, keep_nodes=None, layers=1, tmpl=None):
-    """tmpl: a mesh of tests/irregular_meshes.py instead of the rows x cols grid."""
-    tmpl = synth.make_grid_template(rows, cols) if tmpl is None else tmpl
-    fr = synth.make_frame(tmpl, m, pid)
+def case(name, rows, cols, m, pid, regs, keep_nodes=None, layers=1, tmpl=None, point=None):
+    """tmpl: a mesh of tests/irregular_meshes.py instead of the rows x cols grid.  point: a case of tests/operating_points.py (camera,
+    world and weights other than the generator's defaults; regs is ignored)."""
+    if point is not None:
+        tmpl, fr, regs = operating_points.make_problem(point, rows, cols, m, pid)
+    else:
+        tmpl = synth.make_grid_template(rows, cols) if tmpl is None else tmpl
+        fr = synth.make_frame(tmpl, m, pid)
     if keep_nodes is not None:  # partial view: only observations whose facet lies in a corner of the mesh
         sel = np.all(np.isin(fr.obs_nodes, keep_nodes), axis=1)
         for k in ["obs_facet", "obs_nodes", "obs_bary", "obs_uv", "obs_invsig2"]:
@@ -39,6 +44,11 @@ def case(name, rows, cols, m, pid, regs, keep_nodes=None, layers=1, tmpl=None):
     print(name, "iters", r["iters"], "inliers", r["ret"], "M", fr.obs_nodes.shape[0])
 
 
+def operating_point_case():
+    name, rows, cols, m, pid = operating_points.GOLDEN_CASE
+    case(name.replace("/", "_"), rows, cols, m, pid, None, point=name)   # fx != fy, a pose 1.6 rad from identity, the webcam weights
+
+
 if __name__ == "__main__":
     regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
     case("grid10", 10, 10, 300, 0, regs)
@@ -46,3 +56,4 @@ if __name__ == "__main__":
     corner = [c + 10 * r for r in range(5) for c in range(5)]
     case("grid10_partial", 10, 10, 600, 5, regs, keep_nodes=corner)       # fixed nodes outside the viewed 1-ring
     case("disc14", 0, 0, 300, 1, regs, tmpl=irregular_meshes.disc(14, 4))       # a hub of degree 14: the longest lists the packer accepts
+    operating_point_case()

@@ -34,7 +34,8 @@ def _solve_gpu(ctx, tmpl_xyz0, facets, fr_like, regs, layers=1, max_iters=50):
     return f, inl
 
 
-def _compare(f, inl, r_xyz, r_pose7, r_trace, r_outlier, r_rep, r_inl):
+def _compare(f, inl, r_xyz, r_pose7, r_trace, r_outlier, r_rep, r_inl, scene_scale=1.0):
+    """scene_scale: the translation of the pose is in scene units, so its bound is POSE_TOL * max(1, scene scale)."""
     assert f.status == 0
     assert f.iters == r_trace.shape[0]
     np.testing.assert_array_equal(f.trace[:, 2], r_trace[:, 2])      # trials per iteration
@@ -42,7 +43,8 @@ def _compare(f, inl, r_xyz, r_pose7, r_trace, r_outlier, r_rep, r_inl):
     np.testing.assert_allclose(f.trace[:, [0, 1, 3, 4]], r_trace[:, [0, 1, 3, 4]], rtol=1e-8)
     scale = np.abs(r_xyz).max()
     assert np.abs(f.nodes_xyz - r_xyz).max() <= VERT_TOL * scale
-    assert np.abs(f.pose7 - r_pose7).max() <= POSE_TOL
+    assert np.abs(f.pose7[3:] - r_pose7[3:]).max() <= POSE_TOL
+    assert np.abs(f.pose7[:3] - r_pose7[:3]).max() <= POSE_TOL * max(1.0, scene_scale)
     np.testing.assert_array_equal(f.mvbOutlier, np.asarray(r_outlier, bool))
     assert inl == r_inl
     assert f.rep_error_f64 == pytest.approx(r_rep, rel=1e-9)

@@ -77,18 +77,26 @@ def test_shard_range_partitions_everything_once():
 # boundary is what dsh_sft_shared_solve all-reduces over RCCL: the rank's 6x6 Schur complement of the camera and its right-hand
 # side.  Here the per-rank normal equations come from the oracle (no GPU in this container) and the all-reduce is gloo; the
 # result must be the solution of the JOINT system the oracle builds for the union of the patches.
-def _camera_worker(rank, world, port, q):
+def _problem(rows, cols, m, pid, case):
+    """The generator's defaults, or an operating point of tests/operating_points.py: (template, frame, weights)."""
+    from defslam_amd import synth
+    if case is None:
+        tmpl = synth.make_grid_template(rows, cols)
+        return tmpl, synth.make_frame(tmpl, m, pid), (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
+    import operating_points as op
+    return op.make_problem(case, rows, cols, m, pid)
+
+
+def _camera_worker(rank, world, port, q, case=None):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle
-    from defslam_amd import synth
     from test_shared_camera_gpu import _split_template
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        tmpl = synth.make_grid_template(8, 14)
-        fr = synth.make_frame(tmpl, 500, 6)
+        tmpl, fr, regs = _problem(8, 14, 500, 6, case)
         rng = np.random.default_rng(3)
         fr.xyz = fr.xyz + rng.normal(scale=0.002, size=fr.xyz.shape)
         facets, patches = _split_template(tmpl, [7])
@@ -96,7 +104,7 @@ def _camera_worker(rank, world, port, q):
                            np.sort(facets, axis=1).view([("", np.int32)] * 3).ravel())
         for k in ["obs_facet", "obs_nodes", "obs_bary", "obs_uv", "obs_invsig2"]:
             setattr(fr, k, getattr(fr, k)[on_patch])
-        regs = np.array([synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP])
+        regs = np.array(regs)
         tcj = oracle.template_build(tmpl.xyz0, facets)
         # this rank's patch; the regulariser weights divide by the JOINT counts and the joint median edge length: scale the
         # patch's parameters so that its own normalisation gives the joint weights
@@ -138,11 +146,11 @@ def _camera_worker(rank, world, port, q):
         dist.destroy_process_group()
 
 
-def test_shared_camera_exchange_protocol_between_two_processes():
+def test_shared_camera_exchange_protocol_between_two_processes(case=None):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_camera_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_camera_worker, args=(r, 2, port, q, case)) for r in range(2)]
     for p in procs:
         p.start()
     got = sorted(q.get(timeout=300) for _ in range(2))
@@ -154,24 +162,28 @@ def test_shared_camera_exchange_protocol_between_two_processes():
         assert err_cam < 1e-9 and err_nodes < 1e-9 and err_chi < 1e-12
 
 
+def test_shared_camera_exchange_protocol_at_another_operating_point():
+    """The operating point test_shared_camera_gpu.py adds: fy > fx, a pose near a half turn about y, RegTemp = 0."""
+    test_shared_camera_exchange_protocol_between_two_processes("tall/turn_y/switch")
+
+
 # ---- the connected-mesh protocol between two real processes ---------------------------------------------------------------------
 # dsh_sft_connected_solve: ONE connected template, the band ordering cut at a separator of one bandwidth; rank g eliminates part g, the
 # ranks all-reduce their Schur contributions to the separator + camera system, solve it, back-substitute their part, and all-reduce the
 # pieces of the update.  Here the normal equations of the connected mesh come from the oracle (no GPU in this container), the two
 # all-reduces are gloo, and the result must be the solution of the undivided system.
-def _connected_worker(rank, world, port, q):
+def _connected_worker(rank, world, port, q, case=None):
     sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle
-    from defslam_amd import sft, synth
+    from defslam_amd import sft
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        tmpl = synth.make_grid_template(14, 9)            # connected 14 x 9 grid: nothing is dropped at the cut
-        fr = synth.make_frame(tmpl, 500, 11)
+        tmpl, fr, regs = _problem(14, 9, 500, 11, case)   # connected 14 x 9 grid: nothing is dropped at the cut
         fr.xyz = fr.xyz + np.random.default_rng(5).normal(scale=0.002, size=fr.xyz.shape)
         tc = oracle.template_build(tmpl.xyz0, tmpl.facets)
-        regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
         H, b, chi = oracle.sft_system(tc, fr.Tcw, fr.K, fr.n_frame, fr.obs_nodes, fr.obs_bary, fr.obs_uv, fr.obs_invsig2, fr.xyz, *regs)
         D = H.shape[0]
         Dn = D - 6
@@ -216,11 +228,11 @@ def _connected_worker(rank, world, port, q):
         dist.destroy_process_group()
 
 
-def test_connected_mesh_exchange_protocol_between_two_processes():
+def test_connected_mesh_exchange_protocol_between_two_processes(case=None):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_connected_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_connected_worker, args=(r, 2, port, q, case)) for r in range(2)]
     for p in procs:
         p.start()
     got = sorted(q.get(timeout=300) for _ in range(2))
@@ -230,3 +242,8 @@ def test_connected_mesh_exchange_protocol_between_two_processes():
     assert [g[0] for g in got] == [0, 1]
     for _, err, kd, s, c0 in got:
         assert err < 1e-9 and s >= kd and c0 > 0
+
+
+def test_connected_mesh_exchange_protocol_at_another_operating_point():
+    """The operating point test_shared_camera_gpu.py adds: fx != fy, a pose near a half turn about x, the webcam weights."""
+    test_connected_mesh_exchange_protocol_between_two_processes("hamlyn/turn_x/webcam")

@@ -61,19 +61,33 @@ def test_one_rank_equals_the_ordinary_solve(gpu_ctx):
     assert f.rep_error_f64 == pytest.approx(ref.rep_error_f64, rel=1e-10)
 
 
-@pytest.mark.parametrize("rows,cols,cuts,m,pid", [(10, 20, [10], 800, 1), (12, 24, [8, 16], 1200, 2)])
-def test_patches_on_separate_ranks_equal_the_joint_solve_of_the_oracle(oracle_mod, rows, cols, cuts, m, pid):
-    """The union of the patches as ONE problem for the oracle (one template of disconnected meshes, all observations, one camera)
-    against the shared-camera protocol with one rank per patch: same LM trajectory, joint pose, every patch's vertices."""
-    from defslam_amd import sft, synth
-    tmpl = synth.make_grid_template(rows, cols)
-    fr = synth.make_frame(tmpl, m, pid)
+def _joint_problem(rows, cols, cuts, m, pid, case=None):
+    """The union of the patches: (template, frame without the observations on facets that were cut away, joint facets, patches, weights).
+    case: an operating point of tests/operating_points.py (camera, world and weights other than the generator's defaults)."""
+    from defslam_amd import synth
+    if case is None:
+        tmpl = synth.make_grid_template(rows, cols)
+        fr = synth.make_frame(tmpl, m, pid)
+        regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
+    else:
+        import operating_points as op
+        tmpl, fr, regs = op.make_problem(case, rows, cols, m, pid)
     facets, patches = _split_template(tmpl, cuts)
     on_patch = np.isin(np.sort(tmpl.facets[fr.obs_facet], axis=1).view([("", np.int32)] * 3).ravel(), np.sort(facets, axis=1).view([("", np.int32)] * 3).ravel())
     for k in ["obs_facet", "obs_nodes", "obs_bary", "obs_uv", "obs_invsig2"]:      # observations on the facets that were cut away have no patch
         setattr(fr, k, getattr(fr, k)[on_patch])
+    return tmpl, fr, facets, patches, regs
+
+
+@pytest.mark.parametrize("rows,cols,cuts,m,pid,case", [(10, 20, [10], 800, 1, None), (12, 24, [8, 16], 1200, 2, None), (10, 20, [10], 800, 1, "tall/turn_y/switch")],
+                         ids=["10-20-cuts0-800-1", "12-24-cuts1-1200-2", "10-20-cuts0-800-1-tall/turn_y/switch"])
+def test_patches_on_separate_ranks_equal_the_joint_solve_of_the_oracle(oracle_mod, rows, cols, cuts, m, pid, case):
+    """The union of the patches as ONE problem for the oracle (one template of disconnected meshes, all observations, one camera)
+    against the shared-camera protocol with one rank per patch: same LM trajectory, joint pose, every patch's vertices.  The last case at
+    fy > fx, a pose near a half turn about y and RegTemp = 0 (every rank works the weights out on its own)."""
+    from defslam_amd import sft
+    tmpl, fr, facets, patches, regs = _joint_problem(rows, cols, cuts, m, pid, case)
     tc = oracle_mod.template_build(tmpl.xyz0, facets)
-    regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
     r = oracle_mod.sft_solve(tc, fr.Tcw, fr.K, fr.n_frame, fr.obs_nodes, fr.obs_bary, fr.obs_uv, fr.obs_invsig2, fr.xyz, *regs, ldlt_mode=1)
     ctxs = [sft.Context(0) for _ in patches]
     try:
@@ -118,17 +132,23 @@ def test_rccl_communicator_of_one_rank(gpu_ctx):
 
 
 # ---- one CONNECTED template cut across two ranks (dsh_sft_connected_solve*) -----------------------------------------------------
-@pytest.mark.parametrize("cfg,pid", [("smoke", 2), ("C2", 1), ("W12", 2), ("W16", 5)])
-def test_connected_mesh_cut_across_two_ranks_equals_the_oracle_solve_of_the_whole_mesh(oracle_mod, cfg, pid):
+@pytest.mark.parametrize("cfg,pid,case", [("smoke", 2, None), ("C2", 1, None), ("W12", 2, None), ("W16", 5, None), ("smoke", 2, "hamlyn/turn_x/webcam")],
+                         ids=["smoke-2", "C2-1", "W12-2", "W16-5", "smoke-2-hamlyn/turn_x/webcam"])
+def test_connected_mesh_cut_across_two_ranks_equals_the_oracle_solve_of_the_whole_mesh(oracle_mod, cfg, pid, case):
     """No facet is dropped at the cut: the template is the connected grid, every curvature / stretching / observation edge that crosses
     the cut is in the system through the separator (one bandwidth of unknowns, the 2-ring halo of the cut).  Two ranks (two contexts,
     the all-reduces are summation kernels), rank g factors part g: the Levenberg-Marquardt trajectory, pose and vertices are the
     oracle's solve of the whole connected mesh; both ranks end with bit-identical results.  Narrow bands (kd <= 128: smoke, C2) and wide
-    ones (kd = 182, 248) alike."""
+    ones (kd = 182, 248) alike.  The last case at another operating point (tests/operating_points.py): fx != fy, a pose near a half turn
+    about x, the webcam weights."""
     from defslam_amd import sft, synth
     tmpl, fr = synth.make_problem(cfg, pid)
-    tc = oracle_mod.template_build(tmpl.xyz0, tmpl.facets)
     regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
+    if case is not None:
+        import operating_points as op
+        rows, cols, m = synth.CONFIGS[cfg]
+        tmpl, fr, regs = op.make_problem(case, rows, cols, m, pid)
+    tc = oracle_mod.template_build(tmpl.xyz0, tmpl.facets)
     r = oracle_mod.sft_solve(tc, fr.Tcw, fr.K, fr.n_frame, fr.obs_nodes, fr.obs_bary, fr.obs_uv, fr.obs_invsig2, fr.xyz, *regs, ldlt_mode=1)
     ctxs = [sft.Context(0), sft.Context(0)]
     try:

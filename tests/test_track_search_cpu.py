@@ -6,13 +6,20 @@ import pytest
 import track_search_ref as R
 
 
-def hand_frame(kp, octave, state=None, desc=None, levels=8):
-    """Identity pose, 640 x 480, fx = fy = 500: a point (X, Y, 1) with dyadic X, Y projects exactly to (500 X + 320, 500 Y + 240)."""
+K_ISO, BOUNDS_ISO = (500, 500, 320, 240), (0, 640, 0, 480)
+# a dyadic anisotropic camera whose undistorted image area starts at negative coordinates: (X, Y, 1) with X, Y multiples of 1/1024 projects
+# exactly to (512 X + 300.5, 256 Y + 140.25); columns are 720 / 64 = 11.25 px wide, rows 288 / 48 = 6 px high
+K_DY, BOUNDS_DY = (512, 256, 300.5, 140.25), (-8, 712, -4, 284)
+
+
+def hand_frame(kp, octave, state=None, desc=None, levels=8, K=K_ISO, bounds=BOUNDS_ISO):
+    """Identity pose, 640 x 480, fx = fy = 500: a point (X, Y, 1) with dyadic X, Y projects exactly to (500 X + 320, 500 Y + 240).
+    K, bounds: another pinhole (fx, fy, cx, cy) and image area (mnMinX, mnMaxX, mnMinY, mnMaxY)."""
     from defslam_amd import track
     kp = np.asarray(kp, np.float32).reshape(-1, 2)
     N = kp.shape[0]
     sf, logsf = track.orb_pyramid(levels)
-    return track.TrackFrame(Tcw=np.eye(4, dtype=np.float32), K=np.array([500, 500, 320, 240], np.float32), bounds=np.array([0, 640, 0, 480], np.float32),
+    return track.TrackFrame(Tcw=np.eye(4, dtype=np.float32), K=np.array(K, np.float32), bounds=np.array(bounds, np.float32),
                             kp=kp, octave=np.asarray(octave, np.int32), desc=np.zeros((N, 32), np.uint8) if desc is None else desc,
                             scale_factors=sf, log_scale_factor=float(logsf), state=np.zeros(N, np.uint8) if state is None else np.asarray(state, np.uint8))
 
@@ -154,3 +161,79 @@ def test_image_bounds_are_inclusive(bounds, inside):
     fr = R.ref_frame(tf)
     nrm = P0 / np.float32(np.linalg.norm(P0))
     assert (R.is_in_frustum(fr, P0[0], nrm[0], np.float32(1.0)) is not None) == inside
+
+
+# ---- the same known answers at fx != fy with image bounds that start below zero (K_DY, BOUNDS_DY) ---------------------------------------
+UD, VD = np.float32(364.5), np.float32(156.25)   # projection of P0 = (0.125, 0.0625, 1): 512 / 8 + 300.5, 256 / 16 + 140.25
+# on the four bounds: (-8, -4) and (712, 284) are the projections of (-617 / 1024, -577 / 1024, 1) and (823 / 1024, 575 / 1024, 1)
+P_MIN = np.array([[-617.0 / 1024, -577.0 / 1024, 1.0]], np.float32)
+P_MAX = np.array([[823.0 / 1024, 575.0 / 1024, 1.0]], np.float32)
+# in the image only with fx on x and fy on y: v = 256 / 2 + 140.25 = 268.25 (swapped 396.25 > 284) -- and the other way round: u = 812.5 > 712
+# (swapped: 556.5, 204.25, inside)
+P_ONLY_UNSWAPPED = np.array([[0.125, 0.5, 1.0]], np.float32)
+P_ONLY_SWAPPED = np.array([[1.0, 0.125, 1.0]], np.float32)
+
+
+def dyadic_frame(kp, octave, **kw):
+    return hand_frame(kp, octave, K=K_DY, bounds=BOUNDS_DY, **kw)
+
+
+def test_dyadic_camera_projects_with_fx_on_x_and_fy_on_y():
+    """P0 lands on (364.5, 156.25), not on the swapped (332.5, 172.25); a point that only the right assignment of fx and fy puts into
+    the image is in view and matched, one that only the swapped assignment would put there is not."""
+    nrm = lambda P: P / np.float32(np.linalg.norm(P))
+    zero = np.zeros((1, 32), np.uint8)
+    tf = dyadic_frame([[UD, VD], [332.5, 172.25]], [0, 0])
+    fr = R.ref_frame(tf)
+    r = R.is_in_frustum(fr, P0[0], nrm(P0)[0], np.float32(1.0))
+    assert r is not None and r[0] == UD and r[1] == VD
+    m, n, _ = R.search_frame(fr, tf.state, P0, [0], zero, 3)           # r = 3 px: only the key point at the projection
+    assert m.tolist() == [0]
+    tf = dyadic_frame([[364.5, 268.25], [556.5, 204.25]], [0, 0])
+    fr = R.ref_frame(tf)
+    r = R.is_in_frustum(fr, P_ONLY_UNSWAPPED[0], nrm(P_ONLY_UNSWAPPED)[0], np.float32(1.0))
+    assert r is not None and (r[0], r[1]) == (np.float32(364.5), np.float32(268.25))
+    assert R.search_frame(fr, tf.state, P_ONLY_UNSWAPPED, [0], zero, 20)[0].tolist() == [0]
+    assert R.is_in_frustum(fr, P_ONLY_SWAPPED[0], nrm(P_ONLY_SWAPPED)[0], np.float32(1.0)) is None
+    assert R.search_frame(fr, tf.state, P_ONLY_SWAPPED, [0], zero, 20)[0].tolist() == [-1]
+
+
+def test_dyadic_window_edge_is_strict():
+    """|dx| == r is outside at fx != fy as well; the window is a square in pixels, not in normalised coordinates."""
+    tf = dyadic_frame([[UD + 20, VD], [UD, VD - 20], [UD + 19.75, VD - 19.75]], [0, 0, 0])
+    fr = R.ref_frame(tf)
+    assert fr.features_in_area(UD, VD, np.float32(20), -1, 1) == [2]
+    m, n, _ = R.search_frame(fr, tf.state, P0, [0], np.zeros((1, 32), np.uint8), 20)
+    assert m.tolist() == [2]
+
+
+DYADIC_BOUND_CASES = [(P_MIN, (-8, 712, -4, 284), True), (P_MIN, (-7.75, 712, -4, 284), False), (P_MIN, (-8, 712, -3.75, 284), False),
+                      (P_MAX, (-8, 712, -4, 284), True), (P_MAX, (-8, 711.75, -4, 284), False), (P_MAX, (-8, 712, -4, 283.75), False)]
+
+
+@pytest.mark.parametrize("P,bounds,inside", DYADIC_BOUND_CASES)
+def test_dyadic_image_bounds_are_inclusive_at_negative_minima(P, bounds, inside):
+    """A projection exactly on mnMinX = -8 / mnMinY = -4 (and on the maxima) is in; a quarter pixel beyond is out."""
+    tf = hand_frame([[UD, VD]], [0], K=K_DY, bounds=bounds)
+    fr = R.ref_frame(tf)
+    nrm = P / np.float32(np.linalg.norm(P))
+    assert (R.is_in_frustum(fr, P[0], nrm[0], np.float32(1.0)) is not None) == inside
+
+
+def test_dyadic_grid_cells_around_a_negative_minimum_bound():
+    """PosInGrid measures from mnMinX = -8, mnMinY = -4.  Rows are 6 px high: y = -1 is (y + 4) / 6 = 0.5 -> row 1 (half away from zero), y = -1.01
+    row 0.  Key points left of the image: x = -9 is column round(-1 / 11.25) = 0 -- the reference keeps it, in column 0 --, x = -14 is column
+    round(-6 / 11.25) = -1, in no cell.  Inside, x = -7 is column 0 and x = 4 column round(12 / 11.25) = 1."""
+    tf = dyadic_frame([[100.0, -1.0], [100.0, -1.01], [-9.0, 50.0], [-14.0, 50.0], [-7.0, 50.0], [4.0, 50.0]], [0] * 6)
+    fr = R.ref_frame(tf)
+    col = round(108.0 / 11.25)
+    assert 0 in fr.grid[col][1] and 1 in fr.grid[col][0]
+    assert fr.grid[0][9] == [2, 4] and fr.grid[1][9] == [5]
+    assert all(3 not in fr.grid[ix][iy] for ix in range(64) for iy in range(48))
+    # the search finds the key points on both sides of the bound: the projection (-8, 50) of (-617 / 1024, -90.25 / 256, 1) is on mnMinX
+    P = np.array([[-617.0 / 1024, -90.25 / 256, 1.0]], np.float32)
+    assert fr.features_in_area(np.float32(-8), np.float32(50), np.float32(20), -1, 1) == [2, 4, 5]
+    descs = np.stack([desc_with_dist(d) for d in (0, 0, 7, 1, 9, 20)])
+    tf = dyadic_frame(tf.kp, tf.octave, desc=descs)
+    m, n, _ = R.search_frame(R.ref_frame(tf), tf.state, P, [0], np.zeros((1, 32), np.uint8), 20)
+    assert m.tolist() == [2]   # the key point outside the image wins (distance 7); the better one at x = -14 (distance 1) is in no cell

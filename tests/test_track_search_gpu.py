@@ -4,7 +4,9 @@ import numpy as np
 import pytest
 
 import track_search_ref as R
-from test_track_search_cpu import P0, U, V, desc_with_dist, hand_frame
+import operating_points as op
+from test_track_search_cpu import (DYADIC_BOUND_CASES, K_DY, P0, P_ONLY_SWAPPED, P_ONLY_UNSWAPPED, U, UD, V, VD, desc_with_dist, dyadic_frame,
+                                   hand_frame)
 
 pytestmark = pytest.mark.gpu
 
@@ -251,3 +253,108 @@ def test_a_window_over_the_candidate_limit_is_refused(gpu_ctx):
         track.SearchByProjectionFrame(gpu_ctx, tf, fq, 20)
     tf = hand_frame(np.tile(np.array([[U + 1, V]], np.float32), (4096, 1)), np.zeros(4096))
     assert check_frame(gpu_ctx, tf, fq, 20).match.tolist() == [0]
+
+
+# ---- other cameras, image bounds and poses (tests/operating_points.py) -----------------------------------------------------------------------
+# (camera, world, image bounds or None for (0, width, 0, height), seed)
+MOVED_SCENES = [("hamlyn", "oblique", None, 31), ("tall", "turn_y", None, 32), ("webcam", "turn_x", None, 33), ("hamlyn", "turn_z", (-12.3, 707.7, -7.6, 280.4), 34),
+                ("tall", "oblique", None, 35)]
+_SCENES = {}
+
+
+def moved_scene(camera, world, bounds, seed):
+    """make_track_scene in a camera of the reference's settings files (fx != fy) and its image area, then the whole scene moved by a world:
+    points G x and normals R n as float32, the pose Tcw G^-1 as float32 (Ow follows from it).  Built once per scene and shared."""
+    key = (camera, world, bounds, seed)
+    if key not in _SCENES:
+        from defslam_amd import synth, track
+        fx, fy, cx, cy, w, h = op.CAMERAS[camera]
+        sc = synth.make_track_scene(seed, n_kp=1200, n_frame_q=400, n_local_q=300, state_mix=seed % 2 == 1, camera=(fx, fy, cx, cy),
+                                    bounds=(0.0, float(w), 0.0, float(h)) if bounds is None else bounds)
+        G = op.world_matrix(world)
+        mv = lambda x: (np.asarray(x, np.float64) @ G[:3, :3].T + G[:3, 3]).astype(np.float32)
+        tf = track.TrackFrame(**{**sc["frame"].__dict__, "Tcw": op.move_pose(G, sc["frame"].Tcw), "Ow": None})
+        assert op.quaternion_branch(tf.Tcw) == op.WORLD_BRANCH[world] and tf.K[0] != tf.K[1]
+        fq = track.FrameQueries(xyz=mv(sc["fq"].xyz), octave=sc["fq"].octave, desc=sc["fq"].desc)
+        lq = sc["lq"]
+        lq = track.LocalQueries(xyz=mv(lq.xyz), normal=(lq.normal.astype(np.float64) @ G[:3, :3].T).astype(np.float32), max_distance=lq.max_distance, desc=lq.desc,
+                                skip=lq.skip)
+        _SCENES[key] = (tf, fq, lq)
+    return _SCENES[key]
+
+
+@pytest.mark.parametrize("camera,world,bounds,seed", MOVED_SCENES, ids=[f"{c}-{w}" + ("-negative-bounds" if b else "") for c, w, b, _ in MOVED_SCENES])
+def test_both_searches_at_other_cameras_bounds_and_poses(gpu_ctx, camera, world, bounds, seed):
+    """fx > fy and fy > fx, image areas other than 640 x 480 (one that starts at a negative non-integer minimum), poses far from identity:
+    both searches at both thresholds, every output bit-exact against the restatement; and they do find the scene's matches."""
+    tf, fq, lq = moved_scene(camera, world, bounds, seed)
+    g20 = check_frame(gpu_ctx, tf, fq, 20)
+    g25 = check_frame(gpu_ctx, tf, fq, 25)
+    assert g20.nmatches > 0.3 * len(g20.match) and g25.nmatches > 0
+    g3 = check_local(gpu_ctx, tf, lq, 3)
+    g5 = check_local(gpu_ctx, tf, lq, 5)
+    assert g3.nmatches > 0 and g5.nmatches > 0 and g3.in_view.sum() > 0.3 * len(g3.match)
+
+
+def test_batch_of_frames_with_different_cameras_and_bounds(gpu_ctx):
+    """One batch whose frames differ in camera, image bounds and pose (a kernel that took problem 0's camera or bounds for all fails):
+    every problem gives what it gives alone, bit for bit, and what the restatement gives."""
+    from defslam_amd import track
+    items = []
+    for camera, world, bounds, seed in MOVED_SCENES[:4]:
+        tf, fq, lq = moved_scene(camera, world, bounds, seed)
+        items += [(tf, fq, 20), (tf, lq, 3)]
+    items = items[1:] + items[:1]                                   # neither sorted by frame nor by mode
+    batch = track.search_batch(gpu_ctx, items)
+    for (f, qs, th), b in zip(items, batch):
+        one = track.search_batch(gpu_ctx, [(f, qs, th)])[0]
+        np.testing.assert_array_equal(b.match, one.match)
+        assert b.nmatches == one.nmatches and b.nmatches > 0
+        if isinstance(qs, track.LocalQueries):
+            np.testing.assert_array_equal(b.in_view, one.in_view)
+            np.testing.assert_array_equal(b.level, one.level)
+            np.testing.assert_array_equal(b.uv, one.uv)
+            m, n, *_ = R.search_local(R.ref_frame(f), f.arrays()["state"], qs.xyz, qs.normal, qs.max_distance, qs.desc, qs.skip, th)
+        else:
+            m, n, _ = R.search_frame(R.ref_frame(f), f.arrays()["state"], qs.xyz, qs.octave, qs.desc, th)
+        np.testing.assert_array_equal(b.match, m)
+        assert b.nmatches == n
+
+
+def test_dyadic_anisotropic_camera_on_the_device(gpu_ctx):
+    """The known answers of test_track_search_cpu.py at fx = 512, fy = 256 and image bounds (-8, 712, -4, 284), on the device: fx on x and fy
+    on y (a point only the right assignment puts into the image; one only the swapped assignment would), the strict window edge, inclusive
+    bounds at negative minima, grid cells on both sides of a negative minimum bound."""
+    from defslam_amd import track
+    zero = np.zeros((1, 32), np.uint8)
+    nrm = lambda P: P / np.float32(np.linalg.norm(P))
+    one = np.array([1.0], np.float32)
+    tf = dyadic_frame([[UD, VD], [332.5, 172.25]], [0, 0])
+    assert check_frame(gpu_ctx, tf, track.FrameQueries(P0, [0], zero), 3).match.tolist() == [0]
+    g = check_local(gpu_ctx, tf, track.LocalQueries(P0, nrm(P0), one, zero), 1)
+    assert g.in_view[0] and g.uv[0].tolist() == [UD, VD] and g.match.tolist() == [0]
+    tf = dyadic_frame([[364.5, 268.25], [556.5, 204.25]], [0, 0])
+    assert check_frame(gpu_ctx, tf, track.FrameQueries(P_ONLY_UNSWAPPED, [0], zero), 20).match.tolist() == [0]
+    assert check_frame(gpu_ctx, tf, track.FrameQueries(P_ONLY_SWAPPED, [0], zero), 20).match.tolist() == [-1]
+    g = check_local(gpu_ctx, tf, track.LocalQueries(np.concatenate([P_ONLY_UNSWAPPED, P_ONLY_SWAPPED]), np.concatenate([nrm(P_ONLY_UNSWAPPED), nrm(P_ONLY_SWAPPED)]),
+                                                    np.array([1.0, 1.0], np.float32), np.zeros((2, 32), np.uint8)), 3)
+    assert g.in_view.tolist() == [True, False] and g.uv[0].tolist() == [364.5, 268.25] and g.match.tolist() == [0, -1]
+    tf = dyadic_frame([[UD + 20, VD], [UD, VD - 20], [UD + 19.75, VD - 19.75]], [0, 0, 0])
+    assert check_frame(gpu_ctx, tf, track.FrameQueries(P0, [0], zero), 20).match.tolist() == [2]
+    for P, bounds, inside in DYADIC_BOUND_CASES:
+        # the key point 6 / 4 px inside the image from the projection (closer to a max bound it would round to the column / row past the grid:
+        # columns are 11.25 px wide, rows 6 px high; the local search looks 7.5 px far)
+        kx = float(np.float32(512) * P[0, 0] + np.float32(300.5)) + (6.0 if P[0, 0] < 0 else -6.0)
+        ky = float(np.float32(256) * P[0, 1] + np.float32(140.25)) + (4.0 if P[0, 1] < 0 else -4.0)
+        tf = hand_frame([[kx, ky]], [0], K=K_DY, bounds=bounds)
+        assert (check_frame(gpu_ctx, tf, track.FrameQueries(P, [0], zero), 20).match[0] == 0) == inside, bounds
+        g = check_local(gpu_ctx, tf, track.LocalQueries(P, nrm(P), one, zero), 3)
+        assert bool(g.in_view[0]) == inside and (g.match[0] == 0) == inside, bounds
+    descs = np.stack([desc_with_dist(d) for d in (0, 0, 7, 1, 9, 20)])
+    tf = dyadic_frame([[100.0, -1.0], [100.0, -1.01], [-9.0, 50.0], [-14.0, 50.0], [-7.0, 50.0], [4.0, 50.0]], [0] * 6, desc=descs)
+    P = np.array([[-617.0 / 1024, -90.25 / 256, 1.0]], np.float32)          # projects to (-8, 50): on mnMinX
+    assert check_frame(gpu_ctx, tf, track.FrameQueries(P, [0], zero), 20).match.tolist() == [2]
+    # rows around y = -1: equal distances, the key point in the lower row (y = -1.01, row 0) is visited first and wins
+    Pr = np.array([[(100.0 - 300.5) / 512, (-1.0 - 140.25) / 256, 1.0]], np.float32)
+    tf = dyadic_frame([[100.0, -1.0], [100.0, -1.01]], [0, 0], desc=np.stack([desc_with_dist(3), desc_with_dist(3)]))
+    assert check_frame(gpu_ctx, tf, track.FrameQueries(Pr, [0], zero), 20).match.tolist() == [1]
