@@ -121,6 +121,11 @@ DSH_MPDB_NORMAL_DEPTH = 2
 DSH_MPDB_DESCRIPTOR = 4
 
 
+class TrackCloseCountsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("matches_inliers", "matches_outliers", "to_match_local", "observed", "inliers", "outliers",
+                                         "local_map_points", "n_moved")]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -143,6 +148,8 @@ EXPORTED_SYMBOLS = [
     "dsh_mpdb_update_points", "dsh_mpdb_set_points_bad", "dsh_mpdb_add_observations", "dsh_mpdb_erase_observations", "dsh_mpdb_add_keyframe",
     "dsh_mpdb_set_keyframe_point", "dsh_mpdb_set_keyframe_parent", "dsh_mpdb_set_keyframe_bad",
     "dsh_local_map_update", "dsh_local_map_points", "dsh_local_map_search",
+    "dsh_trackstate_set_embedding", "dsh_trackstate_clear_embedding", "dsh_trackstate_set_counters", "dsh_trackstate_get",
+    "dsh_trackstate_seed_local_points", "dsh_trackstate_repose", "dsh_trackstate_cull", "dsh_track_close_frame",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -265,6 +272,14 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_local_map_update.argtypes = [vp, C.c_int, c_i32_p, c_u8_p, i32, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p]
     L.dsh_local_map_points.argtypes = [vp, i32, c_i32_p, c_i32_p]
     L.dsh_local_map_search.argtypes = [vp, C.POINTER(TrackFrameC), C.c_float, i32, c_i32_p, c_i32_p, c_u8_p, c_i32_p, c_float_p, c_float_p, c_i32_p]
+    L.dsh_trackstate_set_embedding.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, c_double_p]
+    L.dsh_trackstate_clear_embedding.argtypes = [vp]
+    L.dsh_trackstate_set_counters.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, c_i32_p]
+    L.dsh_trackstate_get.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_float_p]
+    L.dsh_trackstate_seed_local_points.argtypes = [vp, C.c_int, c_i32_p]
+    L.dsh_trackstate_repose.argtypes = [vp, C.c_int, c_double_p, c_i32_p]
+    L.dsh_trackstate_cull.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_u8_p]
+    L.dsh_track_close_frame.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_i32_p, c_u8_p, C.c_int, c_double_p, i32, C.POINTER(TrackCloseCountsC)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

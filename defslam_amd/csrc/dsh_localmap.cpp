@@ -1,6 +1,8 @@
-// Host side of the map point store and the local map (include/defslam_hip.h: dsh_mpdb_*, dsh_local_map_*): the store's arrays in HBM,
-// the host mirror that validates (who observes whom, the keyframes' sizes), and per call one upload, the launches of
-// localmap_kernels.hip (and, for the search, of track_kernels.hip) and one download.
+// Host side of the map point store and the local map (include/defslam_hip.h: dsh_mpdb_*, dsh_local_map_*): the store's arrays in HBM and
+// the host mirror that validates (mpdb_store.h), and per call one upload, the launches of localmap_kernels.hip (and, for the search, of
+// track_kernels.hip) and one download.  The entries here also keep the per-point tracking state of dsh_trackstate_* current
+// (trackclose_kernels.hip): new points start at mnVisible = mnFound = 1, observations count into nObs, the update keeps the previous
+// local point list, the search adds SearchLocalPoints' IncreaseVisible.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,82 +16,11 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "localmap_problem.h"
+#include "mpdb_store.h"
+#include "trackclose_problem.h"
 #include "track_problem.h"
 
-struct dsh_mpdb : dsh_store {
-  int32_t P = 0, Pcap = 0, K = 0, Kcap = 0;
-  long long R = 0, Rcap = 0, T = 0, Tcap = 0;   // log records, table entries
-  // points
-  float *d_xyz = nullptr, *d_nrm = nullptr, *d_maxd = nullptr;
-  uint4* d_desc = nullptr;
-  int32_t *d_bad = nullptr, *d_cnt = nullptr, *d_local_ids = nullptr;
-  // observations, keyframes, the resident local map
-  int2* d_log = nullptr;
-  LmKf* d_kf = nullptr;
-  int32_t *d_table = nullptr, *d_local_kf = nullptr;
-  LmHdr* d_hdr = nullptr;
-  // host mirror
-  std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
-  std::vector<LmKf> kf;
-  int32_t n_local_points = 0;
-
-  void free_all() {
-    for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_log, (void*)d_kf,
-                    (void*)d_table, (void*)d_local_kf, (void*)d_hdr})
-      if (p) (void)hipFree(p);
-  }
-};
-
 namespace {
-
-uint64_t obs_key(int32_t point, int32_t slot) { return ((uint64_t)(uint32_t)point << 32) | (uint32_t)slot; }
-
-// grow-on-demand device array of T: a new allocation, the `used` leading elements copied device to device
-template <class T>
-hipError_t grow(T** p, size_t used, size_t cap) {
-  return dsh_store_grow((void**)p, sizeof(T) * cap, [&](char* q) { return used ? hipMemcpy(q, *p, sizeof(T) * used, hipMemcpyDeviceToDevice) : hipSuccess; });
-}
-
-hipError_t reserve_points(dsh_mpdb* db, long long need) {
-  if (need <= db->Pcap) return hipSuccess;
-  const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Pcap), INT32_MAX), P = (size_t)db->P;
-  hipError_t e;
-  if ((e = grow(&db->d_xyz, 3 * P, 3 * cap)) != hipSuccess || (e = grow(&db->d_nrm, 3 * P, 3 * cap)) != hipSuccess ||
-      (e = grow(&db->d_maxd, P, cap)) != hipSuccess || (e = grow(&db->d_desc, 2 * P, 2 * cap)) != hipSuccess ||
-      (e = grow(&db->d_bad, P, cap)) != hipSuccess || (e = grow(&db->d_cnt, P, cap)) != hipSuccess ||
-      (e = grow(&db->d_local_ids, P, cap)) != hipSuccess)
-    return e;
-  db->Pcap = (int32_t)cap;
-  return hipSuccess;
-}
-
-hipError_t reserve_keyframes(dsh_mpdb* db, long long need) {
-  if (need <= db->Kcap) return hipSuccess;
-  const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Kcap), INT32_MAX), K = (size_t)db->K;
-  hipError_t e;
-  if ((e = grow(&db->d_kf, K, cap)) != hipSuccess || (e = grow(&db->d_local_kf, K, cap)) != hipSuccess) return e;
-  db->Kcap = (int32_t)cap;
-  return hipSuccess;
-}
-
-// the first checks of every entry point: a store that is alive and attached
-#define MPDB_ENTER(who)                              \
-  if (!db || !db->ctx) return DSH_ERR_ARG;           \
-  dsh_ctx_base* c = db->ctx;                         \
-  auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, std::string(who) + ": " + m); }
-
-// n distinct ids inside [0, count)
-std::string ids_error(int n, const int32_t* ids, int32_t count, const char* what) {
-  if (n < 0) return "n < 0";
-  if (n > 0 && !ids) return std::string(what) + " array is NULL";
-  std::vector<int32_t> s(ids, ids + n);
-  std::sort(s.begin(), s.end());
-  for (int i = 0; i < n; i++) {
-    if (s[i] < 0 || s[i] >= count) return std::string(what) + " " + std::to_string(s[i]) + " outside the store";
-    if (i > 0 && s[i] == s[i - 1]) return std::string(what) + " " + std::to_string(s[i]) + " repeated in the batch";
-  }
-  return "";
-}
 
 // one int32 of the store, written in stream order
 int put_i32(dsh_ctx_base* c, int32_t* dst, int32_t v) {
@@ -116,7 +47,7 @@ int dsh_mpdb_create(const dsh_mpdb_desc* desc, dsh_mpdb** out) {
     if (const int rc = dsh_enter(c, "dsh_mpdb_create")) { delete db; return rc; }
     db->Tcap = (long long)desc->keyframe_capacity * 1024;
     db->Rcap = desc->observation_capacity;
-    if (reserve_points(db, desc->point_capacity) != hipSuccess || reserve_keyframes(db, desc->keyframe_capacity) != hipSuccess ||
+    if (mpdb_reserve_points(db, desc->point_capacity) != hipSuccess || mpdb_reserve_keyframes(db, desc->keyframe_capacity) != hipSuccess ||
         hipMalloc((void**)&db->d_log, sizeof(int2) * (size_t)db->Rcap) != hipSuccess ||
         hipMalloc((void**)&db->d_table, 4 * (size_t)db->Tcap) != hipSuccess || hipMalloc((void**)&db->d_hdr, sizeof(LmHdr)) != hipSuccess ||
         hipMemset(db->d_hdr, 0, sizeof(LmHdr)) != hipSuccess) {
@@ -149,7 +80,10 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   }
   db->P = db->K = 0;
   db->R = db->T = 0;
-  db->n_local_points = 0;
+  db->n_local_points = db->n_ref_points = db->P_cnt = 0;
+  db->top_node.clear();
+  db->max_node = -1;
+  db->max_node_stale = false;
   db->obs.clear();
   db->kf.clear();
   return DSH_OK;
@@ -167,7 +101,7 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
   if (const int rc = dsh_enter(c, "dsh_mpdb_add_points")) return rc;
   if (first_id) *first_id = db->P;
   if (n == 0) return DSH_OK;
-  HIPCHK(c, reserve_points(db, (long long)db->P + n));
+  HIPCHK(c, mpdb_reserve_points(db, (long long)db->P + n));
   std::vector<int32_t> b32(n, 0);
   if (bad_flags)
     for (int i = 0; i < n; i++) b32[i] = bad_flags[i] ? 1 : 0;
@@ -178,8 +112,13 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
   HIPCHK(c, hipMemcpyAsync(db->d_maxd + P, max_distance, 4 * (size_t)n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(db->d_desc + 2 * P, desc, 32 * (size_t)n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(db->d_bad + P, b32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+  TcState ts;
+  ts.xyz = db->d_xyz; ts.bad = db->d_bad; ts.visible = db->d_visible; ts.found = db->d_found; ts.nobs = db->d_nobs; ts.nodes = db->d_nodes;
+  ts.bary = db->d_bary;
+  HIPCHK(c, tc_init_points_launch(ts, db->P, n, st));   // mnVisible = mnFound = 1, nObs = 0, no facet
   HIPCHK(c, hipStreamSynchronize(st));
   db->P += n;
+  db->top_node.resize((size_t)db->P, -1);
   return DSH_OK;
 }
 
@@ -188,7 +127,7 @@ int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what
   MPDB_ENTER("dsh_mpdb_update_points");
   if (what < 1 || what > (DSH_MPDB_POSITION | DSH_MPDB_NORMAL_DEPTH | DSH_MPDB_DESCRIPTOR))
     return bad("what is not a non-empty mask of DSH_MPDB_POSITION, DSH_MPDB_NORMAL_DEPTH, DSH_MPDB_DESCRIPTOR");
-  const std::string ie = ids_error(n, ids, db->P, "point id");
+  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
   if (!ie.empty()) return bad(ie);
   const bool wp = (what & DSH_MPDB_POSITION) != 0, wn = (what & DSH_MPDB_NORMAL_DEPTH) != 0, wd = (what & DSH_MPDB_DESCRIPTOR) != 0;
   if (n > 0 && ((wp && !xyz) || (wn && (!normal || !max_distance)) || (wd && !desc))) return bad("an array that `what` selects is NULL");
@@ -222,7 +161,7 @@ int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what
 
 int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8_t* bad_flags) {
   MPDB_ENTER("dsh_mpdb_set_points_bad");
-  const std::string ie = ids_error(n, ids, db->P, "point id");
+  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
   if (!ie.empty()) return bad(ie);
   if (const int rc = dsh_enter(c, "dsh_mpdb_set_points_bad")) return rc;
   if (n == 0) return DSH_OK;
@@ -253,22 +192,23 @@ int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, con
     const std::string at = "pair " + std::to_string(i) + ": ";
     if (p < 0 || p >= db->P) return bad(at + "point id outside the store");
     if (s < 0 || s >= db->K) return bad(at + "keyframe slot outside the store");
-    if (db->obs.count(obs_key(p, s))) return bad(at + "the point already observes this keyframe");
-    if (!batch.insert(obs_key(p, s)).second) return bad(at + "repeated in the batch");
+    if (db->obs.count(mpdb_obs_key(p, s))) return bad(at + "the point already observes this keyframe");
+    if (!batch.insert(mpdb_obs_key(p, s)).second) return bad(at + "repeated in the batch");
   }
   if (const int rc = dsh_enter(c, "dsh_mpdb_add_observations")) return rc;
   if (n == 0) return DSH_OK;
   if (db->R + n > db->Rcap) {
     const long long cap = std::max(db->R + n, 2 * db->Rcap);
-    HIPCHK(c, grow(&db->d_log, (size_t)db->R, (size_t)cap));
+    HIPCHK(c, mpdb_grow(&db->d_log, (size_t)db->R, (size_t)cap));
     db->Rcap = cap;
   }
   HIPCHK(c, c->pin_in.ensure(8 * (size_t)n, true));
   int2* h = reinterpret_cast<int2*>(c->pin_in.p);
   for (int i = 0; i < n; i++) h[i] = make_int2(point_ids[i], keyframe_slots[i]);
   HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, tc_add_by_index_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log + db->R), 2, 1, n, c->stream));   // nObs++ (MapPoint.cc:116-119)
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; i++) db->obs[obs_key(point_ids[i], keyframe_slots[i])] = db->R + i;
+  for (int i = 0; i < n; i++) db->obs[mpdb_obs_key(point_ids[i], keyframe_slots[i])] = db->R + i;
   db->R += n;
   return DSH_OK;
 }
@@ -287,7 +227,7 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
   std::vector<int32_t> idx;
   std::vector<uint64_t> keys;
   for (int i = 0; i < n; i++) {
-    const uint64_t k = obs_key(point_ids[i], keyframe_slots[i]);
+    const uint64_t k = mpdb_obs_key(point_ids[i], keyframe_slots[i]);
     const auto it = db->obs.find(k);
     if (it == db->obs.end() || std::find(keys.begin(), keys.end(), k) != keys.end()) continue;
     if (it->second > (INT32_MAX >> 1)) return bad("log too long to erase from");
@@ -301,6 +241,8 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
   void* dup = nullptr;
   HIPCHK(c, c->scratch.take(bytes, &dup));
   HIPCHK(c, hipMemcpyAsync(dup, c->pin_in.p, bytes, hipMemcpyHostToDevice, c->stream));
+  // nObs-- of every pair that was found (MapPoint.cc:114-133), read from the records before they are blanked
+  HIPCHK(c, tc_add_by_record_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log), static_cast<const int32_t*>(dup), -1, (int)idx.size(), c->stream));
   HIPCHK(c, lm_scatter_i32_launch(reinterpret_cast<int32_t*>(db->d_log), static_cast<const int32_t*>(dup), nullptr, -1, (int)idx.size(), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (const uint64_t k : keys) db->obs.erase(k);
@@ -316,10 +258,10 @@ int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_
   if (parent < -1 || parent >= db->K) return bad("parent is neither -1 nor a slot of the store");
   if (db->K == INT32_MAX || db->T + N > INT32_MAX) return bad("store full");
   if (const int rc = dsh_enter(c, "dsh_mpdb_add_keyframe")) return rc;
-  HIPCHK(c, reserve_keyframes(db, (long long)db->K + 1));
+  HIPCHK(c, mpdb_reserve_keyframes(db, (long long)db->K + 1));
   if (db->T + N > db->Tcap) {
     const long long cap = std::max(db->T + N, 2 * db->Tcap);
-    HIPCHK(c, grow(&db->d_table, (size_t)db->T, (size_t)cap));
+    HIPCHK(c, mpdb_grow(&db->d_table, (size_t)db->T, (size_t)cap));
     db->Tcap = cap;
   }
   LmKf k;
@@ -386,6 +328,11 @@ int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8
   HIPCHK(c, c->scratch.take(down_bytes, &ddown));
   if (N > 0) HIPCHK(c, hipMemcpyAsync(dup, c->pin_in.p, 4 * (size_t)N, hipMemcpyHostToDevice, st));
   char* dd = static_cast<char*>(ddown);
+  // Tracking.cc:1475: SetReferenceMapPoints(mvpLocalMapPoints) before the list is rebuilt -- the list this call found stays, as the
+  // reference list of dsh_track_close_frame, and the new one is written into the other buffer
+  std::swap(db->d_local_ids, db->d_ref_ids);
+  db->n_ref_points = db->n_local_points;
+  db->P_cnt = db->P;
   LmBufs b;
   b.P = db->P; b.K = db->K; b.N = N; b.R = db->R;
   b.bad = db->d_bad; b.log = db->d_log; b.kf = db->d_kf; b.table = db->d_table;
@@ -443,7 +390,12 @@ int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, i
   if (Q > (1 << 28)) return bad("too many local points");
   if (const int rc = dsh_enter(c, "dsh_local_map_search")) return rc;
   if (nmatches) *nmatches = 0;
-  if (Q == 0) return DSH_OK;
+  if (Q == 0) {
+    // no query, but the frame's own points are still seen (Tracking.cc:1408-1425)
+    HIPCHK(c, tc_visible_launch(db->d_visible, db->d_cnt, db->P_cnt, nullptr, nullptr, 0, nullptr, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSH_OK;
+  }
 
   // up: the frame and its key points; the queries are gathered from the store on the device
   const dsh_track_frame& f = *frame;
@@ -517,6 +469,8 @@ int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, i
   b.vcos = reinterpret_cast<float*>(dd + d_vcos);
   b.pstat = reinterpret_cast<int32_t*>(dd + d_pstat);
   HIPCHK(c, trk_launch(b, 1, Q, st));
+  // MapPoint::IncreaseVisible of the points the frame holds and of the queries in view (Tracking.cc:1408-1425, :1456); not when the search refuses
+  HIPCHK(c, tc_visible_launch(db->d_visible, db->d_cnt, db->P_cnt, g.out_ids, b.inview, Q, b.pstat + 2, st));
   HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
 

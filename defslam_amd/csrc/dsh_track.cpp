@@ -9,11 +9,17 @@
 #include "dsh_ctx.h"
 #include "track_problem.h"
 
-std::string trk_frame_error(const dsh_track_frame& f) {
+std::string trk_pose_error(const dsh_track_frame& f) {
   if (!f.Tcw) return "Tcw is NULL";
   for (int k = 0; k < 4; k++)
     if (!std::isfinite(f.K[k]) || !std::isfinite(f.bounds[k])) return "K / bounds not finite";
   if (!(f.bounds[1] > f.bounds[0]) || !(f.bounds[3] > f.bounds[2])) return "empty image bounds";
+  return "";
+}
+
+std::string trk_frame_error(const dsh_track_frame& f) {
+  const std::string pe = trk_pose_error(f);
+  if (!pe.empty()) return pe;
   if (f.grid_cols <= 0 || f.grid_rows <= 0 || (long long)f.grid_cols * f.grid_rows > TRK_MAX_CELLS) return "grid size outside 1 .. 8192 cells";
   if (f.levels <= 0 || f.levels > TRK_MAX_LEVELS || !f.scale_factors) return "levels outside 1 .. 32 or no scale factors";
   if (f.N < 0 || f.N > TRK_MAX_KEYPOINTS) return "N outside 0 .. 8192";
@@ -25,7 +31,7 @@ std::string trk_frame_error(const dsh_track_frame& f) {
   return "";
 }
 
-void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int Q) {
+void trk_fill_pose(TrkProb& P, const dsh_track_frame& f) {
   std::memset(&P, 0, sizeof(P));
   for (int i = 0; i < 3; i++) {
     for (int k = 0; k < 3; k++) P.R[3 * i + k] = f.Tcw[4 * i + k];
@@ -34,6 +40,10 @@ void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int
   }
   P.fx = f.K[0]; P.fy = f.K[1]; P.cx = f.K[2]; P.cy = f.K[3];
   P.minX = f.bounds[0]; P.maxX = f.bounds[1]; P.minY = f.bounds[2]; P.maxY = f.bounds[3];
+}
+
+void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int Q) {
+  trk_fill_pose(P, f);
   // Frame.cc:97-98: mfGridElementWidthInv = float(FRAME_GRID_COLS) / (mnMaxX - mnMinX)
   P.winv = (float)f.grid_cols / (P.maxX - P.minX);
   P.hinv = (float)f.grid_rows / (P.maxY - P.minY);

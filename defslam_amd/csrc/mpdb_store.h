@@ -1,0 +1,107 @@
+// The map point store dsh_mpdb as its two translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*) and dsh_trackclose.cpp
+// (dsh_trackstate_*, dsh_track_close_frame).  The arrays in HBM, the host mirror that validates, and the first checks of an entry point.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/defslam_hip.h"
+#include "dsh_ctx.h"
+#include "localmap_problem.h"
+
+struct dsh_mpdb : dsh_store {
+  int32_t P = 0, Pcap = 0, K = 0, Kcap = 0;
+  long long R = 0, Rcap = 0, T = 0, Tcap = 0;   // log records, table entries
+  // points
+  float *d_xyz = nullptr, *d_nrm = nullptr, *d_maxd = nullptr;
+  uint4* d_desc = nullptr;
+  int32_t *d_bad = nullptr, *d_cnt = nullptr, *d_local_ids = nullptr;
+  // tracking state per point (dsh_trackstate_*, dsh_track_close_frame): mnVisible, mnFound, nObs, the facet as three ascending node
+  // indices (-1: none) with its barycentrics, and the local point list as it was before the last dsh_local_map_update
+  int32_t *d_visible = nullptr, *d_found = nullptr, *d_nobs = nullptr, *d_nodes = nullptr, *d_ref_ids = nullptr;
+  double* d_bary = nullptr;
+  // observations, keyframes, the resident local map
+  int2* d_log = nullptr;
+  LmKf* d_kf = nullptr;
+  int32_t *d_table = nullptr, *d_local_kf = nullptr;
+  LmHdr* d_hdr = nullptr;
+  // host mirror
+  std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
+  std::vector<LmKf> kf;
+  int32_t n_local_points = 0;
+  int32_t n_ref_points = 0;            // length of d_ref_ids
+  int32_t P_cnt = 0;                   // points d_cnt covers: the store's size at the last dsh_local_map_update
+  std::vector<int32_t> top_node;       // per point its largest node index, -1 without a facet
+  int32_t max_node = -1;               // the largest of top_node, unless max_node_stale
+  bool max_node_stale = false;
+
+  int32_t largest_node() {
+    if (max_node_stale) {
+      max_node = -1;
+      for (const int32_t v : top_node) max_node = std::max(max_node, v);
+      max_node_stale = false;
+    }
+    return max_node;
+  }
+  void free_all() {
+    for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
+                    (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
+                    (void*)d_local_kf, (void*)d_hdr})
+      if (p) (void)hipFree(p);
+  }
+};
+
+inline uint64_t mpdb_obs_key(int32_t point, int32_t slot) { return ((uint64_t)(uint32_t)point << 32) | (uint32_t)slot; }
+
+// grow-on-demand device array of T: a new allocation, the `used` leading elements copied device to device
+template <class T>
+hipError_t mpdb_grow(T** p, size_t used, size_t cap) {
+  return dsh_store_grow((void**)p, sizeof(T) * cap, [&](char* q) { return used ? hipMemcpy(q, *p, sizeof(T) * used, hipMemcpyDeviceToDevice) : hipSuccess; });
+}
+
+inline hipError_t mpdb_reserve_points(dsh_mpdb* db, long long need) {
+  if (need <= db->Pcap) return hipSuccess;
+  const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Pcap), INT32_MAX), P = (size_t)db->P;
+  hipError_t e;
+  if ((e = mpdb_grow(&db->d_xyz, 3 * P, 3 * cap)) != hipSuccess || (e = mpdb_grow(&db->d_nrm, 3 * P, 3 * cap)) != hipSuccess ||
+      (e = mpdb_grow(&db->d_maxd, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_desc, 2 * P, 2 * cap)) != hipSuccess ||
+      (e = mpdb_grow(&db->d_bad, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_cnt, P, cap)) != hipSuccess ||
+      (e = mpdb_grow(&db->d_local_ids, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_ref_ids, P, cap)) != hipSuccess ||
+      (e = mpdb_grow(&db->d_visible, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_found, P, cap)) != hipSuccess ||
+      (e = mpdb_grow(&db->d_nobs, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_nodes, 3 * P, 3 * cap)) != hipSuccess ||
+      (e = mpdb_grow(&db->d_bary, 3 * P, 3 * cap)) != hipSuccess)
+    return e;
+  db->Pcap = (int32_t)cap;
+  return hipSuccess;
+}
+
+inline hipError_t mpdb_reserve_keyframes(dsh_mpdb* db, long long need) {
+  if (need <= db->Kcap) return hipSuccess;
+  const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Kcap), INT32_MAX), K = (size_t)db->K;
+  hipError_t e;
+  if ((e = mpdb_grow(&db->d_kf, K, cap)) != hipSuccess || (e = mpdb_grow(&db->d_local_kf, K, cap)) != hipSuccess) return e;
+  db->Kcap = (int32_t)cap;
+  return hipSuccess;
+}
+
+// the first checks of every entry point: a store that is alive and attached
+#define MPDB_ENTER(who)                              \
+  if (!db || !db->ctx) return DSH_ERR_ARG;           \
+  dsh_ctx_base* c = db->ctx;                         \
+  auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, std::string(who) + ": " + m); }
+
+// n distinct ids inside [0, count)
+inline std::string mpdb_ids_error(int n, const int32_t* ids, int32_t count, const char* what) {
+  if (n < 0) return "n < 0";
+  if (n > 0 && !ids) return std::string(what) + " array is NULL";
+  std::vector<int32_t> s(ids, ids + n);
+  std::sort(s.begin(), s.end());
+  for (int i = 0; i < n; i++) {
+    if (s[i] < 0 || s[i] >= count) return std::string(what) + " " + std::to_string(s[i]) + " outside the store";
+    if (i > 0 && s[i] == s[i - 1]) return std::string(what) + " " + std::to_string(s[i]) + " repeated in the batch";
+  }
+  return "";
+}

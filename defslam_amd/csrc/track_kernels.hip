@@ -15,6 +15,7 @@
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
+#include "track_frustum.h"
 #include "track_problem.h"
 
 namespace {
@@ -23,13 +24,6 @@ __device__ __forceinline__ int kdist(unsigned long long k) { return (int)(k >> 4
 __device__ __forceinline__ int kidx(unsigned long long k) { return (int)((k >> 8) & 0xFFFF); }
 __device__ __forceinline__ int klevel(unsigned long long k) { return (int)(k & 0x7F); }
 __device__ __forceinline__ bool kstate2(unsigned long long k) { return (k & 0x80) != 0; }
-
-// x3Dc = Rcw * x3Dw + tcw of a float cv::Mat: the three products summed in float32 in row order, tcw added in double and
-// rounded once (OpenCV's gemm for 3-element operands accumulates in the element type and adds C in double)
-__device__ __forceinline__ float cam_coord(const TrkProb& P, int k, float x, float y, float z) {
-  const float s = P.R[3 * k] * x + P.R[3 * k + 1] * y + P.R[3 * k + 2] * z;
-  return (float)((double)s + (double)P.t[k]);
-}
 
 // Frame::GetFeaturesInArea (Frame.cc:421-480): the grid cells of the window, false when it is empty
 __device__ __forceinline__ bool window_cells(const TrkProb& P, float u, float v, float r, int& c0, int& c1, int& r0, int& r1) {
@@ -182,7 +176,7 @@ __global__ __launch_bounds__(256) void trk_search_kernel(TrkBufs b, int Qt) {
   int lmin = 0, lmax = 0, level = 0;
   if (P.mode == 0) {
     // ORBmatcher.cc:1389-1411: invzc = 1.0 / z in double, stored as float; radius = th * mvScaleFactors[nLastOctave]
-    const float xc = cam_coord(P, 0, x, y, z), yc = cam_coord(P, 1, x, y, z), zc = cam_coord(P, 2, x, y, z);
+    const float xc = trk_cam_coord(P, 0, x, y, z), yc = trk_cam_coord(P, 1, x, y, z), zc = trk_cam_coord(P, 2, x, y, z);
     const float invzc = (float)(1.0 / (double)zc);
     if (invzc < 0) live = false;
     u = P.fx * xc * invzc + P.cx;
@@ -193,21 +187,12 @@ __global__ __launch_bounds__(256) void trk_search_kernel(TrkBufs b, int Qt) {
     lmin = meta - 1;
     lmax = meta + 1;
   } else {
-    // Frame::isInFrustum(pMP, 0.5) (Frame.cc:338-390) without a distance-range test, MapPoint::PredictScale (MapPoint.cc:422-437)
+    // Frame::isInFrustum(pMP, 0.5) (track_frustum.h), MapPoint::PredictScale (MapPoint.cc:422-437)
+    TrkView w;
+    live = trk_in_frustum(P, x, y, z, b.qnrm[3 * (size_t)gq], b.qnrm[3 * (size_t)gq + 1], b.qnrm[3 * (size_t)gq + 2], w);
     if (meta) live = false;
-    const float PcX = cam_coord(P, 0, x, y, z), PcY = cam_coord(P, 1, x, y, z), PcZ = cam_coord(P, 2, x, y, z);
-    if (PcZ < 0.0f) live = false;
-    const float invz = 1.0f / PcZ;
-    u = P.fx * PcX * invz + P.cx;
-    v = P.fy * PcY * invz + P.cy;
-    if (u < P.minX || u > P.maxX) live = false;
-    if (v < P.minY || v > P.maxY) live = false;
-    const float POx = x - P.Ow[0], POy = y - P.Ow[1], POz = z - P.Ow[2];
-    const float dist = (float)sqrt((double)POx * (double)POx + (double)POy * (double)POy + (double)POz * (double)POz);   // cv::norm
-    const float nx = b.qnrm[3 * (size_t)gq], ny = b.qnrm[3 * (size_t)gq + 1], nz = b.qnrm[3 * (size_t)gq + 2];
-    const double dot = (double)POx * (double)nx + (double)POy * (double)ny + (double)POz * (double)nz;   // cv::Mat::dot
-    vc = (float)(dot / (double)dist);
-    if (vc < 0.5f) live = false;
+    u = w.u; v = w.v; vc = w.vc;
+    const float dist = w.dist;
     const float ratio = b.qmaxd[gq] / dist;
     level = (int)ceil(log((double)ratio) / (double)P.logsf);
     if (level < 0) level = 0;

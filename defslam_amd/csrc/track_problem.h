@@ -67,3 +67,6 @@ extern "C" hipError_t trk_launch(const TrkBufs& b, int B, int Qt, hipStream_t st
 // what is wrong with a frame ("" when nothing is), and a frame as a TrkProb -- everything but the offsets into the concatenated buffers.
 std::string trk_frame_error(const dsh_track_frame& f);
 void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int Q);
+// The part of both that the frustum test alone reads (dsh_track_close_frame): Tcw, Ow, K and the image bounds; the rest of P is zero.
+std::string trk_pose_error(const dsh_track_frame& f);
+void trk_fill_pose(TrkProb& P, const dsh_track_frame& f);

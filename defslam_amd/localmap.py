@@ -2,7 +2,9 @@
 
   * Tracking::UpdateLocalMap = Tracking::UpdateLocalKeyFrames (Thirdparty/ORBSLAM_2/src/Tracking.cc:1510-1629) +
     DefTracking::UpdateLocalPoints (Modules/Tracking/DefTracking.cc:426-454);
-  * Tracking::SearchLocalPoints (Tracking.cc:1405-1470) with the resident local points as queries.
+  * Tracking::SearchLocalPoints (Tracking.cc:1405-1470) with the resident local points as queries;
+  * the back half of DefTracking::TrackLocalMap (DefTracking.cc:253-339) on the store's per-point tracking state (dsh_trackstate_*,
+    dsh_track_close_frame): the position write-back of DefPoseOptimization, the counting loops, LocalMapping::MapPointCulling.
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -45,6 +47,32 @@ class LocalSearch:
     uv: np.ndarray                      # (Q,2) mTrackProjX, mTrackProjY
     view_cos: np.ndarray                # mTrackViewCos
     nmatches: int
+
+
+@dataclass
+class PointState:
+    """What dsh_trackstate_get returns, per id asked for."""
+    visible: np.ndarray                 # mnVisible
+    found: np.ndarray                   # mnFound
+    n_obs: np.ndarray                   # MapPoint::nObs (stale after the point became bad, like the reference)
+    xyz: np.ndarray                     # (n,3) float32 mWorldPos
+
+
+@dataclass
+class CloseCounts:
+    """What dsh_track_close_frame returns (DefTracking.cc:253-328)."""
+    matches_inliers: int                # mnMatchesInliers: decides whether the tracking succeeded
+    matches_outliers: int               # mnMatchesOutliers
+    to_match_local: int                 # DefnToMatchLOCAL
+    observed: int                       # observedFrame
+    inliers: int                        # mI  } the Matches.txt row
+    outliers: int                       # mO  }
+    local_map_points: int               # numberLocalMapPoints
+    n_moved: int                        # points the repose moved
+
+
+# dsh_trackstate_cull: what became of an entry of mlpRecentAddedMapPoints
+CULL_STAYS, CULL_WAS_BAD, CULL_SET_BAD, CULL_OLD = 0, 1, 2, 3
 
 
 def _i32(a):
@@ -171,3 +199,62 @@ class MapPointStore:
                    _ptr(lev, C.c_int32), _ptr(uv, C.c_float), _ptr(vc, C.c_float), C.byref(nm))
         return LocalSearch(local_ids=ids[:Q], match=match[:Q], in_view=iv[:Q].astype(bool), level=lev[:Q], uv=uv[:Q], view_cos=vc[:Q],
                            nmatches=int(nm.value))
+
+    # ---- the per-point tracking state and the end of a tracked frame ----
+    def set_embedding(self, ids, nodes, bary=None):
+        """DefMapPoint::SetFacet + SetCoordinates: nodes (n,3) ascending node indices (-1 -1 -1 removes the facet), bary (n,3) in that order."""
+        ids = _i32(ids)
+        n = ids.shape[0]
+        nd = np.ascontiguousarray(nodes, np.int32).reshape(n, 3)
+        b = None if bary is None else np.ascontiguousarray(bary, np.float64).reshape(n, 3)
+        self._call("dsh_trackstate_set_embedding", n, _ptr(ids, C.c_int32), _ptr(nd, C.c_int32), _ptr(b, C.c_double))
+
+    def clear_embedding(self):
+        """DefMap::clearTemplate: every point loses its facet."""
+        self._call("dsh_trackstate_clear_embedding")
+
+    def set_counters(self, ids, visible, found):
+        ids = _i32(ids)
+        v, f = _i32(visible), _i32(found)
+        self._call("dsh_trackstate_set_counters", ids.shape[0], _ptr(ids, C.c_int32), _ptr(v, C.c_int32), _ptr(f, C.c_int32))
+
+    def get_state(self, ids=None) -> PointState:
+        """mnVisible, mnFound, nObs and the position of ids (None: every point of the store)."""
+        ids = np.arange(self.n_points, dtype=np.int32) if ids is None else _i32(ids)
+        n = ids.shape[0]
+        m = max(n, 1)
+        v, f, o, x = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 3), np.float32)
+        self._call("dsh_trackstate_get", n, _ptr(ids, C.c_int32), _ptr(v, C.c_int32), _ptr(f, C.c_int32), _ptr(o, C.c_int32), _ptr(x, C.c_float))
+        return PointState(visible=v[:n], found=f[:n], n_obs=o[:n], xyz=x[:n])
+
+    def seed_local_points(self, ids):
+        """DefTracking::MonocularInitialization: the local list and the reference list become ids (ascending)."""
+        ids = _i32(ids)
+        self._call("dsh_trackstate_seed_local_points", ids.shape[0], _ptr(ids, C.c_int32))
+
+    def repose(self, node_xyz) -> int:
+        """DefOptimizer.cc:568-576: every point that is not bad and has a facet moves to its barycentric position; returns how many."""
+        x = np.ascontiguousarray(node_xyz, np.float64).reshape(-1, 3)
+        moved = C.c_int32(0)
+        self._call("dsh_trackstate_repose", x.shape[0], _ptr(x, C.c_double), C.byref(moved))
+        return int(moved.value)
+
+    def cull(self, ids, first_kf, current_kf: int) -> np.ndarray:
+        """LocalMapping::MapPointCulling over ids (mnFirstKFid in first_kf): CULL_* per entry; CULL_SET_BAD points are bad in the store."""
+        ids, fk = _i32(ids), _i32(first_kf)
+        act = np.zeros(max(ids.shape[0], 1), np.uint8)
+        self._call("dsh_trackstate_cull", ids.shape[0], _ptr(ids, C.c_int32), _ptr(fk, C.c_int32), int(current_kf), _ptr(act, C.c_uint8))
+        return act[:ids.shape[0]]
+
+    def close_frame(self, frame: TrackFrame, frame_points, outlier, node_xyz=None, only_tracking: bool = False) -> CloseCounts:
+        """The rest of DefTracking::TrackLocalMap after the optimisation: frame carries the pose after SetPose (only Tcw, Ow, K and bounds are
+        read), frame_points / outlier are mvpMapPoints (ids or -1) / mvbOutlier, node_xyz the optimised nodes (None: no position changes)."""
+        keep = []
+        f = frame.c(keep)
+        fp = _i32(frame_points)
+        out = np.ascontiguousarray(outlier, np.uint8).reshape(fp.shape[0])
+        x = None if node_xyz is None else np.ascontiguousarray(node_xyz, np.float64).reshape(-1, 3)
+        cc = _lib.TrackCloseCountsC()
+        self._call("dsh_track_close_frame", C.byref(f), fp.shape[0], _ptr(fp, C.c_int32), _ptr(out, C.c_uint8), 0 if x is None else x.shape[0],
+                   _ptr(x, C.c_double), 1 if only_tracking else 0, C.byref(cc))
+        return CloseCounts(**{n: int(getattr(cc, n)) for n, _ in _lib.TrackCloseCountsC._fields_})

@@ -688,7 +688,8 @@ def make_local_map_scene(seed: int = 0, n_kf: int = 30, n_kp: int = 1200, obs_pe
     ProcessNewKeyFrame: its table is filled, its observations are not there yet.  Frame: a track.TrackFrame near the end of the path whose
     key points were generated around the projections of the most recently seen points; frame_points (N ids or -1) holds what the
     frame-to-frame search would have matched -- most of those points at their own key point, a few of them at a second key point as
-    well (they vote twice), some bad points among them -- and frame.state is 1 where a point is held."""
+    well (they vote twice), some bad points among them -- and frame.state is 1 where a point is held.  Also what the points were drawn
+    from: template (the GridTemplate), template_xyz (its bent nodes), facet and facet_bary per point."""
     from . import track
     rng = np.random.default_rng(7000 + seed)
     P = max(8, int(n_kf * n_kp * fill / obs_per_point))
@@ -757,7 +758,8 @@ def make_local_map_scene(seed: int = 0, n_kf: int = 30, n_kp: int = 1200, obs_pe
     state = (frame_points >= 0).astype(np.uint8)
     frame = track.TrackFrame(**{**frame.__dict__, "state": state})
     return dict(xyz=xyz, normal=normal, max_distance=max_distance, desc=desc, bad=bad, tables=tables, parents=parents, kf_bad=kf_bad,
-                obs_point=obs_point, obs_kf=obs_kf, frame=frame, frame_points=frame_points)
+                obs_point=obs_point, obs_kf=obs_kf, frame=frame, frame_points=frame_points,
+                template=tmpl, template_xyz=gt, facet=fac, facet_bary=bary)
 
 
 def write_local_map_scene(sc, path):
@@ -778,3 +780,104 @@ def write_local_map_scene(sc, path):
         f.write(f"{fl(a['K'])} {fl(a['bounds'])}\n{fl(a['Tcw'].ravel())}\n{fl(a['Ow'])}\n{N}\n")
         for j in range(N):
             f.write(f"{float(a['kp'][j, 0])!r} {float(a['kp'][j, 1])!r} {int(a['octave'][j])} {int(sc['frame_points'][j])} {by(a['desc'][j])}\n")
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Closing a tracked frame (MapPointStore.close_frame / repose / cull): a local-map scene with the template embedding of its points
+# and the state of the frame after the pose optimisation.
+# ---------------------------------------------------------------------------------------------------------
+def make_track_close_scene(seed: int = 0, no_facet_frac: float = 0.15, away_frac: float = 0.1, outlier_frac: float = 0.15, **local_map):
+    """make_local_map_scene(seed, **local_map) (its keys are kept; normal and the observations differ, see below) plus
+      nodes (P,3) int32 / bary (P,3) float64   the facet of every point as ascending node indices with the barycentrics in that order;
+                                               a share no_facet_frac has none (-1 -1 -1, zeros)
+      normal                                   a share away_frac of the points looks away from the camera (normal negated): not in the frustum
+      obs_point, obs_kf                        without the pairs of up to three points, which the final frame holds: n_obs == 0
+      late_bad                                 ids that become bad after the previous frame built its local list (they sit in the reference list)
+      visible (P,), found (P,)                 mnVisible / mnFound of a loaded map (found <= visible; some ratios below 0.40)
+      first_kf (P,), current_kf                mnFirstKFid per point and the id of the keyframe LocalMapping::MapPointCulling runs for
+      node_xyz (n,3) float64, frame_after      the template nodes and the frame "after the optimisation": the nodes moved by a few millimetres,
+                                               a slightly different pose (only Tcw and Ow differ from frame)
+      final_points (N,), outlier (N,)          mvpMapPoints / mvbOutlier after the local-map search and the optimisation.  Among the held points:
+                                               one held twice and inlier at both key points, bad ones, points without an observation
+                                               (n_obs == 0), one without a facet."""
+    from . import track
+    sc = dict(make_local_map_scene(seed, **local_map))
+    rng = np.random.default_rng(9000 + seed)
+    P = sc["xyz"].shape[0]
+    tmpl = sc["template"]
+    raw = tmpl.facets[sc["facet"]].astype(np.int32)
+    order = np.argsort(raw, axis=1, kind="stable")                 # std::set<Node*> order
+    nodes = np.take_along_axis(raw, order, 1)
+    bary = np.take_along_axis(np.asarray(sc["facet_bary"], np.float64), order, 1)
+    fp0 = sc["frame_points"]
+    N = fp0.shape[0]
+    held0 = np.unique(fp0[fp0 >= 0])
+    n_obs = np.bincount(sc["obs_point"], minlength=P)
+    bad = sc["bad"]
+    free_pts = np.setdiff1d(np.nonzero(~bad)[0], held0)
+    # the final frame: the bad entries are nulled (Tracking.cc:1527-1530) but for one; the local-map search adds matches; some points
+    # without an observation come in (they sit in the newest keyframe's table only)
+    final = fp0.copy()
+    bad_at = np.nonzero((fp0 >= 0) & bad[np.maximum(fp0, 0)])[0]
+    final[bad_at[1:]] = -1
+    free_kp = np.nonzero(final < 0)[0]
+    rng.shuffle(free_kp)
+    zero_obs = rng.choice(free_pts, min(3, free_pts.shape[0]), replace=False)      # created by the tracking, not yet seen by a keyframe
+    keep_obs = ~np.isin(sc["obs_point"], zero_obs)
+    sc["obs_point"], sc["obs_kf"] = sc["obs_point"][keep_obs], sc["obs_kf"][keep_obs]
+    n_obs[zero_obs] = 0
+    more = rng.choice(np.setdiff1d(free_pts, zero_obs), min(max(1, free_kp.shape[0] // 4), max(free_pts.shape[0] - 3, 1)), replace=False) \
+        if free_pts.shape[0] > 3 else np.zeros(0, np.int64)
+    new = np.concatenate([zero_obs, more])[:free_kp.shape[0]]
+    final[free_kp[:new.shape[0]]] = new
+    outlier = ((final >= 0) & (rng.uniform(size=N) < outlier_frac)).astype(np.uint8)
+    vals, counts = np.unique(final[final >= 0], return_counts=True)
+    twice = [int(p) for p in vals[counts >= 2] if not bad[p] and n_obs[p] > 0]
+    if twice:
+        outlier[final == twice[0]] = 0
+    outlier[np.isin(final, zero_obs)] = 0
+    if bad_at.shape[0]:
+        outlier[bad_at[0]] = 0
+    no_facet = rng.uniform(size=P) < no_facet_frac
+    inl = [int(p) for p in final[(final >= 0) & (outlier == 0)] if not bad[p] and n_obs[p] > 0 and p not in twice[:1]]
+    if inl:
+        no_facet[inl[0]] = True
+    nodes[no_facet] = -1
+    bary[no_facet] = 0.0
+    normal = sc["normal"].copy()
+    away = free_pts[rng.uniform(size=free_pts.shape[0]) < away_frac]
+    normal[away] = -normal[away]
+    late_bad = rng.choice(free_pts, min(max(2, P // 50), free_pts.shape[0]), replace=False).astype(np.int32) if free_pts.shape[0] else np.zeros(0, np.int32)
+    n_kf = sc["tables"].shape[0]
+    first_kf = rng.integers(max(0, n_kf - 5), n_kf + 1, P).astype(np.int32)
+    visible = rng.integers(1, 20, P).astype(np.int32)
+    found = np.minimum(rng.integers(1, 20, P), visible).astype(np.int32)
+    node_xyz = sc["template_xyz"] + rng.normal(0.0, 2e-3, sc["template_xyz"].shape)
+    f = sc["frame"]
+    dT = np.eye(4)
+    dT[:3, :3] = _rodrigues(rng.normal(size=3) * 0.002)
+    dT[:3, 3] = rng.uniform(-0.002, 0.002, 3)
+    Tc = (dT @ np.asarray(f.Tcw, np.float64)).astype(np.float32)
+    frame_after = track.TrackFrame(**{**f.__dict__, "Tcw": Tc, "Ow": track.camera_center(Tc)})
+    sc.update(nodes=nodes, bary=bary, normal=normal, late_bad=np.sort(late_bad), visible=visible, found=found, first_kf=first_kf, current_kf=int(n_kf), node_xyz=node_xyz,
+              frame_after=frame_after, final_points=final.astype(np.int32), outlier=outlier)
+    return sc
+
+
+def write_track_close_scene(sc, prev_points, path):
+    """What integration/trackclose_shim_test_main.cc reads beside the write_local_map_scene file of the same scene: the template nodes before
+    and after the optimisation, per point its facet, barycentrics, counters and first keyframe, the culling keyframe, the points that turn
+    bad after the previous frame, the pose after the optimisation, and per key point what the previous frame held (prev_points), the final
+    map point and the outlier flag."""
+    fl = lambda vs: " ".join(repr(float(v)) for v in vs)
+    a = sc["frame_after"].arrays()
+    with open(path, "w") as f:
+        f.write(f"{sc['node_xyz'].shape[0]}\n")
+        for x0, x1 in zip(sc["template_xyz"], sc["node_xyz"]):
+            f.write(f"{fl(x0)} {fl(x1)}\n")
+        for p in range(sc["xyz"].shape[0]):
+            f.write(f"{' '.join(str(int(n)) for n in sc['nodes'][p])} {fl(sc['bary'][p])} {int(sc['visible'][p])} {int(sc['found'][p])} {int(sc['first_kf'][p])}\n")
+        f.write(f"{int(sc['current_kf'])} {sc['late_bad'].shape[0]} {' '.join(str(int(p)) for p in sc['late_bad'])}\n")
+        f.write(f"{fl(a['Tcw'].ravel())}\n{fl(a['Ow'])}\n")
+        for j in range(sc["final_points"].shape[0]):
+            f.write(f"{int(prev_points[j])} {int(sc['final_points'][j])} {int(sc['outlier'][j])}\n")

@@ -647,6 +647,72 @@ int dsh_local_map_points(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* 
 int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, int32_t capacity, int32_t* local_ids, int32_t* match,
                          uint8_t* in_view, int32_t* level, float* uv, float* view_cos, int32_t* nmatches);
 
+/* ---- tracking: closing a tracked frame on the resident map point store --------------------------------------------------------
+ * The back half of DefTracking::TrackLocalMap (Modules/Tracking/DefTracking.cc:253-339) and what it needs of the points:
+ *   position write-back   DefPoseOptimization moves EVERY map point with a facet, observed or not (Modules/Tracking/DefOptimizer.cc:568-576,
+ *                         DefMapPoint::RecalculatePosition, Modules/Common/DefMapPoint.cc:129-147)
+ *   counting loops        IncreaseFound, mnMatchesInliers, the Matches.txt row, numberLocalMapPoints (DefTracking.cc:253-319)
+ *   culling               LocalMapping::MapPointCulling (Thirdparty/ORBSLAM_2/src/LocalMapping.cc:173-199), which reads mnFound / mnVisible
+ * dsh_mpdb therefore also keeps per point, resident, growing with the point arrays and forgotten by dsh_mpdb_clear:
+ *   visible, found  mnVisible / mnFound; both 1 for a new point (MapPoint.cc:38,58).  dsh_local_map_search adds to visible what
+ *                   Tracking::SearchLocalPoints does: +1 per key point of the frame of the preceding dsh_local_map_update that holds the
+ *                   point when it is not bad (Tracking.cc:1408-1425; a point held twice gets +2) and +1 per query reported in view (:1456)
+ *   n_obs           MapPoint::nObs, monocular: +1 per pair dsh_mpdb_add_observations stores, -1 per pair dsh_mpdb_erase_observations
+ *                   finds (MapPoint.cc:114-133).  STALE ON PURPOSE: setBadFlag clears mObservations and leaves nObs (DefMapPoint.cc:76-94),
+ *                   so setting a point bad here leaves n_obs, and TrackLocalMap's Observations() > 0 test (:266) reads the stale number
+ *   nodes, bary     DefMapPoint::facet as its three node indices in ascending order (std::set<Node*> order, index for pointer) with
+ *                   b1..b3 in that order -- the convention of dsh_sft_frame.obs_nodes / obs_bary; nodes -1 -1 -1: no facet
+ *   reference list  Map::GetReferenceMapPoints() as TrackLocalMap reads it at :284.  Tracking::UpdateLocalMap calls
+ *                   SetReferenceMapPoints(mvpLocalMapPoints) BEFORE it rebuilds that list (Tracking.cc:1475), so this is the local point
+ *                   list of the PREVIOUS frame: dsh_local_map_update keeps the list it found (two buffers that swap).  Empty before
+ *                   the first dsh_local_map_update or dsh_trackstate_seed_local_points
+ * Discipline of the other store calls: arguments are checked on the host first -- an id outside the store, an id repeated within one
+ * batch, NULL with n > 0 give DSH_ERR_ARG with a message naming the entry, and nothing is stored; then a host-only context answers
+ * DSH_ERR_NO_DEVICE; a detached store answers DSH_ERR_ARG.  Integer valued but for the positions, which are the reference's expression
+ * rounded the same way: every output is exact. */
+/* DefMapPoint::SetFacet + SetCoordinates (DefMapPoint.cc:97-118) of the n distinct points ids[n]: nodes[n x 3] ascending and distinct,
+ * bary[n x 3] in that order; nodes -1 -1 -1 removes the facet (bary may be NULL when every entry does). */
+int dsh_trackstate_set_embedding(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* nodes, const double* bary);
+/* DefMap::clearTemplate (Modules/Common/DefMap.cc:75-81): every point loses its facet. */
+int dsh_trackstate_clear_embedding(dsh_mpdb* db);
+/* Overwrite mnVisible / mnFound of n distinct points (a loaded map; MapPoint::Replace, MapPoint.cc:223-224, is get + set by the caller). */
+int dsh_trackstate_set_counters(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* visible, const int32_t* found);
+/* Read back n distinct points; each output may be NULL: visible[n], found[n], n_obs[n], xyz[n x 3]. */
+int dsh_trackstate_get(dsh_mpdb* db, int n, const int32_t* ids, int32_t* visible, int32_t* found, int32_t* n_obs, float* xyz);
+/* DefTracking::MonocularInitialization (DefTracking.cc:641,645): mvpLocalMapPoints = GetAllMapPoints() and SetReferenceMapPoints of it --
+ * the resident local list AND the reference list become ids[n] (ascending, distinct). */
+int dsh_trackstate_seed_local_points(dsh_mpdb* db, int n, const int32_t* ids);
+/* DefOptimizer.cc:568-576 on its own: every point that is not bad (setBadFlag erased those from the map the loop walks) and has a facet
+ * moves to (float)((b1 * x[n1] + b2 * x[n2]) + b3 * x[n3]) per coordinate, every product and sum rounded to nearest in double, no
+ * contraction -- the expression of dsh_sft_result.mappoint_xyz, so the observed points get those very bytes.  node_xyz[n_nodes x 3] is e.g.
+ * dsh_sft_result.xyz.  A stored node index >= n_nodes is DSH_ERR_ARG and nothing moves.  *n_moved (may be NULL) = points moved. */
+int dsh_trackstate_repose(dsh_mpdb* db, int n_nodes, const double* node_xyz, int32_t* n_moved);
+/* LocalMapping::MapPointCulling (LocalMapping.cc:173-199) over mlpRecentAddedMapPoints = ids[n] (distinct), first_kf[n] = mnFirstKFid,
+ * current_kf = mpCurrentKeyFrame->mnId.  Per point, the first case that applies: action[n] = 1 already bad (leaves the list); 2
+ * (float)found / (float)visible < 0.40f: the store sets the point's bad flag (leaves the list); 3 (int)current_kf - first_kf >= 3 (leaves
+ * the list); 0 stays.  Setting bad is what dsh_mpdb_set_points_bad does: observation records, n_obs and table entries are untouched (bad
+ * points neither vote nor become local points); KeyFrame::EraseMapPointMatch stays with the caller, who knows the index. */
+int dsh_trackstate_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* first_kf, int32_t current_kf, uint8_t* action);
+
+typedef struct dsh_track_close_counts {
+  int32_t matches_inliers, matches_outliers, to_match_local;   /* mnMatchesInliers, mnMatchesOutliers, DefnToMatchLOCAL (DefTracking.cc:254-283) */
+  int32_t observed, inliers, outliers;                         /* observedFrame, mI, mO: the Matches.txt row (:300-328) */
+  int32_t local_map_points;                                    /* numberLocalMapPoints (:284-298) */
+  int32_t n_moved;                                             /* points the repose moved; 0 without node_xyz */
+} dsh_track_close_counts;
+/* The rest of TrackLocalMap after the optimisation, in the reference's order.  frame: only Tcw, Ow, K and bounds are read (the pose AFTER
+ * SetPose, DefOptimizer.cc:566).  frame_points[N] = mvpMapPoints as ids or -1, outlier[N] = mvbOutlier.
+ *   1. repose as dsh_trackstate_repose when node_xyz[n_nodes x 3] is given (NULL: no position changes)
+ *   2. :257-283 per key point i with a point p: !outlier[i] gives found[p] += 1 (per key point, NO bad test), then with only_tracking == 0
+ *      matches_inliers++ when n_obs[p] > 0 and also to_match_local++ when p has a facet, with only_tracking != 0 matches_inliers++
+ *      unconditionally; outlier[i] gives matches_outliers++
+ *   3. :284-298 local_map_points = the entries of the reference list that are not bad, have a facet and pass Frame::isInFrustum(pMP, 0.5)
+ *      at the given pose -- the test of dsh_local_map_search (no distance range; a NaN projection is not in view), on the moved positions
+ *   4. :300-319 held and not bad gives observed++, then inliers++ or outliers++
+ * One upload (pose, ids, flags, nodes), at most three launches, one download of the counts.  N <= 2^20. */
+int dsh_track_close_frame(dsh_mpdb* db, const dsh_track_frame* frame, int N, const int32_t* frame_points, const uint8_t* outlier,
+                          int n_nodes, const double* node_xyz, int32_t only_tracking, dsh_track_close_counts* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -4,7 +4,9 @@
 //       owns a dsh_mpdb and the two dictionaries pointer <-> number (MapPoint* <-> id, KeyFrame* <-> slot).  The mapping thread calls
 //       it where it changes the map: AddMapPoint / AddKeyFrame when one is created, AddObservation / EraseObservation next to
 //       MapPoint::AddObservation / EraseObservation, SetKeyFramePoint next to KeyFrame::AddMapPoint / EraseMapPointMatch, SetParent next
-//       to KeyFrame::ChangeParent, SetBad next to SetBadFlag, UpdatePositions after DefPoseOptimization moved the points.
+//       to KeyFrame::ChangeParent, SetBad next to SetBadFlag, UpdatePositions after DefPoseOptimization moved the points (or, with SetEmbedding next to
+//       DefMapPoint::SetFacet / SetCoordinates, ClearEmbedding next to DefMap::clearTemplate and SeedLocalPoints at the initialisation,
+//       nothing per frame: track_close_hip.h moves the points on the device).
 //   UpdateLocalMapHIP(store, CurrentFrame, mvpLocalKeyFrames, mvpLocalMapPoints, mpReferenceKF)
 //       drop-in for Tracking::UpdateLocalMap (Thirdparty/ORBSLAM_2/src/Tracking.cc:1472-1480, called at DefTracking.cc:237): fills the
 //       two vectors and does the reference's write-backs -- bad points leave CurrentFrame.mvpMapPoints (:1529), the listed keyframes and
@@ -93,6 +95,31 @@ class MapPointStoreHIP {
     const int32_t i = id(p);
     return dsh_mpdb_set_points_bad(db_, 1, &i, nullptr) == DSH_OK;
   }
+  // DefMapPoint::SetFacet + SetCoordinates of these points (a point whose getFacet() is null loses its facet in the store too);
+  // index_of(Node*) is the node's index in the template, and pointer order of a facet's nodes must be index order
+  template <class NodeIndex>
+  bool SetEmbedding(const std::vector<MapPointT*>& pts, NodeIndex index_of) {
+    const size_t n = pts.size();
+    std::vector<int32_t> ids(n), nodes(3 * n, -1);
+    std::vector<double> bary(3 * n, 0.0);
+    for (size_t i = 0; i < n; i++) {
+      ids[i] = id(pts[i]);
+      if (!pts[i]->getFacet()) continue;
+      const auto set = pts[i]->getFacet()->getNodes();
+      int k = 0;
+      for (auto* nd : set) nodes[3 * i + k++] = index_of(nd);
+      bary[3 * i] = pts[i]->b1; bary[3 * i + 1] = pts[i]->b2; bary[3 * i + 2] = pts[i]->b3;
+    }
+    return dsh_trackstate_set_embedding(db_, (int)n, ids.data(), nodes.data(), bary.data()) == DSH_OK;
+  }
+  bool ClearEmbedding() { return dsh_trackstate_clear_embedding(db_) == DSH_OK; }                 // DefMap::clearTemplate
+  // DefTracking::MonocularInitialization (DefTracking.cc:641,645): the local and the reference list become pts (in creation order)
+  bool SeedLocalPoints(const std::vector<MapPointT*>& pts) {
+    std::vector<int32_t> ids(pts.size());
+    for (size_t i = 0; i < pts.size(); i++) ids[i] = id(pts[i]);
+    return dsh_trackstate_seed_local_points(db_, (int)ids.size(), ids.data()) == DSH_OK;
+  }
+  int point_count() const { return (int)points_.size(); }
   // DefPoseOptimization moved these points (DefMapPoint::RecalculatePosition)
   template <class FrameT>
   bool UpdatePositions(const std::vector<MapPointT*>& pts) {

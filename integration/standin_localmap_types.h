@@ -1,4 +1,5 @@
-// Stand-ins of the members of ORB_SLAM2::KeyFrame, ORB_SLAM2::MapPoint and ORB_SLAM2::Frame that integration/local_map_hip.h touches
+// Stand-ins of the members of ORB_SLAM2::KeyFrame, ORB_SLAM2::MapPoint (with defSLAM::DefMapPoint's) and ORB_SLAM2::Frame that
+// integration/local_map_hip.h and integration/track_close_hip.h touch
 // (reference declaration behind each), for the repository's CI: OpenCV is not in the build image.  Inside DefSLAM these are not used.
 #pragma once
 #include <cstddef>
@@ -12,6 +13,16 @@
 namespace standin {
 
 class LmKeyFrame;
+
+struct LmNode {                                // Modules/Template/Node.h
+  double x = 0, y = 0, z = 0;                                           // :140
+};
+
+class LmFacet {                                // Modules/Template/Facet.h
+ public:
+  std::set<LmNode*> getNodes() { return Nodes; }                        // :65 (a copy, ordered by pointer)
+  std::set<LmNode*> Nodes;                                              // :99
+};
 
 class LmMapPoint {                             // Thirdparty/ORBSLAM_2/include/MapPoint.h
  public:
@@ -32,6 +43,24 @@ class LmMapPoint {                             // Thirdparty/ORBSLAM_2/include/M
   std::map<LmKeyFrame*, size_t> mObservations;                          // :127
   int nVisible = 0;
   bool bad = false;
+  // what the end of DefTracking::TrackLocalMap and LocalMapping::MapPointCulling touch
+  void IncreaseFound(int n = 1) { mnFound += n; }                       // :70
+  float GetFoundRatio() { return static_cast<float>(mnFound) / nVisible; }   // :71 (MapPoint.cc:251-255)
+  void setBadFlag() { bad = true; mObservations.clear(); }              // :63; nObs stays (DefMapPoint.cc:76-94)
+  int mnFound = 1;                                                      // :144
+  int nObs = 0;                                                         // :96: what Observations() returns in the reference
+  long int mnFirstKFid = 0;                                             // :94
+  // defSLAM::DefMapPoint (Modules/Common/DefMapPoint.h)
+  LmFacet* getFacet() { return facet; }                                 // :76
+  void RecalculatePosition() {                                          // :86 (DefMapPoint.cc:129-147)
+    const std::set<LmNode*> nodes = facet->getNodes();
+    std::vector<LmNode*> v(nodes.begin(), nodes.end());
+    pos[0] = b1 * v[0]->x + b2 * v[1]->x + b3 * v[2]->x;
+    pos[1] = b1 * v[0]->y + b2 * v[1]->y + b3 * v[2]->y;
+    pos[2] = b1 * v[0]->z + b2 * v[1]->z + b3 * v[2]->z;
+  }
+  LmFacet* facet = nullptr;                                             // :100
+  double b1 = 0, b2 = 0, b3 = 0;                                        // :96
 };
 
 class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/KeyFrame.h

@@ -30,6 +30,7 @@ struct TrackAccess {
   static void center(const FrameT& f, float* Ow) { std::memcpy(Ow, f.mOw, 3 * sizeof(float)); }
   static const uint8_t* descriptors(const FrameT& f) { return f.mDescriptors.data(); }   // N x 32, row j = mDescriptors.row(j)
   static void world_pos(MapPointT* p, float* x) { std::memcpy(x, p->pos, 3 * sizeof(float)); }
+  static void set_world_pos(MapPointT* p, const float* x) { std::memcpy(p->pos, x, 3 * sizeof(float)); }   // mWorldPos (track_close_hip.h)
   static void normal(MapPointT* p, float* n) { std::memcpy(n, p->normal, 3 * sizeof(float)); }
   static void descriptor(MapPointT* p, uint8_t* d) { std::memcpy(d, p->desc, 32); }
 };
