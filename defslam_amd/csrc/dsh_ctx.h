@@ -1,6 +1,7 @@
 // Internal definition of the opaque dsh_ctx (shared by the translation units of libdefslam_hip.so) and the host-side plumbing every
 // C ABI module uses: error reporting (dsh_fail, HIPCHK), the device gate (dsh_enter), scratch slices (DevBuf), block layout (Arena),
-// page-locked host buffers (HostBuf) and the life cycle of the device-resident stores (dsh_store).
+// page-locked host buffers (HostBuf), the one-copy blocks of a call (UpBlock, DownBlock) and the life cycle of the device-resident
+// stores (dsh_store, DSH_STORE_ENTER, dsh_store_grow).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,6 +137,11 @@ hipError_t dsh_store_grow(void** p, size_t bytes, Copy copy) {
   *p = q;
   return hipSuccess;
 }
+// the usual case: a device array of T grows to `cap` elements and keeps its `used` leading ones
+template <class T>
+hipError_t dsh_store_grow_array(T** p, size_t used, size_t cap) {
+  return dsh_store_grow((void**)p, sizeof(T) * cap, [&](char* q) { return used ? hipMemcpy(q, *p, sizeof(T) * used, hipMemcpyDeviceToDevice) : hipSuccess; });
+}
 
 // error helper usable from every translation unit
 inline int dsh_fail(dsh_ctx_base* c, int code, const std::string& m) {
@@ -170,6 +176,67 @@ struct DevBuf {
   hipError_t alloc(dsh_ctx_base* c, size_t bytes) { return c->scratch.take(bytes, &p); }
   template <class T> T* as() { return static_cast<T*>(p); }
 };
+// The same for a typed pointer of a kernel's argument struct: n elements.
+template <class T>
+hipError_t dsh_scratch_array(dsh_ctx_base* c, T** p, size_t n) { return c->scratch.take(sizeof(T) * n, (void**)p); }
+
+// A block of a call that moves in one copy: slices laid out as by Arena, the host side in a page-locked buffer of the context, the device
+// side in one scratch slice.  An empty block enqueues no copy; a take(0) slice is legal and never dereferenced.
+struct CopyBlock : Arena {   // size: what the copy moves
+  char *h = nullptr, *d = nullptr;
+  // a slice without padding: the last one of a block whose copy ends with it
+  size_t take_exact(size_t bytes) {
+    const size_t off = size;
+    size += bytes;
+    return off;
+  }
+  template <class T> T* host(size_t off) const { return reinterpret_cast<T*>(h + off); }
+  template <class T> T* dev(size_t off) const { return reinterpret_cast<T*>(d + off); }
+};
+
+// Up: filled in pin_in after stage(), copied by send().  The two are apart because some calls stage here and copy into a store's own
+// arrays.  The kernels may write the device side (counters that go up as zeros).
+struct UpBlock : CopyBlock {
+  int stage(dsh_ctx_base* c) {
+    HIPCHK(c, c->pin_in.ensure(size, true));
+    h = c->pin_in.p;
+    return DSH_OK;
+  }
+  int send(dsh_ctx_base* c) {
+    HIPCHK(c, c->scratch.take(size, (void**)&d));
+    if (size > 0) HIPCHK(c, hipMemcpyAsync(d, h, size, hipMemcpyHostToDevice, c->stream));
+    return DSH_OK;
+  }
+};
+
+// Down: the kernels write a scratch slice (alloc) or the block lies where a kernel's output is already (at: counters inside the upload
+// block); fetch() copies into pin_out and does not synchronise: host() is read after the caller's hipStreamSynchronize.
+struct DownBlock : CopyBlock {
+  int alloc(dsh_ctx_base* c) {
+    HIPCHK(c, c->scratch.take(size, (void**)&d));
+    return at(c, d);
+  }
+  int at(dsh_ctx_base* c, void* dev_block) {
+    HIPCHK(c, c->pin_out.ensure(size, true));
+    h = c->pin_out.p;
+    d = static_cast<char*>(dev_block);
+    return DSH_OK;
+  }
+  int fetch(dsh_ctx_base* c) {
+    if (size > 0) HIPCHK(c, hipMemcpyAsync(h, d, size, hipMemcpyDeviceToHost, c->stream));
+    return DSH_OK;
+  }
+};
+
+// The first checks of every entry point on a device-resident store `db`: a store that is alive and attached.  Leaves its context in c
+// and bad(message), which refuses with DSH_ERR_ARG and "who: message".
+#define DSH_STORE_ENTER(who)                            \
+  if (!db || !db->ctx) return DSH_ERR_ARG;              \
+  [[maybe_unused]] dsh_ctx_base* c = db->ctx;           \
+  [[maybe_unused]] auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, std::string(who) + ": " + m); }
+
+// The key point count of a frame or a keyframe: what is wrong with it, or null.
+inline const char* dsh_keypoint_count_error(long long N) { return N < 0 || N > (1 << 20) ? "N outside 0 .. 2^20" : nullptr; }
 
 namespace dsh {
 // Dense bending matrix of a B-spline (dsh_sfn.cpp; the warp initialisation of dsh_schwarp.cpp uses it too).

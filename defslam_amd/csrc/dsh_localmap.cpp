@@ -17,7 +17,6 @@
 #include "dsh_ctx.h"
 #include "localmap_problem.h"
 #include "mpdb_store.h"
-#include "trackclose_problem.h"
 #include "track_problem.h"
 
 namespace {
@@ -71,8 +70,7 @@ int dsh_mpdb_destroy(dsh_mpdb* db) {
 }
 
 int dsh_mpdb_clear(dsh_mpdb* db) {
-  MPDB_ENTER("dsh_mpdb_clear");
-  (void)bad;
+  DSH_STORE_ENTER("dsh_mpdb_clear");
   if (db->d_hdr) {
     if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_mpdb_clear: hipSetDevice failed");
     HIPCHK(c, hipMemsetAsync(db->d_hdr, 0, sizeof(LmHdr), c->stream));
@@ -94,7 +92,7 @@ int32_t dsh_mpdb_keyframe_count(const dsh_mpdb* db) { return db ? db->K : -1; }
 
 int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* normal, const float* max_distance, const uint8_t* desc,
                         const uint8_t* bad_flags, int32_t* first_id) {
-  MPDB_ENTER("dsh_mpdb_add_points");
+  DSH_STORE_ENTER("dsh_mpdb_add_points");
   if (n < 0) return bad("n < 0");
   if (n > 0 && (!xyz || !normal || !max_distance || !desc)) return bad("a point array is NULL");
   if ((long long)db->P + n > INT32_MAX) return bad("store full");
@@ -112,10 +110,7 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
   HIPCHK(c, hipMemcpyAsync(db->d_maxd + P, max_distance, 4 * (size_t)n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(db->d_desc + 2 * P, desc, 32 * (size_t)n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(db->d_bad + P, b32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
-  TcState ts;
-  ts.xyz = db->d_xyz; ts.bad = db->d_bad; ts.visible = db->d_visible; ts.found = db->d_found; ts.nobs = db->d_nobs; ts.nodes = db->d_nodes;
-  ts.bary = db->d_bary;
-  HIPCHK(c, tc_init_points_launch(ts, db->P, n, st));   // mnVisible = mnFound = 1, nObs = 0, no facet
+  HIPCHK(c, tc_init_points_launch(mpdb_state(db), db->P, n, st));   // mnVisible = mnFound = 1, nObs = 0, no facet
   HIPCHK(c, hipStreamSynchronize(st));
   db->P += n;
   db->top_node.resize((size_t)db->P, -1);
@@ -124,7 +119,7 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
 
 int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what, const float* xyz, const float* normal,
                            const float* max_distance, const uint8_t* desc) {
-  MPDB_ENTER("dsh_mpdb_update_points");
+  DSH_STORE_ENTER("dsh_mpdb_update_points");
   if (what < 1 || what > (DSH_MPDB_POSITION | DSH_MPDB_NORMAL_DEPTH | DSH_MPDB_DESCRIPTOR))
     return bad("what is not a non-empty mask of DSH_MPDB_POSITION, DSH_MPDB_NORMAL_DEPTH, DSH_MPDB_DESCRIPTOR");
   const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
@@ -133,26 +128,22 @@ int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what
   if (n > 0 && ((wp && !xyz) || (wn && (!normal || !max_distance)) || (wd && !desc))) return bad("an array that `what` selects is NULL");
   if (const int rc = dsh_enter(c, "dsh_mpdb_update_points")) return rc;
   if (n == 0) return DSH_OK;
-  Arena up;
+  UpBlock up;
   const size_t m = (size_t)n, o_ids = up.take(4 * m), o_xyz = up.take(wp ? 12 * m : 0), o_nrm = up.take(wn ? 12 * m : 0), o_maxd = up.take(wn ? 4 * m : 0),
                o_desc = up.take(wd ? 32 * m : 0);
-  HIPCHK(c, c->pin_in.ensure(up.size, true));
-  char* h = c->pin_in.p;
-  std::memcpy(h + o_ids, ids, 4 * m);
-  if (wp) std::memcpy(h + o_xyz, xyz, 12 * m);
-  if (wn) { std::memcpy(h + o_nrm, normal, 12 * m); std::memcpy(h + o_maxd, max_distance, 4 * m); }
-  if (wd) std::memcpy(h + o_desc, desc, 32 * m);
-  void* dup = nullptr;
-  HIPCHK(c, c->scratch.take(up.size, &dup));
+  if (const int rc = up.stage(c)) return rc;
+  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
+  if (wp) std::memcpy(up.host<float>(o_xyz), xyz, 12 * m);
+  if (wn) { std::memcpy(up.host<float>(o_nrm), normal, 12 * m); std::memcpy(up.host<float>(o_maxd), max_distance, 4 * m); }
+  if (wd) std::memcpy(up.host<uint4>(o_desc), desc, 32 * m);
+  if (const int rc = up.send(c)) return rc;
   hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dup, h, up.size, hipMemcpyHostToDevice, st));
-  const char* du = static_cast<const char*>(dup);
   LmWriteBufs w;
-  w.ids = reinterpret_cast<const int32_t*>(du + o_ids);
-  w.src_xyz = reinterpret_cast<const float*>(du + o_xyz);
-  w.src_normal = reinterpret_cast<const float*>(du + o_nrm);
-  w.src_max_distance = reinterpret_cast<const float*>(du + o_maxd);
-  w.src_desc = reinterpret_cast<const uint4*>(du + o_desc);
+  w.ids = up.dev<const int32_t>(o_ids);
+  w.src_xyz = up.dev<const float>(o_xyz);
+  w.src_normal = up.dev<const float>(o_nrm);
+  w.src_max_distance = up.dev<const float>(o_maxd);
+  w.src_desc = up.dev<const uint4>(o_desc);
   w.xyz = db->d_xyz; w.normal = db->d_nrm; w.max_distance = db->d_maxd; w.desc = db->d_desc;
   HIPCHK(c, lm_write_points_launch(w, n, what, st));
   HIPCHK(c, hipStreamSynchronize(st));
@@ -160,38 +151,33 @@ int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what
 }
 
 int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8_t* bad_flags) {
-  MPDB_ENTER("dsh_mpdb_set_points_bad");
+  DSH_STORE_ENTER("dsh_mpdb_set_points_bad");
   const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
   if (!ie.empty()) return bad(ie);
   if (const int rc = dsh_enter(c, "dsh_mpdb_set_points_bad")) return rc;
   if (n == 0) return DSH_OK;
-  Arena up;
+  UpBlock up;
   const size_t m = (size_t)n, o_ids = up.take(4 * m), o_val = up.take(4 * m);
-  HIPCHK(c, c->pin_in.ensure(up.size, true));
-  char* h = c->pin_in.p;
-  std::memcpy(h + o_ids, ids, 4 * m);
-  int32_t* v = reinterpret_cast<int32_t*>(h + o_val);
+  if (const int rc = up.stage(c)) return rc;
+  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
+  int32_t* v = up.host<int32_t>(o_val);
   for (int i = 0; i < n; i++) v[i] = !bad_flags || bad_flags[i] ? 1 : 0;
-  void* dup = nullptr;
-  HIPCHK(c, c->scratch.take(up.size, &dup));
+  if (const int rc = up.send(c)) return rc;
   hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dup, h, up.size, hipMemcpyHostToDevice, st));
-  const char* du = static_cast<const char*>(dup);
-  HIPCHK(c, lm_scatter_i32_launch(db->d_bad, reinterpret_cast<const int32_t*>(du + o_ids), reinterpret_cast<const int32_t*>(du + o_val), 0, n, st));
+  HIPCHK(c, lm_scatter_i32_launch(db->d_bad, up.dev<const int32_t>(o_ids), up.dev<const int32_t>(o_val), 0, n, st));
   HIPCHK(c, hipStreamSynchronize(st));
   return DSH_OK;
 }
 
 int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots) {
-  MPDB_ENTER("dsh_mpdb_add_observations");
+  DSH_STORE_ENTER("dsh_mpdb_add_observations");
   if (n < 0) return bad("n < 0");
   if (n > 0 && (!point_ids || !keyframe_slots)) return bad("point_ids or keyframe_slots is NULL");
   std::unordered_set<uint64_t> batch;
   for (int i = 0; i < n; i++) {
     const int32_t p = point_ids[i], s = keyframe_slots[i];
-    const std::string at = "pair " + std::to_string(i) + ": ";
-    if (p < 0 || p >= db->P) return bad(at + "point id outside the store");
-    if (s < 0 || s >= db->K) return bad(at + "keyframe slot outside the store");
+    const std::string at = "pair " + std::to_string(i) + ": ", pe = mpdb_pair_error(db, p, s);
+    if (!pe.empty()) return bad(at + pe);
     if (db->obs.count(mpdb_obs_key(p, s))) return bad(at + "the point already observes this keyframe");
     if (!batch.insert(mpdb_obs_key(p, s)).second) return bad(at + "repeated in the batch");
   }
@@ -199,13 +185,15 @@ int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, con
   if (n == 0) return DSH_OK;
   if (db->R + n > db->Rcap) {
     const long long cap = std::max(db->R + n, 2 * db->Rcap);
-    HIPCHK(c, mpdb_grow(&db->d_log, (size_t)db->R, (size_t)cap));
+    HIPCHK(c, dsh_store_grow_array(&db->d_log, (size_t)db->R, (size_t)cap));
     db->Rcap = cap;
   }
-  HIPCHK(c, c->pin_in.ensure(8 * (size_t)n, true));
-  int2* h = reinterpret_cast<int2*>(c->pin_in.p);
+  UpBlock up;   // staged here, copied to the end of the log
+  const size_t o_rec = up.take_exact(8 * (size_t)n);
+  if (const int rc = up.stage(c)) return rc;
+  int2* h = up.host<int2>(o_rec);
   for (int i = 0; i < n; i++) h[i] = make_int2(point_ids[i], keyframe_slots[i]);
-  HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, up.size, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, tc_add_by_index_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log + db->R), 2, 1, n, c->stream));   // nObs++ (MapPoint.cc:116-119)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; i++) db->obs[mpdb_obs_key(point_ids[i], keyframe_slots[i])] = db->R + i;
@@ -214,13 +202,12 @@ int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, con
 }
 
 int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots) {
-  MPDB_ENTER("dsh_mpdb_erase_observations");
+  DSH_STORE_ENTER("dsh_mpdb_erase_observations");
   if (n < 0) return bad("n < 0");
   if (n > 0 && (!point_ids || !keyframe_slots)) return bad("point_ids or keyframe_slots is NULL");
   for (int i = 0; i < n; i++) {
-    const std::string at = "pair " + std::to_string(i) + ": ";
-    if (point_ids[i] < 0 || point_ids[i] >= db->P) return bad(at + "point id outside the store");
-    if (keyframe_slots[i] < 0 || keyframe_slots[i] >= db->K) return bad(at + "keyframe slot outside the store");
+    const std::string pe = mpdb_pair_error(db, point_ids[i], keyframe_slots[i]);
+    if (!pe.empty()) return bad("pair " + std::to_string(i) + ": " + pe);
   }
   if (const int rc = dsh_enter(c, "dsh_mpdb_erase_observations")) return rc;
   // the records to blank: 2 * record is the point field of the log seen as int32 pairs
@@ -235,33 +222,33 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
     keys.push_back(k);
   }
   if (idx.empty()) return DSH_OK;
-  const size_t bytes = 4 * idx.size();
-  HIPCHK(c, c->pin_in.ensure(bytes, true));
-  std::memcpy(c->pin_in.p, idx.data(), bytes);
-  void* dup = nullptr;
-  HIPCHK(c, c->scratch.take(bytes, &dup));
-  HIPCHK(c, hipMemcpyAsync(dup, c->pin_in.p, bytes, hipMemcpyHostToDevice, c->stream));
+  UpBlock up;
+  const size_t o_idx = up.take_exact(4 * idx.size());
+  if (const int rc = up.stage(c)) return rc;
+  std::memcpy(up.host<int32_t>(o_idx), idx.data(), up.size);
+  if (const int rc = up.send(c)) return rc;
+  const int32_t* didx = up.dev<const int32_t>(o_idx);
   // nObs-- of every pair that was found (MapPoint.cc:114-133), read from the records before they are blanked
-  HIPCHK(c, tc_add_by_record_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log), static_cast<const int32_t*>(dup), -1, (int)idx.size(), c->stream));
-  HIPCHK(c, lm_scatter_i32_launch(reinterpret_cast<int32_t*>(db->d_log), static_cast<const int32_t*>(dup), nullptr, -1, (int)idx.size(), c->stream));
+  HIPCHK(c, tc_add_by_record_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log), didx, -1, (int)idx.size(), c->stream));
+  HIPCHK(c, lm_scatter_i32_launch(reinterpret_cast<int32_t*>(db->d_log), didx, nullptr, -1, (int)idx.size(), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (const uint64_t k : keys) db->obs.erase(k);
   return DSH_OK;
 }
 
 int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_t parent, int32_t bad_flag, int32_t* slot) {
-  MPDB_ENTER("dsh_mpdb_add_keyframe");
-  if (N < 0 || N > (1 << 20)) return bad("N outside 0 .. 2^20");
+  DSH_STORE_ENTER("dsh_mpdb_add_keyframe");
+  if (const char* ne = dsh_keypoint_count_error(N)) return bad(ne);
   if (N > 0 && !points) return bad("the table is NULL");
-  for (int j = 0; j < N; j++)
-    if (points[j] < -1 || points[j] >= db->P) return bad("table entry " + std::to_string(j) + " is neither -1 nor a point of the store");
+  const std::string te = mpdb_table_error(db, N, points, "table entry ", "");
+  if (!te.empty()) return bad(te);
   if (parent < -1 || parent >= db->K) return bad("parent is neither -1 nor a slot of the store");
   if (db->K == INT32_MAX || db->T + N > INT32_MAX) return bad("store full");
   if (const int rc = dsh_enter(c, "dsh_mpdb_add_keyframe")) return rc;
   HIPCHK(c, mpdb_reserve_keyframes(db, (long long)db->K + 1));
   if (db->T + N > db->Tcap) {
     const long long cap = std::max(db->T + N, 2 * db->Tcap);
-    HIPCHK(c, mpdb_grow(&db->d_table, (size_t)db->T, (size_t)cap));
+    HIPCHK(c, dsh_store_grow_array(&db->d_table, (size_t)db->T, (size_t)cap));
     db->Tcap = cap;
   }
   LmKf k;
@@ -277,7 +264,7 @@ int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_
 }
 
 int dsh_mpdb_set_keyframe_point(dsh_mpdb* db, int32_t slot, int32_t idx, int32_t point_id) {
-  MPDB_ENTER("dsh_mpdb_set_keyframe_point");
+  DSH_STORE_ENTER("dsh_mpdb_set_keyframe_point");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
   if (idx < 0 || idx >= db->kf[slot].N) return bad("index outside the keyframe's key points");
   if (point_id < -1 || point_id >= db->P) return bad("point_id is neither -1 nor a point of the store");
@@ -286,7 +273,7 @@ int dsh_mpdb_set_keyframe_point(dsh_mpdb* db, int32_t slot, int32_t idx, int32_t
 }
 
 int dsh_mpdb_set_keyframe_parent(dsh_mpdb* db, int32_t slot, int32_t parent) {
-  MPDB_ENTER("dsh_mpdb_set_keyframe_parent");
+  DSH_STORE_ENTER("dsh_mpdb_set_keyframe_parent");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
   if (parent < -1 || parent >= db->K || parent == slot) return bad("parent is neither -1 nor another slot of the store");
   if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_parent")) return rc;
@@ -295,7 +282,7 @@ int dsh_mpdb_set_keyframe_parent(dsh_mpdb* db, int32_t slot, int32_t parent) {
 }
 
 int dsh_mpdb_set_keyframe_bad(dsh_mpdb* db, int32_t slot, int32_t bad_flag) {
-  MPDB_ENTER("dsh_mpdb_set_keyframe_bad");
+  DSH_STORE_ENTER("dsh_mpdb_set_keyframe_bad");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
   if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_bad")) return rc;
   db->kf[slot].bad = bad_flag ? 1 : 0;
@@ -304,59 +291,52 @@ int dsh_mpdb_set_keyframe_bad(dsh_mpdb* db, int32_t slot, int32_t bad_flag) {
 
 int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8_t* frame_bad, int32_t kf_capacity, int32_t* local_kf,
                          int32_t* local_votes, int32_t* n_voted, int32_t* n_local_kf, int32_t* ref_kf, int32_t* n_local_points) {
-  MPDB_ENTER("dsh_local_map_update");
-  if (N < 0 || N > (1 << 20)) return bad("N outside 0 .. 2^20");
+  DSH_STORE_ENTER("dsh_local_map_update");
+  if (const char* ne = dsh_keypoint_count_error(N)) return bad(ne);
   if (N > 0 && !frame_points) return bad("frame_points is NULL");
-  for (int i = 0; i < N; i++)
-    if (frame_points[i] < -1 || frame_points[i] >= db->P) return bad("frame_points[" + std::to_string(i) + "] is neither -1 nor a point of the store");
+  const std::string te = mpdb_table_error(db, N, frame_points, "frame_points[", "]");
+  if (!te.empty()) return bad(te);
   if ((local_kf || local_votes) && kf_capacity < db->K) return bad("kf_capacity is smaller than the store's keyframe count");
   if (const int rc = dsh_enter(c, "dsh_local_map_update")) return rc;
 
   const size_t P = (size_t)db->P, K = (size_t)db->K, nb = (P + LM_CHUNK - 1) / LM_CHUNK;
-  Arena down;
-  const size_t d_hdr = down.take(sizeof(LmHdr)), d_kf = down.take(4 * K), d_votes = down.take(4 * K), d_fbad = down.take((size_t)N), down_bytes = down.size;
-  HIPCHK(c, c->pin_in.ensure(4 * (size_t)N, true));
-  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
-  if (N > 0) std::memcpy(c->pin_in.p, frame_points, 4 * (size_t)N);
+  UpBlock up;
+  DownBlock down;
+  const size_t o_fp = up.take_exact(4 * (size_t)N);
+  const size_t d_hdr = down.take(sizeof(LmHdr)), d_kf = down.take(4 * K), d_votes = down.take(4 * K), d_fbad = down.take((size_t)N);
+  if (const int rc = up.stage(c)) return rc;
+  if (N > 0) std::memcpy(up.host<int32_t>(o_fp), frame_points, 4 * (size_t)N);
   hipStream_t st = c->stream;
-  void *dup = nullptr, *dvotes = nullptr, *dmark = nullptr, *dflag = nullptr, *dblk = nullptr, *ddown = nullptr;
-  HIPCHK(c, c->scratch.take(4 * (size_t)N, &dup));
-  HIPCHK(c, c->scratch.take(4 * K, &dvotes));
-  HIPCHK(c, c->scratch.take(4 * K, &dmark));
-  HIPCHK(c, c->scratch.take(4 * P, &dflag));
-  HIPCHK(c, c->scratch.take(4 * nb, &dblk));
-  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
-  if (N > 0) HIPCHK(c, hipMemcpyAsync(dup, c->pin_in.p, 4 * (size_t)N, hipMemcpyHostToDevice, st));
-  char* dd = static_cast<char*>(ddown);
+  LmBufs b;
+  if (const int rc = up.send(c)) return rc;
+  HIPCHK(c, dsh_scratch_array(c, &b.votes, K));
+  HIPCHK(c, dsh_scratch_array(c, &b.mark, K));
+  HIPCHK(c, dsh_scratch_array(c, &b.flag, P));
+  HIPCHK(c, dsh_scratch_array(c, &b.block_cnt, nb));
+  if (const int rc = down.alloc(c)) return rc;
   // Tracking.cc:1475: SetReferenceMapPoints(mvpLocalMapPoints) before the list is rebuilt -- the list this call found stays, as the
   // reference list of dsh_track_close_frame, and the new one is written into the other buffer
   std::swap(db->d_local_ids, db->d_ref_ids);
   db->n_ref_points = db->n_local_points;
   db->P_cnt = db->P;
-  LmBufs b;
   b.P = db->P; b.K = db->K; b.N = N; b.R = db->R;
   b.bad = db->d_bad; b.log = db->d_log; b.kf = db->d_kf; b.table = db->d_table;
-  b.frame_points = static_cast<const int32_t*>(dup);
+  b.frame_points = up.dev<const int32_t>(o_fp);
   b.cnt = db->d_cnt;
-  b.votes = static_cast<int32_t*>(dvotes);
-  b.mark = static_cast<int32_t*>(dmark);
-  b.flag = static_cast<int32_t*>(dflag);
-  b.block_cnt = static_cast<int32_t*>(dblk);
   b.local_kf = db->d_local_kf; b.local_ids = db->d_local_ids; b.hdr = db->d_hdr;
-  b.out_hdr = reinterpret_cast<LmHdr*>(dd + d_hdr);
-  b.out_kf = reinterpret_cast<int32_t*>(dd + d_kf);
-  b.out_votes = reinterpret_cast<int32_t*>(dd + d_votes);
-  b.out_frame_bad = reinterpret_cast<uint8_t*>(dd + d_fbad);
+  b.out_hdr = down.dev<LmHdr>(d_hdr);
+  b.out_kf = down.dev<int32_t>(d_kf);
+  b.out_votes = down.dev<int32_t>(d_votes);
+  b.out_frame_bad = down.dev<uint8_t>(d_fbad);
   HIPCHK(c, lm_update_launch(b, st));
-  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
 
-  const char* o = c->pin_out.p;
-  const LmHdr h = *reinterpret_cast<const LmHdr*>(o + d_hdr);
+  const LmHdr h = *down.host<LmHdr>(d_hdr);
   db->n_local_points = h.n_local_points;
-  if (frame_bad && N > 0) std::memcpy(frame_bad, o + d_fbad, (size_t)N);
-  if (local_kf) std::memcpy(local_kf, o + d_kf, 4 * (size_t)h.n_local_kf);
-  if (local_votes) std::memcpy(local_votes, o + d_votes, 4 * (size_t)h.n_voted);
+  if (frame_bad && N > 0) std::memcpy(frame_bad, down.host<uint8_t>(d_fbad), (size_t)N);
+  if (local_kf) std::memcpy(local_kf, down.host<int32_t>(d_kf), 4 * (size_t)h.n_local_kf);
+  if (local_votes) std::memcpy(local_votes, down.host<int32_t>(d_votes), 4 * (size_t)h.n_voted);
   if (n_voted) *n_voted = h.n_voted;
   if (n_local_kf) *n_local_kf = h.n_local_kf;
   if (ref_kf) *ref_kf = h.ref_kf;
@@ -365,7 +345,7 @@ int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8
 }
 
 int dsh_local_map_points(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* n) {
-  MPDB_ENTER("dsh_local_map_points");
+  DSH_STORE_ENTER("dsh_local_map_points");
   if (capacity < db->n_local_points) return bad("capacity is smaller than the number of local points");
   if (db->n_local_points > 0 && !ids) return bad("ids is NULL");
   if (const int rc = dsh_enter(c, "dsh_local_map_points")) return rc;
@@ -379,7 +359,7 @@ int dsh_local_map_points(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* 
 
 int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, int32_t capacity, int32_t* local_ids, int32_t* match,
                          uint8_t* in_view, int32_t* level, float* uv, float* view_cos, int32_t* nmatches) {
-  MPDB_ENTER("dsh_local_map_search");
+  DSH_STORE_ENTER("dsh_local_map_search");
   if (!frame) return bad("frame is NULL");
   const std::string fe = trk_frame_error(*frame);
   if (!fe.empty()) return bad(fe);
@@ -397,96 +377,50 @@ int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, i
     return DSH_OK;
   }
 
-  // up: the frame and its key points; the queries are gathered from the store on the device
+  // up: the frame and its key points; the queries are gathered from the store on the device, and their ids come down too
   const dsh_track_frame& f = *frame;
-  const size_t N = (size_t)f.N, q = (size_t)Q, cells = (size_t)f.grid_cols * f.grid_rows + 1;
-  Arena up, down;
-  const size_t o_prob = up.take(sizeof(TrkProb)), o_kp = up.take(8 * N), o_km = up.take(4 * N), o_kd = up.take(32 * N), up_bytes = up.size;
-  const size_t d_match = down.take(4 * q), d_level = down.take(4 * q), d_inview = down.take(4 * q), d_uv = down.take(8 * q), d_vcos = down.take(4 * q),
-               d_pstat = down.take(16), d_ids = down.take(4 * q), down_bytes = down.size;
-  HIPCHK(c, c->pin_in.ensure(up_bytes, true));
-  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
-  char* h = c->pin_in.p;
+  const size_t q = (size_t)Q;
+  UpBlock up;
+  DownBlock down;
+  TrkPlan pl;
+  trk_plan_layout(pl, up, down, 1, (size_t)f.N, q, (size_t)f.grid_cols * f.grid_rows + 1);
+  const size_t d_ids = down.take(4 * q);
+  if (const int rc = up.stage(c)) return rc;
   TrkProb pr;
   trk_fill_prob(pr, f, DSH_TRACK_LOCAL, th, Q);
-  std::memcpy(h + o_prob, &pr, sizeof(pr));
-  if (N > 0) {
-    std::memcpy(h + o_kp, f.kp, 8 * N);
-    int32_t* km = reinterpret_cast<int32_t*>(h + o_km);
-    for (size_t j = 0; j < N; j++) km[j] = f.octave[j] | ((int32_t)f.state[j] << 8);
-    std::memcpy(h + o_kd, f.desc, 32 * N);
-  }
+  trk_plan_pack_frame(pl, up, 0, pr, f);
   hipStream_t st = c->stream;
-  void *dup = nullptr, *dcell = nullptr, *dskp = nullptr, *dsmeta = nullptr, *dsdesc = nullptr, *dkeys = nullptr, *dncand = nullptr, *dwin = nullptr,
-       *ddown = nullptr, *dqpid = nullptr, *dqxyz = nullptr, *dqnrm = nullptr, *dqmaxd = nullptr, *dqmeta = nullptr, *dqdesc = nullptr;
-  HIPCHK(c, c->scratch.take(up_bytes, &dup));
-  HIPCHK(c, c->scratch.take(4 * cells, &dcell));
-  HIPCHK(c, c->scratch.take(8 * N, &dskp));
-  HIPCHK(c, c->scratch.take(4 * N, &dsmeta));
-  HIPCHK(c, c->scratch.take(32 * N, &dsdesc));
-  HIPCHK(c, c->scratch.take(8 * (size_t)TRK_K * q, &dkeys));
-  HIPCHK(c, c->scratch.take(4 * q, &dncand));
-  HIPCHK(c, c->scratch.take(sizeof(TrkWin) * q, &dwin));
-  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
-  HIPCHK(c, c->scratch.take(4 * q, &dqpid));
-  HIPCHK(c, c->scratch.take(12 * q, &dqxyz));
-  HIPCHK(c, c->scratch.take(12 * q, &dqnrm));
-  HIPCHK(c, c->scratch.take(4 * q, &dqmaxd));
-  HIPCHK(c, c->scratch.take(4 * q, &dqmeta));
-  HIPCHK(c, c->scratch.take(32 * q, &dqdesc));
-  HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
-  char* du = static_cast<char*>(dup);
-  char* dd = static_cast<char*>(ddown);
-  HIPCHK(c, hipMemsetAsync(dd + d_pstat, 0, 16, st));
+  TrkBufs b;
+  if (const int rc = trk_plan_device(c, pl, up, down, b)) return rc;
   LmQueryBufs g;
+  HIPCHK(c, dsh_scratch_array(c, &g.qpid, q));
+  HIPCHK(c, dsh_scratch_array(c, &g.qxyz, 3 * q));
+  HIPCHK(c, dsh_scratch_array(c, &g.qnrm, 3 * q));
+  HIPCHK(c, dsh_scratch_array(c, &g.qmaxd, q));
+  HIPCHK(c, dsh_scratch_array(c, &g.qmeta, q));
+  HIPCHK(c, dsh_scratch_array(c, &g.qdesc, 2 * q));
   g.xyz = db->d_xyz; g.normal = db->d_nrm; g.max_distance = db->d_maxd; g.desc = db->d_desc; g.bad = db->d_bad; g.cnt = db->d_cnt;
   g.local_ids = db->d_local_ids;
-  g.qpid = static_cast<int32_t*>(dqpid);
-  g.qxyz = static_cast<float*>(dqxyz);
-  g.qnrm = static_cast<float*>(dqnrm);
-  g.qmaxd = static_cast<float*>(dqmaxd);
-  g.qmeta = static_cast<int32_t*>(dqmeta);
-  g.qdesc = static_cast<uint4*>(dqdesc);
-  g.out_ids = reinterpret_cast<int32_t*>(dd + d_ids);
+  g.out_ids = down.dev<int32_t>(d_ids);
   HIPCHK(c, lm_gather_launch(g, Q, st));
-  TrkBufs b;
-  b.prob = reinterpret_cast<const TrkProb*>(du + o_prob);
-  b.kp = reinterpret_cast<const float2*>(du + o_kp);
-  b.kmeta = reinterpret_cast<const int32_t*>(du + o_km);
-  b.kdesc = reinterpret_cast<const uint4*>(du + o_kd);
-  b.cell_start = static_cast<int32_t*>(dcell);
-  b.skp = static_cast<float2*>(dskp);
-  b.smeta = static_cast<int32_t*>(dsmeta);
-  b.sdesc = static_cast<uint4*>(dsdesc);
   b.qpid = g.qpid; b.qxyz = g.qxyz; b.qnrm = g.qnrm; b.qmaxd = g.qmaxd; b.qmeta = g.qmeta; b.qdesc = g.qdesc;
-  b.keys = static_cast<unsigned long long*>(dkeys);
-  b.ncand = static_cast<int32_t*>(dncand);
-  b.win = static_cast<TrkWin*>(dwin);
-  b.match = reinterpret_cast<int32_t*>(dd + d_match);
-  b.level = reinterpret_cast<int32_t*>(dd + d_level);
-  b.inview = reinterpret_cast<int32_t*>(dd + d_inview);
-  b.uv = reinterpret_cast<float*>(dd + d_uv);
-  b.vcos = reinterpret_cast<float*>(dd + d_vcos);
-  b.pstat = reinterpret_cast<int32_t*>(dd + d_pstat);
   HIPCHK(c, trk_launch(b, 1, Q, st));
   // MapPoint::IncreaseVisible of the points the frame holds and of the queries in view (Tracking.cc:1408-1425, :1456); not when the search refuses
   HIPCHK(c, tc_visible_launch(db->d_visible, db->d_cnt, db->P_cnt, g.out_ids, b.inview, Q, b.pstat + 2, st));
-  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
 
-  const char* o = c->pin_out.p;
-  const int32_t* pstat = reinterpret_cast<const int32_t*>(o + d_pstat);
-  if (pstat[2]) return bad("a query window holds more than 4096 candidates");
-  std::memcpy(match, o + d_match, 4 * q);
-  if (local_ids) std::memcpy(local_ids, o + d_ids, 4 * q);
+  if (trk_plan_refused(pl, down) >= 0) return bad(TRK_REFUSED);
+  std::memcpy(match, down.host<int32_t>(pl.d_match), 4 * q);
+  if (local_ids) std::memcpy(local_ids, down.host<int32_t>(d_ids), 4 * q);
   if (in_view) {
-    const int32_t* iv = reinterpret_cast<const int32_t*>(o + d_inview);
+    const int32_t* iv = down.host<int32_t>(pl.d_inview);
     for (size_t i = 0; i < q; i++) in_view[i] = (uint8_t)iv[i];
   }
-  if (level) std::memcpy(level, o + d_level, 4 * q);
-  if (uv) std::memcpy(uv, o + d_uv, 8 * q);
-  if (view_cos) std::memcpy(view_cos, o + d_vcos, 4 * q);
-  if (nmatches) *nmatches = pstat[0];
+  if (level) std::memcpy(level, down.host<int32_t>(pl.d_level), 4 * q);
+  if (uv) std::memcpy(uv, down.host<float>(pl.d_uv), 8 * q);
+  if (view_cos) std::memcpy(view_cos, down.host<float>(pl.d_vcos), 4 * q);
+  if (nmatches) *nmatches = down.host<int32_t>(pl.d_pstat)[0];
   return DSH_OK;
 }
 

@@ -29,11 +29,6 @@ struct dsh_kfdb : dsh_store {
 
 namespace {
 
-// grow-on-demand device arrays: a new allocation of at least twice the capacity, the stored part copied device to device
-hipError_t grow(void** p, size_t used, size_t need_bytes) {
-  return dsh_store_grow(p, need_bytes, [&](char* q) { return used ? hipMemcpy(q, *p, used, hipMemcpyDeviceToDevice) : hipSuccess; });
-}
-
 int width_class(int M) { return M <= 8 ? 0 : M <= 16 ? 1 : M <= 32 ? 2 : 3; }
 
 }  // namespace
@@ -70,7 +65,7 @@ int dsh_kfdb_destroy(dsh_kfdb* db) {
 }
 
 int dsh_kfdb_clear(dsh_kfdb* db) {
-  if (!db || !db->ctx) return DSH_ERR_ARG;
+  DSH_STORE_ENTER("dsh_kfdb_clear");
   db->count = 0;
   db->rows = 0;
   db->kf.clear();
@@ -79,21 +74,19 @@ int dsh_kfdb_clear(dsh_kfdb* db) {
 
 int32_t dsh_kfdb_count(const dsh_kfdb* db) { return db ? db->count : -1; }
 
-int dsh_kfdb_set_bad(dsh_kfdb* db, int32_t slot, int32_t bad) {
-  if (!db || !db->ctx) return DSH_ERR_ARG;
-  if (slot < 0 || slot >= db->count) return dsh_fail(db->ctx, DSH_ERR_ARG, "dsh_kfdb_set_bad: slot outside the store");
-  db->kf[slot].bad = bad ? 1 : 0;   // read by the host when it lists a call's election rows
+int dsh_kfdb_set_bad(dsh_kfdb* db, int32_t slot, int32_t bad_flag) {
+  DSH_STORE_ENTER("dsh_kfdb_set_bad");
+  if (slot < 0 || slot >= db->count) return bad("slot outside the store");
+  db->kf[slot].bad = bad_flag ? 1 : 0;   // read by the host when it lists a call's election rows
   return DSH_OK;
 }
 
 int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
-  if (!db || !db->ctx) return DSH_ERR_ARG;
-  dsh_ctx_base* c = db->ctx;
-  auto bad = [&](const char* m) { return dsh_fail(c, DSH_ERR_ARG, std::string("dsh_kfdb_add: ") + m); };
+  DSH_STORE_ENTER("dsh_kfdb_add");
   if (!kf) return bad("keyframe is NULL");
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(kf->Ow[k])) return bad("camera centre not finite");
-  if (kf->N < 0 || kf->N > (1 << 20)) return bad("N outside 0 .. 2^20");
+  if (const char* ne = dsh_keypoint_count_error(kf->N)) return bad(ne);
   if (kf->N > 0 && (!kf->desc || !kf->octave)) return bad("key point arrays are NULL");
   if (kf->levels <= 0 || kf->levels > MPU_MAX_LEVELS || !kf->scale_factors) return bad("levels outside 1 .. 32 or no scale factors");
   for (int j = 0; j < kf->N; j++)
@@ -102,13 +95,13 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
   if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: hipSetDevice failed");
   if (db->count + 1 > db->cap) {
     const int32_t ncap = (int32_t)std::min<long long>(2ll * db->cap, INT32_MAX);
-    if (grow((void**)&db->d_slots, sizeof(MpuSlot) * (size_t)db->count, sizeof(MpuSlot) * (size_t)ncap) != hipSuccess)
+    if (dsh_store_grow_array(&db->d_slots, (size_t)db->count, (size_t)ncap) != hipSuccess)
       return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
     db->cap = ncap;
   }
   if (db->rows + kf->N > db->row_cap) {
     const long long ncap = std::max(db->rows + kf->N, 2 * db->row_cap);
-    if (grow((void**)&db->d_rows, 32 * (size_t)db->rows, 32 * (size_t)ncap) != hipSuccess)
+    if (dsh_store_grow_array(&db->d_rows, 2 * (size_t)db->rows, 2 * (size_t)ncap) != hipSuccess)
       return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
     db->row_cap = ncap;
   }
@@ -236,53 +229,45 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   const size_t Met = el_row.size();
 
   // one host buffer, one copy up
-  Arena up, down;
+  UpBlock up;
+  DownBlock down;
   const size_t o_pts = up.take(sizeof(MpuPoint) * P), o_oslot = up.take(4 * (size_t)Mt), o_el = up.take(4 * Met), o_small = up.take(4 * small_order.size()),
-               o_blk = up.take(4 * blocks.size()), o_lpts = up.take(4 * (size_t)NL), up_bytes = up.size;
-  const size_t d_best = down.take(4 * (size_t)P), d_desc = down.take(32 * (size_t)P), d_nrm = down.take(12 * (size_t)P), d_dist = down.take(8 * (size_t)P),
-               down_bytes = down.size;
-  HIPCHK(c, c->pin_in.ensure(up_bytes, true));
-  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
-  char* h = c->pin_in.p;
-  std::memcpy(h + o_pts, pts.data(), sizeof(MpuPoint) * P);
-  if (Mt > 0) std::memcpy(h + o_oslot, obs_kf, 4 * (size_t)Mt);
-  if (Met > 0) std::memcpy(h + o_el, el_row.data(), 4 * Met);
-  if (!small_order.empty()) std::memcpy(h + o_small, small_order.data(), 4 * small_order.size());
-  if (!blocks.empty()) std::memcpy(h + o_blk, blocks.data(), 4 * blocks.size());
-  if (NL > 0) std::memcpy(h + o_lpts, large_pts.data(), 4 * (size_t)NL);
+               o_blk = up.take(4 * blocks.size()), o_lpts = up.take(4 * (size_t)NL);
+  const size_t d_best = down.take(4 * (size_t)P), d_desc = down.take(32 * (size_t)P), d_nrm = down.take(12 * (size_t)P), d_dist = down.take(8 * (size_t)P);
+  if (const int rc = up.stage(c)) return rc;
+  std::memcpy(up.host<MpuPoint>(o_pts), pts.data(), sizeof(MpuPoint) * P);
+  if (Mt > 0) std::memcpy(up.host<int32_t>(o_oslot), obs_kf, 4 * (size_t)Mt);
+  if (Met > 0) std::memcpy(up.host<int32_t>(o_el), el_row.data(), 4 * Met);
+  if (!small_order.empty()) std::memcpy(up.host<int32_t>(o_small), small_order.data(), 4 * small_order.size());
+  if (!blocks.empty()) std::memcpy(up.host<int32_t>(o_blk), blocks.data(), 4 * blocks.size());
+  if (NL > 0) std::memcpy(up.host<int32_t>(o_lpts), large_pts.data(), 4 * (size_t)NL);
 
   hipStream_t st = c->stream;
-  void *dup = nullptr, *ddown = nullptr, *dkey = nullptr;
-  HIPCHK(c, c->scratch.take(up_bytes, &dup));
-  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
-  HIPCHK(c, c->scratch.take(4 * (size_t)P, &dkey));
-  HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
-  if (NL > 0) HIPCHK(c, hipMemsetAsync(dkey, 0xFF, 4 * (size_t)P, st));
-  char* du = static_cast<char*>(dup);
-  char* dd = static_cast<char*>(ddown);
   MpuBufs b;
+  if (const int rc = up.send(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  HIPCHK(c, dsh_scratch_array(c, &b.large_key, (size_t)P));
+  if (NL > 0) HIPCHK(c, hipMemsetAsync(b.large_key, 0xFF, 4 * (size_t)P, st));
   b.slots = db->d_slots;
   b.rows = db->d_rows;
-  b.pts = reinterpret_cast<const MpuPoint*>(du + o_pts);
-  b.obs_slot = reinterpret_cast<const int32_t*>(du + o_oslot);
-  b.el_row = reinterpret_cast<const int32_t*>(du + o_el);
-  b.small_order = reinterpret_cast<const int32_t*>(du + o_small);
-  b.large_blocks = reinterpret_cast<const int2*>(du + o_blk);
-  b.large_key = static_cast<uint32_t*>(dkey);
-  b.large_pts = reinterpret_cast<const int32_t*>(du + o_lpts);
-  b.best = reinterpret_cast<int32_t*>(dd + d_best);
-  b.desc = reinterpret_cast<uint4*>(dd + d_desc);
-  b.normal = reinterpret_cast<float*>(dd + d_nrm);
-  b.dist = reinterpret_cast<float*>(dd + d_dist);
+  b.pts = up.dev<const MpuPoint>(o_pts);
+  b.obs_slot = up.dev<const int32_t>(o_oslot);
+  b.el_row = up.dev<const int32_t>(o_el);
+  b.small_order = up.dev<const int32_t>(o_small);
+  b.large_blocks = up.dev<const int2>(o_blk);
+  b.large_pts = up.dev<const int32_t>(o_lpts);
+  b.best = down.dev<int32_t>(d_best);
+  b.desc = down.dev<uint4>(d_desc);
+  b.normal = down.dev<float>(d_nrm);
+  b.dist = down.dev<float>(d_dist);
   HIPCHK(c, mpu_launch(b, small_off, NB, NL, st));
-  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
 
   // outputs: only what was asked for, only where the reference writes
-  const char* o = c->pin_out.p;
-  const int32_t* obest = reinterpret_cast<const int32_t*>(o + d_best);
-  const float* onrm = reinterpret_cast<const float*>(o + d_nrm);
-  const float* odist = reinterpret_cast<const float*>(o + d_dist);
+  const int32_t* obest = down.host<int32_t>(d_best);
+  const float* onrm = down.host<float>(d_nrm);
+  const float* odist = down.host<float>(d_dist);
   for (int p = 0; p < P; p++) {
     const MpuPoint& q = pts[p];
     int32_t flags = 0;
@@ -291,7 +276,7 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
     if (want_d) {
       const bool elected = q.Me > 0;
       if (best) best[p] = elected ? el_obs[q.el_off + obest[p]] : -1;
-      if (elected) std::memcpy(desc + 32 * (size_t)p, o + d_desc + 32 * (size_t)p, 32);
+      if (elected) std::memcpy(desc + 32 * (size_t)p, down.host<uint4>(d_desc) + 2 * (size_t)p, 32);
     }
     if (want_g && q.M > 0) {
       std::memcpy(normal + 3 * (size_t)p, onrm + 3 * (size_t)p, 12);

@@ -1,5 +1,5 @@
 // Host side of the tracking searches (include/defslam_hip.h: dsh_search_by_projection_*): validation, one packed upload, the three
-// launches of track_kernels.hip, one download.
+// launches of track_kernels.hip, one download.  The device plan of a search (trk_plan_*) is shared with dsh_local_map_search.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -54,6 +54,54 @@ void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int
   P.N = f.N; P.Q = Q;
 }
 
+void trk_plan_layout(TrkPlan& pl, UpBlock& up, DownBlock& down, size_t B, size_t Nt, size_t Qt, size_t Ct) {
+  pl.B = B; pl.Nt = Nt; pl.Qt = Qt; pl.Ct = Ct;
+  pl.o_prob = up.take(sizeof(TrkProb) * B); pl.o_kp = up.take(8 * Nt); pl.o_km = up.take(4 * Nt); pl.o_kd = up.take(32 * Nt);
+  pl.d_match = down.take(4 * Qt); pl.d_level = down.take(4 * Qt); pl.d_inview = down.take(4 * Qt); pl.d_uv = down.take(8 * Qt);
+  pl.d_vcos = down.take(4 * Qt); pl.d_pstat = down.take(16 * B);
+}
+
+void trk_plan_pack_frame(const TrkPlan& pl, UpBlock& up, int p, const TrkProb& P, const dsh_track_frame& f) {
+  up.host<TrkProb>(pl.o_prob)[p] = P;
+  if (f.N <= 0) return;
+  const size_t N = (size_t)f.N, at = (size_t)P.kp_off;
+  std::memcpy(up.host<float2>(pl.o_kp) + at, f.kp, 8 * N);
+  int32_t* km = up.host<int32_t>(pl.o_km) + at;
+  for (size_t j = 0; j < N; j++) km[j] = f.octave[j] | ((int32_t)f.state[j] << 8);
+  std::memcpy(up.host<uint4>(pl.o_kd) + 2 * at, f.desc, 32 * N);
+}
+
+int trk_plan_device(dsh_ctx_base* c, const TrkPlan& pl, UpBlock& up, DownBlock& down, TrkBufs& b) {
+  if (const int rc = up.send(c)) return rc;
+  HIPCHK(c, dsh_scratch_array(c, &b.cell_start, pl.Ct));
+  HIPCHK(c, dsh_scratch_array(c, &b.skp, pl.Nt));
+  HIPCHK(c, dsh_scratch_array(c, &b.smeta, pl.Nt));
+  HIPCHK(c, dsh_scratch_array(c, &b.sdesc, 2 * pl.Nt));
+  HIPCHK(c, dsh_scratch_array(c, &b.keys, TRK_K * pl.Qt));
+  HIPCHK(c, dsh_scratch_array(c, &b.ncand, pl.Qt));
+  HIPCHK(c, dsh_scratch_array(c, &b.win, pl.Qt));
+  if (const int rc = down.alloc(c)) return rc;
+  b.pstat = down.dev<int32_t>(pl.d_pstat);
+  HIPCHK(c, hipMemsetAsync(b.pstat, 0, 16 * pl.B, c->stream));
+  b.prob = up.dev<const TrkProb>(pl.o_prob);
+  b.kp = up.dev<const float2>(pl.o_kp);
+  b.kmeta = up.dev<const int32_t>(pl.o_km);
+  b.kdesc = up.dev<const uint4>(pl.o_kd);
+  b.match = down.dev<int32_t>(pl.d_match);
+  b.level = down.dev<int32_t>(pl.d_level);
+  b.inview = down.dev<int32_t>(pl.d_inview);
+  b.uv = down.dev<float>(pl.d_uv);
+  b.vcos = down.dev<float>(pl.d_vcos);
+  return DSH_OK;
+}
+
+int trk_plan_refused(const TrkPlan& pl, const DownBlock& down) {
+  const int32_t* pstat = down.host<int32_t>(pl.d_pstat);
+  for (size_t p = 0; p < pl.B; p++)
+    if (pstat[4 * p + 2]) return (int)p;
+  return -1;
+}
+
 extern "C" {
 
 int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* problems) {
@@ -87,18 +135,14 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   if (const int rc = dsh_enter(c, "dsh_search_by_projection")) return rc;
   if (B == 0) return DSH_OK;
 
-  // one host buffer, one copy up: problem descriptors, key points, queries
-  Arena up;
-  const size_t o_prob = up.take(sizeof(TrkProb) * B), o_kp = up.take(8 * Nt), o_km = up.take(4 * Nt), o_kd = up.take(32 * Nt), o_qpid = up.take(4 * Qt),
-               o_qxyz = up.take(12 * Qt), o_qnrm = up.take(12 * Qt), o_qmaxd = up.take(4 * Qt), o_qmeta = up.take(4 * Qt), o_qdesc = up.take(32 * Qt),
-               up_bytes = up.size;
-  // downloads: match, level, in view, uv, view cos, per-problem counters
-  Arena down;
-  const size_t d_match = down.take(4 * Qt), d_level = down.take(4 * Qt), d_inview = down.take(4 * Qt), d_uv = down.take(8 * Qt), d_vcos = down.take(4 * Qt),
-               d_pstat = down.take(16 * (size_t)B), down_bytes = down.size;
-  HIPCHK(c, c->pin_in.ensure(up_bytes, true));
-  HIPCHK(c, c->pin_out.ensure(down_bytes, true));
-  char* h = c->pin_in.p;
+  // one host buffer, one copy up: problem descriptors, key points, queries; one copy down: match, level, in view, uv, view cos, counters
+  UpBlock up;
+  DownBlock down;
+  TrkPlan pl;
+  trk_plan_layout(pl, up, down, (size_t)B, (size_t)Nt, (size_t)Qt, (size_t)Ct);
+  const size_t o_qpid = up.take(4 * Qt), o_qxyz = up.take(12 * Qt), o_qnrm = up.take(12 * Qt), o_qmaxd = up.take(4 * Qt), o_qmeta = up.take(4 * Qt),
+               o_qdesc = up.take(32 * Qt);
+  if (const int rc = up.stage(c)) return rc;
   long long kp_off = 0, q_off = 0, cell_off = 0;
   for (int p = 0; p < B; p++) {
     const dsh_track_problem& pr = problems[p];
@@ -106,26 +150,20 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
     TrkProb P;
     trk_fill_prob(P, f, pr.mode, pr.th, pr.Q);
     P.kp_off = (int32_t)kp_off; P.q_off = (int32_t)q_off; P.cell_off = (int32_t)cell_off;
-    std::memcpy(h + o_prob + sizeof(TrkProb) * p, &P, sizeof(P));
-    if (f.N > 0) {
-      std::memcpy(h + o_kp + 8 * kp_off, f.kp, 8 * (size_t)f.N);
-      int32_t* km = reinterpret_cast<int32_t*>(h + o_km) + kp_off;
-      for (int j = 0; j < f.N; j++) km[j] = f.octave[j] | ((int32_t)f.state[j] << 8);
-      std::memcpy(h + o_kd + 32 * kp_off, f.desc, 32 * (size_t)f.N);
-    }
+    trk_plan_pack_frame(pl, up, p, P, f);
     if (pr.Q > 0) {
-      int32_t* qpid = reinterpret_cast<int32_t*>(h + o_qpid) + q_off;
-      int32_t* qmeta = reinterpret_cast<int32_t*>(h + o_qmeta) + q_off;
+      int32_t* qpid = up.host<int32_t>(o_qpid) + q_off;
+      int32_t* qmeta = up.host<int32_t>(o_qmeta) + q_off;
       for (int q = 0; q < pr.Q; q++) {
         qpid[q] = p;
         qmeta[q] = pr.mode == DSH_TRACK_FRAME ? pr.octave[q] : (pr.skip && pr.skip[q] ? 1 : 0);
       }
-      std::memcpy(h + o_qxyz + 12 * q_off, pr.xyz, 12 * (size_t)pr.Q);
+      std::memcpy(up.host<float>(o_qxyz) + 3 * q_off, pr.xyz, 12 * (size_t)pr.Q);
       if (pr.mode == DSH_TRACK_LOCAL) {
-        std::memcpy(h + o_qnrm + 12 * q_off, pr.normal, 12 * (size_t)pr.Q);
-        std::memcpy(h + o_qmaxd + 4 * q_off, pr.max_distance, 4 * (size_t)pr.Q);
+        std::memcpy(up.host<float>(o_qnrm) + 3 * q_off, pr.normal, 12 * (size_t)pr.Q);
+        std::memcpy(up.host<float>(o_qmaxd) + q_off, pr.max_distance, 4 * (size_t)pr.Q);
       }
-      std::memcpy(h + o_qdesc + 32 * q_off, pr.desc, 32 * (size_t)pr.Q);
+      std::memcpy(up.host<uint4>(o_qdesc) + 2 * q_off, pr.desc, 32 * (size_t)pr.Q);
     }
     kp_off += f.N;
     q_off += pr.Q;
@@ -133,67 +171,34 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   }
 
   hipStream_t st = c->stream;
-  void *dup = nullptr, *dcell = nullptr, *dskp = nullptr, *dsmeta = nullptr, *dsdesc = nullptr, *dkeys = nullptr, *dncand = nullptr, *dwin = nullptr,
-       *ddown = nullptr;
-  HIPCHK(c, c->scratch.take(up_bytes, &dup));
-  HIPCHK(c, c->scratch.take(4 * (size_t)Ct, &dcell));
-  HIPCHK(c, c->scratch.take(8 * (size_t)Nt, &dskp));
-  HIPCHK(c, c->scratch.take(4 * (size_t)Nt, &dsmeta));
-  HIPCHK(c, c->scratch.take(32 * (size_t)Nt, &dsdesc));
-  HIPCHK(c, c->scratch.take(8 * (size_t)TRK_K * Qt, &dkeys));
-  HIPCHK(c, c->scratch.take(4 * (size_t)Qt, &dncand));
-  HIPCHK(c, c->scratch.take(sizeof(TrkWin) * (size_t)Qt, &dwin));
-  HIPCHK(c, c->scratch.take(down_bytes, &ddown));
-  HIPCHK(c, hipMemcpyAsync(dup, h, up_bytes, hipMemcpyHostToDevice, st));
-  char* du = static_cast<char*>(dup);
-  char* dd = static_cast<char*>(ddown);
-  HIPCHK(c, hipMemsetAsync(dd + d_pstat, 0, 16 * (size_t)B, st));
   TrkBufs b;
-  b.prob = reinterpret_cast<const TrkProb*>(du + o_prob);
-  b.kp = reinterpret_cast<const float2*>(du + o_kp);
-  b.kmeta = reinterpret_cast<const int32_t*>(du + o_km);
-  b.kdesc = reinterpret_cast<const uint4*>(du + o_kd);
-  b.cell_start = static_cast<int32_t*>(dcell);
-  b.skp = static_cast<float2*>(dskp);
-  b.smeta = static_cast<int32_t*>(dsmeta);
-  b.sdesc = static_cast<uint4*>(dsdesc);
-  b.qpid = reinterpret_cast<const int32_t*>(du + o_qpid);
-  b.qxyz = reinterpret_cast<const float*>(du + o_qxyz);
-  b.qnrm = reinterpret_cast<const float*>(du + o_qnrm);
-  b.qmaxd = reinterpret_cast<const float*>(du + o_qmaxd);
-  b.qmeta = reinterpret_cast<const int32_t*>(du + o_qmeta);
-  b.qdesc = reinterpret_cast<const uint4*>(du + o_qdesc);
-  b.keys = static_cast<unsigned long long*>(dkeys);
-  b.ncand = static_cast<int32_t*>(dncand);
-  b.win = static_cast<TrkWin*>(dwin);
-  b.match = reinterpret_cast<int32_t*>(dd + d_match);
-  b.level = reinterpret_cast<int32_t*>(dd + d_level);
-  b.inview = reinterpret_cast<int32_t*>(dd + d_inview);
-  b.uv = reinterpret_cast<float*>(dd + d_uv);
-  b.vcos = reinterpret_cast<float*>(dd + d_vcos);
-  b.pstat = reinterpret_cast<int32_t*>(dd + d_pstat);
+  if (const int rc = trk_plan_device(c, pl, up, down, b)) return rc;
+  b.qpid = up.dev<const int32_t>(o_qpid);
+  b.qxyz = up.dev<const float>(o_qxyz);
+  b.qnrm = up.dev<const float>(o_qnrm);
+  b.qmaxd = up.dev<const float>(o_qmaxd);
+  b.qmeta = up.dev<const int32_t>(o_qmeta);
+  b.qdesc = up.dev<const uint4>(o_qdesc);
   HIPCHK(c, trk_launch(b, B, (int)Qt, st));
-  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, ddown, down_bytes, hipMemcpyDeviceToHost, st));
+  if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
 
-  const char* o = c->pin_out.p;
-  const int32_t* pstat = reinterpret_cast<const int32_t*>(o + d_pstat);
-  for (int p = 0; p < B; p++)
-    if (pstat[4 * p + 2])
-      return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(p) + ": a query window holds more than 4096 candidates");
+  const int refused = trk_plan_refused(pl, down);
+  if (refused >= 0) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(refused) + ": " TRK_REFUSED);
+  const int32_t* pstat = down.host<int32_t>(pl.d_pstat);
   q_off = 0;
   for (int p = 0; p < B; p++) {
     dsh_track_problem& pr = problems[p];
     const size_t Q = (size_t)pr.Q;
     if (Q > 0) {
-      std::memcpy(pr.match, o + d_match + 4 * q_off, 4 * Q);
+      std::memcpy(pr.match, down.host<int32_t>(pl.d_match) + q_off, 4 * Q);
       if (pr.mode == DSH_TRACK_LOCAL) {
-        const int32_t* iv = reinterpret_cast<const int32_t*>(o + d_inview) + q_off;
+        const int32_t* iv = down.host<int32_t>(pl.d_inview) + q_off;
         if (pr.in_view)
           for (size_t q = 0; q < Q; q++) pr.in_view[q] = (uint8_t)iv[q];
-        if (pr.level) std::memcpy(pr.level, o + d_level + 4 * q_off, 4 * Q);
-        if (pr.uv) std::memcpy(pr.uv, o + d_uv + 8 * q_off, 8 * Q);
-        if (pr.view_cos) std::memcpy(pr.view_cos, o + d_vcos + 4 * q_off, 4 * Q);
+        if (pr.level) std::memcpy(pr.level, down.host<int32_t>(pl.d_level) + q_off, 4 * Q);
+        if (pr.uv) std::memcpy(pr.uv, down.host<float>(pl.d_uv) + 2 * q_off, 8 * Q);
+        if (pr.view_cos) std::memcpy(pr.view_cos, down.host<float>(pl.d_vcos) + q_off, 4 * Q);
       }
     }
     pr.nmatches = pstat[4 * p];

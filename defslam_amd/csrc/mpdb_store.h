@@ -1,5 +1,5 @@
 // The map point store dsh_mpdb as its two translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*) and dsh_trackclose.cpp
-// (dsh_trackstate_*, dsh_track_close_frame).  The arrays in HBM, the host mirror that validates, and the first checks of an entry point.
+// (dsh_trackstate_*, dsh_track_close_frame).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "localmap_problem.h"
+#include "trackclose_problem.h"
 
 struct dsh_mpdb : dsh_store {
   int32_t P = 0, Pcap = 0, K = 0, Kcap = 0;
@@ -56,23 +57,25 @@ struct dsh_mpdb : dsh_store {
 
 inline uint64_t mpdb_obs_key(int32_t point, int32_t slot) { return ((uint64_t)(uint32_t)point << 32) | (uint32_t)slot; }
 
-// grow-on-demand device array of T: a new allocation, the `used` leading elements copied device to device
-template <class T>
-hipError_t mpdb_grow(T** p, size_t used, size_t cap) {
-  return dsh_store_grow((void**)p, sizeof(T) * cap, [&](char* q) { return used ? hipMemcpy(q, *p, sizeof(T) * used, hipMemcpyDeviceToDevice) : hipSuccess; });
+// the per-point tracking state as the kernels of trackclose_kernels.hip take it
+inline TcState mpdb_state(const dsh_mpdb* db) {
+  TcState s;
+  s.xyz = db->d_xyz; s.bad = db->d_bad; s.visible = db->d_visible; s.found = db->d_found; s.nobs = db->d_nobs; s.nodes = db->d_nodes;
+  s.bary = db->d_bary;
+  return s;
 }
 
 inline hipError_t mpdb_reserve_points(dsh_mpdb* db, long long need) {
   if (need <= db->Pcap) return hipSuccess;
   const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Pcap), INT32_MAX), P = (size_t)db->P;
   hipError_t e;
-  if ((e = mpdb_grow(&db->d_xyz, 3 * P, 3 * cap)) != hipSuccess || (e = mpdb_grow(&db->d_nrm, 3 * P, 3 * cap)) != hipSuccess ||
-      (e = mpdb_grow(&db->d_maxd, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_desc, 2 * P, 2 * cap)) != hipSuccess ||
-      (e = mpdb_grow(&db->d_bad, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_cnt, P, cap)) != hipSuccess ||
-      (e = mpdb_grow(&db->d_local_ids, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_ref_ids, P, cap)) != hipSuccess ||
-      (e = mpdb_grow(&db->d_visible, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_found, P, cap)) != hipSuccess ||
-      (e = mpdb_grow(&db->d_nobs, P, cap)) != hipSuccess || (e = mpdb_grow(&db->d_nodes, 3 * P, 3 * cap)) != hipSuccess ||
-      (e = mpdb_grow(&db->d_bary, 3 * P, 3 * cap)) != hipSuccess)
+  if ((e = dsh_store_grow_array(&db->d_xyz, 3 * P, 3 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_nrm, 3 * P, 3 * cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_maxd, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_desc, 2 * P, 2 * cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_bad, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_cnt, P, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_local_ids, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_ref_ids, P, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_visible, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_found, P, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_nobs, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_nodes, 3 * P, 3 * cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_bary, 3 * P, 3 * cap)) != hipSuccess)
     return e;
   db->Pcap = (int32_t)cap;
   return hipSuccess;
@@ -82,16 +85,10 @@ inline hipError_t mpdb_reserve_keyframes(dsh_mpdb* db, long long need) {
   if (need <= db->Kcap) return hipSuccess;
   const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Kcap), INT32_MAX), K = (size_t)db->K;
   hipError_t e;
-  if ((e = mpdb_grow(&db->d_kf, K, cap)) != hipSuccess || (e = mpdb_grow(&db->d_local_kf, K, cap)) != hipSuccess) return e;
+  if ((e = dsh_store_grow_array(&db->d_kf, K, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_local_kf, K, cap)) != hipSuccess) return e;
   db->Kcap = (int32_t)cap;
   return hipSuccess;
 }
-
-// the first checks of every entry point: a store that is alive and attached
-#define MPDB_ENTER(who)                              \
-  if (!db || !db->ctx) return DSH_ERR_ARG;           \
-  dsh_ctx_base* c = db->ctx;                         \
-  auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, std::string(who) + ": " + m); }
 
 // n distinct ids inside [0, count)
 inline std::string mpdb_ids_error(int n, const int32_t* ids, int32_t count, const char* what) {
@@ -103,5 +100,19 @@ inline std::string mpdb_ids_error(int n, const int32_t* ids, int32_t count, cons
     if (s[i] < 0 || s[i] >= count) return std::string(what) + " " + std::to_string(s[i]) + " outside the store";
     if (i > 0 && s[i] == s[i - 1]) return std::string(what) + " " + std::to_string(s[i]) + " repeated in the batch";
   }
+  return "";
+}
+
+// a table of N entries that are -1 or a point of the store; entry i is named open + i + close in the message
+inline std::string mpdb_table_error(const dsh_mpdb* db, int N, const int32_t* table, const char* open, const char* close) {
+  for (int i = 0; i < N; i++)
+    if (table[i] < -1 || table[i] >= db->P) return open + std::to_string(i) + close + " is neither -1 nor a point of the store";
+  return "";
+}
+
+// an observation: a point and a keyframe of the store
+inline std::string mpdb_pair_error(const dsh_mpdb* db, int32_t point, int32_t slot) {
+  if (point < 0 || point >= db->P) return "point id outside the store";
+  if (slot < 0 || slot >= db->K) return "keyframe slot outside the store";
   return "";
 }

@@ -70,3 +70,23 @@ void trk_fill_prob(TrkProb& P, const dsh_track_frame& f, int mode, float th, int
 // The part of both that the frustum test alone reads (dsh_track_close_frame): Tcw, Ow, K and the image bounds; the rest of P is zero.
 std::string trk_pose_error(const dsh_track_frame& f);
 void trk_fill_pose(TrkProb& P, const dsh_track_frame& f);
+
+// The device plan of one search over B frames with Nt key points, Qt queries and Ct grid cells in all, shared by dsh_search_by_projection_batch
+// and dsh_local_map_search (which takes its queries from the store on the device and downloads their ids too); dsh_ctx.h has the blocks.
+struct dsh_ctx_base;
+struct UpBlock;
+struct DownBlock;
+struct TrkPlan {
+  size_t B, Nt, Qt, Ct;
+  size_t o_prob, o_kp, o_km, o_kd;                               // slices of the upload block
+  size_t d_match, d_level, d_inview, d_uv, d_vcos, d_pstat;      // slices of the download block
+};
+// Lays out the frames' slices in `up` and the six output slices in `down`; the caller may add slices of its own to both before it stages.
+void trk_plan_layout(TrkPlan& pl, UpBlock& up, DownBlock& down, size_t B, size_t Nt, size_t Qt, size_t Ct);
+// Frame p into the staged upload block: its TrkProb and its key points (x y, octave | state << 8, descriptors) at P.kp_off.
+void trk_plan_pack_frame(const TrkPlan& pl, UpBlock& up, int p, const TrkProb& P, const dsh_track_frame& f);
+// Sends `up`, allocates `down` and the work arrays, enqueues the zeroing of pstat and wires b -- all of it but the six query arrays.
+int trk_plan_device(dsh_ctx_base* c, const TrkPlan& pl, UpBlock& up, DownBlock& down, TrkBufs& b);
+// After the download: the first frame with a query window over TRK_MAX_CANDIDATES (the search refuses, TRK_REFUSED says why), or -1.
+int trk_plan_refused(const TrkPlan& pl, const DownBlock& down);
+#define TRK_REFUSED "a query window holds more than 4096 candidates"
