@@ -197,13 +197,22 @@ struct CopyBlock : Arena {   // size: what the copy moves
 // Up: filled in pin_in after stage(), copied by send().  The two are apart because some calls stage here and copy into a store's own
 // arrays.  The kernels may write the device side (counters that go up as zeros).
 struct UpBlock : CopyBlock {
-  int stage(dsh_ctx_base* c) {
-    HIPCHK(c, c->pin_in.ensure(size, true));
+  // tail: bytes staged behind the block in the same page-locked buffer, at host<T>(size); they are not part of `size` and send() does
+  // not move them: the caller copies them where they belong (the Schwarp fits' start values go into the head of their output block)
+  int stage(dsh_ctx_base* c, size_t tail = 0) {
+    HIPCHK(c, c->pin_in.ensure(size + tail, true));
     h = c->pin_in.p;
     return DSH_OK;
   }
-  int send(dsh_ctx_base* c) {
+  // the device side ahead of send(): for a block whose records hold device addresses of its own slices
+  int place(dsh_ctx_base* c) {
     HIPCHK(c, c->scratch.take(size, (void**)&d));
+    return DSH_OK;
+  }
+  int send(dsh_ctx_base* c) {
+    if (!d) {
+      if (const int rc = place(c)) return rc;
+    }
     if (size > 0) HIPCHK(c, hipMemcpyAsync(d, h, size, hipMemcpyHostToDevice, c->stream));
     return DSH_OK;
   }

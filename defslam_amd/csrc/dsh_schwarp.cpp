@@ -1,10 +1,9 @@
-// C ABI of the Schwarzian warp fit (include/defslam_hip.h: dsh_schwarp_fit, dsh_schwarp_eval).
-// The trust-region loop (3 iterations in the reference, SchwarpDatabase.cc:211-222) is sequenced on the host;
-// residuals, Jacobian, normal equations, the 2N x 2N Cholesky solve and the DiffProp extraction run on the GPU.
+// C ABI of the Schwarzian warp fit (include/defslam_hip.h: dsh_schwarp_eval, dsh_schwarp_fit, _fit_batch, _fit_batch_store).
+// A fit -- the trust-region loop of the reference (3 iterations, SchwarpDatabase.cc:211-222) with its control on the device -- is one fixed
+// sequence of launches for the whole batch (nrsfm_kernels.hip: nrsfm_swp_fit_batch); the single fit is a batch of one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -13,56 +12,9 @@
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
 #include "mapping_launch.h"
+#include "schwarp_problem.h"
 
 namespace {
-
-struct Fit {
-  dsh_ctx_base* c;
-  const dsh_bbs* b;
-  int P, N, n2, m;
-  double fxs, fys, lambda;
-  DevBuf kp1, kp2, isg, x, xn, cs, g, dx, r, J, A, M, W, scal;
-  hipStream_t st;
-
-  int eval(const double* xdev, bool with_j) {
-    HIPCHK(c, nrsfm_swp_eval(b->umin, b->umax, b->nptsu, b->vmin, b->vmax, b->nptsv, P, fxs, fys, lambda, kp1.as<float>(), kp2.as<float>(), isg.as<float>(),
-                             xdev, r.as<double>(), J.as<double>(), with_j ? 1 : 0, st));
-    HIPCHK(c, nrsfm_swp_loss(2 * P, m, r.as<double>(), scal.as<double>(), st));
-    if (with_j) HIPCHK(c, nrsfm_swp_normal(2 * P, m, n2, J.as<double>(), r.as<double>(), cs.as<double>(), scal.as<double>(), A.as<double>(), g.as<double>(), st));
-    return DSH_OK;
-  }
-  int scalars(double* out8) {
-    HIPCHK(c, hipMemcpyAsync(out8, scal.p, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return DSH_OK;
-  }
-};
-
-int setup(Fit& f, dsh_ctx_base* c, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, const float* invsig, double fxs, double fys, double lambda,
-          const double* x) {
-  f.c = c; f.b = bbs; f.P = P; f.N = bbs->nptsu * bbs->nptsv; f.n2 = 2 * f.N; f.m = 2 * P + 4 * f.N;
-  f.fxs = fxs; f.fys = fys; f.lambda = lambda; f.st = c->stream;
-  c->scratch.reset();
-  HIPCHK(c, f.kp1.alloc(c, 8 * (size_t)P)); HIPCHK(c, f.kp2.alloc(c, 8 * (size_t)P)); HIPCHK(c, f.isg.alloc(c, 4 * (size_t)P));
-  HIPCHK(c, f.x.alloc(c, 8 * (size_t)f.n2)); HIPCHK(c, f.xn.alloc(c, 8 * (size_t)f.n2)); HIPCHK(c, f.cs.alloc(c, 8 * (size_t)f.n2)); HIPCHK(c, f.g.alloc(c, 8 * (size_t)f.n2));
-  HIPCHK(c, f.dx.alloc(c, 8 * (size_t)f.n2)); HIPCHK(c, f.r.alloc(c, 8 * (size_t)f.m)); HIPCHK(c, f.J.alloc(c, 8 * (size_t)f.m * f.n2));
-  HIPCHK(c, f.A.alloc(c, 8 * (size_t)f.n2 * f.n2)); {
-    const size_t np = (size_t)nrsfm_swp_solve_np(f.n2);
-    HIPCHK(c, f.M.alloc(c, 8 * np * np)); HIPCHK(c, f.W.alloc(c, 8 * np * 16));
-  }
-  HIPCHK(c, f.scal.alloc(c, 64));
-  HIPCHK(c, hipMemcpyAsync(f.kp1.p, kp1, 8 * (size_t)P, hipMemcpyHostToDevice, f.st));
-  HIPCHK(c, hipMemcpyAsync(f.kp2.p, kp2, 8 * (size_t)P, hipMemcpyHostToDevice, f.st));
-  HIPCHK(c, hipMemcpyAsync(f.isg.p, invsig, 4 * (size_t)P, hipMemcpyHostToDevice, f.st));
-  HIPCHK(c, hipMemcpyAsync(f.x.p, x, 8 * (size_t)f.n2, hipMemcpyHostToDevice, f.st));
-  std::vector<double> ones(f.n2, 1.0);
-  HIPCHK(c, hipMemcpyAsync(f.cs.p, ones.data(), 8 * (size_t)f.n2, hipMemcpyHostToDevice, f.st));
-  HIPCHK(c, hipMemsetAsync(f.scal.p, 0, 64, f.st));
-  HIPCHK(c, hipMemsetAsync(f.dx.p, 0, 8 * (size_t)f.n2, f.st));
-  HIPCHK(c, hipStreamSynchronize(f.st));
-  return DSH_OK;
-}
-
 bool args_ok(const dsh_bbs* b, int P, const float* kp1, const float* kp2, const float* invsig, const double* x) {
   return b && b->nptsu >= 4 && b->nptsv >= 4 && b->umax > b->umin && b->vmax > b->vmin && P > 0 && kp1 && kp2 && invsig && x && b->nptsu * b->nptsv <= 4096;
 }
@@ -76,14 +28,22 @@ int dsh_schwarp_eval(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, 
   if (!c) return DSH_ERR_ARG;
   if (const int rc = dsh_enter(c, "dsh_schwarp_eval")) return rc;
   if (!args_ok(bbs, P, kp1, kp2, invsig, x) || !residuals) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_eval: bad argument");
-  Fit f;
-  int rc = setup(f, c, bbs, P, kp1, kp2, invsig, fx_slot, fy_slot, lambda, x);
-  if (rc != DSH_OK) return rc;
-  HIPCHK(c, nrsfm_swp_eval(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, P, fx_slot, fy_slot, lambda, f.kp1.as<float>(), f.kp2.as<float>(),
-                           f.isg.as<float>(), f.x.as<double>(), f.r.as<double>(), f.J.as<double>(), jacobian ? 1 : 0, f.st));
-  HIPCHK(c, hipMemcpyAsync(residuals, f.r.p, 8 * (size_t)f.m, hipMemcpyDeviceToHost, f.st));
-  if (jacobian) HIPCHK(c, hipMemcpyAsync(jacobian, f.J.p, 8 * (size_t)f.m * f.n2, hipMemcpyDeviceToHost, f.st));
-  HIPCHK(c, hipStreamSynchronize(f.st));
+  const SwpSizes s = swp_sizes(bbs->nptsu, bbs->nptsv, P);
+  const size_t r_bytes = 8 * (size_t)s.m, j_bytes = r_bytes * s.n2;   // the dense (2P + 4N) x 2N Jacobian: only when it is asked for
+  hipStream_t st = c->stream;
+  DevBuf dkp1, dkp2, disg, dx, dr, dJ;
+  HIPCHK(c, dkp1.alloc(c, 8 * (size_t)P)); HIPCHK(c, dkp2.alloc(c, 8 * (size_t)P)); HIPCHK(c, disg.alloc(c, 4 * (size_t)P));
+  HIPCHK(c, dx.alloc(c, 8 * (size_t)s.n2)); HIPCHK(c, dr.alloc(c, r_bytes));
+  if (jacobian) HIPCHK(c, dJ.alloc(c, j_bytes));
+  HIPCHK(c, hipMemcpyAsync(dkp1.p, kp1, 8 * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dkp2.p, kp2, 8 * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(disg.p, invsig, 4 * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dx.p, x, 8 * (size_t)s.n2, hipMemcpyHostToDevice, st));
+  HIPCHK(c, nrsfm_swp_eval(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, P, fx_slot, fy_slot, lambda, dkp1.as<float>(), dkp2.as<float>(),
+                           disg.as<float>(), dx.as<double>(), dr.as<double>(), dJ.as<double>(), jacobian ? 1 : 0, st));
+  HIPCHK(c, hipMemcpyAsync(residuals, dr.p, r_bytes, hipMemcpyDeviceToHost, st));
+  if (jacobian) HIPCHK(c, hipMemcpyAsync(jacobian, dJ.p, j_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return DSH_OK;
 }
 
@@ -116,18 +76,22 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
   }
   hipStream_t st = c->stream;
   // ---- layout of the input block (host-staged) and of the output block
-  const size_t fit_bytes = nrsfm_swp_fit_bytes();
-  Arena in, out;
-  in.take(fit_bytes * (size_t)B);   // the fit descriptors
+  UpBlock in;
+  DownBlock out;
+  const size_t o_fits = in.take(sizeof(SwpFit) * (size_t)B);   // the fit descriptors
   int with_init = 0;
-  struct Off { size_t kp1, kp2, isg, x0, cs, xo, diff, drop, info, costs, bend; };
+  struct Off { size_t kp1, kp2, isg, cs, xo, diff, drop, info, costs, bend; };
   std::vector<Off> off(B);
+  std::vector<SwpSizes> sizes(B);
   // x lives at the head of the output block (in/out): only that part is uploaded with the start values
-  for (int b = 0; b < B; b++) off[b].xo = out.take(8 * 2 * (size_t)probs[b].bbs.nptsu * probs[b].bbs.nptsv);
+  for (int b = 0; b < B; b++) {
+    sizes[b] = swp_sizes(probs[b].bbs.nptsu, probs[b].bbs.nptsv, probs[b].P);
+    off[b].xo = out.take(8 * (size_t)sizes[b].n2);
+  }
   const size_t x_bytes = out.size;
   for (int b = 0; b < B; b++) {
     const dsh_schwarp_problem& q = probs[b];
-    const size_t n2 = 2 * (size_t)q.bbs.nptsu * q.bbs.nptsv;
+    const size_t n2 = (size_t)sizes[b].n2;
     Off& o = off[b];
     o.kp1 = in.take(8 * (size_t)q.P);
     o.kp2 = in.take(8 * (size_t)q.P);
@@ -157,78 +121,84 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     HIPCHK(c, sdiff.alloc(c, 72 * nall)); HIPCHK(c, sdrop.alloc(c, nall)); HIPCHK(c, skeep.alloc(c, 4 * nall)); HIPCHK(c, spos.alloc(c, 4 * nall));
     HIPCHK(c, stmp.alloc(c, ddb_scan_tmp_bytes((int)nall)));
   }
-  DevBuf din, dout;
-  HIPCHK(c, din.alloc(c, in.size)); HIPCHK(c, dout.alloc(c, out.size));
-  HIPCHK(c, c->pin_in.ensure(in.size + x_bytes, true)); HIPCHK(c, c->pin_out.ensure(out.size, true));
-  char* hin = c->pin_in.p;
-  char* hx = c->pin_in.p + in.size;   // start values of x, laid out like the head of the output block
+  // the descriptors hold device addresses of both blocks: both are placed before anything is filled in.  The start values of x are
+  // staged behind the input block, laid out like the head of the output block, and go up in a copy of their own
+  if (const int rc = in.place(c)) return rc;
+  if (const int rc = out.alloc(c)) return rc;
+  if (const int rc = in.stage(c, x_bytes)) return rc;
+  char* hx = in.host<char>(in.size);
   std::memset(hx, 0, x_bytes);
-  char* dib = din.as<char>();
-  char* dob = dout.as<char>();
   // what has to start at zero (scalars of the controller, the step vector) lies in one block: one memset for the whole batch
   DevBuf dzero;
   size_t zero_bytes = 0;
-  for (int b = 0; b < B; b++) zero_bytes += 128 + Arena::round(8 * 2 * (size_t)probs[b].bbs.nptsu * probs[b].bbs.nptsv);
+  for (int b = 0; b < B; b++) zero_bytes += 128 + Arena::round(8 * (size_t)sizes[b].n2);
   HIPCHK(c, dzero.alloc(c, zero_bytes));
   HIPCHK(c, hipMemsetAsync(dzero.p, 0, zero_bytes, st));
   size_t zoff = 0;
   for (int b = 0; b < B; b++) {
     const dsh_schwarp_problem& q = probs[b];
     const Off& o = off[b];
-    const int N = q.bbs.nptsu * q.bbs.nptsv, n2 = 2 * N, m = 2 * q.P + 4 * N;
-    std::memcpy(hin + o.kp1, q.kp1, 8 * (size_t)q.P); std::memcpy(hin + o.kp2, q.kp2, 8 * (size_t)q.P); std::memcpy(hin + o.isg, q.invsig, 4 * (size_t)q.P);
-    double* cs = reinterpret_cast<double*>(hin + o.cs);
-    for (int j = 0; j < n2; j++) cs[j] = 1.0;
-    if (q.init_lambda > 0.0) {
-      if (b == 0 || off[b - 1].bend != o.bend) dsh::bbs_bending_dense(&q.bbs, q.init_lambda, reinterpret_cast<double*>(hin + o.bend));
+    const SwpSizes& s = sizes[b];
+    const bool init = q.init_lambda > 0.0;
+    std::memcpy(in.host<float>(o.kp1), q.kp1, 8 * (size_t)q.P); std::memcpy(in.host<float>(o.kp2), q.kp2, 8 * (size_t)q.P);
+    std::memcpy(in.host<float>(o.isg), q.invsig, 4 * (size_t)q.P);
+    std::fill_n(in.host<double>(o.cs), s.n2, 1.0);
+    if (init) {
+      if (b == 0 || off[b - 1].bend != o.bend) dsh::bbs_bending_dense(&q.bbs, q.init_lambda, in.host<double>(o.bend));
     } else {
-      std::memcpy(hx + o.xo, q.x, 8 * (size_t)n2);
+      std::memcpy(hx + o.xo, q.x, 8 * (size_t)s.n2);
     }
-    DevBuf xn, g, r, J, A, M, W, compact;
-    double* scal = reinterpret_cast<double*>(dzero.as<char>() + zoff);
-    double* dx = reinterpret_cast<double*>(dzero.as<char>() + zoff + 128);
-    zoff += 128 + Arena::round(8 * (size_t)n2);
-    const size_t np = (size_t)nrsfm_swp_solve_np(n2);
-    HIPCHK(c, xn.alloc(c, 8 * (size_t)n2)); HIPCHK(c, g.alloc(c, 8 * (size_t)n2)); HIPCHK(c, r.alloc(c, 8 * (size_t)m));
-    // the dense (2P+4N) x 2N buffer only serves the Warp::initialize stage (its colocation matrix); the fit keeps its Jacobian structured
-    HIPCHK(c, J.alloc(c, q.init_lambda > 0.0 ? 8 * (size_t)m * n2 : 256)); HIPCHK(c, compact.alloc(c, nrsfm_swp_compact_bytes(q.P, q.bbs.nptsu, q.bbs.nptsv)));
-    HIPCHK(c, A.alloc(c, 8 * (size_t)n2 * n2)); HIPCHK(c, M.alloc(c, 8 * np * np)); HIPCHK(c, W.alloc(c, 8 * np * 16));
-    nrsfm_swp_fit_fill(hin + fit_bytes * (size_t)b, q.bbs.umin, q.bbs.umax, q.bbs.nptsu, q.bbs.vmin, q.bbs.vmax, q.bbs.nptsv, q.P, q.fx_slot, q.fy_slot, q.lambda, q.fx, q.fy,
-                       q.max_iters, reinterpret_cast<const float*>(dib + o.kp1), reinterpret_cast<const float*>(dib + o.kp2), reinterpret_cast<const float*>(dib + o.isg),
-                       reinterpret_cast<double*>(dob + o.xo), xn.as<double>(), reinterpret_cast<double*>(dib + o.cs), g.as<double>(), dx, r.as<double>(),
-                       J.as<double>(), A.as<double>(), M.as<double>(), W.as<double>(), scal,
-                       db ? sdiff.as<float>() + 18 * (size_t)b * maxP : (q.diff ? reinterpret_cast<float*>(dob + o.diff) : nullptr),
-                       db ? sdrop.as<uint8_t>() + (size_t)b * maxP : (q.drop ? reinterpret_cast<uint8_t*>(dob + o.drop) : nullptr),
-                       reinterpret_cast<int32_t*>(dob + o.info), reinterpret_cast<double*>(dob + o.costs),
-                       q.init_lambda > 0.0 ? reinterpret_cast<const double*>(dib + o.bend) : nullptr, compact.p);
+    SwpFit f{};
+    f.p = SwpPar{q.bbs.umin, q.bbs.umax, q.bbs.vmin, q.bbs.vmax, q.fx_slot, q.fy_slot, q.lambda, q.bbs.nptsu, q.bbs.nptsv, q.bbs.nptsu * q.bbs.nptsv, q.P};
+    f.fx = q.fx; f.fy = q.fy;
+    f.n2 = s.n2; f.m = s.m; f.np = s.np; f.il = s.il; f.bwt = s.bwt; f.npi = s.npi; f.bwti = s.bwti;
+    f.max_iters = q.max_iters;
+    f.kp1 = in.dev<float>(o.kp1); f.kp2 = in.dev<float>(o.kp2); f.isg = in.dev<float>(o.isg);
+    f.cs = in.dev<double>(o.cs);
+    f.bend = init ? in.dev<double>(o.bend) : nullptr;
+    f.x = out.dev<double>(o.xo);
+    f.diff = db ? sdiff.as<float>() + 18 * (size_t)b * maxP : (q.diff ? out.dev<float>(o.diff) : nullptr);
+    f.drop = db ? sdrop.as<uint8_t>() + (size_t)b * maxP : (q.drop ? out.dev<uint8_t>(o.drop) : nullptr);
+    f.info = out.dev<int32_t>(o.info);
+    f.costs = out.dev<double>(o.costs);
+    f.scal = reinterpret_cast<double*>(dzero.as<char>() + zoff);
+    f.dx = reinterpret_cast<double*>(dzero.as<char>() + zoff + 128);
+    zoff += 128 + Arena::round(8 * (size_t)s.n2);
+    // the per-fit scratch.  The dense (2P+4N) x 2N buffer only serves the Warp::initialize stage (its colocation matrix); the fit keeps
+    // its Jacobian structured
+    DevBuf compact;
+    HIPCHK(c, dsh_scratch_array(c, &f.xn, (size_t)s.n2)); HIPCHK(c, dsh_scratch_array(c, &f.g, (size_t)s.n2)); HIPCHK(c, dsh_scratch_array(c, &f.r, (size_t)s.m));
+    HIPCHK(c, dsh_scratch_array(c, &f.J, init ? (size_t)s.m * s.n2 : 32)); HIPCHK(c, compact.alloc(c, swp_compact(f, nullptr)));
+    HIPCHK(c, dsh_scratch_array(c, &f.A, (size_t)s.n2 * s.n2)); HIPCHK(c, dsh_scratch_array(c, &f.M, (size_t)s.np * s.np)); HIPCHK(c, dsh_scratch_array(c, &f.W, (size_t)s.np * 16));
+    swp_compact(f, compact.as<char>());
+    in.host<SwpFit>(o_fits)[b] = f;
   }
   int32_t max_pid = -1;
   if (db) {
-    int32_t* hp = reinterpret_cast<int32_t*>(hin + o_pid);
-    int32_t* ht = reinterpret_cast<int32_t*>(hin + o_tag);
-    int32_t* hi = reinterpret_cast<int32_t*>(hin + o_idx2);
+    int32_t* hp = in.host<int32_t>(o_pid);
+    int32_t* ht = in.host<int32_t>(o_tag);
+    int32_t* hi = in.host<int32_t>(o_idx2);
     for (int b = 0; b < B; b++)
       for (int i = 0; i < maxP; i++) {
-        const bool in = i < probs[b].P;
-        const int32_t id = in ? stores[b].point_id[i] : -1;
+        const bool in_fit = i < probs[b].P;
+        const int32_t id = in_fit ? stores[b].point_id[i] : -1;
         hp[(size_t)b * maxP + i] = id;
         ht[(size_t)b * maxP + i] = stores[b].tag;
-        hi[(size_t)b * maxP + i] = (in && stores[b].idx2) ? stores[b].idx2[i] : (in ? i : -1);
+        hi[(size_t)b * maxP + i] = (in_fit && stores[b].idx2) ? stores[b].idx2[i] : (in_fit ? i : -1);
         max_pid = std::max(max_pid, id);
       }
   }
-  HIPCHK(c, hipMemcpyAsync(dib, hin, in.size, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dob, hx, x_bytes, hipMemcpyHostToDevice, st));
-  if (out.size > x_bytes) HIPCHK(c, hipMemsetAsync(dob + x_bytes, 0, out.size - x_bytes, st));
-  HIPCHK(c, nrsfm_swp_fit_batch(dib, B, maxP, maxN, max_it, with_init, st));
-  HIPCHK(c, hipMemcpyAsync(c->pin_out.p, dob, out.size, hipMemcpyDeviceToHost, st));
+  if (const int rc = in.send(c)) return rc;
+  HIPCHK(c, hipMemcpyAsync(out.d, hx, x_bytes, hipMemcpyHostToDevice, st));
+  if (out.size > x_bytes) HIPCHK(c, hipMemsetAsync(out.d + x_bytes, 0, out.size - x_bytes, st));
+  HIPCHK(c, nrsfm_swp_fit_batch(in.dev<SwpFit>(o_fits), B, maxP, maxN, max_it, with_init, st));
+  if (const int rc = out.fetch(c)) return rc;
   std::vector<uint8_t> hdrop;
   std::vector<float> hdiff;
   int32_t added = 0;
   if (db) {   // kept records -> the database, in (fit, match) order; only the drop flags (and, if asked for, the records) travel to the host
-    HIPCHK(c, ddb_append((int)nall, sdrop.as<uint8_t>(), sdiff.as<float>(), reinterpret_cast<const int32_t*>(dib + o_pid), reinterpret_cast<const int32_t*>(dib + o_tag),
-                         reinterpret_cast<const int32_t*>(dib + o_idx2), skeep.as<int32_t>(), spos.as<int32_t>(), stmp.p, ddb_scan_tmp_bytes((int)nall), db->count,
-                         db->cap, db->rec, db->pid, db->tag, db->idx2, st));
+    HIPCHK(c, ddb_append((int)nall, sdrop.as<uint8_t>(), sdiff.as<float>(), in.dev<int32_t>(o_pid), in.dev<int32_t>(o_tag), in.dev<int32_t>(o_idx2),
+                         skeep.as<int32_t>(), spos.as<int32_t>(), stmp.p, ddb_scan_tmp_bytes((int)nall), db->count, db->cap, db->rec, db->pid, db->tag, db->idx2, st));
     hdrop.resize(nall);
     HIPCHK(c, hipMemcpyAsync(hdrop.data(), sdrop.p, nall, hipMemcpyDeviceToHost, st));
     bool want_diff = false;
@@ -246,19 +216,17 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     db->count += added;
     db->max_pid = std::max(db->max_pid, max_pid);
   }
-  const char* ho = c->pin_out.p;
   for (int b = 0; b < B; b++) {
     dsh_schwarp_problem& q = probs[b];
     const Off& o = off[b];
-    const size_t n2 = 2 * (size_t)q.bbs.nptsu * q.bbs.nptsv;
-    std::memcpy(q.x, ho + o.xo, 8 * n2);
+    std::memcpy(q.x, out.host<double>(o.xo), 8 * (size_t)sizes[b].n2);
     if (db) {
       if (q.drop) std::memcpy(q.drop, hdrop.data() + (size_t)b * maxP, (size_t)q.P);
       if (q.diff) std::memcpy(q.diff, hdiff.data() + 18 * (size_t)b * maxP, 72 * (size_t)q.P);
-    } else if (q.diff) { std::memcpy(q.diff, ho + o.diff, 72 * (size_t)q.P); std::memcpy(q.drop, ho + o.drop, (size_t)q.P); }
-    std::memcpy(q.info, ho + o.info, sizeof q.info);
-    std::memcpy(&q.init_ok, ho + o.info + sizeof q.info, sizeof q.init_ok);
-    std::memcpy(q.costs, ho + o.costs, sizeof q.costs);
+    } else if (q.diff) { std::memcpy(q.diff, out.host<float>(o.diff), 72 * (size_t)q.P); std::memcpy(q.drop, out.host<uint8_t>(o.drop), (size_t)q.P); }
+    std::memcpy(q.info, out.host<int32_t>(o.info), sizeof q.info);
+    std::memcpy(&q.init_ok, out.host<int32_t>(o.info) + 2, sizeof q.init_ok);   // info[2]: the verdict on the initialisation
+    std::memcpy(q.costs, out.host<double>(o.costs), sizeof q.costs);
   }
   return DSH_OK;
 }

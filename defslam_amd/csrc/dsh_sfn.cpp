@@ -14,6 +14,7 @@
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
 #include "mapping_launch.h"
+#include "schwarp_problem.h"
 
 namespace {
 
@@ -134,7 +135,7 @@ static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u
   double* scal = dscal.as<double>();
   for (int it = 0; it < 3; it++) {
     HIPCHK(c, nrsfm_sfn_residual(m, N, dA.as<double>(), dx.as<double>(), db.as<double>(), -1.0, dr.as<double>(), st));
-    HIPCHK(c, nrsfm_swp_normal(0, m, N, dA.as<double>(), dr.as<double>(), dones.as<double>(), scal, dG.as<double>(), dg.as<double>(), st));
+    HIPCHK(c, nrsfm_swp_normal(m, N, dA.as<double>(), dr.as<double>(), dones.as<double>(), dG.as<double>(), dg.as<double>(), st));
     if (it == 0) HIPCHK(c, nrsfm_swp_solve(N, dG.as<double>(), dg.as<double>(), 1e300, dM.as<double>(), dW.as<double>(), ddx.as<double>(), scal + 2, 0, N, st));   // dense: the mean-depth row couples every pair of control points
     else HIPCHK(c, nrsfm_swp_resolve(N, dg.as<double>(), dM.as<double>(), dW.as<double>(), ddx.as<double>(), 0, N, st));
     HIPCHK(c, nrsfm_sfn_axpy(N, ddx.as<double>(), dx.as<double>(), st));
@@ -208,8 +209,8 @@ int dsh_warp_initialize(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp
                              dr1.as<double>(), st));
   double* scal = dscal.as<double>();
   // g1 = C^T (-q2y) first (G is rebuilt by the second call), then G = C^T C, g0 = C^T (-q2x); G += Bending
-  HIPCHK(c, nrsfm_swp_normal(0, P, N, dC.as<double>(), dr1.as<double>(), dones.as<double>(), scal, dG.as<double>(), dg1.as<double>(), st));
-  HIPCHK(c, nrsfm_swp_normal(0, P, N, dC.as<double>(), dr0.as<double>(), dones.as<double>(), scal, dG.as<double>(), dg0.as<double>(), st));
+  HIPCHK(c, nrsfm_swp_normal(P, N, dC.as<double>(), dr1.as<double>(), dones.as<double>(), dG.as<double>(), dg1.as<double>(), st));
+  HIPCHK(c, nrsfm_swp_normal(P, N, dC.as<double>(), dr0.as<double>(), dones.as<double>(), dG.as<double>(), dg0.as<double>(), st));
   HIPCHK(c, nrsfm_mat_add((size_t)N * N, dB.as<double>(), dG.as<double>(), st));
   HIPCHK(c, nrsfm_swp_solve(N, dG.as<double>(), dg0.as<double>(), 1e300, dM.as<double>(), dW.as<double>(), dx.as<double>(), scal + 2, 0, 3 * bbs->nptsv + 3, st));   // colocation and bending couple a 4 x 4 patch: banded
   HIPCHK(c, nrsfm_swp_resolve(N, dg1.as<double>(), dM.as<double>(), dW.as<double>(), dx.as<double>() + N, 0, 3 * bbs->nptsv + 3, st));

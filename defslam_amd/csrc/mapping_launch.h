@@ -15,26 +15,14 @@ extern "C" hipError_t nrsfm_launch_normals(int P, int R, const int32_t* rec_ptr,
                                            double* Q, double* k1k2, double* cov, int32_t* status, float* normal_ref, float* normal_rec, uint8_t* written,
                                            int32_t* iters, hipStream_t st);
 
-// ---- nrsfm_kernels.hip: Schwarp fit (dsh_schwarp.cpp) and the dense solver it shares with Shape from Normals (dsh_sfn.cpp)
+// ---- nrsfm_kernels.hip: one Schwarp evaluation (dsh_schwarp.cpp), the dense normal equations and the one-workgroup solver that Shape from
+// Normals and the warp initialisation run on (dsh_sfn.cpp).  The batched fit and nrsfm_swp_solve_np: schwarp_problem.h.
 extern "C" hipError_t nrsfm_swp_eval(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
                                      const float* kp1, const float* kp2, const float* invsig, const double* x, double* r, double* J, int with_j, hipStream_t st);
-extern "C" hipError_t nrsfm_swp_loss(int P2, int m, const double* r, double* scal, hipStream_t st);
-extern "C" hipError_t nrsfm_swp_normal(int P2, int m, int n2, double* J, double* r, const double* cs, const double* scal, double* A, double* g, hipStream_t st);
-extern "C" hipError_t nrsfm_swp_colscale(int n2, const double* A, double* cs, hipStream_t st);
-extern "C" int nrsfm_swp_solve_np(int n2);
+extern "C" hipError_t nrsfm_swp_normal(int m, int n, const double* J, const double* r, const double* cs, double* A, double* g, hipStream_t st);
 extern "C" hipError_t nrsfm_swp_solve(int n2, const double* A, const double* g, double radius, double* M, double* Winv, double* dx, double* out, int interleave,
                                       int kd, hipStream_t st);
 extern "C" hipError_t nrsfm_swp_resolve(int n2, const double* g, const double* M, const double* Winv, double* dx, int interleave, int kd, hipStream_t st);
-extern "C" hipError_t nrsfm_swp_step(int n2, const double* x, const double* dx, const double* cs, const double* g, double* xn, double* out, hipStream_t st);
-extern "C" hipError_t nrsfm_swp_diffprop(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, const float* kp1, const float* kp2,
-                                         const double* x, float fx_true, float fy_true, float* diff, uint8_t* drop, hipStream_t st);
-extern "C" size_t nrsfm_swp_fit_bytes();
-extern "C" void nrsfm_swp_fit_fill(void* host_slot, double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
-                                   float fx, float fy, int max_iters, const float* kp1, const float* kp2, const float* isg, double* x, double* xn, double* cs,
-                                   double* g, double* dx, double* r, double* J, double* A, double* M, double* W, double* scal, float* diff, uint8_t* drop,
-                                   int32_t* info, double* costs, const double* bend, void* compact);
-extern "C" size_t nrsfm_swp_compact_bytes(int P, int nu, int nv);
-extern "C" hipError_t nrsfm_swp_fit_batch(void* d_fits_v, int B, int maxP, int maxN, int max_iters, int with_init, hipStream_t st);
 
 // ---- nrsfm_kernels.hip: Shape from Normals, warp initialisation, search by Schwarp (dsh_sfn.cpp)
 extern "C" hipError_t nrsfm_sfn_rows(double umin, double umax, int nu, double vmin, double vmax, int nv, int n, const double* u, const double* v,

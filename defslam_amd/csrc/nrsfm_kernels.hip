@@ -12,11 +12,11 @@
 // All kernels are embarrassingly parallel and bandwidth-trivial; records are stored SoA so neighbouring
 // threads read neighbouring addresses.
 #include <hip/hip_runtime.h>
-#include <cstring>
 #include "tile_chol.h"
 #include <math.h>
 #include <stdint.h>
 #include "mapping_launch.h"
+#include "schwarp_problem.h"
 
 namespace {
 
@@ -316,7 +316,6 @@ __global__ void normals_propagate_kernel(int R, const float* __restrict__ recs, 
 // Parameter layout x[0..N) first coordinate, x[N..2N) second; dense row-major Jacobian (2P+4N) x 2N.
 // ------------------------------------------------------------------------------------------------
 typedef double v2d_t __attribute__((ext_vector_type(2)));
-struct SwpPar { double umin, umax, vmin, vmax, fxs, fys, lambda; int nu, nv, N, P; };
 
 __device__ __forceinline__ void swp_eval16(const SwpPar& p, const double* x, double u, double v, int du, int dv, double& ox, double& oy) {
   BbsPar b = {p.umin, p.umax, p.vmin, p.vmax, p.nu, p.nv, 2, 0};
@@ -642,13 +641,6 @@ __device__ __forceinline__ void swp_loss_body(int P2, int m, const double* __res
     scal[0] = (rho0 + rest) * 0.5;
     scal[1] = sqrt(rho1);
   }
-}
-
-__device__ __forceinline__ void swp_scale_body(int P2, int n2, const double* __restrict__ scal, double* __restrict__ r, double* __restrict__ J) {
-  const double sc = scal[1];
-  const size_t tot = (size_t)P2 * n2;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < tot; i += (size_t)gridDim.x * blockDim.x) J[i] *= sc;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)P2; i += (size_t)gridDim.x * blockDim.x) r[i] *= sc;
 }
 
 // A = (J S)^T (J S) (lower and mirrored), g = (J S)^T r on FP64 MFMA: one wavefront per 16x16 tile of A (lower triangle),
@@ -1432,69 +1424,29 @@ __device__ __forceinline__ void swp_diffprop_body(SwpPar p, const float* __restr
   d[12] = dquu[0]; d[13] = dquu[1]; d[14] = dquv[0]; d[15] = dquv[1]; d[16] = dqvv[0]; d[17] = dqvv[1];
 }
 
-// ---- thin kernels over the bodies above (one fit per launch: dsh_schwarp_eval, Shape from Normals, warp initialisation) ----------
+// ---- thin kernels over the bodies above (one problem per launch: dsh_schwarp_eval, Shape from Normals, dsh_warp_initialize) ----------
 template <bool WITH_J>
 __global__ void swp_eval_kernel(SwpPar p, const float* __restrict__ kp1, const float* __restrict__ kp2, const float* __restrict__ invsig,
                                 const double* __restrict__ x, double* __restrict__ r, double* __restrict__ J) { swp_eval_body<WITH_J>(p, kp1, kp2, invsig, x, r, J); }
-__global__ __launch_bounds__(256) void swp_loss_kernel(int P2, int m, const double* __restrict__ r, double* __restrict__ scal) { swp_loss_body(P2, m, r, scal); }
-__global__ void swp_scale_kernel(int P2, int n2, const double* __restrict__ scal, double* __restrict__ r, double* __restrict__ J) { swp_scale_body(P2, n2, scal, r, J); }
 __global__ __launch_bounds__(256) void swp_normal_kernel(int m, int n2, int nt, const double* __restrict__ J, const double* __restrict__ r,
                                                          const double* __restrict__ cs, double* __restrict__ A, double* __restrict__ g) { swp_normal_body(m, n2, nt, J, r, cs, A, g); }
 __global__ __launch_bounds__(256) void swp_damp_kernel(int n, int np, int il, const double* __restrict__ A, double radius, double* __restrict__ M) { swp_damp_body(n, np, il, A, radius, M); }
 __global__ __launch_bounds__(512) void swp_solve_kernel(int n, int np, int il, int bwt, const double* __restrict__ A, const double* __restrict__ g, double radius,
                                                         double* __restrict__ M, double* __restrict__ Winv, double* __restrict__ dx, double* __restrict__ out) { swp_solve_body(n, np, il, bwt, A, g, radius, M, Winv, dx, out); }
-__global__ __launch_bounds__(256) void swp_step_kernel(int n, const double* __restrict__ x, const double* __restrict__ dx, const double* __restrict__ cs,
-                                                       const double* __restrict__ g, double* __restrict__ xn, double* __restrict__ out) { swp_step_body(n, x, dx, cs, g, xn, out); }
-__global__ void swp_colscale_kernel(int n, const double* __restrict__ A, double* __restrict__ cs) { swp_colscale_body(n, A, cs); }
-__global__ void swp_diffprop_kernel(SwpPar p, const float* __restrict__ kp1, const float* __restrict__ kp2, const double* __restrict__ x,
-                                    float fx_true, float fy_true, float* __restrict__ diff, uint8_t* __restrict__ drop) { swp_diffprop_body(p, kp1, kp2, x, fx_true, fy_true, diff, drop); }
 
 // ------------------------------------------------------------------------------------------------
-// Batched Schwarp fit (SchwarpDatabase::add fits one warp per anchor keyframe, SchwarpDatabase.cc:50-128): B fits advance
-// together, one launch per stage with the fit in blockIdx.y (blockIdx.z for the 2D damp grid); each kernel reads its arguments
-// from the fit's descriptor.  The trust-region control of the reference's Ceres run (dsh_schwarp.cpp restated it on the host
-// with one round trip per iteration) runs in swp_ctl_kernel on the device: the whole batch is a fixed sequence of launches
-// without a single host synchronisation, and a finished fit skips its stages by a flag.
+// Batched Schwarp fit (SchwarpDatabase::add fits one warp per anchor keyframe, SchwarpDatabase.cc:50-128): the stage kernels over the
+// fit descriptors of schwarp_problem.h (SwpFit), the Warp::initialize stage, the trust-region controller.  A single fit is a batch of one.
 // ------------------------------------------------------------------------------------------------
-struct SwpFit {
-  SwpPar p;                      // domain, grid, P, N, slots, lambda
-  float fx, fy;                  // true focal lengths (DiffProp drop test)
-  int n2, m, np, il, bwt, max_iters;
-  const float *kp1, *kp2, *isg;
-  double *x, *xn, *cs, *g, *dx, *r, *J, *A, *M, *W, *scal;   // scal: [0] cost [1] sqrt(rho') [2] solve ok [3] model change [4] |step| [5] |x| [6] max |g|
-  float* diff;
-  uint8_t* drop;
-  int32_t* info;                 // [0] iterations [1] accepted steps
-  double* costs;                 // [0] initial [1] final
-  // trust-region state (Ceres LM as restated in dsh_schwarp.cpp / oracle/schwarp_oracle.c)
-  double radius, nu, cost, cost0, change, old;
-  int it, good, invalid, done, accepted, pending;   // pending: an accepted step was re-linearised, its max |g| has not been tested yet
-  // optional first stage, Warps::Warp::initialize (Schwarp.cc:99-160): x = the regularised linear fit of the warp with this bending
-  // matrix (N x N, shared by the fits of one grid and weight; NULL: x holds the caller's start value).  It borrows the buffers of
-  // the fit: C in J, the two right-hand sides in r, C^T C + Bending in A, C^T kp2 in g, the factor in M / W.
-  const double* bend;
-  int npi, bwti;                 // padded size and band width (in tiles) of the N x N system
-  // Structured Jacobian of the fit (every row touches the 4 x 4 patch of control points of ONE knot cell -- SURVEY 7 K11): the warp rows
-  // as 16 values per match (the x row; the reference's y row is a copy of it, Schwarp.cc:291-298), the Schwarzian rows as 32 values per
-  // row (16 for each coordinate), and the rows bucketed by knot cell (matches in index order: a fixed summation order).
-  double *Jw, *Js;               // P x 16;  N x 4 x 32 (site, row, [x taps | y taps])
-  int32_t *bw_ptr, *bw_idx;      // ncell + 1, P: matches of cell (Iu, Iv) = Iu * (nv - 3) + Iv
-  int32_t *bs_ptr, *bs_idx;      // ncell + 1, N: grid sites of the cell
-  int32_t* cid;                  // P + N: knot cell of every match / grid site (-1: outside the domain)
-};
-#define SWP_STAGE_ALWAYS 0      // setup stages: run for every fit
-#define SWP_STAGE_ACTIVE 1      // stages of an iteration: skipped once the fit is done
-#define SWP_STAGE_ACCEPTED 2    // re-linearisation: only after an accepted step
-
 __device__ __forceinline__ bool swp_on(const SwpFit& f, int stage) {
   return stage == SWP_STAGE_ALWAYS || (stage == SWP_STAGE_ACTIVE && !f.done) || (stage == SWP_STAGE_ACCEPTED && f.accepted);
 }
 
-template <bool WITH_J>
+// residuals alone, at x or at the trial point xn
 __global__ void swpb_eval_kernel(const SwpFit* fits, int stage, int at_xn) {
   const SwpFit& f = fits[blockIdx.y];
   if (!swp_on(f, stage)) return;
-  swp_eval_body<WITH_J>(f.p, f.kp1, f.kp2, f.isg, at_xn ? f.xn : f.x, f.r, f.J);
+  swp_eval_body<false>(f.p, f.kp1, f.kp2, f.isg, at_xn ? f.xn : f.x, f.r, f.J);
 }
 __global__ void swpb_zero_j_kernel(const SwpFit* fits, int stage) {
   const SwpFit& f = fits[blockIdx.y];
@@ -1507,16 +1459,6 @@ __global__ __launch_bounds__(256) void swpb_loss_kernel(const SwpFit* fits, int 
   const SwpFit& f = fits[blockIdx.y];
   if (!swp_on(f, stage)) return;
   swp_loss_body(2 * f.p.P, f.m, f.r, f.scal);
-}
-__global__ void swpb_scale_kernel(const SwpFit* fits, int stage) {
-  const SwpFit& f = fits[blockIdx.y];
-  if (!swp_on(f, stage)) return;
-  swp_scale_body(2 * f.p.P, f.n2, f.scal, f.r, f.J);
-}
-__global__ __launch_bounds__(256) void swpb_normal_kernel(const SwpFit* fits, int stage, int nt) {
-  const SwpFit& f = fits[blockIdx.y];
-  if (!swp_on(f, stage)) return;
-  swp_normal_body(f.m, f.n2, nt, f.J, f.r, f.cs, f.A, f.g);
 }
 __global__ void swpb_evalc_kernel(const SwpFit* fits, int stage) {
   const SwpFit& f = fits[blockIdx.y];
@@ -1627,7 +1569,7 @@ __global__ void swpb_accept_kernel(SwpFit* fits) {
 // measures max |g|); 1: top of an iteration; 5: behind solve + step -- the gradient test of the previous accepted step (the step
 // kernel measures max |g| of the current linearisation); 2: after the trial evaluation (accept / reject, radius update);
 // 3: after the re-linearisation of an accepted step (function tolerance); 4: results.  Same decisions, in the same order, as
-// the host loop this replaces (oracle/schwarp_oracle.c is the restatement both are tested against).
+// oracle/schwarp_oracle.c, the sequential restatement of the reference's Ceres run it is tested against.
 __global__ void swpb_ctl_kernel(SwpFit* fits, int B, int phase) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -1672,7 +1614,7 @@ __global__ void swpb_ctl_kernel(SwpFit* fits, int B, int phase) {
   } else if (phase == 3) {
     if (!f.accepted) return;
     f.pending = 1;
-    if (fabs(f.change) <= ftol * f.old) f.done = 1;   // function tolerance, tested behind the re-linearisation like on the host
+    if (fabs(f.change) <= ftol * f.old) f.done = 1;   // function tolerance, tested behind the re-linearisation like in the oracle
   } else {
     if (f.info) { f.info[0] = f.it; f.info[1] = f.good; }
     if (f.costs) { f.costs[0] = f.cost0; f.costs[1] = f.cost; }
@@ -1681,7 +1623,7 @@ __global__ void swpb_ctl_kernel(SwpFit* fits, int B, int phase) {
 
 }  // namespace
 
-// ---- launchers (called from dsh_nrsfm.cpp) ---------------------------------------------------------
+// ---- launchers, declared in mapping_launch.h / schwarp_problem.h: B-spline and normals (dsh_nrsfm.cpp, dsh_diffdb.cpp) ----------
 extern "C" hipError_t nrsfm_launch_bbs_eval(double umin, double umax, int nptsu, double vmin, double vmax, int nptsv, int valdim, const double* ctrl,
                                             const double* u, const double* v, int n, int du, int dv, double* val, uint8_t* outside, hipStream_t st) {
   BbsPar p = {umin, umax, vmin, vmax, nptsu, nptsv, valdim, 0};
@@ -1717,7 +1659,7 @@ extern "C" hipError_t nrsfm_launch_normals(int P, int R, const int32_t* rec_ptr,
   return hipGetLastError();
 }
 
-// ---- Schwarp launchers ------------------------------------------------------------------------------
+// ---- Schwarp: one evaluation (dsh_schwarp.cpp), the dense normal equations and the solver (dsh_sfn.cpp), the batched fit (dsh_schwarp.cpp) ----
 extern "C" hipError_t nrsfm_swp_eval(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
                                      const float* kp1, const float* kp2, const float* invsig, const double* x, double* r, double* J, int with_j, hipStream_t st) {
   SwpPar p = {umin, umax, vmin, vmax, fxs, fys, lambda, nu, nv, nu * nv, P};
@@ -1731,22 +1673,13 @@ extern "C" hipError_t nrsfm_swp_eval(double umin, double umax, int nu, double vm
   }
   return hipGetLastError();
 }
-extern "C" hipError_t nrsfm_swp_loss(int P2, int m, const double* r, double* scal, hipStream_t st) {
-  hipLaunchKernelGGL(swp_loss_kernel, dim3(1), dim3(256), 0, st, P2, m, r, scal);
-  return hipGetLastError();
-}
-extern "C" hipError_t nrsfm_swp_normal(int P2, int m, int n2, double* J, double* r, const double* cs, const double* scal, double* A, double* g, hipStream_t st) {
-  hipLaunchKernelGGL(swp_scale_kernel, dim3(256), dim3(256), 0, st, P2, n2, scal, r, J);
-  const int nt = (n2 + 15) / 16, tiles = nt * (nt + 1) / 2;
-  hipLaunchKernelGGL(swp_normal_kernel, dim3(tiles), dim3(256), 0, st, m, n2, nt, J, r, cs, A, g);
-  return hipGetLastError();
-}
-extern "C" hipError_t nrsfm_swp_colscale(int n2, const double* A, double* cs, hipStream_t st) {
-  hipLaunchKernelGGL(swp_colscale_kernel, dim3((n2 + 127) / 128), dim3(128), 0, st, n2, A, cs);
+// A = (J S)^T (J S), g = (J S)^T r of a dense row-major m x n matrix J, S = diag(cs)
+extern "C" hipError_t nrsfm_swp_normal(int m, int n, const double* J, const double* r, const double* cs, double* A, double* g, hipStream_t st) {
+  const int nt = (n + 15) / 16, tiles = nt * (nt + 1) / 2;
+  hipLaunchKernelGGL(swp_normal_kernel, dim3(tiles), dim3(256), 0, st, m, n, nt, J, r, cs, A, g);
   return hipGetLastError();
 }
 // M: np*np doubles, Winv: np*16 doubles with np = nrsfm_swp_solve_np(n2)
-extern "C" int nrsfm_swp_solve_np(int n2) { return 16 * ((n2 + 15) / 16); }
 // interleave: two-coordinate unknown vector (first coordinates, then second ones) reordered inside the solver; kd: scalar
 // half-bandwidth of the (reordered) matrix, >= n for a dense one.
 extern "C" hipError_t nrsfm_swp_solve(int n2, const double* A, const double* g, double radius, double* M, double* Winv, double* dx, double* out, int interleave,
@@ -1763,54 +1696,9 @@ extern "C" hipError_t nrsfm_swp_solve(int n2, const double* A, const double* g, 
   hipLaunchKernelGGL(swp_solve_kernel, dim3(1), dim3(512), lds, st, n2, np, interleave, bwt, A, g, radius, M, Winv, dx, out);
   return hipGetLastError();
 }
-extern "C" hipError_t nrsfm_swp_step(int n2, const double* x, const double* dx, const double* cs, const double* g, double* xn, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(swp_step_kernel, dim3(1), dim3(256), 0, st, n2, x, dx, cs, g, xn, out);
-  return hipGetLastError();
-}
-extern "C" hipError_t nrsfm_swp_diffprop(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, const float* kp1, const float* kp2,
-                                         const double* x, float fx_true, float fy_true, float* diff, uint8_t* drop, hipStream_t st) {
-  SwpPar p = {umin, umax, vmin, vmax, 0.0, 0.0, 0.0, nu, nv, nu * nv, P};
-  hipLaunchKernelGGL(swp_diffprop_kernel, dim3((P + 127) / 128), dim3(128), 0, st, p, kp1, kp2, x, fx_true, fy_true, diff, drop);
-  return hipGetLastError();
-}
 
-// The batched Schwarp fit: a fixed sequence of launches over B fit descriptors (device array), no host synchronisation inside.
-// maxP / maxN / maxn2 / maxnp: the largest sizes in the batch (grid extents); max_iters: the largest iteration limit.
-extern "C" size_t nrsfm_swp_fit_bytes() { return sizeof(SwpFit); }
-extern "C" void nrsfm_swp_fit_fill(void* host_slot, double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
-                                   float fx, float fy, int max_iters, const float* kp1, const float* kp2, const float* isg, double* x, double* xn, double* cs,
-                                   double* g, double* dx, double* r, double* J, double* A, double* M, double* W, double* scal, float* diff, uint8_t* drop,
-                                   int32_t* info, double* costs, const double* bend, void* compact) {
-  SwpFit f{};
-  f.p = SwpPar{umin, umax, vmin, vmax, fxs, fys, lambda, nu, nv, nu * nv, P};
-  f.fx = fx; f.fy = fy;
-  f.n2 = 2 * nu * nv; f.m = 2 * P + 4 * nu * nv; f.np = nrsfm_swp_solve_np(f.n2); f.il = 1;
-  f.bwt = min(f.np / 16 - 1, (2 * (3 * nv + 3) + 1 + 15) / 16);
-  f.max_iters = max_iters;
-  f.kp1 = kp1; f.kp2 = kp2; f.isg = isg; f.x = x; f.xn = xn; f.cs = cs; f.g = g; f.dx = dx; f.r = r; f.J = J; f.A = A; f.M = M; f.W = W; f.scal = scal;
-  f.diff = diff; f.drop = drop; f.info = info; f.costs = costs;
-  f.bend = bend;
-  f.npi = nrsfm_swp_solve_np(nu * nv);
-  f.bwti = min(f.npi / 16 - 1, (3 * nv + 3 + 15) / 16);   // colocation and bending couple a 4 x 4 patch of control points
-  {   // structured Jacobian + row buckets (nrsfm_swp_compact_bytes)
-    const int N = nu * nv, ncell = (nu - 3) * (nv - 3);
-    char* cb = static_cast<char*>(compact);
-    f.Jw = reinterpret_cast<double*>(cb); cb += 8 * (size_t)P * 16;
-    f.Js = reinterpret_cast<double*>(cb); cb += 8 * (size_t)N * 128;
-    f.bw_ptr = reinterpret_cast<int32_t*>(cb); cb += 4 * (size_t)(ncell + 1);
-    f.bw_idx = reinterpret_cast<int32_t*>(cb); cb += 4 * (size_t)P;
-    f.bs_ptr = reinterpret_cast<int32_t*>(cb); cb += 4 * (size_t)(ncell + 1);
-    f.bs_idx = reinterpret_cast<int32_t*>(cb); cb += 4 * (size_t)N;
-    f.cid = reinterpret_cast<int32_t*>(cb);
-  }
-  memcpy(host_slot, &f, sizeof f);
-}
-extern "C" size_t nrsfm_swp_compact_bytes(int P, int nu, int nv) {
-  const size_t N = (size_t)nu * nv, ncell = (size_t)(nu - 3) * (nv - 3);
-  return 8 * (size_t)P * 16 + 8 * N * 128 + 4 * (ncell + 1) * 2 + 4 * (size_t)P + 4 * N + 4 * ((size_t)P + N) + 64;
-}
-extern "C" hipError_t nrsfm_swp_fit_batch(void* d_fits_v, int B, int maxP, int maxN, int max_iters, int with_init, hipStream_t st) {
-  SwpFit* fits = static_cast<SwpFit*>(d_fits_v);
+// The batched Schwarp fit (schwarp_problem.h)
+extern "C" hipError_t nrsfm_swp_fit_batch(SwpFit* fits, int B, int maxP, int maxN, int max_iters, int with_init, hipStream_t st) {
   const int maxn2 = 2 * maxN, maxnp = nrsfm_swp_solve_np(maxn2), NT = maxnp / 16;
   const size_t lds = sizeof(double) * ((size_t)max(NT * SWS_TILE, 8 * 256) + SWS_TILE + maxnp + 16);
   if (lds > 150 * 1024 || maxnp > 512) return hipErrorInvalidValue;
@@ -1819,9 +1707,7 @@ extern "C" hipError_t nrsfm_swp_fit_batch(void* d_fits_v, int B, int maxP, int m
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(wib_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  const int nt = (maxn2 + 15) / 16, tiles = nt * (nt + 1) / 2;
   const dim3 g_eval((maxP + maxN + 127) / 128, B), g_one(1, B);
-  (void)tiles;
   auto linearise = [&](int stage) {   // residuals + structured Jacobian at x, loss (the Huber weight of the warp block), normal equations by gather
     hipLaunchKernelGGL(swpb_evalc_kernel, g_eval, dim3(128), 0, st, fits, stage);
     hipLaunchKernelGGL(swpb_loss_kernel, g_one, dim3(256), 0, st, fits, stage);
@@ -1859,7 +1745,7 @@ extern "C" hipError_t nrsfm_swp_fit_batch(void* d_fits_v, int B, int maxP, int m
     hipLaunchKernelGGL(swpb_solve_kernel, g_one, dim3(512), lds, st, fits, SWP_STAGE_ACTIVE);
     hipLaunchKernelGGL(swpb_step_kernel, g_one, dim3(256), 0, st, fits, SWP_STAGE_ACTIVE);
     hipLaunchKernelGGL(swpb_ctl_kernel, g_ctl, dim3(64), 0, st, fits, B, 5);
-    hipLaunchKernelGGL(swpb_eval_kernel<false>, g_eval, dim3(128), 0, st, fits, SWP_STAGE_ACTIVE, 1);   // residuals at the trial point
+    hipLaunchKernelGGL(swpb_eval_kernel, g_eval, dim3(128), 0, st, fits, SWP_STAGE_ACTIVE, 1);   // residuals at the trial point
     hipLaunchKernelGGL(swpb_loss_kernel, g_one, dim3(256), 0, st, fits, SWP_STAGE_ACTIVE);
     hipLaunchKernelGGL(swpb_ctl_kernel, g_ctl, dim3(64), 0, st, fits, B, 2);
     hipLaunchKernelGGL(swpb_accept_kernel, dim3(2, B), dim3(256), 0, st, fits);
