@@ -126,6 +126,22 @@ class TrackCloseCountsC(C.Structure):
                                          "local_map_points", "n_moved")]
 
 
+class KfKeypointsC(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("N", C.c_int32), ("kp", c_float_p)]
+
+
+class SurfaceGridC(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("bbs", C.POINTER(BbsC)), ("depth_ctrl", c_double_p), ("Twc", c_float_p), ("xs", C.c_int32), ("ys", C.c_int32)]
+
+
+class TemplateSwitchCountsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_new", "first_id", "n_moved", "n_masked", "n_embedded", "n_points")]
+
+
+class TemplateSwitchInputC(C.Structure):
+    _fields_ = [("kfdb", C.c_void_p), ("slot", C.c_int32), ("kf", C.POINTER(KfKeypointsC)), ("surface_pts", c_float_p), ("Twc", c_float_p)]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -150,6 +166,7 @@ EXPORTED_SYMBOLS = [
     "dsh_local_map_update", "dsh_local_map_points", "dsh_local_map_search",
     "dsh_trackstate_set_embedding", "dsh_trackstate_clear_embedding", "dsh_trackstate_set_counters", "dsh_trackstate_get",
     "dsh_trackstate_seed_local_points", "dsh_trackstate_repose", "dsh_trackstate_cull", "dsh_track_close_frame",
+    "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -280,6 +297,11 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_trackstate_repose.argtypes = [vp, C.c_int, c_double_p, c_i32_p]
     L.dsh_trackstate_cull.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_u8_p]
     L.dsh_track_close_frame.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_i32_p, c_u8_p, C.c_int, c_double_p, i32, C.POINTER(TrackCloseCountsC)]
+    L.dsh_surface_vertices.argtypes = [C.POINTER(SurfaceGridC), c_double_p]
+    L.dsh_need_new_template.argtypes = [vp, i32, C.POINTER(KfKeypointsC), c_i32_p, c_u8_p]
+    L.dsh_template_switch.argtypes = [vp, C.POINTER(TemplateSwitchInputC), c_i32_p, C.POINTER(TemplateSwitchCountsC)]
+    L.dsh_point_store_get_points.argtypes = [vp, C.c_int, c_i32_p, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p]
+    L.dsh_point_store_get_embedding.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, c_double_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

@@ -118,6 +118,10 @@ struct dsh_ctx : dsh_ctx_base {
 };
 
 dsh_ctx_base* dsh_base(dsh_ctx* ctx) { return static_cast<dsh_ctx_base*>(ctx); }
+const dsh::TemplateHost* dsh_facet_template(dsh_ctx_base* c) {
+  const dsh_ctx* x = static_cast<const dsh_ctx*>(c);
+  return x && x->tmpl.valid && x->tmpl.F > 0 ? &x->tmpl : nullptr;
+}
 
 namespace {
 

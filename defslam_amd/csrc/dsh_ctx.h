@@ -97,6 +97,9 @@ struct dsh_ctx_base {
   std::vector<dsh_store*> stores;   // device-resident stores created on this context: dsh_destroy detaches them (dsh_detach_stores)
 };
 dsh_ctx_base* dsh_base(dsh_ctx* ctx);   // the opaque handle of the ABI as its base (dsh_api.cpp, where dsh_ctx is complete)
+namespace dsh { struct TemplateHost; }
+// the context's current template when it was built from facets, else null (a store call that embeds reaches it through its context)
+const dsh::TemplateHost* dsh_facet_template(dsh_ctx_base* c);
 
 // What the device-resident stores (dsh_diffdb, dsh_kfdb) share: the owning context and the device of their allocations.  A store works
 // in either order with dsh_destroy of its context: dsh_destroy detaches it (every call on it but its destroy then returns DSH_ERR_ARG),

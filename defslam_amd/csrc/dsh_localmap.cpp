@@ -82,6 +82,7 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->top_node.clear();
   db->max_node = -1;
   db->max_node_stale = false;
+  db->top_on_device = false;
   db->obs.clear();
   db->kf.clear();
   return DSH_OK;

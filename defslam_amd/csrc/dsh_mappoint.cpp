@@ -10,22 +10,8 @@
 
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
+#include "kfdb_store.h"
 #include "mappoint_problem.h"
-
-// The store: descriptor rows and camera centres on the device; what validation and the election lists need on the host.
-struct dsh_kfdb : dsh_store {
-  int32_t cap = 0, count = 0;    // keyframes
-  long long row_cap = 0, rows = 0;
-  MpuSlot* d_slots = nullptr;
-  uint4* d_rows = nullptr;       // two uint4 per descriptor row
-  struct Kf {
-    long long row_off;
-    int32_t N, levels, bad;
-    float sf[MPU_MAX_LEVELS];
-    std::vector<int8_t> octave;
-  };
-  std::vector<Kf> kf;
-};
 
 namespace {
 

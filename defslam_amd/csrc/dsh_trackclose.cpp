@@ -55,7 +55,7 @@ int dsh_trackstate_set_embedding(dsh_mpdb* db, int n, const int32_t* ids, const 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; i++) {
     int32_t& top = db->top_node[ids[i]];
-    if (top == db->max_node && nodes[3 * i + 2] < top) db->max_node_stale = true;
+    if ((db->top_on_device || top == db->max_node) && nodes[3 * i + 2] < db->max_node) db->max_node_stale = true;
     top = nodes[3 * i + 2];
     if (!db->max_node_stale) db->max_node = std::max(db->max_node, top);
   }
@@ -70,6 +70,7 @@ int dsh_trackstate_clear_embedding(dsh_mpdb* db) {
   std::fill(db->top_node.begin(), db->top_node.end(), -1);
   db->max_node = -1;
   db->max_node_stale = false;
+  db->top_on_device = false;
   return DSH_OK;
 }
 

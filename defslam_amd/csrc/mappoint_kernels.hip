@@ -14,6 +14,7 @@
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
+#include "mappoint_device.h"
 #include "mappoint_problem.h"
 
 namespace {
@@ -23,36 +24,12 @@ __device__ __forceinline__ int hamming(const uint4 a0, const uint4 a1, const uin
          __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
-// one term of UpdateNormalAndDepth's loop (MapPoint.cc:370-374): normali = mWorldPos - Owi, alpha = (float)(1.0 / cv::norm(normali));
-// cv::scaleAdd adds normali * alpha to the running sum
-__device__ __forceinline__ void normal_term(const MpuSlot& s, float x, float y, float z, float& tx, float& ty, float& tz) {
-  const float nx = x - s.Ow[0], ny = y - s.Ow[1], nz = z - s.Ow[2];
-  const double nrm = sqrt((double)nx * (double)nx + (double)ny * (double)ny + (double)nz * (double)nz);
-  const float a = (float)(1.0 / nrm);
-  tx = nx * a;
-  ty = ny * a;
-  tz = nz * a;
-}
-
 // mNormalVector = normal / n (MapPoint.cc:389) and the depth range (:379-388), written by one lane
 __device__ __forceinline__ void write_geometry(const MpuBufs& b, const MpuPoint& pt, int p, float sx, float sy, float sz) {
-  float* nv = b.normal + 3 * (size_t)p;
-  if (pt.M > 1) {
-    const float a = (float)(1.0 / (double)pt.M);   // Mat::convertTo(scale 1.0 / n): cvt_32f's src * a + b with b = 0
-    nv[0] = sx * a + 0.0f;
-    nv[1] = sy * a + 0.0f;
-    nv[2] = sz * a + 0.0f;
-  } else {   // n == 1: cv::add(normal, Scalar(0))
-    nv[0] = sx + 0.0f;
-    nv[1] = sy + 0.0f;
-    nv[2] = sz + 0.0f;
-  }
-  const MpuSlot r = b.slots[pt.ref_slot];
-  const float px = pt.x - r.Ow[0], py = pt.y - r.Ow[1], pz = pt.z - r.Ow[2];
-  const float dist = (float)sqrt((double)px * (double)px + (double)py * (double)py + (double)pz * (double)pz);
-  const float mx = dist * pt.sf_level;
+  float mx, mn;
+  mp_geometry(pt.M, sx, sy, sz, b.slots[pt.ref_slot], pt.x, pt.y, pt.z, pt.sf_level, pt.sf_last, b.normal + 3 * (size_t)p, mx, mn);
   b.dist[2 * (size_t)p] = mx;
-  b.dist[2 * (size_t)p + 1] = mx / pt.sf_last;
+  b.dist[2 * (size_t)p + 1] = mn;
 }
 
 // W lanes per point; a block of 256 threads serves 256 / W points of one width class

@@ -1,5 +1,5 @@
-// The map point store dsh_mpdb as its two translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*) and dsh_trackclose.cpp
-// (dsh_trackstate_*, dsh_track_close_frame).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
+// The map point store dsh_mpdb as its translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*), dsh_trackclose.cpp
+// (dsh_trackstate_*, dsh_track_close_frame) and dsh_tmplswitch.cpp (dsh_need_new_template, dsh_template_switch and the read-backs).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "localmap_problem.h"
+#include "tmplswitch_problem.h"
 #include "trackclose_problem.h"
 
 struct dsh_mpdb : dsh_store {
@@ -38,11 +39,22 @@ struct dsh_mpdb : dsh_store {
   std::vector<int32_t> top_node;       // per point its largest node index, -1 without a facet
   int32_t max_node = -1;               // the largest of top_node, unless max_node_stale
   bool max_node_stale = false;
+  bool top_on_device = false;          // a template switch wrote facets on the device: top_node does not know them, max_node does
 
+  // INT32_MAX, which refuses every template, when the device cannot be asked
   int32_t largest_node() {
     if (max_node_stale) {
       max_node = -1;
-      for (const int32_t v : top_node) max_node = std::max(max_node, v);
+      if (top_on_device) {
+        int32_t* d = nullptr;
+        if (hipSetDevice(device) != hipSuccess || ctx->scratch.take(4, (void**)&d) != hipSuccess ||
+            hipMemcpyAsync(d, &max_node, 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            ts_max_node_launch(d_nodes, P, d, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(&max_node, d, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+          return INT32_MAX;
+      } else {
+        for (const int32_t v : top_node) max_node = std::max(max_node, v);
+      }
       max_node_stale = false;
     }
     return max_node;

@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <float.h>
 #include "mapping_launch.h"
+#include "tmplswitch_problem.h"
 
 namespace {
 
@@ -61,14 +62,10 @@ __device__ bool point_in_triangle(const float* q, const float* v0, const float* 
   return (0 <= alpha) && (alpha <= 1) && (0 <= beta) && (beta <= 1) && (0 <= gamma) && (gamma <= 1);
 }
 
-__global__ __launch_bounds__(256) void embed_kernel(int P, const float* __restrict__ pts, int n, const double* __restrict__ xyz0,
-                                                    const int32_t* __restrict__ facets, const int32_t* __restrict__ nf_ptr,
-                                                    const int32_t* __restrict__ nf_idx, int32_t* __restrict__ facet_id,
-                                                    int32_t* __restrict__ nodes, float* __restrict__ bary) {
+// the embedding of one point by its wavefront: every lane returns the facet (-1: none), its nodes and the barycentrics
+__device__ __forceinline__ int embed_point(const float* mp, int n, const double* __restrict__ xyz0, const int32_t* __restrict__ facets,
+                                           const int32_t* __restrict__ nf_ptr, const int32_t* __restrict__ nf_idx, int* nd, float* bb) {
   const int lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= P) return;
-  const float mp[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
   // closest node: first index of the minimum distance below 100 (TriangularMesh.cc:152-163)
   double best = 100;
   int closest = -1;
@@ -83,8 +80,9 @@ __global__ __launch_bounds__(256) void embed_kernel(int P, const float* __restri
     const int oc = __shfl_xor(closest, m, 64);
     if (oc >= 0 && (closest < 0 || ob < best || (ob == best && oc < closest))) { best = ob; closest = oc; }
   }
-  int fid = -1, nd[3] = {-1, -1, -1};
-  float bb[3] = {0.f, 0.f, 0.f};
+  int fid = -1;
+  nd[0] = nd[1] = nd[2] = -1;
+  bb[0] = bb[1] = bb[2] = 0.f;
   if (closest >= 0) {
     const int q0 = nf_ptr[closest], q1 = nf_ptr[closest + 1];
     for (int base = q0; base < q1 && fid < 0; base += 64) {
@@ -112,11 +110,54 @@ __global__ __launch_bounds__(256) void embed_kernel(int P, const float* __restri
       }
     }
   }
+  return fid;
+}
+
+__global__ __launch_bounds__(256) void embed_kernel(int P, const float* __restrict__ pts, int n, const double* __restrict__ xyz0,
+                                                    const int32_t* __restrict__ facets, const int32_t* __restrict__ nf_ptr,
+                                                    const int32_t* __restrict__ nf_idx, int32_t* __restrict__ facet_id,
+                                                    int32_t* __restrict__ nodes, float* __restrict__ bary) {
+  const int lane = threadIdx.x & 63;
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= P) return;
+  const float mp[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+  int nd[3];
+  float bb[3];
+  const int fid = embed_point(mp, n, xyz0, facets, nf_ptr, nf_idx, nd, bb);
   if (lane == 0) {
     facet_id[p] = fid;
 #pragma unroll
     for (int k = 0; k < 3; k++) { nodes[3 * p + k] = nd[k]; bary[3 * p + k] = bb[k]; }
   }
+}
+
+// DefMap::clearTemplate and the embedding half of TriangularMesh::TriangularMesh (TriangularMesh.cc:86-89: calculateFeaturesCoordinates,
+// Repose) on the map point store: one wavefront per point of the store, the points a template switch created in the launches before
+// included (their number is read from the device).  A bad point only loses its facet: Map::GetAllMapPoints does not hold it.  Every other
+// point is embedded from its position in the store; with a facet it gets SetFacet / SetCoordinates (the float32 barycentrics widened) and
+// DefMapPoint::RecalculatePosition on the rest positions, the expression of the store's repose (trackclose_kernels.hip).
+__global__ __launch_bounds__(256) void embed_store_kernel(TcState s, int P, TsTemplate t, TsCounts* counts) {
+  const int lane = threadIdx.x & 63;
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= P + counts->c.n_new) return;
+  const size_t o = 3 * (size_t)p;
+  int nd[3] = {-1, -1, -1};
+  float bb[3] = {0.f, 0.f, 0.f};
+  int fid = -1;
+  if (!s.bad[p]) {
+    const float mp[3] = {s.xyz[o], s.xyz[o + 1], s.xyz[o + 2]};
+    fid = embed_point(mp, t.n, t.xyz0, t.facets, t.nf_ptr, t.nf_idx, nd, bb);
+  }
+  if (lane != 0) return;
+  const double b0 = (double)bb[0], b1 = (double)bb[1], b2 = (double)bb[2];
+  s.nodes[o] = nd[0]; s.nodes[o + 1] = nd[1]; s.nodes[o + 2] = nd[2];
+  s.bary[o] = b0; s.bary[o + 1] = b1; s.bary[o + 2] = b2;
+  if (fid < 0) return;
+  for (int k = 0; k < 3; k++)
+    s.xyz[o + k] = (float)__dadd_rn(__dadd_rn(__dmul_rn(b0, t.xyz0[3 * (size_t)nd[0] + k]), __dmul_rn(b1, t.xyz0[3 * (size_t)nd[1] + k])),
+                                    __dmul_rn(b2, t.xyz0[3 * (size_t)nd[2] + k]));
+  atomicAdd(&counts->c.n_embedded, 1);
+  atomicMax(&counts->max_node, nd[2]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -602,6 +643,12 @@ __global__ __launch_bounds__(256) void horn_lm_kernel(int n, const float* __rest
 extern "C" hipError_t reg_embed(int P, const float* pts, int n, const double* xyz0, const int32_t* facets, const int32_t* nf_ptr, const int32_t* nf_idx,
                                 int32_t* facet_id, int32_t* nodes, float* bary, hipStream_t st) {
   if (P > 0) hipLaunchKernelGGL(embed_kernel, dim3((P + 3) / 4), dim3(256), 0, st, P, pts, n, xyz0, facets, nf_ptr, nf_idx, facet_id, nodes, bary);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t reg_embed_store(const TcState& s, int P, int max_new, const TsTemplate& t, TsCounts* counts, hipStream_t st) {
+  const long long top = (long long)P + max_new;
+  if (top > 0) hipLaunchKernelGGL(embed_store_kernel, dim3((unsigned)((top + 3) / 4)), dim3(256), 0, st, s, P, t, counts);
   return hipGetLastError();
 }
 

@@ -4,7 +4,9 @@
     DefTracking::UpdateLocalPoints (Modules/Tracking/DefTracking.cc:426-454);
   * Tracking::SearchLocalPoints (Tracking.cc:1405-1470) with the resident local points as queries;
   * the back half of DefTracking::TrackLocalMap (DefTracking.cc:253-339) on the store's per-point tracking state (dsh_trackstate_*,
-    dsh_track_close_frame): the position write-back of DefPoseOptimization, the counting loops, LocalMapping::MapPointCulling.
+    dsh_track_close_frame): the position write-back of DefPoseOptimization, the counting loops, LocalMapping::MapPointCulling;
+  * DefLocalMapping::updateTemplate and needNewTemplate (Modules/Mapping/DefLocalMapping.cc:138-153, :355-404) on the store
+    (dsh_template_switch, dsh_need_new_template): the occupancy mask, the new map points, the embedding in the new template.
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -69,6 +71,41 @@ class CloseCounts:
     outliers: int                       # mO  }
     local_map_points: int               # numberLocalMapPoints
     n_moved: int                        # points the repose moved
+
+
+@dataclass
+class StoredPoints:
+    """What dsh_point_store_get_points returns, per id asked for."""
+    xyz: np.ndarray                     # (n,3) float32 mWorldPos
+    normal: np.ndarray                  # (n,3) float32 mNormalVector
+    max_distance: np.ndarray            # (n,) float32 mfMaxDistance
+    desc: np.ndarray                    # (n,32) uint8 mDescriptor
+    bad: np.ndarray                     # (n,) bool
+
+
+@dataclass
+class KeyFramePoints:
+    """What the occupancy mask reads of a keyframe (dsh_kf_keypoints)."""
+    rows: int                           # imGray.rows
+    cols: int                           # imGray.cols
+    kp: np.ndarray                      # (N,2) float32 mvKeysUn[i].pt
+
+    def c(self, keep: list) -> _lib.KfKeypointsC:
+        kp = np.ascontiguousarray(self.kp, np.float32).reshape(-1, 2)
+        keep.append(kp)
+        return _lib.KfKeypointsC(int(self.rows), int(self.cols), int(kp.shape[0]), _ptr(kp, C.c_float))
+
+
+@dataclass
+class TemplateSwitch:
+    """What dsh_template_switch returns (DefLocalMapping::updateTemplate on the store)."""
+    n_new: int                          # points created: ids first_id .. first_id + n_new - 1
+    first_id: int
+    n_moved: int                        # key points that hold a point that is not bad
+    n_masked: int                       # empty key points inside the occupancy mask
+    n_embedded: int                     # points with a facet afterwards
+    n_points: int                       # the store's size afterwards
+    new_idx: np.ndarray                 # (n_new,) the key point of each new point
 
 
 # dsh_trackstate_cull: what became of an entry of mlpRecentAddedMapPoints
@@ -258,3 +295,48 @@ class MapPointStore:
         self._call("dsh_track_close_frame", C.byref(f), fp.shape[0], _ptr(fp, C.c_int32), _ptr(out, C.c_uint8), 0 if x is None else x.shape[0],
                    _ptr(x, C.c_double), 1 if only_tracking else 0, C.byref(cc))
         return CloseCounts(**{n: int(getattr(cc, n)) for n, _ in _lib.TrackCloseCountsC._fields_})
+
+    # ---- the template switch ----
+    def get_points(self, ids=None) -> StoredPoints:
+        """Position, normal, max distance, descriptor and bad flag of ids (None: every point of the store)."""
+        ids = np.arange(self.n_points, dtype=np.int32) if ids is None else _i32(ids)
+        n = ids.shape[0]
+        m = max(n, 1)
+        x, nr, md = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32), np.zeros(m, np.float32)
+        d, b = np.zeros((m, 32), np.uint8), np.zeros(m, np.uint8)
+        self._call("dsh_point_store_get_points", n, _ptr(ids, C.c_int32), _ptr(x, C.c_float), _ptr(nr, C.c_float), _ptr(md, C.c_float), _ptr(d, C.c_uint8),
+                   _ptr(b, C.c_uint8))
+        return StoredPoints(xyz=x[:n], normal=nr[:n], max_distance=md[:n], desc=d[:n], bad=b[:n].astype(bool))
+
+    def get_embedding(self, ids=None):
+        """(nodes (n,3) int32, bary (n,3) float64) of ids (None: every point of the store); nodes -1 -1 -1: no facet."""
+        ids = np.arange(self.n_points, dtype=np.int32) if ids is None else _i32(ids)
+        n = ids.shape[0]
+        m = max(n, 1)
+        nd, b = np.full((m, 3), -1, np.int32), np.zeros((m, 3), np.float64)
+        self._call("dsh_point_store_get_embedding", n, _ptr(ids, C.c_int32), _ptr(nd, C.c_int32), _ptr(b, C.c_double))
+        return nd[:n], b[:n]
+
+    def need_new_template(self, slot: int, kf: KeyFramePoints):
+        """DefLocalMapping::needNewTemplate on keyframe `slot`: (newPoints, candidate (N,) bool); the caller compares the count with
+        pointsToTemplate_."""
+        keep = []
+        k = kf.c(keep)
+        cand = np.zeros(max(k.N, 1), np.uint8)
+        n = C.c_int32(0)
+        self._call("dsh_need_new_template", int(slot), C.byref(k), C.byref(n), _ptr(cand, C.c_uint8))
+        return int(n.value), cand[:k.N].astype(bool)
+
+    def switch_template(self, kf_store, slot: int, kf: KeyFramePoints, surface_pts, Twc) -> TemplateSwitch:
+        """DefLocalMapping::updateTemplate for the reference keyframe `slot` (the same slot in kf_store, a mappoint.KeyFrameStore): the
+        context's template must have been built just before (sft.surface_vertices, Context.template_build).  surface_pts (N,3) float32 is
+        Surface::get3DSurfacePoint per key point, Twc (4,4) float32 the keyframe's GetPoseInverse()."""
+        keep = []
+        k = kf.c(keep)
+        sp = np.ascontiguousarray(surface_pts, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(Twc, np.float32).reshape(16)
+        inp = _lib.TemplateSwitchInputC(kf_store._h if kf_store is not None else None, int(slot), C.pointer(k), _ptr(sp, C.c_float), _ptr(T, C.c_float))
+        idx = np.zeros(max(k.N, 1), np.int32)
+        cc = _lib.TemplateSwitchCountsC()
+        self._call("dsh_template_switch", C.byref(inp), _ptr(idx, C.c_int32), C.byref(cc))
+        return TemplateSwitch(new_idx=idx[:cc.n_new].copy(), **{n: int(getattr(cc, n)) for n, _ in _lib.TemplateSwitchCountsC._fields_})

@@ -355,3 +355,16 @@ def searchBySchwarp(ctx: Context, bbs: Bbs, x, kp1, desc1, cam2, bounds2, kp2, d
                                             float(radius), int(th_low), _ptr(match, C.c_int32), C.byref(nm)), "dsh_search_by_schwarp")
     assert nm.value == int((match >= 0).sum())
     return match
+
+
+def surface_vertices(ctx: Context, bbs: Bbs, depth_ctrl: np.ndarray, Twc: np.ndarray, xs: int, ys: int) -> np.ndarray:
+    """Surface::getVertex (Modules/Mapping/Surface.cc:125-161) and the world positions TriangularMesh::TriangularMesh hands to its nodes
+    (Modules/Template/TriangularMesh.cc:71-84): (xs * ys, 3) float64, site (x, j) at index x * ys + j.  depth_ctrl is the keyframe's depth
+    spline (valdim 1), Twc (4,4) float32 its GetPoseInverse().  The triangulation stays with the caller (synth.regular_triangulation)."""
+    ctrl = np.ascontiguousarray(depth_ctrl, np.float64).reshape(-1)
+    T = np.ascontiguousarray(Twc, np.float32).reshape(16)
+    b = bbs.c()
+    out = np.zeros((max(int(xs) * int(ys), 1), 3))
+    g = _lib.SurfaceGridC(ctx._h, C.pointer(b), _ptr(ctrl, C.c_double), _ptr(T, C.c_float), int(xs), int(ys))
+    ctx._check(ctx._L.dsh_surface_vertices(C.byref(g), _ptr(out, C.c_double)), "dsh_surface_vertices")
+    return out[:int(xs) * int(ys)]

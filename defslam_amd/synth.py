@@ -881,3 +881,107 @@ def write_track_close_scene(sc, prev_points, path):
         f.write(f"{fl(a['Tcw'].ravel())}\n{fl(a['Ow'])}\n")
         for j in range(sc["final_points"].shape[0]):
             f.write(f"{int(prev_points[j])} {int(sc['final_points'][j])} {int(sc['outlier'][j])}\n")
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The template switch (MapPointStore.switch_template / need_new_template): a track-close scene whose map gets a reference keyframe
+# with key points on a small image, a depth spline, surface points and the keyframe store's side of every keyframe.
+# ---------------------------------------------------------------------------------------------------------
+def switch_depth(u, v, seed: int = 0):
+    """The smooth depth the template switch scenes put under their reference keyframe, over normalised image coordinates."""
+    return 1.0 + 0.08 * np.sin(2.5 * np.asarray(u, np.float64) + 0.3 * seed) * np.cos(2.0 * np.asarray(v, np.float64))
+
+
+def make_template_switch_scene(seed: int = 0, rows: int = 120, cols: int = 160, n_kp: int = 300, held_frac: float = 0.4, n_kf: int = 3,
+                               ref_slot: int = -2, ctrl=(13, 15), levels: int = 8, half: bool = False, **local_map):
+    """make_track_close_scene(seed, n_kf, n_kp, ...) (its keys are kept; the table of the reference keyframe, the observations and one bad
+    flag differ, see below) plus what DefLocalMapping::updateTemplate reads of the reference keyframe ref_slot (negative: from the end):
+      rows, cols, kp (n_kp,2) float32          its image size and undistorted key points.  About held_frac of the key points keep their point
+                                               (the others are emptied and lose their observation); one held point is bad.  Half of the empty
+                                               key points sit inside the box window of a held one (random key points mask very little at
+                                               this size), the others are spread over the image; a few key points lie on the image border.
+                                               half=True keeps the held key points in the left half of the image (an exploring camera)
+      camera                                   fx, fy, cx, cy of that image; the B-spline domain is narrower than the image, so key points
+                                               near the left and right border lie beside the mesh and embed in no facet
+      bbs (umin, umax, nptsu, vmin, vmax, nptsv, 1), depth_ctrl (nptsu * nptsv,)   the keyframe's depth spline (switch_depth at the control sites)
+      surface_pts (n_kp,3) float32             Surface::get3DSurfacePoint per key point: (u d, v d, d) with d = switch_depth
+      Twc (4,4) float32                        GetPoseInverse() of the reference keyframe
+      kf_Ow (K,3), kf_desc (K,n_kp,32), kf_octave (K,n_kp), scale_factors (levels,)   the keyframe store's side of every keyframe"""
+    from . import track
+    sc = dict(make_track_close_scene(seed, n_kf=n_kf, n_kp=n_kp, **local_map))
+    rng = np.random.default_rng(11000 + seed)
+    K = sc["tables"].shape[0]
+    r = ref_slot % K
+    tables = sc["tables"].copy()
+    bad = sc["bad"].copy()
+    sc["kf_bad"] = sc["kf_bad"].copy()
+    sc["kf_bad"][r] = False                                        # referenceKF_ is a keyframe of the map: never a bad one
+    held = np.nonzero(tables[r] >= 0)[0]
+    want = max(4, int(held_frac * n_kp))
+    if held.shape[0] > want:                                       # empty the others; their points no longer observe the keyframe
+        drop = rng.choice(held, held.shape[0] - want, replace=False)
+        gone = np.isin(sc["obs_point"], tables[r, drop]) & (sc["obs_kf"] == r)
+        sc["obs_point"], sc["obs_kf"] = sc["obs_point"][~gone], sc["obs_kf"][~gone]
+        tables[r, drop] = -1
+    held = np.nonzero(tables[r] >= 0)[0]
+    empty = np.nonzero(tables[r] < 0)[0]
+    bad[tables[r, held[:-1]]] = False                              # exactly one held bad point
+    bad[tables[r, held[-1]]] = True
+    good = held[:-1]
+    k = cols // 20
+    a = k // 2
+    kp = np.stack([rng.uniform(0, cols - 1e-3, n_kp), rng.uniform(0, rows - 1e-3, n_kp)], 1)
+    if half:
+        kp[held, 0] = rng.uniform(0, cols / 2, held.shape[0])
+    near = empty[: empty.shape[0] // 2]                             # inside the window of a held key point: px - (k-1-a) .. px + a
+    src = rng.choice(good, near.shape[0])
+    kp[near, 0] = np.clip(np.floor(kp[src, 0]) + rng.integers(-(k - 1 - a), a + 1, near.shape[0]) + rng.uniform(0, 0.99, near.shape[0]), 0, cols - 1e-3)
+    kp[near, 1] = np.clip(np.floor(kp[src, 1]) + rng.integers(-(k - 1 - a), a + 1, near.shape[0]) + rng.uniform(0, 0.99, near.shape[0]), 0, rows - 1e-3)
+    border = np.concatenate([good[:4], empty[-4:]])                # held and empty key points in the first and last column and row
+    kp[border[0::4], 0] = 0.25
+    kp[border[1::4], 0] = cols - 0.5
+    kp[border[2::4], 1] = 0.75
+    kp[border[3::4], 1] = rows - 0.25
+    kp = kp.astype(np.float32)
+    fx = fy = 0.625 * cols
+    cx, cy = cols / 2.0, rows / 2.0
+    u, v = (kp[:, 0].astype(np.float64) - cx) / fx, (kp[:, 1].astype(np.float64) - cy) / fy
+    d = switch_depth(u, v, seed)
+    surface_pts = np.stack([u * d, v * d, d], 1).astype(np.float32)
+    umax, vmax = 0.875 * (cols - cx) / fx, 1.05 * (rows - cy) / fy
+    nu, nv = ctrl
+    su = -umax + (np.arange(nu) - 1) * (2 * umax / (nu - 3))       # the sites of a uniform cubic B-spline's control points
+    sv = -vmax + (np.arange(nv) - 1) * (2 * vmax / (nv - 3))
+    depth_ctrl = switch_depth(su[:, None], sv[None, :], seed).reshape(-1)
+    Twc = np.eye(4)
+    Twc[:3, :3] = _rodrigues(rng.normal(size=3) * 0.02)
+    Twc[:3, 3] = rng.uniform(-0.03, 0.03, 3)
+    Twc = Twc.astype(np.float32)
+    sf, _ = track.orb_pyramid(levels)
+    kf_Ow = rng.uniform(-0.05, 0.05, (K, 3)).astype(np.float32)
+    kf_Ow[r] = Twc[:3, 3]
+    sc.update(tables=tables, bad=bad, ref_slot=int(r), rows=int(rows), cols=int(cols), kp=kp, camera=(fx, fy, cx, cy),
+              bbs=(-umax, umax, int(nu), -vmax, vmax, int(nv), 1), depth_ctrl=depth_ctrl, surface_pts=surface_pts, Twc=Twc, kf_Ow=kf_Ow,
+              kf_desc=rng.integers(0, 256, (K, n_kp, 32), dtype=np.uint8), kf_octave=rng.integers(0, levels, (K, n_kp)).astype(np.int32),
+              scale_factors=sf)
+    return sc
+
+
+def write_template_switch_scene(sc, grid, path):
+    """What integration/tmplswitch_shim_test_main.cc reads beside the write_local_map_scene file of the same scene: the reference keyframe,
+    its image size and the template grid, Twc, the depth spline, the pyramid, per keyframe the camera centre and per key point the octave
+    and the descriptor row, and per key point of the reference keyframe the position and the surface point."""
+    fl = lambda vs: " ".join(repr(float(v)) for v in vs)
+    K, n_kp = sc["tables"].shape
+    r = sc["ref_slot"]
+    with open(path, "w") as f:
+        f.write(f"{r} {sc['rows']} {sc['cols']} {grid[0]} {grid[1]}\n{fl(sc['Twc'].ravel())}\n")
+        b = sc["bbs"]
+        f.write(f"{b[0]!r} {b[1]!r} {b[2]} {b[3]!r} {b[4]!r} {b[5]} {b[6]}\n{fl(sc['depth_ctrl'])}\n")
+        f.write(f"{sc['scale_factors'].shape[0]}\n{fl(sc['scale_factors'])}\n")
+        for k in range(K):
+            f.write(f"{fl(sc['kf_Ow'][k])}\n")
+            for j in range(n_kp):
+                f.write(f"{int(sc['kf_octave'][k, j])} {' '.join(str(int(v)) for v in sc['kf_desc'][k, j])}\n")
+        for j in range(n_kp):
+            f.write(f"{fl(sc['kp'][j])} {fl(sc['surface_pts'][j])}\n")

@@ -713,6 +713,111 @@ typedef struct dsh_track_close_counts {
 int dsh_track_close_frame(dsh_mpdb* db, const dsh_track_frame* frame, int N, const int32_t* frame_points, const uint8_t* outlier,
                           int n_nodes, const double* node_xyz, int32_t only_tracking, dsh_track_close_counts* out);
 
+/* ---- mapping meets tracking: the template switch on the resident map point store -----------------------------------------------
+ * DefLocalMapping::updateTemplate (Modules/Mapping/DefLocalMapping.cc:138-153), which DefTracking::Track calls on the tracking thread
+ * (Modules/Tracking/DefTracking.cc:109) in front of the frame's two pose optimisations, and the mapping thread's trigger
+ * DefLocalMapping::needNewTemplate (:355-404), on dsh_mpdb and dsh_kfdb:
+ *   DefMap::clearTemplate                  Modules/Common/DefMap.cc:67-82
+ *   DefLocalMapping::CreateNewMapPoints    DefLocalMapping.cc:240-347
+ *   DefMap::createTemplate                 TriangularMesh::TriangularMesh (Modules/Template/TriangularMesh.cc:57-89): Surface::getVertex
+ *                                          (Modules/Mapping/Surface.cc:125-161), calculateFeaturesCoordinates, Repose
+ * Discipline of the other store calls: arguments are checked on the host before any device work, DSH_ERR_ARG comes with a message that
+ * names the entry and nothing is stored; a host-only context then answers DSH_ERR_NO_DEVICE; a detached store answers DSH_ERR_ARG.  No
+ * CPU fallback.  The two entries that need more than the store take a descriptor that names the context or the keyframe store, the
+ * way dsh_mpdb_create does.
+ *
+ * THE OCCUPANCY MASK (needNewTemplate :359-383, CreateNewMapPoints :245-271), restated in integers.  This is a reading of OpenCV's
+ * documented filter2D / threshold semantics; no OpenCV build was available to check against, as for the other OpenCV restatements.
+ *   held pixels   key point i of the keyframe's table marks pixel ((int)kp.y, (int)kp.x) -- the conversion truncates toward zero -- when
+ *                 its table entry is a point that is not bad; several key points may share a pixel
+ *   kernel        k = cols / 20 (integer division), a k x k box of ones, anchor a = k / 2: the window of pixel x is x - a .. x + k - 1 - a
+ *                 in each axis (asymmetric for even k)
+ *   border        BORDER_REFLECT_101: a source index p < 0 reads -p, p >= n reads 2 (n - 1) - p
+ *   result        the 8-bit sum saturates and the threshold > 1 keeps every pixel whose window saw a held pixel (255 each): mask(y, x) != 0
+ *                 exactly when at least one held pixel lies in the reflected window.  Nothing else of OpenCV's arithmetic survives
+ * The device does not build the image: with lo = x - a, hi = x + k - 1 - a, L = max(lo, 0), H = min(hi, cols - 1), then H = max(H, -lo)
+ * when lo < 0 and L = min(L, 2 (cols - 1) - hi) when hi > cols - 1, pixel x is masked by a held column px iff L <= px <= H, and alike
+ * for the rows (tests/test_template_switch_cpu.py holds the two forms against each other).
+ * Refused with DSH_ERR_ARG, because the reference's behaviour is undefined there: cols < 40 (k < 2); k >= rows or k >= cols; a key point
+ * whose pixel lies outside [0, cols) x [0, rows) (the reference writes outside the cv::Mat; the message names the key point); kf->N
+ * different from the N the keyframe has in the store. */
+typedef struct dsh_kf_keypoints {   /* what the mask reads of a keyframe */
+  int32_t rows, cols;               /* imGray.rows, imGray.cols */
+  int32_t N;                        /* == the N the keyframe has in the store */
+  const float* kp;                  /* N x 2: mvKeysUn[i].pt.x, .pt.y */
+} dsh_kf_keypoints;
+
+/* Surface::getVertex with xs, ys >= 2 (the reference divides by xs - 1) and the positions TriangularMesh.cc:71-84 hands to the Node
+ * constructor: nodes_xyz[xs * ys x 3] in world coordinates, site (x, j) at index x * ys + j.  In double as written at Surface.cc:140-143:
+ * u = ((umax - umin - 2 t) * x) / (xs - 1) + (umin + t) with t = 0.03, v alike from j and ys; d = the B-spline depth_ctrl (valdim 1) at
+ * (u, v), by the kernel of dsh_bbs_eval; the camera point is (float)(u d), (float)(v d), (float)d, 1; the world point is Twc times it
+ * in float32 (the product of dsh_template_switch, below), widened to double.  The triangulation stays with the caller.  Two launches. */
+typedef struct dsh_surface_grid {
+  dsh_ctx* ctx;
+  const dsh_bbs* bbs;               /* valdim 1 */
+  const double* depth_ctrl;         /* nptsu * nptsv */
+  const float* Twc;                 /* 16, row major */
+  int32_t xs, ys;
+} dsh_surface_grid;
+int dsh_surface_vertices(const dsh_surface_grid* grid, double* nodes_xyz);
+
+/* DefLocalMapping::needNewTemplate on keyframe `slot` of the store: candidate[i] (N entries, may be NULL) = 1 where the table entry is
+ * -1 and the mask is 0 at the key point's pixel; *n_candidates = their number, the reference's newPoints, which the caller compares with
+ * pointsToTemplate_.  A held bad point is neither a source of the mask nor a candidate (pMP is not null at :389).  One launch. */
+int dsh_need_new_template(dsh_mpdb* db, int32_t slot, const dsh_kf_keypoints* kf, int32_t* n_candidates, uint8_t* candidate);
+
+typedef struct dsh_template_switch_counts {
+  int32_t n_new, first_id;          /* points created; they are first_id .. first_id + n_new - 1 */
+  int32_t n_moved;                  /* key points that hold a point that is not bad */
+  int32_t n_masked;                 /* empty key points inside the mask */
+  int32_t n_embedded;               /* points with a facet afterwards */
+  int32_t n_points;                 /* the store's size afterwards */
+} dsh_template_switch_counts;
+typedef struct dsh_template_switch_input {
+  dsh_kfdb* kfdb;                   /* of the same context; the reference keyframe has the same slot in both stores */
+  int32_t slot;                     /* referenceKF_ */
+  const dsh_kf_keypoints* kf;
+  const float* surface_pts;         /* N x 3: Surface::get3DSurfacePoint per key point, camera frame */
+  const float* Twc;                 /* 16, row major: referenceKF_->GetPoseInverse() */
+} dsh_template_switch_input;
+/* DefLocalMapping::updateTemplate on the store, in the reference's order.  The context's current template must be one built from facets,
+ * else DSH_ERR_STATE: the caller builds it just before with dsh_template_build from the nodes of dsh_surface_vertices.
+ *   1. clearTemplate: every point of the store loses its facet.
+ *   2. The mask of the keyframe, as above.
+ *   3. CreateNewMapPoints per key point i; the iterations do not interact, so one parallel pass is exact.  Held and not bad: the point's
+ *      position becomes Twc (s_i, 1), counted in n_moved (a point held by two key points keeps the later one's, as in the sequential
+ *      loop).  Held and bad: nothing.  Empty and masked: nothing, counted in n_masked.  Empty and not masked: a new point.  New points get
+ *      the ids first_id + j in ascending i; new_idx[j] (N entries, may be NULL) = the key point of new point j.
+ *      x3wh = Twc * x3ch is a cv::Mat product of float32 4x4 by 4x1.  Reading, as for the pose products of the tracking search (a reading
+ *      of OpenCV's gemm for small operands; no OpenCV build to check against): the four products of a row are summed left to right in
+ *      float32, every product and sum rounded, no contraction.
+ *   4. A new point is what new DefMapPoint(x3w, referenceKF_, map) and :337-342 leave: not bad, visible = found = 1, no facet, one
+ *      observation record (id, slot) in the log, n_obs = 1, table entry i of the keyframe = its id; the descriptor is row i of the keyframe
+ *      in kfdb (ComputeDistinctiveDescriptors with one observation elects it); normal and max distance are UpdateNormalAndDepth with
+ *      that observation and this keyframe as reference, in the arithmetic of dsh_mappoint_update (n = 1: no division; level = the octave of
+ *      key point i), by the same device function.  The keyframe's bad flag is not read: referenceKF_ is a keyframe of the map (with a
+ *      bad one the reference's election would find no row and leave the descriptor empty).  Ow, the octaves and the scale factors come
+ *      from kfdb; an octave >= levels anywhere in the keyframe is DSH_ERR_ARG.  Every later call behaves as if the caller had made
+ *      these mutations through dsh_mpdb_add_points, dsh_mpdb_add_observations and dsh_mpdb_set_keyframe_point.
+ *   5. createTemplate's embedding: every point of the store that is not bad, the new ones included, is embedded in the context's template
+ *      from its position after step 3, as by dsh_template_embed_device (closest node, then that node's facets in index order, float32
+ *      pointInTriangle).  A point with a facet gets its three node indices in ascending order and the float32 barycentrics widened to
+ *      double (SetCoordinates takes doubles), and RecalculatePosition moves it: the expression of dsh_trackstate_repose on the template's
+ *      rest positions.  A point without a facet keeps its position of step 3.
+ * Transfers: up go the key points, the surface points, Twc, the keyframe's octaves and scale factors and the template, in one block;
+ * down come the counts and new_idx.  Nothing per map point travels.  Three launches: classification with the mask, creation with the
+ * prefix sum of the ids, embedding with the repose.
+ * NOT COVERED: Repose's UpdateNormalAndDepth of the embedded points (the store keeps neither the key point index of an observation nor
+ * mpRefKF: the caller runs dsh_mappoint_update with DSH_MP_NORMAL_DEPTH and dsh_mpdb_update_points as before, reading positions with
+ * dsh_trackstate_get); selectKeyframe (it iterates an unordered_map, its tie order is unspecified); DefKeyFrame::assignTemplate, the
+ * textures and lastincorporasion (host bookkeeping); the template constants (dsh_template_build). */
+int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32_t* new_idx, dsh_template_switch_counts* out);
+
+/* Read back n distinct points; each output may be NULL: xyz[n x 3], normal[n x 3], max_distance[n], desc[n x 32], bad[n]. */
+int dsh_point_store_get_points(dsh_mpdb* db, int n, const int32_t* ids, float* xyz, float* normal, float* max_distance, uint8_t* desc, uint8_t* bad);
+/* Read back the facets of n distinct points; each output may be NULL: nodes[n x 3] (-1 -1 -1: none), bary[n x 3]. */
+int dsh_point_store_get_embedding(dsh_mpdb* db, int n, const int32_t* ids, int32_t* nodes, double* bary);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -120,6 +120,13 @@ class MapPointStoreHIP {
     return dsh_trackstate_seed_local_points(db_, (int)ids.size(), ids.data()) == DSH_OK;
   }
   int point_count() const { return (int)points_.size(); }
+  // a point the store created itself (dsh_template_switch): the host object made for it takes the id; ids arrive in order
+  bool AdoptPoint(MapPointT* p, int id) {
+    if (id != (int)points_.size()) return false;
+    ids_[p] = id;
+    points_.push_back(p);
+    return true;
+  }
   // DefPoseOptimization moved these points (DefMapPoint::RecalculatePosition)
   template <class FrameT>
   bool UpdatePositions(const std::vector<MapPointT*>& pts) {

@@ -61,6 +61,17 @@ class LmMapPoint {                             // Thirdparty/ORBSLAM_2/include/M
   }
   LmFacet* facet = nullptr;                                             // :100
   double b1 = 0, b2 = 0, b3 = 0;                                        // :96
+  // what DefLocalMapping::CreateNewMapPoints and TriangularMesh::calculateFeaturesCoordinates touch (template_switch_hip.h)
+  void SetWorldPos(const float* x) { pos[0] = x[0]; pos[1] = x[1]; pos[2] = x[2]; }   // MapPoint.h:48
+  void AddObservation(LmKeyFrame* kf, size_t idx) {                     // MapPoint.h:57 (MapPoint.cc:86-97, monocular)
+    if (mObservations.count(kf)) return;
+    mObservations[kf] = idx;
+    nObs++;
+  }
+  void SetFacet(LmFacet* f) { facet = f; }                              // DefMapPoint.h:73
+  void SetCoordinates(double a, double b, double c) { b1 = a; b2 = b; b3 = c; }   // DefMapPoint.h:80
+  float mfMinDistance = 0.f;                                            // MapPoint.h:151
+  LmKeyFrame* mpRefKF = nullptr;                                        // MapPoint.h:141
 };
 
 class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/KeyFrame.h
@@ -75,6 +86,17 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
   LmKeyFrame* mpParent = nullptr;                                       // :217
   std::set<LmKeyFrame*> mspChildrens;                                   // :218
   bool bad = false;
+  // what DefLocalMapping::updateTemplate reads of the reference keyframe (template_switch_hip.h, mappoint_upkeep_hip.h)
+  void addMapPoint(LmMapPoint* p, size_t idx) { mvpMapPoints[idx] = p; }    // :86 AddMapPoint
+  int N = 0;                                                            // :149
+  std::vector<KeyPoint> mvKeysUn;                                       // :163
+  std::vector<uint8_t> mDescriptors;                                    // :171 N rows of 32 bytes (cv::Mat CV_8U)
+  int mnScaleLevels = 8;                                                // :184
+  std::vector<float> mvScaleFactors;                                    // :187
+  float Ow[3] = {0, 0, 0};                                              // GetCameraCenter() :62
+  float Twc[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPoseInverse() :61 (cv::Mat 4x4 float)
+  int rows = 0, cols = 0;                                               // imGray.rows, imGray.cols :228
+  std::vector<float> surface_points;                                    // DefKeyFrame::surface->get3DSurfacePoint(i, x3c): 3 per key point
 };
 
 class LmFrame {                                // Thirdparty/ORBSLAM_2/include/Frame.h
