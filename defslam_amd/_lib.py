@@ -126,6 +126,10 @@ class TrackCloseCountsC(C.Structure):
                                          "local_map_points", "n_moved")]
 
 
+class TrackEndCountsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("cleaned", "dropped", "kept")]
+
+
 class KfKeypointsC(C.Structure):
     _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("N", C.c_int32), ("kp", c_float_p)]
 
@@ -166,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "dsh_local_map_update", "dsh_local_map_points", "dsh_local_map_search",
     "dsh_trackstate_set_embedding", "dsh_trackstate_clear_embedding", "dsh_trackstate_set_counters", "dsh_trackstate_get",
     "dsh_trackstate_seed_local_points", "dsh_trackstate_repose", "dsh_trackstate_cull", "dsh_track_close_frame",
+    "dsh_track_end_frame", "dsh_track_last_frame", "dsh_motion_model_search",
     "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
 ]
 DSH_COMM_ID_BYTES = 128
@@ -297,6 +302,9 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_trackstate_repose.argtypes = [vp, C.c_int, c_double_p, c_i32_p]
     L.dsh_trackstate_cull.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_u8_p]
     L.dsh_track_close_frame.argtypes = [vp, C.POINTER(TrackFrameC), C.c_int, c_i32_p, c_u8_p, C.c_int, c_double_p, i32, C.POINTER(TrackCloseCountsC)]
+    L.dsh_track_end_frame.argtypes = [vp, C.c_int, c_i32_p, c_u8_p, c_i32_p, c_i32_p, c_u8_p, C.POINTER(TrackEndCountsC)]
+    L.dsh_track_last_frame.argtypes = [vp, i32, c_i32_p, c_i32_p, c_i32_p]
+    L.dsh_motion_model_search.argtypes = [vp, C.POINTER(TrackFrameC), C.c_float, C.c_float, i32, c_i32_p, c_i32_p, c_i32_p, c_float_p]
     L.dsh_surface_vertices.argtypes = [C.POINTER(SurfaceGridC), c_double_p]
     L.dsh_need_new_template.argtypes = [vp, i32, C.POINTER(KfKeypointsC), c_i32_p, c_u8_p]
     L.dsh_template_switch.argtypes = [vp, C.POINTER(TemplateSwitchInputC), c_i32_p, C.POINTER(TemplateSwitchCountsC)]

@@ -83,6 +83,9 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->max_node = -1;
   db->max_node_stale = false;
   db->top_on_device = false;
+  db->last_N = -1;
+  db->last_kept = 0;
+  db->last_max_octave = -1;
   db->obs.clear();
   db->kf.clear();
   return DSH_OK;

@@ -1,5 +1,6 @@
 // The map point store dsh_mpdb as its translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*), dsh_trackclose.cpp
-// (dsh_trackstate_*, dsh_track_close_frame) and dsh_tmplswitch.cpp (dsh_need_new_template, dsh_template_switch and the read-backs).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
+// (dsh_trackstate_*, dsh_track_close_frame), dsh_tmplswitch.cpp (dsh_need_new_template, dsh_template_switch and the read-backs) and
+// dsh_motionmodel.cpp (dsh_track_end_frame, dsh_track_last_frame, dsh_motion_model_search).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,9 @@ struct dsh_mpdb : dsh_store {
   LmKf* d_kf = nullptr;
   int32_t *d_table = nullptr, *d_local_kf = nullptr;
   LmHdr* d_hdr = nullptr;
+  // the resident last-frame list (dsh_track_end_frame): per key point of the last frame the id it holds or -1, and its octave (-1 there)
+  int32_t *d_last_ids = nullptr, *d_last_oct = nullptr;
+  int32_t last_cap = 0;
   // host mirror
   std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
   std::vector<LmKf> kf;
@@ -40,6 +44,9 @@ struct dsh_mpdb : dsh_store {
   int32_t max_node = -1;               // the largest of top_node, unless max_node_stale
   bool max_node_stale = false;
   bool top_on_device = false;          // a template switch wrote facets on the device: top_node does not know them, max_node does
+  int32_t last_N = -1;                 // length of the resident last-frame list, -1: there is none
+  int32_t last_kept = 0;               // its entries that hold a point
+  int32_t last_max_octave = -1;        // the largest octave among them
 
   // INT32_MAX, which refuses every template, when the device cannot be asked
   int32_t largest_node() {
@@ -62,7 +69,7 @@ struct dsh_mpdb : dsh_store {
   void free_all() {
     for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
                     (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
-                    (void*)d_local_kf, (void*)d_hdr})
+                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct})
       if (p) (void)hipFree(p);
   }
 };
@@ -90,6 +97,16 @@ inline hipError_t mpdb_reserve_points(dsh_mpdb* db, long long need) {
       (e = dsh_store_grow_array(&db->d_bary, 3 * P, 3 * cap)) != hipSuccess)
     return e;
   db->Pcap = (int32_t)cap;
+  return hipSuccess;
+}
+
+// room for a last-frame list of N entries (the list it holds stays until the call that grows it writes the new one)
+inline hipError_t mpdb_reserve_last_frame(dsh_mpdb* db, int32_t N) {
+  if (N <= db->last_cap) return hipSuccess;
+  const size_t cap = (size_t)std::max(N, 2 * db->last_cap), used = (size_t)std::max(db->last_N, 0);
+  hipError_t e;
+  if ((e = dsh_store_grow_array(&db->d_last_ids, used, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_last_oct, used, cap)) != hipSuccess) return e;
+  db->last_cap = (int32_t)cap;
   return hipSuccess;
 }
 

@@ -11,6 +11,9 @@
 //            best (and second best) walks its window again
 // The reference visits column ix, then row iy, then a cell's index order and keeps the first strictly better candidate, so its
 // best / second best are the two smallest keys (distance, cell = ix * rows + iy, index).
+// dsh_motion_model_search runs phases A and B twice on one grid (trk_launch_search): its queries are compacted on the device (qcount),
+// a query without observations does not block the key point it takes (qfree), and the second, wider pass is gated on the first
+// pass's count (gate).  All three are null for the other callers.
 // Compiled without FMA contraction: the reference's float32 expression order is kept (see include/defslam_hip.h).
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
@@ -166,8 +169,9 @@ __global__ __launch_bounds__(1024) void trk_cells_kernel(TrkBufs b) {
 
 // phase A: one wavefront per query
 __global__ __launch_bounds__(256) void trk_search_kernel(TrkBufs b, int Qt) {
+  if (b.gate && b.gate[0] >= b.gate_min) return;
   const int gq = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (gq >= Qt) return;
+  if (gq >= Qt || (b.qcount && gq >= b.qcount[0])) return;
   const TrkProb& P = b.prob[b.qpid[gq]];
   const float x = b.qxyz[3 * (size_t)gq], y = b.qxyz[3 * (size_t)gq + 1], z = b.qxyz[3 * (size_t)gq + 2];
   const int meta = b.qmeta[gq];
@@ -280,8 +284,9 @@ __device__ __forceinline__ int decide(const unsigned long long (&a)[TRK_K], int 
 __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
   __shared__ uint32_t taken[TRK_MAX_KEYPOINTS / 32];
   __shared__ uint32_t owner[TRK_MAX_KEYPOINTS];   // lowest pending lane of the round that picks the key point, 64 = none
+  if (b.gate && b.gate[0] >= b.gate_min) return;
   const TrkProb& P = b.prob[blockIdx.x];
-  const int lane = threadIdx.x, Q = P.Q, q_off = P.q_off;
+  const int lane = threadIdx.x, Q = b.qcount ? min(P.Q, b.qcount[0]) : P.Q, q_off = P.q_off;
   const bool local = P.mode == 1;
   for (int i = lane; i < TRK_MAX_KEYPOINTS / 32; i += 64) taken[i] = 0;
   for (int i = lane; i < TRK_MAX_KEYPOINTS; i += 64) owner[i] = 64;
@@ -295,6 +300,8 @@ __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
 #pragma unroll
     for (int k = 0; k < TRK_K; k++) lk[k] = mq < Q ? b.keys[(size_t)(q_off + mq) * TRK_K + k] : TRK_NO_KEY;
     if (mq < Q) lnc = b.ncand[q_off + mq];
+    // DefORBmatcher.cc:381-383: a pick blocks its key point only when the query's point has observations
+    const bool blocks = !(b.qfree && mq < Q && b.qfree[q_off + mq]);
     const int cnt = min(64, Q - base);
     int myres = -1;
     int start = 0;
@@ -303,7 +310,7 @@ __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
       bool rescan = false;
       int nexam = 0, res = -1;
       if (pending && lnc > 0) res = decide(lk, lnc, taken, local, &rescan, &nexam);
-      if (res >= 0) atomicMin(&owner[res], (uint32_t)lane);
+      if (res >= 0 && blocks) atomicMin(&owner[res], (uint32_t)lane);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       bool dirty = pending && rescan;
@@ -312,13 +319,13 @@ __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
         if (k < nexam && owner[kidx(lk[k])] < (uint32_t)lane) dirty = true;
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (res >= 0) owner[res] = 64;
+      if (res >= 0 && blocks) owner[res] = 64;
       const unsigned long long dm = __ballot(dirty);
       const int f = dm ? (int)__ffsll((long long)dm) - 1 : cnt;
       if (f > start) {
         const bool commit = pending && lane < f;
         if (commit) myres = res;
-        if (commit && res >= 0) atomicOr(&taken[res >> 5], 1u << (res & 31));
+        if (commit && res >= 0 && blocks) atomicOr(&taken[res >> 5], 1u << (res & 31));
         nm += __popcll(__ballot(commit && res >= 0));
         start = f;
       } else {
@@ -330,9 +337,10 @@ __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
         int n2;
         scan_window<2>(b, P, w.u, w.v, w.r, w.lmin, w.lmax, qd0, qd1, taken, lane, t2, &n2);
         const int r = accept(t2[0], t2[1], local);
+        const int sblocks = __shfl((int)blocks, start, 64);
         if (lane == start) myres = r;
         if (r >= 0) {
-          if (lane == 0) atomicOr(&taken[r >> 5], 1u << (r & 31));
+          if (lane == 0 && sblocks) atomicOr(&taken[r >> 5], 1u << (r & 31));
           nm++;
         }
         nres++;
@@ -344,6 +352,7 @@ __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
   if (lane == 0) {
     b.pstat[4 * blockIdx.x] = nm;
     b.pstat[4 * blockIdx.x + 1] = nres;
+    if (b.gate) b.pstat[4 * blockIdx.x + 3] = 1;
   }
 }
 
@@ -352,6 +361,11 @@ __global__ __launch_bounds__(64) void trk_resolve_kernel(TrkBufs b) {
 extern "C" hipError_t trk_launch(const TrkBufs& b, int B, int Qt, hipStream_t st) {
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(trk_cells_kernel, dim3(B), dim3(1024), 0, st, b);
+  return trk_launch_search(b, B, Qt, st);
+}
+
+extern "C" hipError_t trk_launch_search(const TrkBufs& b, int B, int Qt, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
   if (Qt > 0) hipLaunchKernelGGL(trk_search_kernel, dim3((Qt + 3) / 4), dim3(256), 0, st, b, Qt);
   hipLaunchKernelGGL(trk_resolve_kernel, dim3(B), dim3(64), 0, st, b);
   return hipGetLastError();

@@ -58,10 +58,18 @@ struct TrkBufs {
   int32_t* inview;
   float* uv;
   float* vcos;
-  int32_t* pstat;   // 4 per frame: matches, queries re-scanned in phase B, window over TRK_MAX_CANDIDATES, unused
+  int32_t* pstat;   // 4 per frame: matches, queries re-scanned in phase B, window over TRK_MAX_CANDIDATES, a gated pass ran
+  // dsh_motion_model_search only (motionmodel_kernels.hip fills what they point to); null for every other caller
+  const int32_t* gate = nullptr;     // phases A and B leave at once when gate[0] >= gate_min (the narrow pass found enough); null: run
+  int32_t gate_min = 0;
+  const int32_t* qcount = nullptr;   // the queries the device kept: they bound Qt and TrkProb::Q, which are upper limits then
+  const uint8_t* qfree = nullptr;    // per query 1: its point has no observations, so its pick does not block the key point
 };
 
+// cells, phase A, phase B
 extern "C" hipError_t trk_launch(const TrkBufs& b, int B, int Qt, hipStream_t st);
+// phases A and B alone, on the grid an earlier trk_launch of the same frames built (the wide pass of dsh_motion_model_search)
+extern "C" hipError_t trk_launch_search(const TrkBufs& b, int B, int Qt, hipStream_t st);
 
 // Host side shared by the entry points that run these kernels (dsh_track.cpp; dsh_localmap.cpp takes its queries from the store):
 // what is wrong with a frame ("" when nothing is), and a frame as a TrkProb -- everything but the offsets into the concatenated buffers.

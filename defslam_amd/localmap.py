@@ -5,6 +5,9 @@
   * Tracking::SearchLocalPoints (Tracking.cc:1405-1470) with the resident local points as queries;
   * the back half of DefTracking::TrackLocalMap (DefTracking.cc:253-339) on the store's per-point tracking state (dsh_trackstate_*,
     dsh_track_close_frame): the position write-back of DefPoseOptimization, the counting loops, LocalMapping::MapPointCulling;
+  * the end of a tracked frame in DefTracking::Track (CleanMatches, the outlier drop, mLastFrame: DefTracking.cc:169-172, :185-191, :211)
+    and the next frame's TrackWithMotionModel (:342-375) with the resident last-frame list as queries (dsh_track_end_frame,
+    dsh_motion_model_search);
   * DefLocalMapping::updateTemplate and needNewTemplate (Modules/Mapping/DefLocalMapping.cc:138-153, :355-404) on the store
     (dsh_template_switch, dsh_need_new_template): the occupancy mask, the new map points, the embedding in the new template.
 
@@ -74,6 +77,33 @@ class CloseCounts:
 
 
 @dataclass
+class EndFrame:
+    """What dsh_track_end_frame returns (DefTracking.cc:169-172, :185-191, :211)."""
+    points: np.ndarray                  # (N,) mvpMapPoints after CleanMatches: what CreateNewKeyFrame copies, outliers included
+    outlier: np.ndarray                 # (N,) bool mvbOutlier after CleanMatches
+    cleaned: int                        # entries CleanMatches emptied
+    dropped: int                        # outliers emptied afterwards
+    kept: int                           # entries of the resident last-frame list that hold a point
+
+
+@dataclass
+class LastFrame:
+    """The resident last-frame list (dsh_track_last_frame)."""
+    ids: np.ndarray                     # (N,) the point each key point of the last frame holds, or -1
+    octave: np.ndarray                  # (N,) its octave, -1 where the entry is empty
+
+
+@dataclass
+class MotionModelSearch:
+    """What dsh_motion_model_search returns (DefTracking::TrackWithMotionModel from the store)."""
+    frame_points: np.ndarray            # (N,) mvpMapPoints of the current frame as ids or -1
+    match: np.ndarray                   # (N_last,) the key point each last-frame entry took, or -1
+    nmatches: int
+    th_used: float                      # th or th_wide: the search that produced the result
+    ok: bool                            # TrackWithMotionModel's return value (nmatches >= 15, :373)
+
+
+@dataclass
 class StoredPoints:
     """What dsh_point_store_get_points returns, per id asked for."""
     xyz: np.ndarray                     # (n,3) float32 mWorldPos
@@ -121,6 +151,7 @@ class MapPointStore:
 
     def __init__(self, ctx: Context, points: int = 4096, keyframes: int = 64, observations: int = 1 << 16):
         self._ctx, self._h = ctx, None
+        self._n_last = 0                                       # length of the resident last-frame list (the N of the last end_frame)
         d = _lib.MpdbDescC(ctx._h, int(points), int(keyframes), int(observations))
         h = C.c_void_p()
         ctx._check(ctx._L.dsh_mpdb_create(C.byref(d), C.byref(h)), "dsh_mpdb_create")
@@ -138,6 +169,7 @@ class MapPointStore:
 
     def clear(self):
         self._call("dsh_mpdb_clear")
+        self._n_last = 0
 
     @property
     def n_points(self) -> int:
@@ -295,6 +327,42 @@ class MapPointStore:
         self._call("dsh_track_close_frame", C.byref(f), fp.shape[0], _ptr(fp, C.c_int32), _ptr(out, C.c_uint8), 0 if x is None else x.shape[0],
                    _ptr(x, C.c_double), 1 if only_tracking else 0, C.byref(cc))
         return CloseCounts(**{n: int(getattr(cc, n)) for n, _ in _lib.TrackCloseCountsC._fields_})
+
+    # ---- the end of a frame and the next frame's motion-model search ----
+    def end_frame(self, frame_points, outlier, octave) -> EndFrame:
+        """CleanMatches, the outlier drop and mLastFrame = Frame(*mCurrentFrame): frame_points / outlier / octave are mvpMapPoints (ids or
+        -1) / mvbOutlier / mvKeys[i].octave; the result of the two loops stays in the store as the last-frame list."""
+        fp = _i32(frame_points)
+        N = fp.shape[0]
+        out = np.ascontiguousarray(outlier, np.uint8).reshape(N)
+        oc = _i32(octave).reshape(N)
+        m = max(N, 1)
+        pts, flag = np.full(m, -1, np.int32), np.zeros(m, np.uint8)
+        cc = _lib.TrackEndCountsC()
+        self._call("dsh_track_end_frame", N, _ptr(fp, C.c_int32), _ptr(out, C.c_uint8), _ptr(oc, C.c_int32), _ptr(pts, C.c_int32), _ptr(flag, C.c_uint8),
+                   C.byref(cc))
+        self._n_last = N
+        return EndFrame(points=pts[:N], outlier=flag[:N].astype(bool), cleaned=int(cc.cleaned), dropped=int(cc.dropped), kept=int(cc.kept))
+
+    def last_frame(self, capacity: int = 8192) -> LastFrame:
+        """The resident last-frame list (capacity: at least its length; a frame has at most 8192 key points)."""
+        m = max(int(capacity), 1)
+        ids, oc = np.full(m, -1, np.int32), np.full(m, -1, np.int32)
+        n = C.c_int32(0)
+        self._call("dsh_track_last_frame", int(capacity), _ptr(ids, C.c_int32), _ptr(oc, C.c_int32), C.byref(n))
+        return LastFrame(ids=ids[:n.value].copy(), octave=oc[:n.value].copy())
+
+    def motion_model_search(self, frame: TrackFrame, th: float = 20.0, th_wide: float = 25.0, min_matches: int = 20) -> MotionModelSearch:
+        """DefTracking::TrackWithMotionModel after SetPose, with the resident last-frame list (of the preceding end_frame) as LastFrame;
+        frame.state is not read."""
+        keep = []
+        f = frame.c(keep)
+        N, NL = int(f.N), self._n_last
+        fp, match = np.full(max(N, 1), -1, np.int32), np.full(max(NL, 1), -1, np.int32)
+        nm, used = C.c_int32(0), C.c_float(0.0)
+        self._call("dsh_motion_model_search", C.byref(f), float(th), float(th_wide), int(min_matches), _ptr(fp, C.c_int32), _ptr(match, C.c_int32),
+                   C.byref(nm), C.byref(used))
+        return MotionModelSearch(frame_points=fp[:N], match=match[:NL], nmatches=int(nm.value), th_used=float(used.value), ok=nm.value >= 15)
 
     # ---- the template switch ----
     def get_points(self, ids=None) -> StoredPoints:

@@ -713,6 +713,58 @@ typedef struct dsh_track_close_counts {
 int dsh_track_close_frame(dsh_mpdb* db, const dsh_track_frame* frame, int N, const int32_t* frame_points, const uint8_t* outlier,
                           int n_nodes, const double* node_xyz, int32_t only_tracking, dsh_track_close_counts* out);
 
+/* ---- tracking: the end of a frame and the next frame's motion-model search on the resident map point store ----------------------
+ * What DefTracking::Track does with mvpMapPoints after a successful TrackLocalMap (Modules/Tracking/DefTracking.cc:169-172, :185-191,
+ * :211) and what TrackWithMotionModel (:342-375) reads of the frame that results, mLastFrame.  The store keeps that frame's point list
+ * resident -- per key point of the last frame the id it holds or -1, and the key point's octave -- so the next frame's first search
+ * sends up its own key points only.  dsh_mpdb_clear forgets the list.  Discipline of the other store calls: arguments are checked on
+ * the host first and DSH_ERR_ARG names the entry, nothing is stored or changed; then a host-only context answers DSH_ERR_NO_DEVICE;
+ * a detached store answers DSH_ERR_ARG.  Integer valued: every output is exact. */
+typedef struct dsh_track_end_counts {
+  int32_t cleaned;   /* entries CleanMatches emptied */
+  int32_t dropped;   /* outliers the loop at :185-191 emptied */
+  int32_t kept;      /* entries of the resident last-frame list that hold a point */
+} dsh_track_end_counts;
+/* frame_points[N] = mvpMapPoints as ids or -1, outlier[N] = mvbOutlier, octave[N] = mvKeys[i].octave, in the reference's order:
+ *   1. CleanMatches (:667-679): an entry whose point has n_obs < 1 becomes -1 and its outlier flag 0.  n_obs is the store's, stale
+ *      after a bad flag exactly as Observations() is (see n_obs above); there is no bad test, as in the reference.
+ *   2. points_out[N], outlier_out[N] (each may be NULL) = the state after step 1: what CreateNewKeyFrame copies into a keyframe,
+ *      outliers included (:175-178).
+ *   3. The outlier drop (:185-191): an entry that still holds a point and is an outlier becomes -1; its flag stays 1.
+ *   4. mLastFrame = Frame(*mCurrentFrame) (:211): the store keeps the result of steps 1 and 3 and octave[] as the resident last-frame
+ *      list of N entries, in place of the previous one.
+ *   5. *out (may be NULL) = the counts.
+ * N in [0, 8192], octaves in [0, 128).  One upload, one launch, one download.  DefTracking::MonocularInitialization (:637) makes the
+ * same call with the initial frame's points. */
+int dsh_track_end_frame(dsh_mpdb* db, int N, const int32_t* frame_points, const uint8_t* outlier, const int32_t* octave, int32_t* points_out,
+                        uint8_t* outlier_out, dsh_track_end_counts* out);
+/* The resident last-frame list read back: ids[capacity] and octave[capacity] (each may be NULL) receive its *n entries, the id or -1
+ * and the octave (-1 where the entry is empty).  DSH_ERR_ARG when capacity is smaller or when there is no list. */
+int dsh_track_last_frame(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* octave, int32_t* n);
+/* DefTracking::TrackWithMotionModel (:342-375) after SetPose: DefORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, true)
+ * (Modules/Matching/DefORBmatcher.cc:296-424) with the resident last-frame list as LastFrame, and again with th_wide on cleared
+ * mvpMapPoints when the first search finds fewer than min_matches (:364-370).  The reference passes th = 20, th_wide = 25,
+ * min_matches = 20; the caller applies nmatches < 15 (:373).  frame is the current frame at the pose the caller set (:350);
+ * frame->state is not read and may be NULL: mvpMapPoints are cleared first (:352-353), every key point enters empty.
+ * Queries: the entries of the list that hold a point, in index order (the last frame's outliers left it at the end of that frame).
+ * A query whose point is bad (:329-332) or has no facet (:331) is skipped, on the device and at call time; position, descriptor and
+ * n_obs are the store's at call time, the octave is the list's.  An octave >= frame->levels in the list is DSH_ERR_ARG.
+ * Projection, window, octave band [o - 1, o + 1], visiting order, strict-less best and TH_HIGH = 75 are those of DSH_TRACK_FRAME,
+ * by the same kernels; the arithmetic notes above dsh_track_frame apply unchanged.  No rotation histogram (mbCheckOrientation is false).
+ * Overwrite semantics, literally: a key point is no candidate only while the point it holds has Observations() > 0 (:381-383); :406
+ * assigns and :407 counts whatever the key point held.  So the pick of a query whose point has n_obs == 0 does not block its key
+ * point, a later query may take it again, the last writer in query order owns the entry and *nmatches counts both.
+ * Outputs: frame_points[frame->N] = mvpMapPoints as ids or -1; match[n] (may be NULL; n = the length of the list) = the key point each
+ * last-frame entry took, -1 for an empty, skipped or unmatched entry; *nmatches = the return value of the search that produced them;
+ * *th_used = th or th_wide, whichever search that was (each may be NULL).
+ * One upload (the frame), at most six launches -- the gather of the queries with its ordered compaction, the grid, and two search
+ * phases per pass; the wide pass is enqueued behind the narrow one and leaves at its first instruction when the narrow count
+ * suffices, there is no host read-back in between -- and one download.  Limits and refusals as dsh_search_by_projection_batch.  After
+ * the device gate: no resident list (before the first dsh_track_end_frame, after dsh_mpdb_clear) is DSH_ERR_ARG.  The call changes
+ * nothing in the store, the list included. */
+int dsh_motion_model_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, float th_wide, int32_t min_matches, int32_t* frame_points,
+                            int32_t* match, int32_t* nmatches, float* th_used);
+
 /* ---- mapping meets tracking: the template switch on the resident map point store -----------------------------------------------
  * DefLocalMapping::updateTemplate (Modules/Mapping/DefLocalMapping.cc:138-153), which DefTracking::Track calls on the tracking thread
  * (Modules/Tracking/DefTracking.cc:109) in front of the frame's two pose optimisations, and the mapping thread's trigger

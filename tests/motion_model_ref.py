@@ -1,0 +1,222 @@
+"""TEST INFRASTRUCTURE ONLY: sequential restatement of the end of a frame in DefTracking::Track and of the next frame's
+TrackWithMotionModel (the checker of dsh_track_end_frame, dsh_track_last_frame and dsh_motion_model_search), on top of
+tests/track_close_ref.py (the map with nObs and facets) and tests/track_search_ref.py (RefFrame: the grid and the arithmetic).
+
+Plain Python, statement by statement after the reference:
+  DefTracking::CleanMatches ........................... Modules/Tracking/DefTracking.cc:667-679 (called at :170)
+  the outlier drop, mLastFrame = Frame(*mCurrentFrame) . DefTracking.cc:185-191, :211
+  DefTracking::TrackWithMotionModel .................... DefTracking.cc:342-375
+  DefORBmatcher::SearchByProjection (Frame, Frame) ..... Modules/Matching/DefORBmatcher.cc:296-424, monocular, mbCheckOrientation false
+Unlike ORBmatcher.cc:1360-1510 (track_search_ref.search_frame) this copy skips bad points and points without a facet, tests
+Observations() > 0 of whatever a candidate key point holds, and assigns over it.  Nothing in defslam_amd/ imports this module.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+import track_close_ref as T
+import track_search_ref as R
+
+f32 = np.float32
+
+
+class MotionRefMap(T.TrackRefMap):
+    """TrackRefMap that also keeps mLastFrame's mvpMapPoints, mvbOutlier and key point octaves."""
+
+    def __init__(self):
+        super().__init__()
+        self.last_points = None                  # mLastFrame.mvpMapPoints as ids or -1; None: no frame has ended yet
+        self.last_outlier = None
+        self.last_octave = None
+
+    def forget_last_frame(self):
+        self.last_points = self.last_outlier = self.last_octave = None
+
+    # ---- DefTracking::Track after a successful TrackLocalMap ----
+    def end_frame(self, frame_points, outlier, octave):
+        mp = [int(p) for p in frame_points]
+        out = [bool(o) for o in outlier]
+        cleaned = dropped = 0
+        for i in range(len(mp)):                                      # CleanMatches, :669-678
+            if mp[i] >= 0:
+                if self.n_obs[mp[i]] < 1:                             # Observations(): nObs, stale after setBadFlag; no isBad test
+                    out[i] = False
+                    mp[i] = -1
+                    cleaned += 1
+        points_out, outlier_out = np.array(mp, np.int32).reshape(-1), np.array(out, bool).reshape(-1)      # CreateNewKeyFrame, :175-178
+        for i in range(len(mp)):                                      # :185-191
+            if mp[i] >= 0 and out[i]:
+                mp[i] = -1
+                dropped += 1
+        self.last_points, self.last_outlier = mp, out                 # :211
+        self.last_octave = [int(o) for o in octave]
+        return dict(points=points_out, outlier=outlier_out, cleaned=cleaned, dropped=dropped, kept=sum(p >= 0 for p in mp))
+
+    def last_frame(self):
+        """(ids, octave) as MapPointStore.last_frame() returns them: the octave of an empty entry is -1."""
+        ids = np.array(self.last_points, np.int32).reshape(-1)
+        return ids, np.where(ids >= 0, np.array(self.last_octave, np.int32).reshape(-1), -1).astype(np.int32)
+
+    # ---- DefORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, true) ----
+    def search_by_projection(self, fr: R.RefFrame, th):
+        """Returns (mvpMapPoints of the current frame as ids or -1, the key point each last-frame entry took or -1, nmatches)."""
+        th = f32(th)
+        mp = [-1] * fr.N                                              # cleared by the caller, DefTracking.cc:352-353 / :366-367
+        match = np.full(len(self.last_points), -1, np.int32)
+        nmatches = 0
+        for i, p in enumerate(self.last_points):                      # :321
+            if p < 0:                                                 # :325
+                continue
+            if self.last_outlier[i]:                                  # :327
+                continue
+            pt = self.points[p]
+            if pt.bad:                                                # :329
+                continue
+            if self.nodes[p] is None:                                 # :331 getFacet()
+                continue
+            xc, yc, zc = fr.cam(f32(pt.xyz[0]), f32(pt.xyz[1]), f32(pt.xyz[2]))
+            invzc = f32(1.0 / float(zc))                              # :339 double 1.0 / float, stored as float
+            if invzc < 0:
+                continue
+            u = f32(f32(fr.fx * xc) * invzc) + fr.cx
+            v = f32(f32(fr.fy * yc) * invzc) + fr.cy
+            if u != u or v != v:                                      # NaN: outside by contract (include/defslam_hip.h)
+                continue
+            if u < fr.minX or u > fr.maxX:
+                continue
+            if v < fr.minY or v > fr.maxY:
+                continue
+            nLastOctave = self.last_octave[i]                         # :352
+            radius = f32(th * fr.sf[nLastOctave])
+            vIndices2 = fr.features_in_area(u, v, radius, nLastOctave - 1, nLastOctave + 1)      # monocular: :365-366
+            if not vIndices2:
+                continue
+            dMP = int.from_bytes(np.asarray(pt.desc, np.uint8).tobytes(), "little")
+            bestDist, bestIdx2 = 256, -1
+            for i2 in vIndices2:
+                if mp[i2] >= 0:                                       # :381-383
+                    if self.n_obs[mp[i2]] > 0:
+                        continue
+                dist = (dMP ^ fr.desc[i2]).bit_count()
+                if dist < bestDist:
+                    bestDist, bestIdx2 = dist, i2
+            if bestDist <= R.TH_HIGH:                                 # :404-407: assigns over whatever the key point held
+                mp[bestIdx2] = p
+                match[i] = bestIdx2
+                nmatches += 1
+        return np.array(mp, np.int32).reshape(-1), match, nmatches
+
+    # ---- DefTracking::TrackWithMotionModel ----
+    def motion_model_search(self, track_frame, th=20, th_wide=25, min_matches=20):
+        fr = R.ref_frame(track_frame)
+        fp, match, n = self.search_by_projection(fr, th)
+        used = th
+        if n < min_matches:                                           # :364-370: cleared, searched again
+            fp, match, n = self.search_by_projection(fr, th_wide)
+            used = th_wide
+        return dict(frame_points=fp, match=match, nmatches=n, th_used=float(used), ok=n >= 15)
+
+    def last_frame_queries(self):
+        """The last frame's entries the search does not skip, as the packed arrays of dsh_search_by_projection_frame:
+        (entry index, xyz, octave, desc)."""
+        idx = [i for i, p in enumerate(self.last_points)
+               if p >= 0 and not self.last_outlier[i] and not self.points[p].bad and self.nodes[p] is not None]
+        Q = len(idx)
+        ids = [self.last_points[i] for i in idx]
+        return (np.array(idx, np.int64), np.array([self.points[p].xyz for p in ids], np.float32).reshape(Q, 3),
+                np.array([self.last_octave[i] for i in idx], np.int32), np.array([self.points[p].desc for p in ids], np.uint8).reshape(Q, 32))
+
+
+def scene_to_ref(sc) -> MotionRefMap:
+    """A synth.make_track_close_scene dict as a MotionRefMap."""
+    rm = MotionRefMap()
+    base = T.scene_to_ref(sc)
+    rm.__dict__.update({k: v for k, v in base.__dict__.items()})
+    return rm
+
+
+def make_last_frame(sc, L, seed=0, hole=0.12, other=0.2, outlier=0.1):
+    """A last frame of L key points for the current frame of a generated scene: (points (L,), outlier (L,), octave (L,)).  Most entries
+    hold a point that the scene's frame has a key point for, each such point at most once while they last, with the octave of that key
+    point; a share `other` holds any point of the map (bad ones, points without a facet or without an observation among them) at a
+    random octave, a share `hole` is empty, a share `outlier` of the held entries is an outlier."""
+    rng = np.random.default_rng(4200 + 31 * seed + L)
+    P = sc["xyz"].shape[0]
+    a = sc["frame"].arrays()
+    levels = a["sf"].shape[0]
+    kp_of = {}
+    for src in (sc["final_points"], sc["frame_points"]):
+        for j, p in enumerate(src):
+            if p >= 0:
+                kp_of.setdefault(int(p), j)
+    seen = list(kp_of)
+    rng.shuffle(seen)
+    pts, octs = np.full(L, -1, np.int32), np.zeros(L, np.int32)
+    for i in range(L):
+        r = rng.uniform() if i else 1.0                               # entry 0 always holds a point with a key point
+        if r < hole:
+            octs[i] = rng.integers(0, levels)
+        elif r < hole + other or not seen:
+            pts[i], octs[i] = rng.integers(0, P), rng.integers(0, levels)
+        else:
+            p = seen.pop()
+            pts[i], octs[i] = p, a["octave"][kp_of[p]]
+    out = ((pts >= 0) & (rng.uniform(size=L) < outlier)).astype(np.uint8)
+    out[0] = 0
+    return pts, out, octs
+
+
+def trim_to_narrow_count(rm: MotionRefMap, track_frame, target, th=20):
+    """Empty matched entries of rm's last frame, from its end, until the search at th finds exactly `target`; returns the entries emptied.
+    Emptying the last matched entry frees its key point for the entries behind it only, which all were unmatched: at most one of them
+    takes it, so a step lowers the count by one or leaves it, and the target is never stepped over."""
+    fr = R.ref_frame(track_frame)
+    gone = []
+    while True:
+        _, match, n = rm.search_by_projection(fr, th)
+        if n <= target:
+            assert n == target, (n, target)
+            return gone
+        i = int(np.nonzero(match >= 0)[0][-1])
+        rm.last_points[i] = -1
+        gone.append(i)
+
+
+# ---- the hand-built case: eight last-frame entries around one projection, three key points ---------------------------------------------
+
+HAND_U, HAND_V = np.float32(382.5), np.float32(271.25)                # projection of (0.125, 0.0625, 1) by the hand frame's camera
+HAND_LAST_POINTS = [0, 1, -1, 2, 3, 4, 5, 6]
+HAND_LAST_OUTLIER = [0, 0, 0, 0, 0, 0, 1, 0]
+HAND_LAST_OCTAVE = [0, 1, 3, 0, 0, 0, 0, 1]
+HAND_END = dict(points=[0, 1, -1, 2, 3, 4, 5, -1], outlier=[0, 0, 0, 0, 0, 0, 1, 0], cleaned=1, dropped=1, kept=5)
+HAND_LIST = ([0, 1, -1, 2, 3, 4, -1, -1], [0, 1, -1, 0, 0, 0, -1, -1])
+# after erase_observation(0, 0) and set_bad(3): p0 takes key point 0 and does not block it, p1 takes it again, p2 falls back to key point
+# 1, p3 is bad, p4 has no facet; key point 2 is beyond TH_HIGH for everyone
+HAND_FRAME_POINTS = [1, 2, -1]
+HAND_MATCH = [0, 0, -1, 1, -1, -1, -1, -1]
+HAND_NMATCHES = 3
+# had p0 kept its observation it would block key point 0: p1 takes key point 1 and p2 finds nothing
+HAND_BLOCKING_FRAME_POINTS = [0, 1, -1]
+HAND_BLOCKING_MATCH = [0, 1, -1, -1, -1, -1, -1, -1]
+HAND_BLOCKING_NMATCHES = 2
+
+
+def hand_map() -> MotionRefMap:
+    """Seven points at (0.125, 0.0625, 1) with the all-zero descriptor; keyframe 0 holds and observes p0..p5, p6 is observed by nobody
+    (CleanMatches empties its entry); p4 has no facet; the entry of p5 is an outlier."""
+    rm = MotionRefMap()
+    for _ in range(7):
+        rm.add_point(xyz=(0.125, 0.0625, 1.0))
+    rm.add_keyframe([0, 1, 2, 3, 4, 5], parent=-1)
+    for p in range(6):
+        rm.add_observation(p, 0)
+    for p in (0, 1, 2, 3, 5, 6):
+        rm.set_embedding(p, (0, 1, 2), (0.5, 0.25, 0.25))
+    return rm
+
+
+def hand_frame():
+    """The identity-pose frame of tests/test_track_search_cpu.py with key points at Hamming distance 3, 10 and 80 from the points."""
+    from test_track_search_cpu import desc_with_dist, hand_frame as hf
+    return hf([[HAND_U + 1, HAND_V], [HAND_U - 2, HAND_V], [HAND_U + 3, HAND_V]], [0, 0, 0],
+              desc=np.stack([desc_with_dist(3), desc_with_dist(10), desc_with_dist(80)]))
