@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdefslam_hip.so")
 LAB_LIB_PATH = os.path.join(_HERE, "lib", "libdefslam_hip_lab.so")
 
 DSH_OK = 0
+DSH_ERR_ARG = 1
+DSH_ERR_STATE = 3
 DSH_TRACE_STRIDE = 8
 DSH_MAX_ITERS = 64
 
@@ -146,6 +148,13 @@ class TemplateSwitchInputC(C.Structure):
     _fields_ = [("kfdb", C.c_void_p), ("slot", C.c_int32), ("kf", C.POINTER(KfKeypointsC)), ("surface_pts", c_float_p), ("Twc", c_float_p)]
 
 
+class AnchorListsC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("anchor_capacity", "pair_capacity", "query_capacity")] + [("max_matrix_bytes", C.c_int64)] +
+                [(n, c_i32_p) for n in ("anchor_slot", "anchor_count", "anchor_pairs", "pair_ptr", "pair_idx1", "pair_idx2", "pair_point")] +
+                [("pair_own", c_u8_p)] + [(n, c_i32_p) for n in ("query_ptr", "query_idx1", "query_point")] + [("has", c_u8_p)] +
+                [(n, C.c_int32) for n in ("n_anchors", "n_pairs", "n_queries", "n_no_ref")])
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -172,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "dsh_trackstate_seed_local_points", "dsh_trackstate_repose", "dsh_trackstate_cull", "dsh_track_close_frame",
     "dsh_track_end_frame", "dsh_track_last_frame", "dsh_motion_model_search",
     "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
+    "dsh_point_store_add_observations_indexed", "dsh_point_store_set_reference_keyframes", "dsh_point_store_get_reference_keyframes", "dsh_keyframe_anchors",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -310,6 +320,10 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_template_switch.argtypes = [vp, C.POINTER(TemplateSwitchInputC), c_i32_p, C.POINTER(TemplateSwitchCountsC)]
     L.dsh_point_store_get_points.argtypes = [vp, C.c_int, c_i32_p, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p]
     L.dsh_point_store_get_embedding.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, c_double_p]
+    L.dsh_point_store_add_observations_indexed.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, c_i32_p]
+    L.dsh_point_store_set_reference_keyframes.argtypes = [vp, C.c_int, c_i32_p, c_i32_p]
+    L.dsh_point_store_get_reference_keyframes.argtypes = [vp, C.c_int, c_i32_p, c_i32_p]
+    L.dsh_keyframe_anchors.argtypes = [vp, i32, i32, C.POINTER(AnchorListsC)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

@@ -28,6 +28,47 @@ int put_i32(dsh_ctx_base* c, int32_t* dst, int32_t v) {
   return DSH_OK;
 }
 
+// MapPoint::AddObservation for n pairs, with the key point index of each (indexed) or without one
+int add_observations(dsh_mpdb* db, const char* who, int n, const int32_t* point_ids, const int32_t* keyframe_slots, const int32_t* idx, bool indexed) {
+  DSH_STORE_ENTER(who);
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!point_ids || !keyframe_slots)) return bad("point_ids or keyframe_slots is NULL");
+  if (n > 0 && indexed && !idx) return bad("idx is NULL");
+  std::unordered_set<uint64_t> batch;
+  for (int i = 0; i < n; i++) {
+    const int32_t p = point_ids[i], s = keyframe_slots[i];
+    const std::string at = "pair " + std::to_string(i) + ": ", pe = mpdb_pair_error(db, p, s);
+    if (!pe.empty()) return bad(at + pe);
+    if (indexed && (idx[i] < 0 || idx[i] >= db->kf[s].N)) return bad(at + "index outside the keyframe's key points");
+    if (db->obs.count(mpdb_obs_key(p, s))) return bad(at + "the point already observes this keyframe");
+    if (!batch.insert(mpdb_obs_key(p, s)).second) return bad(at + "repeated in the batch");
+  }
+  if (const int rc = dsh_enter(c, who)) return rc;
+  if (n == 0) return DSH_OK;
+  HIPCHK(c, mpdb_reserve_log(db, db->R + n));
+  UpBlock up;   // staged here, copied to the end of the log and of the indices beside it
+  const size_t o_rec = up.take(8 * (size_t)n), o_idx = up.take_exact(indexed ? 4 * (size_t)n : 0);
+  if (const int rc = up.stage(c)) return rc;
+  int2* h = up.host<int2>(o_rec);
+  for (int i = 0; i < n; i++) h[i] = make_int2(point_ids[i], keyframe_slots[i]);
+  HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  if (indexed) {
+    std::memcpy(up.host<int32_t>(o_idx), idx, 4 * (size_t)n);
+    HIPCHK(c, hipMemcpyAsync(db->d_log_idx + db->R, up.host<int32_t>(o_idx), 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  } else {
+    HIPCHK(c, hipMemsetAsync(db->d_log_idx + db->R, 0xff, 4 * (size_t)n, c->stream));   // -1: no index
+  }
+  HIPCHK(c, tc_add_by_index_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log + db->R), 2, 1, n, c->stream));   // nObs++ (MapPoint.cc:116-119)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; i++) {
+    const uint64_t k = mpdb_obs_key(point_ids[i], keyframe_slots[i]);
+    db->obs[k] = db->R + i;
+    if (!indexed) db->unindexed.insert(k);
+  }
+  db->R += n;
+  return DSH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -47,7 +88,7 @@ int dsh_mpdb_create(const dsh_mpdb_desc* desc, dsh_mpdb** out) {
     db->Tcap = (long long)desc->keyframe_capacity * 1024;
     db->Rcap = desc->observation_capacity;
     if (mpdb_reserve_points(db, desc->point_capacity) != hipSuccess || mpdb_reserve_keyframes(db, desc->keyframe_capacity) != hipSuccess ||
-        hipMalloc((void**)&db->d_log, sizeof(int2) * (size_t)db->Rcap) != hipSuccess ||
+        mpdb_reserve_log(db, db->Rcap) != hipSuccess ||
         hipMalloc((void**)&db->d_table, 4 * (size_t)db->Tcap) != hipSuccess || hipMalloc((void**)&db->d_hdr, sizeof(LmHdr)) != hipSuccess ||
         hipMemset(db->d_hdr, 0, sizeof(LmHdr)) != hipSuccess) {
       db->free_all();
@@ -87,6 +128,7 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->last_kept = 0;
   db->last_max_octave = -1;
   db->obs.clear();
+  db->unindexed.clear();
   db->kf.clear();
   return DSH_OK;
 }
@@ -114,6 +156,7 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
   HIPCHK(c, hipMemcpyAsync(db->d_maxd + P, max_distance, 4 * (size_t)n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(db->d_desc + 2 * P, desc, 32 * (size_t)n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(db->d_bad + P, b32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(db->d_ref_kf + P, 0xff, 4 * (size_t)n, st));   // no reference keyframe yet (dsh_point_store_set_reference_keyframes)
   HIPCHK(c, tc_init_points_launch(mpdb_state(db), db->P, n, st));   // mnVisible = mnFound = 1, nObs = 0, no facet
   HIPCHK(c, hipStreamSynchronize(st));
   db->P += n;
@@ -174,35 +217,11 @@ int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8
 }
 
 int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots) {
-  DSH_STORE_ENTER("dsh_mpdb_add_observations");
-  if (n < 0) return bad("n < 0");
-  if (n > 0 && (!point_ids || !keyframe_slots)) return bad("point_ids or keyframe_slots is NULL");
-  std::unordered_set<uint64_t> batch;
-  for (int i = 0; i < n; i++) {
-    const int32_t p = point_ids[i], s = keyframe_slots[i];
-    const std::string at = "pair " + std::to_string(i) + ": ", pe = mpdb_pair_error(db, p, s);
-    if (!pe.empty()) return bad(at + pe);
-    if (db->obs.count(mpdb_obs_key(p, s))) return bad(at + "the point already observes this keyframe");
-    if (!batch.insert(mpdb_obs_key(p, s)).second) return bad(at + "repeated in the batch");
-  }
-  if (const int rc = dsh_enter(c, "dsh_mpdb_add_observations")) return rc;
-  if (n == 0) return DSH_OK;
-  if (db->R + n > db->Rcap) {
-    const long long cap = std::max(db->R + n, 2 * db->Rcap);
-    HIPCHK(c, dsh_store_grow_array(&db->d_log, (size_t)db->R, (size_t)cap));
-    db->Rcap = cap;
-  }
-  UpBlock up;   // staged here, copied to the end of the log
-  const size_t o_rec = up.take_exact(8 * (size_t)n);
-  if (const int rc = up.stage(c)) return rc;
-  int2* h = up.host<int2>(o_rec);
-  for (int i = 0; i < n; i++) h[i] = make_int2(point_ids[i], keyframe_slots[i]);
-  HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, up.size, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, tc_add_by_index_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log + db->R), 2, 1, n, c->stream));   // nObs++ (MapPoint.cc:116-119)
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; i++) db->obs[mpdb_obs_key(point_ids[i], keyframe_slots[i])] = db->R + i;
-  db->R += n;
-  return DSH_OK;
+  return add_observations(db, "dsh_mpdb_add_observations", n, point_ids, keyframe_slots, nullptr, false);
+}
+
+int dsh_point_store_add_observations_indexed(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots, const int32_t* idx) {
+  return add_observations(db, "dsh_point_store_add_observations_indexed", n, point_ids, keyframe_slots, idx, true);
 }
 
 int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots) {
@@ -236,7 +255,10 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
   HIPCHK(c, tc_add_by_record_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log), didx, -1, (int)idx.size(), c->stream));
   HIPCHK(c, lm_scatter_i32_launch(reinterpret_cast<int32_t*>(db->d_log), didx, nullptr, -1, (int)idx.size(), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (const uint64_t k : keys) db->obs.erase(k);
+  for (const uint64_t k : keys) {
+    db->obs.erase(k);
+    db->unindexed.erase(k);
+  }
   return DSH_OK;
 }
 

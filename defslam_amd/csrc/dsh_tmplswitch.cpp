@@ -154,11 +154,7 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   // room for a new point per key point: how many are empty is known on the device only
   const size_t N = (size_t)kf.N;
   HIPCHK(c, mpdb_reserve_points(db, (long long)db->P + kf.N));
-  if (db->R + kf.N > db->Rcap) {
-    const long long cap = std::max(db->R + kf.N, 2 * db->Rcap);
-    HIPCHK(c, dsh_store_grow_array(&db->d_log, (size_t)db->R, (size_t)cap));
-    db->Rcap = cap;
-  }
+  HIPCHK(c, mpdb_reserve_log(db, db->R + kf.N));
 
   // up: the counts (zero), Twc, the key points, the surface points, the octaves and scale factors, the template
   UpBlock up;
@@ -194,7 +190,7 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   k.sf = up.dev<const float>(o_sf);
   k.levels = hk.levels;
   k.kf_slots = kfdb->d_slots; k.kf_rows = kfdb->d_rows;
-  k.log = db->d_log; k.normal = db->d_nrm; k.max_distance = db->d_maxd; k.desc = db->d_desc;
+  k.log = db->d_log; k.log_idx = db->d_log_idx; k.ref_kf = db->d_ref_kf; k.normal = db->d_nrm; k.max_distance = db->d_maxd; k.desc = db->d_desc;
   k.counts = down.dev<TsCounts>(d_cnt);
   k.new_idx = down.dev<int32_t>(d_idx);
   HIPCHK(c, dsh_scratch_array(c, &k.cls, N));

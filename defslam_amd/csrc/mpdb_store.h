@@ -1,12 +1,14 @@
 // The map point store dsh_mpdb as its translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*), dsh_trackclose.cpp
 // (dsh_trackstate_*, dsh_track_close_frame), dsh_tmplswitch.cpp (dsh_need_new_template, dsh_template_switch and the read-backs) and
-// dsh_motionmodel.cpp (dsh_track_end_frame, dsh_track_last_frame, dsh_motion_model_search).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
+// dsh_motionmodel.cpp (dsh_track_end_frame, dsh_track_last_frame, dsh_motion_model_search) and dsh_anchor.cpp (dsh_keyframe_anchors and the
+// two fields it reads: the key point index of an observation, the reference keyframe of a point).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/defslam_hip.h"
@@ -22,12 +24,14 @@ struct dsh_mpdb : dsh_store {
   float *d_xyz = nullptr, *d_nrm = nullptr, *d_maxd = nullptr;
   uint4* d_desc = nullptr;
   int32_t *d_bad = nullptr, *d_cnt = nullptr, *d_local_ids = nullptr;
+  int32_t* d_ref_kf = nullptr;   // per point MapPoint::GetReferenceKeyFrame as a slot, -1: not given
   // tracking state per point (dsh_trackstate_*, dsh_track_close_frame): mnVisible, mnFound, nObs, the facet as three ascending node
   // indices (-1: none) with its barycentrics, and the local point list as it was before the last dsh_local_map_update
   int32_t *d_visible = nullptr, *d_found = nullptr, *d_nobs = nullptr, *d_nodes = nullptr, *d_ref_ids = nullptr;
   double* d_bary = nullptr;
   // observations, keyframes, the resident local map
   int2* d_log = nullptr;
+  int32_t* d_log_idx = nullptr;   // parallel to the log: the key point index of the observation in its keyframe, -1: not given
   LmKf* d_kf = nullptr;
   int32_t *d_table = nullptr, *d_local_kf = nullptr;
   LmHdr* d_hdr = nullptr;
@@ -36,6 +40,7 @@ struct dsh_mpdb : dsh_store {
   int32_t last_cap = 0;
   // host mirror
   std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
+  std::unordered_set<uint64_t> unindexed;        // the live records without a key point index (dsh_mpdb_add_observations)
   std::vector<LmKf> kf;
   int32_t n_local_points = 0;
   int32_t n_ref_points = 0;            // length of d_ref_ids
@@ -69,7 +74,7 @@ struct dsh_mpdb : dsh_store {
   void free_all() {
     for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
                     (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
-                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct})
+                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx})
       if (p) (void)hipFree(p);
   }
 };
@@ -94,9 +99,19 @@ inline hipError_t mpdb_reserve_points(dsh_mpdb* db, long long need) {
       (e = dsh_store_grow_array(&db->d_local_ids, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_ref_ids, P, cap)) != hipSuccess ||
       (e = dsh_store_grow_array(&db->d_visible, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_found, P, cap)) != hipSuccess ||
       (e = dsh_store_grow_array(&db->d_nobs, P, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_nodes, 3 * P, 3 * cap)) != hipSuccess ||
-      (e = dsh_store_grow_array(&db->d_bary, 3 * P, 3 * cap)) != hipSuccess)
+      (e = dsh_store_grow_array(&db->d_bary, 3 * P, 3 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_ref_kf, P, cap)) != hipSuccess)
     return e;
   db->Pcap = (int32_t)cap;
+  return hipSuccess;
+}
+
+// room for `need` log records: the log and the key point indices beside it
+inline hipError_t mpdb_reserve_log(dsh_mpdb* db, long long need) {
+  if (need <= db->Rcap && db->d_log && db->d_log_idx) return hipSuccess;
+  const size_t cap = (size_t)std::max(need, db->d_log ? 2 * db->Rcap : db->Rcap), R = (size_t)db->R;
+  hipError_t e;
+  if ((e = dsh_store_grow_array(&db->d_log, R, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_log_idx, R, cap)) != hipSuccess) return e;
+  db->Rcap = (long long)cap;
   return hipSuccess;
 }
 

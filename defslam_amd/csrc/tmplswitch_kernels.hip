@@ -136,6 +136,8 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_create_kernel(TcState s, TsSwitch
   s.found[p] = 1;
   s.nobs[p] = 1;
   k.log[k.R + j] = make_int2((int)p, k.slot);
+  k.log_idx[k.R + j] = i;   // the observation's key point, and mpRefKF = referenceKF_ (what dsh_keyframe_anchors reads)
+  k.ref_kf[p] = k.slot;
   k.table[k.tab_off + i] = (int)p;
   const MpuSlot kf = k.kf_slots[k.slot];
   k.desc[2 * p] = k.kf_rows[2 * ((size_t)kf.row_off + i)];   // one observation: its descriptor is elected

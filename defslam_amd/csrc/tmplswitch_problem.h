@@ -43,6 +43,8 @@ struct TsSwitch {
   // dsh_mpdb besides TcState
   int32_t* table;
   int2* log;
+  int32_t* log_idx;              // the key point index of each log record
+  int32_t* ref_kf;               // the reference keyframe of each point
   float* normal;
   float* max_distance;
   uint4* desc;

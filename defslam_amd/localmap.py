@@ -9,7 +9,10 @@
     and the next frame's TrackWithMotionModel (:342-375) with the resident last-frame list as queries (dsh_track_end_frame,
     dsh_motion_model_search);
   * DefLocalMapping::updateTemplate and needNewTemplate (Modules/Mapping/DefLocalMapping.cc:138-153, :355-404) on the store
-    (dsh_template_switch, dsh_need_new_template): the occupancy mask, the new map points, the embedding in the new template.
+    (dsh_template_switch, dsh_need_new_template): the occupancy mask, the new map points, the embedding in the new template;
+  * what SchwarpDatabase::add (Modules/Mapping/SchwarpDatabase.cc:61-106) and DefORBmatcher::searchBySchwarp
+    (Modules/Matching/DefORBmatcher.cc:200-211) read of the map for a new keyframe (dsh_keyframe_anchors): its anchor keyframes, the
+    matched key point indices and the search queries per anchor.
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -138,6 +141,32 @@ class TemplateSwitch:
     new_idx: np.ndarray                 # (n_new,) the key point of each new point
 
 
+@dataclass
+class KeyframeAnchors:
+    """What dsh_keyframe_anchors returns: the anchors by ascending slot, the pairs and queries of the anchors that reached min_pairs as CSR."""
+    anchor_slot: np.ndarray             # (A,) the reference keyframes of the new keyframe's points
+    anchor_count: np.ndarray            # (A,) countKFMatches
+    anchor_pairs: np.ndarray            # (A,) len(vMatchedIndices), below min_pairs or not
+    pair_ptr: np.ndarray                # (A+1,)
+    pair_idx1: np.ndarray               # key point in the anchor
+    pair_idx2: np.ndarray               # key point in the new keyframe
+    pair_point: np.ndarray              # the shared point
+    pair_own: np.ndarray                # bool: the anchor is the point's reference keyframe (its record is stored after the fit)
+    query_ptr: np.ndarray               # (A+1,)
+    query_idx1: np.ndarray              # entries of the anchor's table that searchBySchwarp looks for in the new keyframe
+    query_point: np.ndarray
+    has: np.ndarray                     # (N,) bool: the new keyframe's entry holds a point
+    n_no_ref: int                       # entries whose point has no reference keyframe
+
+    def pairs(self, a: int):
+        """vMatchedIndices of anchor a: (idx1, idx2) rows."""
+        s = slice(self.pair_ptr[a], self.pair_ptr[a + 1])
+        return np.stack([self.pair_idx1[s], self.pair_idx2[s]], 1)
+
+    def queries(self, a: int) -> np.ndarray:
+        return self.query_idx1[self.query_ptr[a]:self.query_ptr[a + 1]]
+
+
 # dsh_trackstate_cull: what became of an entry of mlpRecentAddedMapPoints
 CULL_STAYS, CULL_WAS_BAD, CULL_SET_BAD, CULL_OLD = 0, 1, 2, 3
 
@@ -152,6 +181,7 @@ class MapPointStore:
     def __init__(self, ctx: Context, points: int = 4096, keyframes: int = 64, observations: int = 1 << 16):
         self._ctx, self._h = ctx, None
         self._n_last = 0                                       # length of the resident last-frame list (the N of the last end_frame)
+        self._kf_n = []                                        # key points per keyframe slot
         d = _lib.MpdbDescC(ctx._h, int(points), int(keyframes), int(observations))
         h = C.c_void_p()
         ctx._check(ctx._L.dsh_mpdb_create(C.byref(d), C.byref(h)), "dsh_mpdb_create")
@@ -170,6 +200,7 @@ class MapPointStore:
     def clear(self):
         self._call("dsh_mpdb_clear")
         self._n_last = 0
+        self._kf_n = []
 
     @property
     def n_points(self) -> int:
@@ -211,19 +242,36 @@ class MapPointStore:
         self._call("dsh_mpdb_set_points_bad", ids.shape[0], _ptr(ids, C.c_int32), _ptr(b, C.c_uint8))
 
     # ---- observations ----
-    def add_observations(self, point_ids, keyframe_slots):
+    def add_observations(self, point_ids, keyframe_slots, idx=None):
+        """MapPoint::AddObservation; idx: the key point index of each observation in its keyframe (needed by keyframe_anchors)."""
         p, k = _i32(point_ids), _i32(keyframe_slots)
-        self._call("dsh_mpdb_add_observations", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32))
+        if idx is None:
+            self._call("dsh_mpdb_add_observations", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32))
+        else:
+            i = _i32(idx)
+            self._call("dsh_point_store_add_observations_indexed", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32), _ptr(i, C.c_int32))
 
     def erase_observations(self, point_ids, keyframe_slots):
         p, k = _i32(point_ids), _i32(keyframe_slots)
         self._call("dsh_mpdb_erase_observations", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32))
+
+    def set_reference_keyframes(self, ids, slots):
+        """MapPoint::GetReferenceKeyFrame of ids: a slot each, or -1."""
+        ids, sl = _i32(ids), _i32(slots)
+        self._call("dsh_point_store_set_reference_keyframes", ids.shape[0], _ptr(ids, C.c_int32), _ptr(sl, C.c_int32))
+
+    def get_reference_keyframes(self, ids=None) -> np.ndarray:
+        ids = np.arange(self.n_points, dtype=np.int32) if ids is None else _i32(ids)
+        out = np.full(max(ids.shape[0], 1), -1, np.int32)
+        self._call("dsh_point_store_get_reference_keyframes", ids.shape[0], _ptr(ids, C.c_int32), _ptr(out, C.c_int32))
+        return out[:ids.shape[0]]
 
     # ---- keyframes ----
     def add_keyframe(self, points, parent: int = -1, bad: bool = False) -> int:
         t = _i32(points)
         slot = C.c_int32(-1)
         self._call("dsh_mpdb_add_keyframe", t.shape[0], _ptr(t, C.c_int32), int(parent), 1 if bad else 0, C.byref(slot))
+        self._kf_n.append(t.shape[0])
         return int(slot.value)
 
     def set_keyframe_point(self, slot: int, idx: int, point_id: int):
@@ -408,3 +456,31 @@ class MapPointStore:
         cc = _lib.TemplateSwitchCountsC()
         self._call("dsh_template_switch", C.byref(inp), _ptr(idx, C.c_int32), C.byref(cc))
         return TemplateSwitch(new_idx=idx[:cc.n_new].copy(), **{n: int(getattr(cc, n)) for n, _ in _lib.TemplateSwitchCountsC._fields_})
+
+    # ---- the mapping thread: anchors of a new keyframe ----
+    def keyframe_anchors(self, slot: int, min_pairs: int = 20, max_matrix_bytes: int = 0) -> KeyframeAnchors:
+        """What SchwarpDatabase::add reads of the map for the new keyframe `slot`.  Every live observation must carry its key point
+        index (add_observations(..., idx=...)).  max_matrix_bytes bounds the device's anchors x N matrix (0: the library's default)."""
+        N = self._kf_n[slot] if 0 <= int(slot) < len(self._kf_n) else 0
+        ca, cp, cq = max(self.n_keyframes, 1), 4 * max(N, 1), 16 * max(N, 1)
+        has = np.zeros(max(N, 1), np.uint8)
+        while True:
+            a = {n: np.zeros(ca, np.int32) for n in ("anchor_slot", "anchor_count", "anchor_pairs")}
+            a.update({n: np.zeros(ca + 1, np.int32) for n in ("pair_ptr", "query_ptr")})
+            a.update({n: np.zeros(max(cp, 1), np.int32) for n in ("pair_idx1", "pair_idx2", "pair_point")})
+            a.update({n: np.zeros(max(cq, 1), np.int32) for n in ("query_idx1", "query_point")})
+            own = np.zeros(max(cp, 1), np.uint8)
+            r = _lib.AnchorListsC(anchor_capacity=ca, pair_capacity=cp, query_capacity=cq, max_matrix_bytes=int(max_matrix_bytes),
+                                  pair_own=_ptr(own, C.c_uint8), has=_ptr(has, C.c_uint8), **{n: _ptr(v, C.c_int32) for n, v in a.items()})
+            rc = self._ctx._L.dsh_keyframe_anchors(self._h, int(slot), int(min_pairs), C.byref(r))
+            if rc == _lib.DSH_ERR_ARG and (r.n_anchors > ca or r.n_pairs > cp or r.n_queries > cq):   # a list did not fit: the needed sizes came back
+                ca, cp, cq = max(ca, r.n_anchors), max(cp, r.n_pairs), max(cq, r.n_queries)
+                continue
+            self._ctx._check(rc, "dsh_keyframe_anchors")
+            break
+        A, npair, nq = r.n_anchors, r.n_pairs, r.n_queries
+        return KeyframeAnchors(anchor_slot=a["anchor_slot"][:A], anchor_count=a["anchor_count"][:A], anchor_pairs=a["anchor_pairs"][:A],
+                               pair_ptr=a["pair_ptr"][:A + 1], pair_idx1=a["pair_idx1"][:npair], pair_idx2=a["pair_idx2"][:npair],
+                               pair_point=a["pair_point"][:npair], pair_own=own[:npair].astype(bool), query_ptr=a["query_ptr"][:A + 1],
+                               query_idx1=a["query_idx1"][:nq], query_point=a["query_point"][:nq], has=has[:N].astype(bool),
+                               n_no_ref=int(r.n_no_ref))

@@ -566,7 +566,9 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
  *   points      id 0, 1, 2 ... in creation order: mWorldPos (float32), the normal, mfMaxDistance, the 32-byte descriptor, the bad flag
  *   observations  MapPoint::mObservations, the point-side relation, as an append-only log of (point id, keyframe slot) records; an
  *               erased record is blanked in place.  A host mirror finds a pair's record and refuses a pair that is already there
- *               (MapPoint::AddObservation, MapPoint.cc:88-91).  The key point index of an observation is not read here and not stored
+ *               (MapPoint::AddObservation, MapPoint.cc:88-91).  Beside the log lies the key point index of each observation in its
+ *               keyframe (dsh_point_store_add_observations_indexed; -1 for a record added without one), and per point its reference
+ *               keyframe mpRefKF as a slot (dsh_point_store_set_reference_keyframes; -1: not given).  The tracking entries read neither
  *   keyframes   slot 0, 1, 2 ... in insertion order -- add keyframes to dsh_kfdb and to this store in the same order and the numbers
  *               agree: N, the keyframe-side table mvpMapPoints (a point id or -1 per key point), the parent in the spanning tree (a
  *               slot or -1, KeyFrame::GetParent; the children of a keyframe are the slots whose parent it is) and the bad flag
@@ -609,6 +611,14 @@ int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8
  * DSH_ERR_ARG; erasing a pair that is not stored changes nothing, like the reference. */
 int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots);
 int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots);
+/* dsh_mpdb_add_observations with the key point index of each observation, mObservations[pKF] = idx (MapPoint.cc:88-91): in addition
+ * 0 <= idx[i] < N of keyframe keyframe_slots[i], else DSH_ERR_ARG and nothing is stored.  A record added by the call without indices
+ * has none; the store counts its live records without an index, and erasing one takes it out of that count (dsh_keyframe_anchors). */
+int dsh_point_store_add_observations_indexed(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots, const int32_t* idx);
+/* MapPoint::GetReferenceKeyFrame of the n distinct points ids[n]: slots[n], each a slot of the store or -1 (not given, the state of a
+ * point after dsh_mpdb_add_points).  The points dsh_template_switch creates have the switch's keyframe.  The read-back writes slots_out[n]. */
+int dsh_point_store_set_reference_keyframes(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* slots);
+int dsh_point_store_get_reference_keyframes(dsh_mpdb* db, int n, const int32_t* ids, int32_t* slots_out);
 /* A keyframe with its table points[N] (ids or -1) and its parent (an existing slot or -1); *slot (may be NULL) = its slot. */
 int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_t parent, int32_t bad, int32_t* slot);
 /* KeyFrame::AddMapPoint / EraseMapPointMatch: table entry idx of the keyframe becomes point_id (or -1). */
@@ -859,9 +869,9 @@ typedef struct dsh_template_switch_input {
  * Transfers: up go the key points, the surface points, Twc, the keyframe's octaves and scale factors and the template, in one block;
  * down come the counts and new_idx.  Nothing per map point travels.  Three launches: classification with the mask, creation with the
  * prefix sum of the ids, embedding with the repose.
- * NOT COVERED: Repose's UpdateNormalAndDepth of the embedded points (the store keeps neither the key point index of an observation nor
- * mpRefKF: the caller runs dsh_mappoint_update with DSH_MP_NORMAL_DEPTH and dsh_mpdb_update_points as before, reading positions with
- * dsh_trackstate_get); selectKeyframe (it iterates an unordered_map, its tie order is unspecified); DefKeyFrame::assignTemplate, the
+ * NOT COVERED: Repose's UpdateNormalAndDepth of the embedded points (the store now keeps the key point index of an observation and
+ * mpRefKF, and the new points get both here, but no entry point runs that upkeep on the store yet: the caller runs dsh_mappoint_update
+ * with DSH_MP_NORMAL_DEPTH and dsh_mpdb_update_points as before, reading positions with dsh_trackstate_get); selectKeyframe (it iterates an unordered_map, its tie order is unspecified); DefKeyFrame::assignTemplate, the
  * textures and lastincorporasion (host bookkeeping); the template constants (dsh_template_build). */
 int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32_t* new_idx, dsh_template_switch_counts* out);
 
@@ -869,6 +879,52 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
 int dsh_point_store_get_points(dsh_mpdb* db, int n, const int32_t* ids, float* xyz, float* normal, float* max_distance, uint8_t* desc, uint8_t* bad);
 /* Read back the facets of n distinct points; each output may be NULL: nodes[n x 3] (-1 -1 -1: none), bary[n x 3]. */
 int dsh_point_store_get_embedding(dsh_mpdb* db, int n, const int32_t* ids, int32_t* nodes, double* bary);
+
+/* ---- mapping: the anchor keyframes and match lists of a new keyframe from the resident map point store --------------------------
+ * What SchwarpDatabase::add (Modules/Mapping/SchwarpDatabase.cc:50-128) reads of the map before its first fit, for the new keyframe
+ * `slot` of the store, and what DefORBmatcher::searchBySchwarp (Modules/Matching/DefORBmatcher.cc:200-211) lists per anchor.  The
+ * stages behind it are on the device already (dsh_warp_initialize, dsh_search_by_schwarp, dsh_schwarp_fit_batch_store,
+ * dsh_normals_estimate_db).  Integer valued: every output is exact.  ORDER: the reference iterates an unordered_map<KeyFrame*, int>
+ * there, whose order is unspecified; here index order stands for pointer and hash order: anchors by ascending slot.
+ *   COUNTS (:61-80).  For each entry i of the keyframe's table, p = table[i]: skipped when p is -1 or bad; counted in n_no_ref and
+ *     skipped when p has no reference keyframe; else count[ref[p]]++.  A point held by k entries counts k times (vpMapPointMatches is
+ *     walked per entry).  The anchors are the keyframes with count > 0, by ascending slot: anchor_slot[a], anchor_count[a].
+ *   PAIRS (:83-106).  For every anchor a, for i ascending, an entry emits a pair when its point p is not bad, the log holds a live
+ *     record (p, slot) and the log holds a live record (p, anchor a): pair_idx1 = the key point index of (p, a), pair_idx2 = that of
+ *     (p, slot) -- from the record, not from i: a table entry whose point does not observe the keyframe yet (the state between
+ *     CreateNewKeyFrame and ProcessNewKeyFrame) emits nothing -- and pair_point = p.  ref[p] == a is NOT required: the reference takes
+ *     every shared point for the fit and only stores the records of the anchor's own points (:294-298); pair_own = 1 where
+ *     ref[p] == a, which is the point_id >= 0 test of dsh_schwarp_store.  a == slot is legal and literal: idx1 == idx2.
+ *     anchor_pairs[a] = the pairs of anchor a.  An anchor with fewer than min_pairs (the reference's 20, :105) keeps its place in the
+ *     anchor list and contributes nothing to the lists: pairs of anchor a are pair_ptr[a] .. pair_ptr[a + 1] - 1.
+ *   QUERIES (DefORBmatcher.cc:200-211).  For every anchor that passed min_pairs, the entries j of the ANCHOR's table, ascending, whose
+ *     point is not -1, not bad and has no live record with `slot`: query_idx1 = j, query_point = the point, at query_ptr[a] ..
+ *     query_ptr[a + 1] - 1.  has[j] = table[j] != -1 per entry of the NEW keyframe's table is the `has` of dsh_search_by_schwarp.
+ * The key point coordinates stay with the caller, who indexes its own arrays with idx1, idx2.
+ * Refusals, by the store's rules: arguments are checked on the host first (DSH_ERR_ARG, nothing written); while the store holds a live
+ * observation record without a key point index the call returns DSH_ERR_STATE, decided by the host mirror before any launch; a
+ * host-only context then answers DSH_ERR_NO_DEVICE.  The keyframe has at most 8192 key points; the number of anchors is not capped
+ * below the store's keyframe count.  CAPACITIES are passed in; when a list does not fit the call returns DSH_ERR_ARG with n_anchors,
+ * n_pairs, n_queries set to what is needed, and no array of the caller is written (every other refusal leaves them 0).
+ * Nothing goes up (the inputs travel as kernel arguments) and one block comes down; no host round trip between the launches; the
+ * temporaries come from the context's scratch.  The matrix of key point indices, anchors x N int32, takes at most max_matrix_bytes
+ * (0: 64 MiB); beyond that the anchors are processed in chunks, one more pass over the log per chunk, with the same result. */
+typedef struct dsh_anchor_lists {
+  /* in */
+  int32_t anchor_capacity;          /* entries of anchor_slot, anchor_count, anchor_pairs; pair_ptr and query_ptr have one more */
+  int32_t pair_capacity;            /* entries of pair_idx1, pair_idx2, pair_point, pair_own */
+  int32_t query_capacity;           /* entries of query_idx1, query_point */
+  int64_t max_matrix_bytes;         /* 0: the default */
+  int32_t *anchor_slot, *anchor_count, *anchor_pairs;
+  int32_t *pair_ptr, *pair_idx1, *pair_idx2, *pair_point;
+  uint8_t* pair_own;
+  int32_t *query_ptr, *query_idx1, *query_point;
+  uint8_t* has;                     /* N of the keyframe; may be NULL */
+  /* out */
+  int32_t n_anchors, n_pairs, n_queries;
+  int32_t n_no_ref;                 /* entries whose point is not bad and has no reference keyframe */
+} dsh_anchor_lists;
+int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anchor_lists* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

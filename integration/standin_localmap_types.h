@@ -1,5 +1,5 @@
 // Stand-ins of the members of ORB_SLAM2::KeyFrame, ORB_SLAM2::MapPoint (with defSLAM::DefMapPoint's) and ORB_SLAM2::Frame that
-// integration/local_map_hip.h and integration/track_close_hip.h touch
+// integration/local_map_hip.h, integration/track_close_hip.h and integration/anchor_pairs_hip.h touch
 // (reference declaration behind each), for the repository's CI: OpenCV is not in the build image.  Inside DefSLAM these are not used.
 #pragma once
 #include <cstddef>
@@ -72,6 +72,15 @@ class LmMapPoint {                             // Thirdparty/ORBSLAM_2/include/M
   void SetCoordinates(double a, double b, double c) { b1 = a; b2 = b; b3 = c; }   // DefMapPoint.h:80
   float mfMinDistance = 0.f;                                            // MapPoint.h:151
   LmKeyFrame* mpRefKF = nullptr;                                        // MapPoint.h:141
+  // what SchwarpDatabase::add and DefORBmatcher::searchBySchwarp touch (anchor_pairs_hip.h)
+  LmKeyFrame* GetReferenceKeyFrame() { return mpRefKF; }                // MapPoint.h:52
+  bool IsInKeyFrame(LmKeyFrame* kf) { return mObservations.count(kf) != 0; }   // :59
+  int GetIndexInKeyFrame(LmKeyFrame* kf) {                              // :58
+    return mObservations.count(kf) ? (int)mObservations[kf] : -1;
+  }
+  void EraseObservation(LmKeyFrame* kf) {                               // :58 (MapPoint.cc:99-133, without the bad-flag rule)
+    if (mObservations.erase(kf)) nObs--;
+  }
 };
 
 class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/KeyFrame.h
@@ -88,6 +97,8 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
   bool bad = false;
   // what DefLocalMapping::updateTemplate reads of the reference keyframe (template_switch_hip.h, mappoint_upkeep_hip.h)
   void addMapPoint(LmMapPoint* p, size_t idx) { mvpMapPoints[idx] = p; }    // :86 AddMapPoint
+  LmMapPoint* GetMapPoint(size_t idx) { return mvpMapPoints[idx]; }         // :90
+  void EraseMapPointMatch(size_t idx) { mvpMapPoints[idx] = nullptr; }      // :87
   int N = 0;                                                            // :149
   std::vector<KeyPoint> mvKeysUn;                                       // :163
   std::vector<uint8_t> mDescriptors;                                    // :171 N rows of 32 bytes (cv::Mat CV_8U)
