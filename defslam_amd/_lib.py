@@ -155,6 +155,28 @@ class AnchorListsC(C.Structure):
                 [(n, C.c_int32) for n in ("n_anchors", "n_pairs", "n_queries", "n_no_ref")])
 
 
+DSH_MP_NO_REF = 4
+DSH_MP_SKIPPED_BAD = 8
+DSH_UPKEEP_IDS = 0
+DSH_UPKEEP_EMBEDDED = 1
+
+
+class KeyframeProcessInputC(C.Structure):
+    _fields_ = [("kfdb", C.c_void_p), ("slot", C.c_int32)]
+
+
+class KeyframeProcessCountsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_empty", "n_bad", "n_added", "n_recent", "n_no_good_desc", "n_no_ref")] + [("first_record", C.c_int64)]
+
+
+class PointUpkeepInputC(C.Structure):
+    _fields_ = [("kfdb", C.c_void_p), ("what", C.c_int32), ("select", C.c_int32), ("n", C.c_int32), ("ids", c_i32_p)]
+
+
+class PointUpkeepCountsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_selected", "n_no_obs", "n_no_good_desc", "n_no_ref", "n_bad")]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -182,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "dsh_track_end_frame", "dsh_track_last_frame", "dsh_motion_model_search",
     "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
     "dsh_point_store_add_observations_indexed", "dsh_point_store_set_reference_keyframes", "dsh_point_store_get_reference_keyframes", "dsh_keyframe_anchors",
+    "dsh_keyframe_process_new", "dsh_point_store_upkeep",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -324,6 +347,8 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_point_store_set_reference_keyframes.argtypes = [vp, C.c_int, c_i32_p, c_i32_p]
     L.dsh_point_store_get_reference_keyframes.argtypes = [vp, C.c_int, c_i32_p, c_i32_p]
     L.dsh_keyframe_anchors.argtypes = [vp, i32, i32, C.POINTER(AnchorListsC)]
+    L.dsh_keyframe_process_new.argtypes = [vp, C.POINTER(KeyframeProcessInputC), c_u8_p, c_i32_p, C.POINTER(KeyframeProcessCountsC)]
+    L.dsh_point_store_upkeep.argtypes = [vp, C.POINTER(PointUpkeepInputC), c_i32_p, C.POINTER(PointUpkeepCountsC)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

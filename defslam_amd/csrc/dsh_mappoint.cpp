@@ -1,4 +1,5 @@
-// Host side of the map point upkeep (include/defslam_hip.h: dsh_kfdb_*, dsh_mappoint_update): the keyframe store in HBM, validation,
+// Host side of the map point upkeep (include/defslam_hip.h: dsh_kfdb_*, dsh_mappoint_update): the keyframe store in HBM (descriptor rows
+// and camera centres, and beside them the octaves and scale pyramids that the upkeep on the stores reads: dsh_kfinsert.cpp), validation,
 // one packed upload, the launches of mappoint_kernels.hip, one download.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,11 @@ namespace {
 
 int width_class(int M) { return M <= 8 ? 0 : M <= 16 ? 1 : M <= 32 ? 2 : 3; }
 
+void free_arrays(dsh_kfdb* db) {
+  for (void* p : {(void*)db->d_slots, (void*)db->d_rows, (void*)db->d_oct, (void*)db->d_levels, (void*)db->d_sf})
+    if (p) (void)hipFree(p);
+}
+
 }  // namespace
 
 extern "C" {
@@ -30,8 +36,10 @@ int dsh_kfdb_create(dsh_ctx* ctx, int32_t capacity, dsh_kfdb** out) {
   dsh_kfdb* db = new dsh_kfdb();
   db->row_cap = (long long)capacity * 1024;
   if (hipMalloc((void**)&db->d_slots, sizeof(MpuSlot) * (size_t)capacity) != hipSuccess ||
-      hipMalloc((void**)&db->d_rows, 32 * (size_t)db->row_cap) != hipSuccess) {
-    if (db->d_slots) (void)hipFree(db->d_slots);
+      hipMalloc((void**)&db->d_rows, 32 * (size_t)db->row_cap) != hipSuccess || hipMalloc((void**)&db->d_oct, (size_t)db->row_cap) != hipSuccess ||
+      hipMalloc((void**)&db->d_levels, 4 * (size_t)capacity) != hipSuccess ||
+      hipMalloc((void**)&db->d_sf, 4 * MPU_MAX_LEVELS * (size_t)capacity) != hipSuccess) {
+    free_arrays(db);
     delete db;
     return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_create: out of device memory");
   }
@@ -44,8 +52,7 @@ int dsh_kfdb_create(dsh_ctx* ctx, int32_t capacity, dsh_kfdb** out) {
 int dsh_kfdb_destroy(dsh_kfdb* db) {
   if (!db) return DSH_ERR_ARG;
   dsh_store_unregister(db);
-  if (db->d_slots) (void)hipFree(db->d_slots);
-  if (db->d_rows) (void)hipFree(db->d_rows);
+  free_arrays(db);
   delete db;
   return DSH_OK;
 }
@@ -54,6 +61,7 @@ int dsh_kfdb_clear(dsh_kfdb* db) {
   DSH_STORE_ENTER("dsh_kfdb_clear");
   db->count = 0;
   db->rows = 0;
+  db->n_octave_over = 0;
   db->kf.clear();
   return DSH_OK;
 }
@@ -81,31 +89,42 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
   if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: hipSetDevice failed");
   if (db->count + 1 > db->cap) {
     const int32_t ncap = (int32_t)std::min<long long>(2ll * db->cap, INT32_MAX);
-    if (dsh_store_grow_array(&db->d_slots, (size_t)db->count, (size_t)ncap) != hipSuccess)
+    if (dsh_store_grow_array(&db->d_slots, (size_t)db->count, (size_t)ncap) != hipSuccess ||
+        dsh_store_grow_array(&db->d_levels, (size_t)db->count, (size_t)ncap) != hipSuccess ||
+        dsh_store_grow_array(&db->d_sf, MPU_MAX_LEVELS * (size_t)db->count, MPU_MAX_LEVELS * (size_t)ncap) != hipSuccess)
       return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
     db->cap = ncap;
   }
   if (db->rows + kf->N > db->row_cap) {
     const long long ncap = std::max(db->rows + kf->N, 2 * db->row_cap);
-    if (dsh_store_grow_array(&db->d_rows, 2 * (size_t)db->rows, 2 * (size_t)ncap) != hipSuccess)
+    if (dsh_store_grow_array(&db->d_rows, 2 * (size_t)db->rows, 2 * (size_t)ncap) != hipSuccess ||
+        dsh_store_grow_array(&db->d_oct, (size_t)db->rows, (size_t)ncap) != hipSuccess)
       return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
     db->row_cap = ncap;
   }
-  MpuSlot s;
-  s.Ow[0] = kf->Ow[0]; s.Ow[1] = kf->Ow[1]; s.Ow[2] = kf->Ow[2];
-  s.row_off = (int32_t)db->rows;
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(db->d_slots + db->count, &s, sizeof(s), hipMemcpyHostToDevice, st));
-  if (kf->N > 0) HIPCHK(c, hipMemcpyAsync(db->d_rows + 2 * db->rows, kf->desc, 32 * (size_t)kf->N, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipStreamSynchronize(st));
   dsh_kfdb::Kf h;
   h.row_off = db->rows;
   h.N = kf->N;
   h.levels = kf->levels;
   h.bad = kf->bad ? 1 : 0;
+  h.octave_over = false;
   std::memset(h.sf, 0, sizeof(h.sf));
   for (int l = 0; l < kf->levels; l++) h.sf[l] = kf->scale_factors[l];
   h.octave.assign(kf->octave, kf->octave + kf->N);
+  for (const int8_t o : h.octave) h.octave_over = h.octave_over || o >= kf->levels;
+  MpuSlot s;
+  s.Ow[0] = kf->Ow[0]; s.Ow[1] = kf->Ow[1]; s.Ow[2] = kf->Ow[2];
+  s.row_off = (int32_t)db->rows;
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(db->d_slots + db->count, &s, sizeof(s), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(db->d_levels + db->count, &h.levels, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(db->d_sf + MPU_MAX_LEVELS * (size_t)db->count, h.sf, sizeof(h.sf), hipMemcpyHostToDevice, st));
+  if (kf->N > 0) {
+    HIPCHK(c, hipMemcpyAsync(db->d_rows + 2 * db->rows, kf->desc, 32 * (size_t)kf->N, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(db->d_oct + db->rows, h.octave.data(), (size_t)kf->N, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  db->n_octave_over += h.octave_over ? 1 : 0;
   db->kf.push_back(std::move(h));
   if (slot) *slot = db->count;
   db->count++;

@@ -19,11 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ int hamming(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-         __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // mNormalVector = normal / n (MapPoint.cc:389) and the depth range (:379-388), written by one lane
 __device__ __forceinline__ void write_geometry(const MpuBufs& b, const MpuPoint& pt, int p, float sx, float sy, float sz) {
   float mx, mn;
@@ -54,33 +49,7 @@ __global__ __launch_bounds__(256) void mpu_small_kernel(MpuBufs b, int off, int 
   sd[2 * t + 1] = d1;
   __syncthreads();
   if (elect) {
-    // row r of D as 16-bit distances; columns past Me hold 511, above every value the bisection tests
-    uint32_t dd[W / 2];
-    const uint4* gd = sd + 2 * (t - r);
-#pragma unroll
-    for (int j = 0; j < W; j += 2) {
-      const int a = j < pt.Me ? hamming(d0, d1, gd[2 * j], gd[2 * j + 1]) : 511;
-      const int c = j + 1 < pt.Me ? hamming(d0, d1, gd[2 * j + 2], gd[2 * j + 3]) : 511;
-      dd[j / 2] = (uint32_t)a | ((uint32_t)c << 16);
-    }
-    // the smallest v with #{j : D[r][j] <= v} > floor((Me-1)/2): sorted(row)[(size_t)(0.5 * (Me - 1))] (MapPoint.cc:311-313)
-    const int kth = (pt.Me - 1) / 2;
-    int lo = 0, hi = 256;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      int cnt = 0;
-#pragma unroll
-      for (int j = 0; j < W / 2; j++) cnt += (int)((dd[j] & 0xFFFF) <= (uint32_t)mid) + (int)((dd[j] >> 16) <= (uint32_t)mid);
-      if (cnt > kth) hi = mid;
-      else lo = mid + 1;
-    }
-    uint32_t key = r < pt.Me ? ((uint32_t)lo << 16) | (uint32_t)r : 0xFFFFFFFFu;
-    // the first row with a strictly smaller median (MapPoint.cc:315-319): the (median, row) minimum of the group
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-      const uint32_t other = (uint32_t)__shfl_xor((int)key, o, 64);
-      key = other < key ? other : key;
-    }
+    const uint32_t key = mp_elect_small<W>(d0, d1, sd + 2 * (t - r), pt.Me, r);
     if (r == 0) {
       const int e = (int)(key & 0xFFFF);
       b.best[p] = e;
@@ -91,16 +60,8 @@ __global__ __launch_bounds__(256) void mpu_small_kernel(MpuBufs b, int off, int 
   // the normal: lane r forms the term of observation r, every lane of the group sums the group's terms in observation order
   float tx = 0.f, ty = 0.f, tz = 0.f;
   if (geom && r < pt.M) normal_term(b.slots[b.obs_slot[pt.obs_off + r]], pt.x, pt.y, pt.z, tx, ty, tz);
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-#pragma unroll
-  for (int j = 0; j < W; j++) {
-    const float ux = __shfl(tx, gbase + j, 64), uy = __shfl(ty, gbase + j, 64), uz = __shfl(tz, gbase + j, 64);
-    if (j < pt.M) {
-      sx = ux + sx;
-      sy = uy + sy;
-      sz = uz + sz;
-    }
-  }
+  float sx, sy, sz;
+  mp_normal_sum_small<W>(tx, ty, tz, gbase, pt.M, sx, sy, sz);
   if (geom && r == 0) write_geometry(b, pt, p, sx, sy, sz);
 }
 
@@ -112,51 +73,12 @@ __global__ __launch_bounds__(64) void mpu_large_kernel(MpuBufs b) {
   const MpuPoint pt = b.pts[p];
   if (row0 < 0) {
     // UpdateNormalAndDepth: 64 terms at a time, summed in observation order by every lane (the same value in each)
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int base = 0; base < pt.M; base += 64) {
-      float tx = 0.f, ty = 0.f, tz = 0.f;
-      if (base + lane < pt.M) normal_term(b.slots[b.obs_slot[pt.obs_off + base + lane]], pt.x, pt.y, pt.z, tx, ty, tz);
-      const int cnt = min(64, pt.M - base);
-      for (int l = 0; l < cnt; l++) {
-        sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tx), l)) + sx;
-        sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ty), l)) + sy;
-        sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tz), l)) + sz;
-      }
-    }
+    float sx, sy, sz;
+    mp_normal_sum_large(b.slots, b.obs_slot, pt.obs_off, pt.M, pt.x, pt.y, pt.z, lane, sx, sy, sz);
     if (lane == 0) write_geometry(b, pt, p, sx, sy, sz);
     return;
   }
-  const int i = row0 + lane;
-  const bool valid = i < pt.Me;
-  uint32_t* h = hist + lane * MPU_HIST_WORDS;
-  for (int w = 0; w < MPU_HIST_WORDS; w++) h[w] = 0;
-  uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
-  if (valid) {
-    const int row = b.el_row[pt.el_off + i];
-    d0 = b.rows[2 * (size_t)row];
-    d1 = b.rows[2 * (size_t)row + 1];
-  }
-  // each lane's histogram is its own: plain read-modify-write, no atomics.  Counts <= Me <= 65535 fit their 16 bits.
-  for (int j = 0; j < pt.Me; j++) {
-    const int row = b.el_row[pt.el_off + j];
-    const int dist = hamming(d0, d1, b.rows[2 * (size_t)row], b.rows[2 * (size_t)row + 1]);
-    if (valid) h[dist >> 1] += 1u << ((dist & 1) << 4);
-  }
-  const int kth = (pt.Me - 1) / 2;
-  int med = 256, cum = 0;
-  for (int w = 0; w < MPU_HIST_WORDS; w++) {
-    const uint32_t v = h[w];
-    const int lo = (int)(v & 0xFFFF), hi = (int)(v >> 16);
-    if (cum + lo > kth) { med = 2 * w; break; }
-    cum += lo;
-    if (cum + hi > kth) { med = 2 * w + 1; break; }
-    cum += hi;
-  }
-  uint32_t key = valid ? ((uint32_t)med << 16) | (uint32_t)i : 0xFFFFFFFFu;
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t other = (uint32_t)__shfl_xor((int)key, o, 64);
-    key = other < key ? other : key;
-  }
+  const uint32_t key = mp_elect_block(b.rows, b.el_row, pt.el_off, pt.Me, row0, lane, hist);
   if (lane == 0) atomicMin(&b.large_key[p], key);
 }
 

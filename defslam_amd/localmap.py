@@ -12,7 +12,10 @@
     (dsh_template_switch, dsh_need_new_template): the occupancy mask, the new map points, the embedding in the new template;
   * what SchwarpDatabase::add (Modules/Mapping/SchwarpDatabase.cc:61-106) and DefORBmatcher::searchBySchwarp
     (Modules/Matching/DefORBmatcher.cc:200-211) read of the map for a new keyframe (dsh_keyframe_anchors): its anchor keyframes, the
-    matched key point indices and the search queries per anchor.
+    matched key point indices and the search queries per anchor;
+  * LocalMapping::ProcessNewKeyFrame's loop (Thirdparty/ORBSLAM_2/src/LocalMapping.cc:142-165) and the upkeep of DefMapPoint::Repose
+    (Modules/Common/DefMapPoint.cc:122-126) with the observation lists read from the store's log (dsh_keyframe_process_new,
+    dsh_point_store_upkeep): AddObservation, UpdateNormalAndDepth, ComputeDistinctiveDescriptors, results written into the store.
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -166,6 +169,38 @@ class KeyframeAnchors:
     def queries(self, a: int) -> np.ndarray:
         return self.query_idx1[self.query_ptr[a]:self.query_ptr[a + 1]]
 
+
+@dataclass
+class NewKeyframe:
+    """What dsh_keyframe_process_new returns (LocalMapping::ProcessNewKeyFrame's loop on the stores)."""
+    action: np.ndarray                  # (N,) KF_EMPTY, KF_BAD_POINT, KF_ADDED or KF_RECENT per table entry
+    added: np.ndarray                   # (n_added,) the points that got the observation and the upkeep, by ascending entry
+    n_empty: int
+    n_bad: int
+    n_added: int
+    n_recent: int                       # entries for the caller's mlpRecentAddedMapPoints
+    n_no_good_desc: int                 # added points whose observing keyframes are all bad: descriptor unchanged
+    n_no_ref: int                       # added points without a reference keyframe: normal and range unchanged
+    first_record: int                   # log position of the first record appended
+
+
+@dataclass
+class Upkeep:
+    """What dsh_point_store_upkeep returns."""
+    status: Optional[np.ndarray]        # (n,) UPKEEP_* flags per id; None for the embedded selection
+    n_selected: int                     # points the selection names that are not bad
+    n_no_obs: int
+    n_no_good_desc: int
+    n_no_ref: int
+    n_bad: int                          # ids that name a bad point
+
+
+# dsh_keyframe_process_new: what became of a table entry
+KF_EMPTY, KF_BAD_POINT, KF_ADDED, KF_RECENT = 0, 1, 2, 3
+# dsh_point_store_upkeep: the parts to update, and the status flags per point
+UPKEEP_DESCRIPTOR, UPKEEP_NORMAL_DEPTH, UPKEEP_BOTH = _lib.DSH_MP_DESCRIPTOR, _lib.DSH_MP_NORMAL_DEPTH, _lib.DSH_MP_DESCRIPTOR | _lib.DSH_MP_NORMAL_DEPTH
+UPKEEP_NO_OBS, UPKEEP_NO_GOOD_DESC, UPKEEP_NO_REF, UPKEEP_SKIPPED_BAD = (_lib.DSH_MP_NO_OBS, _lib.DSH_MP_NO_GOOD_DESC, _lib.DSH_MP_NO_REF,
+                                                                         _lib.DSH_MP_SKIPPED_BAD)
 
 # dsh_trackstate_cull: what became of an entry of mlpRecentAddedMapPoints
 CULL_STAYS, CULL_WAS_BAD, CULL_SET_BAD, CULL_OLD = 0, 1, 2, 3
@@ -484,3 +519,27 @@ class MapPointStore:
                                pair_point=a["pair_point"][:npair], pair_own=own[:npair].astype(bool), query_ptr=a["query_ptr"][:A + 1],
                                query_idx1=a["query_idx1"][:nq], query_point=a["query_point"][:nq], has=has[:N].astype(bool),
                                n_no_ref=int(r.n_no_ref))
+
+    # ---- the mapping thread: the map point upkeep of a new keyframe and of Repose ----
+    def process_new_keyframe(self, kf_store, slot: int) -> NewKeyframe:
+        """LocalMapping::ProcessNewKeyFrame's loop for keyframe `slot` (the same slot in kf_store, a mappoint.KeyFrameStore): every point
+        of its table that does not observe it yet gets the observation, then UpdateNormalAndDepth and ComputeDistinctiveDescriptors over
+        its observations by ascending slot, written into the store.  Every live observation must carry its key point index."""
+        N = self._kf_n[slot] if 0 <= int(slot) < len(self._kf_n) else 0
+        inp = _lib.KeyframeProcessInputC(kf_store._h if kf_store is not None else None, int(slot))
+        act, added = np.zeros(max(N, 1), np.uint8), np.full(max(N, 1), -1, np.int32)
+        cc = _lib.KeyframeProcessCountsC()
+        self._call("dsh_keyframe_process_new", C.byref(inp), _ptr(act, C.c_uint8), _ptr(added, C.c_int32), C.byref(cc))
+        return NewKeyframe(action=act[:N], added=added[:cc.n_added].copy(), **{n: int(getattr(cc, n)) for n, _ in _lib.KeyframeProcessCountsC._fields_})
+
+    def upkeep(self, kf_store, ids=None, what: int = UPKEEP_BOTH, embedded: bool = False) -> Upkeep:
+        """The map point upkeep on the store: the parts `what` names of the distinct points ids, or (embedded) of every point that is not
+        bad and has a facet -- DefMapPoint::Repose's UpdateNormalAndDepth after switch_template with what=UPKEEP_NORMAL_DEPTH."""
+        ids = np.zeros(0, np.int32) if ids is None else _i32(ids)
+        n = 0 if embedded else ids.shape[0]
+        inp = _lib.PointUpkeepInputC(kf_store._h if kf_store is not None else None, int(what),
+                                     _lib.DSH_UPKEEP_EMBEDDED if embedded else _lib.DSH_UPKEEP_IDS, n, _ptr(ids, C.c_int32))
+        st = np.zeros(max(n, 1), np.int32)
+        cc = _lib.PointUpkeepCountsC()
+        self._call("dsh_point_store_upkeep", C.byref(inp), _ptr(st, C.c_int32), C.byref(cc))
+        return Upkeep(status=None if embedded else st[:n], **{f: int(getattr(cc, f)) for f, _ in _lib.PointUpkeepCountsC._fields_})

@@ -496,7 +496,8 @@ int dsh_search_by_projection_local(dsh_ctx* ctx, const dsh_track_frame* frame, i
  * DefTracking::MonocularInitialization (DefTracking.cc:610-611: both) and DefMapPoint::Repose (DefMapPoint.cc:122-126, from
  * TriangularMesh.cc:192: normal and depth only).
  * dsh_kfdb keeps what these read of every keyframe resident in HBM: the descriptor rows, the octaves of mvKeysUn, the camera centre,
- * the scale pyramid and the bad flag.  A keyframe is copied up once, when it is added; keyframe poses do not change after insertion in
+ * the scale pyramid and the bad flag (descriptor rows, octaves, centre and pyramid on the device; the bad flag of this store stays on
+ * the host, where dsh_mappoint_update lists the election rows).  A keyframe is copied up once, when it is added; keyframe poses do not change after insertion in
  * DefSLAM (there is no keyframe bundle adjustment), so the store has no pose update.  Lifetime as dsh_diffdb: a store belongs to the
  * context it was created on; dsh_destroy of that context detaches it -- every call on it then returns DSH_ERR_ARG -- and
  * dsh_kfdb_destroy works before or after dsh_destroy. */
@@ -869,9 +870,9 @@ typedef struct dsh_template_switch_input {
  * Transfers: up go the key points, the surface points, Twc, the keyframe's octaves and scale factors and the template, in one block;
  * down come the counts and new_idx.  Nothing per map point travels.  Three launches: classification with the mask, creation with the
  * prefix sum of the ids, embedding with the repose.
- * NOT COVERED: Repose's UpdateNormalAndDepth of the embedded points (the store now keeps the key point index of an observation and
- * mpRefKF, and the new points get both here, but no entry point runs that upkeep on the store yet: the caller runs dsh_mappoint_update
- * with DSH_MP_NORMAL_DEPTH and dsh_mpdb_update_points as before, reading positions with dsh_trackstate_get); selectKeyframe (it iterates an unordered_map, its tie order is unspecified); DefKeyFrame::assignTemplate, the
+ * Repose's UpdateNormalAndDepth of the embedded points (DefMapPoint.cc:122-126) is the next call on the store: dsh_point_store_upkeep
+ * with DSH_UPKEEP_EMBEDDED and DSH_MP_NORMAL_DEPTH, below.
+ * NOT COVERED: selectKeyframe (it iterates an unordered_map, its tie order is unspecified); DefKeyFrame::assignTemplate, the
  * textures and lastincorporasion (host bookkeeping); the template constants (dsh_template_build). */
 int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32_t* new_idx, dsh_template_switch_counts* out);
 
@@ -925,6 +926,78 @@ typedef struct dsh_anchor_lists {
   int32_t n_no_ref;                 /* entries whose point is not bad and has no reference keyframe */
 } dsh_anchor_lists;
 int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anchor_lists* out);
+
+/* ---- mapping: a new keyframe's map point upkeep on the resident stores --------------------------------------------------------
+ * LocalMapping::ProcessNewKeyFrame's loop (Thirdparty/ORBSLAM_2/src/LocalMapping.cc:142-165, via DefLocalMapping.cc:160-164) and the
+ * upkeep of DefMapPoint::Repose (Modules/Common/DefMapPoint.cc:122-126, from TriangularMesh.cc:192) with every input on the device:
+ * the observation lists come from the point store's log, the key point indices from beside it, the reference keyframes from the
+ * points, the descriptor rows, camera centres, octaves and scale pyramids from the keyframe store, and the results go into the
+ * point store's descriptor, normal and max distance (dsh_point_store_get_points reads them; min = max / scale_factors[levels - 1] of
+ * the reference keyframe stays with the caller, as for dsh_template_switch).  Election, normal and depth are the arithmetic stated
+ * above dsh_mappoint_update, run by the same device functions.
+ * ORDER.  The observations of a point are taken by ascending slot, which stands for the pointer order of std::map<KeyFrame*, size_t>:
+ * the order of the float32 normal sum and of the election's ties.  It does not depend on the order in which the records arrived.
+ * BAD FLAGS.  The election skips the observations whose keyframe is bad in the POINT store (dsh_mpdb_set_keyframe_bad): that flag is
+ * resident, and it is the one the local map reads.  The flag of dsh_kfdb_set_bad is not read here; a caller keeps both current.
+ * The keyframe store travels in the input struct: it belongs to the same context, holds at least the keyframes of the point store,
+ * in the same order with the same N each, and at most DSH_MP_MAX_OBS of them; none of its keyframes may hold an octave >= levels.
+ * A point may have up to DSH_MP_MAX_OBS observations, but that limit is legal, not fast: one wavefront ranks a point's observations
+ * by slot with M wave-uniform loads per 64 observations (M^2 / 64 steps), measured up to M = 500 only; its cost near the limit is
+ * unmeasured.  A refused call writes nothing, the caller's counts included.
+ * Refusals, by the store's rules: arguments against the point store first, then the keyframe store, each DSH_ERR_ARG with nothing
+ * changed; a live observation record without a key point index is DSH_ERR_STATE, as for dsh_keyframe_anchors; a host-only context
+ * then answers DSH_ERR_NO_DEVICE.  All of it is decided on the host mirrors before any launch; no host read between the launches.
+ * Limits found on the device only: a reference keyframe that is not among the observations and has no key point 0 to lend its octave
+ * counts as no reference keyframe (dsh_mappoint_update refuses it). */
+#define DSH_MP_NO_REF 4        /* status: the point has no reference keyframe -- normal and range unchanged */
+#define DSH_MP_SKIPPED_BAD 8   /* status: the point is bad -- nothing changed */
+
+typedef struct dsh_keyframe_process_input {
+  dsh_kfdb* kfdb;                   /* of the same context; a keyframe has the same slot in both stores */
+  int32_t slot;                     /* the new keyframe */
+} dsh_keyframe_process_input;
+typedef struct dsh_keyframe_process_counts {
+  int32_t n_empty, n_bad, n_added, n_recent;        /* per table entry */
+  int32_t n_no_good_desc, n_no_ref;                 /* among the added points */
+  int64_t first_record;                             /* log position of the first record appended */
+} dsh_keyframe_process_counts;
+/* For table entry i of keyframe `slot` with point p, in the reference's order:
+ *   p == -1                                             action 0
+ *   p bad                                               action 1
+ *   no live record (p, slot), i the lowest entry with p action 2: the record (p, slot, i) is appended to the log, n_obs[p] += 1, and
+ *                                                       UpdateNormalAndDepth and ComputeDistinctiveDescriptors run over the point's
+ *                                                       observations, the new one included
+ *   otherwise                                           action 3, the caller's mlpRecentAddedMapPoints: the point observes the keyframe
+ *                                                       already, or an earlier entry has just added it; nothing changes for it
+ * Records are appended in ascending i; added_point[n_added] (N entries, may be NULL) holds their points in that order, action[N] (may
+ * be NULL) the actions.  An added point whose observing keyframes are all bad keeps its descriptor (n_no_good_desc); one without a
+ * reference keyframe keeps normal and range (n_no_ref).  Afterwards every call behaves as if the caller had added the pairs with
+ * dsh_point_store_add_observations_indexed.  Nothing goes up (the inputs travel as kernel arguments); one block comes down.
+ * DSH_ERR_HIP from this call can mean that the device appended records the host mirror does not know: the store is not usable
+ * afterwards and is to be cleared or destroyed (the other calls that append on the device, dsh_template_switch, share this). */
+int dsh_keyframe_process_new(dsh_mpdb* db, const dsh_keyframe_process_input* in, uint8_t* action, int32_t* added_point,
+                             dsh_keyframe_process_counts* out);
+
+#define DSH_UPKEEP_IDS 0       /* the n distinct points ids[n] */
+#define DSH_UPKEEP_EMBEDDED 1  /* every point that is not bad and has a facet (Repose after a switch); ids ignored */
+typedef struct dsh_point_upkeep_input {
+  dsh_kfdb* kfdb;
+  int32_t what;                     /* DSH_MP_DESCRIPTOR | DSH_MP_NORMAL_DEPTH */
+  int32_t select;                   /* DSH_UPKEEP_* */
+  int32_t n;
+  const int32_t* ids;
+} dsh_point_upkeep_input;
+typedef struct dsh_point_upkeep_counts {
+  int32_t n_selected;               /* points the selection names that are not bad */
+  int32_t n_no_obs, n_no_good_desc, n_no_ref;       /* among them */
+  int32_t n_bad;                    /* ids that name a bad point */
+} dsh_point_upkeep_counts;
+/* The `what` mask of dsh_mappoint_update applied to the selected points of the store.  status[n] (DSH_UPKEEP_IDS only, may be NULL)
+ * holds DSH_MP_* flags per id: a bad point is skipped (DSH_MP_SKIPPED_BAD alone); no live observation: DSH_MP_NO_OBS alone, nothing
+ * written; every observing keyframe bad: DSH_MP_NO_GOOD_DESC, descriptor unchanged, geometry still from all observations; no reference
+ * keyframe: DSH_MP_NO_REF, normal and range unchanged, descriptor still elected.  The two last flags are set whatever `what` asks.
+ * Up go the ids; one block comes down. */
+int dsh_point_store_upkeep(dsh_mpdb* db, const dsh_point_upkeep_input* in, int32_t* status, dsh_point_upkeep_counts* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
