@@ -177,6 +177,10 @@ class PointUpkeepCountsC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_selected", "n_no_obs", "n_no_good_desc", "n_no_ref", "n_bad")]
 
 
+class PointEraseCountsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_found", "n_ref_moved", "n_set_bad", "n_records", "n_entries")]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -205,6 +209,8 @@ EXPORTED_SYMBOLS = [
     "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
     "dsh_point_store_add_observations_indexed", "dsh_point_store_set_reference_keyframes", "dsh_point_store_get_reference_keyframes", "dsh_keyframe_anchors",
     "dsh_keyframe_process_new", "dsh_point_store_upkeep",
+    "dsh_point_store_erase_observations", "dsh_point_store_set_bad", "dsh_point_store_cull", "dsh_point_store_get_observations",
+    "dsh_point_store_get_keyframe_table",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -349,6 +355,11 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_keyframe_anchors.argtypes = [vp, i32, i32, C.POINTER(AnchorListsC)]
     L.dsh_keyframe_process_new.argtypes = [vp, C.POINTER(KeyframeProcessInputC), c_u8_p, c_i32_p, C.POINTER(KeyframeProcessCountsC)]
     L.dsh_point_store_upkeep.argtypes = [vp, C.POINTER(PointUpkeepInputC), c_i32_p, C.POINTER(PointUpkeepCountsC)]
+    L.dsh_point_store_erase_observations.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_u8_p, C.POINTER(PointEraseCountsC)]
+    L.dsh_point_store_set_bad.argtypes = [vp, C.c_int, c_i32_p, C.POINTER(PointEraseCountsC)]
+    L.dsh_point_store_cull.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_u8_p, C.POINTER(PointEraseCountsC)]
+    L.dsh_point_store_get_observations.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_i32_p, c_i32_p, c_i32_p]
+    L.dsh_point_store_get_keyframe_table.argtypes = [vp, i32, i32, c_i32_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

@@ -165,15 +165,8 @@ __global__ __launch_bounds__(TC_BLOCK) void tc_cull_kernel(TcState s, const int3
   const int i = blockIdx.x * TC_BLOCK + threadIdx.x;
   if (i >= n) return;
   const int p = ids[i];
-  uint8_t a = 0;
-  if (s.bad[p]) {
-    a = 1;                                                                       // :184
-  } else if (__fdiv_rn((float)s.found[p], (float)s.visible[p]) < 0.40f) {        // GetFoundRatio (MapPoint.cc:251-255), :188
-    a = 2;
-    s.bad[p] = 1;
-  } else if (current_kf - first_kf[i] >= 3) {                                    // :194
-    a = 3;
-  }
+  const uint8_t a = tc_cull_action(s.bad[p], s.found[p], s.visible[p], current_kf, first_kf[i]);
+  if (a == 2) s.bad[p] = 1;
   action[i] = a;
 }
 

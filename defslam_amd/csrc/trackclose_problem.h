@@ -32,6 +32,16 @@ struct TcClose {
   dsh_track_close_counts* counts;  // zero on entry
 };
 
+// LocalMapping::MapPointCulling's decision for one entry of mlpRecentAddedMapPoints (LocalMapping.cc:184-197), the first case that applies:
+// 1 already bad, 2 GetFoundRatio() < 0.40f (MapPoint.cc:251-255), 3 old enough to leave the list, 0 stays.  tc_cull_kernel and the
+// select stage of dsh_point_store_cull (pointerase_kernels.hip) share it.
+__device__ __forceinline__ uint8_t tc_cull_action(int bad, int found, int visible, int32_t current_kf, int32_t first_kf) {
+  if (bad) return 1;                                                         // :184
+  if (__fdiv_rn((float)found, (float)visible) < 0.40f) return 2;             // :188
+  if (current_kf - first_kf >= 3) return 3;                                  // :194
+  return 0;
+}
+
 // visible = found = 1, nobs = 0, no facet for the points first .. first + n - 1 (MapPoint.cc:38,58)
 extern "C" hipError_t tc_init_points_launch(const TcState& s, int first, int n, hipStream_t st);
 // dst[src[i * stride]] += delta for i < n; entries < 0 are skipped (nObs from the records of the observation log)

@@ -15,7 +15,10 @@
     matched key point indices and the search queries per anchor;
   * LocalMapping::ProcessNewKeyFrame's loop (Thirdparty/ORBSLAM_2/src/LocalMapping.cc:142-165) and the upkeep of DefMapPoint::Repose
     (Modules/Common/DefMapPoint.cc:122-126) with the observation lists read from the store's log (dsh_keyframe_process_new,
-    dsh_point_store_upkeep): AddObservation, UpdateNormalAndDepth, ComputeDistinctiveDescriptors, results written into the store.
+    dsh_point_store_upkeep): AddObservation, UpdateNormalAndDepth, ComputeDistinctiveDescriptors, results written into the store;
+  * MapPoint::EraseObservation (MapPoint.cc:122-148), DefMapPoint::setBadFlag (DefMapPoint.cc:76-94) and LocalMapping::MapPointCulling
+    (LocalMapping.cc:173-199) in full on the store's log and tables (dsh_point_store_erase_observations, dsh_point_store_set_bad,
+    dsh_point_store_cull), with the read-backs of a point's observations and a keyframe's table.
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -194,6 +197,46 @@ class Upkeep:
     n_no_ref: int
     n_bad: int                          # ids that name a bad point
 
+
+@dataclass
+class EraseCounts:
+    """dsh_point_erase_counts."""
+    n_found: int                        # pairs whose record was live (erase_observations_full only)
+    n_ref_moved: int                    # points whose reference keyframe changed
+    n_set_bad: int                      # points setBadFlag ran on
+    n_records: int                      # log records blanked, the pairs' own included
+    n_entries: int                      # table entries written to -1, once per record that names them
+
+
+@dataclass
+class ObservationErase:
+    """What dsh_point_store_erase_observations returns."""
+    status: np.ndarray                  # (n,) ERASE_NOT_STORED, ERASE_DONE or ERASE_SET_BAD per pair
+    counts: EraseCounts
+
+
+@dataclass
+class PointCull:
+    """What dsh_point_store_cull returns."""
+    action: np.ndarray                  # (n,) CULL_* per entry of mlpRecentAddedMapPoints
+    counts: EraseCounts
+
+
+@dataclass
+class PointObservations:
+    """What dsh_point_store_get_observations returns: MapPoint::GetObservations of the ids as a CSR by ascending slot."""
+    ptr: np.ndarray                     # (n+1,)
+    slots: np.ndarray                   # the observing keyframes
+    idx: np.ndarray                     # the key point index in each, -1: added without one
+
+    def of(self, i: int) -> dict:
+        """mObservations of the i-th id asked for: {slot: idx} in slot order."""
+        s = slice(self.ptr[i], self.ptr[i + 1])
+        return dict(zip(self.slots[s].tolist(), self.idx[s].tolist()))
+
+
+# dsh_point_store_erase_observations: what became of a pair
+ERASE_NOT_STORED, ERASE_DONE, ERASE_SET_BAD = 0, 1, 2
 
 # dsh_keyframe_process_new: what became of a table entry
 KF_EMPTY, KF_BAD_POINT, KF_ADDED, KF_RECENT = 0, 1, 2, 3
@@ -543,3 +586,54 @@ class MapPointStore:
         cc = _lib.PointUpkeepCountsC()
         self._call("dsh_point_store_upkeep", C.byref(inp), _ptr(st, C.c_int32), C.byref(cc))
         return Upkeep(status=None if embedded else st[:n], **{f: int(getattr(cc, f)) for f, _ in _lib.PointUpkeepCountsC._fields_})
+
+    # ---- the mapping thread: erasing observations and culling points ----
+    def _erase_counts(self, cc) -> EraseCounts:
+        return EraseCounts(**{f: int(getattr(cc, f)) for f, _ in _lib.PointEraseCountsC._fields_})
+
+    def erase_observations_full(self, points, slots, erase_match: bool = False) -> ObservationErase:
+        """MapPoint::EraseObservation of the pairs (distinct points): the record, nObs, the reference keyframe when it was the erased one,
+        and setBadFlag when nObs falls to 2; erase_match adds KeyFrame::EraseMapPointMatch of the record's key point (the Schwarp fit's drop)."""
+        p, k = _i32(points), _i32(slots)
+        st = np.zeros(max(p.shape[0], 1), np.uint8)
+        cc = _lib.PointEraseCountsC()
+        self._call("dsh_point_store_erase_observations", p.shape[0], _ptr(p, C.c_int32), _ptr(k, C.c_int32), 1 if erase_match else 0,
+                   _ptr(st, C.c_uint8), C.byref(cc))
+        return ObservationErase(status=st[:p.shape[0]], counts=self._erase_counts(cc))
+
+    def set_bad_full(self, ids) -> EraseCounts:
+        """DefMapPoint::setBadFlag of the distinct points: the flag, their observation records and the table entries those name."""
+        ids = _i32(ids)
+        cc = _lib.PointEraseCountsC()
+        self._call("dsh_point_store_set_bad", ids.shape[0], _ptr(ids, C.c_int32), C.byref(cc))
+        return self._erase_counts(cc)
+
+    def cull_full(self, ids, first_kf, current_kf: int) -> PointCull:
+        """LocalMapping::MapPointCulling over ids: cull()'s decisions, with setBadFlag in full for the CULL_SET_BAD points."""
+        ids, fk = _i32(ids), _i32(first_kf)
+        act = np.zeros(max(ids.shape[0], 1), np.uint8)
+        cc = _lib.PointEraseCountsC()
+        self._call("dsh_point_store_cull", ids.shape[0], _ptr(ids, C.c_int32), _ptr(fk, C.c_int32), int(current_kf), _ptr(act, C.c_uint8), C.byref(cc))
+        return PointCull(action=act[:ids.shape[0]], counts=self._erase_counts(cc))
+
+    def observations(self, ids=None) -> PointObservations:
+        """MapPoint::GetObservations of ids (None: every point of the store), by ascending slot."""
+        ids = np.arange(self.n_points, dtype=np.int32) if ids is None else _i32(ids)
+        n, cap = ids.shape[0], max(4 * ids.shape[0], 64)
+        while True:
+            ptr, sl, ix = np.zeros(n + 1, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+            total = C.c_int32(0)
+            rc = self._ctx._L.dsh_point_store_get_observations(self._h, n, _ptr(ids, C.c_int32), _ptr(ptr, C.c_int32), cap, _ptr(sl, C.c_int32),
+                                                               _ptr(ix, C.c_int32), C.byref(total))
+            if rc == _lib.DSH_ERR_ARG and total.value > cap:   # the lists did not fit: the needed size came back
+                cap = int(total.value)
+                continue
+            self._ctx._check(rc, "dsh_point_store_get_observations")
+            return PointObservations(ptr=ptr, slots=sl[:total.value].copy(), idx=ix[:total.value].copy())
+
+    def keyframe_table(self, slot: int) -> np.ndarray:
+        """KeyFrame::GetMapPointMatches of keyframe `slot` as ids or -1."""
+        N = self._kf_n[slot] if 0 <= int(slot) < len(self._kf_n) else 0
+        t = np.full(max(N, 1), -1, np.int32)
+        self._call("dsh_point_store_get_keyframe_table", int(slot), N, _ptr(t, C.c_int32))
+        return t[:N]

@@ -606,10 +606,12 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
  * the write-back of DefMapPoint::RecalculatePosition after the pose optimisation (dsh_sft_result.mappoint_xyz, DSH_MPDB_POSITION). */
 int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what, const float* xyz, const float* normal,
                            const float* max_distance, const uint8_t* desc);
-/* MapPoint::SetBadFlag of n distinct points; bad[n] may be NULL (all become bad). */
+/* MapPoint::SetBadFlag of n distinct points; bad[n] may be NULL (all become bad).  The flag alone: dsh_point_store_set_bad is setBadFlag
+ * in full, with the point's observation records and table entries. */
 int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8_t* bad);
 /* MapPoint::AddObservation / EraseObservation for n (point, keyframe) pairs.  Adding a pair that is stored, or twice in one batch, is
- * DSH_ERR_ARG; erasing a pair that is not stored changes nothing, like the reference. */
+ * DSH_ERR_ARG; erasing a pair that is not stored changes nothing, like the reference.  The erase blanks the record and decrements
+ * n_obs only: dsh_point_store_erase_observations also moves the reference keyframe and runs the n_obs <= 2 cascade. */
 int dsh_mpdb_add_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots);
 int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots);
 /* dsh_mpdb_add_observations with the key point index of each observation, mObservations[pKF] = idx (MapPoint.cc:88-91): in addition
@@ -702,7 +704,8 @@ int dsh_trackstate_repose(dsh_mpdb* db, int n_nodes, const double* node_xyz, int
  * current_kf = mpCurrentKeyFrame->mnId.  Per point, the first case that applies: action[n] = 1 already bad (leaves the list); 2
  * (float)found / (float)visible < 0.40f: the store sets the point's bad flag (leaves the list); 3 (int)current_kf - first_kf >= 3 (leaves
  * the list); 0 stays.  Setting bad is what dsh_mpdb_set_points_bad does: observation records, n_obs and table entries are untouched (bad
- * points neither vote nor become local points); KeyFrame::EraseMapPointMatch stays with the caller, who knows the index. */
+ * points neither vote nor become local points); KeyFrame::EraseMapPointMatch stays with the caller, who knows the index.
+ * dsh_point_store_cull takes the same decisions and erases the records and table entries of the action-2 points as well. */
 int dsh_trackstate_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* first_kf, int32_t current_kf, uint8_t* action);
 
 typedef struct dsh_track_close_counts {
@@ -998,6 +1001,70 @@ typedef struct dsh_point_upkeep_counts {
  * keyframe: DSH_MP_NO_REF, normal and range unchanged, descriptor still elected.  The two last flags are set whatever `what` asks.
  * Up go the ids; one block comes down. */
 int dsh_point_store_upkeep(dsh_mpdb* db, const dsh_point_upkeep_input* in, int32_t* status, dsh_point_upkeep_counts* out);
+
+/* ---- mapping: erasing observations and culling map points on the resident map point store --------------------------------------
+ * What takes a point out of the map, on dsh_mpdb's log, tables and per-point state:
+ *   MapPoint::EraseObservation       Thirdparty/ORBSLAM_2/src/MapPoint.cc:122-148
+ *   DefMapPoint::setBadFlag          Modules/Common/DefMapPoint.cc:76-94
+ *   KeyFrame::EraseMapPointMatch     Thirdparty/ORBSLAM_2/src/KeyFrame.cc:248-252
+ *   LocalMapping::MapPointCulling    Thirdparty/ORBSLAM_2/src/LocalMapping.cc:173-199
+ *   the Schwarp fit's drop           Modules/Mapping/SchwarpDatabase.cc:288-292
+ * Integer valued: every output is exact.  ORDER: slot order stands for pointer order, as everywhere in the library.
+ * A PAIR (p, s) THAT HAS A LIVE RECORD r (MapPoint.cc:127-143), in the reference's order:
+ *   - the record is blanked and n_obs[p] -= 1;
+ *   - with erase_match, table entry log_idx[r] of keyframe s becomes -1 WHATEVER THAT ENTRY HOLDS: EraseMapPointMatch(const size_t&)
+ *     does not look, and between CreateNewKeyFrame and ProcessNewKeyFrame the two relations disagree;
+ *   - if ref_kf[p] == s the reference keyframe becomes the lowest slot among the records of p that are still live (:137-138).  When none
+ *     is left it stays as it is: the reference dereferences end() there, the one place where it is undefined;
+ *   - if the decremented n_obs[p] <= 2, setBadFlag(p) (:141-147).  The reference keyframe moves BEFORE this cascade, so the move is
+ *     decided on the records the cascade then removes;
+ *   - status: 0 the pair is not stored, nothing changes, as in the reference; 1 erased; 2 erased and setBadFlag ran.
+ *   No bad test is made anywhere: a point that is already bad and still has records is treated like any other.
+ * setBadFlag OF p (DefMapPoint.cc:76-94): the bad flag is set, every live record of p is blanked, and for each such record the table
+ *   entry it names becomes -1, whatever it holds.  n_obs[p] is NOT touched -- the stale-nObs quirk stated for dsh_track_close_frame.
+ *   The reference keyframe, the embedding and the counters stay.  n_set_bad counts the points setBadFlag ran on, bad before or not.
+ * dsh_point_store_cull: the decision is dsh_trackstate_cull's, by the same device function -- (float)found / (float)visible < 0.40f and
+ *   the same order of cases.  Action 2 runs setBadFlag as above; action 1 (already bad) changes nothing, the records of such a point
+ *   stay if it still has any.
+ * BATCHES are order-free by construction: every table write is -1 and every log write is a blank, and a point's n_obs and reference
+ *   keyframe depend on its own records only.  The one sequential effect in the reference needs the same point twice in a batch (an
+ *   erase after the cascade finds nothing), so a repeated point is refused: DSH_ERR_ARG, "point id ... repeated in the batch".  The
+ *   fit's drops (one keyframe, distinct points) and the culling list (distinct points) never repeat a point.
+ * REFUSALS follow the store's rules.  Arguments are checked on the host first: ids or slots outside the store, NULL with n > 0,
+ *   out == NULL, a repeated point and too small a capacity give DSH_ERR_ARG with a message naming the entry, and nothing changes.  A
+ *   live record without a key point index gives DSH_ERR_STATE, as for dsh_keyframe_anchors, decided on the host mirror before any
+ *   launch; the two read-backs are exempt and report -1 as the index.  A host-only context then gives DSH_ERR_NO_DEVICE; a detached
+ *   store gives DSH_ERR_ARG.  A refused call leaves the caller's counts as they were.  The log may have any length: records are
+ *   addressed as 64-bit positions (dsh_mpdb_erase_observations refuses a log beyond 2^30 records).
+ * One upload and at most four launches per call -- clear, select, one sweep over the log that leaves at its first instruction when no
+ * point lost its reference keyframe or became bad, finish -- with no host read between them; one block comes down, and behind it the
+ * (point, slot) of the records the sweep erased, which the host mirror then drops: cost proportional to the records erased.
+ * DSH_ERR_HIP from these calls can mean that the device erased records the host mirror still knows: the store is not usable
+ * afterwards and is to be cleared or destroyed (the calls that append on the device, dsh_keyframe_process_new and
+ * dsh_template_switch, share this). */
+typedef struct dsh_point_erase_counts {
+  int32_t n_found;      /* pairs whose record was live (erase_observations); 0 for the other two calls */
+  int32_t n_ref_moved;  /* points whose reference keyframe changed */
+  int32_t n_set_bad;    /* points this call set bad */
+  int32_t n_records;    /* log records blanked, the pairs' own included */
+  int32_t n_entries;    /* table entries written to -1, counted once per record that names them */
+} dsh_point_erase_counts;
+
+/* MapPoint::EraseObservation (MapPoint.cc:122-148) for n pairs with DISTINCT points; erase_match != 0 adds
+ * KeyFrame::EraseMapPointMatch(idx) of the erased record's key point (SchwarpDatabase.cc:290-291).  status[n] may be NULL. */
+int dsh_point_store_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, const int32_t* keyframe_slots, int32_t erase_match,
+                                       uint8_t* status, dsh_point_erase_counts* out);
+/* DefMapPoint::setBadFlag (DefMapPoint.cc:76-94) of n distinct points. */
+int dsh_point_store_set_bad(dsh_mpdb* db, int n, const int32_t* ids, dsh_point_erase_counts* out);
+/* LocalMapping::MapPointCulling (LocalMapping.cc:173-199): dsh_trackstate_cull's arguments and actions, with action 2 doing setBadFlag in full. */
+int dsh_point_store_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* first_kf, int32_t current_kf, uint8_t* action,
+                         dsh_point_erase_counts* out);
+/* Read-backs: MapPoint::GetObservations of n distinct points as a CSR by ascending slot (obs_ptr[n + 1], slots / idx of `capacity`
+ * entries; when they do not fit: DSH_ERR_ARG with *n_total set and no array written), and KeyFrame::GetMapPointMatches: points[N] of
+ * keyframe `slot`, capacity >= N.  A record added without a key point index reports -1. */
+int dsh_point_store_get_observations(dsh_mpdb* db, int n, const int32_t* ids, int32_t* obs_ptr, int32_t capacity, int32_t* slots,
+                                     int32_t* idx, int32_t* n_total);
+int dsh_point_store_get_keyframe_table(dsh_mpdb* db, int32_t slot, int32_t capacity, int32_t* points);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -13,8 +13,9 @@
 //       library refuses (dsh_last_error of the store's context says why).
 //   DropMatchHIP(out, a_from, idx2)
 //       THE ONE SEQUENTIAL EFFECT between the anchors of a keyframe.  The lists are a snapshot taken before the first fit.  A fit that
-//       drops a match erases (point, KF2) and empties KF2's entry idx2 (SchwarpDatabase.cc:288-292; the caller does both on its
-//       objects and in the store), so for the anchors behind a_from the point is no longer in both keyframes: its pair leaves their
+//       drops a match erases (point, KF2) and empties KF2's entry idx2 (SchwarpDatabase.cc:288-292; DropMatchesStoreHIP of
+//       point_erase_hip.h does both on the objects and in the store, for all drops of a fit in one call), so for the anchors behind
+//       a_from the point is no longer in both keyframes: its pair leaves their
 //       vMatchedIndices, and where their table holds the point it becomes a query of their search (DefORBmatcher.cc:208).  This helper
 //       applies exactly that to the snapshot (an anchor that falls below min_pairs stops fitting; n_pairs of an anchor that did not fit
 //       in the snapshot stays the snapshot's: its pairs were not listed).  Matches that findbyWarp ADDS land on entries of KF2 that were empty in the snapshot and
