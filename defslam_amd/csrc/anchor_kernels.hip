@@ -14,7 +14,6 @@
 //   an_queries_kernel  a workgroup per anchor counts the queries of the anchor's table
 //   an_scan_kernel     ONE wavefront: min_pairs, the CSR offsets of pairs and queries, the counters
 //   an_write_kernel    a workgroup per anchor: ordered compaction of its matrix row into the pairs and of its table into the queries
-//                      (ballot per wavefront, the wavefronts' totals through LDS: mm_gather_kernel's pattern)
 // When max_anchors x N cells exceed the matrix the host allows, the anchors are taken `chunk` at a time: the matrix is cleared, filled by
 // one more pass over the log and written, per chunk; counts and offsets are complete before the first write, so the result does not
 // depend on the chunking.  Lists are written as far as the caller's capacities reach; the counters always come down in full.
@@ -22,10 +21,9 @@
 #include <hip/hip_runtime.h>
 
 #include "anchor_problem.h"
+#include "mpdb_device.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 __global__ __launch_bounds__(AN_BLOCK) void an_clear_kernel(AnBufs b) {
   const int i = blockIdx.x * AN_BLOCK + threadIdx.x;
@@ -145,21 +143,6 @@ __global__ __launch_bounds__(64) void an_scan_kernel(AnBufs b) {
   }
 }
 
-// the position of this thread's element among the taken ones of the workgroup's tile, behind `base`; base moves past the tile
-__device__ __forceinline__ int ordered_slot(bool take, int& base, int* wsum) {
-  const int wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(take);
-  __syncthreads();   // the previous tile's totals have been read
-  if ((threadIdx.x & 63) == 0) wsum[wave] = __popcll(m);
-  __syncthreads();
-  int pos = base + __popcll(m & lanes_below());
-  for (int w = 0; w < AN_BLOCK / 64; w++) {
-    if (w < wave) pos += wsum[w];
-    base += wsum[w];
-  }
-  return pos;
-}
-
 __global__ __launch_bounds__(AN_BLOCK) void an_write_kernel(AnBufs b, int c0) {
   __shared__ int wsum[AN_BLOCK / 64];
   const int a = c0 + blockIdx.x;
@@ -179,7 +162,7 @@ __global__ __launch_bounds__(AN_BLOCK) void an_write_kernel(AnBufs b, int c0) {
       }
     }
     const bool take = idx1 >= 0 && idx2 >= 0;
-    const int pos = ordered_slot(take, base, wsum);
+    const int pos = ordered_slot<AN_BLOCK>(take, base, wsum);
     if (take && pos < b.cap_pairs) {
       b.out_idx1[pos] = idx1;
       b.out_idx2[pos] = idx2;
@@ -194,7 +177,7 @@ __global__ __launch_bounds__(AN_BLOCK) void an_write_kernel(AnBufs b, int c0) {
     const int j = t0 + threadIdx.x;
     const int p = j < f.N ? b.table[f.tab_off + j] : -1;
     const bool take = is_query(b, p);
-    const int pos = ordered_slot(take, base, wsum);
+    const int pos = ordered_slot<AN_BLOCK>(take, base, wsum);
     if (take && pos < b.cap_queries) {
       b.out_qidx1[pos] = j;
       b.out_qpoint[pos] = p;
@@ -207,27 +190,19 @@ __global__ __launch_bounds__(AN_BLOCK) void an_gather_i32_kernel(const int32_t* 
   if (i < n) out[i] = src[ids[i]];
 }
 
-inline int blocks_for(long long n) { return (int)((n + AN_BLOCK - 1) / AN_BLOCK); }
-
-// eight records per thread, at most 1024 workgroups, as lm_votes_kernel
-inline int log_blocks(long long R) {
-  const long long g = (R + 8 * AN_BLOCK - 1) / (8 * AN_BLOCK);
-  return (int)(g > 1024 ? 1024 : g);
-}
-
 }  // namespace
 
 extern "C" hipError_t an_anchors_launch(const AnBufs& b, hipStream_t st) {
   const int top = b.P > b.K ? b.P : b.K;
-  hipLaunchKernelGGL(an_clear_kernel, dim3(blocks_for(top > b.max_anchors ? top : b.max_anchors)), dim3(AN_BLOCK), 0, st, b);
-  if (b.N > 0) hipLaunchKernelGGL(an_mark_kernel, dim3(blocks_for(b.N)), dim3(AN_BLOCK), 0, st, b);
-  if (b.R > 0) hipLaunchKernelGGL(an_idx2_kernel, dim3(log_blocks(b.R)), dim3(AN_BLOCK), 0, st, b);
+  hipLaunchKernelGGL(an_clear_kernel, dim3(blocks_for(top > b.max_anchors ? top : b.max_anchors, AN_BLOCK)), dim3(AN_BLOCK), 0, st, b);
+  if (b.N > 0) hipLaunchKernelGGL(an_mark_kernel, dim3(blocks_for(b.N, AN_BLOCK)), dim3(AN_BLOCK), 0, st, b);
+  if (b.R > 0) hipLaunchKernelGGL(an_idx2_kernel, dim3(log_blocks(b.R, AN_BLOCK)), dim3(AN_BLOCK), 0, st, b);
   hipLaunchKernelGGL(an_rank_kernel, dim3(1), dim3(64), 0, st, b);
   for (int c0 = 0; c0 < b.max_anchors; c0 += b.chunk) {
     const int rows = b.max_anchors - c0 < b.chunk ? b.max_anchors - c0 : b.chunk;
     const hipError_t e = hipMemsetAsync(b.matrix, 0xff, 4 * (size_t)rows * b.N, st);   // -1: the point does not observe the anchor
     if (e != hipSuccess) return e;
-    if (b.R > 0) hipLaunchKernelGGL(an_pairs_kernel, dim3(log_blocks(b.R)), dim3(AN_BLOCK), 0, st, b, c0, c0 == 0 ? 1 : 0);
+    if (b.R > 0) hipLaunchKernelGGL(an_pairs_kernel, dim3(log_blocks(b.R, AN_BLOCK)), dim3(AN_BLOCK), 0, st, b, c0, c0 == 0 ? 1 : 0);
     if (c0 == 0) {
       hipLaunchKernelGGL(an_queries_kernel, dim3(b.max_anchors), dim3(AN_BLOCK), 0, st, b);
       hipLaunchKernelGGL(an_scan_kernel, dim3(1), dim3(64), 0, st, b);
@@ -239,6 +214,6 @@ extern "C" hipError_t an_anchors_launch(const AnBufs& b, hipStream_t st) {
 }
 
 extern "C" hipError_t an_gather_i32_launch(const int32_t* src, const int32_t* ids, int n, int32_t* out, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(an_gather_i32_kernel, dim3(blocks_for(n)), dim3(AN_BLOCK), 0, st, src, ids, n, out);
+  if (n > 0) hipLaunchKernelGGL(an_gather_i32_kernel, dim3(blocks_for(n, AN_BLOCK)), dim3(AN_BLOCK), 0, st, src, ids, n, out);
   return hipGetLastError();
 }

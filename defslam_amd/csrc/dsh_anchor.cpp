@@ -76,10 +76,7 @@ int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anch
   if (out->anchor_capacity > 0 && (!out->anchor_slot || !out->anchor_count || !out->anchor_pairs)) return bad("an anchor array is NULL");
   if (out->pair_capacity > 0 && (!out->pair_idx1 || !out->pair_idx2 || !out->pair_point || !out->pair_own)) return bad("a pair array is NULL");
   if (out->query_capacity > 0 && (!out->query_idx1 || !out->query_point)) return bad("a query array is NULL");
-  if (!db->unindexed.empty())
-    return dsh_fail(c, DSH_ERR_STATE,
-                    "dsh_keyframe_anchors: the store holds " + std::to_string(db->unindexed.size()) +
-                        " live observation records without a key point index (dsh_mpdb_add_observations); add them with dsh_point_store_add_observations_indexed");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_keyframe_anchors");
   if (const int rc = dsh_enter(c, "dsh_keyframe_anchors")) return rc;
 
   // what the host knows of the sizes: an anchor takes a vote of an entry, a pair an entry per anchor, a query an entry of a table

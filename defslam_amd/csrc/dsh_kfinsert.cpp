@@ -29,30 +29,20 @@ std::string kfdb_error(const dsh_mpdb* db, const dsh_kfdb* kfdb) {
   return "";
 }
 
-int state_error(dsh_mpdb* db, const char* who) {
-  return dsh_fail(db->ctx, DSH_ERR_STATE,
-                  std::string(who) + ": the store holds " + std::to_string(db->unindexed.size()) +
-                      " live observation records without a key point index (dsh_mpdb_add_observations); add them with dsh_point_store_add_observations_indexed");
-}
-
 // the stores' arrays and the temporaries of a call that selects at most S points with at most cap_obs observations
 int fill_bufs(dsh_ctx_base* c, KiBufs& b, dsh_mpdb* db, const dsh_kfdb* kfdb, int32_t S, long long cap_obs) {
   std::memset(&b, 0, sizeof(b));
-  b.P = db->P; b.S = S; b.R = db->R;
-  b.xyz = db->d_xyz; b.bad = db->d_bad; b.ref_kf = db->d_ref_kf; b.nodes = db->d_nodes; b.nobs = db->d_nobs;
-  b.log = db->d_log; b.log_idx = db->d_log_idx; b.kf = db->d_kf; b.table = db->d_table;
+  b.P = db->P; b.S = S;
+  b.xyz = db->d_xyz; b.bad = db->d_bad; b.ref_kf = db->d_ref_kf; b.nodes = db->d_nodes; b.nobs = db->d_nobs; b.table = db->d_table;
   b.desc = db->d_desc; b.normal = db->d_nrm; b.max_distance = db->d_maxd;
   b.slots = kfdb->d_slots; b.rows = kfdb->d_rows; b.oct = kfdb->d_oct; b.levels = kfdb->d_levels; b.sf = kfdb->d_sf;
-  const size_t P = (size_t)db->P, s = (size_t)S, m = (size_t)cap_obs;
+  const size_t s = (size_t)S, m = (size_t)cap_obs;
   // a large point has more than MPU_SMALL observations and takes a block for its normal and one per MPU_ROWS election rows
   const size_t cap_blocks = m / MPU_ROWS + 2 * (m / (MPU_SMALL + 1)) + 2;
-  HIPCHK(c, dsh_scratch_array(c, &b.sel_of, P));
+  HIPCHK(c, mpdb_obs_lists(db, b.ol, s, m));
+  b.ol.kf = db->d_kf;
+  HIPCHK(c, dsh_scratch_array(c, &b.ol.off, s + 1));
   HIPCHK(c, dsh_scratch_array(c, &b.sel_pid, s));
-  HIPCHK(c, dsh_scratch_array(c, &b.cnt, s));
-  HIPCHK(c, dsh_scratch_array(c, &b.fill, s));
-  HIPCHK(c, dsh_scratch_array(c, &b.off, s + 1));
-  HIPCHK(c, dsh_scratch_array(c, &b.raw_slot, m));
-  HIPCHK(c, dsh_scratch_array(c, &b.raw_idx, m));
   HIPCHK(c, dsh_scratch_array(c, &b.obs_slot, m));
   HIPCHK(c, dsh_scratch_array(c, &b.el_row, m));
   HIPCHK(c, dsh_scratch_array(c, &b.pts, s));
@@ -78,7 +68,7 @@ int dsh_keyframe_process_new(dsh_mpdb* db, const dsh_keyframe_process_input* in,
   const LmKf nk = db->kf[in->slot];
   const long long cap_obs = (long long)db->obs.size() + nk.N;
   if (cap_obs > INT32_MAX || db->R + nk.N > INT32_MAX) return bad("store full");
-  if (!db->unindexed.empty()) return state_error(db, "dsh_keyframe_process_new");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_keyframe_process_new");
   if (const int rc = dsh_enter(c, "dsh_keyframe_process_new")) return rc;
   std::memset(out, 0, sizeof(*out));   // a refused call leaves the caller's counts as they were
   out->first_record = db->R;
@@ -129,7 +119,7 @@ int dsh_point_store_upkeep(dsh_mpdb* db, const dsh_point_upkeep_input* in, int32
   const std::string ke = kfdb_error(db, in->kfdb);
   if (!ke.empty()) return bad(ke);
   if (db->obs.size() > (size_t)INT32_MAX) return bad("store full");
-  if (!db->unindexed.empty()) return state_error(db, "dsh_point_store_upkeep");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_upkeep");
   if (const int rc = dsh_enter(c, "dsh_point_store_upkeep")) return rc;
   std::memset(out, 0, sizeof(*out));   // a refused call leaves the caller's counts as they were
   const int32_t S = embedded ? db->P : in->n;

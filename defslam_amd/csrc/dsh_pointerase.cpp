@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
@@ -15,25 +14,6 @@
 #include "pointerase_problem.h"
 
 namespace {
-
-// n distinct ids inside [0, count): mpdb_ids_error with the repeat named ahead of the range
-std::string ids_error(int n, const int32_t* ids, int32_t count) {
-  if (n < 0) return "n < 0";
-  if (n > 0 && !ids) return "point id array is NULL";
-  std::vector<int32_t> s(ids, ids + n);
-  std::sort(s.begin(), s.end());
-  for (int i = 1; i < n; i++)
-    if (s[i] == s[i - 1]) return "point id " + std::to_string(s[i]) + " repeated in the batch";
-  for (int i = 0; i < n; i++)
-    if (ids[i] < 0 || ids[i] >= count) return "point id " + std::to_string(ids[i]) + " outside the store";
-  return "";
-}
-
-int state_error(dsh_mpdb* db, const char* who) {
-  return dsh_fail(db->ctx, DSH_ERR_STATE,
-                  std::string(who) + ": the store holds " + std::to_string(db->unindexed.size()) +
-                      " live observation records without a key point index (dsh_mpdb_add_observations); add them with dsh_point_store_add_observations_indexed");
-}
 
 // One erase call from the device gate on: mode PE_*; slots and first_kf as the mode needs them; code[n] receives the status or the action.
 int run(dsh_mpdb* db, dsh_ctx_base* c, int mode, int n, const int32_t* ids, const int32_t* slots, const int32_t* first_kf, int32_t erase_match,
@@ -108,11 +88,11 @@ int dsh_point_store_erase_observations(dsh_mpdb* db, int n, const int32_t* point
   DSH_STORE_ENTER("dsh_point_store_erase_observations");
   if (!out) return bad("out is NULL");
   if (n > 0 && !keyframe_slots) return bad("keyframe_slots is NULL");
-  const std::string ie = ids_error(n, point_ids, db->P);
+  const std::string ie = mpdb_ids_error(n, point_ids, db->P, "point id", true);
   if (!ie.empty()) return bad(ie);
   for (int i = 0; i < n; i++)
     if (keyframe_slots[i] < 0 || keyframe_slots[i] >= db->K) return bad("pair " + std::to_string(i) + ": keyframe slot outside the store");
-  if (!db->unindexed.empty()) return state_error(db, "dsh_point_store_erase_observations");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_erase_observations");
   if (const int rc = dsh_enter(c, "dsh_point_store_erase_observations")) return rc;
   return run(db, c, PE_ERASE, n, point_ids, keyframe_slots, nullptr, erase_match ? 1 : 0, 0, status, out);
 }
@@ -120,9 +100,9 @@ int dsh_point_store_erase_observations(dsh_mpdb* db, int n, const int32_t* point
 int dsh_point_store_set_bad(dsh_mpdb* db, int n, const int32_t* ids, dsh_point_erase_counts* out) {
   DSH_STORE_ENTER("dsh_point_store_set_bad");
   if (!out) return bad("out is NULL");
-  const std::string ie = ids_error(n, ids, db->P);
+  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id", true);
   if (!ie.empty()) return bad(ie);
-  if (!db->unindexed.empty()) return state_error(db, "dsh_point_store_set_bad");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_set_bad");
   if (const int rc = dsh_enter(c, "dsh_point_store_set_bad")) return rc;
   return run(db, c, PE_SET_BAD, n, ids, nullptr, nullptr, 0, 0, nullptr, out);
 }
@@ -131,10 +111,10 @@ int dsh_point_store_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t*
                          dsh_point_erase_counts* out) {
   DSH_STORE_ENTER("dsh_point_store_cull");
   if (!out) return bad("out is NULL");
-  const std::string ie = ids_error(n, ids, db->P);
+  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id", true);
   if (!ie.empty()) return bad(ie);
   if (n > 0 && (!first_kf || !action)) return bad("first_kf or action is NULL");
-  if (!db->unindexed.empty()) return state_error(db, "dsh_point_store_cull");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_cull");
   if (const int rc = dsh_enter(c, "dsh_point_store_cull")) return rc;
   return run(db, c, PE_CULL, n, ids, nullptr, first_kf, 0, current_kf, action, out);
 }
@@ -142,7 +122,7 @@ int dsh_point_store_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t*
 int dsh_point_store_get_observations(dsh_mpdb* db, int n, const int32_t* ids, int32_t* obs_ptr, int32_t capacity, int32_t* slots, int32_t* idx,
                                      int32_t* n_total) {
   DSH_STORE_ENTER("dsh_point_store_get_observations");
-  const std::string ie = ids_error(n, ids, db->P);
+  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id", true);
   if (!ie.empty()) return bad(ie);
   if (!obs_ptr || !n_total) return bad("obs_ptr or n_total is NULL");
   if (capacity < 0) return bad("capacity < 0");
@@ -161,15 +141,10 @@ int dsh_point_store_get_observations(dsh_mpdb* db, int n, const int32_t* ids, in
   if (const int rc = down.alloc(c)) return rc;
   PeObsBufs b;
   std::memset(&b, 0, sizeof(b));
-  b.P = db->P; b.n = n; b.cap = (int32_t)cap; b.R = db->R;
-  b.log = db->d_log; b.log_idx = db->d_log_idx; b.ids = up.dev<const int32_t>(o_ids);
-  HIPCHK(c, dsh_scratch_array(c, &b.sel_of, (size_t)db->P));
-  HIPCHK(c, dsh_scratch_array(c, &b.cnt, m));
-  HIPCHK(c, dsh_scratch_array(c, &b.fill, m));
-  HIPCHK(c, dsh_scratch_array(c, &b.raw_slot, live));
-  HIPCHK(c, dsh_scratch_array(c, &b.raw_idx, live));
+  b.P = db->P; b.n = n; b.cap = (int32_t)cap; b.ids = up.dev<const int32_t>(o_ids);
+  HIPCHK(c, mpdb_obs_lists(db, b.ol, m, live));
   b.hdr = down.dev<PeHdr>(d_hdr);
-  b.out_ptr = down.dev<int32_t>(d_ptr); b.out_slot = down.dev<int32_t>(d_slot); b.out_idx = down.dev<int32_t>(d_idx);
+  b.ol.off = down.dev<int32_t>(d_ptr); b.out_slot = down.dev<int32_t>(d_slot); b.out_idx = down.dev<int32_t>(d_idx);
   HIPCHK(c, pe_observations_launch(b, c->stream));
   if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));

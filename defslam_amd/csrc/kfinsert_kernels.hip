@@ -7,11 +7,9 @@
 //   selection            dsh_keyframe_process_new: ki_first_kernel (the lowest entry that holds each point), ki_observes_kernel (first pass
 //                        over the log: who observes the keyframe already) and ki_classify_kernel, ONE workgroup that walks the table in
 //                        order: the action per entry, and for action 2 the record appended to the log at R + position, nObs++ and the
-//                        point's place in the selection (ordered compaction: an_write_kernel's pattern)
+//                        point's place in the selection (ordered compaction)
 //                        dsh_point_store_upkeep: ki_select_ids_kernel, or ki_select_embedded_kernel (one atomic per wavefront)
-//   ki_count_kernel      pass over the log: live observations per selected point
-//   ki_scan_kernel       ONE workgroup: the CSR offsets
-//   ki_fill_kernel       pass over the log: the observations in arrival order, each with its keyframe's bad flag
+//   obs_lists_launch     obslist_kernels.hip: the observations of every selected point in arrival order, each with its keyframe's bad flag
 //   ki_sort_kernel       a wavefront per point: every observation's rank by slot (slots are unique within a point, so the result does not
 //                        depend on arrival order) and its rank among the observations whose keyframe is not bad -> the observation slots
 //                        and the election rows by ascending slot; the reference record; the point's MpuPoint, its status, and its place in
@@ -19,25 +17,24 @@
 //   ki_small_kernel<W>   worst-case grids that read their count from KiHdr and leave at once without work
 //   ki_large_kernel      a fixed grid that strides over the block list
 //   ki_finish_kernel     the winner's descriptor row of every large point
-// Election and geometry are the device functions of mappoint_device.h, the ones dsh_mappoint_update runs.  Compiled without FMA
+// Election and geometry are the kernel bodies of mappoint_device.h, the ones dsh_mappoint_update runs.  Compiled without FMA
 // contraction (see include/defslam_hip.h).
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
 #include "kfinsert_problem.h"
 #include "mappoint_device.h"
+#include "mpdb_device.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 __global__ __launch_bounds__(KI_BLOCK) void ki_clear_kernel(KiBufs b, int new_kf) {
   const int i = blockIdx.x * KI_BLOCK + threadIdx.x;
   if (i < b.P) {
-    b.sel_of[i] = -1;
+    b.ol.sel_of[i] = -1;
     if (new_kf) { b.first_i[i] = KI_UNMARKED; b.observes[i] = 0; }
   }
-  if (i < b.S) { b.sel_pid[i] = -1; b.cnt[i] = 0; b.fill[i] = 0; b.large_key[i] = 0xFFFFFFFFu; }
+  if (i < b.S) { b.sel_pid[i] = -1; b.ol.cnt[i] = 0; b.ol.fill[i] = 0; b.large_key[i] = 0xFFFFFFFFu; }
   if (i == 0) {
     KiHdr h = {};
     *b.hdr = h;
@@ -52,8 +49,8 @@ __global__ __launch_bounds__(KI_BLOCK) void ki_first_kernel(KiBufs b) {
 }
 
 __global__ __launch_bounds__(KI_BLOCK) void ki_observes_kernel(KiBufs b) {
-  for (long long r = (long long)blockIdx.x * KI_BLOCK + threadIdx.x; r < b.R; r += (long long)gridDim.x * KI_BLOCK) {
-    const int2 rec = b.log[r];
+  for (long long r = (long long)blockIdx.x * KI_BLOCK + threadIdx.x; r < b.ol.R; r += (long long)gridDim.x * KI_BLOCK) {
+    const int2 rec = b.ol.log[r];
     if (rec.x >= 0 && rec.y == b.slot) b.observes[rec.x] = 1;
   }
 }
@@ -61,7 +58,6 @@ __global__ __launch_bounds__(KI_BLOCK) void ki_observes_kernel(KiBufs b) {
 // LocalMapping.cc:142-161 over the table in order; one workgroup
 __global__ __launch_bounds__(KI_BLOCK) void ki_classify_kernel(KiBufs b) {
   __shared__ int wsum[KI_BLOCK / 64];
-  const int wave = threadIdx.x >> 6;
   int base = 0, n_empty = 0, n_bad = 0, n_recent = 0;
   for (int t0 = 0; t0 < b.N; t0 += KI_BLOCK) {
     const int i = t0 + threadIdx.x;
@@ -75,20 +71,12 @@ __global__ __launch_bounds__(KI_BLOCK) void ki_classify_kernel(KiBufs b) {
       n_recent += a == 3;
     }
     const bool take = a == 2;
-    const unsigned long long m = __ballot(take);
-    __syncthreads();   // the previous tile's totals have been read
-    if ((threadIdx.x & 63) == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int pos = base + __popcll(m & lanes_below());
-    for (int w = 0; w < KI_BLOCK / 64; w++) {
-      if (w < wave) pos += wsum[w];
-      base += wsum[w];
-    }
+    const int pos = ordered_slot<KI_BLOCK>(take, base, wsum);
     if (take) {   // pos < N: the host reserved N records behind R and N entries of the selection
-      b.log[b.R + pos] = make_int2(p, b.slot);
-      b.log_idx[b.R + pos] = i;
+      b.ol.log[b.ol.R + pos] = make_int2(p, b.slot);
+      b.ol.log_idx[b.ol.R + pos] = i;
       b.nobs[p] += 1;   // MapPoint.cc:116-119; the lowest entry alone takes the point
-      b.sel_of[p] = pos;
+      b.ol.sel_of[p] = pos;
       b.sel_pid[pos] = p;
       b.out_added[pos] = p;
     }
@@ -109,7 +97,7 @@ __global__ __launch_bounds__(KI_BLOCK) void ki_select_ids_kernel(KiBufs b) {
     if (b.out_status) b.out_status[i] = DSH_MP_SKIPPED_BAD;
     return;
   }
-  b.sel_of[p] = i;
+  b.ol.sel_of[p] = i;
   b.sel_pid[i] = p;
 }
 
@@ -117,64 +105,10 @@ __global__ __launch_bounds__(KI_BLOCK) void ki_select_ids_kernel(KiBufs b) {
 __global__ __launch_bounds__(KI_BLOCK) void ki_select_embedded_kernel(KiBufs b) {
   const int p = blockIdx.x * KI_BLOCK + threadIdx.x;
   const bool take = p < b.P && !b.bad[p] && b.nodes[3 * (size_t)p] >= 0;
-  const unsigned long long m = __ballot(take);
-  int base = 0;
-  if ((threadIdx.x & 63) == 0 && m) base = atomicAdd(&b.hdr->n_sel, __popcll(m));
-  base = __shfl(base, 0, 64);
+  const int k = wave_append(take, &b.hdr->n_sel);
   if (take) {   // k < S = P
-    const int k = base + __popcll(m & lanes_below());
-    b.sel_of[p] = k;
+    b.ol.sel_of[p] = k;
     b.sel_pid[k] = p;
-  }
-}
-
-__global__ __launch_bounds__(KI_BLOCK) void ki_count_kernel(KiBufs b) {
-  const long long R = b.R + b.hdr->n_appended;
-  for (long long r = (long long)blockIdx.x * KI_BLOCK + threadIdx.x; r < R; r += (long long)gridDim.x * KI_BLOCK) {
-    const int p = b.log[r].x;
-    if (p < 0) continue;   // erased
-    const int k = b.sel_of[p];
-    if (k >= 0) atomicAdd(&b.cnt[k], 1);
-  }
-}
-
-// exclusive scan of cnt[0 .. n_sel) into off[0 .. n_sel]; one workgroup, a contiguous chunk per thread
-__global__ __launch_bounds__(KI_BLOCK) void ki_scan_kernel(KiBufs b) {
-  __shared__ int part[KI_BLOCK];
-  const int n = b.hdr->n_sel, per = (n + KI_BLOCK - 1) / KI_BLOCK, t = threadIdx.x;
-  const int lo = min(t * per, n), hi = min(lo + per, n);
-  int s = 0;
-  for (int k = lo; k < hi; k++) s += b.cnt[k];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int w = 0; w < KI_BLOCK; w++) {
-      const int v = part[w];
-      part[w] = run;
-      run += v;
-    }
-    b.off[n] = run;
-    b.hdr->total = run;
-  }
-  __syncthreads();
-  int run = part[t];
-  for (int k = lo; k < hi; k++) {
-    b.off[k] = run;
-    run += b.cnt[k];
-  }
-}
-
-__global__ __launch_bounds__(KI_BLOCK) void ki_fill_kernel(KiBufs b) {
-  const long long R = b.R + b.hdr->n_appended;
-  for (long long r = (long long)blockIdx.x * KI_BLOCK + threadIdx.x; r < R; r += (long long)gridDim.x * KI_BLOCK) {
-    const int2 rec = b.log[r];
-    if (rec.x < 0) continue;
-    const int k = b.sel_of[rec.x];
-    if (k < 0) continue;
-    const int pos = b.off[k] + atomicAdd(&b.fill[k], 1);   // pos < off[k + 1]: the count pass saw the same records
-    b.raw_slot[pos] = rec.y | (b.kf[rec.y].bad ? (int)0x80000000 : 0);   // slots fit 16 bits (DSH_MP_MAX_OBS keyframes)
-    b.raw_idx[pos] = b.log_idx[r];
   }
 }
 
@@ -185,22 +119,17 @@ __global__ __launch_bounds__(64) void ki_sort_kernel(KiBufs b) {
   for (int k = blockIdx.x; k < n; k += gridDim.x) {
     const int pid = b.sel_pid[k];
     if (pid < 0) continue;   // wave-uniform: an id that names a bad point
-    const int M = b.cnt[k], o = b.off[k], ref = b.ref_kf[pid];
+    const int M = b.ol.cnt[k], o = b.ol.off[k], ref = b.ref_kf[pid];
     int ngood = 0, ref_idx = 0;   // observations[pRefKF] of a copy that lacks pRefKF inserts and yields 0
     bool has_ref = false;
     for (int base = 0; base < M; base += 64) {
       const int i = base + lane;
       const bool valid = i < M;
-      const uint32_t v = valid ? (uint32_t)b.raw_slot[o + i] : 0u;
-      const int s = (int)(v & 0x7FFFFFFFu), j = valid ? b.raw_idx[o + i] : 0;
+      const uint32_t v = valid ? (uint32_t)b.ol.raw_slot[o + i] : 0u;
+      const int s = (int)(v & 0x7FFFFFFFu), j = valid ? b.ol.raw_idx[o + i] : 0;
       const bool good = valid && !(v >> 31);
-      int rank = 0, grank = 0;
-      for (int q = 0; q < M; q++) {   // wave-uniform address
-        const uint32_t u = (uint32_t)b.raw_slot[o + q];
-        const bool lt = (int)(u & 0x7FFFFFFFu) < s;
-        rank += lt;
-        grank += lt && !(u >> 31);
-      }
+      int grank;
+      const int rank = obs_rank(b.ol.raw_slot, o, M, s, grank);
       if (valid) b.obs_slot[o + rank] = s;                          // rank < M: slots are unique within a point
       if (good) b.el_row[o + grank] = b.slots[s].row_off + j;       // grank < the good ones <= M
       ngood += __popcll(__ballot(good));
@@ -220,7 +149,7 @@ __global__ __launch_bounds__(64) void ki_sort_kernel(KiBufs b) {
       } else {
         if (ngood == 0) { status |= DSH_MP_NO_GOOD_DESC; atomicAdd(&b.hdr->n_no_good_desc, 1); }
         // no reference keyframe; one that is not observed and has no key point 0 to lend its octave counts as none
-        if (ref < 0 || (!has_ref && b.kf[ref].N <= 0)) {
+        if (ref < 0 || (!has_ref && b.ol.kf[ref].N <= 0)) {
           status |= DSH_MP_NO_REF;
           what &= ~DSH_MP_NORMAL_DEPTH;
           atomicAdd(&b.hdr->n_no_ref, 1);
@@ -252,97 +181,42 @@ __global__ __launch_bounds__(64) void ki_sort_kernel(KiBufs b) {
   }
 }
 
-// mNormalVector = normal / n (MapPoint.cc:389) and mfMaxDistance (:379-388) into the store, written by one lane
-__device__ __forceinline__ void store_geometry(const KiBufs& b, const MpuPoint& pt, int pid, float sx, float sy, float sz) {
-  float mx, mn;
-  mp_geometry(pt.M, sx, sy, sz, b.slots[pt.ref_slot], pt.x, pt.y, pt.z, pt.sf_level, pt.sf_last, b.normal + 3 * (size_t)pid, mx, mn);
-  b.max_distance[pid] = mx;
-}
+// the lists the device built, the results into the point store: a point k of the selection is the store's point sel_pid[k]
+struct KiView {
+  const KiBufs& b;
+  const int32_t* list;
+  int n;
+  __device__ int id(int k) const { return b.sel_pid[k]; }
+  __device__ void store_desc(int pid, int, const uint4& d0, const uint4& d1) const {
+    b.desc[2 * (size_t)pid] = d0;
+    b.desc[2 * (size_t)pid + 1] = d1;
+  }
+  __device__ float* normal(int pid) const { return b.normal + 3 * (size_t)pid; }
+  __device__ void store_depth(int pid, float mx, float) const { b.max_distance[pid] = mx; }   // mfMaxDistance alone is kept
+};
 
-// mpu_small_kernel on the device-built list of width class c: W lanes per point, 256 / W points per workgroup
+// mpu_small_kernel on the device-built list of width class c: a worst-case grid that reads its count from KiHdr
 template <int W>
 __global__ __launch_bounds__(256) void ki_small_kernel(KiBufs b, int c) {
   __shared__ uint4 sd[2 * 256];
-  const int n = b.hdr->cls_n[c];
-  if (blockIdx.x * (256 / W) >= n) return;   // workgroup-uniform
-  const int t = threadIdx.x, r = t % W, g = t / W, gbase = (t & 63) - r;
-  const int kk = blockIdx.x * (256 / W) + g;
-  const bool has = kk < n;
-  const int k = has ? b.small_list[(size_t)c * b.S + kk] : 0;
-  MpuPoint pt;
-  if (has) pt = b.pts[k];
-  else { pt.M = pt.Me = 0; pt.what = 0; pt.x = pt.y = pt.z = 0.f; }
-  const int pid = has ? b.sel_pid[k] : 0;
-  const bool elect = (pt.what & 1) && pt.Me > 0, geom = (pt.what & 2) && pt.M > 0;
-  uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
-  if (elect && r < pt.Me) {
-    const int row = b.el_row[pt.el_off + r];
-    d0 = b.rows[2 * (size_t)row];
-    d1 = b.rows[2 * (size_t)row + 1];
-  }
-  sd[2 * t] = d0;
-  sd[2 * t + 1] = d1;
-  __syncthreads();
-  if (elect) {
-    const uint32_t key = mp_elect_small<W>(d0, d1, sd + 2 * (t - r), pt.Me, r);
-    if (r == 0) {
-      const int e = (int)(key & 0xFFFF);
-      b.desc[2 * (size_t)pid] = sd[2 * (t + e)];
-      b.desc[2 * (size_t)pid + 1] = sd[2 * (t + e) + 1];
-    }
-  }
-  float tx = 0.f, ty = 0.f, tz = 0.f;
-  if (geom && r < pt.M) normal_term(b.slots[b.obs_slot[pt.obs_off + r]], pt.x, pt.y, pt.z, tx, ty, tz);
-  float sx, sy, sz;
-  mp_normal_sum_small<W>(tx, ty, tz, gbase, pt.M, sx, sy, sz);
-  if (geom && r == 0) store_geometry(b, pt, pid, sx, sy, sz);
+  mp_small_body<W>(KiView{b, b.small_list + (size_t)c * b.S, b.hdr->cls_n[c]}, sd);
 }
 
 // mpu_large_kernel, one wavefront striding over the device-built block list
 __global__ __launch_bounds__(64) void ki_large_kernel(KiBufs b) {
   __shared__ uint32_t hist[64 * MPU_HIST_WORDS];
-  const int lane = threadIdx.x, nb = b.hdr->n_blocks;
-  for (int bi = blockIdx.x; bi < nb; bi += gridDim.x) {
-    const int2 blk = b.large_blocks[bi];
-    const int k = blk.x, row0 = blk.y;
-    const MpuPoint pt = b.pts[k];
-    if (row0 < 0) {
-      float sx, sy, sz;
-      mp_normal_sum_large(b.slots, b.obs_slot, pt.obs_off, pt.M, pt.x, pt.y, pt.z, lane, sx, sy, sz);
-      if (lane == 0) store_geometry(b, pt, b.sel_pid[k], sx, sy, sz);
-      continue;
-    }
-    const uint32_t key = mp_elect_block(b.rows, b.el_row, pt.el_off, pt.Me, row0, lane, hist);   // each lane clears its own histogram
-    if (lane == 0) atomicMin(&b.large_key[k], key);
-  }
+  mp_large_body(KiView{b, nullptr, b.hdr->n_blocks}, hist);
 }
 
-__global__ __launch_bounds__(64) void ki_finish_kernel(KiBufs b) {
-  const int n = b.hdr->n_large;
-  for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) {
-    const int k = b.large_pts[i];
-    const MpuPoint pt = b.pts[k];
-    if (!(pt.what & 1) || pt.Me <= 0) continue;
-    const int e = (int)(b.large_key[k] & 0xFFFF), row = b.el_row[pt.el_off + e], pid = b.sel_pid[k];
-    b.desc[2 * (size_t)pid] = b.rows[2 * (size_t)row];
-    b.desc[2 * (size_t)pid + 1] = b.rows[2 * (size_t)row + 1];
-  }
-}
-
-inline int blocks_for(long long n) { return (int)((n + KI_BLOCK - 1) / KI_BLOCK); }
-
-// eight records per thread, at most 1024 workgroups, as lm_votes_kernel
-inline int log_blocks(long long R) {
-  const long long g = (R + 8 * KI_BLOCK - 1) / (8 * KI_BLOCK);
-  return (int)(g > 1024 ? 1024 : g < 1 ? 1 : g);
-}
+__global__ __launch_bounds__(64) void ki_finish_kernel(KiBufs b) { mp_finish_body(KiView{b, b.large_pts, b.hdr->n_large}); }
 
 // from the selection to the results: R_max bounds the log the passes read
 hipError_t upkeep_launches(const KiBufs& b, long long R_max, hipStream_t st) {
   if (b.S == 0) return hipGetLastError();
-  if (R_max > 0) hipLaunchKernelGGL(ki_count_kernel, dim3(log_blocks(R_max)), dim3(KI_BLOCK), 0, st, b);
-  hipLaunchKernelGGL(ki_scan_kernel, dim3(1), dim3(KI_BLOCK), 0, st, b);
-  if (R_max > 0) hipLaunchKernelGGL(ki_fill_kernel, dim3(log_blocks(R_max)), dim3(KI_BLOCK), 0, st, b);
+  ObsLists a = b.ol;
+  a.n = b.S; a.n_dev = &b.hdr->n_sel; a.n_extra = &b.hdr->n_appended; a.total = &b.hdr->total;
+  const hipError_t e = obs_lists_launch(a, R_max, st);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(ki_sort_kernel, dim3(b.S < 4096 ? b.S : 4096), dim3(64), 0, st, b);
   hipLaunchKernelGGL(ki_large_kernel, dim3(KI_LARGE_GRID), dim3(64), 0, st, b);
   hipLaunchKernelGGL(ki_finish_kernel, dim3(b.S < 64 * 256 ? (b.S + 63) / 64 : 256), dim3(64), 0, st, b);
@@ -357,20 +231,20 @@ hipError_t upkeep_launches(const KiBufs& b, long long R_max, hipStream_t st) {
 
 extern "C" hipError_t ki_process_new_launch(const KiBufs& b, hipStream_t st) {
   const int top = b.P > b.S ? b.P : b.S;
-  hipLaunchKernelGGL(ki_clear_kernel, dim3(blocks_for(top > 1 ? top : 1)), dim3(KI_BLOCK), 0, st, b, 1);
-  if (b.N > 0) hipLaunchKernelGGL(ki_first_kernel, dim3(blocks_for(b.N)), dim3(KI_BLOCK), 0, st, b);
-  if (b.R > 0) hipLaunchKernelGGL(ki_observes_kernel, dim3(log_blocks(b.R)), dim3(KI_BLOCK), 0, st, b);
+  hipLaunchKernelGGL(ki_clear_kernel, dim3(blocks_for(top > 1 ? top : 1, KI_BLOCK)), dim3(KI_BLOCK), 0, st, b, 1);
+  if (b.N > 0) hipLaunchKernelGGL(ki_first_kernel, dim3(blocks_for(b.N, KI_BLOCK)), dim3(KI_BLOCK), 0, st, b);
+  if (b.ol.R > 0) hipLaunchKernelGGL(ki_observes_kernel, dim3(log_blocks(b.ol.R, KI_BLOCK)), dim3(KI_BLOCK), 0, st, b);
   hipLaunchKernelGGL(ki_classify_kernel, dim3(1), dim3(KI_BLOCK), 0, st, b);
-  return upkeep_launches(b, b.R + b.N, st);
+  return upkeep_launches(b, b.ol.R + b.N, st);
 }
 
 extern "C" hipError_t ki_upkeep_launch(const KiBufs& b, int embedded, hipStream_t st) {
   const int top = b.P > b.S ? b.P : b.S;
-  hipLaunchKernelGGL(ki_clear_kernel, dim3(blocks_for(top > 1 ? top : 1)), dim3(KI_BLOCK), 0, st, b, 0);
+  hipLaunchKernelGGL(ki_clear_kernel, dim3(blocks_for(top > 1 ? top : 1, KI_BLOCK)), dim3(KI_BLOCK), 0, st, b, 0);
   if (embedded) {
-    if (b.P > 0) hipLaunchKernelGGL(ki_select_embedded_kernel, dim3(blocks_for(b.P)), dim3(KI_BLOCK), 0, st, b);
+    if (b.P > 0) hipLaunchKernelGGL(ki_select_embedded_kernel, dim3(blocks_for(b.P, KI_BLOCK)), dim3(KI_BLOCK), 0, st, b);
   } else if (b.n_ids > 0) {
-    hipLaunchKernelGGL(ki_select_ids_kernel, dim3(blocks_for(b.n_ids)), dim3(KI_BLOCK), 0, st, b);
+    hipLaunchKernelGGL(ki_select_ids_kernel, dim3(blocks_for(b.n_ids, KI_BLOCK)), dim3(KI_BLOCK), 0, st, b);
   }
-  return upkeep_launches(b, b.R, st);
+  return upkeep_launches(b, b.ol.R, st);
 }

@@ -7,6 +7,7 @@
 #include "../../include/defslam_hip.h"
 #include "localmap_problem.h"
 #include "mappoint_problem.h"
+#include "obslist_problem.h"
 
 #define KI_BLOCK 256
 #define KI_UNMARKED 0x7fffffff   // first_i of a point no entry of the keyframe holds
@@ -27,16 +28,15 @@ struct KiHdr {
 struct KiBufs {
   int32_t P, S;                  // points of the store; what the host knows of the number of selected points
   int32_t what;                  // DSH_MP_* mask
-  long long R;                   // log records before the call; the passes read R + hdr->n_appended
+  // the store's log (R: its records before the call), the store's keyframes (the bad flag the election reads), sel_of (the position of
+  // a point in sel_pid, else -1) and the observation lists of the selected points; the launchers point n_dev, n_extra and total into hdr
+  ObsLists ol;
   // the point store
   const float* xyz;
   const int32_t* bad;
   const int32_t* ref_kf;
   const int32_t* nodes;          // 3 per point, -1: no facet
   int32_t* nobs;
-  int2* log;
-  int32_t* log_idx;
-  const LmKf* kf;                // the point store's keyframes: the bad flag the election reads
   const int32_t* table;
   uint4* desc;                   // results: two uint4 per point
   float* normal;                 // 3 per point
@@ -55,13 +55,7 @@ struct KiBufs {
   int32_t n_ids;
   const int32_t* ids;
   // temporaries
-  int32_t* sel_of;               // P: position of the point in sel_pid, else -1
   int32_t* sel_pid;              // S: the selected points (-1: an id that names a bad point)
-  int32_t* cnt;                  // S: live observations
-  int32_t* fill;                 // S
-  int32_t* off;                  // S + 1: CSR offsets
-  int32_t* raw_slot;             // cap_obs: the observations in log order
-  int32_t* raw_idx;
   int32_t* obs_slot;             // cap_obs: by ascending slot
   int32_t* el_row;               // cap_obs: the election rows, by ascending slot, at the same offsets
   MpuPoint* pts;                 // S

@@ -12,10 +12,9 @@
 //   lm_count_kernel, lm_compact_kernel   ordered compaction of the marks into the local id list (64-bit ballots, then block offsets)
 // Where the reference iterates pointer-ordered containers the order here is the index: keyframes by slot, points by id.
 #include "localmap_problem.h"
+#include "mpdb_device.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 __global__ __launch_bounds__(LM_BLOCK) void lm_clear_kernel(LmBufs b) {
   const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
@@ -210,20 +209,14 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_scatter_i32_kernel(int32_t* dst, 
   if (i < n) dst[idx[i]] = val ? val[i] : fill;
 }
 
-inline int blocks_for(long long n) { return (int)((n + LM_BLOCK - 1) / LM_BLOCK); }
-
 }  // namespace
 
 extern "C" hipError_t lm_update_launch(const LmBufs& b, hipStream_t st) {
   const int top = b.P > b.K ? b.P : b.K;
-  hipLaunchKernelGGL(lm_clear_kernel, dim3(blocks_for(top > 0 ? top : 1)), dim3(LM_BLOCK), 0, st, b);
-  if (b.N > 0) hipLaunchKernelGGL(lm_scatter_kernel, dim3(blocks_for(b.N)), dim3(LM_BLOCK), 0, st, b);
-  if (b.R > 0 && b.N > 0) {
-    // eight records per thread, at most 1024 workgroups: every workgroup flushes its touched bins once
-    long long g = (b.R + 8 * LM_BLOCK - 1) / (8 * LM_BLOCK);
-    if (g > 1024) g = 1024;
-    hipLaunchKernelGGL(lm_votes_kernel, dim3((int)g), dim3(LM_BLOCK), 0, st, b);
-  }
+  hipLaunchKernelGGL(lm_clear_kernel, dim3(blocks_for(top > 0 ? top : 1, LM_BLOCK)), dim3(LM_BLOCK), 0, st, b);
+  if (b.N > 0) hipLaunchKernelGGL(lm_scatter_kernel, dim3(blocks_for(b.N, LM_BLOCK)), dim3(LM_BLOCK), 0, st, b);
+  // few workgroups: every workgroup flushes its touched bins once
+  if (b.R > 0 && b.N > 0) hipLaunchKernelGGL(lm_votes_kernel, dim3(log_blocks(b.R, LM_BLOCK)), dim3(LM_BLOCK), 0, st, b);
   hipLaunchKernelGGL(lm_build_kernel, dim3(1), dim3(64), 0, st, b);
   if (b.K > 0 && b.P > 0) hipLaunchKernelGGL(lm_flags_kernel, dim3(b.K), dim3(LM_BLOCK), 0, st, b);
   if (b.P > 0) {
@@ -235,16 +228,16 @@ extern "C" hipError_t lm_update_launch(const LmBufs& b, hipStream_t st) {
 }
 
 extern "C" hipError_t lm_gather_launch(const LmQueryBufs& q, int Q, hipStream_t st) {
-  if (Q > 0) hipLaunchKernelGGL(lm_gather_kernel, dim3(blocks_for(Q)), dim3(LM_BLOCK), 0, st, q, Q);
+  if (Q > 0) hipLaunchKernelGGL(lm_gather_kernel, dim3(blocks_for(Q, LM_BLOCK)), dim3(LM_BLOCK), 0, st, q, Q);
   return hipGetLastError();
 }
 
 extern "C" hipError_t lm_write_points_launch(const LmWriteBufs& w, int n, int what, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(lm_write_points_kernel, dim3(blocks_for(n)), dim3(LM_BLOCK), 0, st, w, n, what);
+  if (n > 0) hipLaunchKernelGGL(lm_write_points_kernel, dim3(blocks_for(n, LM_BLOCK)), dim3(LM_BLOCK), 0, st, w, n, what);
   return hipGetLastError();
 }
 
 extern "C" hipError_t lm_scatter_i32_launch(int32_t* dst, const int32_t* idx, const int32_t* val, int32_t fill, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(lm_scatter_i32_kernel, dim3(blocks_for(n)), dim3(LM_BLOCK), 0, st, dst, idx, val, fill, n);
+  if (n > 0) hipLaunchKernelGGL(lm_scatter_i32_kernel, dim3(blocks_for(n, LM_BLOCK)), dim3(LM_BLOCK), 0, st, dst, idx, val, fill, n);
   return hipGetLastError();
 }

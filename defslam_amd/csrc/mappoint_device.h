@@ -1,9 +1,9 @@
 // Device functions of MapPoint::UpdateNormalAndDepth (Thirdparty/ORBSLAM_2/src/MapPoint.cc:348-391) and of
 // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:257-325) that more than one kernel file uses: mappoint_kernels.hip
 // (dsh_mappoint_update, lists from the host), kfinsert_kernels.hip (dsh_keyframe_process_new and dsh_point_store_upkeep, lists built on
-// the device from the store's log) and tmplswitch_kernels.hip (the new points of dsh_template_switch, one observation each).  The
-// arithmetic is the one include/defslam_hip.h states for dsh_mappoint_update; a file that includes this header is compiled without FMA
-// contraction.
+// the device from the store's log) and tmplswitch_kernels.hip (the new points of dsh_template_switch, one observation each); at the end
+// the bodies of the election and geometry kernels the first two wrap.  The arithmetic is the one include/defslam_hip.h states for
+// dsh_mappoint_update; a file that includes this header is compiled without FMA contraction.
 #pragma once
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
@@ -149,4 +149,89 @@ __device__ __forceinline__ uint32_t mp_elect_block(const uint4* rows, const int3
     key = other < key ? other : key;
   }
   return key;
+}
+
+// ---- the bodies of the election and geometry kernels -------------------------------------------------------------------------------
+// A kernel hands its body a view V of where its work comes from and where the results go:
+//   v.b                 the buffers: pts, el_row, rows, slots, obs_slot, large_blocks, large_key
+//   v.list, v.n         the list the kernel works on and its length (the large body reads v.b.large_blocks)
+//   v.id(k)             the id under which point k of pts is stored
+//   v.store_desc(id, e, d0, d1), v.normal(id), v.store_depth(id, mx, mn)   the elected row e with its descriptor; the normal; the depth range
+
+// mNormalVector = normal / n (MapPoint.cc:389) and the depth range (:379-388), written by one lane
+template <class V>
+__device__ __forceinline__ void mp_store_geometry(const V& v, const MpuPoint& pt, int id, float sx, float sy, float sz) {
+  float mx, mn;
+  mp_geometry(pt.M, sx, sy, sz, v.b.slots[pt.ref_slot], pt.x, pt.y, pt.z, pt.sf_level, pt.sf_last, v.normal(id), mx, mn);
+  v.store_depth(id, mx, mn);
+}
+
+// The small points of one width class: W lanes per point, a block of 256 threads serves 256 / W points of v.list; sd: 2 x 256 uint4 of LDS
+template <int W, class V>
+__device__ __forceinline__ void mp_small_body(const V& v, uint4* sd) {
+  if (blockIdx.x * (256 / W) >= v.n) return;   // workgroup-uniform: a grid sized for the worst case
+  const int t = threadIdx.x, r = t % W, g = t / W, gbase = (t & 63) - r;   // gbase: the group's first lane in the wavefront
+  const int kk = blockIdx.x * (256 / W) + g;
+  const bool has = kk < v.n;
+  const int k = has ? v.list[kk] : 0;
+  MpuPoint pt;
+  if (has) pt = v.b.pts[k];
+  else { pt.M = pt.Me = 0; pt.what = 0; pt.x = pt.y = pt.z = 0.f; }
+  const int id = has ? v.id(k) : 0;
+  const bool elect = (pt.what & 1) && pt.Me > 0, geom = (pt.what & 2) && pt.M > 0;
+  uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
+  if (elect && r < pt.Me) {
+    const int row = v.b.el_row[pt.el_off + r];
+    d0 = v.b.rows[2 * (size_t)row];
+    d1 = v.b.rows[2 * (size_t)row + 1];
+  }
+  sd[2 * t] = d0;
+  sd[2 * t + 1] = d1;
+  __syncthreads();
+  if (elect) {
+    const uint32_t key = mp_elect_small<W>(d0, d1, sd + 2 * (t - r), pt.Me, r);
+    if (r == 0) {
+      const int e = (int)(key & 0xFFFF);
+      v.store_desc(id, e, sd[2 * (t + e)], sd[2 * (t + e) + 1]);
+    }
+  }
+  // the normal: lane r forms the term of observation r, every lane of the group sums the group's terms in observation order
+  float tx = 0.f, ty = 0.f, tz = 0.f;
+  if (geom && r < pt.M) normal_term(v.b.slots[v.b.obs_slot[pt.obs_off + r]], pt.x, pt.y, pt.z, tx, ty, tz);
+  float sx, sy, sz;
+  mp_normal_sum_small<W>(tx, ty, tz, gbase, pt.M, sx, sy, sz);
+  if (geom && r == 0) mp_store_geometry(v, pt, id, sx, sy, sz);
+}
+
+// The large points: one wavefront strides over the v.n entries of large_blocks, (k, first election row) or (k, -1) for the point's normal
+// and depth; blocks publish their (median << 16 | row) minimum in large_key[k].  hist: 64 x MPU_HIST_WORDS words of LDS
+template <class V>
+__device__ __forceinline__ void mp_large_body(const V& v, uint32_t* hist) {
+  const int lane = threadIdx.x;
+  for (int bi = blockIdx.x; bi < v.n; bi += gridDim.x) {
+    const int2 blk = v.b.large_blocks[bi];
+    const int k = blk.x, row0 = blk.y;
+    const MpuPoint pt = v.b.pts[k];
+    if (row0 < 0) {
+      // UpdateNormalAndDepth: 64 terms at a time, summed in observation order by every lane (the same value in each)
+      float sx, sy, sz;
+      mp_normal_sum_large(v.b.slots, v.b.obs_slot, pt.obs_off, pt.M, pt.x, pt.y, pt.z, lane, sx, sy, sz);
+      if (lane == 0) mp_store_geometry(v, pt, v.id(k), sx, sy, sz);
+      continue;
+    }
+    const uint32_t key = mp_elect_block(v.b.rows, v.b.el_row, pt.el_off, pt.Me, row0, lane, hist);   // each lane clears its own histogram
+    if (lane == 0) atomicMin(&v.b.large_key[k], key);
+  }
+}
+
+// The winner's descriptor row of the large points v.list[0 .. v.n), a thread per point
+template <class V>
+__device__ __forceinline__ void mp_finish_body(const V& v) {
+  for (int i = blockIdx.x * 64 + threadIdx.x; i < v.n; i += gridDim.x * 64) {
+    const int k = v.list[i];
+    const MpuPoint pt = v.b.pts[k];
+    if (!(pt.what & 1) || pt.Me <= 0) continue;
+    const int e = (int)(v.b.large_key[k] & 0xFFFF), row = v.b.el_row[pt.el_off + e];
+    v.store_desc(v.id(k), e, v.b.rows[2 * (size_t)row], v.b.rows[2 * (size_t)row + 1]);
+  }
 }

@@ -19,81 +19,38 @@
 
 namespace {
 
-// mNormalVector = normal / n (MapPoint.cc:389) and the depth range (:379-388), written by one lane
-__device__ __forceinline__ void write_geometry(const MpuBufs& b, const MpuPoint& pt, int p, float sx, float sy, float sz) {
-  float mx, mn;
-  mp_geometry(pt.M, sx, sy, sz, b.slots[pt.ref_slot], pt.x, pt.y, pt.z, pt.sf_level, pt.sf_last, b.normal + 3 * (size_t)p, mx, mn);
-  b.dist[2 * (size_t)p] = mx;
-  b.dist[2 * (size_t)p + 1] = mn;
-}
+// the lists the host built, the results into the call's arrays: a point of pts is stored under its own index
+struct MpuView {
+  const MpuBufs& b;
+  const int32_t* list;
+  int n;
+  __device__ int id(int p) const { return p; }
+  __device__ void store_desc(int p, int e, const uint4& d0, const uint4& d1) const {
+    b.best[p] = e;
+    b.desc[2 * (size_t)p] = d0;
+    b.desc[2 * (size_t)p + 1] = d1;
+  }
+  __device__ float* normal(int p) const { return b.normal + 3 * (size_t)p; }
+  __device__ void store_depth(int p, float mx, float mn) const {
+    b.dist[2 * (size_t)p] = mx;
+    b.dist[2 * (size_t)p + 1] = mn;
+  }
+};
 
 // W lanes per point; a block of 256 threads serves 256 / W points of one width class
 template <int W>
 __global__ __launch_bounds__(256) void mpu_small_kernel(MpuBufs b, int off, int n) {
   __shared__ uint4 sd[2 * 256];
-  const int t = threadIdx.x, r = t % W, g = t / W, gbase = (t & 63) - r;   // gbase: the group's first lane in the wavefront
-  const int k = blockIdx.x * (256 / W) + g;
-  const bool has = k < n;
-  const int p = has ? b.small_order[off + k] : 0;
-  MpuPoint pt;
-  if (has) pt = b.pts[p];
-  else { pt.M = pt.Me = 0; pt.what = 0; pt.x = pt.y = pt.z = 0.f; }
-  const bool elect = (pt.what & 1) && pt.Me > 0, geom = (pt.what & 2) && pt.M > 0;
-  uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
-  if (elect && r < pt.Me) {
-    const int row = b.el_row[pt.el_off + r];
-    d0 = b.rows[2 * (size_t)row];
-    d1 = b.rows[2 * (size_t)row + 1];
-  }
-  sd[2 * t] = d0;
-  sd[2 * t + 1] = d1;
-  __syncthreads();
-  if (elect) {
-    const uint32_t key = mp_elect_small<W>(d0, d1, sd + 2 * (t - r), pt.Me, r);
-    if (r == 0) {
-      const int e = (int)(key & 0xFFFF);
-      b.best[p] = e;
-      b.desc[2 * (size_t)p] = sd[2 * (t + e)];
-      b.desc[2 * (size_t)p + 1] = sd[2 * (t + e) + 1];
-    }
-  }
-  // the normal: lane r forms the term of observation r, every lane of the group sums the group's terms in observation order
-  float tx = 0.f, ty = 0.f, tz = 0.f;
-  if (geom && r < pt.M) normal_term(b.slots[b.obs_slot[pt.obs_off + r]], pt.x, pt.y, pt.z, tx, ty, tz);
-  float sx, sy, sz;
-  mp_normal_sum_small<W>(tx, ty, tz, gbase, pt.M, sx, sy, sz);
-  if (geom && r == 0) write_geometry(b, pt, p, sx, sy, sz);
+  mp_small_body<W>(MpuView{b, b.small_order + off, n}, sd);
 }
 
-// one wavefront per block: (p, first election row) or (p, -1) for the point's normal and depth
+// one wavefront per block of large_blocks
 __global__ __launch_bounds__(64) void mpu_large_kernel(MpuBufs b) {
   __shared__ uint32_t hist[64 * MPU_HIST_WORDS];
-  const int2 blk = b.large_blocks[blockIdx.x];
-  const int p = blk.x, row0 = blk.y, lane = threadIdx.x;
-  const MpuPoint pt = b.pts[p];
-  if (row0 < 0) {
-    // UpdateNormalAndDepth: 64 terms at a time, summed in observation order by every lane (the same value in each)
-    float sx, sy, sz;
-    mp_normal_sum_large(b.slots, b.obs_slot, pt.obs_off, pt.M, pt.x, pt.y, pt.z, lane, sx, sy, sz);
-    if (lane == 0) write_geometry(b, pt, p, sx, sy, sz);
-    return;
-  }
-  const uint32_t key = mp_elect_block(b.rows, b.el_row, pt.el_off, pt.Me, row0, lane, hist);
-  if (lane == 0) atomicMin(&b.large_key[p], key);
+  mp_large_body(MpuView{b, nullptr, (int)gridDim.x}, hist);
 }
 
-__global__ __launch_bounds__(64) void mpu_finish_kernel(MpuBufs b, int n_large) {
-  const int k = blockIdx.x * 64 + threadIdx.x;
-  if (k >= n_large) return;
-  const int p = b.large_pts[k];
-  const MpuPoint pt = b.pts[p];
-  if (!(pt.what & 1) || pt.Me <= 0) return;
-  const int e = (int)(b.large_key[p] & 0xFFFF);
-  const int row = b.el_row[pt.el_off + e];
-  b.best[p] = e;
-  b.desc[2 * (size_t)p] = b.rows[2 * (size_t)row];
-  b.desc[2 * (size_t)p + 1] = b.rows[2 * (size_t)row + 1];
-}
+__global__ __launch_bounds__(64) void mpu_finish_kernel(MpuBufs b, int n_large) { mp_finish_body(MpuView{b, b.large_pts, n_large}); }
 
 }  // namespace
 

@@ -13,10 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "motionmodel_problem.h"
+#include "mpdb_device.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 __global__ __launch_bounds__(MM_END_BLOCK) void mm_end_frame_kernel(MmEnd e) {
   __shared__ int tot[4];   // cleaned, dropped, kept, the largest octave kept
@@ -68,21 +67,17 @@ __device__ __forceinline__ bool is_query(const MmGather& g, int i) {
 __global__ __launch_bounds__(MM_BLOCK) void mm_gather_kernel(MmGather g) {
   __shared__ int part[MM_BLOCK / 64];
   __shared__ int own[MM_BLOCK / 64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, first = blockIdx.x * MM_BLOCK;
+  const int first = blockIdx.x * MM_BLOCK;
   // the queries in front of this workgroup's entries
   int pre = 0;
   for (int j = threadIdx.x; j < first; j += MM_BLOCK) pre += is_query(g, j) ? 1 : 0;
   for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
   const int i = first + threadIdx.x;
   const bool take = i < g.N && is_query(g, i);
-  const unsigned long long m = __ballot(take);
-  if (lane == 0) {
-    part[wave] = pre;
-    own[wave] = __popcll(m);
-  }
-  __syncthreads();
-  int pos = __popcll(m & lanes_below());
-  for (int w = 0; w < MM_BLOCK / 64; w++) pos += part[w] + (w < wave ? own[w] : 0);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = pre;
+  int total;
+  int pos = tile_rank<MM_BLOCK>(take, own, total);
+  for (int w = 0; w < MM_BLOCK / 64; w++) pos += part[w];
   if (take) {
     const size_t p = (size_t)g.last_ids[i];
     g.out_ids[pos] = (int32_t)p;
@@ -95,8 +90,7 @@ __global__ __launch_bounds__(MM_BLOCK) void mm_gather_kernel(MmGather g) {
     g.qfree[pos] = g.nobs[p] > 0 ? 0 : 1;   // DefORBmatcher.cc:381-383
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    int total = 0;
-    for (int w = 0; w < MM_BLOCK / 64; w++) total += part[w] + own[w];
+    for (int w = 0; w < MM_BLOCK / 64; w++) total += part[w];
     *g.out_count = total;
   }
 }
@@ -109,6 +103,6 @@ extern "C" hipError_t mm_end_frame_launch(const MmEnd& e, hipStream_t st) {
 }
 
 extern "C" hipError_t mm_gather_launch(const MmGather& g, hipStream_t st) {
-  if (g.N > 0) hipLaunchKernelGGL(mm_gather_kernel, dim3((g.N + MM_BLOCK - 1) / MM_BLOCK), dim3(MM_BLOCK), 0, st, g);
+  if (g.N > 0) hipLaunchKernelGGL(mm_gather_kernel, dim3(blocks_for(g.N, MM_BLOCK)), dim3(MM_BLOCK), 0, st, g);
   return hipGetLastError();
 }

@@ -1,7 +1,14 @@
-// The map point store dsh_mpdb as its translation units see it: dsh_localmap.cpp (dsh_mpdb_*, dsh_local_map_*), dsh_trackclose.cpp
-// (dsh_trackstate_*, dsh_track_close_frame), dsh_tmplswitch.cpp (dsh_need_new_template, dsh_template_switch and the read-backs) and
-// dsh_motionmodel.cpp (dsh_track_end_frame, dsh_track_last_frame, dsh_motion_model_search) and dsh_anchor.cpp (dsh_keyframe_anchors and the
-// two fields it reads: the key point index of an observation, the reference keyframe of a point).  The arrays in HBM, the host mirror that validates, and the checks the entry points share.
+// The map point store dsh_mpdb as its translation units see it: the arrays in HBM, the host mirror that validates, and the checks and
+// set-up the entry points share.
+//   dsh_localmap.cpp      dsh_mpdb_*, dsh_local_map_*
+//   dsh_trackclose.cpp    dsh_trackstate_*, dsh_track_close_frame
+//   dsh_tmplswitch.cpp    dsh_need_new_template, dsh_template_switch and the read-backs of points and facets
+//   dsh_motionmodel.cpp   dsh_track_end_frame, dsh_track_last_frame, dsh_motion_model_search
+//   dsh_anchor.cpp        dsh_keyframe_anchors and the two fields it reads: the key point index of an observation, the reference
+//                         keyframe of a point
+//   dsh_kfinsert.cpp      dsh_keyframe_process_new, dsh_point_store_upkeep
+//   dsh_pointerase.cpp    dsh_point_store_erase_observations, dsh_point_store_set_bad, dsh_point_store_cull and the read-backs of
+//                         observations and keyframe tables
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +21,7 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "localmap_problem.h"
+#include "obslist_problem.h"
 #include "tmplswitch_problem.h"
 #include "trackclose_problem.h"
 
@@ -134,12 +142,18 @@ inline hipError_t mpdb_reserve_keyframes(dsh_mpdb* db, long long need) {
   return hipSuccess;
 }
 
-// n distinct ids inside [0, count)
-inline std::string mpdb_ids_error(int n, const int32_t* ids, int32_t count, const char* what) {
+// n distinct ids inside [0, count): the first fault in sorted order.  With repeat_first (the erase calls) a repeat is named ahead of
+// an id outside the store, and that id is the first in the caller's order.
+inline std::string mpdb_ids_error(int n, const int32_t* ids, int32_t count, const char* what, bool repeat_first = false) {
   if (n < 0) return "n < 0";
   if (n > 0 && !ids) return std::string(what) + " array is NULL";
   std::vector<int32_t> s(ids, ids + n);
   std::sort(s.begin(), s.end());
+  if (repeat_first) {
+    for (int i = 1; i < n; i++)
+      if (s[i] == s[i - 1]) return std::string(what) + " " + std::to_string(s[i]) + " repeated in the batch";
+    s.assign(ids, ids + n);   // distinct: the loop below finds the range alone
+  }
   for (int i = 0; i < n; i++) {
     if (s[i] < 0 || s[i] >= count) return std::string(what) + " " + std::to_string(s[i]) + " outside the store";
     if (i > 0 && s[i] == s[i - 1]) return std::string(what) + " " + std::to_string(s[i]) + " repeated in the batch";
@@ -159,4 +173,25 @@ inline std::string mpdb_pair_error(const dsh_mpdb* db, int32_t point, int32_t sl
   if (point < 0 || point >= db->P) return "point id outside the store";
   if (slot < 0 || slot >= db->K) return "keyframe slot outside the store";
   return "";
+}
+
+// DSH_ERR_STATE of an entry point that reads the key point index of every observation
+inline int mpdb_unindexed_error(dsh_mpdb* db, const char* who) {
+  return dsh_fail(db->ctx, DSH_ERR_STATE,
+                  std::string(who) + ": the store holds " + std::to_string(db->unindexed.size()) +
+                      " live observation records without a key point index (dsh_mpdb_add_observations); add them with dsh_point_store_add_observations_indexed");
+}
+
+// The builder of observation lists on the store's log: the temporaries of n lists with at most cap_obs observations.  off, n_dev,
+// n_extra, kf and total stay with the caller.
+inline hipError_t mpdb_obs_lists(dsh_mpdb* db, ObsLists& a, size_t n, size_t cap_obs) {
+  a = ObsLists{};
+  a.log = db->d_log; a.log_idx = db->d_log_idx; a.R = db->R; a.n = (int32_t)n;
+  dsh_ctx_base* c = db->ctx;
+  hipError_t e;
+  if ((e = dsh_scratch_array(c, &a.sel_of, (size_t)db->P)) != hipSuccess || (e = dsh_scratch_array(c, &a.cnt, n)) != hipSuccess ||
+      (e = dsh_scratch_array(c, &a.fill, n)) != hipSuccess || (e = dsh_scratch_array(c, &a.raw_slot, cap_obs)) != hipSuccess ||
+      (e = dsh_scratch_array(c, &a.raw_idx, cap_obs)) != hipSuccess)
+    return e;
+  return hipSuccess;
 }

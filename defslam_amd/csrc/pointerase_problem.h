@@ -6,6 +6,7 @@
 
 #include "../../include/defslam_hip.h"
 #include "localmap_problem.h"
+#include "obslist_problem.h"
 
 #define PE_BLOCK 256
 #define PE_NO_SLOT 0x7fffffff   // cand of a point no live record names
@@ -59,17 +60,9 @@ struct PeBufs {
 // the read-back of observations: MapPoint::GetObservations of ids[n]
 struct PeObsBufs {
   int32_t P, n, cap;             // cap: entries of out_slot / out_idx
-  long long R;
-  const int2* log;
-  const int32_t* log_idx;
   const int32_t* ids;
-  int32_t* sel_of;               // P: position of the point in ids, else -1
-  int32_t* cnt;                  // n
-  int32_t* fill;                 // n
-  int32_t* raw_slot;             // every live record of the store fits: the observations in log order
-  int32_t* raw_idx;
+  ObsLists ol;                   // the lists of ids[n]: sel_of is the position of a point in ids, off the download block's n + 1 offsets
   PeHdr* hdr;
-  int32_t* out_ptr;              // n + 1: CSR offsets
   int32_t* out_slot;             // cap: by ascending slot; written only when total <= cap
   int32_t* out_idx;
 };

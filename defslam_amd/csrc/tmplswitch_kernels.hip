@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mappoint_device.h"
+#include "mpdb_device.h"
 #include "tmplswitch_problem.h"
 
 namespace {
@@ -36,7 +37,6 @@ __device__ __forceinline__ void ts_to_world(const float* T, float x, float y, fl
 
 __global__ __launch_bounds__(TS_BLOCK) void ts_classify_kernel(TcState s, TsSwitch k) {
   __shared__ int sx[TS_BLOCK], sy[TS_BLOCK], sp[TS_BLOCK];   // a chunk of key points: pixel, and the point held if it is not bad (else -1)
-  __shared__ int part[TS_BLOCK / 64][3];
   const int t = threadIdx.x, i = blockIdx.x * TS_BLOCK + t;
   const int ks = k.cols / 20, a = ks / 2;
   int qx = 0, qy = 0, p = -1;
@@ -78,17 +78,8 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_classify_kernel(TcState s, TsSwit
   }
   // n_new, n_moved, n_masked of the workgroup
   const bool f[3] = {c == TS_NEW, c == TS_HELD || c == TS_HELD_AGAIN, c == TS_MASKED};
-  const int wave = t >> 6, lane = t & 63;
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const int n = __popcll(__ballot(f[q]));
-    if (lane == 0) part[wave][q] = n;
-  }
-  __syncthreads();
+  const int n = block_sums<TS_BLOCK, 3>(f);
   if (t < 3) {
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < TS_BLOCK / 64; w++) n += part[w][t];
     if (t == 0) k.block_new[blockIdx.x] = n;
     int32_t* dst = t == 0 ? &k.counts->c.n_new : t == 1 ? &k.counts->c.n_moved : &k.counts->c.n_masked;
     if (n) atomicAdd(dst, n);
@@ -108,13 +99,9 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_create_kernel(TcState s, TsSwitch
   int j = 0;
 #pragma unroll
   for (int w = 0; w < TS_BLOCK / 64; w++) j += wsum[w];
-  __syncthreads();
   const int c = i < k.N ? k.cls[i] : -1;
-  const unsigned long long fresh = __ballot(c == TS_NEW);
-  if (lane == 0) wsum[wave] = __popcll(fresh);
-  __syncthreads();
-  for (int w = 0; w < wave; w++) j += wsum[w];
-  j += __popcll(fresh & ((1ull << lane) - 1ull));
+  int total;
+  j += tile_rank<TS_BLOCK>(c == TS_NEW, wsum, total);   // its first barrier: the sums in front have been read
   if (c != TS_HELD && c != TS_NEW) return;
 
   float w3[3];
@@ -195,40 +182,38 @@ __global__ __launch_bounds__(TS_BLOCK) void ts_get_embedding_kernel(TcState s, c
   }
 }
 
-inline dim3 blocks_for(long long n) { return dim3((unsigned)((n + TS_BLOCK - 1) / TS_BLOCK)); }
-
 }  // namespace
 
 static_assert(sizeof(dsh_template_switch_counts) == 24 && sizeof(TsCounts) == 32, "dsh_template_switch_counts is six int32");
 
 extern "C" hipError_t ts_classify_launch(const TcState& s, const TsSwitch& k, hipStream_t st) {
-  if (k.N > 0) hipLaunchKernelGGL(ts_classify_kernel, blocks_for(k.N), dim3(TS_BLOCK), 0, st, s, k);
+  if (k.N > 0) hipLaunchKernelGGL(ts_classify_kernel, blocks_for(k.N, TS_BLOCK), dim3(TS_BLOCK), 0, st, s, k);
   return hipGetLastError();
 }
 
 extern "C" hipError_t ts_create_launch(const TcState& s, const TsSwitch& k, hipStream_t st) {
-  if (k.N > 0) hipLaunchKernelGGL(ts_create_kernel, blocks_for(k.N), dim3(TS_BLOCK), 0, st, s, k);
+  if (k.N > 0) hipLaunchKernelGGL(ts_create_kernel, blocks_for(k.N, TS_BLOCK), dim3(TS_BLOCK), 0, st, s, k);
   return hipGetLastError();
 }
 
 extern "C" hipError_t ts_max_node_launch(const int32_t* nodes, int P, int32_t* out, hipStream_t st) {
-  if (P > 0) hipLaunchKernelGGL(ts_max_node_kernel, blocks_for(P), dim3(TS_BLOCK), 0, st, nodes, P, out);
+  if (P > 0) hipLaunchKernelGGL(ts_max_node_kernel, blocks_for(P, TS_BLOCK), dim3(TS_BLOCK), 0, st, nodes, P, out);
   return hipGetLastError();
 }
 
 extern "C" hipError_t ts_vertices_launch(const double* u, const double* v, const double* d, const float* Twc, int n, double* nodes_xyz, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(ts_vertices_kernel, blocks_for(n), dim3(TS_BLOCK), 0, st, u, v, d, Twc, n, nodes_xyz);
+  if (n > 0) hipLaunchKernelGGL(ts_vertices_kernel, blocks_for(n, TS_BLOCK), dim3(TS_BLOCK), 0, st, u, v, d, Twc, n, nodes_xyz);
   return hipGetLastError();
 }
 
 extern "C" hipError_t ts_get_points_launch(const TcState& s, const float* normal, const float* max_distance, const uint4* desc, const int32_t* ids, int n,
                                            float* xyz, float* onormal, float* omaxd, uint4* odesc, uint8_t* obad, hipStream_t st) {
   if (n > 0)
-    hipLaunchKernelGGL(ts_get_points_kernel, blocks_for(n), dim3(TS_BLOCK), 0, st, s, normal, max_distance, desc, ids, n, xyz, onormal, omaxd, odesc, obad);
+    hipLaunchKernelGGL(ts_get_points_kernel, blocks_for(n, TS_BLOCK), dim3(TS_BLOCK), 0, st, s, normal, max_distance, desc, ids, n, xyz, onormal, omaxd, odesc, obad);
   return hipGetLastError();
 }
 
 extern "C" hipError_t ts_get_embedding_launch(const TcState& s, const int32_t* ids, int n, int32_t* nodes, double* bary, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(ts_get_embedding_kernel, blocks_for(n), dim3(TS_BLOCK), 0, st, s, ids, n, nodes, bary);
+  if (n > 0) hipLaunchKernelGGL(ts_get_embedding_kernel, blocks_for(n, TS_BLOCK), dim3(TS_BLOCK), 0, st, s, ids, n, nodes, bary);
   return hipGetLastError();
 }

@@ -9,6 +9,7 @@
 // arrays (a point is held by a handful of key points, and integer adds commute: the result does not depend on the order).
 // The repose keeps the reference's double expression (b1 * x1 + b2 * x2) + b3 * x3 with every product and sum rounded (_rn intrinsics),
 // then one rounding to float; the frustum test is track_frustum.h, the one the local-map search applies.
+#include "mpdb_device.h"
 #include "track_frustum.h"
 #include "trackclose_problem.h"
 
@@ -17,20 +18,8 @@ namespace {
 // flags[c] of every thread of the workgroup counted into dst[c]; every thread of the workgroup calls it (it holds a barrier)
 template <int NC>
 __device__ __forceinline__ void block_count(const bool (&flags)[NC], int32_t* dst) {
-  __shared__ int part[TC_BLOCK / 64][NC];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < NC; c++) {
-    const int n = __popcll(__ballot(flags[c]));
-    if (lane == 0) part[wave][c] = n;
-  }
-  __syncthreads();
-  if (threadIdx.x < NC) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < TC_BLOCK / 64; w++) s += part[w][threadIdx.x];
-    if (s) atomicAdd(dst + threadIdx.x, s);
-  }
+  const int s = block_sums<TC_BLOCK, NC>(flags);
+  if (s) atomicAdd(dst + threadIdx.x, s);   // s is 0 in the threads from NC on
 }
 
 __global__ __launch_bounds__(TC_BLOCK) void tc_init_points_kernel(TcState s, int first, int n) {
@@ -170,64 +159,62 @@ __global__ __launch_bounds__(TC_BLOCK) void tc_cull_kernel(TcState s, const int3
   action[i] = a;
 }
 
-inline dim3 blocks_for(long long n) { return dim3((unsigned)((n + TC_BLOCK - 1) / TC_BLOCK)); }
-
 }  // namespace
 
 static_assert(sizeof(dsh_track_close_counts) == 32, "dsh_track_close_counts is eight int32");
 
 extern "C" hipError_t tc_init_points_launch(const TcState& s, int first, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_init_points_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, s, first, n);
+  if (n > 0) hipLaunchKernelGGL(tc_init_points_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, first, n);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_add_by_index_launch(int32_t* dst, const int32_t* src, int stride, int32_t delta, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_add_by_index_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, dst, src, stride, delta, n);
+  if (n > 0) hipLaunchKernelGGL(tc_add_by_index_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, dst, src, stride, delta, n);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_add_by_record_launch(int32_t* dst, const int32_t* src, const int32_t* idx, int32_t delta, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_add_by_record_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, dst, src, idx, delta, n);
+  if (n > 0) hipLaunchKernelGGL(tc_add_by_record_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, dst, src, idx, delta, n);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_visible_launch(int32_t* visible, const int32_t* cnt, int P_cnt, const int32_t* local_ids, const int32_t* inview, int Q,
                                         const int32_t* refused, hipStream_t st) {
   const int top = P_cnt > Q ? P_cnt : Q;
-  if (top > 0) hipLaunchKernelGGL(tc_visible_kernel, blocks_for(top), dim3(TC_BLOCK), 0, st, visible, cnt, P_cnt, local_ids, inview, Q, refused);
+  if (top > 0) hipLaunchKernelGGL(tc_visible_kernel, blocks_for(top, TC_BLOCK), dim3(TC_BLOCK), 0, st, visible, cnt, P_cnt, local_ids, inview, Q, refused);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_set_embedding_launch(const TcState& s, const int32_t* ids, const int32_t* src_nodes, const double* src_bary, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_set_embedding_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, s, ids, src_nodes, src_bary, n);
+  if (n > 0) hipLaunchKernelGGL(tc_set_embedding_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, ids, src_nodes, src_bary, n);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_set_counters_launch(const TcState& s, const int32_t* ids, const int32_t* visible, const int32_t* found, int n, hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_set_counters_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, s, ids, visible, found, n);
+  if (n > 0) hipLaunchKernelGGL(tc_set_counters_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, ids, visible, found, n);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_get_launch(const TcState& s, const int32_t* ids, int n, int32_t* visible, int32_t* found, int32_t* nobs, float* xyz,
                                     hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_get_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, s, ids, n, visible, found, nobs, xyz);
+  if (n > 0) hipLaunchKernelGGL(tc_get_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, ids, n, visible, found, nobs, xyz);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_repose_launch(const TcState& s, int P, const double* node_xyz, int32_t* n_moved, hipStream_t st) {
-  if (P > 0) hipLaunchKernelGGL(tc_repose_kernel, blocks_for(P), dim3(TC_BLOCK), 0, st, s, P, node_xyz, n_moved);
+  if (P > 0) hipLaunchKernelGGL(tc_repose_kernel, blocks_for(P, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, P, node_xyz, n_moved);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_close_launch(const TcState& s, const TcClose& k, hipStream_t st) {
-  if (k.node_xyz && k.P > 0) hipLaunchKernelGGL(tc_repose_kernel, blocks_for(k.P), dim3(TC_BLOCK), 0, st, s, k.P, k.node_xyz, &k.counts->n_moved);
-  if (k.N > 0) hipLaunchKernelGGL(tc_frame_kernel, blocks_for(k.N), dim3(TC_BLOCK), 0, st, s, k);
-  if (k.n_ref > 0) hipLaunchKernelGGL(tc_frustum_kernel, blocks_for(k.n_ref), dim3(TC_BLOCK), 0, st, s, k);
+  if (k.node_xyz && k.P > 0) hipLaunchKernelGGL(tc_repose_kernel, blocks_for(k.P, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, k.P, k.node_xyz, &k.counts->n_moved);
+  if (k.N > 0) hipLaunchKernelGGL(tc_frame_kernel, blocks_for(k.N, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, k);
+  if (k.n_ref > 0) hipLaunchKernelGGL(tc_frustum_kernel, blocks_for(k.n_ref, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, k);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tc_cull_launch(const TcState& s, const int32_t* ids, const int32_t* first_kf, int32_t current_kf, int n, uint8_t* action,
                                      hipStream_t st) {
-  if (n > 0) hipLaunchKernelGGL(tc_cull_kernel, blocks_for(n), dim3(TC_BLOCK), 0, st, s, ids, first_kf, current_kf, n, action);
+  if (n > 0) hipLaunchKernelGGL(tc_cull_kernel, blocks_for(n, TC_BLOCK), dim3(TC_BLOCK), 0, st, s, ids, first_kf, current_kf, n, action);
   return hipGetLastError();
 }

@@ -143,6 +143,46 @@ def test_keyframes_with_no_and_one_key_point(gpu_ctx, table):
     ks.close()
 
 
+def wide_table(n):
+    """A table of n entries over n + 10 points: every ninth entry empty, the point of entry 3 again in entry 66 and in the entry before
+    the last, the point of entry 70 % n again in the last."""
+    t = [int(p) for p in np.random.default_rng(n).permutation(n + 10)[:n]]
+    for i in range(8, n, 9):
+        t[i] = -1
+    t[66], t[n - 2], t[n - 1] = t[3], t[3], t[70 % n]
+    return t
+
+
+@pytest.mark.parametrize("n", [70, 300])
+def test_a_table_that_crosses_the_wavefronts_and_tiles_of_the_classify_kernel(gpu_ctx, n):
+    """A new keyframe of 70 and one of 300 key points: the ordered compaction of the added entries runs over more than one wavefront and
+    more than one tile of 256 entries.  Added entries lie on both sides of entry 64 and of entry 256; a point is held by three entries,
+    some are bad, one observes the keyframe already."""
+    table = wide_table(n)
+    m, slot = KI.random_model(40 + n, K=6, N=40, P=n + 10, p_bad_point=0.1, new_table=table)
+    ks, st = stores_from(gpu_ctx, m, points=8, keyframes=2, observations=16)
+    R0 = len(m.log)
+    g = process_both(st, ks, m, slot)
+    action = g.action.tolist()
+    added_at = [i for i, a in enumerate(action) if a == KI.ADDED]
+    for edge in (64, 256)[:1 if n == 70 else 2]:
+        assert {edge - 1, edge, edge + 1} & set(added_at) and min(added_at) < edge - 1 and max(added_at) > edge + 1
+    assert action.count(KI.BAD_POINT) >= 3 and action.count(KI.EMPTY) == len(range(8, n, 9)) and action[1] == KI.RECENT
+    assert not m.bad[table[3]] and action[3] == KI.ADDED and action[66] == action[n - 2] == KI.RECENT
+    # the records the call appended, in entry order, and every point's observations read back
+    assert [(r[0], r[1], r[2]) for r in m.log[R0:]] == [(table[i], slot, i) for i in added_at] and g.added.tolist() == [table[i] for i in added_at]
+    o = st.observations()
+    for p in range(n + 10):
+        assert list(o.of(p).items()) == sorted(m.observations(p)), p
+    assert st.keyframe_table(slot).tolist() == table
+    check_store(st, m)
+    g2 = process_both(st, ks, m, slot)                                   # again: nothing is added, the added entries are recent now
+    assert g2.n_added == 0 and g2.n_recent == g.n_recent + g.n_added
+    check_store(st, m)
+    st.close()
+    ks.close()
+
+
 def test_bad_keyframes_some_all_and_the_statuses_by_id(gpu_ctx):
     """Case 5: the election skips bad keyframes, the normal does not; with every observing keyframe bad the descriptor stays and the
     geometry is still computed.  Case 7: no reference keyframe.  The point store's flag is the one read, not the keyframe store's."""

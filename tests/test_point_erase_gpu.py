@@ -127,6 +127,40 @@ def test_a_log_that_had_grown_and_holds_blanks_and_the_mirror_afterwards(gpu_ctx
     st.close()
 
 
+def test_read_back_of_points_with_more_than_one_wavefront_of_observations(gpu_ctx):
+    """70 keyframes of 4 key points.  Points observed by 70, 65, 64, 1 and 0 keyframes and a few ordinary ones, the records added in
+    shuffled order; an erase batch first leaves blanks in the log, one of them inside the list of 65.  The rank by slot then runs over
+    lists of more than, exactly and less than a wavefront of 64 observations."""
+    K = 70
+    rm = PE.EraseRefMap()
+    for _ in range(K):
+        rm.add_keyframe([-1] * 4)
+    # point -> (key point index, keyframes): 0 all 70; 1 has 66 and loses one; 2 has 64; 3 one; 4 none; 5 .. 8 ordinary, in entry 3
+    seen = {0: (0, range(K)), 1: (1, range(66)), 2: (2, range(6, K)), 3: (3, [50]), 4: (3, []), 5: (3, [0, 10, 20, 30, 40]), 6: (3, [1, 11, 21]),
+            7: (3, [2, 12, 22, 32]), 8: (3, [3, 13])}
+    pairs = []
+    for p, (i, kfs) in seen.items():
+        assert rm.add_point(ref=min(kfs, default=-1)) == p
+        for kf in kfs:
+            assert rm.kfs[kf]["mvpMapPoints"][i] == -1
+            rm.kfs[kf]["mvpMapPoints"][i] = p
+            pairs.append((p, kf, i))
+    for j in np.random.default_rng(17).permutation(len(pairs)):
+        rm.add_observation(*pairs[int(j)])
+    st = store_from(gpu_ctx, rm, points=4, keyframes=2, observations=32)
+    g = erase_both(st, rm, [1, 5, 6], [30, 20, 11], True, "blanks")      # point 6 goes from 3 to 2 observations: bad, all its records blank
+    assert g.status.tolist() == [1, 1, 2] and g.counts.n_records == 5
+    want = [len(rm.observations(p)) for p in range(9)]
+    assert want == [70, 65, 64, 1, 0, 4, 0, 4, 2]
+    for ids in (list(range(9)), [8, 2, 4, 0, 6, 1], [1]):
+        o = st.observations(ids)
+        assert o.ptr.tolist() == np.concatenate([[0], np.cumsum([want[p] for p in ids])]).tolist(), ids
+        assert len(o.slots) == len(o.idx) == o.ptr[-1]
+        for i, p in enumerate(ids):
+            assert o.of(i) == rm.observations(p), (ids, p)
+    st.close()
+
+
 def test_cull_equals_trackstate_cull_and_erases_the_records(gpu_ctx):
     rm = PE.long_scene(seed=4, K=10, N=160, P=300)
     rm.points[7]["mnFound"], rm.points[7]["mnVisible"] = 2, 5          # 0.4f exactly: stays
