@@ -96,7 +96,7 @@ struct dsh_ctx_base {
   std::string err;
   std::vector<dsh_store*> stores;   // device-resident stores created on this context: dsh_destroy detaches them (dsh_detach_stores)
 };
-dsh_ctx_base* dsh_base(dsh_ctx* ctx);   // the opaque handle of the ABI as its base (dsh_api.cpp, where dsh_ctx is complete)
+dsh_ctx_base* dsh_base(dsh_ctx* ctx);   // the opaque handle of the ABI as its base (dsh_api.cpp; dsh_ctx is complete in dsh_sft_ctx.h)
 namespace dsh { struct TemplateHost; }
 // the context's current template when it was built from facets, else null (a store call that embeds reaches it through its context)
 const dsh::TemplateHost* dsh_facet_template(dsh_ctx_base* c);

@@ -37,9 +37,9 @@ __device__ __forceinline__ void sftb_ctl_lds(char* smem, Ctl*& ctl, double*& red
 }
 
 // counters (zeroed by the host in front of INIT): [0] finished problems, [1] FACTOR's work counter, [2] entries of the LIN list, [3] LIN's work
-// counter, [5] the tail kernel's work counter, [7] rounds that ran, [8] factorisations by FACTOR launches, [9] linearisations by LIN launches, [6] tail mode: few enough problems are left (B - counters[0] <= tail_below, decided by the
-// first kernel of a round from the count the previous round left, so the switch does not depend on how the host groups its launches):
-// the phase kernels leave at their first instruction, the tail kernel runs the rest
+// counter, [5] the tail kernel's work counter, [7] rounds that ran, [8] factorisations by FACTOR launches, [9] linearisations by LIN launches, [6] tail mode: few enough problems are left (B - counters[0] <= tail_below; raised by INIT, by the
+// LIN kernel of a round or by the tail launch itself, each from the count that only grows, so the switch does not depend on how the host groups
+// its launches): the phase kernels leave at their first instruction, the tail kernel runs the rest
 __global__ __launch_bounds__(64 * SFTB_NW, 2) void sftb_init_kernel(const SftDev* __restrict__ probs, SftRun* __restrict__ runs, int* __restrict__ counters, int* __restrict__ lin_list, int tail_below) {
   const SftDev& P = probs[blockIdx.x];
   if (blockIdx.x == 0 && threadIdx.x == 0 && (int)gridDim.x <= tail_below) counters[6] = 1;

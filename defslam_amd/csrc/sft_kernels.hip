@@ -3051,7 +3051,7 @@ __global__ __launch_bounds__(64 * NW, SFT_WAVES_PER_EU) void sft_sc_kernel(const
 // its coupling rows), every rank solves that reduced system, back-substitutes its own part, and a second all-reduce assembles the
 // update.  Residuals, Jacobians and the Levenberg-Marquardt control are replicated (every rank holds the whole state and evaluates all
 // edges: identical numbers, identical decisions, no collective for the control); what is partitioned is the factorisation, i.e. where
-// the time goes.  Phases, sequenced by the host between the collectives (dsh_api.cpp: cn_solve):
+// the time goes.  Phases, sequenced by the host between the collectives (dsh_multi.cpp: cn_solve):
 //   LIN  linearise (both parts' band matrices), initial damping        FAC  push, factor the rank's part -> its exchange buffer
 //   -- all-reduce of the exchange buffers into the reduced problem --
 //   SOL  reduced factor + solve, back substitution of the rank's part, its piece of the update in the natural ordering (zeros elsewhere)
@@ -3409,7 +3409,7 @@ extern "C" hipError_t sft_sc_local_reduce(SftSc* const* d_ptrs, int G, hipStream
   return hipGetLastError();
 }
 
-// `configured` (two slots of the caller's per-DEVICE table, dsh_api.cpp: LdsMarks): the largest dynamic LDS size the two kernels have been
+// `configured` (two slots of the caller's per-DEVICE table, dsh_sft_ctx.h: LdsMarks): the largest dynamic LDS size the two kernels have been
 // enabled for on that device by anybody in this process -- the function attribute belongs to (device, kernel): it is only ever raised,
 // under the caller's lock, so that two contexts on one GPU cannot lower each other's setting.
 extern "C" hipError_t sft_lm_launch(const SftDev* d_probs, int B, int max_kd, size_t jl_doubles, int nw, size_t* configured, hipStream_t stream) {

@@ -213,7 +213,7 @@ struct SftDev {
   SftPart part[4];
 };
 
-// ---- launchers of sft_kernels.hip (called from dsh_api.cpp), declared once: sft_kernels.hip includes this header too
+// ---- launchers of sft_kernels.hip (called from dsh_api.cpp and dsh_multi.cpp), declared once: sft_kernels.hip includes this header too
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 extern "C" size_t sft_lm_kernel_lds_bytes(int kd, size_t jl_doubles);

@@ -531,7 +531,7 @@ def ConnectedPoseOptimizationGroup(ctx0: Context, ctx1: Context, frames: Sequenc
 
 
 def two_sided_cut(Dn: int, kd: int):
-    """The cut of the two-sided factorisation / the connected-mesh mode (dsh_api.cpp, SftPart): (c0, s, n1p, pad) -- part 0 = scalars
+    """The cut of the two-sided factorisation / the connected-mesh mode (sft_plan.cpp, SftPart): (c0, s, n1p, pad) -- part 0 = scalars
     [0, c0), separator [c0, c0 + s) with s = 16 ceil(kd / 16) >= the half-bandwidth, part 1 = the rest (reversed, behind `pad` identity
     scalars that align its separator rows to a tile boundary).  None when the band is too short to cut."""
     sT = -(-kd // 16)

@@ -196,6 +196,64 @@ def test_launch_shapes_between_latency_mode_and_rounds(gpu_ctx, oracle_mod, shap
         _compare(frames[p], snaps[1][p][0], r.xyz, r.pose7, r.trace, r.outlier, r.rep_error, r.ret)
 
 
+@pytest.mark.parametrize("lab", [False, True], ids=["product", "lab"])
+def test_launch_shapes_in_turn_on_one_context_equal_fresh_contexts(request, lab):
+    """One context takes the launch shapes one after the other -- tail kernel alone, latency mode with four lanes, three lanes, rounds + tail
+    on the 9 x 14 mesh, then another template whose single problem is promoted and cut (C2), then the first shape again -- so every upload
+    lays its arena out over what another shape left and replaces the plan the run functions read.  Every step: the expected shape
+    (dsh_sft_batch_problem_info; in the lab build also lanes, cut and tile mode), and results bit for bit those of the same upload on a
+    context created for it."""
+    from defslam_amd import _lib, sft, synth
+    ctx = request.getfixturevalue("lab_ctx" if lab else "gpu_ctx")
+    cus = _lib.device_cus(0)
+    regs = (synth.REG_LAP, synth.REG_INEX, synth.REG_TEMP)
+    mesh = synth.make_grid_template(9, 14)
+    c2 = synth.make_grid_template(*synth.CONFIGS["C2"][:2])
+
+    def ragged(B):   # the frames of test_launch_shapes_between_latency_mode_and_rounds
+        syn = []
+        for p in range(B):
+            fr = synth.make_frame(mesh, 380 + 10 * (p % 5), p)
+            if p % 4 == 2:   # a partial view: another active set, another dimension in the same batch
+                keep = [c + 14 * r for r in range(9) for c in range(13)]
+                sel = np.all(np.isin(fr.obs_nodes, keep), axis=1)
+                for k in ["obs_nodes", "obs_bary", "obs_uv", "obs_invsig2"]:
+                    setattr(fr, k, getattr(fr, k)[sel])
+            syn.append(fr)
+        return syn
+
+    syn_all = ragged(2 * cus)
+    # (template, synthetic frames, wavefronts per problem reported, lanes, (tile mode, cut) of problem 0)
+    steps = [(mesh, syn_all[:cus // 2 + 1], 1, 1, (1, 0)), (mesh, syn_all[:1], 8, 4, (1, 0)), (mesh, syn_all[:cus // 4 + 1], 8, 3, (1, 0)),
+             (mesh, syn_all, 1, 1, (1, 0)), (c2, [synth.make_frame(c2, synth.CONFIGS["C2"][2], 7)], 8, 4, (2, 1)), (mesh, syn_all[:cus // 2 + 1], 1, 1, (1, 0))]
+
+    def solve(c, tmpl, syn, waves, lanes, solver):
+        B = len(syn)
+        assert lanes == (1 if waves == 1 else 4 if 4 * B <= cus else 3 if 3 * B <= cus else 2 if 2 * B <= cus else 1)   # DESIGN 4.0, this device
+        c.template_build(tmpl.xyz0, tmpl.facets)
+        frames = [sft.frame_from_synth(fr) for fr in syn]
+        c.batch_upload(frames, *regs, 1, 50)
+        assert int(c.problem_info(0)[1][7]) == waves
+        if lab:
+            info = c.solver_info(0)
+            assert (info["lanes"], info["tile_mode"], info["split"]) == (lanes,) + solver
+        c.batch_run()
+        return c.batch_download(), frames
+
+    for step, (tmpl, syn, waves, lanes, solver) in enumerate(steps):
+        inl, frames = solve(ctx, tmpl, syn, waves, lanes, solver)
+        fresh = sft.Context(0, lab=lab)
+        try:
+            inl_f, frames_f = solve(fresh, tmpl, syn, waves, lanes, solver)
+        finally:
+            fresh.close()
+        assert list(inl) == list(inl_f), step
+        for p, (a, b) in enumerate(zip(frames, frames_f)):
+            assert (a.iters, a.trials, a.status) == (b.iters, b.trials, b.status), (step, p)
+            for k in ("nodes_xyz", "pose7", "chi2_obs", "mvbOutlier", "trace"):
+                np.testing.assert_array_equal(getattr(a, k), getattr(b, k), err_msg=f"step {step}, problem {p}, {k}")
+
+
 @pytest.fixture(params=[0, -1], ids=["rounds_to_the_end", "product_default_tail"])
 def rounds_ctx(request, lab_ctx):
     """Both ways the throughput shape ends a step.  tail = 0: the rounds of phase kernels run to the END of every problem (the one-wavefront
