@@ -1,7 +1,7 @@
 // CI driver of integration/local_map_hip.h: a map (points, keyframes with tables and a spanning tree, observations) and a current frame
 // from a text file; the map goes into a MapPointStoreHIP, then DefTracking::TrackLocalMap's first two steps (DefTracking.cc:237-240) run
 // through UpdateLocalMapHIP and SearchLocalPointsStoreHIP, and what the reference's calls change is dumped.
-//   usage: localmap_shim_test <input.txt> <output.txt> [device] [timing.json reps]
+//   usage: localmap_shim_test <input.txt> <output.txt> [device] [timing.json reps]; exit codes: shim_driver.h
 // With a timing file the frame is then repeated `reps` times both ways and the medians are written: the device path above, and the way
 // the frame was done before the store existed -- UpdateLocalKeyFrames + UpdateLocalPoints on the host over the same objects
 // (std::map / std::set, below) followed by SearchLocalPointsHIP, which re-packs every local point.  The host lists are also compared
@@ -15,6 +15,7 @@
 #include <string>
 
 #include "local_map_hip.h"
+#include "shim_driver.h"
 #include "standin_localmap_scene.h"
 #include "standin_localmap_types.h"
 
@@ -31,11 +32,12 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc < 3) return 2;
-  std::ifstream in(argv[1]);
+static int drive(const DriverArgs& arg) {
+  dsh_ctx* ctx = arg.ctx;
+  std::FILE* out = arg.out;
+  std::ifstream in(arg.in[0]);
   LmScene scene;
-  if (!scene.read(in)) { std::fprintf(stderr, "bad input\n"); return 2; }
+  if (!scene.read(in)) return driver_bad_input(arg.in[0]);
   const int P = scene.P, K = scene.K, R = scene.R, N = scene.N;
   std::vector<LmMapPoint>& mps = scene.mps;
   std::vector<LmKeyFrame>& kfs = scene.kfs;
@@ -44,8 +46,6 @@ int main(int argc, char** argv) {
   LmFrame& cur = scene.cur;
   const std::vector<LmMapPoint*> frame0 = cur.mvpMapPoints;
 
-  dsh_ctx* ctx = nullptr;
-  if (dsh_create(&ctx, argc > 3 ? std::stoi(argv[3]) : 0) != DSH_OK) { std::fprintf(stderr, "dsh_create failed\n"); return 3; }
   typedef defslam_hip::MapPointStoreHIP<LmKeyFrame, LmMapPoint> Store;
   {
     Store store(ctx, 64, 2, 64);   // small on purpose: the store grows
@@ -54,15 +54,14 @@ int main(int argc, char** argv) {
     bool ok = store.ok() && store.AddMapPoints<LmFrame>(pts);
     for (int k = 0; ok && k < K; k++) ok = store.AddKeyFrame(&kfs[k]);
     ok = ok && store.AddObservations(obs_p, obs_k);
-    if (!ok) { std::fprintf(stderr, "filling the store: %s\n", dsh_last_error(ctx)); return 4; }
+    if (!ok) return driver_fail(ctx, "filling the store");
 
     std::vector<LmKeyFrame*> local_kfs;
     std::vector<LmMapPoint*> local_pts;
     std::vector<int32_t> votes;
     LmKeyFrame* ref_kf = nullptr;
     const int npts = defslam_hip::UpdateLocalMapHIP(store, cur, local_kfs, local_pts, ref_kf, &votes);
-    if (npts < 0) { std::fprintf(stderr, "UpdateLocalMapHIP: %s\n", dsh_last_error(ctx)); return 5; }
-    std::FILE* out = std::fopen(argv[2], "w");
+    if (npts < 0) return driver_fail(ctx, "UpdateLocalMapHIP");
     auto dump_frame = [&]() {
       for (int j = 0; j < N; j++) std::fprintf(out, "%d ", cur.mvpMapPoints[j] ? (int)(cur.mvpMapPoints[j] - mps.data()) : -1);
       std::fprintf(out, "\n");
@@ -82,7 +81,7 @@ int main(int argc, char** argv) {
     for (const LmMapPoint& p : mps) std::fprintf(out, "%lu ", p.mnTrackReferenceForFrame);
     std::fprintf(out, "\n");
     const int n2 = defslam_hip::SearchLocalPointsStoreHIP(store, cur, local_pts, 3.f);
-    if (n2 < 0) { std::fprintf(stderr, "SearchLocalPointsStoreHIP: %s\n", dsh_last_error(ctx)); return 6; }
+    if (n2 < 0) return driver_fail(ctx, "SearchLocalPointsStoreHIP");
     std::fprintf(out, "%d\n", n2);
     for (LmMapPoint* p : local_pts)
       std::fprintf(out, "%d %d %.9g %.9g %.9g %d %lu\n", p->mbTrackInView ? 1 : 0, p->mnTrackScaleLevel, p->mTrackProjX, p->mTrackProjY, p->mTrackViewCos,
@@ -105,10 +104,9 @@ int main(int argc, char** argv) {
     const int h_n = defslam_hip::SearchLocalPointsHIP<LmFrame, LmMapPoint>(ctx, cur, h_pts, 3.f);
     const int same = h_kfs == local_kfs && h_pts == local_pts && h_ref == ref_kf && h_n == n2 && cur.mvpMapPoints == frame_end;
     std::fprintf(out, "%d\n", same);
-    std::fclose(out);
 
-    if (argc > 5) {
-      const int reps = std::stoi(argv[5]);
+    if (arg.n_extra > 1) {
+      const int reps = std::stoi(arg.extra[1]);
       std::vector<double> t_host, t_shim, t_dev_up, t_dev_search;
       unsigned long id = 100;
       for (int r = 0; r < reps + 3; r++) {   // three warm-up rounds
@@ -116,23 +114,24 @@ int main(int argc, char** argv) {
         double t0 = now_ms();
         host_update_local_map(cur, all_kfs, h_kfs, h_pts, h_ref);
         double t1 = now_ms();
-        if (defslam_hip::SearchLocalPointsHIP<LmFrame, LmMapPoint>(ctx, cur, h_pts, 3.f) < 0) return 7;
+        if (defslam_hip::SearchLocalPointsHIP<LmFrame, LmMapPoint>(ctx, cur, h_pts, 3.f) < 0) return driver_fail(ctx, "SearchLocalPointsHIP");
         double t2 = now_ms();
         fresh_frame(id++);
         double t3 = now_ms();
-        if (defslam_hip::UpdateLocalMapHIP(store, cur, local_kfs, local_pts, ref_kf) < 0) return 7;
+        if (defslam_hip::UpdateLocalMapHIP(store, cur, local_kfs, local_pts, ref_kf) < 0) return driver_fail(ctx, "UpdateLocalMapHIP");
         double t4 = now_ms();
-        if (defslam_hip::SearchLocalPointsStoreHIP(store, cur, local_pts, 3.f) < 0) return 7;
+        if (defslam_hip::SearchLocalPointsStoreHIP(store, cur, local_pts, 3.f) < 0) return driver_fail(ctx, "SearchLocalPointsStoreHIP");
         double t5 = now_ms();
         if (r >= 3) { t_host.push_back(t1 - t0); t_shim.push_back(t2 - t1); t_dev_up.push_back(t4 - t3); t_dev_search.push_back(t5 - t4); }
       }
-      std::FILE* tj = std::fopen(argv[4], "w");
+      std::FILE* tj = std::fopen(arg.extra[0], "w");
       std::fprintf(tj, "{\"reps\": %d, \"keyframes\": %d, \"points\": %d, \"observations\": %d, \"frame_keypoints\": %d, \"local_points\": %zu, "
                    "\"host_update_ms\": %.4f, \"host_repack_search_ms\": %.4f, \"store_update_ms\": %.4f, \"store_search_ms\": %.4f}\n",
                    reps, K, P, R, N, local_pts.size(), median(t_host), median(t_shim), median(t_dev_up), median(t_dev_search));
       std::fclose(tj);
     }
   }
-  dsh_destroy(ctx);
   return 0;
 }
+
+int main(int argc, char** argv) { return run_driver(argc, argv, 1, drive); }

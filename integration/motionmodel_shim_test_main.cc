@@ -8,13 +8,14 @@
 //                  and the points without a facet, which DefORBmatcher's search skips (DefORBmatcher.cc:329-332)
 // Frame 1 is searched at the pose before the optimisation, frame 2 at the pose after it; before frame 2 the points of the scene's
 // late_bad list turn bad.  Every seventh held entry of a searched frame becomes an outlier before the frame ends.
-//   usage: motionmodel_shim_test <map.txt> <close.txt> <output.txt> [device]
+//   usage: motionmodel_shim_test <map.txt> <close.txt> <output.txt> [device]; exit codes: shim_driver.h
 #include <algorithm>
 #include <cstdio>
 #include <fstream>
 #include <string>
 
 #include "motion_model_hip.h"
+#include "shim_driver.h"
 #include "standin_localmap_scene.h"
 
 using namespace standin;
@@ -111,20 +112,18 @@ void dump_frame(std::FILE* out, const LmScene& sc, const LmFrame& F) {
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc < 4) return 2;
+static int drive(const DriverArgs& arg) {
+  dsh_ctx* ctx = arg.ctx;
+  std::FILE* out = arg.out;
   LmScene dev, host;                        // two copies of the same objects, one per way
   CloseData dd, hd;
   for (int w = 0; w < 2; w++) {
-    std::ifstream in(argv[1]), in2(argv[2]);
+    std::ifstream in(arg.in[0]), in2(arg.in[1]);
     LmScene& sc = w ? host : dev;
-    if (!sc.read(in) || !read_close(in2, sc, w ? hd : dd)) { std::fprintf(stderr, "bad input\n"); return 2; }
+    if (!sc.read(in) || !read_close(in2, sc, w ? hd : dd)) return driver_bad_input(arg.in[0]);
   }
   const int P = dev.P, K = dev.K;
-  dsh_ctx* ctx = nullptr;
-  if (dsh_create(&ctx, argc > 4 ? std::stoi(argv[4]) : 0) != DSH_OK) { std::fprintf(stderr, "dsh_create failed\n"); return 3; }
   typedef defslam_hip::MapPointStoreHIP<LmKeyFrame, LmMapPoint> Store;
-  std::FILE* out = std::fopen(argv[3], "w");
   {
     Store store(ctx, 64, 2, 64);   // small on purpose: the store grows
     std::vector<LmMapPoint*> pts(P);
@@ -133,7 +132,7 @@ int main(int argc, char** argv) {
     for (int k = 0; ok && k < K; k++) ok = store.AddKeyFrame(&dev.kfs[k]);
     ok = ok && store.AddObservations(dev.obs_p, dev.obs_k);
     ok = ok && store.SetEmbedding(pts, [&](LmNode* n) { return (int)(n - dd.nodes.data()); });
-    if (!ok) { std::fprintf(stderr, "filling the store: %s\n", dsh_last_error(ctx)); return 4; }
+    if (!ok) return driver_fail(ctx, "filling the store");
 
     for (int w = 0; w < 2; w++) {
       LmScene& sc = w ? host : dev;
@@ -158,12 +157,12 @@ int main(int argc, char** argv) {
           if (t == 2)
             for (int p : d.late_bad) {
               sc.mps[p].setBadFlag();
-              if (!w && !store.SetBad(&sc.mps[p])) return 5;
+              if (!w && !store.SetBad(&sc.mps[p])) return driver_fail(ctx, "SetBad");
             }
           float th_used = 0.f;
           const int n = w ? host_motion_model(ctx, F, last, th_used)
                           : defslam_hip::TrackWithMotionModelStoreHIP(store, F, last, true, &th_used);
-          if (n < 0) { std::fprintf(stderr, "frame %d, way %d, search: %s\n", t, w, dsh_last_error(ctx)); return 6; }
+          if (n < 0) { std::fprintf(stderr, "frame %d, way %d: ", t, w); return driver_fail(ctx, "search"); }
           std::fprintf(out, "%d %d\n", n, (int)th_used);
           dump_frame(out, sc, F);
           mark_outliers(F);
@@ -172,15 +171,15 @@ int main(int argc, char** argv) {
         if (w) {
           host_end_frame(F, last, c);
         } else {
-          if (defslam_hip::EndTrackedFrameHIP(store, F, &c) < 0) { std::fprintf(stderr, "frame %d, end: %s\n", t, dsh_last_error(ctx)); return 7; }
+          if (defslam_hip::EndTrackedFrameHIP(store, F, &c) < 0) { std::fprintf(stderr, "frame %d: ", t); return driver_fail(ctx, "EndTrackedFrameHIP"); }
           last = F;                                                  // mLastFrame = Frame(*mCurrentFrame)
         }
         std::fprintf(out, "%d %d %d\n", c.cleaned, c.dropped, c.kept);
         dump_frame(out, sc, F);
       }
     }
-    std::fclose(out);
   }
-  dsh_destroy(ctx);
   return 0;
 }
+
+int main(int argc, char** argv) { return run_driver(argc, argv, 2, drive); }

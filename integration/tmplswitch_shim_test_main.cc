@@ -6,7 +6,7 @@
 //                   UpdateNormalAndDepth of the new points, then the embedding with the library's host routine dsh_template_embed,
 //                   SetFacet / SetCoordinates / RecalculatePosition
 // Both use the template the caller builds first: dsh_surface_vertices -> the regular triangulation -> dsh_template_build.
-//   usage: tmplswitch_shim_test <map.txt> <switch.txt> <output.txt> [device]
+//   usage: tmplswitch_shim_test <map.txt> <switch.txt> <output.txt> [device]; exit codes: shim_driver.h
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -16,6 +16,7 @@
 #include <map>
 #include <string>
 
+#include "shim_driver.h"
 #include "standin_localmap_scene.h"
 #include "template_switch_hip.h"
 
@@ -224,28 +225,26 @@ void dump(std::FILE* out, int need, const dsh_template_switch_counts& c, const s
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc < 4) return 2;
+static int drive(const DriverArgs& arg) {
+  dsh_ctx* ctx = arg.ctx;
+  std::FILE* out = arg.out;
   LmScene dev, host;                        // two copies of the same objects, one per way
   SwitchData dd, hd;
   for (int w = 0; w < 2; w++) {
-    std::ifstream in(argv[1]), in2(argv[2]);
+    std::ifstream in(arg.in[0]), in2(arg.in[1]);
     LmScene& sc = w ? host : dev;
-    if (!sc.read(in) || !read_switch(in2, sc, w ? hd : dd)) { std::fprintf(stderr, "bad input\n"); return 2; }
+    if (!sc.read(in) || !read_switch(in2, sc, w ? hd : dd)) return driver_bad_input(arg.in[0]);
   }
   const int P = dev.P, K = dev.K;
-  dsh_ctx* ctx = nullptr;
-  if (dsh_create(&ctx, argc > 4 ? std::stoi(argv[4]) : 0) != DSH_OK) { std::fprintf(stderr, "dsh_create failed\n"); return 3; }
-  std::FILE* out = std::fopen(argv[3], "w");
   {
     // the caller's side of createTemplate: the vertices, the triangulation, the template constants
     dsh_surface_grid g;
     g.ctx = ctx; g.bbs = &dd.bbs; g.depth_ctrl = dd.ctrl.data(); g.Twc = dev.kfs[dd.ref].Twc; g.xs = dd.xs; g.ys = dd.ys;
     std::vector<double> xyz(3 * (size_t)dd.xs * dd.ys);
-    if (dsh_surface_vertices(&g, xyz.data()) != DSH_OK) { std::fprintf(stderr, "dsh_surface_vertices: %s\n", dsh_last_error(ctx)); return 4; }
+    if (dsh_surface_vertices(&g, xyz.data()) != DSH_OK) return driver_fail(ctx, "dsh_surface_vertices");
     Mesh mesh;
     mesh.build(xyz, dd.xs, dd.ys);
-    if (dsh_template_build(ctx, (int)mesh.nodes.size(), xyz.data(), (int)mesh.facets.size(), mesh.tri.data()) != DSH_OK) return 4;
+    if (dsh_template_build(ctx, (int)mesh.nodes.size(), xyz.data(), (int)mesh.facets.size(), mesh.tri.data()) != DSH_OK) return driver_fail(ctx, "dsh_template_build");
 
     // ---- the device way ----
     typedef defslam_hip::MapPointStoreHIP<LmKeyFrame, LmMapPoint> Store;
@@ -257,20 +256,17 @@ int main(int argc, char** argv) {
     int rc = DSH_OK;
     for (int k = 0; ok && k < K; k++) ok = store.AddKeyFrame(&dev.kfs[k]) && kfstore.Slot(&dev.kfs[k], &rc) == k;
     ok = ok && store.AddObservations(dev.obs_p, dev.obs_k);
-    if (!ok) { std::fprintf(stderr, "filling the stores: %s\n", dsh_last_error(ctx)); return 5; }
+    if (!ok) return driver_fail(ctx, "filling the stores");
     LmKeyFrame* ref = &dev.kfs[dd.ref];
     const int d_need = defslam_hip::NeedNewTemplateHIP(store, ref);
-    if (d_need < 0) { std::fprintf(stderr, "NeedNewTemplateHIP: %s\n", dsh_last_error(ctx)); return 6; }
+    if (d_need < 0) return driver_fail(ctx, "NeedNewTemplateHIP");
     std::deque<LmMapPoint> d_fresh;
     std::vector<LmMapPoint*> created;
     dsh_template_switch_counts dc;
     if (!defslam_hip::UpdateTemplateHIP(
             store, kfstore, ref,
             [&](const float* x3w) { d_fresh.emplace_back(); d_fresh.back().SetWorldPos(x3w); d_fresh.back().nVisible = 1; return &d_fresh.back(); },
-            [&](int a, int b, int c) { return mesh.facet_of(a, b, c); }, created, &dc)) {
-      std::fprintf(stderr, "UpdateTemplateHIP: %s\n", dsh_last_error(ctx));
-      return 7;
-    }
+            [&](int a, int b, int c) { return mesh.facet_of(a, b, c); }, created, &dc)) return driver_fail(ctx, "UpdateTemplateHIP");
     pts.insert(pts.end(), created.begin(), created.end());
     dump(out, d_need, dc, pts, *ref, mesh);
     const int d_again = defslam_hip::NeedNewTemplateHIP(store, ref);   // the new points are held now
@@ -282,11 +278,11 @@ int main(int argc, char** argv) {
     for (int p = 0; p < P; p++) all[p] = &host.mps[p];
     std::deque<LmMapPoint> h_fresh;
     dsh_template_switch_counts hc;
-    if (!host_update_template(ctx, *href, all, h_fresh, mesh, hc)) return 8;
+    if (!host_update_template(ctx, *href, all, h_fresh, mesh, hc)) return driver_fail(ctx, "the host way's updateTemplate");
     dump(out, h_need, hc, all, *href, mesh);
     std::fprintf(out, "%d %d\n", d_again, host_need_new_template(*href));
-    std::fclose(out);
   }
-  dsh_destroy(ctx);
   return 0;
 }
+
+int main(int argc, char** argv) { return run_driver(argc, argv, 2, drive); }

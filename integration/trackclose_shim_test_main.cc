@@ -5,7 +5,7 @@
 //   the host way    what the frame did before: UpdateLocalMap on the host, SearchLocalPointsHIP, DefMapPoint::RecalculatePosition of every
 //                   point with a facet (and, for the timing, dsh_mpdb_update_points of all of them), the loops of
 //                   DefTracking.cc:253-319 and LocalMapping.cc:173-199 over the pointer graph
-//   usage: trackclose_shim_test <map.txt> <close.txt> <output.txt> [device] [timing.json reps]
+//   usage: trackclose_shim_test <map.txt> <close.txt> <output.txt> [device] [timing.json reps]; exit codes: shim_driver.h
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -14,6 +14,7 @@
 #include <list>
 #include <string>
 
+#include "shim_driver.h"
 #include "standin_localmap_scene.h"
 #include "track_close_hip.h"
 
@@ -168,22 +169,20 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc < 4) return 2;
+static int drive(const DriverArgs& arg) {
+  dsh_ctx* ctx = arg.ctx;
+  std::FILE* out = arg.out;
   LmScene dev, host;                        // two copies of the same objects, one per way
   CloseData dd, hd;
   for (int w = 0; w < 2; w++) {
-    std::ifstream in(argv[1]), in2(argv[2]);
+    std::ifstream in(arg.in[0]), in2(arg.in[1]);
     LmScene& sc = w ? host : dev;
-    if (!sc.read(in) || !read_close(in2, sc, w ? hd : dd, true)) { std::fprintf(stderr, "bad input\n"); return 2; }
+    if (!sc.read(in) || !read_close(in2, sc, w ? hd : dd, true)) return driver_bad_input(arg.in[0]);
   }
   const int P = dev.P, K = dev.K, N = dev.N;
   std::vector<int> frame0(N);
   for (int j = 0; j < N; j++) frame0[j] = dev.cur.mvpMapPoints[j] ? (int)(dev.cur.mvpMapPoints[j] - dev.mps.data()) : -1;
-  dsh_ctx* ctx = nullptr;
-  if (dsh_create(&ctx, argc > 4 ? std::stoi(argv[4]) : 0) != DSH_OK) { std::fprintf(stderr, "dsh_create failed\n"); return 3; }
   typedef defslam_hip::MapPointStoreHIP<LmKeyFrame, LmMapPoint> Store;
-  std::FILE* out = std::fopen(argv[3], "w");
   {
     // ---- the device way ----
     Store store(ctx, 64, 2, 64);   // small on purpose: the store grows
@@ -195,29 +194,29 @@ int main(int argc, char** argv) {
     ok = ok && store.AddObservations(dev.obs_p, dev.obs_k);
     ok = ok && dsh_trackstate_set_counters(store.handle(), P, ids.data(), vis.data(), fnd.data()) == DSH_OK;   // a loaded map
     ok = ok && store.SetEmbedding(pts, [&](LmNode* n) { return (int)(n - dd.nodes.data()); });
-    if (!ok) { std::fprintf(stderr, "filling the store: %s\n", dsh_last_error(ctx)); return 4; }
+    if (!ok) return driver_fail(ctx, "filling the store");
     std::vector<LmKeyFrame*> local_kfs;
     std::vector<LmMapPoint*> local_pts;
     LmKeyFrame* ref_kf = nullptr;
     hold(dev, dd.prev, 7);                                           // the previous frame: its list becomes the reference list
-    if (defslam_hip::UpdateLocalMapHIP(store, dev.cur, local_kfs, local_pts, ref_kf) < 0) return 5;
+    if (defslam_hip::UpdateLocalMapHIP(store, dev.cur, local_kfs, local_pts, ref_kf) < 0) return driver_fail(ctx, "UpdateLocalMapHIP");
     for (int p : dd.late_bad) { dev.mps[p].setBadFlag(); store.SetBad(&dev.mps[p]); }
     hold(dev, frame0, 8);
-    if (defslam_hip::UpdateLocalMapHIP(store, dev.cur, local_kfs, local_pts, ref_kf) < 0) return 5;
-    if (defslam_hip::SearchLocalPointsStoreHIP(store, dev.cur, local_pts, 3.f) < 0) return 6;
+    if (defslam_hip::UpdateLocalMapHIP(store, dev.cur, local_kfs, local_pts, ref_kf) < 0) return driver_fail(ctx, "UpdateLocalMapHIP");
+    if (defslam_hip::SearchLocalPointsStoreHIP(store, dev.cur, local_pts, 3.f) < 0) return driver_fail(ctx, "SearchLocalPointsStoreHIP");
     after_optimisation(dev, dd);
     std::vector<LmNode*> nodes(dd.n_nodes);
     for (int n = 0; n < dd.n_nodes; n++) nodes[n] = &dd.nodes[n];
     dsh_track_close_counts dc;
-    if (!defslam_hip::CloseTrackedFrameHIP(store, dev.cur, nodes, false, dc)) { std::fprintf(stderr, "CloseTrackedFrameHIP: %s\n", dsh_last_error(ctx)); return 7; }
+    if (!defslam_hip::CloseTrackedFrameHIP(store, dev.cur, nodes, false, dc)) return driver_fail(ctx, "CloseTrackedFrameHIP");
     std::list<LmMapPoint*> d_recent = recent_list(dev);
     const int d_bad = defslam_hip::MapPointCullingHIP(store, d_recent, (unsigned long)dd.current_kf);
-    if (d_bad < 0) { std::fprintf(stderr, "MapPointCullingHIP: %s\n", dsh_last_error(ctx)); return 8; }
+    if (d_bad < 0) return driver_fail(ctx, "MapPointCullingHIP");
     dump(out, dev, dc, d_bad, d_recent);
     // the store's own counters and positions
     std::vector<int32_t> s_vis(P), s_fnd(P), s_obs(P);
     std::vector<float> s_xyz(3 * (size_t)P);
-    if (dsh_trackstate_get(store.handle(), P, ids.data(), s_vis.data(), s_fnd.data(), s_obs.data(), s_xyz.data()) != DSH_OK) return 9;
+    if (dsh_trackstate_get(store.handle(), P, ids.data(), s_vis.data(), s_fnd.data(), s_obs.data(), s_xyz.data()) != DSH_OK) return driver_fail(ctx, "dsh_trackstate_get");
     for (int p = 0; p < P; p++) std::fprintf(out, "%.9g %.9g %.9g %d %d %d\n", s_xyz[3 * p], s_xyz[3 * p + 1], s_xyz[3 * p + 2], s_fnd[p], s_vis[p], s_obs[p]);
 
     // ---- the host way, over the second copy ----
@@ -231,45 +230,45 @@ int main(int argc, char** argv) {
     hold(host, frame0, 8);
     h_ref_pts = h_pts;                                               // Tracking.cc:1475: SetReferenceMapPoints before the rebuild
     host_update_local_map(host.cur, all_kfs, h_kfs, h_pts, h_ref);
-    if (defslam_hip::SearchLocalPointsHIP<LmFrame, LmMapPoint>(ctx, host.cur, h_pts, 3.f) < 0) return 6;
+    if (defslam_hip::SearchLocalPointsHIP<LmFrame, LmMapPoint>(ctx, host.cur, h_pts, 3.f) < 0) return driver_fail(ctx, "SearchLocalPointsHIP");
     after_optimisation(host, hd);
     dsh_track_close_counts hc;
     host_close(host, h_ref_pts, false, hc);
     std::list<LmMapPoint*> h_recent = recent_list(host);
     const int h_bad = host_culling(h_recent, (unsigned long)hd.current_kf);
     dump(out, host, hc, h_bad, h_recent);
-    std::fclose(out);
 
-    if (argc > 6) {
+    if (arg.n_extra > 1) {
       // medians of closing the frame both ways (the counters drift with the repeats; the work per call does not)
-      const int reps = std::stoi(argv[6]);
+      const int reps = std::stoi(arg.extra[1]);
       std::vector<LmMapPoint*> facet_pts;
       for (LmMapPoint& m : host.mps)
         if (!m.isBad() && m.getFacet()) facet_pts.push_back(&m);
       Store parent(ctx, P, K, 64);                                   // the parent's store: positions are uploaded per frame
       std::vector<LmMapPoint*> hpts(P);
       for (int p = 0; p < P; p++) hpts[p] = &host.mps[p];
-      if (!parent.ok() || !parent.AddMapPoints<LmFrame>(hpts)) return 10;
+      if (!parent.ok() || !parent.AddMapPoints<LmFrame>(hpts)) return driver_fail(ctx, "the parent's store");
       std::vector<double> t_dev, t_host_repose, t_host_upload, t_host_loops;
       for (int r = 0; r < reps + 3; r++) {   // three warm-up rounds
         double t0 = now_ms();
-        if (!defslam_hip::CloseTrackedFrameHIP(store, dev.cur, nodes, false, dc)) return 7;
+        if (!defslam_hip::CloseTrackedFrameHIP(store, dev.cur, nodes, false, dc)) return driver_fail(ctx, "CloseTrackedFrameHIP");
         double t1 = now_ms();
         for (LmMapPoint* m : facet_pts) m->RecalculatePosition();
         double t2 = now_ms();
-        if (!parent.UpdatePositions<LmFrame>(facet_pts)) return 10;
+        if (!parent.UpdatePositions<LmFrame>(facet_pts)) return driver_fail(ctx, "UpdatePositions");
         double t3 = now_ms();
         host_close(host, h_ref_pts, false, hc, false);   // the loops alone: the repose was timed above
         double t4 = now_ms();
         if (r >= 3) { t_dev.push_back(t1 - t0); t_host_repose.push_back(t2 - t1); t_host_upload.push_back(t3 - t2); t_host_loops.push_back(t4 - t3); }
       }
-      std::FILE* tj = std::fopen(argv[5], "w");
+      std::FILE* tj = std::fopen(arg.extra[0], "w");
       std::fprintf(tj, "{\"reps\": %d, \"points\": %d, \"facet_points\": %zu, \"frame_keypoints\": %d, \"reference_points\": %zu, "
                    "\"device_close_ms\": %.4f, \"host_repose_ms\": %.4f, \"host_upload_ms\": %.4f, \"host_loops_ms\": %.4f}\n",
                    reps, P, facet_pts.size(), N, h_ref_pts.size(), median(t_dev), median(t_host_repose), median(t_host_upload), median(t_host_loops));
       std::fclose(tj);
     }
   }
-  dsh_destroy(ctx);
   return 0;
 }
+
+int main(int argc, char** argv) { return run_driver(argc, argv, 2, drive); }

@@ -1,77 +1,28 @@
-"""TEST INFRASTRUCTURE ONLY: a Python model of the two resident stores for dsh_keyframe_process_new and dsh_point_store_upkeep.
+"""TEST INFRASTRUCTURE ONLY: the restatement of dsh_keyframe_process_new and dsh_point_store_upkeep on the model of the two resident stores.
 
-It holds what the stores hold -- the points, the log of (point, slot, key point index) records with blanked erasures, the keyframes'
-tables, the reference keyframes, the point store's keyframe bad flags -- and drives tests/mappoint_ref.py one point at a time with the
-point's live observations by ASCENDING SLOT, whatever order the records arrived in.  Nothing in defslam_amd/ imports this module.
+On what the stores hold (tests/store_model.py) it drives tests/mappoint_ref.py one point at a time with the point's live observations by
+ASCENDING SLOT, whatever order the records arrived in.  Nothing in defslam_amd/ imports this module.
 """
 from __future__ import annotations
-
-from types import SimpleNamespace
 
 import numpy as np
 
 import mappoint_ref as R
+from store_model import MapModel
 
 DESCRIPTOR, NORMAL_DEPTH, BOTH = 1, 2, 3
 NO_OBS, NO_GOOD_DESC, NO_REF, SKIPPED_BAD = 1, 2, 4, 8
 EMPTY, BAD_POINT, ADDED, RECENT = 0, 1, 2, 3
 
 
-class StoreModel:
-    def __init__(self):
-        self.kfs = []            # SimpleNamespace(Ow, desc, octave, scale_factors, bad): bad is the POINT store's flag
-        self.tables = []         # per slot: list of point ids or -1
-        self.xyz, self.normal, self.max_distance, self.min_distance, self.desc, self.bad, self.ref, self.n_obs = [], [], [], [], [], [], [], []
-        self.log = []            # [point, slot, idx, live]: an erased record keeps its place, blanked
-        self._live = {}          # (point, slot) -> its live record
-        self._obs = []           # per point: slot -> idx of the live records
-
-    # ---- the mutations of the stores ----
-    def add_keyframe(self, Ow, desc, octave, scale_factors, table, bad=False):
-        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        assert len(table) == desc.shape[0] == len(octave)
-        self.kfs.append(SimpleNamespace(Ow=np.asarray(Ow, np.float32), desc=desc, octave=np.asarray(octave, np.int32),
-                                        scale_factors=np.asarray(scale_factors, np.float32), bad=bool(bad)))
-        self.tables.append([int(p) for p in table])
-        return len(self.kfs) - 1
-
-    def add_point(self, xyz, normal, max_distance, desc, ref=-1, bad=False):
-        self.xyz.append(np.asarray(xyz, np.float32))
-        self.normal.append(np.asarray(normal, np.float32))
-        self.max_distance.append(np.float32(max_distance))
-        self.min_distance.append(np.float32(0))
-        self.desc.append(np.asarray(desc, np.uint8))
-        self.bad.append(bool(bad))
-        self.ref.append(int(ref))
-        self.n_obs.append(0)
-        self._obs.append({})
-        return len(self.xyz) - 1
-
-    def live(self, p, s):
-        return (p, s) in self._live
-
-    def add_observation(self, p, s, idx):
-        assert not self.live(p, s)
-        self.log.append([int(p), int(s), int(idx), True])
-        self._live[(p, s)] = self.log[-1]
-        self._obs[p][int(s)] = int(idx)
-        self.n_obs[p] += 1
-
-    def erase_observation(self, p, s):
-        r = self._live.pop((p, s), None)
-        if r is not None:
-            r[3] = False
-            del self._obs[p][s]
-            self.n_obs[p] -= 1
-
-    def observations(self, p):
-        """The live observations of p as (slot, idx), by ascending slot."""
-        return sorted(self._obs[p].items())
+class StoreModel(MapModel):
+    """The model of the two stores with the upkeep of a point and the insertion of a new keyframe."""
 
     # ---- the upkeep ----
     def upkeep_point(self, p, what=BOTH):
         """-> status; writes desc / normal / max_distance / min_distance of point p where the reference would."""
-        if self.bad[p]:
+        pt = self.points[p]
+        if pt.bad:
             return SKIPPED_BAD
         obs = self.observations(p)
         if not obs:
@@ -79,54 +30,47 @@ class StoreModel:
         status = 0
         if all(self.kfs[s].bad for s, _ in obs):
             status |= NO_GOOD_DESC
-        ref = self.ref[p]
-        no_ref = ref < 0 or (ref not in dict(obs) and len(self.tables[ref]) == 0)
+        ref = pt.ref
+        no_ref = ref < 0 or (ref not in dict(obs) and len(self.kfs[ref].table) == 0)
         if no_ref:
             status |= NO_REF
         if what & DESCRIPTOR:
             _, row = R.compute_distinctive_descriptors(self.kfs, obs)
             if row is not None:
-                self.desc[p] = row
+                pt.desc = row
         if (what & NORMAL_DEPTH) and not no_ref:
-            self.normal[p], self.max_distance[p], self.min_distance[p] = R.update_normal_and_depth(self.kfs, self.xyz[p], obs, ref)
+            pt.normal, pt.max_distance, pt.min_distance = R.update_normal_and_depth(self.kfs, pt.xyz, obs, ref)
         return status
 
     def upkeep(self, ids, what=BOTH):
         return [self.upkeep_point(int(p), what) for p in ids]
 
     def embedded_ids(self, has_facet):
-        return [p for p in range(len(self.xyz)) if not self.bad[p] and has_facet[p]]
+        return [p for p, pt in enumerate(self.points) if not pt.bad and has_facet[p]]
 
     def process_new_keyframe(self, slot):
         """LocalMapping.cc:142-165 -> (action per entry, added points, statuses of the added points)."""
         action, added, status = [], [], []
-        for i, p in enumerate(self.tables[slot]):
+        for i, p in enumerate(self.kfs[slot].table):
             if p < 0:
                 action.append(EMPTY)
-            elif self.bad[p]:
+            elif self.points[p].bad:
                 action.append(BAD_POINT)
             elif self.live(p, slot):
                 action.append(RECENT)
             else:
-                self.add_observation(p, slot, i)
+                assert self.add_observation(p, slot, i)
                 status.append(self.upkeep_point(p))
                 added.append(p)
                 action.append(ADDED)
         return action, added, status
 
-    # ---- read-backs in the shape of the store's ----
-    def points(self):
-        n = len(self.xyz)
-        return dict(xyz=np.stack(self.xyz) if n else np.zeros((0, 3), np.float32), normal=np.stack(self.normal) if n else np.zeros((0, 3), np.float32),
-                    max_distance=np.array(self.max_distance, np.float32), desc=np.stack(self.desc) if n else np.zeros((0, 32), np.uint8),
-                    bad=np.array(self.bad, bool))
 
-
-def random_model(seed, K=6, N=6, P=20, levels=4, p_obs=0.5, p_bad_kf=0.2, p_bad_point=0.1, p_no_ref=0.0, new_table=None, shuffle=True):
+def random_model(seed, K=6, N=6, P=20, levels=4, p_obs=0.5, p_bad_kf=0.2, p_bad_point=0.1, p_no_ref=0.0, new_table=None, shuffle=True, cls=None):
     """K old keyframes with N key points each and P points that observe some of them, then a new keyframe whose table holds some of the
     points (one of them twice, one observing it already).  Records are appended in shuffled order, so log order and slot order differ."""
     rng = np.random.default_rng(seed)
-    m = StoreModel()
+    m = (cls or StoreModel)()                        # cls: a class that combines StoreModel with other restatements
     sf = (1.2 ** np.arange(levels)).astype(np.float32)
     for p in range(P):
         m.add_point(rng.normal(0, 1, 3).astype(np.float32) + np.float32([0, 0, 5]), rng.normal(0, 1, 3).astype(np.float32), np.float32(rng.uniform(1, 9)),
@@ -138,55 +82,24 @@ def random_model(seed, K=6, N=6, P=20, levels=4, p_obs=0.5, p_bad_kf=0.2, p_bad_
             if rng.random() < p_obs:
                 table[j] = int(p)
                 pairs.append((int(p), s, j))
-        m.add_keyframe(rng.normal(0, 1, 3).astype(np.float32), rng.integers(0, 256, (N, 32), dtype=np.uint8), rng.integers(0, levels, N), sf, table,
-                       bad=rng.random() < p_bad_kf)
+        m.add_keyframe(Ow=rng.normal(0, 1, 3).astype(np.float32), desc=rng.integers(0, 256, (N, 32), dtype=np.uint8), octave=rng.integers(0, levels, N),
+                       scale_factors=sf, table=table, bad=rng.random() < p_bad_kf)
     perm = rng.permutation(len(pairs))
     if shuffle:
         pairs = [pairs[i] for i in perm]
     for p, s, j in pairs:
-        m.add_observation(p, s, j)
+        assert m.add_observation(p, s, j)
     for p in range(P):
         seen = [s for s, _ in m.observations(p)]
-        m.ref[p] = -1 if (not seen and rng.random() < 0.5) or rng.random() < p_no_ref else int(rng.choice(seen)) if seen and rng.random() < 0.8 else int(rng.integers(0, K))
+        m.points[p].ref = -1 if (not seen and rng.random() < 0.5) or rng.random() < p_no_ref else int(rng.choice(seen)) if seen and rng.random() < 0.8 else int(rng.integers(0, K))
     if new_table is None:
         held = [int(p) for p in rng.permutation(P)[:max(N - 2, 1)]]
         new_table = (held + [held[0], -1])[:N] if N >= 3 else held[:N]
-    slot = m.add_keyframe(rng.normal(0, 1, 3).astype(np.float32), rng.integers(0, 256, (len(new_table), 32), dtype=np.uint8),
-                          rng.integers(0, levels, len(new_table)), sf, new_table)
+    slot = m.add_keyframe(Ow=rng.normal(0, 1, 3).astype(np.float32), desc=rng.integers(0, 256, (len(new_table), 32), dtype=np.uint8),
+                          octave=rng.integers(0, levels, len(new_table)), scale_factors=sf, table=new_table)
     if len(new_table) >= 3 and new_table[1] >= 0 and new_table[1] != new_table[0]:
-        m.add_observation(new_table[1], slot, 1)   # this point observes the new keyframe already
+        assert m.add_observation(new_table[1], slot, 1)   # this point observes the new keyframe already
     return m, slot
-
-
-def fill_stores(m: StoreModel, kf_store, st):
-    """The model's state into a mappoint.KeyFrameStore and a localmap.MapPointStore (records in the model's log order, erasures replayed)."""
-    from defslam_amd import mappoint
-    n = len(m.xyz)
-    if n:
-        st.add_points(np.stack(m.xyz), np.stack(m.normal), np.array(m.max_distance, np.float32), np.stack(m.desc), bad=np.array(m.bad, np.uint8))
-    for s, k in enumerate(m.kfs):
-        assert kf_store.add(mappoint.MpKeyFrame(k.Ow, k.desc, k.octave, k.scale_factors, bad=k.bad)) == s
-        assert st.add_keyframe(np.array(m.tables[s], np.int32), bad=k.bad) == s
-    if n:
-        st.set_reference_keyframes(np.arange(n), m.ref)
-    # the log in its order, blanked records too, in as few batches as the pairs allow: a pair that is in the batch already (erased and
-    # added again) closes the batch, and a batch's erased records are blanked right after it
-    batch, pairs = [], set()
-
-    def flush():
-        if batch:
-            st.add_observations([r[0] for r in batch], [r[1] for r in batch], idx=[r[2] for r in batch])
-            gone = [r for r in batch if not r[3]]
-            if gone:
-                st.erase_observations([r[0] for r in gone], [r[1] for r in gone])
-            batch.clear()
-    for r in m.log:
-        if (r[0], r[1]) in pairs:
-            flush()
-            pairs.clear()
-        pairs.add((r[0], r[1]))
-        batch.append(r)
-    flush()
 
 
 # ---- the scene of the GPU tests: every width class, the large path, a log that strides ---------------------------------------------------
@@ -249,8 +162,8 @@ def big_scene(seed=7, fillers=200, filler_obs=118, singles=0, ties=()):
         if tables[s_][j] < 0:
             tables[s_][j] = p
     for s_ in range(K_OLD):
-        m.add_keyframe(rng.normal(0, 1, 3).astype(np.float32), rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), rng.integers(0, levels, N_KP), sf,
-                       tables[s_], bad=s_ in BAD_SLOTS)
+        m.add_keyframe(Ow=rng.normal(0, 1, 3).astype(np.float32), desc=rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), octave=rng.integers(0, levels, N_KP),
+                       scale_factors=sf, table=tables[s_], bad=s_ in BAD_SLOTS)
     for t, (p, slots, two) in enumerate(names["ties"]):
         for rank, s_ in enumerate(slots):
             m.kfs[s_].desc[t] = two[rank % 2]
@@ -260,32 +173,32 @@ def big_scene(seed=7, fillers=200, filler_obs=118, singles=0, ties=()):
     again = next(r for r in pairs if r[0] == p33)
     for i, (p, s_, j) in enumerate(pairs):
         if (p, s_, j) == again:
-            m.add_observation(p, s_, (j + 1) % N_KP)
+            assert m.add_observation(p, s_, (j + 1) % N_KP)
             m.erase_observation(p, s_)
             names["again"] = (p, s_, j)
         elif i in blank:
-            m.add_observation(p, s_, j)
+            assert m.add_observation(p, s_, j)
             m.erase_observation(p, s_)
         else:
-            m.add_observation(p, s_, j)
-    m.add_observation(*again)
-    A = m.add_keyframe(rng.normal(0, 1, 3).astype(np.float32), rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), rng.integers(0, levels, N_KP), sf,
-                       count_pts[:6])
-    B = m.add_keyframe(rng.normal(0, 1, 3).astype(np.float32), rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), rng.integers(0, levels, N_KP), sf,
-                       count_pts[6:])
-    Ck = m.add_keyframe(rng.normal(0, 1, 3).astype(np.float32), rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), rng.integers(0, levels, N_KP), sf,
-                        [names["twice"], names["already"], names["bad_point"], -1, names["twice"], names["all_bad"]])
-    m.add_observation(names["already"], Ck, 1)
+            assert m.add_observation(p, s_, j)
+    assert m.add_observation(*again)
+    A = m.add_keyframe(Ow=rng.normal(0, 1, 3).astype(np.float32), desc=rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), octave=rng.integers(0, levels, N_KP),
+                       scale_factors=sf, table=count_pts[:6])
+    B = m.add_keyframe(Ow=rng.normal(0, 1, 3).astype(np.float32), desc=rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), octave=rng.integers(0, levels, N_KP),
+                       scale_factors=sf, table=count_pts[6:])
+    Ck = m.add_keyframe(Ow=rng.normal(0, 1, 3).astype(np.float32), desc=rng.integers(0, 256, (N_KP, 32), dtype=np.uint8), octave=rng.integers(0, levels, N_KP),
+                        scale_factors=sf, table=[names["twice"], names["already"], names["bad_point"], -1, names["twice"], names["all_bad"]])
+    assert m.add_observation(names["already"], Ck, 1)
     names.update(A=A, B=B, C=Ck)
     # reference keyframes: observed ones, the new keyframe itself (a point created from it), one that is not observed, and none
     for i, p in enumerate(count_pts):
         seen = [s_ for s_, _ in m.observations(p)]
-        m.ref[p] = (A if i < 6 else B) if not seen else seen[len(seen) // 2]
-    m.ref[count_pts[3]] = next(s_ for s_ in range(K_OLD) if s_ not in dict(m.observations(count_pts[3])))   # not observed
-    m.ref[count_pts[8]] = -1
+        m.points[p].ref = (A if i < 6 else B) if not seen else seen[len(seen) // 2]
+    m.points[count_pts[3]].ref = next(s_ for s_ in range(K_OLD) if s_ not in dict(m.observations(count_pts[3])))   # not observed
+    m.points[count_pts[8]].ref = -1
     for name in ("twice", "already", "bad_point", "plain", "all_bad"):
-        m.ref[names[name]] = m.observations(names[name])[0][0]
-    m.ref[names["no_obs"]] = 0
+        m.points[names[name]].ref = m.observations(names[name])[0][0]
+    m.points[names["no_obs"]].ref = 0
     for p in fill + names["singles"] + [t[0] for t in names["ties"]]:
-        m.ref[p] = m.observations(p)[0][0]
+        m.points[p].ref = m.observations(p)[0][0]
     return m, names

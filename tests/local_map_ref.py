@@ -13,50 +13,17 @@ from __future__ import annotations
 import numpy as np
 
 import track_search_ref as R
+from store_model import MapModel
 
 
-class RefPoint:
-    def __init__(self, xyz, normal, max_distance, desc, bad=False):
-        self.xyz = np.asarray(xyz, np.float32).reshape(3).copy()
-        self.normal = np.asarray(normal, np.float32).reshape(3).copy()
-        self.max_distance = np.float32(max_distance)
-        self.desc = np.asarray(desc, np.uint8).reshape(32).copy()
-        self.bad = bool(bad)
-        self.obs = {}                    # mObservations: keyframe slot -> True (the key point index is not read here)
-
-
-class RefKeyFrame:
-    def __init__(self, table, parent=-1, bad=False):
-        self.table = [int(p) for p in table]     # mvpMapPoints: a point id or -1
-        self.parent = int(parent)
-        self.bad = bool(bad)
-
-
-class RefMap:
-    """The map as the tracking thread reads it, with the mutations the store offers, and Tracking's own state (mvpLocalKeyFrames)."""
+class RefMap(MapModel):
+    """The map as the tracking thread reads it, and Tracking's own state (mvpLocalKeyFrames)."""
 
     def __init__(self):
-        self.points = []
-        self.kfs = []
+        super().__init__()
         self.local_kf = []               # mvpLocalKeyFrames of the previous frame
         self.local_points = []
         self.held = set()                # points with mnLastFrameSeen == the frame of the last update
-
-    # ---- mutations ----
-    def add_point(self, xyz=(0, 0, 1), normal=(0, 0, 1), max_distance=1.0, desc=None, bad=False):
-        self.points.append(RefPoint(xyz, normal, max_distance, np.zeros(32, np.uint8) if desc is None else desc, bad))
-        return len(self.points) - 1
-
-    def add_keyframe(self, table, parent=-1, bad=False):
-        self.kfs.append(RefKeyFrame(table, parent, bad))
-        return len(self.kfs) - 1
-
-    def add_observation(self, p, k):
-        assert k not in self.points[p].obs       # MapPoint::AddObservation returns on a keyframe it already has
-        self.points[p].obs[k] = True
-
-    def erase_observation(self, p, k):
-        self.points[p].obs.pop(k, None)
 
     def children(self, k):
         return [s for s, kf in enumerate(self.kfs) if kf.parent == k]        # std::set<KeyFrame*>: by slot
@@ -137,22 +104,6 @@ class RefMap:
         return dict(local_ids=ids, match=m, nmatches=n, in_view=iv, level=lev, uv=uv, view_cos=vc)
 
 
-def fill_store(store, rm: RefMap):
-    """Copy a RefMap into a defslam_amd.localmap.MapPointStore (points, keyframes in slot order, then observations in (point, slot) order)."""
-    if rm.points:
-        store.add_points(np.array([p.xyz for p in rm.points]), np.array([p.normal for p in rm.points]), np.array([p.max_distance for p in rm.points]),
-                         np.array([p.desc for p in rm.points]), np.array([p.bad for p in rm.points], np.uint8))
-    for kf in rm.kfs:
-        # a parent that comes later in slot order is set once it exists
-        store.add_keyframe(kf.table, kf.parent if kf.parent < store.n_keyframes else -1, kf.bad)
-    for s, kf in enumerate(rm.kfs):
-        if kf.parent > s:
-            store.set_keyframe_parent(s, kf.parent)
-    pairs = [(p, k) for p, pt in enumerate(rm.points) for k in sorted(pt.obs)]
-    if pairs:
-        store.add_observations([a for a, _ in pairs], [b for _, b in pairs])
-
-
 # ---- hand-built maps with known answers (CPU test: the restatement; GPU test: the device) ------------------------------------------
 
 def _simple(n_kf, parents=None, bad_kf=(), n_points=None, tables=None):
@@ -166,7 +117,7 @@ def _simple(n_kf, parents=None, bad_kf=(), n_points=None, tables=None):
         rm.add_keyframe(t, -1 if parents is None else parents[k], k in bad_kf)
         for p in t:
             if p >= 0:
-                rm.add_observation(p, k)
+                assert rm.add_observation(p, k)
     return rm
 
 

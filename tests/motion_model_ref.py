@@ -39,7 +39,7 @@ class MotionRefMap(T.TrackRefMap):
         cleaned = dropped = 0
         for i in range(len(mp)):                                      # CleanMatches, :669-678
             if mp[i] >= 0:
-                if self.n_obs[mp[i]] < 1:                             # Observations(): nObs, stale after setBadFlag; no isBad test
+                if self.points[mp[i]].n_obs < 1:                      # Observations(): nObs, stale after setBadFlag; no isBad test
                     out[i] = False
                     mp[i] = -1
                     cleaned += 1
@@ -95,7 +95,7 @@ class MotionRefMap(T.TrackRefMap):
             bestDist, bestIdx2 = 256, -1
             for i2 in vIndices2:
                 if mp[i2] >= 0:                                       # :381-383
-                    if self.n_obs[mp[i2]] > 0:
+                    if self.points[mp[i2]].n_obs > 0:
                         continue
                 dist = (dMP ^ fr.desc[i2]).bit_count()
                 if dist < bestDist:
@@ -129,10 +129,7 @@ class MotionRefMap(T.TrackRefMap):
 
 def scene_to_ref(sc) -> MotionRefMap:
     """A synth.make_track_close_scene dict as a MotionRefMap."""
-    rm = MotionRefMap()
-    base = T.scene_to_ref(sc)
-    rm.__dict__.update({k: v for k, v in base.__dict__.items()})
-    return rm
+    return T.scene_to_ref(sc, cls=MotionRefMap)
 
 
 def make_last_frame(sc, L, seed=0, hole=0.12, other=0.2, outlier=0.1):
@@ -209,7 +206,7 @@ def hand_map() -> MotionRefMap:
         rm.add_point(xyz=(0.125, 0.0625, 1.0))
     rm.add_keyframe([0, 1, 2, 3, 4, 5], parent=-1)
     for p in range(6):
-        rm.add_observation(p, 0)
+        assert rm.add_observation(p, 0)
     for p in (0, 1, 2, 3, 5, 6):
         rm.set_embedding(p, (0, 1, 2), (0.5, 0.25, 0.25))
     return rm

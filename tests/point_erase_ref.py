@@ -7,13 +7,15 @@ reference's lines and not from the kernels:
   LocalMapping::MapPointCulling                                           Thirdparty/ORBSLAM_2/src/LocalMapping.cc:173-199
   the drop of a Schwarp fit                                               Modules/Mapping/SchwarpDatabase.cc:288-292
 
-A point is a dict with mbBad, mpRefKF (a slot, -1: none), nObs, mnFound, mnVisible and mObservations, a map from keyframe slot to key
-point index that is read in slot order (slot order stands for pointer order); a keyframe is a dict whose mvpMapPoints is a list of ids or
--1.  Also here: the counts the store reports, the scenes the CPU and GPU tests share, the replay of a map into a MapPointStore and the
-conversions into the maps of the other restatements.  Nothing in defslam_amd/ imports this module."""
+Of a point of the map (tests/store_model.py) they touch bad (mbBad), ref (mpRefKF: a slot, -1: none), n_obs (nObs), found, visible and
+obs (mObservations), a map from keyframe slot to key point index that is read in slot order (slot order stands for pointer order); of a
+keyframe its table (mvpMapPoints), a list of ids or -1.  Also here: the counts the store reports and the scenes the CPU and GPU tests
+share.  Nothing in defslam_amd/ imports this module."""
 from __future__ import annotations
 
 import numpy as np
+
+from store_model import MapModel
 
 f32 = np.float32
 COUNT_NAMES = ("n_found", "n_ref_moved", "n_set_bad", "n_records", "n_entries")
@@ -23,60 +25,39 @@ def zero_counts():
     return dict.fromkeys(COUNT_NAMES, 0)
 
 
-class EraseRefMap:
-    def __init__(self):
-        self.points = []         # dict(mbBad, mpRefKF, nObs, mnFound, mnVisible, mObservations)
-        self.kfs = []            # dict(mvpMapPoints)
-        self.log = []            # every AddObservation in call order (point, keyframe, index), for the replay
-
-    # ---- building ----
-    def add_point(self, ref=-1, bad=False, found=1, visible=1):
-        self.points.append(dict(mbBad=bool(bad), mpRefKF=int(ref), nObs=0, mnFound=int(found), mnVisible=int(visible), mObservations={}))
-        return len(self.points) - 1
-
-    def add_keyframe(self, table):
-        self.kfs.append(dict(mvpMapPoints=[int(p) for p in table]))
-        return len(self.kfs) - 1
-
-    def add_observation(self, p, kf, idx):                            # MapPoint.cc:109-120, monocular
-        mp = self.points[p]
-        if kf in mp["mObservations"]:
-            return False
-        assert 0 <= idx < len(self.kfs[kf]["mvpMapPoints"])
-        mp["mObservations"][int(kf)] = int(idx)
-        mp["nObs"] += 1
-        self.log.append((int(p), int(kf), int(idx)))
-        return True
+class EraseRefMap(MapModel):
+    """The map with the reference's functions that take a point out of it."""
 
     # ---- the reference's functions ----
     def erase_map_point_match(self, kf, idx):                         # KeyFrame.cc:248-252: it does not look at the entry
-        self.kfs[kf]["mvpMapPoints"][idx] = -1
+        self.kfs[kf].table[idx] = -1
 
     def set_bad_flag(self, p, c):                                     # DefMapPoint.cc:76-94
         mp = self.points[p]
-        mp["mbBad"] = True                                            # :82
-        obs = dict(mp["mObservations"])                               # :83
-        mp["mObservations"].clear()                                   # :84; nObs stays
+        mp.bad = True                                                 # :82
+        obs, n_obs = dict(mp.obs), mp.n_obs                           # :83
+        for kf in obs:                                                # :84 mObservations.clear(): the model blanks the records
+            self.erase_observation(p, kf)
+        mp.n_obs = n_obs                                              # and nObs stays
         for kf in sorted(obs):                                        # :86-91
             self.erase_map_point_match(kf, obs[kf])
             c["n_records"] += 1
             c["n_entries"] += 1
         c["n_set_bad"] += 1
 
-    def erase_observation(self, p, kf, c):                            # MapPoint.cc:122-148 -> the status of the store
+    def map_point_erase_observation(self, p, kf, c):                  # MapPoint.cc:122-148 -> the status of the store
         mp = self.points[p]
         bad = False
-        if kf not in mp["mObservations"]:                             # :127
+        if kf not in mp.obs:                                          # :127
             return 0
-        mp["nObs"] -= 1                                               # :133
-        del mp["mObservations"][kf]                                   # :135
+        self.erase_observation(p, kf)                                 # :133 nObs--, :135 erase
         c["n_found"] += 1
         c["n_records"] += 1
-        if mp["mpRefKF"] == kf:                                       # :137
-            if mp["mObservations"]:                                   # begin() == end() is undefined in the reference: mpRefKF stays
-                mp["mpRefKF"] = min(mp["mObservations"])              # :138
+        if mp.ref == kf:                                              # :137
+            if mp.obs:                                                # begin() == end() is undefined in the reference: mpRefKF stays
+                mp.ref = min(mp.obs)                                  # :138
                 c["n_ref_moved"] += 1
-        if mp["nObs"] <= 2:                                           # :141
+        if mp.n_obs <= 2:                                             # :141
             bad = True
         if bad:
             self.set_bad_flag(p, c)                                   # :147
@@ -88,8 +69,8 @@ class EraseRefMap:
         c, status = zero_counts(), []
         for p, kf in zip(points, slots):
             p, kf = int(p), int(kf)
-            idx = self.points[p]["mObservations"].get(kf)
-            status.append(self.erase_observation(p, kf, c))           # :290
+            idx = self.points[p].obs.get(kf)
+            status.append(self.map_point_erase_observation(p, kf, c))   # :290
             if erase_match and idx is not None:
                 self.erase_map_point_match(kf, idx)                   # :291
                 c["n_entries"] += 1
@@ -106,8 +87,8 @@ class EraseRefMap:
         for i, p in enumerate(ids):
             mp = self.points[int(p)]
             with np.errstate(divide="ignore", invalid="ignore"):
-                ratio = f32(mp["mnFound"]) / f32(mp["mnVisible"])     # MapPoint::GetFoundRatio, MapPoint.cc:251-255
-            if mp["mbBad"]:                                           # :184
+                ratio = f32(mp.found) / f32(mp.visible)               # MapPoint::GetFoundRatio, MapPoint.cc:251-255
+            if mp.bad:                                                # :184
                 action[i] = 1
             elif ratio < f32(0.40):                                   # :188
                 self.set_bad_flag(int(p), c)                          # :191
@@ -116,110 +97,9 @@ class EraseRefMap:
                 action[i] = 3
         return action, c
 
-    # ---- read-backs in the shape of the store's ----
-    def observations(self, p):
-        """MapPoint::GetObservations of p, in slot order."""
-        return dict(sorted(self.points[p]["mObservations"].items()))
-
-    def state(self):
-        P = len(self.points)
-        return dict(bad=np.array([mp["mbBad"] for mp in self.points], bool).reshape(P),
-                    n_obs=np.array([mp["nObs"] for mp in self.points], np.int32).reshape(P),
-                    ref=np.array([mp["mpRefKF"] for mp in self.points], np.int32).reshape(P),
-                    obs=[self.observations(p) for p in range(P)],
-                    tables=[list(kf["mvpMapPoints"]) for kf in self.kfs])
-
-
-def store_state(st):
-    """The same dict read back from a MapPointStore."""
-    P = st.n_points
-    o = st.observations()
-    return dict(bad=st.get_points().bad, n_obs=st.get_state().n_obs, ref=st.get_reference_keyframes(),
-                obs=[o.of(p) for p in range(P)], tables=[st.keyframe_table(s).tolist() for s in range(st.n_keyframes)])
-
-
-def assert_state(st, rm, what=""):
-    g, r = store_state(st), rm.state()
-    for n in ("bad", "n_obs", "ref"):
-        assert np.array_equal(np.asarray(g[n]).astype(np.int64), r[n].astype(np.int64)), (what, n, g[n], r[n])
-    assert g["obs"] == r["obs"], (what, "obs", [(p, a, b) for p, (a, b) in enumerate(zip(g["obs"], r["obs"])) if a != b])
-    assert g["tables"] == r["tables"], (what, "tables", [(s, a, b) for s, (a, b) in enumerate(zip(g["tables"], r["tables"])) if a != b])
-
 
 def assert_counts(got, want, what=""):
     assert {n: int(getattr(got, n)) for n in COUNT_NAMES} == want, (what, got, want)
-
-
-def fill_store(st, rm, batches=1):
-    """Replay rm into an empty MapPointStore: points with their counters, keyframes with their tables, the observations in the order
-    they were added, the reference keyframes.  rm must not have erased anything yet (its log is then its state)."""
-    P = len(rm.points)
-    z = np.zeros((P, 3), np.float32)
-    st.add_points(z, z, np.ones(P, np.float32), np.zeros((P, 32), np.uint8), np.array([mp["mbBad"] for mp in rm.points], np.uint8))
-    st.set_counters(np.arange(P), [mp["mnVisible"] for mp in rm.points], [mp["mnFound"] for mp in rm.points])
-    for k, kf in enumerate(rm.kfs):
-        assert st.add_keyframe(np.array(kf["mvpMapPoints"], np.int32)) == k
-    log = np.array(rm.log, np.int32).reshape(-1, 3)
-    for part in np.array_split(log, batches):
-        if len(part):
-            st.add_observations(part[:, 0], part[:, 1], idx=part[:, 2])
-    st.set_reference_keyframes(np.arange(P), [mp["mpRefKF"] for mp in rm.points])
-
-
-# ---- conversions into the maps of the other restatements ---------------------------------------------------------------------------------
-
-def to_local_map(rm, bad_kf=()):
-    """A local_map_ref.RefMap with rm's points, observations and tables (no spanning tree; bad_kf: the slots of the bad keyframes)."""
-    import local_map_ref as LM
-    m = LM.RefMap()
-    for mp in rm.points:
-        m.add_point(bad=mp["mbBad"])
-    for s, kf in enumerate(rm.kfs):
-        m.add_keyframe(kf["mvpMapPoints"], bad=s in bad_kf)
-    for p, mp in enumerate(rm.points):
-        for kf in sorted(mp["mObservations"]):
-            m.add_observation(p, kf)
-    return m
-
-
-def to_anchor_map(rm):
-    import anchor_pairs_ref as AR
-    m = AR.AnchorRefMap()
-    for mp in rm.points:
-        m.add_point(ref=mp["mpRefKF"], bad=mp["mbBad"])
-    for kf in rm.kfs:
-        m.tables.append(list(kf["mvpMapPoints"]))
-    for p, mp in enumerate(rm.points):
-        m.obs[p] = dict(mp["mObservations"])
-    return m
-
-
-def from_store_model(model):
-    """An EraseRefMap with the points, live observations (in log order), tables and reference keyframes of a keyframe_insert_ref.StoreModel."""
-    rm = EraseRefMap()
-    for p in range(len(model.xyz)):
-        rm.add_point(ref=model.ref[p], bad=model.bad[p])
-    for t in model.tables:
-        rm.add_keyframe(t)
-    for p, s, idx, live in model.log:
-        if live:
-            rm.add_observation(p, s, idx)
-    return rm
-
-
-def into_store_model(rm, model):
-    """Make a keyframe_insert_ref.StoreModel hold rm's state: bad flags, reference keyframes, nObs, tables, and exactly rm's observations."""
-    for p, mp in enumerate(rm.points):
-        for s, idx in model.observations(p):
-            if mp["mObservations"].get(s) != idx:                     # gone, or erased and added again with another index
-                model.erase_observation(p, s)
-        for s, idx in mp["mObservations"].items():
-            if not model.live(p, s):
-                model.add_observation(p, s, idx)
-        assert dict(model.observations(p)) == mp["mObservations"]
-        model.bad[p], model.ref[p], model.n_obs[p] = mp["mbBad"], mp["mpRefKF"], mp["nObs"]
-    for s, kf in enumerate(rm.kfs):
-        model.tables[s] = list(kf["mvpMapPoints"])
 
 
 # ---- scenes --------------------------------------------------------------------------------------------------------------------------------
@@ -241,7 +121,7 @@ def small_scene():
     refs = (0, 2, 2, 1, 1, 0)
     for p in range(6):
         rm.add_point(ref=refs[p], bad=p == 4)
-    T = [kf["mvpMapPoints"] for kf in rm.kfs]
+    T = [kf.table for kf in rm.kfs]
     obs = [(0, 0, 0), (0, 1, 0), (0, 2, 0),
            (1, 0, 1), (1, 1, 5), (1, 2, 1),
            (2, 2, 2),
@@ -255,7 +135,7 @@ def small_scene():
     order = [9, 2, 14, 0, 7, 5, 11, 3, 12, 1, 8, 4, 10, 6, 13]   # arrival order differs from slot order
     assert sorted(order) == list(range(len(obs)))
     for i in order:
-        rm.add_observation(*obs[i])
+        assert rm.add_observation(*obs[i])
     return rm, ([0, 1, 2, 3, 4, 5], [0, 0, 2, 0, 1, 2])
 
 
@@ -274,10 +154,10 @@ def long_scene(seed=3, K=40, N=128, P=700):
             if free[kf]:
                 i = int(free[kf].pop())
                 pairs.append((p, kf, i))
-                rm.kfs[kf]["mvpMapPoints"][i] = p
+                rm.kfs[kf].table[i] = p
     for i in rng.permutation(len(pairs)):
-        rm.add_observation(*pairs[int(i)])
+        assert rm.add_observation(*pairs[int(i)])
     for p, mp in enumerate(rm.points):
-        seen = sorted(mp["mObservations"])
-        mp["mpRefKF"] = seen[int(rng.integers(0, len(seen)))] if seen else -1
+        seen = sorted(mp.obs)
+        mp.ref = seen[int(rng.integers(0, len(seen)))] if seen else -1
     return rm

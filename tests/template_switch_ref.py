@@ -19,6 +19,7 @@ from __future__ import annotations
 import numpy as np
 
 import mappoint_ref as M
+import track_close_ref as T
 
 f32 = np.float32
 COUNT_NAMES = ("n_new", "first_id", "n_moved", "n_masked", "n_embedded", "n_points")
@@ -86,21 +87,6 @@ def masked_by_interval(rows, cols, held_pixels, y, x):
     return any(Lx <= px <= Hx and Ly <= py <= Hy for py, px in held_pixels)
 
 
-def held_pixels(rm, slot, kp):
-    """:249-259 / :363-373: the pixels of the key points that hold a point that is not bad."""
-    return [pixel(kp[i]) for i, p in enumerate(rm.kfs[slot].table) if p >= 0 and not rm.points[p].bad]
-
-
-def need_new_template(rm, slot, rows, cols, kp):
-    """DefLocalMapping::needNewTemplate: (newPoints, candidate flags)."""
-    mask = box_mask(rows, cols, held_pixels(rm, slot, kp))
-    cand = np.zeros(len(rm.kfs[slot].table), bool)
-    for i, p in enumerate(rm.kfs[slot].table):                     # :386-398
-        if p < 0 and not mask[pixel(kp[i])]:
-            cand[i] = True
-    return int(cand.sum()), cand
-
-
 def to_world(Twc, s):
     """x3wh = Twc * x3ch of float32 cv::Mat: the four products of a row summed left to right in float32."""
     T = np.asarray(Twc, np.float32).reshape(4, 4)
@@ -108,48 +94,64 @@ def to_world(Twc, s):
     return np.array([f32(f32(f32(T[r, 0] * x) + f32(T[r, 1] * y)) + f32(T[r, 2] * z)) + f32(T[r, 3] * w) for r in range(3)], np.float32)
 
 
-def switch_template(rm, kfs, slot, rows, cols, kp, surface_pts, Twc, embed, rest_xyz):
-    """DefLocalMapping::updateTemplate on the mirror rm (a TrackRefMap) with the keyframe store's side kfs (RefKfData per slot).
-    embed(pts) -> (facet id, nodes, float32 barycentrics) is the host embedding in the new template, rest_xyz its nodes.
-    Returns the counts (COUNT_NAMES), new_idx, and pre_embed: the positions the embedding was fed (every point, bad ones too)."""
-    c = dict.fromkeys(COUNT_NAMES, 0)
-    rm.clear_embedding()                                            # DefMap::clearTemplate
-    mask = box_mask(rows, cols, held_pixels(rm, slot, kp))          # :245-271
-    c["first_id"] = len(rm.points)
-    new_idx = []
-    table = rm.kfs[slot].table
-    for i in range(len(table)):                                     # :273-345
-        p = table[i]
-        if p >= 0:
-            if rm.points[p].bad:
-                continue
-            rm.points[p].xyz = to_world(Twc, surface_pts[i])        # SetWorldPos
-            c["n_moved"] += 1
-        else:
-            if mask[pixel(kp[i])]:
-                c["n_masked"] += 1
-                continue
-            x3w = to_world(Twc, surface_pts[i])
-            q = rm.add_point(xyz=x3w, desc=kfs[slot].desc[i])       # new DefMapPoint(x3w, referenceKF_, mpMap)
-            rm.add_observation(q, slot)                             # :337
-            table[i] = q                                            # :338
-            pt = rm.points[q]                                       # :340-341: one observation elects its descriptor
-            pt.normal, pt.max_distance, _ = M.update_normal_and_depth(kfs, x3w, [(slot, i)], slot)
-            new_idx.append(i)
-    c["n_new"] = len(new_idx)
-    c["n_points"] = len(rm.points)
-    pre_embed = np.array([pt.xyz for pt in rm.points], np.float32).reshape(-1, 3)
-    ids = [p for p, pt in enumerate(rm.points) if not pt.bad]       # Map::GetAllMapPoints holds no bad point
-    if ids:
-        fid, nodes, bary = embed(pre_embed[ids])                    # calculateFeaturesCoordinates
-        for n, p in enumerate(ids):
-            if fid[n] < 0:
-                continue
-            order = np.argsort(nodes[n], kind="stable")             # std::set<Node*> order
-            rm.set_embedding(p, nodes[n][order], np.asarray(bary[n], np.float32)[order].astype(np.float64))
-            c["n_embedded"] += 1
-    rm.repose(rest_xyz)                                             # Repose -> RecalculatePosition of every point with a facet
-    return c, np.array(new_idx, np.int32), pre_embed
+class TemplateRefMap(T.TrackRefMap):
+    """TrackRefMap with the template switch of the mapping thread."""
+
+    def held_pixels(self, slot, kp):
+        """:249-259 / :363-373: the pixels of the key points that hold a point that is not bad."""
+        return [pixel(kp[i]) for i, p in enumerate(self.kfs[slot].table) if p >= 0 and not self.points[p].bad]
+
+    def need_new_template(self, slot, rows, cols, kp):
+        """DefLocalMapping::needNewTemplate: (newPoints, candidate flags)."""
+        mask = box_mask(rows, cols, self.held_pixels(slot, kp))
+        cand = np.zeros(len(self.kfs[slot].table), bool)
+        for i, p in enumerate(self.kfs[slot].table):                        # :386-398
+            if p < 0 and not mask[pixel(kp[i])]:
+                cand[i] = True
+        return int(cand.sum()), cand
+
+    def switch_template(self, kfs, slot, rows, cols, kp, surface_pts, Twc, embed, rest_xyz):
+        """DefLocalMapping::updateTemplate on the mirror with the keyframe store's side kfs (RefKfData per slot).
+        embed(pts) -> (facet id, nodes, float32 barycentrics) is the host embedding in the new template, rest_xyz its nodes.
+        Returns the counts (COUNT_NAMES), new_idx, and pre_embed: the positions the embedding was fed (every point, bad ones too)."""
+        c = dict.fromkeys(COUNT_NAMES, 0)
+        self.clear_embedding()                                              # DefMap::clearTemplate
+        mask = box_mask(rows, cols, self.held_pixels(slot, kp))             # :245-271
+        c["first_id"] = len(self.points)
+        new_idx = []
+        table = self.kfs[slot].table
+        for i in range(len(table)):                                         # :273-345
+            p = table[i]
+            if p >= 0:
+                if self.points[p].bad:
+                    continue
+                self.points[p].xyz = to_world(Twc, surface_pts[i])          # SetWorldPos
+                c["n_moved"] += 1
+            else:
+                if mask[pixel(kp[i])]:
+                    c["n_masked"] += 1
+                    continue
+                x3w = to_world(Twc, surface_pts[i])
+                q = self.add_point(xyz=x3w, desc=kfs[slot].desc[i])         # new DefMapPoint(x3w, referenceKF_, mpMap)
+                assert self.add_observation(q, slot)                        # :337
+                table[i] = q                                                # :338
+                pt = self.points[q]                                         # :340-341: one observation elects its descriptor
+                pt.normal, pt.max_distance, _ = M.update_normal_and_depth(kfs, x3w, [(slot, i)], slot)
+                new_idx.append(i)
+        c["n_new"] = len(new_idx)
+        c["n_points"] = len(self.points)
+        pre_embed = np.array([pt.xyz for pt in self.points], np.float32).reshape(-1, 3)
+        ids = [p for p, pt in enumerate(self.points) if not pt.bad]         # Map::GetAllMapPoints holds no bad point
+        if ids:
+            fid, nodes, bary = embed(pre_embed[ids])                        # calculateFeaturesCoordinates
+            for n, p in enumerate(ids):
+                if fid[n] < 0:
+                    continue
+                order = np.argsort(nodes[n], kind="stable")                 # std::set<Node*> order
+                self.set_embedding(p, nodes[n][order], np.asarray(bary[n], np.float32)[order].astype(np.float64))
+                c["n_embedded"] += 1
+        self.repose(rest_xyz)                                               # Repose -> RecalculatePosition of every point with a facet
+        return c, np.array(new_idx, np.int32), pre_embed
 
 
 def surface_vertices(bbs, depth, Twc, xs, ys):
@@ -169,19 +171,5 @@ def scene_kf_data(sc):
     return [RefKfData(sc["kf_Ow"][k], sc["kf_desc"][k], sc["kf_octave"][k], sc["scale_factors"], sc["kf_bad"][k]) for k in range(sc["tables"].shape[0])]
 
 
-def point_arrays(rm):
-    """(xyz, normal, max_distance, desc, bad) of every point, as MapPointStore.get_points() returns them."""
-    P = len(rm.points)
-    return (np.array([pt.xyz for pt in rm.points], np.float32).reshape(P, 3), np.array([pt.normal for pt in rm.points], np.float32).reshape(P, 3),
-            np.array([pt.max_distance for pt in rm.points], np.float32).reshape(P), np.array([pt.desc for pt in rm.points], np.uint8).reshape(P, 32),
-            np.array([pt.bad for pt in rm.points], bool))
-
-
-def embedding_arrays(rm):
-    """(nodes, bary) of every point, as MapPointStore.get_embedding() returns them."""
-    P = len(rm.points)
-    nodes, bary = np.full((P, 3), -1, np.int32), np.zeros((P, 3), np.float64)
-    for p in range(P):
-        if rm.nodes[p] is not None:
-            nodes[p], bary[p] = rm.nodes[p], rm.bary[p]
-    return nodes, bary
+def scene_to_ref(sc, embed=True):
+    return T.scene_to_ref(sc, embed, cls=TemplateRefMap)

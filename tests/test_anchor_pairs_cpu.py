@@ -18,33 +18,30 @@ NEW_ENTRIES = ["dsh_point_store_add_observations_indexed", "dsh_point_store_set_
 
 def brute_force(rm, slot):
     """Per keyframe a with a vote: the multiset of (idx1, idx2, point, own) and the set of query entries, from flat arrays and sets
-    instead of the per-point dictionaries: the live records are the log minus the erasures."""
-    live = {}
-    for p, k, i in rm.log:
-        live[(p, k)] = i
-    for p, k in rm.erased:
-        live.pop((p, k), None)
+    instead of the per-point dictionaries: the live records are the log without its blanked records."""
+    live = {(p, k): i for p, k, i, alive in rm.log if alive}
+    assert live == {(p, k): i for p, pt in enumerate(rm.points) for k, i in pt.obs.items()}
     in_new = {p for (p, k) in live if k == slot}
-    good = [p for p in rm.tables[slot] if p >= 0 and not rm.bad[p]]
+    good = [p for p in rm.kfs[slot].table if p >= 0 and not rm.points[p].bad]
     votes = {}
     for p in good:
-        if rm.ref[p] >= 0:
-            votes[rm.ref[p]] = votes.get(rm.ref[p], 0) + 1
+        if rm.points[p].ref >= 0:
+            votes[rm.points[p].ref] = votes.get(rm.points[p].ref, 0) + 1
     out = {}
     for a in votes:
         sees_a = {p for (p, k) in live if k == a}
-        pairs = sorted((live[(p, a)], live[(p, slot)], p, rm.ref[p] == a) for p in good if p in in_new and p in sees_a)
-        queries = {j for j, q in enumerate(rm.tables[a]) if q >= 0 and not rm.bad[q] and q not in in_new}
+        pairs = sorted((live[(p, a)], live[(p, slot)], p, rm.points[p].ref == a) for p in good if p in in_new and p in sees_a)
+        queries = {j for j, q in enumerate(rm.kfs[a].table) if q >= 0 and not rm.points[q].bad and q not in in_new}
         out[a] = (votes[a], pairs, queries)
-    return out, sum(1 for p in good if rm.ref[p] < 0)
+    return out, sum(1 for p in good if rm.points[p].ref < 0)
 
 
 def check_against_brute_force(rm, min_pairs):
-    slot = len(rm.tables) - 1
+    slot = len(rm.kfs) - 1
     r = rm.keyframe_anchors(slot, min_pairs)
     bf, n_no_ref = brute_force(rm, slot)
     assert r["anchor_slot"] == sorted(bf) and r["n_no_ref"] == n_no_ref
-    assert r["has"] == [p >= 0 for p in rm.tables[slot]]
+    assert r["has"] == [p >= 0 for p in rm.kfs[slot].table]
     for n, a in enumerate(r["anchor_slot"]):
         votes, pairs, queries = bf[a]
         assert r["anchor_count"][n] == votes and r["anchor_pairs"][n] == len(pairs)
@@ -55,9 +52,9 @@ def check_against_brute_force(rm, min_pairs):
             continue
         assert sorted(got) == pairs
         assert r["query_idx1"][qs] == sorted(queries)                         # ascending entries of the anchor's table
-        assert [rm.tables[a][j] for j in r["query_idx1"][qs]] == r["query_point"][qs]
-        held = [i for i, p in enumerate(rm.tables[slot]) if p in set(r["pair_point"][ps])]
-        assert [rm.tables[slot][i] for i in held] == r["pair_point"][ps]      # in the order of the new keyframe's entries
+        assert [rm.kfs[a].table[j] for j in r["query_idx1"][qs]] == r["query_point"][qs]
+        held = [i for i, p in enumerate(rm.kfs[slot].table) if p in set(r["pair_point"][ps])]
+        assert [rm.kfs[slot].table[i] for i in held] == r["pair_point"][ps]      # in the order of the new keyframe's entries
     return r
 
 
@@ -78,15 +75,16 @@ def test_the_generated_maps_hold_every_case_the_gpu_tests_need():
     """A condition on the inputs of the GPU tests, checked on the restatement alone."""
     for name, (make, min_pairs) in A.SCENES.items():
         rm = make()
-        slot = len(rm.tables) - 1
-        table = rm.tables[slot]
+        slot = len(rm.kfs) - 1
+        table = rm.kfs[slot].table
         r = rm.keyframe_anchors(slot, min_pairs)
         held = [p for p in table if p >= 0]
+        erased = {(p, k) for p, k, _, alive in rm.log if not alive}
         assert len(held) > len(set(held)), name                                                  # a point held by two entries
-        assert any(rm.bad[p] for p in held), name                                                # a bad point
-        assert any((p, slot) in rm.erased for p in held), name                                   # an erased record of (p, slot)
-        assert any(k != slot and p in held for p, k in rm.erased), name                          # and of (p, a)
-        assert any(not rm.bad[p] and slot not in rm.obs[p] and (p, slot) not in rm.erased for p in held), name   # does not observe the keyframe yet
+        assert any(rm.points[p].bad for p in held), name                                                # a bad point
+        assert any((p, slot) in erased for p in held), name                                      # an erased record of (p, slot)
+        assert any(k != slot and p in held for p, k in erased), name                             # and of (p, a)
+        assert any(not rm.points[p].bad and slot not in rm.points[p].obs and (p, slot) not in erased for p in held), name  # does not observe the keyframe yet
         assert r["n_no_ref"] > 0, name
         assert slot in r["anchor_slot"], name                                                    # a == slot
         a = r["anchor_slot"].index(slot)

@@ -20,7 +20,7 @@ OK, ARG, STATE = 0, 1, 3
 def store_from(ctx, rm, **caps):
     from defslam_amd import localmap
     st = localmap.MapPointStore(ctx, **caps)
-    A.fill_store(st, rm)
+    rm.fill(st, batches=3)
     return st
 
 
@@ -30,7 +30,7 @@ def scenes():
     out = {}
     for name, (make, min_pairs) in A.SCENES.items():
         rm = make()
-        out[name] = (rm, min_pairs, rm.keyframe_anchors(len(rm.tables) - 1, min_pairs))
+        out[name] = (rm, min_pairs, rm.keyframe_anchors(len(rm.kfs) - 1, min_pairs))
     return out
 
 
@@ -41,9 +41,9 @@ def test_every_output_equals_the_restatement(gpu_ctx, scenes, name):
     a == slot among them)."""
     rm, min_pairs, want = scenes[name]
     st = store_from(gpu_ctx, rm, points=2, keyframes=1, observations=2)
-    slot = len(rm.tables) - 1
-    N = len(rm.tables[slot])
-    assert st.get_reference_keyframes().tolist() == rm.ref
+    slot = len(rm.kfs) - 1
+    N = len(rm.kfs[slot].table)
+    assert st.get_reference_keyframes().tolist() == rm.state()["ref"].tolist()
     g = st.keyframe_anchors(slot, min_pairs)
     A.assert_equal(g, want)
     for rows in (3, 1):
@@ -75,22 +75,22 @@ def test_mutations_after_the_first_call_are_seen(gpu_ctx, scenes):
     older keyframe as `slot` works too, and so does an empty keyframe."""
     rm = A.SCENES["n70_k5"][0]()
     st = store_from(gpu_ctx, rm)
-    slot = len(rm.tables) - 1
+    slot = len(rm.kfs) - 1
     A.assert_equal(st.keyframe_anchors(slot, 5), rm.keyframe_anchors(slot, 5))
-    held = [p for p in rm.tables[slot] if p >= 0 and not rm.bad[p] and slot in rm.obs[p]]
-    rm.bad[held[0]] = True
+    held = [p for p in rm.kfs[slot].table if p >= 0 and not rm.points[p].bad and slot in rm.points[p].obs]
+    rm.points[held[0]].bad = True
     st.set_points_bad([held[0]])
     rm.erase_observation(held[1], slot)
     st.erase_observations([held[1]], [slot])
-    late = next(i for i, p in enumerate(rm.tables[slot]) if p >= 0 and not rm.bad[p] and slot not in rm.obs[p] and (p, slot) not in rm.erased)
-    rm.add_observation(rm.tables[slot][late], slot, late)
-    st.add_observations([rm.tables[slot][late]], [slot], idx=[late])
-    rm.ref[held[2]] = 0 if rm.ref[held[2]] != 0 else 1
-    st.set_reference_keyframes([held[2]], [rm.ref[held[2]]])
-    assert st.get_reference_keyframes([held[2], held[3]]).tolist() == [rm.ref[held[2]], rm.ref[held[3]]]
+    late = next(i for i, p in enumerate(rm.kfs[slot].table) if p >= 0 and not rm.points[p].bad and not any(r[:2] == [p, slot] for r in rm.log))
+    assert rm.add_observation(rm.kfs[slot].table[late], slot, late)
+    st.add_observations([rm.kfs[slot].table[late]], [slot], idx=[late])
+    rm.points[held[2]].ref = 0 if rm.points[held[2]].ref != 0 else 1
+    st.set_reference_keyframes([held[2]], [rm.points[held[2]].ref])
+    assert st.get_reference_keyframes([held[2], held[3]]).tolist() == [rm.points[held[2]].ref, rm.points[held[3]].ref]
     A.assert_equal(st.keyframe_anchors(slot, 5), rm.keyframe_anchors(slot, 5))
     A.assert_equal(st.keyframe_anchors(1, 2), rm.keyframe_anchors(1, 2))
-    e = rm.add_keyframe(0)
+    e = rm.add_keyframe([])
     assert st.add_keyframe(np.zeros(0, np.int32)) == e
     g = st.keyframe_anchors(e, 0)
     A.assert_equal(g, rm.keyframe_anchors(e, 0))
@@ -115,7 +115,7 @@ def test_refusals_that_need_a_filled_store(gpu_ctx, scenes):
     from defslam_amd import sft
     rm, min_pairs, want = scenes["n70_k5"]
     st = store_from(gpu_ctx, rm)
-    L, slot = gpu_ctx._L, len(rm.tables) - 1
+    L, slot = gpu_ctx._L, len(rm.kfs) - 1
     msg = lambda: L.dsh_last_error(gpu_ctx._h).decode()
     A_, NP, NQ = len(want["anchor_slot"]), len(want["pair_idx1"]), len(want["query_idx1"])
     assert NP > 1 and NQ > 1
@@ -136,8 +136,8 @@ def test_refusals_that_need_a_filled_store(gpu_ctx, scenes):
     r, a, own = raw_lists(A_, NP, NQ)
     assert L.dsh_keyframe_anchors(st._h, slot + 1, min_pairs, C.byref(r)) == ARG and "slot outside" in msg()
     assert L.dsh_keyframe_anchors(st._h, slot, -1, C.byref(r)) == ARG and "min_pairs" in msg()
-    free = next(p for p in range(len(rm.bad)) if 0 not in rm.obs[p] and (p, 0) not in rm.erased)
-    n0 = len(rm.tables[0])
+    free = next(p for p in range(len(rm.points)) if not any(r[:2] == [p, 0] for r in rm.log))
+    n0 = len(rm.kfs[0].table)
     for idx in (n0, -1):
         with pytest.raises(sft.DshError, match="index outside the keyframe's key points"):
             st.add_observations([free], [0], idx=[idx])
@@ -151,7 +151,7 @@ def test_refusals_that_need_a_filled_store(gpu_ctx, scenes):
         st.set_reference_keyframes([3], [slot + 1])
     with pytest.raises(sft.DshError, match="repeated in the batch"):
         st.get_reference_keyframes([3, 3])
-    assert st.get_reference_keyframes().tolist() == rm.ref                           # nothing was stored
+    assert st.get_reference_keyframes().tolist() == rm.state()["ref"].tolist()     # nothing was stored
     A.assert_equal(st.keyframe_anchors(slot, min_pairs), want)
     st.close()
 
@@ -163,20 +163,20 @@ def test_records_without_an_index_are_a_state_error(gpu_ctx):
     rm = A.threshold_map(4)
     L = gpu_ctx._L
     st = localmap.MapPointStore(gpu_ctx)
-    P = len(rm.bad)
+    P = len(rm.points)
     z = np.zeros((P, 3), np.float32)
     st.add_points(z, z, np.ones(P, np.float32), np.zeros((P, 32), np.uint8))
-    for t in rm.tables:
-        st.add_keyframe(np.array(t, np.int32))
-    log = np.array(rm.log, np.int32)
+    for kf in rm.kfs:
+        st.add_keyframe(np.array(kf.table, np.int32))
+    log = np.array(rm.log, np.int32)                                                 # no erased record in this map
     st.add_observations(log[:, 0], log[:, 1])
-    st.set_reference_keyframes(np.arange(P), rm.ref)
+    st.set_reference_keyframes(np.arange(P), rm.state()["ref"])
     r, a, own = raw_lists(8, 64, 64)
     assert L.dsh_keyframe_anchors(st._h, 2, 4, C.byref(r)) == STATE
     assert f"{len(rm.log)} live observation records without a key point index" in L.dsh_last_error(gpu_ctx._h).decode()
     assert all((v == -7).all() for v in a.values()) and (own == 9).all() and r.n_anchors == 0
     st.clear()
-    A.fill_store(st, rm)
+    rm.fill(st, batches=3)
     A.assert_equal(st.keyframe_anchors(2, 4), rm.keyframe_anchors(2, 4))
     q = rm.add_point(ref=0)
     st.add_points(np.zeros((1, 3), np.float32), np.zeros((1, 3), np.float32), [1.0], np.zeros((1, 32), np.uint8))
@@ -202,13 +202,12 @@ def test_points_of_a_template_switch_carry_both_fields(ctx_switch):
     for p in range(P):
         rm.add_point(bad=sc["bad"][p])
     for k in range(sc["tables"].shape[0]):
-        assert st.add_keyframe(sc["tables"][k], sc["parents"][k], sc["kf_bad"][k]) == rm.add_keyframe(len(sc["tables"][k])) == k
-        rm.tables[k] = [int(p) for p in sc["tables"][k]]
+        assert st.add_keyframe(sc["tables"][k], sc["parents"][k], sc["kf_bad"][k]) == rm.add_keyframe(sc["tables"][k]) == k
     idx = []
     for p, k in zip(sc["obs_point"], sc["obs_kf"]):                                  # the scene's observations: the entry that holds the point, else 0
         hit = np.nonzero(sc["tables"][k] == p)[0]
         idx.append(int(hit[0]) if len(hit) else 0)
-        rm.add_observation(int(p), int(k), idx[-1])
+        assert rm.add_observation(int(p), int(k), idx[-1])
     st.add_observations(sc["obs_point"], sc["obs_kf"], idx=idx)
     ks = kf_store_from_scene(ctx, sc)
     build_template(ctx, sc, xs, ys)
@@ -219,16 +218,15 @@ def test_points_of_a_template_switch_carry_both_fields(ctx_switch):
     assert (st.get_reference_keyframes(np.arange(P)) == -1).all()
     for p, i in zip(new, g.new_idx):                                                 # the mirror follows the switch
         assert rm.add_point(ref=r) == p
-        rm.tables[r][int(i)] = int(p)
-        rm.add_observation(int(p), r, int(i))
+        rm.kfs[r].table[int(i)] = int(p)
+        assert rm.add_observation(int(p), r, int(i))
     n2 = g.n_new + 7                                                                 # a later keyframe that observes the new points, reversed
     table = np.full(n2, -1, np.int32)
     table[:g.n_new] = new[::-1]
     k2 = st.add_keyframe(table)
-    assert rm.add_keyframe(n2) == k2
-    rm.tables[k2] = table.tolist()
+    assert rm.add_keyframe(table) == k2
     for i in range(g.n_new):
-        rm.add_observation(int(table[i]), k2, i)
+        assert rm.add_observation(int(table[i]), k2, i)
     st.add_observations(table[:g.n_new], [k2] * g.n_new, idx=np.arange(g.n_new))
     got = st.keyframe_anchors(k2, min_pairs=10)
     A.assert_equal(got, rm.keyframe_anchors(k2, 10))

@@ -3,51 +3,23 @@ new keyframe the store route (AnchorPairsHIP, one call) and the host route (the 
 vMatchedIndices, own flags, query lists, has and n_no_ref, both equal the sequential restatement (tests/anchor_pairs_ref.py), and one
 dropped match leaves the lists of the later anchors as the host's second walk does (DropMatchHIP)."""
 import os
-import subprocess
 
 import pytest
 
 import anchor_pairs_ref as A
-from conftest import ROOT
+import shim_run
+import store_model
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 MIN_PAIRS = 5
 
 
 def test_anchor_shim_compiles_against_the_c_abi():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    assert os.path.exists(os.path.join(INTEG, "build", "anchor_pairs_shim_test"))
+    shim_run.build()
+    assert os.path.exists(shim_run.exe("anchor_pairs_shim_test"))
     src = open(os.path.join(INTEG, "anchor_pairs_hip.h")).read()
     assert "dsh_keyframe_anchors" in src and "defslam_hip_debug.h" not in src and "dsh_lab" not in src
     assert "anchor_pairs_hip.h" not in open(os.path.join(INTEG, "schwarp_database_hip.h")).read()
-
-
-def write_map(path, rm, slot, min_pairs, drop_anchor, drop_pair):
-    with open(path, "w") as f:
-        f.write(f"{len(rm.bad)} {len(rm.tables)}\n")
-        for b, r in zip(rm.bad, rm.ref):
-            f.write(f"{int(b)} {r}\n")
-        for t in rm.tables:
-            f.write(" ".join(map(str, [len(t)] + t)) + "\n")
-        f.write(f"{len(rm.log)}\n" + "".join(f"{p} {k} {i}\n" for p, k, i in rm.log))
-        f.write(f"{len(rm.erased)}\n" + "".join(f"{p} {k}\n" for p, k in rm.erased))
-        f.write(f"{slot} {min_pairs} {drop_anchor} {drop_pair}\n")
-
-
-def parse(path):
-    """route -> dict(anchors=[(slot, count, n_pairs, fits, [(idx1, idx2, own)], [j])], has=[..], no_ref=n)"""
-    out = {}
-    for line in open(path):
-        w = line.split()
-        r = out.setdefault(w[0], dict(anchors=[], has=None, no_ref=None))
-        if w[1] == "anchor":
-            pairs, queries = (part.split() for part in line.split("|")[1:])
-            r["anchors"].append((int(w[2]), int(w[3]), int(w[4]), int(w[5]), [tuple(map(int, p.split(":"))) for p in pairs], list(map(int, queries))))
-        elif w[1] == "has":
-            r["has"] = [int(x) for x in w[2:]]
-        else:
-            r["no_ref"] = int(w[2])
-    return out
 
 
 def ref_anchors(r, min_pairs, first=0):
@@ -61,10 +33,9 @@ def ref_anchors(r, min_pairs, first=0):
 
 @pytest.mark.gpu
 def test_anchor_shim_routes_agree_with_each_other_and_with_the_restatement(tmp_path):
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    exe = os.path.join(INTEG, "build", "anchor_pairs_shim_test")
+    shim_run.build()
     rm = A.SCENES["n70_k5"][0]()
-    slot = len(rm.tables) - 1
+    slot = len(rm.kfs) - 1
     want = rm.keyframe_anchors(slot, MIN_PAIRS)
     anchors = ref_anchors(want, MIN_PAIRS)
     # the dropped match: a pair of a fitting anchor whose point a later fitting anchor pairs too
@@ -72,15 +43,15 @@ def test_anchor_shim_routes_agree_with_each_other_and_with_the_restatement(tmp_p
     drop = next((a, n) for a in range(len(anchors)) for n, p in enumerate(points[a]) if any(p in later for later in points[a + 1:]))
     point = want["pair_point"][want["pair_ptr"][drop[0]] + drop[1]]
     idx2 = anchors[drop[0]][4][drop[1]][1]
-    write_map(tmp_path / "map.txt", rm, slot, MIN_PAIRS, *drop)
-    subprocess.run([exe, str(tmp_path / "map.txt"), str(tmp_path / "out.txt")], check=True, timeout=120)
-    got = parse(tmp_path / "out.txt")
+    store_model.write_scene(rm, tmp_path / "map.txt", f"{slot} {MIN_PAIRS} {drop[0]} {drop[1]}\n")
+    shim_run.run("anchor_pairs_shim_test", tmp_path / "map.txt", tmp_path / "out.txt")
+    got = {route: lists for (route, _), lists in store_model.parse_dump(tmp_path / "out.txt").items()}
     assert got["store"] == got["host"]
     assert got["store"]["anchors"] == anchors and got["store"]["has"] == [int(h) for h in want["has"]] and got["store"]["no_ref"] == want["n_no_ref"]
     # after the drop: (point, KF2) is erased and KF2's entry emptied; the later anchors' lists as a walk after the drop gives them
     assert got["store_drop"] == got["host_drop"]
     rm.erase_observation(point, slot)
-    rm.tables[slot][idx2] = -1
+    rm.kfs[slot].table[idx2] = -1
     again = rm.keyframe_anchors(slot, MIN_PAIRS)
     # the reference counts on its copy of :62, which still holds the point: the counts are the snapshot's, everything else a walk after the drop
     count = {a[0]: a[1] for a in anchors}

@@ -27,10 +27,10 @@ def tiny(ctx):
     for xyz in ([0.0, 0.0, 2.0], [0.1, 0.0, 2.0], [-0.1, 0.1, 2.0], [0.0, -0.1, 3.0]):
         rm.add_point(np.float32(xyz), np.float32(nrm), 4.0, rng.integers(0, 256, 32).astype(np.uint8))
     rm.add_keyframe([0, 1, -1])
-    rm.add_observation(0, 0)
-    rm.add_observation(1, 0)
+    assert rm.add_observation(0, 0)
+    assert rm.add_observation(1, 0)
     st = localmap.MapPointStore(ctx, points=4, keyframes=1, observations=2)
-    T.LM.fill_store(st, rm)
+    rm.fill(st)
     assert st.n_points == 4 and st.n_keyframes == 1
     return st, rm
 

@@ -9,19 +9,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import shim_run
 from conftest import ROOT
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 
 
 def _build():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    return os.path.join(INTEG, "build", "shim_test")
+    shim_run.build()
 
 
 def test_shim_and_writers_compile_against_the_c_abi():
-    exe = _build()
-    assert os.path.exists(exe) and os.path.exists(os.path.join(INTEG, "build", "result_writers.o"))
+    _build()
+    assert os.path.exists(shim_run.exe("shim_test")) and os.path.exists(shim_run.exe("result_writers.o"))
     # the shim header only names the public ABI
     src = open(os.path.join(INTEG, "defslam_hip_shim.h")).read()
     assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
@@ -40,7 +40,7 @@ def test_writers_produce_what_twiddle_reads(tmp_path):
                     '    if (!defslam_hip::save_results(e, defslam_hip::error_gts_name(argv[1], t))) return 1; }\n'
                     '  return m.ok() ? 0 : 1; }\n')
     exe = tmp_path / "w"
-    subprocess.run(["g++", "-std=c++11", "-Wall", "-Werror", "-I", ROOT, str(prog), os.path.join(INTEG, "build", "result_writers.o"), "-o", str(exe)], check=True)
+    subprocess.run(["g++", "-std=c++11", "-Wall", "-Werror", "-I", ROOT, str(prog), shim_run.exe("result_writers.o"), "-o", str(exe)], check=True)
     subprocess.run([str(exe), str(tmp_path)], check=True)
     assert open(tmp_path / "Matches.txt").read() == "00003 410 12 640\n00012 388 40 655\n00104 0 0 700\n"
     assert sorted(f for f in os.listdir(tmp_path) if f.startswith("ErrorGTs")) == ["ErrorGTs00003.txt", "ErrorGTs00012.txt"]
@@ -69,7 +69,7 @@ def test_writers_produce_what_twiddle_reads(tmp_path):
 @pytest.mark.gpu
 def test_def_pose_optimization_hip_mutates_frame_map_and_template_like_the_reference(gpu_ctx, oracle_mod, tmp_path):
     from defslam_amd import sft, synth
-    exe = _build()
+    _build()
     tmpl, fr = synth.make_problem("smoke", 3)
     rng = np.random.default_rng(5)
     M = fr.obs_nodes.shape[0]
@@ -100,8 +100,7 @@ def test_def_pose_optimization_hip_mutates_frame_map_and_template_like_the_refer
             f.write(f"{float(fr.obs_uv[m, 0])!r} {float(fr.obs_uv[m, 1])!r} {octave[m]} {kinds[i]} {fr.obs_facet[m]} "
                     + " ".join(repr(float(v)) for v in fr.obs_bary[m]) + "\n")
         f.write(f"{synth.REG_LAP!r} {synth.REG_INEX!r} {synth.REG_TEMP!r} 1\n640\n")
-    r = subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), str(tmp_path / "Matches.txt"), "0"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("shim_test", tmp_path / "in.txt", tmp_path / "out.txt", tmp_path / "Matches.txt", "0")
     tok = open(tmp_path / "out.txt").read().split()
     it = iter(tok)
     inliers, rep, pose_sets, locks, held_after, moved_under_lock = int(next(it)), float(next(it)), int(next(it)), int(next(it)), int(next(it)), int(next(it))
@@ -160,7 +159,6 @@ def test_schwarp_database_hip_and_normal_estimator_hip_follow_the_reference_flow
     found through the warp, which DiffProp records are stored, the normals and covariances written back."""
     from defslam_amd import nrsfm, synth
     _build()
-    exe = os.path.join(INTEG, "build", "mapping_shim_test")
     sc = synth.make_mapping_scene(seed=31)
     P, nt = sc["kp0"].shape[0], sc["n_tracked"]
     cam, lam = sc["cam"], 0.1
@@ -187,8 +185,7 @@ def test_schwarp_database_hip_and_normal_estimator_hip_follow_the_reference_flow
             for i in range(kf["N"]):
                 f.write(f"{float(kf['pix'][i, 0])!r} {float(kf['pix'][i, 1])!r} {int(kf['octave'][i])} {float(kf['norm'][i, 0])!r} {float(kf['norm'][i, 1])!r} {int(kf['mp'][i])} "
                         + " ".join(str(int(b)) for b in kf["desc"][i]) + "\n")
-    r = subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "0"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("mapping_shim_test", tmp_path / "in.txt", tmp_path / "out.txt", "0")
     tok = iter(open(tmp_path / "out.txt").read().split())
     nrec = int(next(tok))
     db = np.array([[float(next(tok)) for _ in range(22)] for _ in range(nrec)])
@@ -302,8 +299,7 @@ def test_schwarp_database_hip_and_normal_estimator_hip_follow_the_reference_flow
         np.testing.assert_allclose(sk[allrec[sel, 3].astype(int), 1:], ng.normal_rec[sel], rtol=2e-7)
     # ---- the same run with the DiffProp records resident in HBM (SchwarpDatabaseHIP::enable_device_records + ObtainK1K2DeviceHIP: dsh_diffdb,
     # dsh_schwarp_fit_batch_store, dsh_normals_estimate_db): no record on the host, and everything the calls change comes out the same
-    r2 = subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out_dev.txt"), "0", "devrec"], capture_output=True, text=True)
-    assert r2.returncode == 0, r2.stderr
+    r2 = shim_run.run("mapping_shim_test", tmp_path / "in.txt", tmp_path / "out_dev.txt", "0", "devrec")
     host_lines = open(tmp_path / "out.txt").read().split("\n")
     dev_lines = open(tmp_path / "out_dev.txt").read().split("\n")
     assert dev_lines[0].split() == [str(nrec), "0"]                # as many records on the device as the host map held; none on the host
@@ -311,8 +307,7 @@ def test_schwarp_database_hip_and_normal_estimator_hip_follow_the_reference_flow
     # ---- a point whose reference keyframe changed after its records were stored (MapPoint::EraseObservation can reassign mpRefKF): the stored
     # records are anchored in the OLD keyframe, the device mode has no first-keyframe normals for them -> it must skip the point (and say so),
     # not solve it against the new keyframe's key point.  The first 3 points with records are re-anchored before the normals are solved.
-    r3 = subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out_dev3.txt"), "0", "devrec", "3"], capture_output=True, text=True)
-    assert r3.returncode == 0, r3.stderr
+    r3 = shim_run.run("mapping_shim_test", tmp_path / "in.txt", tmp_path / "out_dev3.txt", "0", "devrec", "3")
     assert "reanchored 3 skipped 3" in r3.stderr
     l3 = open(tmp_path / "out_dev3.txt").read().split("\n")
     nkf = len(kfs)
@@ -345,7 +340,7 @@ def test_switch_frame_two_calls_through_the_shim_follow_the_oracle(oracle_mod, t
     then the regular call on the SAME frame object -- from the pose and the nodes the first call wrote, without the key points it flagged
     (DefOptimizer.cc:295).  The compiled shim executable makes both calls; each is checked against the oracle on the inputs it saw."""
     from defslam_amd import synth
-    exe = _build()
+    _build()
     tmpl, fr = synth.make_problem("smoke", 5)
     M = fr.obs_nodes.shape[0]
     facets_sorted = np.sort(tmpl.facets, axis=1)
@@ -366,8 +361,7 @@ def test_switch_frame_two_calls_through_the_shim_follow_the_oracle(oracle_mod, t
         for m in range(M):
             f.write(f"{float(fr.obs_uv[m, 0])!r} {float(fr.obs_uv[m, 1])!r} {octave[m]} 1 {fr.obs_facet[m]} " + " ".join(repr(float(v)) for v in fr.obs_bary[m]) + "\n")
         f.write(f"{synth.REG_LAP!r} {synth.REG_INEX!r} {synth.REG_TEMP!r} 1\n640\n")
-    r = subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), str(tmp_path / "Matches.txt"), "0", "switch"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("shim_test", tmp_path / "in.txt", tmp_path / "out.txt", tmp_path / "Matches.txt", "0", "switch")
     first = _parse_shim_out(str(tmp_path / "out.txt") + ".first", tmpl.n, N, M)
     second = _parse_shim_out(tmp_path / "out.txt", tmpl.n, N, M)
     obs_nodes = facets_sorted[fr.obs_facet].astype(np.int32)

@@ -105,8 +105,8 @@ def test_a_detached_store_refuses_both_entries():
 
 def _objects(m):
     """MapPoint-like objects of tests/mappoint_ref.py from the model's state."""
-    return [SimpleNamespace(xyz=m.xyz[p].copy(), ref_kf=m.ref[p], obs=dict(m.observations(p)), desc=m.desc[p].copy(), normal=m.normal[p].copy(),
-                            max_distance=m.max_distance[p], min_distance=m.min_distance[p], bad=m.bad[p]) for p in range(len(m.xyz))]
+    return [SimpleNamespace(xyz=pt.xyz.copy(), ref_kf=pt.ref, obs=dict(pt.obs), desc=pt.desc.copy(), normal=pt.normal.copy(),
+                            max_distance=pt.max_distance, min_distance=pt.min_distance, bad=pt.bad) for pt in m.points]
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -115,28 +115,29 @@ def test_model_equals_the_restatement_on_random_scenes(seed):
     and every mutated field of every point equal as bytes.  The scenes hold a point in two entries, a point that observes the new
     keyframe already, bad points, bad keyframes and reference keyframes outside the observations."""
     m, slot = KI.random_model(seed, K=7, N=8, P=24)
-    m.ref = [max(r, 0) for r in m.ref]            # the restatement has no "no reference keyframe"
+    for pt in m.points:
+        pt.ref = max(pt.ref, 0)                   # the restatement has no "no reference keyframe"
     pts = _objects(m)
-    table = m.tables[slot]
+    table = m.kfs[slot].table
     assert len({p for p in table if p >= 0}) < len([p for p in table if p >= 0])     # a point held twice
     updated, recent = R.process_new_keyframe(m.kfs, slot, [None if p < 0 else pts[p] for p in table])
     action, added, status = m.process_new_keyframe(slot)
     where = {id(o): p for p, o in enumerate(pts)}
     assert [where[id(x)] for x in updated] == added
     assert [where[id(x)] for x in recent] == [p for p, a in zip(table, action) if a == KI.RECENT]
-    assert [a == KI.BAD_POINT for a in action] == [p >= 0 and m.bad[p] for p in table]
+    assert [a == KI.BAD_POINT for a in action] == [p >= 0 and m.points[p].bad for p in table]
     assert KI.RECENT in action and KI.ADDED in action
     for p, o in enumerate(pts):
-        assert o.obs == dict(m.observations(p)) and len(o.obs) == m.n_obs[p], p
-        assert o.desc.tobytes() == m.desc[p].tobytes(), p
-        assert np.asarray(o.normal, np.float32).tobytes() == m.normal[p].tobytes(), p
-        assert np.float32(o.max_distance).tobytes() == m.max_distance[p].tobytes() and np.float32(o.min_distance).tobytes() == m.min_distance[p].tobytes(), p
+        assert o.obs == dict(m.observations(p)) and len(o.obs) == m.points[p].n_obs, p
+        assert o.desc.tobytes() == m.points[p].desc.tobytes(), p
+        assert np.asarray(o.normal, np.float32).tobytes() == m.points[p].normal.tobytes(), p
+        assert np.float32(o.max_distance).tobytes() == m.points[p].max_distance.tobytes() and np.float32(o.min_distance).tobytes() == m.points[p].min_distance.tobytes(), p
     assert all((s & KI.NO_OBS) == 0 for s in status)
     # a second pass adds nothing
-    before = m.points()
+    before = m.point_arrays()
     action2, added2, _ = m.process_new_keyframe(slot)
     assert added2 == [] and all(a != KI.ADDED for a in action2)
-    assert all(before[k].tobytes() == m.points()[k].tobytes() for k in before)
+    assert all(before[k].tobytes() == m.point_arrays()[k].tobytes() for k in before)
 
 
 def test_model_does_not_depend_on_the_order_of_the_log():
@@ -144,28 +145,28 @@ def test_model_does_not_depend_on_the_order_of_the_log():
     b, _ = KI.random_model(3, shuffle=False)
     assert [r[:3] for r in a.log] != [r[:3] for r in b.log] and sorted(r[:3] for r in a.log) == sorted(r[:3] for r in b.log)
     assert a.process_new_keyframe(slot) == b.process_new_keyframe(slot)
-    assert all(a.points()[k].tobytes() == b.points()[k].tobytes() for k in a.points())
+    assert all(v.tobytes() == b.point_arrays()[k].tobytes() for k, v in a.point_arrays().items())
 
 
 def test_model_statuses():
     """A bad point is skipped; no observation, every keyframe bad and no reference keyframe each leave what the contract says."""
     m, slot = KI.random_model(1, K=4, N=6, P=10, p_bad_kf=0.0, p_bad_point=0.0)
     p = next(p for p in range(10) if len(m.observations(p)) >= 2)
-    before = {k: v[p].copy() for k, v in m.points().items() if k != "bad"}
-    m.bad[p] = True
-    assert m.upkeep([p]) == [KI.SKIPPED_BAD] and all(before[k].tobytes() == m.points()[k][p].tobytes() for k in before)
-    m.bad[p] = False
+    before = {k: v[p].copy() for k, v in m.point_arrays().items() if k != "bad"}
+    m.points[p].bad = True
+    assert m.upkeep([p]) == [KI.SKIPPED_BAD] and all(before[k].tobytes() == m.point_arrays()[k][p].tobytes() for k in before)
+    m.points[p].bad = False
     for s, _ in m.observations(p):
         m.kfs[s].bad = True
-    m.ref[p] = m.observations(p)[0][0]
+    m.points[p].ref = m.observations(p)[0][0]
     assert m.upkeep([p]) == [KI.NO_GOOD_DESC]
-    after = {k: v[p].copy() for k, v in m.points().items()}
+    after = {k: v[p].copy() for k, v in m.point_arrays().items()}
     assert after["desc"].tobytes() == before["desc"].tobytes() and after["normal"].tobytes() != before["normal"].tobytes()
-    m.ref[p] = -1
+    m.points[p].ref = -1
     m.kfs[m.observations(p)[0][0]].bad = False
-    m.normal[p] = before["normal"]
+    m.points[p].normal = before["normal"]
     assert m.upkeep([p]) == [KI.NO_REF]
-    assert m.normal[p].tobytes() == before["normal"].tobytes() and m.desc[p].tobytes() == m.kfs[m.observations(p)[0][0]].desc[m.observations(p)[0][1]].tobytes()
+    assert m.points[p].normal.tobytes() == before["normal"].tobytes() and m.points[p].desc.tobytes() == m.kfs[m.observations(p)[0][0]].desc[m.observations(p)[0][1]].tobytes()
     for s, _ in m.observations(p):
         m.erase_observation(p, s)
-    assert m.upkeep([p]) == [KI.NO_OBS] and m.n_obs[p] == 0
+    assert m.upkeep([p]) == [KI.NO_OBS] and m.points[p].n_obs == 0

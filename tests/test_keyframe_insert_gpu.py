@@ -21,17 +21,17 @@ def stores_from(ctx, m, **caps):
     from defslam_amd import localmap, mappoint
     ks = mappoint.KeyFrameStore(ctx, 2)                                             # it grows, the resident octaves and pyramids too
     st = localmap.MapPointStore(ctx, **caps)
-    KI.fill_stores(m, ks, st)
+    m.fill(st, ks)
     return ks, st
 
 
 def check_store(st, m):
     """dsh_point_store_get_points of EVERY point and n_obs against the model."""
-    g, w = st.get_points(), m.points()
+    g, w = st.get_points(), m.point_arrays()
     for k in ("xyz", "normal", "max_distance", "desc"):
         assert getattr(g, k).tobytes() == w[k].tobytes(), k
     assert g.bad.tolist() == w["bad"].tolist()
-    assert st.get_state().n_obs.tolist() == m.n_obs
+    assert st.get_state().n_obs.tolist() == m.state()["n_obs"].tolist()
     return g
 
 
@@ -53,7 +53,7 @@ def test_big_scene_every_count_class_log_order_and_the_second_call(gpu_ctx):
     observed and a reference of -1; then every call once more, which adds nothing and changes nothing."""
     from defslam_amd import sft
     m, nm = KI.big_scene()
-    assert len(m.log) >= 24000 and len(m.kfs) == 132 and all(len(t) == 6 for t in m.tables)
+    assert len(m.log) >= 24000 and len(m.kfs) == 132 and all(len(k.table) == 6 for k in m.kfs)
     assert sum(1 for r in m.log if not r[3]) >= 20
     ks, st = stores_from(gpu_ctx, m, points=8, keyframes=4, observations=64)
     check_store(st, m)
@@ -112,8 +112,8 @@ def test_strides_of_the_work_lists_and_ties_in_every_class(gpu_ctx):
     the large path, and the lowest slot wins although the highest holds the other descriptor."""
     m, nm = KI.big_scene(fillers=350, singles=4200, ties=(12, 24, 48, 124))
     ks, st = stores_from(gpu_ctx, m)
-    ids = list(range(len(m.xyz)))
-    large = [p for p in ids if not m.bad[p] and len(m.observations(p)) > 64]
+    ids = list(range(len(m.points)))
+    large = [p for p in ids if not m.points[p].bad and len(m.observations(p)) > 64]
     assert len(ids) > 4096 and sum(1 + -(-sum(1 for s, _ in m.observations(p) if not m.kfs[s].bad) // 64) for p in large) > 1024
     u = st.upkeep(ks, ids)
     assert u.status.tolist() == m.upkeep(ids) and u.n_selected == len(ids) - u.n_bad
@@ -123,7 +123,7 @@ def test_strides_of_the_work_lists_and_ties_in_every_class(gpu_ctx):
     # the embedded selection over the same long store: every point gets a facet first
     st.set_embedding(ids, np.tile(np.int32([0, 1, 2]), (len(ids), 1)), np.tile([1.0, 0.0, 0.0], (len(ids), 1)))
     e = st.upkeep(ks, what=KI.NORMAL_DEPTH, embedded=True)
-    assert e.n_selected == sum(1 for p in ids if not m.bad[p]) > 4096
+    assert e.n_selected == sum(1 for p in ids if not m.points[p].bad) > 4096
     m.upkeep(ids, KI.NORMAL_DEPTH)
     check_store(st, m)
     st.close()
@@ -134,7 +134,7 @@ def test_strides_of_the_work_lists_and_ties_in_every_class(gpu_ctx):
 def test_keyframes_with_no_and_one_key_point(gpu_ctx, table):
     m, slot = KI.random_model(11, K=5, N=6, P=12, new_table=table)
     ks, st = stores_from(gpu_ctx, m)
-    m.bad[4] = False
+    m.points[4].bad = False
     st.set_points_bad([4], [0])
     g = process_both(st, ks, m, slot)
     assert g.n_added == len(table)
@@ -168,7 +168,7 @@ def test_a_table_that_crosses_the_wavefronts_and_tiles_of_the_classify_kernel(gp
     for edge in (64, 256)[:1 if n == 70 else 2]:
         assert {edge - 1, edge, edge + 1} & set(added_at) and min(added_at) < edge - 1 and max(added_at) > edge + 1
     assert action.count(KI.BAD_POINT) >= 3 and action.count(KI.EMPTY) == len(range(8, n, 9)) and action[1] == KI.RECENT
-    assert not m.bad[table[3]] and action[3] == KI.ADDED and action[66] == action[n - 2] == KI.RECENT
+    assert not m.points[table[3]].bad and action[3] == KI.ADDED and action[66] == action[n - 2] == KI.RECENT
     # the records the call appended, in entry order, and every point's observations read back
     assert [(r[0], r[1], r[2]) for r in m.log[R0:]] == [(table[i], slot, i) for i in added_at] and g.added.tolist() == [table[i] for i in added_at]
     o = st.observations()
@@ -191,7 +191,7 @@ def test_bad_keyframes_some_all_and_the_statuses_by_id(gpu_ctx):
     p = max(range(14), key=lambda q: len(m.observations(q)))
     obs = m.observations(p)
     assert len(obs) >= 3
-    m.ref[p] = obs[0][0]
+    m.points[p].ref = obs[0][0]
     st.set_reference_keyframes([p], [obs[0][0]])
     ids = list(range(14))
     for n_bad in (1, len(obs)):
@@ -205,7 +205,7 @@ def test_bad_keyframes_some_all_and_the_statuses_by_id(gpu_ctx):
         g = check_store(st, m)
         if n_bad == len(obs):
             assert g.desc[p].tobytes() == before.desc[0].tobytes()
-    m.ref[p] = -1
+    m.points[p].ref = -1
     st.set_reference_keyframes([p], [-1])
     u = st.upkeep(ks, [p], what=KI.NORMAL_DEPTH)
     assert u.status.tolist() == m.upkeep([p], KI.NORMAL_DEPTH) == [KI.NO_GOOD_DESC | KI.NO_REF] and u.n_no_ref == 1
@@ -239,29 +239,30 @@ def test_equals_the_three_call_path(gpu_ctx):
     local map's votes are identical."""
     from defslam_amd import mappoint
     m, slot = KI.random_model(21, K=40, N=6, P=60, p_obs=0.9, p_bad_point=0.05, p_bad_kf=0.1)
-    m.ref = [max(r, 0) for r in m.ref]                                              # dsh_mappoint_update needs a reference keyframe
+    for pt in m.points:
+        pt.ref = max(pt.ref, 0)                                                     # dsh_mappoint_update needs a reference keyframe
     ks, new = stores_from(gpu_ctx, m)
     ks2, old = stores_from(gpu_ctx, m)
     g = new.process_new_keyframe(ks, slot)
     # today's path, decided on the host objects
-    table, seen, add = m.tables[slot], set(), []
+    table, seen, add = m.kfs[slot].table, set(), []
     for i, p in enumerate(table):
-        if p >= 0 and not m.bad[p] and not m.live(p, slot) and p not in seen:
+        if p >= 0 and not m.points[p].bad and not m.live(p, slot) and p not in seen:
             seen.add(p)
             add.append((p, i))
     assert g.added.tolist() == [p for p, _ in add] and len(add) >= 3
     old.add_observations([p for p, _ in add], [slot] * len(add), idx=[i for _, i in add])
     for p, i in add:
-        m.add_observation(p, slot, i)
+        assert m.add_observation(p, slot, i)
     ids = [p for p, _ in add]
     cur = old.get_points(ids)
-    u = mappoint.update(gpu_ctx, ks2, cur.xyz, [m.observations(p) for p in ids], [m.ref[p] for p in ids], desc=cur.desc, normal=cur.normal,
+    u = mappoint.update(gpu_ctx, ks2, cur.xyz, [m.observations(p) for p in ids], [m.points[p].ref for p in ids], desc=cur.desc, normal=cur.normal,
                         max_distance=cur.max_distance)
     old.update_points(ids, normal=u.normal, max_distance=u.max_distance, desc=u.desc)
     a, b = new.get_points(), old.get_points()
     for k in ("xyz", "normal", "max_distance", "desc", "bad"):
         assert getattr(a, k).tobytes() == getattr(b, k).tobytes(), k
-    assert new.get_state().n_obs.tolist() == old.get_state().n_obs.tolist() == m.n_obs
+    assert new.get_state().n_obs.tolist() == old.get_state().n_obs.tolist() == m.state()["n_obs"].tolist()
     x, y = new.keyframe_anchors(slot, 1), old.keyframe_anchors(slot, 1)
     for k in x.__dataclass_fields__:
         assert np.asarray(getattr(x, k)).tolist() == np.asarray(getattr(y, k)).tolist(), k
@@ -283,7 +284,7 @@ def test_embedded_upkeep_after_a_template_switch(gpu_ctx):
     ctx = sft.Context(0)                                                             # its own context: the test replaces the template
     m, _ = KI.random_model(31, K=5, N=6, P=16, p_obs=0.7, p_bad_kf=0.2)
     for p in range(3):
-        m.xyz[p] = np.float32([50, 50, 5])                                           # outside the template unless the keyframe moves them
+        m.points[p].xyz = np.float32([50, 50, 5])                                    # outside the template unless the keyframe moves them
     r = 2
     xs = ys = 7
     gx, gy = np.meshgrid(np.linspace(-3, 3, xs), np.linspace(-3, 3, ys), indexing="ij")
@@ -301,29 +302,29 @@ def test_embedded_upkeep_after_a_template_switch(gpu_ctx):
     for j, i in enumerate(sw[0].new_idx.tolist()):
         q = m.add_point(pts.xyz[sw[0].first_id + j], pts.normal[sw[0].first_id + j], pts.max_distance[sw[0].first_id + j], pts.desc[sw[0].first_id + j], ref=r)
         assert q == sw[0].first_id + j and ref[q] == r
-        m.add_observation(q, r, i)
-        m.tables[r][i] = q
-    for p in range(len(m.xyz)):
-        m.xyz[p] = pts.xyz[p].copy()
+        assert m.add_observation(q, r, i)
+        m.kfs[r].table[i] = q
+    for p in range(len(m.points)):
+        m.points[p].xyz = pts.xyz[p].copy()
     has_facet = (st.get_embedding()[0][:, 0] >= 0).tolist()
     ids = m.embedded_ids(has_facet)
-    assert 0 < len(ids) < len(m.xyz) and sw[0].n_embedded == len(ids)
+    assert 0 < len(ids) < len(m.points) and sw[0].n_embedded == len(ids)
     u = st.upkeep(ks, what=KI.NORMAL_DEPTH, embedded=True)
     want = m.upkeep(ids, KI.NORMAL_DEPTH)
     assert u.status is None and u.n_selected == len(ids) and u.n_bad == 0
     assert (u.n_no_obs, u.n_no_ref) == (sum(1 for s in want if s & KI.NO_OBS), sum(1 for s in want if s & KI.NO_REF))
     check_store(st, m)
     # the caller-side path on the second store
-    work = [p for p in ids if m.observations(p) and m.ref[p] >= 0]
+    work = [p for p in ids if m.observations(p) and m.points[p].ref >= 0]
     xyz = st2.get_state(work).xyz
     cur = st2.get_points(work)
-    res = mappoint.update(ctx, ks2, xyz, [m.observations(p) for p in work], [m.ref[p] for p in work], what=mappoint.NORMAL_DEPTH, normal=cur.normal,
+    res = mappoint.update(ctx, ks2, xyz, [m.observations(p) for p in work], [m.points[p].ref for p in work], what=mappoint.NORMAL_DEPTH, normal=cur.normal,
                           max_distance=cur.max_distance)
     st2.update_points(work, normal=res.normal, max_distance=res.max_distance)
     a, b = st.get_points(), st2.get_points()
     for k in ("xyz", "normal", "max_distance", "desc", "bad"):
         assert getattr(a, k).tobytes() == getattr(b, k).tobytes(), k
-    for bad_ids, part in (([1, 1], "repeated"), ([0, len(m.xyz)], "outside the store"), ([-1], "outside the store")):
+    for bad_ids, part in (([1, 1], "repeated"), ([0, len(m.points)], "outside the store"), ([-1], "outside the store")):
         with pytest.raises(sft.DshError, match=part):
             st.upkeep(ks, bad_ids)
     check_store(st, m)
@@ -353,7 +354,7 @@ def test_refusals_that_need_stored_data(gpu_ctx):
     st.add_observations([free], [0])
     both(ks._h, STATE, "without a key point index")
     st.erase_observations([free], [0])
-    m.add_observation(free, 0, 0)                                                    # the blanked record stays in the log
+    assert m.add_observation(free, 0, 0)                                             # the blanked record stays in the log
     m.erase_observation(free, 0)
     # fewer keyframes than the point store, then an N that differs
     short = mappoint.KeyFrameStore(gpu_ctx, 2)

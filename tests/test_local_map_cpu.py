@@ -80,7 +80,7 @@ def scene_to_ref(sc):
     for k in range(sc["tables"].shape[0]):
         rm.add_keyframe(sc["tables"][k], sc["parents"][k], sc["kf_bad"][k])
     for p, k in zip(sc["obs_point"].tolist(), sc["obs_kf"].tolist()):
-        rm.add_observation(p, k)
+        assert rm.add_observation(p, k)
     return rm
 
 

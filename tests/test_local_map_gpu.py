@@ -79,9 +79,9 @@ def test_hand_built_maps_on_the_device(gpu_ctx, name):
     from defslam_amd import localmap
     rm, frame_points, want = LM.hand_maps()[name]
     if name == "erased_observation":                                # the device must see the erase itself, not a log without the pair
-        rm.add_observation(1, 2)
+        assert rm.add_observation(1, 2)
     st = localmap.MapPointStore(gpu_ctx, points=2, keyframes=1, observations=2)        # tiny: every array grows
-    LM.fill_store(st, rm)
+    rm.fill(st)
     if name == "erased_observation":
         st.erase_observations([1], [2])
         rm.erase_observation(1, 2)
@@ -95,7 +95,7 @@ def test_no_votes_keeps_the_previous_list_on_the_device(gpu_ctx):
     from defslam_amd import localmap
     rm, frame_points, want = LM.hand_maps()["parent_break"]
     st = localmap.MapPointStore(gpu_ctx, points=8, keyframes=8, observations=8)
-    LM.fill_store(st, rm)
+    rm.fill(st)
     g0 = st.update_local_map([-1, -1])                              # before any vote: no list at all
     assert g0.local_kf.tolist() == [] and g0.ref_kf == -1 and g0.n_local_points == 0
     rm.update_local_map([-1, -1])
@@ -143,7 +143,7 @@ class Both:
     def observe(self, pairs):
         self.st.add_observations([p for p, _ in pairs], [k for _, k in pairs])
         for p, k in pairs:
-            self.rm.add_observation(p, k)
+            assert self.rm.add_observation(p, k)
 
     def forget(self, pairs):
         self.st.erase_observations([p for p, _ in pairs], [k for _, k in pairs])
@@ -258,7 +258,7 @@ def test_refusals_on_a_live_store_store_nothing(gpu_ctx):
     from defslam_amd import localmap, sft
     rm, frame_points, want = LM.hand_maps()["parent_break"]
     st = localmap.MapPointStore(gpu_ctx, points=8, keyframes=8, observations=8)
-    LM.fill_store(st, rm)
+    rm.fill(st)
     z3, z1, d = np.zeros((1, 3), np.float32), np.ones(1, np.float32), np.zeros((1, 32), np.uint8)
     for call in (lambda: st.add_observations([0, 0], [1, 1]),                  # repeated in the batch
                  lambda: st.add_observations([0], [0]),                        # stored already

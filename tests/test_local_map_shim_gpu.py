@@ -2,21 +2,20 @@
 UpdateLocalMapHIP and SearchLocalPointsStoreHIP change the stand-in objects exactly as the sequential restatements
 (tests/local_map_ref.py, tests/track_search_ref.py) of the reference's calls do."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import shim_run
 from test_local_map_cpu import scene_to_ref
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 FRAME_ID = 7          # mnId of the driver's current frame
 
 
 def test_local_map_shim_compiles_against_the_c_abi():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    assert os.path.exists(os.path.join(INTEG, "build", "localmap_shim_test"))
+    shim_run.build()
+    assert os.path.exists(shim_run.exe("localmap_shim_test"))
     src = open(os.path.join(INTEG, "local_map_hip.h")).read()
     assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
 
@@ -24,12 +23,10 @@ def test_local_map_shim_compiles_against_the_c_abi():
 @pytest.mark.gpu
 def test_local_map_shim_follows_the_reference_flow(tmp_path):
     from defslam_amd import synth, track
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    exe = os.path.join(INTEG, "build", "localmap_shim_test")
+    shim_run.build()
     sc = synth.make_local_map_scene(21, n_kf=40, n_kp=500, obs_per_point=8, n_frame_kp=1000)
     synth.write_local_map_scene(sc, tmp_path / "in.txt")
-    r = subprocess.run(["timeout", "-k", "10", "120", exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "0"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("localmap_shim_test", tmp_path / "in.txt", tmp_path / "out.txt", "0")
     P, K, N = sc["xyz"].shape[0], sc["tables"].shape[0], sc["frame_points"].shape[0]
     tok = iter(open(tmp_path / "out.txt").read().split())
     ints = lambda n: np.array([int(next(tok)) for _ in range(n)])

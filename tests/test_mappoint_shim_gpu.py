@@ -2,21 +2,20 @@
 device: ProcessNewKeyFrameHIP over a short keyframe sequence, then a Repose-style geometry-only update, leave every map point's
 descriptor, normal, depth range and observations as the sequential restatement (tests/mappoint_ref.py) of the reference's calls does."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import mappoint_ref as R
-from conftest import ROOT
+import shim_run
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 LEVELS = 8
 
 
 def test_mappoint_shim_compiles_against_the_c_abi():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    assert os.path.exists(os.path.join(INTEG, "build", "mappoint_shim_test"))
+    shim_run.build()
+    assert os.path.exists(shim_run.exe("mappoint_shim_test"))
     src = open(os.path.join(INTEG, "mappoint_upkeep_hip.h")).read()
     assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
 
@@ -30,8 +29,7 @@ def _flip(rng, d, n):
 @pytest.mark.gpu
 def test_mappoint_shim_follows_the_reference_flow(tmp_path):
     from defslam_amd import mappoint, track
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    exe = os.path.join(INTEG, "build", "mappoint_shim_test")
+    shim_run.build()
     rng = np.random.default_rng(11)
     sf, _ = track.orb_pyramid(LEVELS)
     K, P, N = 12, 300, 400
@@ -73,8 +71,7 @@ def test_mappoint_shim_follows_the_reference_flow(tmp_path):
         for k, m in steps:
             f.write(f"{k} {N} " + " ".join(str(int(x)) for x in m) + "\n")
         f.write(f"{len(moved)}\n" + "".join(f"{int(p)} " + " ".join(repr(float(v)) for v in new_xyz[i]) + "\n" for i, p in enumerate(moved)))
-    r = subprocess.run(["timeout", "-k", "10", "120", exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "0"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("mappoint_shim_test", tmp_path / "in.txt", tmp_path / "out.txt", "0")
     tok = iter(open(tmp_path / "out.txt").read().split())
     order = [int(next(tok)) for _ in range(K)]
 

@@ -59,7 +59,7 @@ def test_restatement_a_query_without_observations_does_not_block_its_key_point()
     assert r["nmatches"] == M.HAND_BLOCKING_NMATCHES and r["th_used"] == 20.0
     rm.erase_observation(0, 0)                                           # n_obs == 0 and not bad: unreachable through the reference's erase rule
     rm.set_bad(3)
-    assert rm.n_obs[0] == 0
+    assert rm.points[0].n_obs == 0
     r = rm.motion_model_search(fr, min_matches=2)
     assert r["frame_points"].tolist() == M.HAND_FRAME_POINTS and r["match"].tolist() == M.HAND_MATCH
     assert r["nmatches"] == M.HAND_NMATCHES == 1 + sum(p >= 0 for p in M.HAND_FRAME_POINTS) and r["th_used"] == 20.0
@@ -88,7 +88,7 @@ def test_restatement_agrees_with_the_packed_search_when_every_query_has_observat
     rm = M.scene_to_ref(sc)
     e = rm.end_frame(*M.make_last_frame(sc, L))
     idx, xyz, octave, desc = rm.last_frame_queries()
-    assert all(rm.n_obs[rm.last_points[i]] > 0 for i in idx) and 0 < len(idx) <= e["kept"]
+    assert all(rm.points[rm.last_points[i]].n_obs > 0 for i in idx) and 0 < len(idx) <= e["kept"]
     if L >= 130:
         assert e["cleaned"] > 0 and len(idx) < e["kept"]              # CleanMatches had work, and so has the search's own filter
     r = rm.motion_model_search(sc["frame"])

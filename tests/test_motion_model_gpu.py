@@ -66,7 +66,7 @@ def hand_both(ctx):
     from defslam_amd import localmap
     rm = M.hand_map()
     st = localmap.MapPointStore(ctx, points=2, keyframes=1, observations=2)        # tiny: every array grows
-    M.T.LM.fill_store(st, rm)
+    rm.fill(st)
     for p in range(len(rm.points)):
         if rm.nodes[p] is not None:
             st.set_embedding([p], [rm.nodes[p]], [rm.bary[p]])

@@ -2,21 +2,20 @@
 TrackWithMotionModelStoreHIP leave the stand-in frames exactly as the host's loops and SearchByProjectionHIP over a second copy of them
 do, and both equal the sequential restatement (tests/motion_model_ref.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import motion_model_ref as M
 import track_close_ref as T
-from conftest import ROOT
+import shim_run
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 
 
 def test_motion_model_shim_compiles_against_the_c_abi():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    assert os.path.exists(os.path.join(INTEG, "build", "motionmodel_shim_test"))
+    shim_run.build()
+    assert os.path.exists(shim_run.exe("motionmodel_shim_test"))
     src = open(os.path.join(INTEG, "motion_model_hip.h")).read()
     assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
     assert "dsh_search_by_projection" not in src and "world_pos" not in src       # nothing per map point is packed on the host
@@ -33,14 +32,11 @@ def mark_outliers(fp):
 @pytest.mark.gpu
 def test_motion_model_shim_store_way_host_way_and_restatement_agree(tmp_path):
     from defslam_amd import synth
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    exe = os.path.join(INTEG, "build", "motionmodel_shim_test")
+    shim_run.build()
     sc = synth.make_track_close_scene(1, n_kf=30, n_kp=300, obs_per_point=6, n_frame_kp=600)
     synth.write_local_map_scene(sc, tmp_path / "map.txt")
     synth.write_track_close_scene(sc, T.previous_frame_points(sc), tmp_path / "close.txt")
-    r = subprocess.run(["timeout", "-k", "10", "120", exe, str(tmp_path / "map.txt"), str(tmp_path / "close.txt"), str(tmp_path / "out.txt"), "0"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("motionmodel_shim_test", tmp_path / "map.txt", tmp_path / "close.txt", tmp_path / "out.txt", "0")
     N = sc["final_points"].shape[0]
     tok = iter(open(tmp_path / "out.txt").read().split())
     ints = lambda n: [int(next(tok)) for _ in range(n)]

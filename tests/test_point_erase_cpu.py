@@ -130,7 +130,7 @@ def _four_obs_point(ref):
         rm.add_keyframe([-1] * 4)
     p = rm.add_point(ref=ref)
     for kf in (3, 1, 4, 2):                                           # arrival order is not slot order
-        rm.kfs[kf]["mvpMapPoints"][kf % 4] = p
+        rm.kfs[kf].table[kf % 4] = p
         rm.add_observation(p, kf, kf % 4)
     return rm, p
 
@@ -139,15 +139,15 @@ def test_erasing_the_reference_keyframe_of_a_four_observation_point_moves_it_to_
     rm, p = _four_obs_point(ref=3)
     status, c = rm.erase_observations([p], [3])
     mp = rm.points[p]
-    assert status.tolist() == [1] and mp["mpRefKF"] == 1 and mp["nObs"] == 3 and not mp["mbBad"]
-    assert rm.observations(p) == {1: 1, 2: 2, 4: 0}
+    assert status.tolist() == [1] and mp.ref == 1 and mp.n_obs == 3 and not mp.bad
+    assert dict(rm.observations(p)) == {1: 1, 2: 2, 4: 0}
     assert c == dict(n_found=1, n_ref_moved=1, n_set_bad=0, n_records=1, n_entries=0)
-    assert rm.kfs[3]["mvpMapPoints"][3] == p                           # EraseObservation alone leaves the keyframe's table
+    assert rm.kfs[3].table[3] == p                           # EraseObservation alone leaves the keyframe's table
     # erasing a keyframe that is not the reference leaves it
     rm, p = _four_obs_point(ref=3)
     status, c = rm.erase_observations([p], [1], erase_match=True)
-    assert status.tolist() == [1] and rm.points[p]["mpRefKF"] == 3 and c["n_ref_moved"] == 0 and c["n_entries"] == 1
-    assert rm.kfs[1]["mvpMapPoints"][1] == -1
+    assert status.tolist() == [1] and rm.points[p].ref == 3 and c["n_ref_moved"] == 0 and c["n_entries"] == 1
+    assert rm.kfs[1].table[1] == -1
 
 
 def test_three_to_two_observations_cascades_and_leaves_n_obs_at_two():
@@ -155,17 +155,17 @@ def test_three_to_two_observations_cascades_and_leaves_n_obs_at_two():
     rm.erase_observations([p], [4])
     status, c = rm.erase_observations([p], [2])
     mp = rm.points[p]
-    assert status.tolist() == [2] and mp["mbBad"] and mp["nObs"] == 2 and rm.observations(p) == {}
-    assert mp["mpRefKF"] == 1                                          # moved before the cascade, on the records the cascade removed
+    assert status.tolist() == [2] and mp.bad and mp.n_obs == 2 and dict(rm.observations(p)) == {}
+    assert mp.ref == 1                                          # moved before the cascade, on the records the cascade removed
     assert c == dict(n_found=1, n_ref_moved=1, n_set_bad=1, n_records=3, n_entries=2)
-    assert [rm.kfs[kf]["mvpMapPoints"][kf % 4] for kf in (1, 2, 3, 4)] == [-1, p, -1, p]   # the cascade's entries; the pairs' own stay
+    assert [rm.kfs[kf].table[kf % 4] for kf in (1, 2, 3, 4)] == [-1, p, -1, p]   # the cascade's entries; the pairs' own stay
     # the only observation: the reference keyframe stays where the reference would read end()
     rm = PE.EraseRefMap()
     rm.add_keyframe([0])
     rm.add_point(ref=0)
     rm.add_observation(0, 0, 0)
     status, c = rm.erase_observations([0], [0])
-    assert status.tolist() == [2] and rm.points[0]["mpRefKF"] == 0 and rm.points[0]["nObs"] == 0 and c["n_ref_moved"] == 0
+    assert status.tolist() == [2] and rm.points[0].ref == 0 and rm.points[0].n_obs == 0 and c["n_ref_moved"] == 0
 
 
 def test_a_pair_that_is_not_stored_changes_nothing():
@@ -179,7 +179,7 @@ def test_a_pair_that_is_not_stored_changes_nothing():
 
 def test_the_small_scene_is_what_its_docstring_says():
     rm, (pts, slots) = PE.small_scene()
-    assert len(rm.kfs) == 3 and all(len(kf["mvpMapPoints"]) == 8 for kf in rm.kfs) and len(rm.points) == 6
+    assert len(rm.kfs) == 3 and all(len(kf.table) == 8 for kf in rm.kfs) and len(rm.points) == 6
     status, c = rm.erase_observations(pts, slots, erase_match=True)
     s = rm.state()
     assert status.tolist() == [2, 2, 2, 2, 2, 0]
@@ -205,7 +205,7 @@ def test_cull_decisions_equal_track_close_ref_on_the_same_counters():
         tr.add_point(bad=bad)
         tr.set_counters(p, v, f)
         rm.add_observation(p, 0, p)
-        rm.kfs[0]["mvpMapPoints"][p] = p
+        rm.kfs[0].table[p] = p
     ids = list(range(len(counters) + 1))
     action, c = rm.cull(ids, first_kf + [9], 10)
     assert action.tolist() == tr.cull(ids, first_kf + [9], 10).tolist()
@@ -213,6 +213,6 @@ def test_cull_decisions_equal_track_close_ref_on_the_same_counters():
     gone = [p for p in ids if action[p] == 2]
     assert c == dict(n_found=0, n_ref_moved=0, n_set_bad=len(gone), n_records=len(gone), n_entries=len(gone))
     for p in ids:
-        assert rm.points[p]["mbBad"] == tr.points[p].bad
-        assert rm.points[p]["nObs"] == 1                               # setBadFlag leaves nObs
-        assert (rm.observations(p) == {}) == (action[p] == 2) and (rm.kfs[0]["mvpMapPoints"][p] == -1) == (action[p] == 2)
+        assert rm.points[p].bad == tr.points[p].bad
+        assert rm.points[p].n_obs == 1                               # setBadFlag leaves nObs
+        assert (dict(rm.observations(p)) == {}) == (action[p] == 2) and (rm.kfs[0].table[p] == -1) == (action[p] == 2)

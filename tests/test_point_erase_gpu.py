@@ -9,7 +9,9 @@ import pytest
 
 import anchor_pairs_ref as AR
 import keyframe_insert_ref as KI
+import local_map_ref as LM
 import point_erase_ref as PE
+from store_model import assert_state
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +21,7 @@ OK, ARG, STATE = 0, 1, 3
 def store_from(ctx, rm, **caps):
     from defslam_amd import localmap
     st = localmap.MapPointStore(ctx, **caps)
-    PE.fill_store(st, rm)
+    rm.fill(st)
     return st
 
 
@@ -28,13 +30,13 @@ def erase_both(st, rm, pts, slots, erase_match, what=""):
     status, c = rm.erase_observations(pts, slots, erase_match=erase_match)
     assert g.status.tolist() == status.tolist(), (what, g.status, status)
     PE.assert_counts(g.counts, c, what)
-    PE.assert_state(st, rm, what)
+    assert_state(st, rm, what)
     return g
 
 
 def set_bad_both(st, rm, ids, what=""):
     PE.assert_counts(st.set_bad_full(ids), rm.set_bad(ids), what)
-    PE.assert_state(st, rm, what)
+    assert_state(st, rm, what)
 
 
 def cull_both(st, rm, ids, first_kf, current_kf, what=""):
@@ -42,7 +44,7 @@ def cull_both(st, rm, ids, first_kf, current_kf, what=""):
     action, c = rm.cull(ids, first_kf, current_kf)
     assert g.action.tolist() == action.tolist(), (what, g.action, action)
     PE.assert_counts(g.counts, c, what)
-    PE.assert_state(st, rm, what)
+    assert_state(st, rm, what)
     return g
 
 
@@ -53,7 +55,7 @@ def test_small_scene_every_case_in_one_batch(gpu_ctx, erase_match):
     pair and under the cascade, a bad point with records, a pair that is not stored; then the same call again, which finds nothing."""
     rm, (pts, slots) = PE.small_scene()
     st = store_from(gpu_ctx, rm, points=2, keyframes=1, observations=4)
-    PE.assert_state(st, rm, "before")
+    assert_state(st, rm, "before")
     g = erase_both(st, rm, pts, slots, erase_match, "first")
     assert g.status.tolist() == [2, 2, 2, 2, 2, 0] and g.counts.n_ref_moved == 2 and g.counts.n_records == 13
     assert st.get_reference_keyframes().tolist() == [1, 2, 2, 1, 0, 0]
@@ -74,21 +76,21 @@ def test_a_log_that_spans_several_workgroups_of_the_sweep(gpu_ctx):
     doomed = sorted({rm.log[r][0] for r in edge})
     # points whose last record in the log has their lowest slot: their reference keyframe becomes the highest slot, which the batch erases
     last = {}
-    for r, (p, kf, _) in enumerate(rm.log):
+    for r, (p, kf, _, _) in enumerate(rm.log):
         last[p] = kf
-    late = [p for p, mp in enumerate(rm.points) if p not in doomed and len(mp["mObservations"]) >= 2 and last[p] == min(mp["mObservations"])]
-    assert sum(1 for p in late if len(rm.points[p]["mObservations"]) >= 4) >= 5 and sum(1 for p in late if len(rm.points[p]["mObservations"]) <= 3) >= 5
+    late = [p for p, mp in enumerate(rm.points) if p not in doomed and len(mp.obs) >= 2 and last[p] == min(mp.obs)]
+    assert sum(1 for p in late if len(rm.points[p].obs) >= 4) >= 5 and sum(1 for p in late if len(rm.points[p].obs) <= 3) >= 5
     for p in late:
-        rm.points[p]["mpRefKF"] = max(rm.points[p]["mObservations"])
+        rm.points[p].ref = max(rm.points[p].obs)
     st = store_from(gpu_ctx, rm, points=16, keyframes=2, observations=64)
     set_bad_both(st, rm, doomed, "edges")
     rng = np.random.default_rng(5)
     others = [int(p) for p in rng.permutation(len(rm.points))[:200] if p not in late and p not in doomed]
     pts = late + others
-    slots = [max(rm.points[p]["mObservations"]) for p in late] + [int(rng.integers(0, len(rm.kfs))) for _ in others]
-    before = [rm.points[p]["mpRefKF"] for p in late]
+    slots = [max(rm.points[p].obs) for p in late] + [int(rng.integers(0, len(rm.kfs))) for _ in others]
+    before = [rm.points[p].ref for p in late]
     g = erase_both(st, rm, pts, slots, True, "late")
-    assert all(rm.points[p]["mpRefKF"] == last[p] != b for p, b in zip(late, before))
+    assert all(rm.points[p].ref == last[p] != b for p, b in zip(late, before))
     assert g.counts.n_ref_moved >= len(late) and 0 < g.counts.n_set_bad < g.counts.n_found < len(pts)
     st.close()
 
@@ -100,8 +102,8 @@ def test_a_log_that_had_grown_and_holds_blanks_and_the_mirror_afterwards(gpu_ctx
     st = store_from(gpu_ctx, rm, points=4, keyframes=1, observations=8)
     rng = np.random.default_rng(2)
     pts = [int(p) for p in rng.permutation(len(rm.points))[:60]]
-    slots = [min(rm.points[p]["mObservations"]) if i % 3 else int(rng.integers(0, 12)) for i, p in enumerate(pts)]
-    before = {p: dict(rm.points[p]["mObservations"]) for p in pts}
+    slots = [min(rm.points[p].obs) if i % 3 else int(rng.integers(0, 12)) for i, p in enumerate(pts)]
+    before = {p: dict(rm.points[p].obs) for p in pts}
     g = erase_both(st, rm, pts, slots, True, "first batch")
     assert g.counts.n_set_bad > 0 and g.counts.n_records > g.counts.n_found > 0
     named = [(p, s) for p, s, c in zip(pts, slots, g.status) if c != 0]
@@ -114,12 +116,12 @@ def test_a_log_that_had_grown_and_holds_blanks_and_the_mirror_afterwards(gpu_ctx
     for (p, s), i in zip(again, idx):
         assert rm.add_observation(p, s, i)
     assert len(rm.log) == R0 + len(again)
-    PE.assert_state(st, rm, "added again")
-    live = next((p, s) for p, mp in enumerate(rm.points) for s in mp["mObservations"])
+    assert_state(st, rm, "added again")
+    live = next((p, s) for p, mp in enumerate(rm.points) for s in mp.obs)
     L = gpu_ctx._L
     i32 = lambda v: np.array([v], np.int32).ctypes.data_as(C.POINTER(C.c_int32))
     assert L.dsh_point_store_add_observations_indexed(st._h, 1, i32(live[0]), i32(live[1]), i32(0)) == ARG   # still live: still refused
-    PE.assert_state(st, rm, "after the refused add")
+    assert_state(st, rm, "after the refused add")
     pts2 = [int(p) for p in rng.permutation(len(rm.points))[:50]]
     slots2 = [int(rng.integers(0, 12)) for _ in pts2]
     erase_both(st, rm, pts2, slots2, False, "second batch")
@@ -142,8 +144,8 @@ def test_read_back_of_points_with_more_than_one_wavefront_of_observations(gpu_ct
     for p, (i, kfs) in seen.items():
         assert rm.add_point(ref=min(kfs, default=-1)) == p
         for kf in kfs:
-            assert rm.kfs[kf]["mvpMapPoints"][i] == -1
-            rm.kfs[kf]["mvpMapPoints"][i] = p
+            assert rm.kfs[kf].table[i] == -1
+            rm.kfs[kf].table[i] = p
             pairs.append((p, kf, i))
     for j in np.random.default_rng(17).permutation(len(pairs)):
         rm.add_observation(*pairs[int(j)])
@@ -157,21 +159,21 @@ def test_read_back_of_points_with_more_than_one_wavefront_of_observations(gpu_ct
         assert o.ptr.tolist() == np.concatenate([[0], np.cumsum([want[p] for p in ids])]).tolist(), ids
         assert len(o.slots) == len(o.idx) == o.ptr[-1]
         for i, p in enumerate(ids):
-            assert o.of(i) == rm.observations(p), (ids, p)
+            assert o.of(i) == dict(rm.observations(p)), (ids, p)
     st.close()
 
 
 def test_cull_equals_trackstate_cull_and_erases_the_records(gpu_ctx):
     rm = PE.long_scene(seed=4, K=10, N=160, P=300)
-    rm.points[7]["mnFound"], rm.points[7]["mnVisible"] = 2, 5          # 0.4f exactly: stays
-    rm.points[8]["mnFound"], rm.points[8]["mnVisible"] = 1, 3
-    rm.points[9]["mbBad"] = True                                       # already bad: action 1, its records stay
+    rm.points[7].found, rm.points[7].visible = 2, 5          # 0.4f exactly: stays
+    rm.points[8].found, rm.points[8].visible = 1, 3
+    rm.points[9].bad = True                                       # already bad: action 1, its records stay
     st, twin = store_from(gpu_ctx, rm), store_from(gpu_ctx, rm)
     rng = np.random.default_rng(8)
     ids = [7, 8, 9] + [int(p) for p in rng.permutation(np.arange(10, 300))[:150]]
     first_kf = [9, 9, 9] + [int(v) for v in rng.integers(5, 10, len(ids) - 3)]      # the three named points are young
     n_obs = st.get_state().n_obs.copy()
-    held = {p: dict(rm.points[p]["mObservations"]) for p in ids}
+    held = {p: dict(rm.points[p].obs) for p in ids}
     g = cull_both(st, rm, ids, first_kf, 10, "cull")
     assert g.action.tolist() == twin.cull(ids, first_kf, 10).tolist()
     assert g.action[0] == 0 and g.action[1] == 2 and g.action[2] == 1 and set(g.action.tolist()) == {0, 1, 2, 3}
@@ -188,33 +190,34 @@ def test_cull_equals_trackstate_cull_and_erases_the_records(gpu_ctx):
     twin.close()
 
 
+class AllRefMap(PE.EraseRefMap, KI.StoreModel, AR.AnchorRefMap, LM.RefMap):
+    """One model object with the four restatements that the mapping thread's calls are checked against."""
+
+
 def _model_stores(ctx, seed, **kw):
-    """A keyframe_insert_ref model with its two stores and the erase restatement of the same state."""
+    """A keyframe_insert_ref scene as a model that every restatement runs on, with its two stores."""
     from defslam_amd import localmap, mappoint
-    m, slot = KI.random_model(seed, **kw)
-    ks, st = mappoint.KeyFrameStore(ctx, 2), localmap.MapPointStore(ctx, points=8, keyframes=2, observations=16)
-    KI.fill_stores(m, ks, st)
-    rm = PE.from_store_model(m)
+    rm, slot = KI.random_model(seed, cls=AllRefMap, **kw)
     rng = np.random.default_rng(seed + 100)
     for mp in rm.points:
-        mp["mnFound"], mp["mnVisible"] = int(rng.integers(1, 8)), int(rng.integers(1, 12))
-    P = len(rm.points)
-    st.set_counters(np.arange(P), [mp["mnVisible"] for mp in rm.points], [mp["mnFound"] for mp in rm.points])
-    return m, slot, ks, st, rm, rng
+        mp.found, mp.visible = int(rng.integers(1, 8)), int(rng.integers(1, 12))
+    ks, st = mappoint.KeyFrameStore(ctx, 2), localmap.MapPointStore(ctx, points=8, keyframes=2, observations=16)
+    rm.fill(st, ks)
+    return slot, ks, st, rm, rng
 
 
 def test_seeded_random_sequence_of_the_three_calls_between_adds_and_new_keyframes(gpu_ctx):
     """5 keyframes of 40 key points, 60 points: eight random batches of the three calls, each followed by add_observations(idx=...) and
     by process_new_keyframe on a random keyframe; every array is compared after every step."""
-    m, slot, ks, st, rm, rng = _model_stores(gpu_ctx, 21, K=4, N=40, P=60, p_bad_point=0.05)
+    slot, ks, st, rm, rng = _model_stores(gpu_ctx, 21, K=4, N=40, P=60, p_bad_point=0.05)
     K, P = len(rm.kfs), len(rm.points)
-    assert K == 5 and P == 60 and all(len(kf["mvpMapPoints"]) == 40 for kf in rm.kfs)
-    PE.assert_state(st, rm, "start")
+    assert K == 5 and P == 60 and all(len(kf.table) == 40 for kf in rm.kfs)
+    assert_state(st, rm, "start")
     for step in range(8):
         ids = [int(p) for p in rng.permutation(P)[:int(rng.integers(1, 25))]]
         kind = step % 3
         if kind == 0:
-            slots = [int(rng.choice(sorted(rm.points[p]["mObservations"]))) if rm.points[p]["mObservations"] and rng.random() < 0.8 else int(rng.integers(0, K))
+            slots = [int(rng.choice(sorted(rm.points[p].obs))) if rm.points[p].obs and rng.random() < 0.8 else int(rng.integers(0, K))
                      for p in ids]
             erase_both(st, rm, ids, slots, bool(rng.integers(0, 2)), f"step {step} erase")
         elif kind == 1:
@@ -224,23 +227,19 @@ def test_seeded_random_sequence_of_the_three_calls_between_adds_and_new_keyframe
         new = []
         for p in rng.permutation(P)[:10]:
             p, s = int(p), int(rng.integers(0, K))
-            if s not in rm.points[p]["mObservations"]:
+            if s not in rm.points[p].obs:
                 new.append((p, s, int(rng.integers(0, 40))))
         if new:
             st.add_observations([a for a, _, _ in new], [b for _, b, _ in new], idx=[c for _, _, c in new])
             for a, b, c in new:
                 assert rm.add_observation(a, b, c)
-            PE.assert_state(st, rm, f"step {step} add")
+            assert_state(st, rm, f"step {step} add")
         s = int(rng.integers(0, K))
-        PE.into_store_model(rm, m)
         g = st.process_new_keyframe(ks, s)
-        action, added, _ = m.process_new_keyframe(s)
+        action, added, _ = rm.process_new_keyframe(s)
         assert g.action.tolist() == action and g.added.tolist() == added, f"step {step} new keyframe"
-        for i, a in enumerate(action):
-            if a == KI.ADDED:
-                assert rm.add_observation(rm.kfs[s]["mvpMapPoints"][i], s, i)
-        PE.assert_state(st, rm, f"step {step} new keyframe")
-    assert any(mp["mbBad"] for mp in rm.points) and any(not mp["mbBad"] and mp["mObservations"] for mp in rm.points)
+        assert_state(st, rm, f"step {step} new keyframe")
+    assert any(mp.bad for mp in rm.points) and any(not mp.bad and mp.obs for mp in rm.points)
     st.close()
     ks.close()
 
@@ -248,44 +247,39 @@ def test_seeded_random_sequence_of_the_three_calls_between_adds_and_new_keyframe
 def test_downstream_calls_after_a_cull_and_a_drop_batch_equal_their_restatements(gpu_ctx):
     """The drift this closes: after MapPointCulling and the drops of one fit, the local map, the anchor lists and ProcessNewKeyFrame of
     the store equal local_map_ref, anchor_pairs_ref and keyframe_insert_ref run on the restated state."""
-    m, slot, ks, st, rm, rng = _model_stores(gpu_ctx, 33, K=6, N=40, P=80, p_obs=0.8, p_bad_point=0.05)
+    slot, ks, st, rm, rng = _model_stores(gpu_ctx, 33, K=6, N=40, P=80, p_obs=0.8, p_bad_point=0.05)
     P = len(rm.points)
     for p, mp in enumerate(rm.points):                                # every point has a reference keyframe it observes, where it has any
-        if mp["mObservations"]:
-            mp["mpRefKF"] = sorted(mp["mObservations"])[p % len(mp["mObservations"])]
-    st.set_reference_keyframes(np.arange(P), [mp["mpRefKF"] for mp in rm.points])
+        if mp.obs:
+            mp.ref = sorted(mp.obs)[p % len(mp.obs)]
+    st.set_reference_keyframes(np.arange(P), [mp.ref for mp in rm.points])
     ids = [int(p) for p in rng.permutation(P)[:40]]
     g = cull_both(st, rm, ids, [int(v) for v in rng.integers(0, 6, len(ids))], 6, "cull")
     assert g.counts.n_set_bad > 0 and g.counts.n_records > 0
     KF2 = 2                                                            # the drops of one fit: distinct points that observe KF2
-    dropped = [p for p, mp in enumerate(rm.points) if KF2 in mp["mObservations"]][::2]
+    dropped = [p for p, mp in enumerate(rm.points) if KF2 in mp.obs][::2]
     g = erase_both(st, rm, dropped, [KF2] * len(dropped), True, "drop")
     assert g.counts.n_found == len(dropped) > 3 and g.counts.n_ref_moved > 0
     # Tracking::UpdateLocalMap
-    frame_points = rm.kfs[slot]["mvpMapPoints"]
-    lm = PE.to_local_map(rm, bad_kf=[s for s, k in enumerate(m.kfs) if k.bad])
-    want = lm.update_local_map(frame_points)
+    frame_points = rm.kfs[slot].table
+    want = rm.update_local_map(frame_points)
     got = st.update_local_map(frame_points)
     assert got.frame_bad.tolist() == want["frame_bad"].tolist() and got.local_kf.tolist() == want["local_kf"].tolist()
     assert got.votes.tolist() == want["votes"].tolist() and got.ref_kf == want["ref_kf"]
     assert st.local_points(got.n_local_points).tolist() == want["local_points"].tolist()
     # SchwarpDatabase::add
     for s in (slot, KF2):
-        AR.assert_equal(st.keyframe_anchors(s, 1), PE.to_anchor_map(rm).keyframe_anchors(s, 1))
+        AR.assert_equal(st.keyframe_anchors(s, 1), rm.keyframe_anchors(s, 1))
     # LocalMapping::ProcessNewKeyFrame
-    PE.into_store_model(rm, m)
     for s in (slot, KF2):
         g = st.process_new_keyframe(ks, s)
-        action, added, _ = m.process_new_keyframe(s)
+        action, added, _ = rm.process_new_keyframe(s)
         assert g.action.tolist() == action and g.added.tolist() == added
-        for i, a in enumerate(action):
-            if a == KI.ADDED:
-                assert rm.add_observation(rm.kfs[s]["mvpMapPoints"][i], s, i)
-    w = m.points()
+    w = rm.point_arrays()
     gp = st.get_points()
     for k in ("normal", "max_distance", "desc"):
         assert getattr(gp, k).tobytes() == w[k].tobytes(), k
-    PE.assert_state(st, rm, "after the new keyframes")
+    assert_state(st, rm, "after the new keyframes")
     st.close()
     ks.close()
 
@@ -304,13 +298,11 @@ def test_state_refusal_while_an_unindexed_live_record_exists(gpu_ctx):
     assert L.dsh_point_store_set_bad(st._h, 6, ip(p), C.byref(cc)) == STATE and "dsh_point_store_set_bad" in msg()
     assert L.dsh_point_store_cull(st._h, 6, ip(p), ip(s), 9, act.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(cc)) == STATE
     assert [getattr(cc, n) for n in PE.COUNT_NAMES] == [7] * 5
-    rm.points[5]["mObservations"][2] = -1                              # the read-backs work and report -1
-    rm.points[5]["nObs"] += 1
-    PE.assert_state(st, rm, "nothing changed")
+    assert rm.add_observation(5, 2)                                    # the read-backs work and report -1
+    assert_state(st, rm, "nothing changed")
     assert st.observations([5]).of(0) == {0: 6, 1: 6, 2: -1}
     st.erase_observations([5], [2])                                    # the old erase takes it out of the count
-    del rm.points[5]["mObservations"][2]
-    rm.points[5]["nObs"] -= 1
+    assert rm.erase_observation(5, 2)
     erase_both(st, rm, pts, slots, True, "after the unindexed record left")
     st.close()
 
@@ -324,7 +316,7 @@ def test_empty_batches_and_a_capacity_that_is_too_small(gpu_ctx):
                  lambda c: L.dsh_point_store_cull(st._h, 0, None, None, 3, None, c)):
         cc = _lib.PointEraseCountsC(7, 7, 7, 7, 7)
         assert call(C.byref(cc)) == OK and [getattr(cc, n) for n in PE.COUNT_NAMES] == [0] * 5
-    PE.assert_state(st, rm, "empty batches")
+    assert_state(st, rm, "empty batches")
     ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
     ids, ptr, sl, ix, tot = np.arange(6, dtype=np.int32), np.full(7, -7, np.int32), np.full(16, -7, np.int32), np.full(16, -7, np.int32), np.zeros(1, np.int32)
     assert L.dsh_point_store_get_observations(st._h, 6, ip(ids), ip(ptr), 14, ip(sl), ip(ix), ip(tot)) == ARG
@@ -336,7 +328,7 @@ def test_empty_batches_and_a_capacity_that_is_too_small(gpu_ctx):
     assert L.dsh_point_store_get_observations(st._h, 0, None, ip(ptr), 0, None, None, ip(tot)) == OK and tot[0] == 0 and ptr[0] == 0
     tab = np.full(8, -7, np.int32)
     assert L.dsh_point_store_get_keyframe_table(st._h, 1, 7, ip(tab)) == ARG and (tab == -7).all()
-    assert L.dsh_point_store_get_keyframe_table(st._h, 1, 8, ip(tab)) == OK and tab.tolist() == rm.kfs[1]["mvpMapPoints"]
+    assert L.dsh_point_store_get_keyframe_table(st._h, 1, 8, ip(tab)) == OK and tab.tolist() == rm.kfs[1].table
     assert L.dsh_point_store_get_keyframe_table(st._h, 3, 8, ip(tab)) == ARG
     # refusals that need a stored point: a slot outside the store, a repeated point; nothing changes
     cc = _lib.PointEraseCountsC(7, 7, 7, 7, 7)
@@ -346,5 +338,5 @@ def test_empty_batches_and_a_capacity_that_is_too_small(gpu_ctx):
     p = np.array([2, 4, 2], np.int32)
     assert L.dsh_point_store_set_bad(st._h, 3, ip(p), C.byref(cc)) == ARG and "point id 2 repeated in the batch" in L.dsh_last_error(gpu_ctx._h).decode()
     assert [getattr(cc, n) for n in PE.COUNT_NAMES] == [7] * 5
-    PE.assert_state(st, rm, "after the refusals")
+    assert_state(st, rm, "after the refusals")
     st.close()

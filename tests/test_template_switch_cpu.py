@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 
 import template_switch_ref as S
-import track_close_ref as T
 
 OK, ARG, STATE, NODEV = 0, 1, 3, 4
 
@@ -115,12 +114,12 @@ SF = np.array([1.0, 1.2, 1.44], np.float32)
 def hand_case(table, kp, bad=()):
     """One keyframe with the given table over len(set(table) - {-1}) points at (0, 0, 1); the keyframe store's side: descriptor row i is
     all i, octave i % 3, camera centre at the origin."""
-    rm = T.TrackRefMap()
+    rm = S.TemplateRefMap()
     for p in range(max(table) + 1 if table else 0):
         rm.add_point(xyz=(0.0, 0.0, 1.0), desc=np.full(32, 200 + p, np.uint8), bad=p in bad)
     rm.add_keyframe(table)
     for p in sorted(set(table) - {-1}):
-        rm.add_observation(p, 0)
+        assert rm.add_observation(p, 0)
     n = len(table)
     kfs = [S.RefKfData([0, 0, 0], np.repeat(np.arange(n, dtype=np.uint8)[:, None], 32, 1), np.arange(n) % 3, SF)]
     return rm, kfs, np.asarray(kp, np.float32).reshape(n, 2)
@@ -134,7 +133,7 @@ def no_facet(pts):
 def run_hand(rm, kfs, kp, Twc=np.eye(4, dtype=np.float32), embed=no_facet, rest=np.zeros((0, 3))):
     n = kp.shape[0]
     surf = np.stack([0.01 * np.arange(n), np.zeros(n), np.ones(n)], 1).astype(np.float32)
-    return S.switch_template(rm, kfs, 0, HAND_ROWS, HAND_COLS, kp, surf, Twc, embed, rest), surf
+    return rm.switch_template(kfs, 0, HAND_ROWS, HAND_COLS, kp, surf, Twc, embed, rest), surf
 
 
 def test_hand_built_keyframe_with_every_case():
@@ -144,7 +143,7 @@ def test_hand_built_keyframe_with_every_case():
     table = [0, 1, 2, -1, -1, -1, 0]
     kp = [[10.2, 5.7], [10.9, 5.1], [30.0, 12.0], [30.5, 12.5], [11.0, 6.0], [20.0, 20.0], [5.0, 5.0]]
     rm, kfs, kp = hand_case(table, kp, bad=(2,))
-    n_cand, cand = S.need_new_template(rm, 0, HAND_ROWS, HAND_COLS, kp)
+    n_cand, cand = rm.need_new_template(0, HAND_ROWS, HAND_COLS, kp)
     assert n_cand == 2 and cand.tolist() == [False, False, False, True, False, True, False]
     (c, new_idx, _), surf = run_hand(rm, kfs, kp)
     assert c == dict(n_new=2, first_id=3, n_moved=3, n_masked=1, n_embedded=0, n_points=5)
@@ -157,20 +156,21 @@ def test_hand_built_keyframe_with_every_case():
         d = np.float32(np.sqrt(np.float64(surf[i][0]) ** 2 + 1.0))                  # one observation from the origin: normal = xyz / |xyz|
         assert pt.max_distance == np.float32(d * SF[i % 3])
         assert np.allclose(pt.normal, surf[i] / d, rtol=0, atol=1e-7)
-    assert rm.visible[3:] == [1, 1] and rm.found[3:] == [1, 1] and rm.n_obs == [1, 1, 1, 1, 1]
-    assert S.need_new_template(rm, 0, HAND_ROWS, HAND_COLS, kp)[0] == 0             # the new points are held now
+    v, f, o, _ = rm.track_state()
+    assert v[3:].tolist() == [1, 1] and f[3:].tolist() == [1, 1] and o.tolist() == [1, 1, 1, 1, 1]
+    assert rm.need_new_template(0, HAND_ROWS, HAND_COLS, kp)[0] == 0             # the new points are held now
 
 
 def test_no_held_point_every_empty_key_point_is_new_and_no_empty_key_point_creates_none():
     rm, kfs, kp = hand_case([-1, -1, -1], [[3, 3], [3.5, 3.5], [30, 20]])
-    assert S.need_new_template(rm, 0, HAND_ROWS, HAND_COLS, kp)[0] == 3
+    assert rm.need_new_template(0, HAND_ROWS, HAND_COLS, kp)[0] == 3
     (c, new_idx, _), _ = run_hand(rm, kfs, kp)
     assert c == dict(n_new=3, first_id=0, n_moved=0, n_masked=0, n_embedded=0, n_points=3) and new_idx.tolist() == [0, 1, 2]
     rm, kfs, kp = hand_case([0, 1, 2], [[3, 3], [3.5, 3.5], [30, 20]])
     (c, new_idx, _), _ = run_hand(rm, kfs, kp)
     assert c == dict(n_new=0, first_id=3, n_moved=3, n_masked=0, n_embedded=0, n_points=3) and new_idx.shape == (0,)
     rm, kfs, kp = hand_case([0, 0], [[3, 3], [8, 8]], bad=(0,))                     # only a held bad point: no mask at all, nothing moves
-    assert S.need_new_template(rm, 0, HAND_ROWS, HAND_COLS, kp)[0] == 0
+    assert rm.need_new_template(0, HAND_ROWS, HAND_COLS, kp)[0] == 0
     (c, _, _), _ = run_hand(rm, kfs, kp)
     assert c["n_moved"] == 0 and c["n_new"] == 0
 
@@ -206,15 +206,15 @@ def test_generated_scenes_hold_every_case(host_ctx, name):
     from defslam_amd import synth
     sc, (xs, ys) = make_scene(name)
     seed = GPU_SCENES[name][0]
-    rm = T.scene_to_ref(sc)
+    rm = S.scene_to_ref(sc)
     r = sc["ref_slot"]
     table = sc["tables"][r]
     assert sum(1 for p in table if p >= 0 and sc["bad"][p]) == 1                    # one held bad point
-    n_cand, cand = S.need_new_template(rm, r, sc["rows"], sc["cols"], sc["kp"])
+    n_cand, cand = rm.need_new_template(r, sc["rows"], sc["cols"], sc["kp"])
     nodes, _ = S.surface_vertices(sc["bbs"], lambda u, v: synth.switch_depth(u, v, seed), sc["Twc"], xs, ys)
     host_ctx.template_build(nodes, synth.regular_triangulation(xs, ys))
     P0 = len(rm.points)
-    c, new_idx, _ = S.switch_template(rm, S.scene_kf_data(sc), r, sc["rows"], sc["cols"], sc["kp"], sc["surface_pts"], sc["Twc"],
+    c, new_idx, _ = rm.switch_template(S.scene_kf_data(sc), r, sc["rows"], sc["cols"], sc["kp"], sc["surface_pts"], sc["Twc"],
                                       host_ctx.template_embed, nodes)
     assert c["n_new"] == n_cand >= 10 and c["n_masked"] >= 10 and c["n_moved"] >= 10 and new_idx.tolist() == np.nonzero(cand)[0].tolist()
     good = [p for p, pt in enumerate(rm.points) if not pt.bad]

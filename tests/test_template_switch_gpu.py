@@ -41,11 +41,11 @@ def build_template(ctx, sc, xs, ys):
 def check_points(store, rm):
     """get_points and get_embedding of ALL points against the mirror, bytes."""
     g = store.get_points()
-    x, n, md, d, b = S.point_arrays(rm)
-    assert g.xyz.tobytes() == x.tobytes() and g.normal.tobytes() == n.tobytes() and g.max_distance.tobytes() == md.tobytes()
-    assert g.desc.tobytes() == d.tobytes() and g.bad.tolist() == b.tolist()
+    w = rm.point_arrays()
+    assert g.xyz.tobytes() == w["xyz"].tobytes() and g.normal.tobytes() == w["normal"].tobytes() and g.max_distance.tobytes() == w["max_distance"].tobytes()
+    assert g.desc.tobytes() == w["desc"].tobytes() and g.bad.tolist() == w["bad"].tolist()
     nodes, bary = store.get_embedding()
-    rn, rb = S.embedding_arrays(rm)
+    rn, rb = rm.embedding_arrays()
     np.testing.assert_array_equal(nodes, rn)
     assert bary.tobytes() == rb.tobytes()
     return g, nodes, bary
@@ -55,7 +55,7 @@ def switch_both(ctx, both, ks, sc, nodes):
     from defslam_amd import localmap
     kf = localmap.KeyFramePoints(sc["rows"], sc["cols"], sc["kp"])
     g = both.st.switch_template(ks, sc["ref_slot"], kf, sc["surface_pts"], sc["Twc"])
-    c, new_idx, pre = S.switch_template(both.rm, S.scene_kf_data(sc), sc["ref_slot"], sc["rows"], sc["cols"], sc["kp"], sc["surface_pts"], sc["Twc"],
+    c, new_idx, pre = both.rm.switch_template(S.scene_kf_data(sc), sc["ref_slot"], sc["rows"], sc["cols"], sc["kp"], sc["surface_pts"], sc["Twc"],
                                         ctx.template_embed, nodes)
     assert {k: getattr(g, k) for k in S.COUNT_NAMES} == c
     np.testing.assert_array_equal(g.new_idx, new_idx)
@@ -67,12 +67,12 @@ def test_switch_equals_the_restatement_and_the_store_tracks_on(ctx, name):
     from defslam_amd import localmap, mappoint
     sc, (xs, ys) = make_scene(name)
     caps = dict(points=2, keyframes=1, observations=2) if name == "grow" else dict(points=64, keyframes=4, observations=256)
-    both = both_from_scene(ctx, sc, **caps)                                         # "grow": every array grows inside the switch
+    both = both_from_scene(ctx, sc, S.scene_to_ref, **caps)                                         # "grow": every array grows inside the switch
     ks = kf_store_from_scene(ctx, sc)
     kf = localmap.KeyFramePoints(sc["rows"], sc["cols"], sc["kp"])
     r = sc["ref_slot"]
     n_cand, cand = both.st.need_new_template(r, kf)
-    rn, rc = S.need_new_template(both.rm, r, sc["rows"], sc["cols"], sc["kp"])
+    rn, rc = both.rm.need_new_template(r, sc["rows"], sc["cols"], sc["kp"])
     assert n_cand == rn and cand.tolist() == rc.tolist()
     check_points(both.st, both.rm)                                                  # the read-backs before: the scene's own facets
     nodes = build_template(ctx, sc, xs, ys)
@@ -99,7 +99,7 @@ def test_switch_equals_the_restatement_and_the_store_tracks_on(ctx, name):
     assert u.desc.tobytes() == pts.desc[new].tobytes() == sc["kf_desc"][r][g.new_idx].tobytes()
     # the new points are held now
     n2, cand2 = both.st.need_new_template(r, kf)
-    assert n2 == 0 and not cand2.any() and S.need_new_template(both.rm, r, sc["rows"], sc["cols"], sc["kp"])[0] == 0
+    assert n2 == 0 and not cand2.any() and both.rm.need_new_template(r, sc["rows"], sc["cols"], sc["kp"])[0] == 0
     # a tracked frame on the switched store: update, search, close with the new template's nodes slightly moved
     fp = sc["frame_points"].copy()
     fp[np.nonzero(fp < 0)[0][:5]] = new[:5]                                         # the frame holds five of the new points
@@ -131,7 +131,7 @@ def test_switch_equals_the_restatement_and_the_store_tracks_on(ctx, name):
     # a second switch on the same keyframe: the key point whose entry was cleared is empty again (new, unless a point of the first
     # switch masks it now), every array consistent
     n3, _ = both.st.need_new_template(r, kf)
-    assert n3 == S.need_new_template(both.rm, r, sc["rows"], sc["cols"], sc["kp"])[0] <= 1
+    assert n3 == both.rm.need_new_template(r, sc["rows"], sc["cols"], sc["kp"])[0] <= 1
     g2, _ = switch_both(ctx, both, ks, sc, nodes)
     assert g2.n_new == n3 and g2.first_id == g.n_points and g2.new_idx.tolist() == [int(g.new_idx[0])][:n3]
     check_points(both.st, both.rm)
@@ -151,7 +151,7 @@ def test_a_point_held_by_two_key_points_keeps_the_later_position(ctx):
     held = np.nonzero((t >= 0) & ~sc["bad"][np.maximum(t, 0)])[0]
     empty = np.nonzero(t < 0)[0]
     sc["tables"][r, empty[-1]] = t[held[0]]                                         # the last empty key point holds the first held point again
-    both = both_from_scene(ctx, sc)
+    both = both_from_scene(ctx, sc, S.scene_to_ref)
     ks = kf_store_from_scene(ctx, sc, 8)
     nodes = build_template(ctx, sc, xs, ys)
     g, pre = switch_both(ctx, both, ks, sc, nodes)
@@ -166,7 +166,7 @@ def test_refused_switch_leaves_the_store_as_it_was(ctx):
     built from facets) store nothing: get_points / get_embedding / the state are byte-identical to before."""
     from defslam_amd import localmap, sft
     sc, (xs, ys) = make_scene("last")
-    both = both_from_scene(ctx, sc)
+    both = both_from_scene(ctx, sc, S.scene_to_ref)
     ks = kf_store_from_scene(ctx, sc, 8)
     build_template(ctx, sc, xs, ys)
     r = sc["ref_slot"]

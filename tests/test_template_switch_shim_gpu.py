@@ -2,22 +2,20 @@
 and UpdateTemplateHIP leave the stand-in objects exactly as DefLocalMapping::needNewTemplate / updateTemplate over a second copy of them
 do, and both equal the sequential restatement (tests/template_switch_ref.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import template_switch_ref as S
-import track_close_ref as T
-from conftest import ROOT
+import shim_run
 from test_template_switch_cpu import make_scene
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 
 
 def test_template_switch_shim_compiles_against_the_c_abi():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    assert os.path.exists(os.path.join(INTEG, "build", "tmplswitch_shim_test"))
+    shim_run.build()
+    assert os.path.exists(shim_run.exe("tmplswitch_shim_test"))
     src = open(os.path.join(INTEG, "template_switch_hip.h")).read()
     assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
     assert "UpdateTemplateHIP" in src and "NeedNewTemplateHIP" in src
@@ -26,14 +24,11 @@ def test_template_switch_shim_compiles_against_the_c_abi():
 @pytest.mark.gpu
 def test_template_switch_shim_device_way_host_way_and_restatement_agree(tmp_path):
     from defslam_amd import nrsfm, sft, synth
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    exe = os.path.join(INTEG, "build", "tmplswitch_shim_test")
+    shim_run.build()
     sc, (xs, ys) = make_scene("grow")
     synth.write_local_map_scene(sc, tmp_path / "map.txt")
     synth.write_template_switch_scene(sc, (xs, ys), tmp_path / "switch.txt")
-    r = subprocess.run(["timeout", "-k", "10", "120", exe, str(tmp_path / "map.txt"), str(tmp_path / "switch.txt"), str(tmp_path / "out.txt"), "0"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("tmplswitch_shim_test", tmp_path / "map.txt", tmp_path / "switch.txt", tmp_path / "out.txt", "0")
     tok = iter(open(tmp_path / "out.txt").read().split())
     N = sc["kp"].shape[0]
 
@@ -58,20 +53,20 @@ def test_template_switch_shim_device_way_host_way_and_restatement_agree(tmp_path
     ctx = sft.Context(0)
     nodes = nrsfm.surface_vertices(ctx, nrsfm.Bbs(*sc["bbs"]), sc["depth_ctrl"], sc["Twc"], xs, ys)
     ctx.template_build(nodes, synth.regular_triangulation(xs, ys))
-    rm = T.scene_to_ref(sc, embed=False)
+    rm = S.scene_to_ref(sc, embed=False)
     slot = sc["ref_slot"]
-    need, _ = S.need_new_template(rm, slot, sc["rows"], sc["cols"], sc["kp"])
+    need, _ = rm.need_new_template(slot, sc["rows"], sc["cols"], sc["kp"])
     kfs = S.scene_kf_data(sc)
-    c, new_idx, _ = S.switch_template(rm, kfs, slot, sc["rows"], sc["cols"], sc["kp"], sc["surface_pts"], sc["Twc"], ctx.template_embed, nodes)
+    c, new_idx, _ = rm.switch_template(kfs, slot, sc["rows"], sc["cols"], sc["kp"], sc["surface_pts"], sc["Twc"], ctx.template_embed, nodes)
     ctx.close()
     head, rows, table = dev
     assert head == [need] + [c[k] for k in S.COUNT_NAMES] and head[1] >= 10 and head[4] >= 10 and head[5] > 0
     assert table == rm.kfs[slot].table
-    x, nrm, md, desc, bad = S.point_arrays(rm)
-    rn, rb = S.embedding_arrays(rm)
+    x, nrm, md, desc, bad = (rm.point_arrays()[k] for k in ("xyz", "normal", "max_distance", "desc", "bad"))
+    rn, rb = rm.embedding_arrays()
     assert np.array([r[0][:3] for r in rows], np.float32).tobytes() == x.tobytes()
     assert [r[1] for r in rows] == desc.tolist() and [bool(r[2][1]) for r in rows] == bad.tolist()
-    assert [r[2][0] for r in rows] == rm.n_obs
+    assert [r[2][0] for r in rows] == rm.state()["n_obs"].tolist()
     live = ~bad                                                      # a bad point keeps what it had: neither way touches it
     assert np.array([r[2][3:6] for r in rows], np.int32)[live].tolist() == rn[live].tolist()
     assert np.array([r[3] for r in rows], np.float64)[live].tobytes() == rb[live].tobytes()

@@ -42,10 +42,10 @@ def test_restatement_first_frame_of_the_hand_built_map():
     list is still empty."""
     rm = T.hand_map()
     assert first_hand_frame(rm) == T.HAND_COUNTS
-    v, f, o, x = rm.state()
+    v, f, o, x = rm.track_state()
     assert v.tolist() == T.HAND_VISIBLE and f.tolist() == T.HAND_FOUND and o.tolist() == T.HAND_N_OBS
     assert x.tobytes() == T.HAND_XYZ_AFTER.tobytes()
-    assert rm.points[3].bad and rm.n_obs[3] == 2                        # the stale nObs
+    assert rm.points[3].bad and rm.points[3].n_obs == 2                        # the stale nObs
 
 
 def test_restatement_only_tracking_counts_every_inlier():
@@ -64,19 +64,19 @@ def test_restatement_second_frame_counts_against_the_previous_list_and_culls():
     assert c["local_map_points"] == T.HAND_SECOND_LOCAL_MAP_POINTS and c["n_moved"] == 0
     assert rm.left_out == dict(bad=1, no_facet=1, out_of_frustum=1)
     assert rm.frustum_count(T.R.ref_frame(fr), rm.local_points)[0] == T.HAND_SECOND_WRONG_LIST_COUNT
-    assert rm.state()[3].tobytes() == T.HAND_XYZ_AFTER.tobytes()
-    assert rm.visible == [4, 2, 3, 2, 2, 2] and rm.found == [4, 1, 2, 2, 2, 1]
+    assert rm.track_state()[3].tobytes() == T.HAND_XYZ_AFTER.tobytes()
+    assert rm.track_state()[0].tolist() == [4, 2, 3, 2, 2, 2] and rm.track_state()[1].tolist() == [4, 1, 2, 2, 2, 1]
     rm.set_counters(1, 5, 1)
     assert rm.cull(range(6), T.HAND_FIRST_KF, T.HAND_CURRENT_KF).tolist() == T.HAND_ACTIONS
-    assert [p.bad for p in rm.points] == [False, True, False, True, False, False] and rm.n_obs[1] == 1
+    assert [p.bad for p in rm.points] == [False, True, False, True, False, False] and rm.points[1].n_obs == 1
 
 
 def test_restatement_seed_clear_embedding_and_erase():
     rm = T.hand_map(erased=False)
-    assert rm.n_obs[5] == 2
+    assert rm.points[5].n_obs == 2
     rm.erase_observation(5, 0)
     rm.erase_observation(5, 0)                                          # a pair that is not there: no change
-    assert rm.n_obs[5] == 1
+    assert rm.points[5].n_obs == 1
     rm.seed_local_points([0, 4, 5])
     assert rm.local_points == [0, 4, 5] and rm.reference_points == [0, 4, 5]
     fr = T.hand_frame()
@@ -113,17 +113,17 @@ def test_generated_scenes_exercise_every_branch_on_the_restatement(name):
     """A condition on the inputs of the GPU tests, checked on the restatement alone."""
     sc = make_scene(name)
     rm = T.scene_to_ref(sc)
-    found0 = np.array(rm.found)
+    found0 = rm.track_state()[1]
     c = T.run_generated_frame(rm, sc)
     assert all(c[k] > 0 for k in T.COUNT_NAMES if k != "n_moved"), c
     assert c["n_moved"] > 0 and c["matches_inliers"] != c["inliers"]
     assert 0 < c["local_map_points"] < len(rm.reference_points)
     assert all(v > 0 for v in rm.left_out.values()), rm.left_out
-    assert (np.array(rm.found) - found0).max() >= 2                    # held twice, inlier at both key points
+    assert (rm.track_state()[1] - found0).max() >= 2                    # held twice, inlier at both key points
     assert rm.reference_points != rm.local_points                      # the previous list is another one
     fp, out = sc["final_points"], sc["outlier"]
     held = fp[fp >= 0]
-    assert sc["bad"][held].any() and (np.array(rm.n_obs)[held] == 0).any() and (sc["nodes"][held, 0] < 0).any()
+    assert sc["bad"][held].any() and (rm.track_state()[2][held] == 0).any() and (sc["nodes"][held, 0] < 0).any()
     ids, first_kf = T.cull_list(sc)
     assert sorted(set(rm.cull(ids, first_kf, sc["current_kf"]).tolist())) == [0, 1, 2, 3]
 

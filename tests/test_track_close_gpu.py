@@ -18,7 +18,7 @@ def counts_dict(c):
 def check_state(store, rm):
     """get_state of all points against the mirror."""
     g = store.get_state()
-    v, f, o, x = rm.state()
+    v, f, o, x = rm.track_state()
     np.testing.assert_array_equal(g.visible, v)
     np.testing.assert_array_equal(g.found, f)
     np.testing.assert_array_equal(g.n_obs, o)
@@ -71,12 +71,12 @@ class BothT(Both):
         return g
 
 
-def both_from_scene(ctx, sc, **caps):
+def both_from_scene(ctx, sc, scene_to_ref=T.scene_to_ref, **caps):
     st = store_from_scene(ctx, sc, **caps)
     P = sc["xyz"].shape[0]
     st.set_counters(np.arange(P), sc["visible"], sc["found"])
     st.set_embedding(np.arange(P), sc["nodes"], sc["bary"])
-    return BothT(st, T.scene_to_ref(sc))
+    return BothT(st, scene_to_ref(sc))
 
 
 # ---- the hand-built map ----------------------------------------------------------------------------------------------------------------
@@ -85,7 +85,7 @@ def hand_both(ctx):
     from defslam_amd import localmap
     rm = T.hand_map(erased=False)
     st = localmap.MapPointStore(ctx, points=2, keyframes=1, observations=2)        # tiny: every array grows, the new ones too
-    T.LM.fill_store(st, rm)
+    rm.fill(st)
     both = BothT(st, rm)
     for p in range(6):
         if rm.nodes[p] is not None:
@@ -224,7 +224,7 @@ def test_repose_chained_with_the_solver(gpu_ctx):
     rm.set_embedding(P - 1, None)                                                   # one point without a facet, one bad
     rm.set_bad(P - 2)
     st = localmap.MapPointStore(ctx, points=64)
-    T.LM.fill_store(st, rm)
+    rm.fill(st)
     st.set_embedding(np.arange(P - 1), nodes[:P - 1], bary[:P - 1])
     assert st.repose(f.nodes_xyz) == rm.repose(f.nodes_xyz) == P - 2
     g = check_state(st, rm)

@@ -2,20 +2,19 @@
 TrackWithMotionModel's SearchByProjectionHIP sequence and SearchLocalPointsHIP fill mvpMapPoints and the map points' tracking members
 exactly as the sequential restatement (tests/track_search_ref.py) of the reference's calls does."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import track_search_ref as R
-from conftest import ROOT
+import shim_run
 
-INTEG = os.path.join(ROOT, "integration")
+INTEG = shim_run.INTEG
 
 
 def test_tracking_shim_compiles_against_the_c_abi():
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    assert os.path.exists(os.path.join(INTEG, "build", "tracking_shim_test"))
+    shim_run.build()
+    assert os.path.exists(shim_run.exe("tracking_shim_test"))
     src = open(os.path.join(INTEG, "tracking_search_hip.h")).read()
     assert "defslam_hip_debug.h" not in src and "dsh_lab" not in src
 
@@ -28,8 +27,7 @@ def _first_unique(ids):
 @pytest.mark.gpu
 def test_tracking_shim_follows_the_reference_flow(tmp_path):
     from defslam_amd import synth, track
-    subprocess.run(["make", "-C", INTEG], check=True, capture_output=True)
-    exe = os.path.join(INTEG, "build", "tracking_shim_test")
+    shim_run.build()
     rng = np.random.default_rng(5)
     sc = synth.make_track_scene(41, n_kp=1200, n_frame_q=400, n_local_q=300, n_clusters=8)
     tf, fq, lq = sc["frame"], sc["fq"], sc["lq"]
@@ -67,8 +65,7 @@ def test_tracking_shim_follows_the_reference_flow(tmp_path):
         f.write(cam + " ".join(repr(float(v)) for v in np.eye(4, dtype=np.float32).ravel()) + "\n0 0 0\n")
         f.write(f"{len(entries)}\n" + "".join(f"{a} {b} {c}\n" for a, b, c in entries))
         f.write(f"{len(local_ids)}\n" + " ".join(str(int(i)) for i in local_ids) + "\n")
-    r = subprocess.run(["timeout", "-k", "10", "120", exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "0"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = shim_run.run("tracking_shim_test", tmp_path / "in.txt", tmp_path / "out.txt", "0")
     tok = iter(open(tmp_path / "out.txt").read().split())
     n1, th = int(next(tok)), int(next(tok))
     after_motion = np.array([int(next(tok)) for _ in range(N)])

@@ -25,33 +25,20 @@ COUNT_NAMES = ("matches_inliers", "matches_outliers", "to_match_local", "observe
 
 
 class TrackRefMap(LM.RefMap):
-    """RefMap whose points also carry mnVisible, mnFound, nObs and the facet, and which keeps Map::mvpReferenceMapPoints."""
+    """RefMap whose points also carry the facet, and which keeps Map::mvpReferenceMapPoints (mnVisible, mnFound and nObs are the model's)."""
 
     def __init__(self):
         super().__init__()
-        self.visible, self.found, self.n_obs = [], [], []
         self.nodes, self.bary = [], []           # per point None or (n0, n1, n2) ascending / (b1, b2, b3) float64
         self.reference_points = []               # Map::GetReferenceMapPoints()
         self.held_count = {}                     # how many key points of the frame of the last update hold a point that was not bad then
 
     # ---- mutations ----
     def add_point(self, *a, **k):
-        p = super().add_point(*a, **k)
-        self.visible.append(1)                   # MapPoint.cc:38,58: mnVisible(1), mnFound(1), nObs(0)
-        self.found.append(1)
-        self.n_obs.append(0)
+        p = super().add_point(*a, **k)           # MapPoint.cc:38,58: mnVisible(1), mnFound(1), nObs(0)
         self.nodes.append(None)
         self.bary.append(None)
         return p
-
-    def add_observation(self, p, k):
-        super().add_observation(p, k)
-        self.n_obs[p] += 1                       # MapPoint.cc:119 (monocular)
-
-    def erase_observation(self, p, k):
-        if k in self.points[p].obs:              # MapPoint.cc:127-133: only a pair that is there
-            self.n_obs[p] -= 1
-        super().erase_observation(p, k)
 
     def set_bad(self, p):
         """DefMapPoint::setBadFlag as the store sees it: the flag; nObs stays (DefMapPoint.cc:84 clears mObservations, not nObs)."""
@@ -68,7 +55,7 @@ class TrackRefMap(LM.RefMap):
             self.nodes[p], self.bary[p] = None, None
 
     def set_counters(self, p, visible, found):
-        self.visible[p], self.found[p] = int(visible), int(found)
+        self.points[p].visible, self.points[p].found = int(visible), int(found)
 
     def seed_local_points(self, ids):
         self.local_points = [int(p) for p in ids]                     # DefTracking.cc:641
@@ -86,11 +73,11 @@ class TrackRefMap(LM.RefMap):
 
     def search_local_points(self, track_frame, th=3):
         for p, k in self.held_count.items():                          # Tracking.cc:1408-1425: IncreaseVisible per key point
-            self.visible[p] += k
+            self.points[p].visible += k
         r = super().search_local_points(track_frame, th)
         for q, p in enumerate(r["local_ids"]):
             if r["in_view"][q]:
-                self.visible[int(p)] += 1                             # :1456
+                self.points[int(p)].visible += 1                      # :1456
         return r
 
     def repose(self, node_xyz):
@@ -134,9 +121,9 @@ class TrackRefMap(LM.RefMap):
             if p < 0:
                 continue
             if not outlier[i]:
-                self.found[p] += 1                                    # IncreaseFound
+                self.points[p].found += 1                             # IncreaseFound
                 if not only_tracking:
-                    if self.n_obs[p] > 0:                             # Observations()
+                    if self.points[p].n_obs > 0:                      # Observations()
                         c["matches_inliers"] += 1
                         if self.nodes[p] is not None:
                             c["to_match_local"] += 1
@@ -162,7 +149,7 @@ class TrackRefMap(LM.RefMap):
         for i, p in enumerate(ids):
             p = int(p)
             with np.errstate(divide="ignore", invalid="ignore"):
-                ratio = f32(self.found[p]) / f32(self.visible[p])     # MapPoint::GetFoundRatio, MapPoint.cc:254
+                ratio = f32(self.points[p].found) / f32(self.points[p].visible)   # MapPoint::GetFoundRatio, MapPoint.cc:254
             if self.points[p].bad:                                    # :184
                 action[i] = 1
             elif ratio < f32(0.40):                                   # :188
@@ -172,22 +159,31 @@ class TrackRefMap(LM.RefMap):
                 action[i] = 3
         return action
 
-    def state(self):
+    def track_state(self):
         """(visible, found, n_obs, xyz) of every point, as MapPointStore.get_state() returns them."""
         P = len(self.points)
-        return (np.array(self.visible, np.int32), np.array(self.found, np.int32), np.array(self.n_obs, np.int32),
-                np.array([pt.xyz for pt in self.points], np.float32).reshape(P, 3))
+        return (np.array([pt.visible for pt in self.points], np.int32), np.array([pt.found for pt in self.points], np.int32),
+                np.array([pt.n_obs for pt in self.points], np.int32), np.array([pt.xyz for pt in self.points], np.float32).reshape(P, 3))
+
+    def embedding_arrays(self):
+        """(nodes, bary) of every point, as MapPointStore.get_embedding() returns them."""
+        P = len(self.points)
+        nodes, bary = np.full((P, 3), -1, np.int32), np.zeros((P, 3), np.float64)
+        for p in range(P):
+            if self.nodes[p] is not None:
+                nodes[p], bary[p] = self.nodes[p], self.bary[p]
+        return nodes, bary
 
 
-def scene_to_ref(sc, embed=True) -> TrackRefMap:
-    """A synth.make_track_close_scene dict as a TrackRefMap."""
-    rm = TrackRefMap()
+def scene_to_ref(sc, embed=True, cls=TrackRefMap):
+    """A synth.make_track_close_scene dict as a TrackRefMap (or as cls, a class over it)."""
+    rm = cls()
     for p in range(sc["xyz"].shape[0]):
         rm.add_point(sc["xyz"][p], sc["normal"][p], sc["max_distance"][p], sc["desc"][p], sc["bad"][p])
     for k in range(sc["tables"].shape[0]):
         rm.add_keyframe(sc["tables"][k], sc["parents"][k], sc["kf_bad"][k])
     for p, k in zip(sc["obs_point"].tolist(), sc["obs_kf"].tolist()):
-        rm.add_observation(p, k)
+        assert rm.add_observation(p, k)
     for p in range(sc["xyz"].shape[0]):
         rm.set_counters(p, sc["visible"][p], sc["found"][p])
         if embed:
@@ -245,7 +241,7 @@ def hand_map(erased=True) -> TrackRefMap:
     rm.add_keyframe([0, 1, 2, 3], parent=-1)
     rm.add_keyframe([3, 4, 5, -1], parent=0)
     for p, k in ((0, 0), (1, 0), (2, 0), (3, 0), (3, 1), (5, 1), (5, 0)):
-        rm.add_observation(p, k)
+        assert rm.add_observation(p, k)
     if erased:
         rm.erase_observation(5, 0)
     rm.set_embedding(0, FACET_A, (0.5, 0.25, 0.25))

@@ -66,13 +66,16 @@ def fill(ctx, ref, tables, log):
 
 
 def write_map(path, ref, tables, log, min_pairs):
+    """The scene file of integration/standin_store_scene.h without appearance, and the driver's tail: the newest keyframe, no drop."""
+    P, K = ref.shape[0], tables.shape[0]
+    n_obs = np.bincount(log[:, 0], minlength=P)
     with open(path, "w") as f:
-        f.write(f"{ref.shape[0]} {tables.shape[0]}\n")
-        f.write("".join(f"0 {r}\n" for r in ref))
+        f.write(f"store_scene {P} {K} {log.shape[0]} 0\n")
+        f.write("".join(f"0 0 1 0 0 1 1 0 0 {r} {n} 1 1" + " 0" * 32 + "\n" for r, n in zip(ref, n_obs)))
         for t in tables:
-            f.write(f"{t.shape[0]} " + " ".join(map(str, t)) + "\n")
-        f.write(f"{log.shape[0]}\n" + "".join(f"{p} {k} {i}\n" for p, k, i in log))
-        f.write(f"0\n{tables.shape[0] - 1} {min_pairs} -1 -1\n")
+            f.write(f"{t.shape[0]} -1 0 " + " ".join(map(str, t)) + "\n")
+        f.write("".join(f"{p} {k} {i} 1\n" for p, k, i in log))
+        f.write(f"{K - 1} {min_pairs} -1 -1\n")
 
 
 def summarize_trace(path):
@@ -137,7 +140,7 @@ def main():
             lines = open(os.path.join(d, "out.txt")).read().splitlines()
         store = [ln.split(" ", 1)[1] for ln in lines if ln.startswith("store ")]
         host = [ln.split(" ", 1)[1] for ln in lines if ln.startswith("host ")]
-        if store != host or len([ln for ln in store if ln.startswith("anchor")]) != A:
+        if store != host or len([ln for ln in store if ln.startswith("lists anchor")]) != A:
             raise SystemExit("the store route, the host walk and the C call disagree")
         host_us, store_us = map(float, lines[-1].split()[1:])
         res.update(driver_reps=a.driver_reps, host_walk_us=host_us, store_route_us=store_us)
