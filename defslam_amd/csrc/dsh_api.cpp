@@ -646,28 +646,17 @@ int dsh_template_embed_device(dsh_ctx* c, int P, const float* pts, int32_t* face
   if (P == 0) return DSH_OK;
   if (const int rc = dsh_enter(c, "dsh_template_embed_device")) return rc;
   const dsh::TemplateHost& t = c->tmpl;
-  hipStream_t st = c->stream;
-  struct Item { const void* src; size_t bytes; void* dev; };
-  Item in[5] = {{pts, 12 * (size_t)P, nullptr}, {t.xyz0.data(), 24 * (size_t)t.n, nullptr}, {t.facets.data(), 12 * (size_t)t.F, nullptr},
-                {t.nf_ptr.data(), 4 * (size_t)(t.n + 1), nullptr}, {t.nf_idx.data(), 4 * t.nf_idx.size(), nullptr}};
-  for (Item& it : in) {
-    if (c->scratch.take(it.bytes, &it.dev) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_template_embed_device: out of device memory");
-    if (it.bytes && hipMemcpyAsync(it.dev, it.src, it.bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-      return dsh_fail(c, DSH_ERR_HIP, "dsh_template_embed_device: upload failed");
-  }
-  void *d_fid = nullptr, *d_nodes = nullptr, *d_bary = nullptr;
-  if (c->scratch.take(4 * (size_t)P, &d_fid) != hipSuccess || c->scratch.take(12 * (size_t)P, &d_nodes) != hipSuccess ||
-      c->scratch.take(12 * (size_t)P, &d_bary) != hipSuccess)
-    return dsh_fail(c, DSH_ERR_HIP, "dsh_template_embed_device: out of device memory");
-  hipError_t e = reg_embed(P, static_cast<const float*>(in[0].dev), t.n, static_cast<const double*>(in[1].dev), static_cast<const int32_t*>(in[2].dev),
-                           static_cast<const int32_t*>(in[3].dev), static_cast<const int32_t*>(in[4].dev), static_cast<int32_t*>(d_fid),
-                           static_cast<int32_t*>(d_nodes), static_cast<float*>(d_bary), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(facet_id, d_fid, 4 * (size_t)P, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(nodes, d_nodes, 12 * (size_t)P, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(bary, d_bary, 12 * (size_t)P, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, std::string("dsh_template_embed_device: ") + hipGetErrorString(e));
-  return DSH_OK;
+  const size_t Pz = (size_t)P;
+  UpBlock up;   // the points and the template's nodes, facets and node-to-facet lists
+  const size_t o_pts = up.copy_of(pts, 12 * Pz), o_xyz = up.copy_of(t.xyz0.data(), 24 * (size_t)t.n), o_fac = up.copy_of(t.facets.data(), 12 * (size_t)t.F),
+               o_ptr = up.copy_of(t.nf_ptr.data(), 4 * (size_t)(t.n + 1)), o_idx = up.copy_of(t.nf_idx.data(), 4 * t.nf_idx.size());
+  DownBlock down;
+  const size_t d_fid = down.copy_to(facet_id, 4 * Pz), d_nodes = down.copy_to(nodes, 12 * Pz), d_bary = down.copy_to(bary, 12 * Pz);
+  if (const int rc = up.copy(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  HIPCHK(c, reg_embed(P, up.dev<float>(o_pts), t.n, up.dev<double>(o_xyz), up.dev<int32_t>(o_fac), up.dev<int32_t>(o_ptr), up.dev<int32_t>(o_idx),
+                      down.dev<int32_t>(d_fid), down.dev<int32_t>(d_nodes), down.dev<float>(d_bary), c->stream));
+  return down.receive(c);
 }
 
 int dsh_sft_batch_upload(dsh_ctx* c, int B, const dsh_sft_frame* frames) { return dsh_sft_upload(c, B, frames, SftUploadMode::batch); }

@@ -1,12 +1,13 @@
 // Internal definition of the opaque dsh_ctx (shared by the translation units of libdefslam_hip.so) and the host-side plumbing every
 // C ABI module uses: error reporting (dsh_fail, HIPCHK), the device gate (dsh_enter), scratch slices (DevBuf), block layout (Arena),
-// page-locked host buffers (HostBuf), the one-copy blocks of a call (UpBlock, DownBlock) and the life cycle of the device-resident
-// stores (dsh_store, DSH_STORE_ENTER, dsh_store_grow).
+// page-locked host buffers (HostBuf), the one-copy blocks of a call (UpBlock, DownBlock), the life cycle of the device-resident
+// stores (dsh_store, DSH_STORE_ENTER, dsh_store_grow) and what the mapping calls share across files (namespace dsh).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -89,7 +90,7 @@ struct dsh_store;
 
 struct dsh_ctx_base {
   dsh_scratch scratch;
-  HostBuf pin_in, pin_out;   // one-copy-in / one-copy-out blocks (Schwarp fits, tracking searches, map point update)
+  HostBuf pin_in, pin_out;   // host side of the one-copy-in / one-copy-out blocks (UpBlock / DownBlock): they grow to the largest call's traffic and never shrink
   int device = 0;
   bool host_only = false;   // device == -1: template + packer only (CPU tests of the host logic)
   hipStream_t stream = nullptr;
@@ -152,7 +153,7 @@ inline int dsh_fail(dsh_ctx_base* c, int code, const std::string& m) {
   return code;
 }
 
-// A failed HIP call: drain the context's stream first (copies from local host buffers may still be in flight), then DSH_ERR_HIP.
+// A failed HIP call: drain the context's stream first (the append calls of the stores still copy from local host buffers), then DSH_ERR_HIP.
 inline int dsh_fail_hip(dsh_ctx_base* c, hipError_t e, const char* call) {
   if (c && !c->host_only && c->stream) (void)hipStreamSynchronize(c->stream);
   return dsh_fail(c, DSH_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
@@ -185,6 +186,8 @@ hipError_t dsh_scratch_array(dsh_ctx_base* c, T** p, size_t n) { return c->scrat
 
 // A block of a call that moves in one copy: slices laid out as by Arena, the host side in a page-locked buffer of the context, the device
 // side in one scratch slice.  An empty block enqueues no copy; a take(0) slice is legal and never dereferenced.
+// pin_in and pin_out are one buffer each, and HostBuf::ensure frees the old buffer when it grows: between two synchronisations of the stream
+// a call stages at most one UpBlock and fetches at most one DownBlock, and reads nothing of a block's host side once the next one is staged.
 struct CopyBlock : Arena {   // size: what the copy moves
   char *h = nullptr, *d = nullptr;
   // a slice without padding: the last one of a block whose copy ends with it
@@ -195,6 +198,15 @@ struct CopyBlock : Arena {   // size: what the copy moves
   }
   template <class T> T* host(size_t off) const { return reinterpret_cast<T*>(h + off); }
   template <class T> T* dev(size_t off) const { return reinterpret_cast<T*>(d + off); }
+  // slices that are plain copies of arrays of the caller (UpBlock::copy_of, DownBlock::copy_to): the block moves them itself; a null array
+  // or one without bytes is an empty slice
+  struct Bound { size_t off, bytes; void* p; };
+  std::vector<Bound> bound;
+  size_t bind(void* p, size_t bytes) {
+    const size_t off = take(p ? bytes : 0);
+    if (p && bytes) bound.push_back({off, bytes, p});
+    return off;
+  }
 };
 
 // Up: filled in pin_in after stage(), copied by send().  The two are apart because some calls stage here and copy into a store's own
@@ -205,7 +217,15 @@ struct UpBlock : CopyBlock {
   int stage(dsh_ctx_base* c, size_t tail = 0) {
     HIPCHK(c, c->pin_in.ensure(size + tail, true));
     h = c->pin_in.p;
+    for (const Bound& b : bound) std::memcpy(h + b.off, b.p, b.bytes);
     return DSH_OK;
+  }
+  // a slice that stage() fills from src
+  size_t copy_of(const void* src, size_t bytes) { return bind(const_cast<void*>(src), bytes); }
+  // stage and send in one: for a block that holds bound slices alone
+  int copy(dsh_ctx_base* c) {
+    if (const int rc = stage(c)) return rc;
+    return send(c);
   }
   // the device side ahead of send(): for a block whose records hold device addresses of its own slices
   int place(dsh_ctx_base* c) {
@@ -238,6 +258,18 @@ struct DownBlock : CopyBlock {
     if (size > 0) HIPCHK(c, hipMemcpyAsync(h, d, size, hipMemcpyDeviceToHost, c->stream));
     return DSH_OK;
   }
+  // a slice that hand_out() copies to dst after the caller's hipStreamSynchronize (null: an optional output nobody asked for)
+  size_t copy_to(void* dst, size_t bytes) { return bind(dst, bytes); }
+  void hand_out() const {
+    for (const Bound& b : bound) std::memcpy(b.p, h + b.off, b.bytes);
+  }
+  // the end of a call: fetch, wait for the stream, hand out
+  int receive(dsh_ctx_base* c) {
+    if (const int rc = fetch(c)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hand_out();
+    return DSH_OK;
+  }
 };
 
 // The first checks of every entry point on a device-resident store `db`: a store that is alive and attached.  Leaves its context in c
@@ -253,4 +285,40 @@ inline const char* dsh_keypoint_count_error(long long N) { return N < 0 || N > (
 namespace dsh {
 // Dense bending matrix of a B-spline (dsh_sfn.cpp; the warp initialisation of dsh_schwarp.cpp uses it too).
 void bbs_bending_dense(const dsh_bbs* b, double lambda, double* Bm);
+
+// Host logic of the mapping calls that writes straight into slices of an upload block; plain functions over host pointers.
+// dsh_nrsfm.cpp: owner[r] = the point of record r, soa[18][R] = the transposed DiffProp records.
+void normals_fill_records(int P, const int32_t* rec_ptr, const dsh_diffprop* recs, int32_t* owner, float* soa);
+// dsh_sfn.cpp: the constant rows of the stacked system, tail[(N + 1) * N] = bending block and row of ones, b[2n + N + 1] = right-hand
+// side (zero except N * mean_depth in the last row), ones[N].
+void sfn_fill_constant_rows(const dsh_bbs* bbs, int n, double bending_weight, double mean_depth, double* tail, double* b, double* ones);
+// dsh_register.cpp: which points of scaleMinMedian are candidates and where their draws start in the stream u[nu]
+// (GroundTruthCalculator.cc:64-84).  cand / off: room for n entries, or both null to count.  Returns the number of candidates, -1 if the
+// stream is too short; *consumed: the draws the reference makes.
+int smm_walk_candidates(int n, const double* u, int64_t nu, int32_t* cand, int64_t* off, int64_t* consumed);
+
+// The normals stage of dsh_normals_estimate and dsh_normals_estimate_db (dsh_nrsfm.cpp): work space, clears, nrsfm_launch_normals, one
+// block down, the synchronise, the caller's arrays.  in: device arrays; out: host arrays, an optional one that is null gets no slice.
+struct NormalsIn {
+  const int32_t *rec_ptr, *owner;
+  const float* soa;
+  const uint8_t* is_ref;
+  const float* first_n;
+  const uint8_t* has_first_n;
+  const float* x0;
+  const uint8_t* has_x0;
+  const float* ref_uv;
+  const int32_t* rec_list[3];   // the database route's per-record lists on the device (point, tag, idx2): copied into the block
+  float* keep_normals;          // device, [3P | 3R] or null: the normals stay behind here
+};
+struct NormalsOut {
+  double *k1k2, *cov;
+  int32_t* status;
+  float* normal_ref;
+  int32_t* iters;
+  float* normal_rec;
+  uint8_t* rec_written;
+  int32_t* rec_list[3];
+};
+int normals_stage(dsh_ctx_base* c, int P, int R, const NormalsIn& in, const NormalsOut& out);
 }  // namespace dsh

@@ -1,5 +1,6 @@
 // C ABI of the device-resident DiffProp database (include/defslam_hip.h: dsh_diffdb_*, dsh_normals_estimate_db): the records of
-// SchwarpDatabase::calculateSchwarps stay in HBM between the Schwarp fits and NormalEstimator::ObtainK1K2.
+// SchwarpDatabase::calculateSchwarps stay in HBM between the Schwarp fits and NormalEstimator::ObtainK1K2.  dsh_normals_estimate_db groups
+// and gathers them, then runs the normals stage it shares with dsh_normals_estimate (dsh::normals_stage, dsh_nrsfm.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -117,68 +118,53 @@ int dsh_normals_estimate_db(dsh_ctx* ctx, dsh_diffdb* db, int P, const int32_t* 
   if (P == 0) return DSH_OK;
   hipStream_t st = c->stream;
   const long long n = db->count;
-  const size_t nn = n > 0 ? (size_t)n : 1;
+  const size_t Pn = (size_t)P, nn = n > 0 ? (size_t)n : 1;
   if (db->max_pid == INT32_MAX) return dsh_fail(c, DSH_ERR_ARG, "dsh_normals_estimate_db: point id 2^31 - 1 is not supported");
   const int nlook = std::max(db->max_pid + 1, 1);
-  DevBuf d_ids, d_look, d_key, d_count, d_cursor, d_perm, d_owner, d_tmp, d_ptr, d_x0, d_hx0, d_uv;
-  HIPCHK(c, d_ids.alloc(c, 4 * (size_t)P)); HIPCHK(c, d_look.alloc(c, 4 * (size_t)nlook)); HIPCHK(c, d_key.alloc(c, 4 * nn)); HIPCHK(c, d_count.alloc(c, 4 * (size_t)(P + 1)));
-  HIPCHK(c, d_cursor.alloc(c, 4 * (size_t)(P + 1))); HIPCHK(c, d_perm.alloc(c, 4 * nn)); HIPCHK(c, d_owner.alloc(c, 4 * nn)); HIPCHK(c, d_tmp.alloc(c, ddb_group_tmp_bytes(P)));
-  HIPCHK(c, d_ptr.alloc(c, 4 * (size_t)(P + 2)));
-  HIPCHK(c, d_x0.alloc(c, 8 * (size_t)P)); HIPCHK(c, d_hx0.alloc(c, P)); HIPCHK(c, d_uv.alloc(c, 8 * (size_t)P));
-  HIPCHK(c, hipMemcpyAsync(d_ids.p, point_ids, 4 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_x0.p, x0, 8 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_hx0.p, has_x0, P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_uv.p, ref_uv, 8 * (size_t)P, hipMemcpyHostToDevice, st));
+  UpBlock up;
+  const size_t o_ids = up.copy_of(point_ids, 4 * Pn), o_x0 = up.copy_of(x0, 8 * Pn), o_hx0 = up.copy_of(has_x0, Pn), o_uv = up.copy_of(ref_uv, 8 * Pn);
+  Arena ws;   // work space of the grouping
+  const size_t o_look = ws.take(4 * (size_t)nlook), o_key = ws.take(4 * nn), o_count = ws.take(4 * (Pn + 1)), o_cursor = ws.take(4 * (Pn + 1)), o_perm = ws.take(4 * nn),
+               o_owner = ws.take(4 * nn), o_tmp = ws.take(ddb_group_tmp_bytes(P)), o_ptr = ws.take(4 * (Pn + 2));
+  char* w = nullptr;
+  HIPCHK(c, c->scratch.take(ws.size, (void**)&w));
+  auto i32 = [&](size_t off) { return reinterpret_cast<int32_t*>(w + off); };
+  if (const int rc = up.copy(c)) return rc;
   // group the database by the requested points (a point's records keep their insertion order)
-  HIPCHK(c, ddb_group(n, db->pid, P, d_ids.as<int32_t>(), nlook, d_look.as<int32_t>(), d_key.as<int32_t>(), d_count.as<int32_t>(), d_cursor.as<int32_t>(),
-                      d_perm.as<int32_t>(), d_owner.as<int32_t>(), d_tmp.p, d_ptr.as<int32_t>(), st));
-  int32_t R = 0;   // records that belong to a requested point: the one number the host needs before it can size the launches
-  HIPCHK(c, hipMemcpyAsync(&R, d_ptr.as<int32_t>() + P, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, ddb_group(n, db->pid, P, up.dev<int32_t>(o_ids), nlook, i32(o_look), i32(o_key), i32(o_count), i32(o_cursor), i32(o_perm), i32(o_owner), w + o_tmp,
+                      i32(o_ptr), st));
+  DownBlock count;   // records that belong to a requested point: the one number the host needs before it can size the launches
+  count.take_exact(4);
+  if (const int rc = count.at(c, i32(o_ptr) + P)) return rc;
+  if (const int rc = count.receive(c)) return rc;
+  const int32_t R = *count.host<int32_t>(0);
   if (n_rec) *n_rec = R;
   if ((rec_point || rec_tag || rec_idx2 || normal_rec || rec_written) && R > max_rec)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_normals_estimate_db: " + std::to_string(R) + " records, the per-record buffers hold " + std::to_string(max_rec));
-  const size_t Rn = R > 0 ? (size_t)R : 1;
-  DevBuf d_soa, d_tag, d_idx2, d_isref, d_fn, d_hfn, d_Q, d_k, d_cov, d_st, d_nref, d_nrec, d_wr, d_it;
-  HIPCHK(c, d_soa.alloc(c, 72 * Rn)); HIPCHK(c, d_tag.alloc(c, 4 * Rn)); HIPCHK(c, d_idx2.alloc(c, 4 * Rn));
-  HIPCHK(c, d_isref.alloc(c, Rn)); HIPCHK(c, d_fn.alloc(c, 8 * Rn)); HIPCHK(c, d_hfn.alloc(c, Rn)); HIPCHK(c, d_Q.alloc(c, 8 * 20 * Rn));
-  HIPCHK(c, d_k.alloc(c, 16 * (size_t)P)); HIPCHK(c, d_cov.alloc(c, 32 * (size_t)P)); HIPCHK(c, d_st.alloc(c, 4 * (size_t)P)); HIPCHK(c, d_nref.alloc(c, 12 * (size_t)P));
-  HIPCHK(c, d_nrec.alloc(c, 12 * Rn)); HIPCHK(c, d_wr.alloc(c, Rn)); HIPCHK(c, d_it.alloc(c, 4 * (size_t)P));
-  HIPCHK(c, ddb_gather(R, d_perm.as<int32_t>(), db->rec, db->tag, db->idx2, d_soa.as<float>(), d_tag.as<int32_t>(), d_idx2.as<int32_t>(), st));
-  // every stored record is anchored in its point's reference keyframe (SchwarpDatabase.cc:297: records of other points are not saved)
-  HIPCHK(c, hipMemsetAsync(d_isref.p, 1, Rn, st));
-  HIPCHK(c, hipMemsetAsync(d_fn.p, 0, 8 * Rn, st));
-  HIPCHK(c, hipMemsetAsync(d_hfn.p, 0, Rn, st));
-  HIPCHK(c, hipMemsetAsync(d_cov.p, 0, 32 * (size_t)P, st));
-  HIPCHK(c, hipMemsetAsync(d_nref.p, 0, 12 * (size_t)P, st));
-  HIPCHK(c, hipMemsetAsync(d_nrec.p, 0, 12 * Rn, st));
-  HIPCHK(c, nrsfm_launch_normals(P, R, d_ptr.as<int32_t>(), d_owner.as<int32_t>(), d_soa.as<float>(), d_isref.as<uint8_t>(), d_fn.as<float>(), d_hfn.as<uint8_t>(),
-                                 d_x0.as<float>(), d_hx0.as<uint8_t>(), d_uv.as<float>(), d_Q.as<double>(), d_k.as<double>(), d_cov.as<double>(), d_st.as<int32_t>(),
-                                 d_nref.as<float>(), d_nrec.as<float>(), d_wr.as<uint8_t>(), d_it.as<int32_t>(), st));
-  // the normals stay behind for dsh_sfn_estimate_db
+  // the normals stay behind for dsh_sfn_estimate_db (nothing is in flight here: the old allocation can go)
   const long long need = 3ll * P + 3ll * R;
   if (need > db->last_cap) {
-    HIPCHK(c, hipStreamSynchronize(st));
     if (db->last_normals) (void)hipFree(db->last_normals);
     db->last_normals = nullptr; db->last_cap = 0;
     if (hipMalloc((void**)&db->last_normals, 4 * (size_t)(need + need / 2)) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_normals_estimate_db: out of device memory");
     db->last_cap = need + need / 2;
   }
-  HIPCHK(c, hipMemcpyAsync(db->last_normals, d_nref.p, 12 * (size_t)P, hipMemcpyDeviceToDevice, st));
-  if (R > 0) HIPCHK(c, hipMemcpyAsync(db->last_normals + 3 * (size_t)P, d_nrec.p, 12 * (size_t)R, hipMemcpyDeviceToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(k1k2, d_k.p, 16 * (size_t)P, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(status, d_st.p, 4 * (size_t)P, hipMemcpyDeviceToHost, st));
-  if (cov) HIPCHK(c, hipMemcpyAsync(cov, d_cov.p, 32 * (size_t)P, hipMemcpyDeviceToHost, st));
-  if (normal_ref) HIPCHK(c, hipMemcpyAsync(normal_ref, d_nref.p, 12 * (size_t)P, hipMemcpyDeviceToHost, st));
-  if (iters) HIPCHK(c, hipMemcpyAsync(iters, d_it.p, 4 * (size_t)P, hipMemcpyDeviceToHost, st));
-  if (R > 0) {
-    if (rec_point) HIPCHK(c, hipMemcpyAsync(rec_point, d_owner.p, 4 * Rn, hipMemcpyDeviceToHost, st));
-    if (rec_tag) HIPCHK(c, hipMemcpyAsync(rec_tag, d_tag.p, 4 * Rn, hipMemcpyDeviceToHost, st));
-    if (rec_idx2) HIPCHK(c, hipMemcpyAsync(rec_idx2, d_idx2.p, 4 * Rn, hipMemcpyDeviceToHost, st));
-    if (normal_rec) HIPCHK(c, hipMemcpyAsync(normal_rec, d_nrec.p, 12 * Rn, hipMemcpyDeviceToHost, st));
-    if (rec_written) HIPCHK(c, hipMemcpyAsync(rec_written, d_wr.p, Rn, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(c, hipStreamSynchronize(st));
+  const size_t Rn = R > 0 ? (size_t)R : 1;
+  Arena ws2;   // the gathered records and what the host-record route uploads with them
+  const size_t o_soa = ws2.take(72 * Rn), o_tag = ws2.take(4 * Rn), o_idx2 = ws2.take(4 * Rn), o_isref = ws2.take(Rn), o_fn = ws2.take(8 * Rn), o_hfn = ws2.take(Rn);
+  char* g = nullptr;
+  HIPCHK(c, c->scratch.take(ws2.size, (void**)&g));
+  float* d_soa = reinterpret_cast<float*>(g + o_soa);
+  int32_t *d_tag = reinterpret_cast<int32_t*>(g + o_tag), *d_idx2 = reinterpret_cast<int32_t*>(g + o_idx2);
+  HIPCHK(c, ddb_gather(R, i32(o_perm), db->rec, db->tag, db->idx2, d_soa, d_tag, d_idx2, st));
+  // every stored record is anchored in its point's reference keyframe (SchwarpDatabase.cc:297: records of other points are not saved)
+  HIPCHK(c, hipMemsetAsync(g + o_isref, 1, Rn, st));
+  HIPCHK(c, hipMemsetAsync(g + o_fn, 0, 8 * Rn, st));
+  HIPCHK(c, hipMemsetAsync(g + o_hfn, 0, Rn, st));
+  const dsh::NormalsIn in = {i32(o_ptr), i32(o_owner), d_soa, reinterpret_cast<uint8_t*>(g + o_isref), reinterpret_cast<float*>(g + o_fn),
+                             reinterpret_cast<uint8_t*>(g + o_hfn), up.dev<float>(o_x0), up.dev<uint8_t>(o_hx0), up.dev<float>(o_uv),
+                             {i32(o_owner), d_tag, d_idx2}, db->last_normals};
+  if (const int rc = dsh::normals_stage(c, P, R, in, {k1k2, cov, status, normal_ref, iters, normal_rec, rec_written, {rec_point, rec_tag, rec_idx2}})) return rc;
   db->last_P = P; db->last_R = R;
   return DSH_OK;
 }

@@ -1,98 +1,96 @@
 // Host side of dsh_scale_min_median / dsh_optimize_horn / dsh_surface_register (include/defslam_hip.h):
 // SurfaceRegistration::registerSurfaces (Modules/Mapping/SurfaceRegistration.cc:48-153) with its two numeric callees.
 // The host only walks the caller's random stream (which points are candidates) and composes the 4x4 result; the
-// residual lists, the medians, the Levenberg-Marquardt loop and its sums run in register_kernels.hip.
+// residual lists, the medians, the Levenberg-Marquardt loop and its sums run in register_kernels.hip.  Each stage moves one block up and
+// one down (UpBlock / DownBlock, dsh_ctx.h); a registration sends its two clouds once, with the first stage.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "mapping_launch.h"
 
+namespace dsh {
+// declared in dsh_ctx.h: one pass with null lists counts, a second one fills the slices of the block
+int smm_walk_candidates(int n, const double* u, int64_t nu, int32_t* cand, int64_t* off, int64_t* consumed) {
+  int64_t k = 0;
+  int nc = 0;
+  for (int i = 0; i < n; i++) {
+    if (k >= nu) return -1;
+    const double r_i = u[k++];
+    if (r_i > 0.25) continue;
+    if (k + (n - 1) > nu) return -1;
+    if (cand) { cand[nc] = i; off[nc] = k; }
+    nc++;
+    k += n - 1;
+  }
+  *consumed = k;
+  return nc;
+}
+}  // namespace dsh
+
 namespace {
 
 constexpr int kMaxPairs = 8000;   // the finishing kernel keeps two floats per pair in LDS
 
-struct Clouds {   // device copies of the two clouds (slices of the context scratch)
-  float *a = nullptr, *b = nullptr;
+struct Clouds {   // device copies of the two clouds (slices of a block up)
+  const float *a = nullptr, *b = nullptr;
 };
 
-int upload_clouds(dsh_ctx_base* c, int n, const float* a, const float* b, Clouds& d) {
-  void* p = nullptr;
-  HIPCHK(c, c->scratch.take(12 * (size_t)n, &p)); d.a = static_cast<float*>(p);
-  HIPCHK(c, c->scratch.take(12 * (size_t)n, &p)); d.b = static_cast<float*>(p);
-  HIPCHK(c, hipMemcpyAsync(d.a, a, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d.b, b, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  return DSH_OK;
-}
-
-// scaleMinMedian on device clouds; returns status through *status (0, 1, 2)
-int scale_min_median_dev(dsh_ctx_base* c, int n, const float* d_mono, const float* d_stereo, const double* u, int64_t nu, float* scale,
-                         int64_t* consumed, int32_t* status) {
-  // which i are candidates and where their j-draws start (GroundTruthCalculator.cc:64-84)
-  std::vector<int32_t> cand;
-  std::vector<int64_t> off;
+// scaleMinMedian: the clouds, the consumed part of the stream and the candidate list go up in one block, which stays in d for a second
+// stage; the scale and the status (0, 1, 2) are read back
+int scale_min_median_dev(dsh_ctx_base* c, int n, const float* mono, const float* stereo, const double* u, int64_t nu, float* scale, int64_t* consumed,
+                         int32_t* status, Clouds& d) {
   int64_t k = 0;
-  bool too_short = false;
-  for (int i = 0; i < n; i++) {
-    if (k >= nu) { too_short = true; break; }
-    const double r_i = u[k++];
-    if (r_i > 0.25) continue;
-    if (k + (n - 1) > nu) { too_short = true; break; }
-    cand.push_back(i);
-    off.push_back(k);
-    k += n - 1;
-  }
-  if (too_short) {
+  const int nc = dsh::smm_walk_candidates(n, u, nu, nullptr, nullptr, &k);
+  if (nc < 0) {
     *status = 1;
     *scale = 0.f;
     return dsh_fail(c, DSH_ERR_ARG, "dsh_scale_min_median: the uniform stream is shorter than the draws the reference makes");
   }
   if (consumed) *consumed = k;
-  const int nc = (int)cand.size();
-  hipStream_t st = c->stream;
-  void *du = nullptr, *dc = nullptr, *doff = nullptr, *dmed = nullptr, *dsc = nullptr, *dout = nullptr;
-  HIPCHK(c, c->scratch.take(8 * (size_t)(k > 0 ? k : 1), &du));
-  HIPCHK(c, c->scratch.take(4 * (size_t)(nc + 1), &dc));
-  HIPCHK(c, c->scratch.take(8 * (size_t)(nc + 1), &doff));
-  HIPCHK(c, c->scratch.take(4 * (size_t)(nc + 1), &dmed));
-  HIPCHK(c, c->scratch.take(8 * (size_t)(nc + 1), &dsc));
-  HIPCHK(c, c->scratch.take(64, &dout));
-  if (k > 0) HIPCHK(c, hipMemcpyAsync(du, u, 8 * (size_t)k, hipMemcpyHostToDevice, st));
-  if (nc > 0) {
-    HIPCHK(c, hipMemcpyAsync(dc, cand.data(), 4 * (size_t)nc, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(doff, off.data(), 8 * (size_t)nc, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, reg_scale_min_median(n, nc, d_mono, d_stereo, static_cast<double*>(du), static_cast<int32_t*>(dc), static_cast<int64_t*>(doff),
-                                 static_cast<float*>(dmed), static_cast<double*>(dsc), static_cast<double*>(dout), st));
-  double out[4];
-  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof out, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));   // also keeps cand/off alive until the copies are done
-  *scale = (float)out[0];
-  *status = (int32_t)out[1];
+  UpBlock up;
+  const size_t o_a = up.copy_of(mono, 12 * (size_t)n), o_b = up.copy_of(stereo, 12 * (size_t)n), o_u = up.copy_of(u, 8 * (size_t)k), o_c = up.take(4 * (size_t)nc),
+               o_off = up.take(8 * (size_t)nc);
+  DownBlock down;
+  const size_t d_out = down.take_exact(64);
+  float* dmed = nullptr;
+  double* dsc = nullptr;
+  HIPCHK(c, dsh_scratch_array(c, &dmed, (size_t)nc + 1));
+  HIPCHK(c, dsh_scratch_array(c, &dsc, (size_t)nc + 1));
+  if (const int rc = up.stage(c)) return rc;
+  dsh::smm_walk_candidates(n, u, nu, up.host<int32_t>(o_c), up.host<int64_t>(o_off), &k);
+  if (const int rc = up.send(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  d = {up.dev<float>(o_a), up.dev<float>(o_b)};
+  HIPCHK(c, reg_scale_min_median(n, nc, d.a, d.b, up.dev<double>(o_u), up.dev<int32_t>(o_c), up.dev<int64_t>(o_off), dmed, dsc, down.dev<double>(d_out), c->stream));
+  if (const int rc = down.receive(c)) return rc;
+  *scale = (float)down.host<double>(d_out)[0];
+  *status = (int32_t)down.host<double>(d_out)[1];
   return DSH_OK;
 }
 
-int optimize_horn_dev(dsh_ctx_base* c, int n, const float* d1, const float* d2, double* sim3, double chi, double huber, int32_t* acceptable,
-                      double* info) {
-  hipStream_t st = c->stream;
-  void *ds = nullptr, *derr = nullptr, *dout = nullptr;
-  HIPCHK(c, c->scratch.take(64, &ds));
-  HIPCHK(c, c->scratch.take(24 * (size_t)(n > 0 ? n : 1), &derr));
-  HIPCHK(c, c->scratch.take(128, &dout));
-  HIPCHK(c, hipMemcpyAsync(ds, sim3, 64, hipMemcpyHostToDevice, st));
+// OptimizeHorn on the clouds in d, or on h1 / h2 when they are not on the device yet: then they go up with the start value
+int optimize_horn_dev(dsh_ctx_base* c, int n, Clouds d, const float* h1, const float* h2, double* sim3, double chi, double huber, int32_t* acceptable, double* info) {
+  UpBlock up;
+  const size_t o_s = up.copy_of(sim3, 64), o_1 = up.copy_of(h1, 12 * (size_t)n), o_2 = up.copy_of(h2, 12 * (size_t)n);
+  DownBlock down;
+  const size_t d_out = down.take_exact(128);
+  double* derr = nullptr;
+  HIPCHK(c, dsh_scratch_array(c, &derr, 3 * (size_t)n));
+  if (const int rc = up.copy(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  if (h1) d = {up.dev<float>(o_1), up.dev<float>(o_2)};
   const float delta_huber = (float)std::sqrt(huber);   // DefOptimizer.cc:869
-  HIPCHK(c, reg_horn(n, d1, d2, static_cast<double*>(ds), chi, (double)delta_huber, static_cast<double*>(derr), static_cast<double*>(dout), st));
-  double out[16];
-  HIPCHK(c, hipMemcpyAsync(out, dout, sizeof out, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, reg_horn(n, d.a, d.b, up.dev<double>(o_s), chi, (double)delta_huber, derr, down.dev<double>(d_out), c->stream));
+  if (const int rc = down.receive(c)) return rc;
+  const double* out = down.host<double>(d_out);
   std::memcpy(sim3, out, 64);
   *acceptable = out[14] != 0.0 ? 1 : 0;
-  if (info) { info[0] = out[8]; info[1] = out[9]; info[2] = out[10]; info[3] = out[11]; info[4] = out[12]; info[5] = out[13]; }
+  if (info) std::memcpy(info, out + 8, 6 * sizeof(double));
   return DSH_OK;
 }
 
@@ -148,9 +146,7 @@ int dsh_scale_min_median(dsh_ctx* ctx, int n, const float* pos_mono, const float
   int rc = dsh_enter(c, "dsh_scale_min_median");
   if (rc != DSH_OK) return rc;
   Clouds d;
-  rc = upload_clouds(c, n, pos_mono, pos_stereo, d);
-  if (rc != DSH_OK) return rc;
-  return scale_min_median_dev(c, n, d.a, d.b, u, nu, scale, consumed, status);
+  return scale_min_median_dev(c, n, pos_mono, pos_stereo, u, nu, scale, consumed, status, d);
 }
 
 int dsh_optimize_horn(dsh_ctx* ctx, int n, const float* pts1, const float* pts2, double* sim3, double chi, double huber, int32_t* acceptable,
@@ -160,10 +156,7 @@ int dsh_optimize_horn(dsh_ctx* ctx, int n, const float* pts1, const float* pts2,
   if (n <= 0 || !pts1 || !pts2 || !sim3 || !acceptable || !(huber >= 0.0)) return dsh_fail(c, DSH_ERR_ARG, "dsh_optimize_horn: bad argument");
   int rc = dsh_enter(c, "dsh_optimize_horn");
   if (rc != DSH_OK) return rc;
-  Clouds d;
-  rc = upload_clouds(c, n, pts1, pts2, d);
-  if (rc != DSH_OK) return rc;
-  return optimize_horn_dev(c, n, d.a, d.b, sim3, chi, huber, acceptable, info);
+  return optimize_horn_dev(c, n, Clouds{}, pts1, pts2, sim3, chi, huber, acceptable, info);
 }
 
 int dsh_surface_register(dsh_ctx* ctx, int n, const float* cloud_surface, const float* cloud_map, const double* u, int64_t nu, const float* Twc,
@@ -177,19 +170,17 @@ int dsh_surface_register(dsh_ctx* ctx, int n, const float* cloud_surface, const 
   if (n < 15) return DSH_OK;   // SurfaceRegistration.cc:108-109
   int rc = dsh_enter(c, "dsh_surface_register");
   if (rc != DSH_OK) return rc;
-  Clouds d;
-  rc = upload_clouds(c, n, cloud_surface, cloud_map, d);
-  if (rc != DSH_OK) return rc;
+  Clouds d;   // the two clouds go up once, with the first stage
   float scale = 0.f;
   int32_t status = 0;
-  rc = scale_min_median_dev(c, n, d.a, d.b, u, nu, &scale, nullptr, &status);
+  rc = scale_min_median_dev(c, n, cloud_surface, cloud_map, u, nu, &scale, nullptr, &status, d);
   if (rc != DSH_OK) return rc;
   // g2o::Sim3(identity rotation, zero translation, scale): Quaterniond(Matrix3d::Identity()) = (0, 0, 0, 1)
   sim3[0] = sim3[1] = sim3[2] = 0.0; sim3[3] = 1.0;
   sim3[4] = sim3[5] = sim3[6] = 0.0; sim3[7] = (double)scale;
   int32_t acceptable = 0;
   double hi[6];
-  rc = optimize_horn_dev(c, n, d.a, d.b, sim3, chi_limit * chi_limit, 0.01, &acceptable, hi);
+  rc = optimize_horn_dev(c, n, d, nullptr, nullptr, sim3, chi_limit * chi_limit, 0.01, &acceptable, hi);
   if (rc != DSH_OK) return rc;
   if (info) {
     info[0] = scale;

@@ -1,6 +1,7 @@
 // C ABI of the Schwarzian warp fit (include/defslam_hip.h: dsh_schwarp_eval, dsh_schwarp_fit, _fit_batch, _fit_batch_store).
 // A fit -- the trust-region loop of the reference (3 iterations, SchwarpDatabase.cc:211-222) with its control on the device -- is one fixed
 // sequence of launches for the whole batch (nrsfm_kernels.hip: nrsfm_swp_fit_batch); the single fit is a batch of one.
+// Every call moves one block up and one block down (UpBlock / DownBlock, dsh_ctx.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,7 +17,7 @@
 
 namespace {
 bool args_ok(const dsh_bbs* b, int P, const float* kp1, const float* kp2, const float* invsig, const double* x) {
-  return b && b->nptsu >= 4 && b->nptsv >= 4 && b->umax > b->umin && b->vmax > b->vmin && P > 0 && kp1 && kp2 && invsig && x && b->nptsu * b->nptsv <= 4096;
+  return bbs_grid_ok(b) && P > 0 && kp1 && kp2 && invsig && x && b->nptsu * b->nptsv <= 4096;
 }
 }  // namespace
 
@@ -31,20 +32,15 @@ int dsh_schwarp_eval(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, 
   const SwpSizes s = swp_sizes(bbs->nptsu, bbs->nptsv, P);
   const size_t r_bytes = 8 * (size_t)s.m, j_bytes = r_bytes * s.n2;   // the dense (2P + 4N) x 2N Jacobian: only when it is asked for
   hipStream_t st = c->stream;
-  DevBuf dkp1, dkp2, disg, dx, dr, dJ;
-  HIPCHK(c, dkp1.alloc(c, 8 * (size_t)P)); HIPCHK(c, dkp2.alloc(c, 8 * (size_t)P)); HIPCHK(c, disg.alloc(c, 4 * (size_t)P));
-  HIPCHK(c, dx.alloc(c, 8 * (size_t)s.n2)); HIPCHK(c, dr.alloc(c, r_bytes));
-  if (jacobian) HIPCHK(c, dJ.alloc(c, j_bytes));
-  HIPCHK(c, hipMemcpyAsync(dkp1.p, kp1, 8 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dkp2.p, kp2, 8 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(disg.p, invsig, 4 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dx.p, x, 8 * (size_t)s.n2, hipMemcpyHostToDevice, st));
-  HIPCHK(c, nrsfm_swp_eval(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, P, fx_slot, fy_slot, lambda, dkp1.as<float>(), dkp2.as<float>(),
-                           disg.as<float>(), dx.as<double>(), dr.as<double>(), dJ.as<double>(), jacobian ? 1 : 0, st));
-  HIPCHK(c, hipMemcpyAsync(residuals, dr.p, r_bytes, hipMemcpyDeviceToHost, st));
-  if (jacobian) HIPCHK(c, hipMemcpyAsync(jacobian, dJ.p, j_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return DSH_OK;
+  UpBlock up;
+  const size_t o_kp1 = up.copy_of(kp1, 8 * (size_t)P), o_kp2 = up.copy_of(kp2, 8 * (size_t)P), o_isg = up.copy_of(invsig, 4 * (size_t)P), o_x = up.copy_of(x, 8 * (size_t)s.n2);
+  DownBlock down;
+  const size_t d_r = down.copy_to(residuals, r_bytes), d_J = down.copy_to(jacobian, j_bytes);
+  if (const int rc = up.copy(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  HIPCHK(c, nrsfm_swp_eval(bbs_par(bbs, 2), P, fx_slot, fy_slot, lambda, up.dev<float>(o_kp1), up.dev<float>(o_kp2), up.dev<float>(o_isg), up.dev<double>(o_x),
+                           down.dev<double>(d_r), jacobian ? down.dev<double>(d_J) : nullptr, jacobian ? 1 : 0, st));
+  return down.receive(c);
 }
 
 }  // extern "C"
@@ -110,16 +106,22 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     o.info = out.take(256);
     o.costs = out.take(256);
   }
-  // store mode: DiffProp records / drop flags / point ids / tags / second-keyframe indices of all fits, problem b at stride maxP
-  DevBuf sdiff, sdrop, skeep, spos, stmp;
-  const size_t nall = (size_t)B * maxP;
-  size_t o_pid = 0, o_tag = 0, o_idx2 = 0;
+  // store mode: DiffProp records / drop flags / point ids / tags / second-keyframe indices of all fits, problem b at stride maxP.  What
+  // the host reads of them -- the flags, the records if a problem asks for them, the count of the records added -- ends the output block
+  DevBuf sdiff_ws, skeep, spos, stmp;
+  const size_t nall = (size_t)B * maxP, fits_end = out.size;   // fits_end: the part of the output block that starts at zero
+  size_t o_pid = 0, o_tag = 0, o_idx2 = 0, o_sdrop = 0, o_sdiff = 0, o_added = 0;
+  bool want_diff = false;
+  for (int b = 0; b < B; b++) want_diff = want_diff || probs[b].diff != nullptr;
   if (db) {
     o_pid = in.take(4 * nall);
     o_tag = in.take(4 * nall);
     o_idx2 = in.take(4 * nall);
-    HIPCHK(c, sdiff.alloc(c, 72 * nall)); HIPCHK(c, sdrop.alloc(c, nall)); HIPCHK(c, skeep.alloc(c, 4 * nall)); HIPCHK(c, spos.alloc(c, 4 * nall));
-    HIPCHK(c, stmp.alloc(c, ddb_scan_tmp_bytes((int)nall)));
+    o_sdrop = out.take(nall);
+    o_sdiff = out.take(want_diff ? 72 * nall : 0);
+    o_added = out.take(8);
+    if (!want_diff) HIPCHK(c, sdiff_ws.alloc(c, 72 * nall));
+    HIPCHK(c, skeep.alloc(c, 4 * nall)); HIPCHK(c, spos.alloc(c, 4 * nall)); HIPCHK(c, stmp.alloc(c, ddb_scan_tmp_bytes((int)nall)));
   }
   // the descriptors hold device addresses of both blocks: both are placed before anything is filled in.  The start values of x are
   // staged behind the input block, laid out like the head of the output block, and go up in a copy of their own
@@ -128,6 +130,8 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
   if (const int rc = in.stage(c, x_bytes)) return rc;
   char* hx = in.host<char>(in.size);
   std::memset(hx, 0, x_bytes);
+  float* sdiff = want_diff ? out.dev<float>(o_sdiff) : sdiff_ws.as<float>();
+  uint8_t* sdrop = out.dev<uint8_t>(o_sdrop);
   // what has to start at zero (scalars of the controller, the step vector) lies in one block: one memset for the whole batch
   DevBuf dzero;
   size_t zero_bytes = 0;
@@ -157,8 +161,8 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     f.cs = in.dev<double>(o.cs);
     f.bend = init ? in.dev<double>(o.bend) : nullptr;
     f.x = out.dev<double>(o.xo);
-    f.diff = db ? sdiff.as<float>() + 18 * (size_t)b * maxP : (q.diff ? out.dev<float>(o.diff) : nullptr);
-    f.drop = db ? sdrop.as<uint8_t>() + (size_t)b * maxP : (q.drop ? out.dev<uint8_t>(o.drop) : nullptr);
+    f.diff = db ? sdiff + 18 * (size_t)b * maxP : (q.diff ? out.dev<float>(o.diff) : nullptr);
+    f.drop = db ? sdrop + (size_t)b * maxP : (q.drop ? out.dev<uint8_t>(o.drop) : nullptr);
     f.info = out.dev<int32_t>(o.info);
     f.costs = out.dev<double>(o.costs);
     f.scal = reinterpret_cast<double*>(dzero.as<char>() + zoff);
@@ -190,28 +194,17 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
   }
   if (const int rc = in.send(c)) return rc;
   HIPCHK(c, hipMemcpyAsync(out.d, hx, x_bytes, hipMemcpyHostToDevice, st));
-  if (out.size > x_bytes) HIPCHK(c, hipMemsetAsync(out.d + x_bytes, 0, out.size - x_bytes, st));
+  if (fits_end > x_bytes) HIPCHK(c, hipMemsetAsync(out.d + x_bytes, 0, fits_end - x_bytes, st));
   HIPCHK(c, nrsfm_swp_fit_batch(in.dev<SwpFit>(o_fits), B, maxP, maxN, max_it, with_init, st));
-  if (const int rc = out.fetch(c)) return rc;
-  std::vector<uint8_t> hdrop;
-  std::vector<float> hdiff;
-  int32_t added = 0;
-  if (db) {   // kept records -> the database, in (fit, match) order; only the drop flags (and, if asked for, the records) travel to the host
-    HIPCHK(c, ddb_append((int)nall, sdrop.as<uint8_t>(), sdiff.as<float>(), in.dev<int32_t>(o_pid), in.dev<int32_t>(o_tag), in.dev<int32_t>(o_idx2),
-                         skeep.as<int32_t>(), spos.as<int32_t>(), stmp.p, ddb_scan_tmp_bytes((int)nall), db->count, db->cap, db->rec, db->pid, db->tag, db->idx2, st));
-    hdrop.resize(nall);
-    HIPCHK(c, hipMemcpyAsync(hdrop.data(), sdrop.p, nall, hipMemcpyDeviceToHost, st));
-    bool want_diff = false;
-    for (int b = 0; b < B; b++) want_diff = want_diff || probs[b].diff != nullptr;
-    if (want_diff) { hdiff.resize(18 * nall); HIPCHK(c, hipMemcpyAsync(hdiff.data(), sdiff.p, 72 * nall, hipMemcpyDeviceToHost, st)); }
-    int32_t last[2] = {0, 0};   // records added = exclusive scan position + keep flag of the last entry
-    HIPCHK(c, hipMemcpyAsync(&last[0], spos.as<int32_t>() + nall - 1, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&last[1], skeep.as<int32_t>() + nall - 1, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    added = last[0] + last[1];
+  if (db) {   // kept records -> the database, in (fit, match) order; records added = exclusive scan position + keep flag of the last entry
+    HIPCHK(c, ddb_append((int)nall, sdrop, sdiff, in.dev<int32_t>(o_pid), in.dev<int32_t>(o_tag), in.dev<int32_t>(o_idx2), skeep.as<int32_t>(), spos.as<int32_t>(),
+                         stmp.p, ddb_scan_tmp_bytes((int)nall), db->count, db->cap, db->rec, db->pid, db->tag, db->idx2, st));
+    HIPCHK(c, hipMemcpyAsync(out.dev<int32_t>(o_added), spos.as<int32_t>() + nall - 1, 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(out.dev<int32_t>(o_added) + 1, skeep.as<int32_t>() + nall - 1, 4, hipMemcpyDeviceToDevice, st));
   }
-  HIPCHK(c, hipStreamSynchronize(st));
+  if (const int rc = out.receive(c)) return rc;
   if (db) {
+    const int32_t added = out.host<int32_t>(o_added)[0] + out.host<int32_t>(o_added)[1];
     if (db->count + added > db->cap) return dsh_fail(c, DSH_ERR_STATE, "dsh_schwarp_fit_batch_store: internal error, the reserved capacity was exceeded");
     db->count += added;
     db->max_pid = std::max(db->max_pid, max_pid);
@@ -221,8 +214,8 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     const Off& o = off[b];
     std::memcpy(q.x, out.host<double>(o.xo), 8 * (size_t)sizes[b].n2);
     if (db) {
-      if (q.drop) std::memcpy(q.drop, hdrop.data() + (size_t)b * maxP, (size_t)q.P);
-      if (q.diff) std::memcpy(q.diff, hdiff.data() + 18 * (size_t)b * maxP, 72 * (size_t)q.P);
+      if (q.drop) std::memcpy(q.drop, out.host<uint8_t>(o_sdrop) + (size_t)b * maxP, (size_t)q.P);
+      if (q.diff) std::memcpy(q.diff, out.host<float>(o_sdiff) + 18 * (size_t)b * maxP, 72 * (size_t)q.P);
     } else if (q.diff) { std::memcpy(q.diff, out.host<float>(o.diff), 72 * (size_t)q.P); std::memcpy(q.drop, out.host<uint8_t>(o.drop), (size_t)q.P); }
     std::memcpy(q.info, out.host<int32_t>(o.info), sizeof q.info);
     std::memcpy(&q.init_ok, out.host<int32_t>(o.info) + 2, sizeof q.init_ok);   // info[2]: the verdict on the initialisation

@@ -2,6 +2,8 @@
 // Modules/Mapping/ShapeFromNormals.cc.  The stacked least squares is solved on the device by corrected semi-normal
 // equations: G = A^T A and A^T b on FP64 MFMA (swp_normal_kernel), tile Cholesky (swp_solve_kernel), two steps of
 // iterative refinement with the residual formed from A itself, which restores the accuracy a QR factorisation has.
+// Also dsh_warp_initialize and dsh_search_by_schwarp.  Every call moves one block up and one down (UpBlock / DownBlock, dsh_ctx.h) and
+// takes its device-only work space as one Arena-laid scratch slice.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,18 +64,26 @@ void bending_dense(const dsh_bbs* b, double lambda, double* Bm) {
         }
 }
 
-bool bbs_ok(const dsh_bbs* b) { return b && b->nptsu >= 4 && b->nptsv >= 4 && b->umax > b->umin && b->vmax > b->vmin; }
 }  // namespace
 
 namespace dsh {
 // dense N x N bending matrix of the grid (used by the batched Schwarp fit for its Warp::initialize stage, dsh_schwarp.cpp)
 void bbs_bending_dense(const dsh_bbs* b, double lambda, double* Bm) { bending_dense(b, lambda, Bm); }
+
+void sfn_fill_constant_rows(const dsh_bbs* bbs, int n, double bending_weight, double mean_depth, double* tail, double* b, double* ones) {
+  const size_t N = (size_t)bbs->nptsu * bbs->nptsv, m = 2 * (size_t)n + N + 1;
+  bending_dense(bbs, bending_weight, tail);
+  std::fill_n(tail + N * N, N, 1.0);
+  std::fill_n(b, m, 0.0);
+  b[m - 1] = (double)N * mean_depth;
+  std::fill_n(ones, N, 1.0);
+}
 }  // namespace dsh
 
 extern "C" {
 
 int dsh_bbs_bending(const dsh_bbs* bbs, double lambda, double* bending) {
-  if (!bbs_ok(bbs) || !bending) return DSH_ERR_ARG;
+  if (!bbs_grid_ok(bbs) || !bending) return DSH_ERR_ARG;
   bending_dense(bbs, lambda, bending);
   return DSH_OK;
 }
@@ -81,14 +91,14 @@ int dsh_bbs_bending(const dsh_bbs* bbs, double lambda, double* bending) {
 }  // extern "C"
 
 // The body of dsh_sfn_estimate / dsh_sfn_estimate_db: the normals come from the host (normals) or are picked on the device out of the
-// last normal solve of a database (db, sel).
+// last normal solve of a database (db, sel).  Two pairs of blocks: the control points come down before the surface points are evaluated.
 static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u, const double* v, const float* normals, const dsh_diffdb* ndb, const int32_t* sel,
                         double bending_weight, double mean_depth, int n_all, const double* u_all, const double* v_all, double* ctrl_raw, double* ctrl, float* pts,
                         int32_t* ok) {
   dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (const int rc = dsh_enter(c, "dsh_sfn_estimate")) return rc;
-  if (!bbs_ok(bbs) || n < 0 || n_all < 0 || (n > 0 && (!u || !v || (!normals && !(ndb && sel)))) || (n_all > 0 && (!u_all || !v_all || !pts)) || !ctrl || !ok)
+  if (!bbs_grid_ok(bbs) || n < 0 || n_all < 0 || (n > 0 && (!u || !v || (!normals && !(ndb && sel)))) || (n_all > 0 && (!u_all || !v_all || !pts)) || !ctrl || !ok)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_sfn_estimate: bad argument");
   if (ndb) {
     if (ndb->ctx != c) return dsh_fail(c, DSH_ERR_ARG, "dsh_sfn_estimate_db: the database belongs to another context");
@@ -101,68 +111,64 @@ static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u
   *ok = 0;
   hipStream_t st = c->stream;
   const int m = 2 * n + N + 1, np = nrsfm_swp_solve_np(N);
-  DevBuf dA, db, dr, dx, ddx, dG, dg, dM, dW, dones, dscal, du, dv, dn, dua, dva, dctrl, dpts;
-  HIPCHK(c, dA.alloc(c, 8 * (size_t)m * N)); HIPCHK(c, db.alloc(c, 8 * (size_t)m)); HIPCHK(c, dr.alloc(c, 8 * (size_t)m));
-  HIPCHK(c, dx.alloc(c, 8 * (size_t)N)); HIPCHK(c, ddx.alloc(c, 8 * (size_t)N)); HIPCHK(c, dG.alloc(c, 8 * (size_t)N * N)); HIPCHK(c, dg.alloc(c, 8 * (size_t)N));
-  HIPCHK(c, dM.alloc(c, 8 * (size_t)np * np)); HIPCHK(c, dW.alloc(c, 8 * (size_t)np * 16)); HIPCHK(c, dones.alloc(c, 8 * (size_t)N)); HIPCHK(c, dscal.alloc(c, 256));
-  HIPCHK(c, du.alloc(c, 8 * (size_t)n)); HIPCHK(c, dv.alloc(c, 8 * (size_t)n)); HIPCHK(c, dn.alloc(c, 12 * (size_t)n));
-  HIPCHK(c, dua.alloc(c, 8 * (size_t)n_all)); HIPCHK(c, dva.alloc(c, 8 * (size_t)n_all)); HIPCHK(c, dctrl.alloc(c, 8 * (size_t)N)); HIPCHK(c, dpts.alloc(c, 12 * (size_t)n_all));
-  // constant rows: bending block, the row of ones, right-hand side (zero except N * mean_depth in the last row)
-  std::vector<double> tail((size_t)(N + 1) * N), bvec((size_t)m, 0.0), ones((size_t)N, 1.0);
-  bending_dense(bbs, bending_weight, tail.data());
-  std::fill(tail.begin() + (size_t)N * N, tail.end(), 1.0);
-  bvec[m - 1] = (double)N * mean_depth;
-  HIPCHK(c, hipMemsetAsync(dA.p, 0, 8 * (size_t)2 * n * N, st));
-  HIPCHK(c, hipMemcpyAsync(dA.as<double>() + (size_t)2 * n * N, tail.data(), 8 * tail.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(db.p, bvec.data(), 8 * (size_t)m, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dones.p, ones.data(), 8 * (size_t)N, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(dx.p, 0, 8 * (size_t)N, st));
-  HIPCHK(c, hipMemsetAsync(dscal.p, 0, 256, st));
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(du.p, u, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(dv.p, v, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    if (ndb) {
-      DevBuf dsel;
-      HIPCHK(c, dsel.alloc(c, 4 * (size_t)n));
-      HIPCHK(c, hipMemcpyAsync(dsel.p, sel, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-      HIPCHK(c, ddb_pick_normals(n, dsel.as<int32_t>(), ndb->last_normals, ndb->last_normals + 3 * (size_t)ndb->last_P, dn.as<float>(), st));
-    } else {
-      HIPCHK(c, hipMemcpyAsync(dn.p, normals, 12 * (size_t)n, hipMemcpyHostToDevice, st));
-    }
+  const size_t nz = (size_t)n, Nz = (size_t)N, rows = 8 * 2 * nz * Nz;   // rows: bytes of the normal rows of A, which sfn_rows_kernel fills
+  // the constant rows lead the block up and land right behind the normal rows: the device side of the block continues A
+  UpBlock up;
+  const size_t o_tail = up.take(8 * (Nz + 1) * Nz), o_b = up.take(8 * (size_t)m), o_ones = up.take(8 * Nz), o_u = up.copy_of(u, 8 * nz), o_v = up.copy_of(v, 8 * nz),
+               o_n = ndb ? up.copy_of(sel, 4 * nz) : up.copy_of(normals, 12 * nz);
+  Arena ws;   // x and the scalars of the solve are neighbours: one memset, and the block down lies on them
+  const size_t o_A = ws.take(rows + up.size), o_r = ws.take(8 * (size_t)m), o_ddx = ws.take(8 * Nz), o_G = ws.take(8 * Nz * Nz), o_g = ws.take(8 * Nz),
+               o_M = ws.take(8 * (size_t)np * np), o_W = ws.take(8 * (size_t)np * 16), o_x = ws.take(8 * Nz), o_scal = ws.take(256), o_pick = ws.take(ndb ? 12 * nz : 0);
+  char* w = nullptr;
+  HIPCHK(c, c->scratch.take(ws.size, (void**)&w));
+  auto f64 = [&](size_t off) { return reinterpret_cast<double*>(w + off); };
+  up.d = w + o_A + rows;
+  if (const int rc = up.stage(c)) return rc;
+  dsh::sfn_fill_constant_rows(bbs, n, bending_weight, mean_depth, up.host<double>(o_tail), up.host<double>(o_b), up.host<double>(o_ones));
+  if (const int rc = up.send(c)) return rc;
+  HIPCHK(c, hipMemsetAsync(w + o_A, 0, rows, st));
+  HIPCHK(c, hipMemsetAsync(w + o_x, 0, o_scal + 256 - o_x, st));
+  const float* dn = up.dev<float>(o_n);
+  if (ndb && n > 0) {
+    dn = reinterpret_cast<float*>(w + o_pick);
+    HIPCHK(c, ddb_pick_normals(n, up.dev<int32_t>(o_n), ndb->last_normals, ndb->last_normals + 3 * (size_t)ndb->last_P, reinterpret_cast<float*>(w + o_pick), st));
   }
-  HIPCHK(c, nrsfm_sfn_rows(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, n, du.as<double>(), dv.as<double>(), dn.as<float>(), dA.as<double>(), st));
+  double *dA = f64(o_A), *dx = f64(o_x), *db = up.dev<double>(o_b), *dones = up.dev<double>(o_ones);
+  HIPCHK(c, nrsfm_sfn_rows(bbs_par(bbs, 1), n, up.dev<double>(o_u), up.dev<double>(o_v), dn, dA, st));
   // x0: G x = A^T b  (the solve kernel returns M dx = -g, so it is fed g = A^T (-(b - A x)))
-  double* scal = dscal.as<double>();
   for (int it = 0; it < 3; it++) {
-    HIPCHK(c, nrsfm_sfn_residual(m, N, dA.as<double>(), dx.as<double>(), db.as<double>(), -1.0, dr.as<double>(), st));
-    HIPCHK(c, nrsfm_swp_normal(m, N, dA.as<double>(), dr.as<double>(), dones.as<double>(), dG.as<double>(), dg.as<double>(), st));
-    if (it == 0) HIPCHK(c, nrsfm_swp_solve(N, dG.as<double>(), dg.as<double>(), 1e300, dM.as<double>(), dW.as<double>(), ddx.as<double>(), scal + 2, 0, N, st));   // dense: the mean-depth row couples every pair of control points
-    else HIPCHK(c, nrsfm_swp_resolve(N, dg.as<double>(), dM.as<double>(), dW.as<double>(), ddx.as<double>(), 0, N, st));
-    HIPCHK(c, nrsfm_sfn_axpy(N, ddx.as<double>(), dx.as<double>(), st));
+    HIPCHK(c, nrsfm_sfn_residual(m, N, dA, dx, db, -1.0, f64(o_r), st));
+    HIPCHK(c, nrsfm_swp_normal(m, N, dA, f64(o_r), dones, f64(o_G), f64(o_g), st));
+    if (it == 0) HIPCHK(c, nrsfm_swp_solve(N, f64(o_G), f64(o_g), 1e300, f64(o_M), f64(o_W), f64(o_ddx), f64(o_scal) + 2, 0, N, st));   // dense: the mean-depth row couples every pair of control points
+    else HIPCHK(c, nrsfm_swp_resolve(N, f64(o_g), f64(o_M), f64(o_W), f64(o_ddx), 0, N, st));
+    HIPCHK(c, nrsfm_sfn_axpy(N, f64(o_ddx), dx, st));
   }
-  std::vector<double> x((size_t)N);
-  double s8[8];
-  HIPCHK(c, hipMemcpyAsync(x.data(), dx.p, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(s8, dscal.p, 64, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (ctrl_raw) std::memcpy(ctrl_raw, x.data(), 8 * (size_t)N);
+  DownBlock down;
+  const size_t d_x = down.take(8 * Nz), d_s = down.take_exact(64);
+  if (const int rc = down.at(c, dx)) return rc;
+  if (const int rc = down.receive(c)) return rc;
+  const double *x = down.host<double>(d_x), *s8 = down.host<double>(d_s);
+  if (ctrl_raw) std::memcpy(ctrl_raw, x, 8 * Nz);
   const bool factor_ok = s8[2] != 0.0 || s8[3] != 0.0;   // out[0] also folds in "model > 0"; a positive-definite G always has it
   bool finite = true;
-  for (double t : x) finite = finite && std::isfinite(t);
+  for (int i = 0; i < N; i++) finite = finite && std::isfinite(x[i]);
   if (!factor_ok || !finite || n_all == 0) return DSH_OK;
   // the reference's scale: 1 / median of the float32 control points (ShapeFromNormals.cc:123-135)
-  std::vector<float> dvec((size_t)N);
+  std::vector<float> dvec(Nz);
   for (int i = 0; i < N; i++) dvec[i] = (float)x[i];
   std::sort(dvec.begin(), dvec.end());
   const float corr = 1 / dvec[dvec.size() / 2];
   for (int i = 0; i < N; i++) ctrl[i] = corr * x[i];
-  HIPCHK(c, hipMemcpyAsync(dctrl.p, ctrl, 8 * (size_t)N, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dua.p, u_all, 8 * (size_t)n_all, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dva.p, v_all, 8 * (size_t)n_all, hipMemcpyHostToDevice, st));
-  HIPCHK(c, nrsfm_sfn_points(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, dctrl.as<double>(), n_all, dua.as<double>(), dva.as<double>(),
-                             dpts.as<float>(), st));
-  HIPCHK(c, hipMemcpyAsync(pts, dpts.p, 12 * (size_t)n_all, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  // second pair (x is not read past this point: the blocks reuse the page-locked buffers)
+  const size_t na = (size_t)n_all;
+  UpBlock up2;
+  const size_t o_ctrl = up2.copy_of(ctrl, 8 * Nz), o_ua = up2.copy_of(u_all, 8 * na), o_va = up2.copy_of(v_all, 8 * na);
+  DownBlock down2;
+  const size_t d_pts = down2.copy_to(pts, 12 * na);
+  if (const int rc = up2.copy(c)) return rc;
+  if (const int rc = down2.alloc(c)) return rc;
+  HIPCHK(c, nrsfm_sfn_points(bbs_par(bbs, 1), up2.dev<double>(o_ctrl), n_all, up2.dev<double>(o_ua), up2.dev<double>(o_va), down2.dev<float>(d_pts), st));
+  if (const int rc = down2.receive(c)) return rc;
   *ok = 1;
   return DSH_OK;
 }
@@ -186,38 +192,40 @@ int dsh_warp_initialize(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp
   dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (const int rc = dsh_enter(c, "dsh_warp_initialize")) return rc;
-  if (!bbs_ok(bbs) || P <= 0 || !kp1 || !kp2 || !x || !ok) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: bad argument");
+  if (!bbs_grid_ok(bbs) || P <= 0 || !kp1 || !kp2 || !x || !ok) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: bad argument");
   const int N = bbs->nptsu * bbs->nptsv;
   if (N > 512) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: more than 512 control points (one-workgroup solve)");
   *ok = 0;
   hipStream_t st = c->stream;
-  const int np = nrsfm_swp_solve_np(N);
-  DevBuf dC, dr0, dr1, dG, dB, dg0, dg1, dM, dW, dx, dones, dscal, dk1, dk2;
-  HIPCHK(c, dC.alloc(c, 8 * (size_t)P * N)); HIPCHK(c, dr0.alloc(c, 8 * (size_t)P)); HIPCHK(c, dr1.alloc(c, 8 * (size_t)P));
-  HIPCHK(c, dG.alloc(c, 8 * (size_t)N * N)); HIPCHK(c, dB.alloc(c, 8 * (size_t)N * N)); HIPCHK(c, dg0.alloc(c, 8 * (size_t)N)); HIPCHK(c, dg1.alloc(c, 8 * (size_t)N));
-  HIPCHK(c, dM.alloc(c, 8 * (size_t)np * np)); HIPCHK(c, dW.alloc(c, 8 * (size_t)np * 16)); HIPCHK(c, dx.alloc(c, 8 * (size_t)2 * N));
-  HIPCHK(c, dones.alloc(c, 8 * (size_t)N)); HIPCHK(c, dscal.alloc(c, 256)); HIPCHK(c, dk1.alloc(c, 8 * (size_t)P)); HIPCHK(c, dk2.alloc(c, 8 * (size_t)P));
-  std::vector<double> Bm((size_t)N * N), ones((size_t)N, 1.0);
-  bending_dense(bbs, lambda, Bm.data());
-  HIPCHK(c, hipMemcpyAsync(dB.p, Bm.data(), 8 * Bm.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dones.p, ones.data(), 8 * (size_t)N, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dk1.p, kp1, 8 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dk2.p, kp2, 8 * (size_t)P, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(dC.p, 0, 8 * (size_t)P * N, st));
-  HIPCHK(c, hipMemsetAsync(dscal.p, 0, 256, st));
-  HIPCHK(c, nrsfm_warp_coloc(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, P, dk1.as<float>(), dk2.as<float>(), dC.as<double>(), dr0.as<double>(),
-                             dr1.as<double>(), st));
-  double* scal = dscal.as<double>();
+  const int np = nrsfm_swp_solve_np(N), kd = 3 * bbs->nptsv + 3;   // colocation and bending couple a 4 x 4 patch: banded
+  const size_t Nz = (size_t)N, Pz = (size_t)P;
+  UpBlock up;
+  const size_t o_B = up.take(8 * Nz * Nz), o_ones = up.take(8 * Nz), o_k1 = up.copy_of(kp1, 8 * Pz), o_k2 = up.copy_of(kp2, 8 * Pz);
+  Arena ws;   // x and the scalars of the solve are neighbours: the block down lies on them
+  const size_t o_C = ws.take(8 * Pz * Nz), o_r0 = ws.take(8 * Pz), o_r1 = ws.take(8 * Pz), o_G = ws.take(8 * Nz * Nz), o_g0 = ws.take(8 * Nz), o_g1 = ws.take(8 * Nz),
+               o_M = ws.take(8 * (size_t)np * np), o_W = ws.take(8 * (size_t)np * 16), o_x = ws.take(8 * 2 * Nz), o_scal = ws.take(256);
+  char* w = nullptr;
+  HIPCHK(c, c->scratch.take(ws.size, (void**)&w));
+  auto f64 = [&](size_t off) { return reinterpret_cast<double*>(w + off); };
+  if (const int rc = up.stage(c)) return rc;
+  bending_dense(bbs, lambda, up.host<double>(o_B));
+  std::fill_n(up.host<double>(o_ones), Nz, 1.0);
+  if (const int rc = up.send(c)) return rc;
+  HIPCHK(c, hipMemsetAsync(w + o_C, 0, 8 * Pz * Nz, st));
+  HIPCHK(c, hipMemsetAsync(w + o_scal, 0, 256, st));
+  HIPCHK(c, nrsfm_warp_coloc(bbs_par(bbs, 1), P, up.dev<float>(o_k1), up.dev<float>(o_k2), f64(o_C), f64(o_r0), f64(o_r1), st));
   // g1 = C^T (-q2y) first (G is rebuilt by the second call), then G = C^T C, g0 = C^T (-q2x); G += Bending
-  HIPCHK(c, nrsfm_swp_normal(P, N, dC.as<double>(), dr1.as<double>(), dones.as<double>(), dG.as<double>(), dg1.as<double>(), st));
-  HIPCHK(c, nrsfm_swp_normal(P, N, dC.as<double>(), dr0.as<double>(), dones.as<double>(), dG.as<double>(), dg0.as<double>(), st));
-  HIPCHK(c, nrsfm_mat_add((size_t)N * N, dB.as<double>(), dG.as<double>(), st));
-  HIPCHK(c, nrsfm_swp_solve(N, dG.as<double>(), dg0.as<double>(), 1e300, dM.as<double>(), dW.as<double>(), dx.as<double>(), scal + 2, 0, 3 * bbs->nptsv + 3, st));   // colocation and bending couple a 4 x 4 patch: banded
-  HIPCHK(c, nrsfm_swp_resolve(N, dg1.as<double>(), dM.as<double>(), dW.as<double>(), dx.as<double>() + N, 0, 3 * bbs->nptsv + 3, st));
-  double s8[8];
-  HIPCHK(c, hipMemcpyAsync(x, dx.p, 8 * (size_t)2 * N, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(s8, dscal.p, 64, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, nrsfm_swp_normal(P, N, f64(o_C), f64(o_r1), up.dev<double>(o_ones), f64(o_G), f64(o_g1), st));
+  HIPCHK(c, nrsfm_swp_normal(P, N, f64(o_C), f64(o_r0), up.dev<double>(o_ones), f64(o_G), f64(o_g0), st));
+  HIPCHK(c, nrsfm_mat_add(Nz * Nz, up.dev<double>(o_B), f64(o_G), st));
+  HIPCHK(c, nrsfm_swp_solve(N, f64(o_G), f64(o_g0), 1e300, f64(o_M), f64(o_W), f64(o_x), f64(o_scal) + 2, 0, kd, st));
+  HIPCHK(c, nrsfm_swp_resolve(N, f64(o_g1), f64(o_M), f64(o_W), f64(o_x) + N, 0, kd, st));
+  DownBlock down;
+  down.copy_to(x, 8 * 2 * Nz);
+  const size_t d_s = down.take_exact(64);
+  if (const int rc = down.at(c, w + o_x)) return rc;
+  if (const int rc = down.receive(c)) return rc;
+  const double* s8 = down.host<double>(d_s);
   bool finite = true;
   for (int i = 0; i < 2 * N; i++) finite = finite && std::isfinite(x[i]);
   *ok = ((s8[2] != 0.0 || s8[3] != 0.0) && finite) ? 1 : 0;
@@ -230,30 +238,24 @@ int dsh_search_by_schwarp(dsh_ctx* ctx, const dsh_bbs* bbs, const double* x, int
   dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
   if (const int rc = dsh_enter(c, "dsh_search_by_schwarp")) return rc;
-  if (!bbs_ok(bbs) || !x || Q < 0 || N2 < 0 || (Q > 0 && (!kp1 || !desc1 || !match)) || (N2 > 0 && (!kp2 || !desc2 || !has_mp2)) || !cam2 || !bounds2 ||
+  if (!bbs_grid_ok(bbs) || !x || Q < 0 || N2 < 0 || (Q > 0 && (!kp1 || !desc1 || !match)) || (N2 > 0 && (!kp2 || !desc2 || !has_mp2)) || !cam2 || !bounds2 ||
       grid_cols <= 0 || grid_rows <= 0 || grid_cols * grid_rows > 8192 || !(bounds2[1] > bounds2[0]) || !(bounds2[3] > bounds2[2]) || th_low > 256)
     return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_schwarp: bad argument");
   if (nmatches) *nmatches = 0;
   if (Q == 0) return DSH_OK;
-  hipStream_t st = c->stream;
-  const int N = bbs->nptsu * bbs->nptsv;
-  DevBuf dx, dk1, dd1, dk2, dd2, dmp, dcell, dmatch;
-  HIPCHK(c, dx.alloc(c, 8 * (size_t)2 * N)); HIPCHK(c, dk1.alloc(c, 8 * (size_t)Q)); HIPCHK(c, dd1.alloc(c, 32 * (size_t)Q));
-  HIPCHK(c, dk2.alloc(c, 8 * (size_t)N2)); HIPCHK(c, dd2.alloc(c, 32 * (size_t)N2)); HIPCHK(c, dmp.alloc(c, (size_t)N2));
-  HIPCHK(c, dcell.alloc(c, 4 * (size_t)N2)); HIPCHK(c, dmatch.alloc(c, 4 * (size_t)Q));
-  HIPCHK(c, hipMemcpyAsync(dx.p, x, 8 * (size_t)2 * N, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dk1.p, kp1, 8 * (size_t)Q, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(dd1.p, desc1, 32 * (size_t)Q, hipMemcpyHostToDevice, st));
-  if (N2 > 0) {
-    HIPCHK(c, hipMemcpyAsync(dk2.p, kp2, 8 * (size_t)N2, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(dd2.p, desc2, 32 * (size_t)N2, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(dmp.p, has_mp2, (size_t)N2, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, nrsfm_match_search(bbs->umin, bbs->umax, bbs->nptsu, bbs->vmin, bbs->vmax, bbs->nptsv, dx.as<double>(), Q, dk1.as<float>(), dd1.as<uint32_t>(), cam2,
-                               bounds2, grid_cols, grid_rows, N2, dk2.as<float>(), dd2.as<uint32_t>(), dmp.as<uint8_t>(), radius, th_low, dcell.as<int32_t>(),
-                               dmatch.as<int32_t>(), st));
-  HIPCHK(c, hipMemcpyAsync(match, dmatch.p, 4 * (size_t)Q, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  const size_t Nz = (size_t)bbs->nptsu * bbs->nptsv, Qz = (size_t)Q, N2z = (size_t)N2;
+  UpBlock up;
+  const size_t o_x = up.copy_of(x, 8 * 2 * Nz), o_k1 = up.copy_of(kp1, 8 * Qz), o_d1 = up.copy_of(desc1, 32 * Qz), o_k2 = up.copy_of(kp2, 8 * N2z),
+               o_d2 = up.copy_of(desc2, 32 * N2z), o_mp = up.copy_of(has_mp2, N2z);
+  DownBlock down;
+  const size_t d_match = down.copy_to(match, 4 * Qz);
+  int32_t* dcell = nullptr;
+  HIPCHK(c, dsh_scratch_array(c, &dcell, N2z));
+  if (const int rc = up.copy(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  HIPCHK(c, nrsfm_match_search(bbs_par(bbs, 2), up.dev<double>(o_x), Q, up.dev<float>(o_k1), up.dev<uint32_t>(o_d1), cam2, bounds2, grid_cols, grid_rows, N2,
+                               up.dev<float>(o_k2), up.dev<uint32_t>(o_d2), up.dev<uint8_t>(o_mp), radius, th_low, dcell, down.dev<int32_t>(d_match), c->stream));
+  if (const int rc = down.receive(c)) return rc;
   if (nmatches) {
     int n = 0;
     for (int q = 0; q < Q; q++) n += match[q] >= 0;

@@ -58,7 +58,7 @@ int dsh_surface_vertices(const dsh_surface_grid* grid, double* nodes_xyz) {
   if (!c) return DSH_ERR_ARG;
   auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, "dsh_surface_vertices: " + m); };
   const dsh_bbs* b = grid->bbs;
-  if (!b || b->nptsu < 4 || b->nptsv < 4 || !(b->umax > b->umin) || !(b->vmax > b->vmin)) return bad("bad B-spline");
+  if (!bbs_grid_ok(b)) return bad("bad B-spline");
   if (b->valdim != 1) return bad("the depth spline has valdim 1");
   if (!grid->depth_ctrl || !grid->Twc || !nodes_xyz) return bad("depth_ctrl, Twc or nodes_xyz is NULL");
   if (grid->xs < 2 || grid->ys < 2) return bad("xs and ys must be at least 2");
@@ -86,7 +86,7 @@ int dsh_surface_vertices(const dsh_surface_grid* grid, double* nodes_xyz) {
   if (const int rc = down.alloc(c)) return rc;
   double* d_val = nullptr;
   HIPCHK(c, dsh_scratch_array(c, &d_val, n));
-  HIPCHK(c, nrsfm_launch_bbs_eval(b->umin, b->umax, b->nptsu, b->vmin, b->vmax, b->nptsv, 1, up.dev<const double>(o_ctrl), up.dev<const double>(o_u),
+  HIPCHK(c, nrsfm_launch_bbs_eval(bbs_par(b, 1), up.dev<const double>(o_ctrl), up.dev<const double>(o_u),
                                   up.dev<const double>(o_v), (int)n, 0, 0, d_val, nullptr, c->stream));
   HIPCHK(c, ts_vertices_launch(up.dev<const double>(o_u), up.dev<const double>(o_v), d_val, up.dev<const float>(o_T), (int)n, down.dev<double>(d_xyz),
                                c->stream));

@@ -21,10 +21,8 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// B-spline
+// B-spline (the grid record BbsPar: mapping_launch.h)
 // ------------------------------------------------------------------------------------------------
-struct BbsPar { double umin, umax, vmin, vmax; int nptsu, nptsv, valdim, pad; };
-
 __device__ __forceinline__ void norm_inter(double xmin, double xmax, int npts, double x, double& nx, int& inter) {
   const int ninter = npts - 3;
   const double width = (xmax - xmin) / ninter;
@@ -1624,10 +1622,8 @@ __global__ void swpb_ctl_kernel(SwpFit* fits, int B, int phase) {
 }  // namespace
 
 // ---- launchers, declared in mapping_launch.h / schwarp_problem.h: B-spline and normals (dsh_nrsfm.cpp, dsh_diffdb.cpp) ----------
-extern "C" hipError_t nrsfm_launch_bbs_eval(double umin, double umax, int nptsu, double vmin, double vmax, int nptsv, int valdim, const double* ctrl,
-                                            const double* u, const double* v, int n, int du, int dv, double* val, uint8_t* outside, hipStream_t st) {
-  BbsPar p = {umin, umax, vmin, vmax, nptsu, nptsv, valdim, 0};
-  const size_t bytes = sizeof(double) * (size_t)valdim * nptsu * nptsv;
+extern "C" hipError_t nrsfm_launch_bbs_eval(BbsPar p, const double* ctrl, const double* u, const double* v, int n, int du, int dv, double* val, uint8_t* outside, hipStream_t st) {
+  const size_t bytes = sizeof(double) * (size_t)p.valdim * p.nptsu * p.nptsv;
   const int use_lds = bytes <= 64 * 1024;
   const int block = 256;
   const int grid = n > 0 ? (n + block - 1) / block : 1;
@@ -1635,9 +1631,7 @@ extern "C" hipError_t nrsfm_launch_bbs_eval(double umin, double umax, int nptsu,
   return hipGetLastError();
 }
 
-extern "C" hipError_t nrsfm_launch_bbs_coloc(double umin, double umax, int nptsu, double vmin, double vmax, int nptsv, const double* u, const double* v,
-                                             int n, int du, int dv, int32_t* cols, double* w, int32_t* n_outside, hipStream_t st) {
-  BbsPar p = {umin, umax, vmin, vmax, nptsu, nptsv, 1, 0};
+extern "C" hipError_t nrsfm_launch_bbs_coloc(BbsPar p, const double* u, const double* v, int n, int du, int dv, int32_t* cols, double* w, int32_t* n_outside, hipStream_t st) {
   const int block = 256;
   const int grid = n > 0 ? (n + block - 1) / block : 1;
   hipLaunchKernelGGL(bbs_coloc_kernel, dim3(grid < 2048 ? grid : 2048), dim3(block), 0, st, p, u, v, n, du, dv, cols, w, n_outside);
@@ -1660,9 +1654,9 @@ extern "C" hipError_t nrsfm_launch_normals(int P, int R, const int32_t* rec_ptr,
 }
 
 // ---- Schwarp: one evaluation (dsh_schwarp.cpp), the dense normal equations and the solver (dsh_sfn.cpp), the batched fit (dsh_schwarp.cpp) ----
-extern "C" hipError_t nrsfm_swp_eval(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, double fxs, double fys, double lambda,
-                                     const float* kp1, const float* kp2, const float* invsig, const double* x, double* r, double* J, int with_j, hipStream_t st) {
-  SwpPar p = {umin, umax, vmin, vmax, fxs, fys, lambda, nu, nv, nu * nv, P};
+extern "C" hipError_t nrsfm_swp_eval(BbsPar b, int P, double fxs, double fys, double lambda, const float* kp1, const float* kp2, const float* invsig, const double* x,
+                                     double* r, double* J, int with_j, hipStream_t st) {
+  SwpPar p = {b.umin, b.umax, b.vmin, b.vmax, fxs, fys, lambda, b.nptsu, b.nptsv, b.nptsu * b.nptsv, P};
   const int tot = P + p.N, block = 128;
   if (with_j) {
     hipError_t e = hipMemsetAsync(J, 0, sizeof(double) * (size_t)(2 * P + 4 * p.N) * 2 * p.N, st);
@@ -1764,10 +1758,8 @@ extern "C" hipError_t nrsfm_swp_resolve(int n2, const double* g, const double* M
   hipLaunchKernelGGL(swp_resolve_kernel, dim3(1), dim3(512), 0, st, n2, np, interleave, bwt, g, M, Winv, dx);
   return hipGetLastError();
 }
-extern "C" hipError_t nrsfm_sfn_rows(double umin, double umax, int nu, double vmin, double vmax, int nv, int n, const double* u, const double* v,
-                                     const float* normals, double* A, hipStream_t st) {
-  BbsPar p = {umin, umax, vmin, vmax, nu, nv, 1, 0};
-  if (n > 0) hipLaunchKernelGGL(sfn_rows_kernel, dim3((n + 127) / 128), dim3(128), 0, st, p, n, u, v, normals, nu * nv, A);
+extern "C" hipError_t nrsfm_sfn_rows(BbsPar p, int n, const double* u, const double* v, const float* normals, double* A, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(sfn_rows_kernel, dim3((n + 127) / 128), dim3(128), 0, st, p, n, u, v, normals, p.nptsu * p.nptsv, A);
   return hipGetLastError();
 }
 extern "C" hipError_t nrsfm_sfn_residual(int m, int N, const double* A, const double* x, const double* b, double sign, double* out, hipStream_t st) {
@@ -1778,17 +1770,13 @@ extern "C" hipError_t nrsfm_sfn_axpy(int n, const double* dx, double* x, hipStre
   hipLaunchKernelGGL(sfn_axpy_kernel, dim3((n + 127) / 128), dim3(128), 0, st, n, dx, x);
   return hipGetLastError();
 }
-extern "C" hipError_t nrsfm_sfn_points(double umin, double umax, int nu, double vmin, double vmax, int nv, const double* ctrl, int n, const double* u,
-                                       const double* v, float* pts, hipStream_t st) {
-  BbsPar p = {umin, umax, vmin, vmax, nu, nv, 1, 0};
+extern "C" hipError_t nrsfm_sfn_points(BbsPar p, const double* ctrl, int n, const double* u, const double* v, float* pts, hipStream_t st) {
   if (n > 0) hipLaunchKernelGGL(sfn_points_kernel, dim3((n + 127) / 128), dim3(128), 0, st, p, ctrl, n, u, v, pts);
   return hipGetLastError();
 }
 
-extern "C" hipError_t nrsfm_warp_coloc(double umin, double umax, int nu, double vmin, double vmax, int nv, int P, const float* kp1, const float* kp2, double* Cm,
-                                       double* rhs0, double* rhs1, hipStream_t st) {
-  BbsPar p = {umin, umax, vmin, vmax, nu, nv, 1, 0};
-  hipLaunchKernelGGL(warp_coloc_kernel, dim3((P + 127) / 128), dim3(128), 0, st, p, P, kp1, kp2, nu * nv, Cm, rhs0, rhs1);
+extern "C" hipError_t nrsfm_warp_coloc(BbsPar p, int P, const float* kp1, const float* kp2, double* Cm, double* rhs0, double* rhs1, hipStream_t st) {
+  hipLaunchKernelGGL(warp_coloc_kernel, dim3((P + 127) / 128), dim3(128), 0, st, p, P, kp1, kp2, p.nptsu * p.nptsv, Cm, rhs0, rhs1);
   return hipGetLastError();
 }
 extern "C" hipError_t nrsfm_mat_add(size_t n, const double* B, double* A, hipStream_t st) {
@@ -1796,10 +1784,9 @@ extern "C" hipError_t nrsfm_mat_add(size_t n, const double* B, double* A, hipStr
   return hipGetLastError();
 }
 
-extern "C" hipError_t nrsfm_match_search(double umin, double umax, int nu, double vmin, double vmax, int nv, const double* x, int Q, const float* kp1,
-                                         const uint32_t* desc1, const float* cam2, const float* bounds2, int cols, int rows, int N2, const float* kp2,
-                                         const uint32_t* desc2, const uint8_t* has_mp2, float radius, int th_low, int32_t* cell, int32_t* match, hipStream_t st) {
-  BbsPar b = {umin, umax, vmin, vmax, nu, nv, 2, 0};
+extern "C" hipError_t nrsfm_match_search(BbsPar b, const double* x, int Q, const float* kp1, const uint32_t* desc1, const float* cam2, const float* bounds2, int cols,
+                                         int rows, int N2, const float* kp2, const uint32_t* desc2, const uint8_t* has_mp2, float radius, int th_low, int32_t* cell,
+                                         int32_t* match, hipStream_t st) {
   MatchPar p;
   p.fx = cam2[0]; p.fy = cam2[1]; p.cx = cam2[2]; p.cy = cam2[3];
   p.minX = bounds2[0]; p.maxX = bounds2[1]; p.minY = bounds2[2]; p.maxY = bounds2[3];
