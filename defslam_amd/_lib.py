@@ -132,6 +132,13 @@ class TrackEndCountsC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("cleaned", "dropped", "kept")]
 
 
+class PoseOnlyProblemC(C.Structure):
+    _fields_ = [("Tcw", c_float_p), ("K", C.c_float * 4), ("N", C.c_int32), ("kp", c_float_p), ("octave", c_i32_p), ("levels", C.c_int32),
+                ("inv_level_sigma2", c_float_p), ("frame_points", c_i32_p), ("outlier", c_u8_p), ("Tcw_out", C.c_float * 16),
+                ("pose", C.c_double * 7), ("n_initial", C.c_int32), ("n_bad", C.c_int32), ("n_good", C.c_int32), ("rounds", C.c_int32),
+                ("iters", C.c_int32 * 4), ("trials", C.c_int32 * 4), ("bad", C.c_int32 * 4), ("chi2", C.c_double * 4)]
+
+
 class KfKeypointsC(C.Structure):
     _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("N", C.c_int32), ("kp", c_float_p)]
 
@@ -206,6 +213,7 @@ EXPORTED_SYMBOLS = [
     "dsh_trackstate_set_embedding", "dsh_trackstate_clear_embedding", "dsh_trackstate_set_counters", "dsh_trackstate_get",
     "dsh_trackstate_seed_local_points", "dsh_trackstate_repose", "dsh_trackstate_cull", "dsh_track_close_frame",
     "dsh_track_end_frame", "dsh_track_last_frame", "dsh_motion_model_search",
+    "dsh_track_pose_only", "dsh_track_pose_only_batch",
     "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
     "dsh_point_store_add_observations_indexed", "dsh_point_store_set_reference_keyframes", "dsh_point_store_get_reference_keyframes", "dsh_keyframe_anchors",
     "dsh_keyframe_process_new", "dsh_point_store_upkeep",
@@ -344,6 +352,8 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_track_end_frame.argtypes = [vp, C.c_int, c_i32_p, c_u8_p, c_i32_p, c_i32_p, c_u8_p, C.POINTER(TrackEndCountsC)]
     L.dsh_track_last_frame.argtypes = [vp, i32, c_i32_p, c_i32_p, c_i32_p]
     L.dsh_motion_model_search.argtypes = [vp, C.POINTER(TrackFrameC), C.c_float, C.c_float, i32, c_i32_p, c_i32_p, c_i32_p, c_float_p]
+    L.dsh_track_pose_only.argtypes = [vp, C.POINTER(PoseOnlyProblemC)]
+    L.dsh_track_pose_only_batch.argtypes = [vp, C.c_int, C.POINTER(PoseOnlyProblemC)]
     L.dsh_surface_vertices.argtypes = [C.POINTER(SurfaceGridC), c_double_p]
     L.dsh_need_new_template.argtypes = [vp, i32, C.POINTER(KfKeypointsC), c_i32_p, c_u8_p]
     L.dsh_template_switch.argtypes = [vp, C.POINTER(TemplateSwitchInputC), c_i32_p, C.POINTER(TemplateSwitchCountsC)]

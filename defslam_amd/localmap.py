@@ -113,6 +113,34 @@ class MotionModelSearch:
 
 
 @dataclass
+class PoseOnlyFrame:
+    """What dsh_track_pose_only reads of a frame (ORB_SLAM2::Optimizer::poseOptimization, monocular)."""
+    Tcw: np.ndarray                     # (4,4) float32 mTcw
+    K: np.ndarray                       # fx, fy, cx, cy
+    kp: np.ndarray                      # (N,2) float32 mvKeysUn
+    octave: np.ndarray                  # (N,) mvKeysUn[i].octave
+    inv_level_sigma2: np.ndarray        # (levels,) float32 mvInvLevelSigma2
+    frame_points: np.ndarray            # (N,) mvpMapPoints as ids or -1
+    outlier: Optional[np.ndarray] = None   # (N,) mvbOutlier on entry (None: all False); kept where no point is held
+
+
+@dataclass
+class PoseOnly:
+    """What dsh_track_pose_only returns."""
+    outlier: np.ndarray                 # (N,) bool mvbOutlier: written where a point is held
+    Tcw: np.ndarray                     # (4,4) float32: the pose SetPose receives; the input pose when n_initial < 3
+    pose: np.ndarray                    # (7,) t, q (x y z w) of the recovered SE3Quat
+    n_initial: int
+    n_bad: int                          # nBad of the last round run
+    n_good: int                         # the return value
+    rounds: int                         # 0, 1 or 4
+    iters: np.ndarray                   # (4,) outer iterations per round
+    trials: np.ndarray                  # (4,) damping trials per round
+    bad: np.ndarray                     # (4,) nBad after each round
+    chi2: np.ndarray                    # (4,) active robust chi2 of the last accepted state per round
+
+
+@dataclass
 class StoredPoints:
     """What dsh_point_store_get_points returns, per id asked for."""
     xyz: np.ndarray                     # (n,3) float32 mWorldPos
@@ -489,6 +517,41 @@ class MapPointStore:
         self._call("dsh_motion_model_search", C.byref(f), float(th), float(th_wide), int(min_matches), _ptr(fp, C.c_int32), _ptr(match, C.c_int32),
                    C.byref(nm), C.byref(used))
         return MotionModelSearch(frame_points=fp[:N], match=match[:NL], nmatches=int(nm.value), th_used=float(used.value), ok=nm.value >= 15)
+
+    # ---- the rigid pose-only optimisation (the else branch of TrackLocalMap) ----
+    def pose_only_batch(self, frames, _single: bool = False) -> list:
+        """ORB_SLAM2::Optimizer::poseOptimization for each PoseOnlyFrame of `frames` against the store's positions, in one launch."""
+        B = len(frames)
+        probs = (_lib.PoseOnlyProblemC * max(B, 1))()
+        keep = []
+        for p, f in zip(probs, frames):
+            fp = _i32(f.frame_points)
+            N = fp.shape[0]
+            T = np.ascontiguousarray(f.Tcw, np.float32).reshape(16)
+            kp = np.ascontiguousarray(f.kp, np.float32).reshape(N, 2)
+            oc = _i32(f.octave).reshape(N)
+            sg = np.ascontiguousarray(f.inv_level_sigma2, np.float32).reshape(-1)
+            fl = np.zeros(max(N, 1), np.uint8)
+            if f.outlier is not None:
+                fl[:N] = np.asarray(f.outlier, bool).reshape(N)
+            keep.append((T, kp, oc, sg, fp, fl))
+            p.Tcw, p.kp, p.octave = _ptr(T, C.c_float), _ptr(kp, C.c_float), _ptr(oc, C.c_int32)
+            p.K = (C.c_float * 4)(*[float(v) for v in np.asarray(f.K).reshape(4)])
+            p.N, p.levels = N, int(sg.shape[0])
+            p.inv_level_sigma2, p.frame_points, p.outlier = _ptr(sg, C.c_float), _ptr(fp, C.c_int32), _ptr(fl, C.c_uint8)
+        if _single:
+            self._call("dsh_track_pose_only", C.byref(probs[0]))
+        else:
+            self._call("dsh_track_pose_only_batch", B, probs)
+        return [PoseOnly(outlier=k[5][:int(p.N)].astype(bool), Tcw=np.array(p.Tcw_out, np.float32).reshape(4, 4), pose=np.array(p.pose, float),
+                         n_initial=int(p.n_initial), n_bad=int(p.n_bad), n_good=int(p.n_good), rounds=int(p.rounds),
+                         iters=np.array(p.iters, np.int32), trials=np.array(p.trials, np.int32), bad=np.array(p.bad, np.int32),
+                         chi2=np.array(p.chi2, float)) for p, k in zip(probs[:B], keep)]
+
+    def pose_only(self, Tcw, K, kp, octave, inv_level_sigma2, frame_points, outlier=None) -> PoseOnly:
+        """One frame: Tcw (4,4) float32, K = fx fy cx cy, kp (N,2) mvKeysUn, octave (N,), inv_level_sigma2 (levels,), frame_points (N,)
+        ids or -1.  The positions are the store's; nothing of the store changes."""
+        return self.pose_only_batch([PoseOnlyFrame(Tcw, K, kp, octave, inv_level_sigma2, frame_points, outlier)], _single=True)[0]
 
     # ---- the template switch ----
     def get_points(self, ids=None) -> StoredPoints:

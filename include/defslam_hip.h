@@ -779,6 +779,65 @@ int dsh_track_last_frame(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* 
 int dsh_motion_model_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, float th_wide, int32_t min_matches, int32_t* frame_points,
                             int32_t* match, int32_t* nmatches, float* th_used);
 
+/* ---- tracking: the rigid pose-only optimisation of a frame from the resident map point store -----------------------------------
+ * The else branch of DefTracking::TrackLocalMap (Modules/Tracking/DefTracking.cc:250), which runs while the map has no template, and
+ * what Tracking::Relocalization and TrackReferenceKeyFrame call: ORB_SLAM2::Optimizer::poseOptimization(Frame*)
+ * (Thirdparty/ORBSLAM_2/src/Optimizer.cc:236-445), monocular branch only (mvuRight < 0 always holds here: no stereo branch).  One SE3
+ * vertex, one unary reprojection edge (EdgeSE3ProjectXYZOnlyPose, types_six_dof_expmap.h:143-172, .cpp:266-296) per key point that
+ * holds a point; the positions are read from the store by id on the device, nothing per map point crosses the bus.
+ *   Edges (:276-315): every key point with frame_points[i] >= 0, in index order; there is no bad test, and an id may be held by several
+ *     key points (one edge each).  outlier[i] is cleared first.  Xw = the store's float32 position, measurement = the float32 key
+ *     point, both widened to double; information = I2 * (double)inv_level_sigma2[octave[i]] (no division by N); Huber with
+ *     delta = (float)sqrt(5.991) (robust_kernel_impl.cpp:78-91).
+ *   Early return (:358-359): n_initial < 3 returns n_good = 0 with rounds = 0; Tcw_out and pose are the input pose, the flags stay 0.
+ *   Four rounds (:368-436).  Each restarts from the input pose (Converter::toSE3Quat of the float32 matrix, :371) with the edges at
+ *     level 0, i.e. those not flagged, and runs optimize(10): g2o's Levenberg-Marquardt (optimization_algorithm_levenberg.cpp:61-164)
+ *     with lambda = 1e-5 * max|diag H| at the round's first iteration, at most 10 trials per iteration, the accept / reject rule, the
+ *     stops on 10 trials, rho == 0 and _nBad >= 3; the 6x6 system goes through LinearSolverDense (Eigen's pivoted LDLT on H + lambda I,
+ *     block_solver.hpp:356-365: no landmark vertex, no Schur complement), a factor that is not positive makes the trial's chi2 DBL_MAX;
+ *     the update is SE3Quat::exp(dx) * estimate (se3quat.h:223-257).  A round without a level-0 edge does not optimise
+ *     (sparse_optimizer.cpp:405-409): its estimate is the input pose.
+ *   Classification after a round (:376-403): an edge flagged outlier recomputes its error at the round's estimate; an inlier edge keeps
+ *     the error of the last trial evaluated, also when that trial was rejected and popped (the quirk of DefOptimizer.cc:515-537).
+ *     chi2 = e' Omega e rounded to float, outlier when > 5.991f; outliers go to level 1, inliers to level 0.  After round index 2 the
+ *     robust kernel is removed from every edge: round 3 is plain least squares.
+ *   The break (:434-435) counts all edges: n_initial in 3 .. 9 runs one round, n_initial >= 10 runs four.
+ *   Result (:439-444): Tcw_out = Converter::toCvMat(estimate) in float32, n_good = n_initial - n_bad of the last round run.
+ * Arithmetic: double throughout.  The sums over the edges of a linearisation (the 21 entries of the triangle of J' rho Omega J that
+ * the factorisation reads, the 6 of the right-hand side, the robust chi2) are taken in a fixed order that depends on N alone (DESIGN
+ * 4.6), not in edge order: the result is a function of the inputs, equal from run to run and from batch to single call, and differs
+ * from a sequential evaluation by the reassociation of those sums.
+ * Not covered: a point at or behind the camera plane, or any other non-finite residual.  The call then still returns a status and
+ * does not fault, but the numbers it produces are not part of the contract.
+ * Discipline of the other store calls: arguments are checked on the host first -- NULL arrays with N > 0, N outside 0 .. 8192, levels
+ * outside 1 .. 32, an octave outside 0 .. levels-1, an id that is neither -1 nor a point of the store, B outside 0 .. 65536 -- and DSH_ERR_ARG names
+ * the entry, nothing is written; then a host-only context answers DSH_ERR_NO_DEVICE; a detached store answers DSH_ERR_ARG.  The call
+ * changes nothing in the store. */
+typedef struct dsh_pose_only_problem {
+  const float* Tcw;                 /* in: 4x4 row-major float32, pFrame->mTcw */
+  float K[4];                       /* in: fx, fy, cx, cy */
+  int32_t N;                        /* in: key points, 0 .. 8192 */
+  const float* kp;                  /* in: N x 2 mvKeysUn */
+  const int32_t* octave;            /* in: N, read where frame_points[i] >= 0 */
+  int32_t levels;                   /* in: 1 .. 32 */
+  const float* inv_level_sigma2;    /* in: levels, mvInvLevelSigma2 (ORBextractor.cc:430, float32) */
+  const int32_t* frame_points;      /* in: N, mvpMapPoints as store ids, -1 = none */
+  uint8_t* outlier;                 /* in/out: N, mvbOutlier; written only where frame_points[i] >= 0 (Optimizer.cc:285, :391-397) */
+  float Tcw_out[16];                /* out: SetPose(Converter::toCvMat(...)); the input pose when n_initial < 3 */
+  double pose[7];                   /* out: t, q (x y z w) of the recovered SE3Quat */
+  int32_t n_initial, n_bad, n_good; /* out: nInitialCorrespondences, nBad of the last round run, the return value */
+  int32_t rounds;                   /* out: rounds run: 0, 1 or 4 */
+  int32_t iters[4], trials[4], bad[4];  /* out, per round: outer iterations, damping trials over all of them, nBad after it */
+  double chi2[4];                   /* out, per round: the active robust chi2 of the last accepted state (0 for a round that did not optimise) */
+} dsh_pose_only_problem;
+/* One frame: dsh_track_pose_only_batch with B = 1. */
+int dsh_track_pose_only(dsh_mpdb* db, dsh_pose_only_problem* p);
+/* B frames against the same store (relocalisation candidates, an offline re-track): one upload of the poses, key points, octaves,
+ * sigma tables and ids of the whole batch, one launch with one workgroup per problem that runs all rounds, their classifications and
+ * the float32 conversion, one download of the flags and the result records.  A problem's result is that of its single call, bit for
+ * bit.  B = 0 does nothing. */
+int dsh_track_pose_only_batch(dsh_mpdb* db, int B, dsh_pose_only_problem* problems);
+
 /* ---- mapping meets tracking: the template switch on the resident map point store -----------------------------------------------
  * DefLocalMapping::updateTemplate (Modules/Mapping/DefLocalMapping.cc:138-153), which DefTracking::Track calls on the tracking thread
  * (Modules/Tracking/DefTracking.cc:109) in front of the frame's two pose optimisations, and the mapping thread's trigger

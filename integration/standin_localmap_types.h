@@ -126,6 +126,12 @@ class LmFrame {                                // Thirdparty/ORBSLAM_2/include/F
   std::vector<float> mvScaleFactors;                                    // :193
   unsigned long mnId = 0;                                               // :184
   LmKeyFrame* mpReferenceKF = nullptr;                                  // :187
+  // what ORB_SLAM2::Optimizer::poseOptimization touches besides the above (pose_only_hip.h)
+  std::vector<float> mvInvLevelSigma2;                                  // :195
+  void SetPose(const float* Tcw) {                                      // :66 (Frame.cc:261-275: mTcw, then UpdatePoseMatrices)
+    for (int i = 0; i < 16; i++) mTcw[i] = Tcw[i];
+    for (int i = 0; i < 3; i++) mOw[i] = -(mTcw[i] * mTcw[3] + mTcw[4 + i] * mTcw[7] + mTcw[8 + i] * mTcw[11]);
+  }
 };
 
 }  // namespace standin
