@@ -545,6 +545,21 @@ def optimize_horn(pts1, pts2, sim3_init, chi, huber=0.01, device_sum_order=False
     return dict(ok=bool(ok), sim3=s, chi2=chi2.value, count=count.value, iters=iters, trials=trials)
 
 
+HORN_COUNTERS = ("exp_both_small", "exp_sigma_small", "exp_theta_small", "exp_general", "quat_trace", "quat_i0", "quat_i1", "quat_i2",
+                 "trial_rejected", "trials_exhausted", "stop_nbad", "ldlt_not_ok", "total_not_finite")
+
+
+def horn_counts(reset=False):
+    """Path counters of horn_oracle.c since the last reset, by name: the branch of sim3_exp, the arm quat_from_R takes for its rotation,
+    rejected damping trials, iterations that end on ten of them, the nBad >= 3 stop, an LDLT that is not positive, the non-finite total."""
+    L = lib()
+    out = (C.c_long * len(HORN_COUNTERS))()
+    L.horn_oracle_counts(out)
+    if reset:
+        L.horn_oracle_counts_reset()
+    return dict(zip(HORN_COUNTERS, (int(v) for v in out)))
+
+
 def horn_compose(sim3, Twc):
     """Tail of SurfaceRegistration::registerSurfaces: (s22, new Tcw float32 4x4)."""
     L = lib()

@@ -24,6 +24,18 @@
 
 typedef struct { quat_t r; double t[3]; double s; } sim3_t;
 
+/* Path counters (tests/register_cases.py names them in this order): which branches a run took.  They only count; no result
+ * depends on them.  Not thread safe: one caller at a time. */
+enum {
+  HC_EXP_BOTH_SMALL, HC_EXP_SIGMA_SMALL, HC_EXP_THETA_SMALL, HC_EXP_GENERAL,   /* the four branches of sim3_exp */
+  HC_QUAT_TRACE, HC_QUAT_I0, HC_QUAT_I1, HC_QUAT_I2,                           /* the arm quat_from_R takes for sim3_exp's R */
+  HC_TRIAL_REJECTED, HC_TRIALS_EXHAUSTED, HC_STOP_NBAD, HC_LDLT_NOT_OK, HC_TOTAL_NOT_FINITE,
+  HC_COUNT
+};
+static long horn_counts[HC_COUNT];
+void horn_oracle_counts(long* out) { for (int i = 0; i < HC_COUNT; i++) out[i] = horn_counts[i]; }
+void horn_oracle_counts_reset(void) { for (int i = 0; i < HC_COUNT; i++) horn_counts[i] = 0; }
+
 static void mat3_add3(const double* A, double a, const double* B, double b, const double* C, double c, double* O) {
   /* (a*A + b*B) + c*C elementwise, the order Eigen's expression tree evaluates */
   for (int i = 0; i < 9; i++) O[i] = (a * A[i] + b * B[i]) + c * C[i];
@@ -45,10 +57,12 @@ static sim3_t sim3_exp(const double u[7]) {
   if (fabs(sigma) < eps) {
     C = 1;
     if (theta < eps) {
+      horn_counts[HC_EXP_BOTH_SMALL]++;
       A = 1. / 2.;
       B = 1. / 6.;
       for (int i = 0; i < 9; i++) R[i] = (I3[i] + Om[i]) + Om2[i];
     } else {
+      horn_counts[HC_EXP_SIGMA_SMALL]++;
       const double theta2 = theta * theta;
       A = (1 - cos(theta)) / (theta2);
       B = (theta - sin(theta)) / (theta2 * theta);
@@ -58,11 +72,13 @@ static sim3_t sim3_exp(const double u[7]) {
   } else {
     C = (S.s - 1) / sigma;
     if (theta < eps) {
+      horn_counts[HC_EXP_THETA_SMALL]++;
       const double sigma2 = sigma * sigma;
       A = ((sigma - 1) * S.s + 1) / sigma2;
       B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
       for (int i = 0; i < 9; i++) R[i] = (I3[i] + Om[i]) + Om2[i];
     } else {
+      horn_counts[HC_EXP_GENERAL]++;
       const double ra = sin(theta) / theta, rb = (1 - cos(theta)) / (theta * theta);
       for (int i = 0; i < 9; i++) R[i] = (I3[i] + ra * Om[i]) + rb * Om2[i];
       const double a = S.s * sin(theta);
@@ -73,6 +89,14 @@ static sim3_t sim3_exp(const double u[7]) {
       A = (a * sigma + (1 - b) * theta) / (theta * c);
       B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
     }
+  }
+  /* the arm quat_from_R (small_algebra.h) is about to take, by its own tests */
+  if (R[0] + R[4] + R[8] > 0.0) horn_counts[HC_QUAT_TRACE]++;
+  else {
+    int qi = 0;
+    if (R[4] > R[0]) qi = 1;
+    if (R[8] > R[qi * 3 + qi]) qi = 2;
+    horn_counts[HC_QUAT_I0 + qi]++;
   }
   S.r = quat_from_R(R);
   mat3_add3(Om, A, Om2, B, I3, C, W);
@@ -297,6 +321,7 @@ static void horn_lm(horn_t* g, int max_iters, int32_t* iters, int32_t* trials) {
       memcpy(Hs, H, sizeof(H));
       for (int j = 0; j < 7; j++) Hs[j + 7 * j] += lambda;
       const int ok = ldlt_pivoted(Hs, 7, perm, tmp);
+      if (!ok) horn_counts[HC_LDLT_NOT_OK]++;
       if (ok) ldlt_pivoted_solve(Hs, 7, perm, b, x);
       { const sim3_t up = sim3_exp(x); g->est = sim3_mul(&up, &g->est); }
       horn_errors(g);
@@ -315,14 +340,16 @@ static void horn_lm(horn_t* g, int max_iters, int32_t* iters, int32_t* trials) {
       } else {
         lambda *= ni; ni *= 2;
         g->est = bak;
+        horn_counts[HC_TRIAL_REJECTED]++;
       }
       qmax++;
     } while (rho < 0 && qmax < maxTrials);
     total_trials += qmax;
     it_count++;
+    if (qmax == maxTrials) horn_counts[HC_TRIALS_EXHAUSTED]++;
     if (qmax == maxTrials || rho == 0) break;
     if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-    if (nBad >= 3) break;
+    if (nBad >= 3) { horn_counts[HC_STOP_NBAD]++; break; }
   }
   *iters = it_count;
   *trials = total_trials;
@@ -352,7 +379,7 @@ int horn_oracle_optimize(int n, const float* pts1, const float* pts2, double* si
   if (chi2_final) *chi2_final = total;
   if (count_out) *count_out = count;
   free(g.err); free(g.term);
-  if (isnan(total) || isinf(total)) return 0;
+  if (isnan(total) || isinf(total)) { horn_counts[HC_TOTAL_NOT_FINITE]++; return 0; }
   return (total / count < chi);
 }
 

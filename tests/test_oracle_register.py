@@ -5,6 +5,8 @@ import pytest
 from scipy.linalg import expm
 from scipy.spatial.transform import Rotation as Rot
 
+from register_cases import smm_numpy as _smm_numpy
+
 
 def _skew(w):
     return np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
@@ -67,47 +69,6 @@ def test_optimize_horn_recovers_a_known_similarity(oracle_mod):
     r = oracle_mod.optimize_horn(sc["surface"], sc["map"], [0, 0, 0, 1, 0, 0, 0, 1.2], chi=0.05 ** 2)
     assert abs(r["sim3"][7] - 1.3) < 0.02 and 350 < r["count"] < 500
     assert r["iters"][0] >= 3 and r["trials"].sum() >= r["iters"].sum()
-
-
-def _smm_numpy(mono, stereo, u):
-    """Independent restatement with numpy sorting (float32 where the reference has float)."""
-    n = mono.shape[0]
-    k = 0
-    min_med = np.float32(10000.0)
-    best = 0.0
-    final_points = 0
-    for i in range(n):
-        r = u[k]; k += 1
-        if r > 0.25:
-            continue
-        scale = float(np.float32(stereo[i, 2]) / np.float32(mono[i, 2]))
-        draws = u[k:k + n - 1]; k += n - 1
-        sel = np.ones(n, bool); sel[i] = False
-        sel[np.arange(n) != i] = ~(draws > 0.25)
-        d = scale * mono[sel].astype(np.float64) - stereo[sel].astype(np.float64)
-        r2 = np.zeros(d.shape[0], np.float32)
-        for c in range(3):
-            r2 = (r2.astype(np.float64) + d[:, c] * d[:, c]).astype(np.float32)
-        res = np.sort(np.sqrt(r2))
-        final_points += 1
-        if res.shape[0] <= 1:
-            return 0.0, k, 2
-        tail = res[1:]
-        med = tail[tail.shape[0] // 2]
-        if med < min_med:
-            min_med = med; best = scale
-    desv = np.float32(1.4826 * (1.0 - (5.0 / (final_points - 1.0))) * float(np.sqrt(min_med)))
-    num = np.float32(0); den = np.float32(0)
-    for i in range(n):
-        d = best * mono[i].astype(np.float64) - stereo[i].astype(np.float64)
-        r = np.float32(0)
-        for c in range(3):
-            r = np.float32(float(r) + d[c] * d[c])
-        r = np.sqrt(r)
-        if float(np.float32(r / desv)) < 2.5:
-            num = np.float32(num + np.float32(stereo[i, 2] * mono[i, 2]))
-            den = np.float32(den + np.float32(mono[i, 2] * mono[i, 2]))
-    return float(np.float32(num / den)), k, 0
 
 
 @pytest.mark.parametrize("n,seed", [(120, 1), (400, 2)])

@@ -39,6 +39,35 @@ def _rows(keep):
     ]
 
 
+@pytest.mark.parametrize("n", [8001, 8000])
+def test_surface_registration_refuses_more_than_8000_pairs(host_ctx, n):
+    """kMaxPairs of dsh_register.cpp (smm_finish_kernel keeps two floats per pair in LDS): the argument check comes before the device
+    entry, so 8001 pairs are DSH_ERR_ARG on a host-only context too, and 8000 pass it and reach "no GPU"."""
+    from defslam_amd import _lib
+    L = host_ctx._L
+    a = np.ones((n, 3), np.float32)
+    u = np.ones(n)      # no candidate: nothing but the stream's first n numbers would be read
+    fp, dp = a.ctypes.data_as(_lib.c_float_p), u.ctypes.data_as(_lib.c_double_p)
+    scale, consumed, status, reg, s22 = C.c_float(-1), C.c_int64(-1), C.c_int32(-1), C.c_int32(-1), C.c_double(-1)
+    Twc, Tcw, sim3 = np.eye(4, dtype=np.float32), np.zeros(16, np.float32), np.zeros(8)
+    calls = [
+        ("dsh_scale_min_median", lambda: L.dsh_scale_min_median(host_ctx._h, n, fp, fp, dp, n, C.byref(scale), C.byref(consumed), C.byref(status)),
+         "dsh_scale_min_median: bad argument (1 <= n <= 8000)"),
+        ("dsh_surface_register", lambda: L.dsh_surface_register(host_ctx._h, n, fp, fp, dp, n, Twc.ctypes.data_as(_lib.c_float_p), 0.05, 1, C.byref(reg),
+                                                                sim3.ctypes.data_as(_lib.c_double_p), C.byref(s22), Tcw.ctypes.data_as(_lib.c_float_p), None),
+         "dsh_surface_register: bad argument (n <= 8000)"),
+    ]
+    for name, call, refusal in calls:
+        rc = call()
+        msg = L.dsh_last_error(host_ctx._h).decode()
+        if n > 8000:
+            assert rc == ARG and msg == refusal
+        else:
+            assert rc == 4 and msg == name + ": host-only context, no GPU (there is no CPU fallback)"      # DSH_ERR_NO_DEVICE
+    assert (scale.value, consumed.value, status.value, s22.value) == (-1, -1, -1, -1) and not sim3.any() and not Tcw.any()
+    assert reg.value == (-1 if n > 8000 else 0)
+
+
 @pytest.mark.parametrize("row", range(12))
 def test_refusal_message_on_a_host_only_store(host_ctx, row):
     from test_local_map_cpu import _raw_store
