@@ -139,6 +139,17 @@ class PoseOnlyProblemC(C.Structure):
                 ("iters", C.c_int32 * 4), ("trials", C.c_int32 * 4), ("bad", C.c_int32 * 4), ("chi2", C.c_double * 4)]
 
 
+class TrackSftFrameC(C.Structure):
+    _fields_ = [("Tcw", c_float_p), ("K", C.c_double * 4), ("N", C.c_int32), ("kp", c_float_p), ("octave", c_i32_p), ("levels", C.c_int32),
+                ("inv_level_sigma2", c_float_p), ("frame_points", c_i32_p), ("outlier", c_u8_p), ("xyz", c_double_p), ("reg_lap", C.c_double),
+                ("reg_inex", C.c_double), ("reg_temp", C.c_double), ("neighbour_layers", C.c_int32), ("max_iters", C.c_int32)]
+
+
+class TrackSftTableC(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("M", C.c_int32), ("points_obs", C.c_int32), ("kp_index", c_i32_p), ("point_id", c_i32_p),
+                ("nodes", c_i32_p), ("bary", c_double_p), ("uv", c_double_p), ("invsig2", c_double_p)]
+
+
 class KfKeypointsC(C.Structure):
     _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("N", C.c_int32), ("kp", c_float_p)]
 
@@ -214,6 +225,7 @@ EXPORTED_SYMBOLS = [
     "dsh_trackstate_seed_local_points", "dsh_trackstate_repose", "dsh_trackstate_cull", "dsh_track_close_frame",
     "dsh_track_end_frame", "dsh_track_last_frame", "dsh_motion_model_search",
     "dsh_track_pose_only", "dsh_track_pose_only_batch",
+    "dsh_track_sft_observations", "dsh_track_sft",
     "dsh_surface_vertices", "dsh_need_new_template", "dsh_template_switch", "dsh_point_store_get_points", "dsh_point_store_get_embedding",
     "dsh_point_store_add_observations_indexed", "dsh_point_store_set_reference_keyframes", "dsh_point_store_get_reference_keyframes", "dsh_keyframe_anchors",
     "dsh_keyframe_process_new", "dsh_point_store_upkeep",
@@ -354,6 +366,8 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_motion_model_search.argtypes = [vp, C.POINTER(TrackFrameC), C.c_float, C.c_float, i32, c_i32_p, c_i32_p, c_i32_p, c_float_p]
     L.dsh_track_pose_only.argtypes = [vp, C.POINTER(PoseOnlyProblemC)]
     L.dsh_track_pose_only_batch.argtypes = [vp, C.c_int, C.POINTER(PoseOnlyProblemC)]
+    L.dsh_track_sft_observations.argtypes = [vp, C.POINTER(TrackSftFrameC), C.POINTER(TrackSftTableC)]
+    L.dsh_track_sft.argtypes = [vp, C.POINTER(TrackSftFrameC), i32, C.POINTER(TrackSftTableC), C.POINTER(SftResultC)]
     L.dsh_surface_vertices.argtypes = [C.POINTER(SurfaceGridC), c_double_p]
     L.dsh_need_new_template.argtypes = [vp, i32, C.POINTER(KfKeypointsC), c_i32_p, c_u8_p]
     L.dsh_template_switch.argtypes = [vp, C.POINTER(TemplateSwitchInputC), c_i32_p, C.POINTER(TemplateSwitchCountsC)]

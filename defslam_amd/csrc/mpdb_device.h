@@ -1,5 +1,5 @@
 // What the kernel files of the map point store dsh_mpdb share (localmap_, trackclose_, tmplswitch_, motionmodel_, anchor_, kfinsert_,
-// pointerase_ and obslist_kernels.hip): the wavefront and workgroup idioms of counting, appending and ordered compaction, and the grid
+// pointerase_, obslist_ and tracksft_kernels.hip): the wavefront and workgroup idioms of counting, appending and ordered compaction, and the grid
 // sizes of the launchers.  Integer valued; wavefronts of 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -9,6 +9,7 @@
 //   dsh_kfinsert.cpp      dsh_keyframe_process_new, dsh_point_store_upkeep
 //   dsh_pointerase.cpp    dsh_point_store_erase_observations, dsh_point_store_set_bad, dsh_point_store_cull and the read-backs of
 //                         observations and keyframe tables
+//   dsh_tracksft.cpp      dsh_track_sft_observations, dsh_track_sft
 #pragma once
 #include <hip/hip_runtime.h>
 

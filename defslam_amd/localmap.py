@@ -141,6 +141,38 @@ class PoseOnly:
 
 
 @dataclass
+class SftObservations:
+    """What dsh_track_sft_observations returns: the observation table of DefPoseOptimization (DefOptimizer.cc:293-361), by key point."""
+    kp_index: np.ndarray                # (M,) the key point of each row, ascending
+    point_id: np.ndarray                # (M,) the point it holds
+    nodes: np.ndarray                   # (M,3) int32: obs_nodes, the store's bytes
+    bary: np.ndarray                    # (M,3) float64: obs_bary, the store's bytes
+    uv: np.ndarray                      # (M,2) float64: the float32 key point
+    invsig2: np.ndarray                 # (M,) float64: the float32 mvInvLevelSigma2[octave]
+    points_obs: int                     # Points_Obs: key points that hold a point and are no outlier, bad points included
+
+
+@dataclass
+class TrackSft:
+    """What dsh_track_sft returns: the result of dsh_sft_solve on the table, and mvbOutlier of the frame."""
+    outlier: np.ndarray                 # (N,) bool mvbOutlier: written at table.kp_index, kept elsewhere
+    table: SftObservations
+    Tcw: np.ndarray                     # (4,4) float32: the pose SetPose receives
+    pose7: np.ndarray                   # (7,) t, q (x y z w)
+    xyz: np.ndarray                     # (n,3) float64 node positions
+    chi2_obs: np.ndarray                # (M,) per row
+    row_outlier: np.ndarray             # (M,) bool per row
+    mappoint_xyz: np.ndarray            # (M,3) float32 per row
+    rep_error: float                    # NaN when the table is empty
+    inliers: int
+    iters: int
+    trials: int
+    dim: int
+    half_bandwidth: int
+    status: int
+
+
+@dataclass
 class StoredPoints:
     """What dsh_point_store_get_points returns, per id asked for."""
     xyz: np.ndarray                     # (n,3) float32 mWorldPos
@@ -552,6 +584,76 @@ class MapPointStore:
         """One frame: Tcw (4,4) float32, K = fx fy cx cy, kp (N,2) mvKeysUn, octave (N,), inv_level_sigma2 (levels,), frame_points (N,)
         ids or -1.  The positions are the store's; nothing of the store changes."""
         return self.pose_only_batch([PoseOnlyFrame(Tcw, K, kp, octave, inv_level_sigma2, frame_points, outlier)], _single=True)[0]
+
+    # ---- Shape-from-Template of a tracked frame (the if branch of TrackLocalMap) ----
+    def _sft_frame(self, kp, octave, inv_level_sigma2, frame_points, outlier, keep: list) -> _lib.TrackSftFrameC:
+        fp = _i32(frame_points)
+        N = fp.shape[0]
+        kp = np.ascontiguousarray(kp, np.float32).reshape(N, 2)
+        oc = _i32(octave).reshape(N)
+        sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+        fl = np.zeros(max(N, 1), np.uint8)
+        if outlier is not None:
+            fl[:N] = np.asarray(outlier, bool).reshape(N)
+        keep += [fp, kp, oc, sg, fl]
+        f = _lib.TrackSftFrameC()
+        f.N, f.levels = N, int(sg.shape[0])
+        f.kp, f.octave, f.inv_level_sigma2 = _ptr(kp, C.c_float), _ptr(oc, C.c_int32), _ptr(sg, C.c_float)
+        f.frame_points, f.outlier = _ptr(fp, C.c_int32), _ptr(fl, C.c_uint8)
+        return f
+
+    @staticmethod
+    def _sft_table(N: int, keep: list) -> _lib.TrackSftTableC:
+        m = max(int(N), 1)
+        a = dict(kp_index=np.zeros(m, np.int32), point_id=np.zeros(m, np.int32), nodes=np.zeros((m, 3), np.int32), bary=np.zeros((m, 3)),
+                 uv=np.zeros((m, 2)), invsig2=np.zeros(m))
+        keep.append(a)
+        return _lib.TrackSftTableC(int(N), 0, 0, _ptr(a["kp_index"], C.c_int32), _ptr(a["point_id"], C.c_int32), _ptr(a["nodes"], C.c_int32),
+                                   _ptr(a["bary"], C.c_double), _ptr(a["uv"], C.c_double), _ptr(a["invsig2"], C.c_double))
+
+    @staticmethod
+    def _sft_rows(t: _lib.TrackSftTableC, a: dict) -> SftObservations:
+        M = int(t.M)
+        return SftObservations(**{k: v[:M].copy() for k, v in a.items()}, points_obs=int(t.points_obs))
+
+    def sft_observations(self, kp, octave, inv_level_sigma2, frame_points, outlier=None) -> SftObservations:
+        """The observation table DefPoseOptimization builds of a frame (DefOptimizer.cc:293-361), selected on the device from the facets
+        and barycentrics the store holds: kp (N,2) mvKeysUn, octave (N,), inv_level_sigma2 (levels,), frame_points (N,) ids or -1,
+        outlier (N,) mvbOutlier on entry (None: all False).  Nothing changes."""
+        keep: list = []
+        f = self._sft_frame(kp, octave, inv_level_sigma2, frame_points, outlier, keep)
+        t = self._sft_table(f.N, keep)
+        self._call("dsh_track_sft_observations", C.byref(f), C.byref(t))
+        return self._sft_rows(t, keep[-1])
+
+    def sft(self, Tcw, K, kp, octave, inv_level_sigma2, frame_points, node_xyz, outlier=None, write_back: bool = True, RegLap: float = 5000.0,
+            RegInex: float = 5000.0, RegTemp: float = 0.0, NeighboursLayers: int = 1, max_iters: int = 50) -> TrackSft:
+        """Optimizer::DefPoseOptimization of a frame against the store: the table of sft_observations, then dsh_sft_solve's path on it
+        with Tcw (4,4) float32, K = fx fy cx cy and node_xyz (n,3) the current node positions.  write_back moves every point that is not
+        bad and has a facet to its position on the optimised nodes (DefOptimizer.cc:568-576); close the frame with node_xyz=None then."""
+        keep: list = []
+        f = self._sft_frame(kp, octave, inv_level_sigma2, frame_points, outlier, keep)
+        N = int(f.N)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        x = np.ascontiguousarray(node_xyz, np.float64).reshape(-1, 3)
+        keep += [T, x]
+        f.Tcw, f.xyz = _ptr(T, C.c_float), _ptr(x, C.c_double)
+        f.K = (C.c_double * 4)(*[float(v) for v in np.asarray(K).reshape(4)])
+        f.reg_lap, f.reg_inex, f.reg_temp = float(RegLap), float(RegInex), float(RegTemp)
+        f.neighbour_layers, f.max_iters = int(NeighboursLayers), int(max_iters)
+        t = self._sft_table(N, keep)
+        m = max(N, 1)
+        b = dict(Tcw=np.zeros((4, 4), np.float32), pose7=np.zeros(7), xyz=np.zeros((x.shape[0], 3)), chi2=np.zeros(m), outl=np.zeros(m, np.uint8),
+                 mp=np.zeros((m, 3), np.float32))
+        r = _lib.SftResultC()
+        r.Tcw, r.pose7, r.xyz = _ptr(b["Tcw"], C.c_float), _ptr(b["pose7"], C.c_double), _ptr(b["xyz"], C.c_double)
+        r.chi2_obs, r.outlier, r.mappoint_xyz = _ptr(b["chi2"], C.c_double), _ptr(b["outl"], C.c_uint8), _ptr(b["mp"], C.c_float)
+        self._call("dsh_track_sft", C.byref(f), 1 if write_back else 0, C.byref(t), C.byref(r))
+        rows = self._sft_rows(t, keep[-1])
+        M = rows.kp_index.shape[0]
+        return TrackSft(outlier=keep[4][:N].astype(bool), table=rows, Tcw=b["Tcw"], pose7=b["pose7"], xyz=b["xyz"], chi2_obs=b["chi2"][:M],
+                        row_outlier=b["outl"][:M].astype(bool), mappoint_xyz=b["mp"][:M], rep_error=float(r.rep_error), inliers=int(r.inliers),
+                        iters=int(r.iters), trials=int(r.trials), dim=int(r.dim), half_bandwidth=int(r.half_bandwidth), status=int(r.status))
 
     # ---- the template switch ----
     def get_points(self, ids=None) -> StoredPoints:

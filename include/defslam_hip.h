@@ -838,6 +838,65 @@ int dsh_track_pose_only(dsh_mpdb* db, dsh_pose_only_problem* p);
  * bit.  B = 0 does nothing. */
 int dsh_track_pose_only_batch(dsh_mpdb* db, int B, dsh_pose_only_problem* problems);
 
+/* ---- tracking: Shape-from-Template of a tracked frame from the resident map point store ---------------------------------------
+ * The if branch of DefTracking::TrackLocalMap and the call of DefTracking::Track (Modules/Tracking/DefTracking.cc:244, :115):
+ * Optimizer::DefPoseOptimization (Modules/Tracking/DefOptimizer.cc:251-578) with its observation table built on the device from the
+ * facet and the barycentrics the store holds per point (dsh_trackstate_set_embedding, dsh_template_switch), instead of the host-built
+ * obs_nodes / obs_bary / obs_uv / obs_invsig2 of dsh_sft_frame.  Both entries take the store alone: the template is the current one of
+ * the store's context.
+ *   Selection (:293-361, literally): key point i gives a row when outlier[i] == 0, frame_points[i] >= 0, the point is not bad and the
+ *     point has a facet.  A key point that holds a point and is no outlier counts in points_obs (Points_Obs of :300) whether the point
+ *     is bad or not.  An id held by several key points gives one row each; the rows are in ascending key point index.  uv is the
+ *     float32 key point widened to double, invsig2 is (double)inv_level_sigma2[octave[i]] (the division by N of :340 stays in the
+ *     packer), nodes and bary are the store's bytes.
+ *   dsh_track_sft_observations runs the selection and downloads the table.  The store and the context's SfT batch are unchanged.
+ *   dsh_track_sft runs the selection, downloads the table once, then packs, plans, uploads and runs one problem exactly as
+ *     dsh_sft_solve does on that table and on the other fields of the frame, and downloads the result once; its numbers are those of
+ *     dsh_sft_solve on the same table on the same context, bit for bit.  The arrays of dsh_sft_result that dsh_sft_solve sizes by M
+ *     (chi2_obs, outlier, mappoint_xyz) take N entries here, the first M of them are written.  Then outlier[kp_index[m]] =
+ *     r->outlier[m] for every row; every other entry of outlier keeps its value (:515-537).  With write_back != 0 every point of the
+ *     store that is not bad and has a facet moves as by dsh_trackstate_repose on r->xyz (:568-576), from the result's node positions
+ *     where they lie in HBM; the frame is then closed with dsh_track_close_frame and node_xyz == NULL.  With write_back == 0 the store
+ *     is unchanged.  The call replaces an uploaded SfT batch of the context, as dsh_sft_solve does.
+ *   No row (M == 0) is NOT the reference's numbers (it runs an optimiser without observation edges): the call returns DSH_OK with
+ *     inliers = iters = trials = dim = half_bandwidth = status = 0, rep_error NaN and Tcw, pose7 and xyz of the input; nothing is
+ *     written back, the flags are untouched and the context's SfT batch stays.
+ * Discipline of the other store calls: arguments are checked on the host first -- NULL arrays with N > 0, N outside 0 .. 8192, levels
+ * outside 1 .. 32, an octave outside 0 .. levels-1 where frame_points[i] >= 0, an id that is neither -1 nor a point of the store, a
+ * table array with capacity < M, a stored node index >= the nodes of the template -- and DSH_ERR_ARG names the entry, nothing is
+ * written; no current template is DSH_ERR_STATE; then a host-only context answers DSH_ERR_NO_DEVICE; a detached store answers
+ * DSH_ERR_ARG.  An observation whose nodes share no mesh edge of the template (a stale embedding) is refused by the packer with
+ * DSH_ERR_ARG; the message names the observation and its key point. */
+typedef struct dsh_track_sft_frame {
+  const float* Tcw;                 /* 4x4 row-major float32, pFrame->mTcw */
+  double K[4];                      /* fx, fy, cx, cy */
+  int32_t N;                        /* pFrame->N, 0 .. 8192 */
+  const float* kp;                  /* N x 2 mvKeysUn */
+  const int32_t* octave;            /* N, read where frame_points[i] >= 0 */
+  int32_t levels;                   /* 1 .. 32 */
+  const float* inv_level_sigma2;    /* levels, mvInvLevelSigma2 */
+  const int32_t* frame_points;      /* N: mvpMapPoints as store ids, -1 = none */
+  uint8_t* outlier;                 /* N: mvbOutlier, in/out (dsh_track_sft_observations only reads it) */
+  const double* xyz;                /* n x 3 current node positions */
+  double reg_lap, reg_inex, reg_temp;
+  int32_t neighbour_layers;         /* as in dsh_sft_frame */
+  int32_t max_iters;                /* as in dsh_sft_frame */
+} dsh_track_sft_frame;
+typedef struct dsh_track_sft_table {
+  int32_t capacity;                 /* in: entries each array that is given has room for; capacity >= M else DSH_ERR_ARG, N always suffices */
+  int32_t M;                        /* out: rows */
+  int32_t points_obs;               /* out: Points_Obs of :300 */
+  int32_t* kp_index;                /* out, each array may be NULL: M, the key point of a row */
+  int32_t* point_id;                /* M */
+  int32_t* nodes;                   /* M x 3 */
+  double* bary;                     /* M x 3 */
+  double* uv;                       /* M x 2 */
+  double* invsig2;                  /* M */
+} dsh_track_sft_table;
+int dsh_track_sft_observations(dsh_mpdb* db, const dsh_track_sft_frame* f, dsh_track_sft_table* t);
+/* t may be NULL */
+int dsh_track_sft(dsh_mpdb* db, const dsh_track_sft_frame* f, int32_t write_back, dsh_track_sft_table* t, dsh_sft_result* r);
+
 /* ---- mapping meets tracking: the template switch on the resident map point store -----------------------------------------------
  * DefLocalMapping::updateTemplate (Modules/Mapping/DefLocalMapping.cc:138-153), which DefTracking::Track calls on the tracking thread
  * (Modules/Tracking/DefTracking.cc:109) in front of the frame's two pose optimisations, and the mapping thread's trigger

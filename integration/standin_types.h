@@ -88,6 +88,11 @@ class DefMapPoint : public MapPoint {          // Modules/Common/DefMapPoint.h
     recalculated++;
     if (mGlobalMutex.held) recalculated_under_lock++;
   }
+  void SetWorldPos(const float* p) {                                     // MapPoint::SetWorldPos (cv::Mat in the reference; def_pose_store_hip.h)
+    for (int c = 0; c < 3; c++) mWorldPos[c] = p[c];
+    recalculated++;
+    if (mGlobalMutex.held) recalculated_under_lock++;
+  }
   Facet* facet = nullptr;
   double b1 = 0, b2 = 0, b3 = 0;                                         // :96
   float mWorldPos[3] = {0, 0, 0};
