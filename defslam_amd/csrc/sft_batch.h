@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64, 1) void sftb_factor_kernel(const SftDev* __rest
   for (int i = lane; i < WV_LDS_DOUBLES; i += 64) lds[i] = 0.0;   // (the landing buffer is multiplied by ring zeros before its first fill)
   if (blockIdx.x == 0 && lane == 0) { counters[2] = 0; counters[3] = 0; }   // the LIN list of this round is consumed; TRIAL appends the next one
   WvPrev Q;
-  Q.Lg = nullptr; Q.Linv = nullptr; Q.x = nullptr; Q.nT = 0; Q.active = 0; Q.xb = 0.0;
+  Q.Lg = nullptr; Q.Linv = nullptr; Q.x = nullptr; Q.nT = 0; Q.active = 0; Q.m8[0] = Q.m8[1] = 0; Q.xb = 0.0;
   int n_done = 0;
   while (true) {
     int b = 0;

@@ -326,9 +326,31 @@ __device__ __forceinline__ bool wv_chol_inv(v4d& a, v4d& w) {
   return plast > 0.0;
 }
 
+// ---- the packed block column of L ------------------------------------------------------------------------------------------------------
+// A tile slot of L (Y_1 .. Y_8, W: 2 KB) is two PLANES of 1 KB, lane l at 16 l: plane h holds registers 2h, 2h + 1 of the tile in accumulator
+// order, i.e. rows g + 8h and g + 4 + 8h of column c for lane (g, c) -- the image of an LDS-resident tile, so one store and one LDS-DMA request
+// move the same 64 GRANULES of 16 bytes and one lane mask serves the writer and the reader.  Only granules that hold a structurally non-zero
+// element are written and read back:
+//   W    (lower triangular: [s][c] with s >= c)                                  plane h: the lanes with c <= g + 4 + 8h        (26 + 58 of 128)
+//   Y_8  (the d = 8 tile of the band: [s][c] with s - c >= z = 128 - kd)         plane h: the lanes with c <= g + 4 + 8h - z    (kd = 122: 3 + 34)
+//   Y_i  of a tile row behind the matrix (k + i >= nT)                           nothing
+// Skipped granules keep their addresses (holes); the memory there is never written and never read -- it may hold anything, the non-finite
+// numbers of an earlier failed factorisation included.  The readers supply the zeros: the deferred back substitution from its landing buffer
+// (zeroed where no request lands: wv_bs_begin), the immediate one in registers.
+__host__ __device__ constexpr unsigned long long wv_granule_mask(int t) {   // the lanes (g, c) with c <= g + t
+  unsigned long long m = 0;
+  for (int g = 0; g < 4; g++) {
+    const int n = t + g + 1 < 0 ? 0 : (t + g + 1 > 16 ? 16 : t + g + 1);
+    m |= ((1ull << n) - 1ull) << (16 * g);
+  }
+  return m;
+}
+constexpr unsigned long long WV_MASK_W0 = wv_granule_mask(4), WV_MASK_W1 = wv_granule_mask(12);
+
 // ---- per-problem constants of a factorisation, all wave-uniform --------------------------------------------------------------------
 struct WvProb {
   int Dn, Dnp, nT, q8;                    // q8: leading row chunks of the d = 8 corner tile that are structurally zero (kd = 122: 1)
+  unsigned long long m8[2];               // the non-zero granules of the two planes of Y_8 (wv_granule_mask)
   double lambda, lam_corner;
   unsigned bofs;                          // per lane: (c & 3) * Dnp + 4 (c >> 2) + g, the lane's QL element (nb = 0) of a border tile relative to column 16 J (doubles); nb = 1: + 4 Dnp
   const SFT_G double* Hc;
@@ -390,6 +412,7 @@ struct WvPrev {
   const SFT_G double* Linv;   // W tiles
   SFT_G double* x;
   int nT, active;
+  unsigned long long m8[2];   // the granules of Y_8 that its factorisation stored (WvProb::m8)
   double xb;                  // per lane: x_cam[c] for c < 6, -1 for c == 6 (the right-hand side column of the border), else 0
 };
 // (r06: the requests as asm -- scalar base + the lane's 32-bit offset + an immediate that advances the global AND the LDS address alike (the
@@ -400,34 +423,55 @@ __device__ __forceinline__ void wv_bs_request(const WvPrev& Q, int J, lds_double
   const SFT_G char* col = reinterpret_cast<const SFT_G char*>(Q.Lg + ((size_t)J * (BT + 1)) * 256);    // wave-uniform
   const SFT_G char* w = reinterpret_cast<const SFT_G char*>(Q.Linv + (size_t)J * 256);
   const unsigned l0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)land);                        // LDS byte address of the landing buffer
-  // slot 0: Yb (1 KB; the second KB of the slot is not used), slots 1..8: Y_1 .. Y_8 = KB 2..17
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %0, %1\n\t"
-               "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-               "global_load_lds_dwordx4 %0, %1 offset:3072"
-               :: "v"(voff), "s"(col), "s"(l0) : "memory", "m0");
+  unsigned long long keep;   // the execution mask across a request of fewer than 64 granules
+  // Only what the factorisation stored is requested (the packed block column, head of the WvProb section): a request under a lane mask leaves the
+  // other lanes' 16 bytes of the landing buffer as they are -- the zeros of wv_bs_begin / of the kernel's entry.
+  if (J + 8 < Q.nT) {   // (wave-uniform) every tile row of the column lies inside the matrix
+    // slot 0: Yb (1 KB; the second KB of the slot is not used), slots 1..7: Y_1 .. Y_7 = KB 2..15
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %0, %1\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
+                 "global_load_lds_dwordx4 %0, %1 offset:3072"
+                 :: "v"(voff), "s"(col), "s"(l0) : "memory", "m0");
 #pragma unroll
-  for (int grp = 1; grp < 5; grp++) {
-    const SFT_G char* cg = col + 4096 * grp;
-    const unsigned lg = l0 + 4096u * grp;
-    if (grp < 4)
+    for (int grp = 1; grp < 4; grp++) {
+      const SFT_G char* cg = col + 4096 * grp;
+      const unsigned lg = l0 + 4096u * grp;
       asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
                    "global_load_lds_dwordx4 %0, %1\n\t"
                    "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
                    "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
                    "global_load_lds_dwordx4 %0, %1 offset:3072"
                    :: "v"(voff), "s"(cg), "s"(lg) : "memory", "m0");
-    else   // KB 16, 17
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %0, %1\n\t"
-                   "global_load_lds_dwordx4 %0, %1 offset:1024"
-                   :: "v"(voff), "s"(cg), "s"(lg) : "memory", "m0");
+    }
+    // slot 8: the non-zero granules of Y_8 (KB 16, 17)
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "s_and_saveexec_b64 %0, %4\n\t"
+                 "global_load_lds_dwordx4 %1, %2\n\t"
+                 "s_mov_b64 exec, %0\n\t"
+                 "s_and_saveexec_b64 %0, %5\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+                 "s_mov_b64 exec, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(col + 16384), "s"(l0 + 16384u), "s"(Q.m8[0]), "s"(Q.m8[1]) : "memory", "m0", "scc");
+  } else {   // the last eight block columns: Y_i of a tile row behind the matrix was not stored, and slot 8 is such a one
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(col), "s"(l0) : "memory", "m0");
+#pragma unroll
+    for (int i = 1; i < 8; i++)
+      if (J + i < Q.nT)
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %0, %1\n\t"
+                     "global_load_lds_dwordx4 %0, %1 offset:1024"
+                     :: "v"(voff), "s"(col + 2048 * i), "s"(l0 + 2048u * i) : "memory", "m0");
   }
-  // W: 2 KB behind the eighteen of the column
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %0, %1\n\t"
-               "global_load_lds_dwordx4 %0, %1 offset:1024"
-               :: "v"(voff), "s"(w), "s"(l0 + 18u * 1024u) : "memory", "m0");
+  // W: 2 KB behind the eighteen of the column, its lower triangle
+  asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\t"
+               "s_and_saveexec_b64 %0, %4\n\t"
+               "global_load_lds_dwordx4 %1, %2\n\t"
+               "s_mov_b64 exec, %0\n\t"
+               "s_and_saveexec_b64 %0, %5\n\t"
+               "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+               "s_mov_b64 exec, %0"
+               : "=&s"(keep) : "v"(voff), "s"(w), "s"(l0 + 18u * 1024u), "s"(WV_MASK_W0), "s"(WV_MASK_W1) : "memory", "m0", "scc");
 }
 // (Measured and dropped, r06: the nineteen requests issued one at a time behind the first tiles of the trailing update instead of as a burst
 // here -- profiles/r06/ab/phases_ab_v7_dma_spread.log: FACTOR 264.4 against 261.2 ms per step; the 1.5-2.0 k cycles the deferred column costs
@@ -436,7 +480,7 @@ __device__ __forceinline__ void wv_bs_request(const WvPrev& Q, int J, lds_double
 // camera term - y at index g + 4q; x_J[c] = sum_r W[r][c] (-S[r]).  The border tile is a ninth tile whose "x" is (x_cam, -1, 0, ...).
 __device__ __forceinline__ void wv_bs_column(const WvPrev& Q, int J, const lds_double* land, lds_double* xring, int lane) {
   const int c = lane & 15;
-  const lds_v2d* t2 = reinterpret_cast<const lds_v2d*>(land) + 2 * lane;   // the lane's 32 bytes of tile 0; tile i: + 128 * i
+  const lds_v2d* t2 = reinterpret_cast<const lds_v2d*>(land) + lane;   // the lane's 16 bytes of plane 0 of tile 0; plane 1: + 64, tile i: + 128 * i
   double s[4];
   {
     const lds_double* tb = land + wv_bstd_index(lane);   // Yb is stored in QL (1 KB): element [g + 4 q][c & 7]; the lanes c >= 8 mirror c - 8 (times xb = 0)
@@ -445,7 +489,7 @@ __device__ __forceinline__ void wv_bs_column(const WvPrev& Q, int J, const lds_d
 #pragma unroll
   for (int d = 1; d <= 8; d++) {
     const double xr = xring[((J + d) & 7) * 16 + c];   // tile rows behind the matrix: the ring still holds its zeros
-    const v2d_w a = t2[128 * d], b = t2[128 * d + 1];
+    const v2d_w a = t2[128 * d], b = t2[128 * d + 64];
     s[0] = fma(a.x, xr, s[0]); s[1] = fma(a.y, xr, s[1]); s[2] = fma(b.x, xr, s[2]); s[3] = fma(b.y, xr, s[3]);
   }
 #pragma unroll
@@ -455,7 +499,7 @@ __device__ __forceinline__ void wv_bs_column(const WvPrev& Q, int J, const lds_d
     s[q] += wv_dpp_mov<0x122>(s[q]);
     s[q] += wv_dpp_mov<0x121>(s[q]);
   }
-  const v2d_w wa = t2[128 * 9], wb = t2[128 * 9 + 1];
+  const v2d_w wa = t2[128 * 9], wb = t2[128 * 9 + 64];
   double p = wa.x * -s[0];
   p = fma(wa.y, -s[1], p); p = fma(wb.x, -s[2], p); p = fma(wb.y, -s[3], p);
   p = sum_rows(p);
@@ -470,6 +514,15 @@ __device__ __forceinline__ void wv_bs_step(const WvPrev& Q, int J, lds_double* l
 __device__ __forceinline__ void wv_bs_begin(const WvPrev& Q, lds_double* lds, int lane) {
   lds_double* xring = lds + WV_L_XRING;
   xring[lane] = 0.0; xring[64 + lane] = 0.0;
+  // Slots 1..8 of the landing buffer hold block column 0 of the back substitution before this one.  The first eight columns of this one request
+  // none or some of them (tile rows behind the matrix), and of slot 8 only the granules of ITS band: what no request overwrites reads as the
+  // zeros the factorisation did not store.  Once per problem; slot 9 (W) has the same granules in every problem and keeps the kernel's zeros.
+  {
+    lds_v2d* z = reinterpret_cast<lds_v2d*>(lds + WV_L_LAND + 256) + lane;
+#pragma unroll
+    for (int i = 0; i < 16; i++) z[64 * i] = (v2d_w){0.0, 0.0};
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
   wv_bs_request(Q, Q.nT - 1, lds + WV_L_LAND, lane);
 }
 // The whole back substitution at once (the last problem of a wave; lab A/B): block columns two ahead in registers.
@@ -483,14 +536,23 @@ __device__ __forceinline__ void wv_backsub_now(const WvPrev& Q, int lane) {
   auto fetch = [&](int J) -> Col {
     Col C;
     if (J >= 0) {
-      const SFT_G double* col = Q.Lg + ((size_t)J * (BT + 1)) * 256 + 4 * lane;
+      // the packed block column (head of the WvProb section): a lane reads its granules of the two planes of a slot where they were stored,
+      // and takes zeros for the others
+      const SFT_G double* col = Q.Lg + ((size_t)J * (BT + 1)) * 256;
+      auto slot = [&](const SFT_G double* t, bool in0, bool in1) -> v4d {
+        const v2d_w zero = (v2d_w){0.0, 0.0};
+        const v2d_w a = in0 ? *reinterpret_cast<const SFT_G v2d_w*>(t + 2 * lane) : zero;
+        const v2d_w b = in1 ? *reinterpret_cast<const SFT_G v2d_w*>(t + 128 + 2 * lane) : zero;
+        return (v4d){a.x, a.y, b.x, b.y};
+      };
 #pragma unroll
-      for (int i = 1; i <= 8; i++) C.t[i] = (J + i < Q.nT) ? *reinterpret_cast<const SFT_G v4d*>(col + 256 * i) : (v4d){0.0, 0.0, 0.0, 0.0};
+      for (int i = 1; i <= 7; i++) { const bool in = J + i < Q.nT; C.t[i] = slot(col + 256 * i, in, in); }
+      C.t[8] = slot(col + 256 * 8, J + 8 < Q.nT && ((Q.m8[0] >> lane) & 1), J + 8 < Q.nT && ((Q.m8[1] >> lane) & 1));
       {   // Yb: stored in QL (1 KB)
-        const SFT_G double* tb = col - 4 * lane + wv_bstd_index(lane);
+        const SFT_G double* tb = col + wv_bstd_index(lane);
         C.t[0] = (v4d){tb[0], tb[8], tb[16], tb[24]};
       }
-      C.t[9] = *reinterpret_cast<const SFT_G v4d*>(Q.Linv + (size_t)J * 256 + 4 * lane);
+      C.t[9] = slot(Q.Linv + (size_t)J * 256, (WV_MASK_W0 >> lane) & 1, (WV_MASK_W1 >> lane) & 1);
     } else {
 #pragma unroll
       for (int i = 0; i < 10; i++) C.t[i] = (v4d){0.0, 0.0, 0.0, 0.0};
@@ -545,7 +607,7 @@ struct WvState {
   WvB2 bnext;        // raw border tile of column k+8 (QL; enters the ring this step): requested at the head of the step
   WvRowList rl;      // gather lists of the row that enters the window this step (row k+8): requested at the head of the step
   unsigned al[4];    // gather list of tile (k+9, k+1), the next step's araw -- the only request that is carried across the update
-  unsigned off_lane, off_bord;   // byte offsets of the lane inside a 2 KB tile slot of L (32 l) and inside the 1 KB border tile (QL: 16 l)
+  unsigned off_lane;   // byte offset of the lane inside a plane of a tile slot of L and inside the 1 KB border tile (QL): 16 l
   int ok;
 };
 
@@ -600,11 +662,19 @@ __device__ __forceinline__ void wv_update_tiles(const WvProb& W, WvState& S, int
           const SFT_G double* slot = col + 256 * (n >> 1);
           if constexpr (n == 0) {   // the border tile Yb in QL: 16 bytes per lane, 1 KB, one store (n == 1: its slot has no second half)
             const v2d_w yb = (v2d_w){S.Yq.n0, S.Yq.n1};
-            asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(S.off_bord), "v"(yb), "s"(slot) : "memory");
-          } else if constexpr (n >= 2) {
+            asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(S.off_lane), "v"(yb), "s"(slot) : "memory");
+          } else if constexpr (n >= 2) {   // plane (n & 1) of the slot; the packed block column: head of the WvProb section
             const v4d& y = S.Y[n >> 1];
             const v2d_w half = (v2d_w){y[2 * (n & 1)], y[2 * (n & 1) + 1]};
-            asm volatile("global_store_dwordx4 %0, %1, %2 offset:%c3" :: "v"(S.off_lane), "v"(half), "s"(slot), "n"(16 * (n & 1)) : "memory");
+            if constexpr ((n >> 1) == 8) {   // Y_8: the non-zero granules of the band's corner tile
+              if constexpr (!TAIL) {   // (TAIL: k + 8 >= nT, behind the matrix)
+                unsigned long long keep;
+                asm volatile("s_and_saveexec_b64 %0, %4\n\tglobal_store_dwordx4 %1, %2, %3 offset:%c5\n\ts_mov_b64 exec, %0"
+                             : "=&s"(keep) : "v"(S.off_lane), "v"(half), "s"(slot), "s"(W.m8[n & 1]), "n"(1024 * (n & 1)) : "memory", "scc");
+              }
+            } else if (!TAIL || k + (n >> 1) < nT) {   // a tile row behind the matrix is not stored
+              asm volatile("global_store_dwordx4 %0, %1, %2 offset:%c3" :: "v"(S.off_lane), "v"(half), "s"(slot), "n"(1024 * (n & 1)) : "memory");
+            }
           }
         }
         // ... and two of the 28 gathers of the row that enters the window (the tiles of ring row PH are free since the TRSM): like the
@@ -738,10 +808,10 @@ __device__ __forceinline__ void wv_step_rest(const WvProb& W, WvState& S, const 
   else wv_trsm_vgpr(S.Y[8], Wt, S.araw, W.q8);
   wv_mfma_fence();
   WV_T(3);
-  // L leaves from the registers it was computed in: block column k = [Yb | Y_1 .. Y_8] at slots (k, 0..8), 2 KB each (lane l: 32 bytes at
-  // 32 l) -- stored half by half between the MFMAs of the update below (wv_update_tiles); tiles behind the matrix are stored as the
-  // zeros they are
-  SFT_G double* col = W.Lg + ((size_t)k * (BT + 1)) * 256;   // (wave-uniform; the lanes' offsets are S.off_lane / S.off_bord)
+  // L leaves from the registers it was computed in: block column k = [Yb | Y_1 .. Y_8] at slots (k, 0..8), 2 KB each (two planes of 1 KB,
+  // lane l: 16 bytes at 16 l) -- stored plane by plane between the MFMAs of the update below (wv_update_tiles); tiles behind the matrix
+  // and the structurally zero granules of Y_8 are not stored (the packed block column: head of the WvProb section)
+  SFT_G double* col = W.Lg + ((size_t)k * (BT + 1)) * 256;   // (wave-uniform; the lanes' offset is S.off_lane)
   // ---- the ring row / border slot of column k are free: row k+8 enters (its lists came a step ahead), the lists of row k+9 are requested
   v4d fresh4 = wv_gather_vgpr(W, S.rl.o[4]);   // (the accumulator-file tiles of the row: wv_update_tiles)
   // A value that is only loaded and stored may be allocated to the accumulator file by the compiler (memory instructions address it) --
@@ -838,6 +908,8 @@ __device__ __forceinline__ int wv_factor(const SftDev& P, double lambda, double 
   W.Dnp = ((W.Dn + NB - 1) / NB) * NB;
   W.nT = W.Dnp / TS;
   W.q8 = min(3, max(0, (TS * BT - uni(P.kd)) / 4));
+  W.m8[0] = wv_granule_mask(4 - (TS * BT - uni(P.kd)));
+  W.m8[1] = wv_granule_mask(12 - (TS * BT - uni(P.kd)));
   W.lambda = lambda;
   W.lam_corner = lam_corner;
   W.bofs = (unsigned)((c & 3) * W.Dnp + 4 * (c >> 2) + g);
@@ -881,10 +953,9 @@ __device__ __forceinline__ int wv_factor(const SftDev& P, double lambda, double 
     const int ph = k & 7;
     // Requests of this step, issued in front of the tile Cholesky (2 us of vector-ALU work: they arrive behind it) and consumed behind the
     // TRSM -- nothing of them is alive during the trailing update, where the 9 Y tiles and the pipelined LDS tiles need the registers.
-    // the lanes' byte offsets inside a 2 KB tile slot of L / inside the compact border tile: computed every step by statements the compiler
-    // cannot hoist -- as loop invariants such registers were parked in the accumulator file, on a window tile (tools/wave_audit.py)
-    asm volatile("v_lshlrev_b32 %0, 5, %1" : "=v"(S.off_lane) : "v"(lane));
-    asm volatile("v_lshlrev_b32 %0, 4, %1" : "=v"(S.off_bord) : "v"(lane));
+    // the lanes' byte offset inside a plane of a tile slot of L / inside the compact border tile: computed every step by a statement the compiler
+    // cannot hoist -- as a loop invariant such a register was parked in the accumulator file, on a window tile (tools/wave_audit.py)
+    asm volatile("v_lshlrev_b32 %0, 4, %1" : "=v"(S.off_lane) : "v"(lane));
     S.araw = wv_gather_vgpr(W, S.al);            // tile (k+8, k)^T through the list that came a step ahead
     // The next list right behind it, in FRONT of the other requests: the wait that consumes them (behind the TRSM) covers it as well, so the
     // compiler's wait in front of the gather above is s_waitcnt vmcnt(14) instead of vmcnt(0) (the list was the youngest load crossing the back
@@ -921,10 +992,13 @@ __device__ __forceinline__ int wv_factor(const SftDev& P, double lambda, double 
       S.ok = 0;
     }
     WV_T(1);
-    {   // W of column k leaves like the tiles of L: scalar base + the lane's 32-bit offset
+    {   // W of column k leaves like the tiles of L: scalar base + the lane's 32-bit offset; the granules of its lower triangle only
       const SFT_G double* slot = W.Linv + (size_t)k * 256;
       const v2d_w w01 = (v2d_w){w[0], w[1]}, w23 = (v2d_w){w[2], w[3]};
-      asm volatile("global_store_dwordx4 %0, %1, %3\n\tglobal_store_dwordx4 %0, %2, %3 offset:16" :: "v"(S.off_lane), "v"(w01), "v"(w23), "s"(slot) : "memory");
+      unsigned long long keep;
+      asm volatile("s_and_saveexec_b64 %0, %5\n\tglobal_store_dwordx4 %1, %2, %4\n\ts_mov_b64 exec, %0\n\t"
+                   "s_and_saveexec_b64 %0, %6\n\tglobal_store_dwordx4 %1, %3, %4 offset:1024\n\ts_mov_b64 exec, %0"
+                   : "=&s"(keep) : "v"(S.off_lane), "v"(w01), "v"(w23), "s"(slot), "s"(WV_MASK_W0), "s"(WV_MASK_W1) : "memory", "scc");
     }
     // (W^T in accumulator order -- through LDS -- is formed inside wv_step_rest, behind the requests of the TRSM's LDS-resident operands)
     switch (ph + ((k + 8 >= W.nT) ? 8 : 0)) {
@@ -1013,6 +1087,8 @@ __device__ __forceinline__ WvPrev wv_prev_of(const SftDev& P, int ok, double xca
   const int Dn = uni(P.Dn), Dnp = ((Dn + NB - 1) / NB) * NB;
   Q.Lg = uni(P.Lb); Q.Linv = uni(P.Linv); Q.x = uni(P.x);
   Q.nT = Dnp / TS;
+  Q.m8[0] = wv_granule_mask(4 - (TS * BT - uni(P.kd)));
+  Q.m8[1] = wv_granule_mask(12 - (TS * BT - uni(P.kd)));
   Q.active = ok;
   Q.xb = (c < 6) ? xcam : ((c == 6) ? -1.0 : 0.0);
   if (ok && lane < 6) P.x[Dnp + lane] = xcam;
@@ -1022,7 +1098,7 @@ __device__ __forceinline__ WvPrev wv_prev_of(const SftDev& P, int ok, double xca
 // factorisation + back substitution of one problem right away (lab A/B kernel)
 __device__ __forceinline__ int wv_factor_solve(const SftDev& P, double lambda, double lam_corner, lds_double* lds) {
   WvPrev none;
-  none.Lg = nullptr; none.Linv = nullptr; none.x = nullptr; none.nT = 0; none.active = 0; none.xb = 0.0;
+  none.Lg = nullptr; none.Linv = nullptr; none.x = nullptr; none.nT = 0; none.active = 0; none.m8[0] = none.m8[1] = 0; none.xb = 0.0;
   double xcam;
   const int ok = wv_factor(P, lambda, lam_corner, lds, none, xcam);
   int lane;   // (formed behind the factorisation: see wv_factor)

@@ -34,6 +34,18 @@ def acc_to_mat(t):   # accumulator order: lane l = (g, c), register q -> [g + 4q
     return M
 
 
+def planes_to_mat(t, z=None):
+    """A tile slot of the one-wavefront solver: plane h at 128 h doubles, lane l at 2 l = registers 2h, 2h + 1 = rows g + 8h, g + 4 + 8h
+    of column c.  z: only the granules with c <= g + 4 + 8h - z were stored (W: 0, the d = 8 tile: 128 - kd); the others hold what was there before."""
+    M = np.zeros((16, 16))
+    for l in range(64):
+        g, c = l >> 4, l & 15
+        for h in range(2):
+            if z is None or c <= g + 4 + 8 * h - z:
+                M[g + 8 * h, c], M[g + 4 + 8 * h, c] = t[128 * h + 2 * l], t[128 * h + 2 * l + 1]
+    return M
+
+
 ctx.wave_check(1.0, 1, only=1)
 Lr = ctx.dump(0, 0, nT * 9 * 256).reshape(nT, 9, 256)
 Wr = ctx.dump(0, 1, nT * 256).reshape(nT, 256)
@@ -55,13 +67,13 @@ Cn = dbg[8:57].reshape(7, 7)
 print("corner: reference (host, from the reference border rows)\n", np.array_str(np.tril(Cref), precision=4, max_line_width=200))
 print("corner: one-wavefront\n", np.array_str(np.tril(Cn), precision=4, max_line_width=200))
 for k in range(min(nT, int(sys.argv[2]) if len(sys.argv) > 2 else 12)):
-    w_r, w_n = acc_to_mat(Wr[k]), acc_to_mat(Wn[k])
+    w_r, w_n = acc_to_mat(Wr[k]), planes_to_mat(Wn[k], 0)
     line = f"col {k}: W diff {np.abs(w_r - w_n).max():.2e} (|W| {np.abs(w_r).max():.2e})"
     for i in range(1, 9):
         if k + i >= nT:
             break
         X = acc_to_mat(Lr[k, i])            # reference: X(k+i, k)
-        Y = acc_to_mat(Ln[k, i])            # one-wavefront: X^T
+        Y = planes_to_mat(Ln[k, i], 128 - int(counts[6]) if i == 8 else None)   # one-wavefront: X^T
         line += f" | i={i}: {np.abs(X - Y.T).max():.1e}/{np.abs(X).max():.1e}"
     Yb = acc_to_mat(Ln[k, 0])               # Xb^T: [b][c] = Xb[c][b]
     Xb = Br[:7, 16 * k:16 * k + 16]
