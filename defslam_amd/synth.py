@@ -191,8 +191,11 @@ def make_problem(config: str = "C2", problem_id: int = 0):
 # ---------------------------------------------------------------------------------------------------------
 # NRSfM normals: a rigid planar scene seen from several keyframes.  For a plane N.X = 1 (camera-1 frame) the
 # inter-image warp in normalised coordinates is the homography (R + t N^T); its first and second derivatives
-# are the DiffProp fields (Modules/Mapping/diffProp.h, SchwarpDatabase.cc:299-345) and the solution of the
-# two bicubic polynomials is k = (N1, N2) / (N.[u,v,1])  (normal ~ [k1, k2, 1 - k1 u - k2 v]).
+# are the DiffProp fields (Modules/Mapping/diffProp.h, SchwarpDatabase.cc:299-345).  The geometric normal of
+# the plane at (u, v) is k = (N1, N2) / (N.[u,v,1])  (normal ~ [k1, k2, 1 - k1 u - k2 v]).  It is NOT the
+# common root of the reference's two bicubic polynomials on these records: the reference forms their t2 from
+# the H12vv fields (NormalEstimator.cc:96-97), and the polynomials vanish at k only with t2 from H12uu as in
+# its propagation (:210).  tests/normals_geometry.py builds records on which both coincide.
 # ---------------------------------------------------------------------------------------------------------
 def _homography_derivs(Hm, u, v):
     p = np.array([u, v, 1.0])
@@ -209,7 +212,8 @@ def _homography_derivs(Hm, u, v):
 
 
 def make_normals_scene(n_points: int = 200, n_views: int = 4, seed: int = 7, nonref_frac: float = 0.3, min_views: int = 1):
-    """Returns a dict with the flat arrays of dsh_normals_estimate plus the ground-truth (k1,k2) per point.
+    """Returns a dict with the flat arrays of dsh_normals_estimate plus k_true, the geometric normal (k1,k2) of every point's plane
+    (not the root of the reference's polynomials on these records, see above: nothing the reference computes here equals it).
     Every point gets between min_views and n_views records (the reference puts no limit on them, NormalEstimator.cc:77-118)."""
     rng = np.random.default_rng(seed)
     recs, is_ref, first_n, has_first_n, rec_ptr = [], [], [], [], [0]
