@@ -199,6 +199,21 @@ class PointEraseCountsC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_found", "n_ref_moved", "n_set_bad", "n_records", "n_entries")]
 
 
+class KeyframeRegisterInputC(C.Structure):
+    _fields_ = [("kfdb", C.c_void_p), ("slot", C.c_int32), ("N", C.c_int32), ("surface_pts", c_float_p), ("Twc", c_float_p), ("u", c_double_p),
+                ("nu", C.c_int64), ("chi_limit", C.c_double), ("check_chi", C.c_int32)]
+
+
+class KeyframeRegisterResultC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("n_pairs", "n_empty", "n_bad", "n_no_facet", "n_no_snapshot", "registered", "stream_status")] +
+                [("consumed", C.c_int64), ("sim3", C.c_double * 8), ("s22", C.c_double), ("info", C.c_double * 8), ("Tcw_new", C.c_float * 16),
+                 ("Ow_new", C.c_float * 3)])
+
+
+class KeyframePoseInputC(C.Structure):
+    _fields_ = [("kfdb", C.c_void_p), ("slot", C.c_int32), ("Tcw", c_float_p)]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -231,6 +246,8 @@ EXPORTED_SYMBOLS = [
     "dsh_keyframe_process_new", "dsh_point_store_upkeep",
     "dsh_point_store_erase_observations", "dsh_point_store_set_bad", "dsh_point_store_cull", "dsh_point_store_get_observations",
     "dsh_point_store_get_keyframe_table",
+    "dsh_keyframe_snapshot_positions", "dsh_keyframe_get_snapshot", "dsh_keyframe_register_clouds", "dsh_keyframe_register",
+    "dsh_keyframe_set_pose", "dsh_keyframe_get_centre",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -384,6 +401,12 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_point_store_cull.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_u8_p, C.POINTER(PointEraseCountsC)]
     L.dsh_point_store_get_observations.argtypes = [vp, C.c_int, c_i32_p, c_i32_p, i32, c_i32_p, c_i32_p, c_i32_p]
     L.dsh_point_store_get_keyframe_table.argtypes = [vp, i32, i32, c_i32_p]
+    L.dsh_keyframe_snapshot_positions.argtypes = [vp, i32, c_i32_p]
+    L.dsh_keyframe_get_snapshot.argtypes = [vp, i32, i32, c_i32_p, c_float_p]
+    L.dsh_keyframe_register_clouds.argtypes = [vp, C.POINTER(KeyframeRegisterInputC), c_i32_p, c_float_p, c_float_p, C.POINTER(KeyframeRegisterResultC)]
+    L.dsh_keyframe_register.argtypes = [vp, C.POINTER(KeyframeRegisterInputC), c_i32_p, c_float_p, C.POINTER(KeyframeRegisterResultC)]
+    L.dsh_keyframe_set_pose.argtypes = [vp, C.POINTER(KeyframePoseInputC), c_float_p]
+    L.dsh_keyframe_get_centre.argtypes = [vp, C.POINTER(KeyframePoseInputC), c_float_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

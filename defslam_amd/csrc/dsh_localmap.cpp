@@ -88,8 +88,7 @@ int dsh_mpdb_create(const dsh_mpdb_desc* desc, dsh_mpdb** out) {
     db->Tcap = (long long)desc->keyframe_capacity * 1024;
     db->Rcap = desc->observation_capacity;
     if (mpdb_reserve_points(db, desc->point_capacity) != hipSuccess || mpdb_reserve_keyframes(db, desc->keyframe_capacity) != hipSuccess ||
-        mpdb_reserve_log(db, db->Rcap) != hipSuccess ||
-        hipMalloc((void**)&db->d_table, 4 * (size_t)db->Tcap) != hipSuccess || hipMalloc((void**)&db->d_hdr, sizeof(LmHdr)) != hipSuccess ||
+        mpdb_reserve_log(db, db->Rcap) != hipSuccess || mpdb_reserve_table(db, db->Tcap) != hipSuccess || hipMalloc((void**)&db->d_hdr, sizeof(LmHdr)) != hipSuccess ||
         hipMemset(db->d_hdr, 0, sizeof(LmHdr)) != hipSuccess) {
       db->free_all();
       delete db;
@@ -130,6 +129,7 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->obs.clear();
   db->unindexed.clear();
   db->kf.clear();
+  db->snapped.clear();
   return DSH_OK;
 }
 
@@ -272,17 +272,17 @@ int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_
   if (db->K == INT32_MAX || db->T + N > INT32_MAX) return bad("store full");
   if (const int rc = dsh_enter(c, "dsh_mpdb_add_keyframe")) return rc;
   HIPCHK(c, mpdb_reserve_keyframes(db, (long long)db->K + 1));
-  if (db->T + N > db->Tcap) {
-    const long long cap = std::max(db->T + N, 2 * db->Tcap);
-    HIPCHK(c, dsh_store_grow_array(&db->d_table, (size_t)db->T, (size_t)cap));
-    db->Tcap = cap;
-  }
+  HIPCHK(c, mpdb_reserve_table(db, db->T + N));
   LmKf k;
   k.tab_off = (int32_t)db->T; k.N = N; k.parent = parent; k.bad = bad_flag ? 1 : 0;
   HIPCHK(c, hipMemcpyAsync(db->d_kf + db->K, &k, sizeof(k), hipMemcpyHostToDevice, c->stream));
-  if (N > 0) HIPCHK(c, hipMemcpyAsync(db->d_table + db->T, points, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  if (N > 0) {
+    HIPCHK(c, hipMemcpyAsync(db->d_table + db->T, points, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(db->d_snap_point + db->T, 0xff, 4 * (size_t)N, c->stream));   // -1: no snapshot yet (dsh_keyframe_snapshot_positions)
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   db->kf.push_back(k);
+  db->snapped.push_back(0);
   if (slot) *slot = db->K;
   db->K++;
   db->T += N;

@@ -11,6 +11,7 @@
 
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
+#include "dsh_register.h"
 #include "mapping_launch.h"
 
 namespace dsh {
@@ -30,18 +31,10 @@ int smm_walk_candidates(int n, const double* u, int64_t nu, int32_t* cand, int64
   *consumed = k;
   return nc;
 }
-}  // namespace dsh
 
-namespace {
-
-constexpr int kMaxPairs = 8000;   // the finishing kernel keeps two floats per pair in LDS
-
-struct Clouds {   // device copies of the two clouds (slices of a block up)
-  const float *a = nullptr, *b = nullptr;
-};
-
-// scaleMinMedian: the clouds, the consumed part of the stream and the candidate list go up in one block, which stays in d for a second
-// stage; the scale and the status (0, 1, 2) are read back
+// The stages, declared in dsh_register.h.
+// scaleMinMedian: the clouds (unless d holds them already), the consumed part of the stream and the candidate list go up in one block,
+// which stays in d for a second stage; the scale and the status (0, 1, 2) are read back
 int scale_min_median_dev(dsh_ctx_base* c, int n, const float* mono, const float* stereo, const double* u, int64_t nu, float* scale, int64_t* consumed,
                          int32_t* status, Clouds& d) {
   int64_t k = 0;
@@ -65,7 +58,7 @@ int scale_min_median_dev(dsh_ctx_base* c, int n, const float* mono, const float*
   dsh::smm_walk_candidates(n, u, nu, up.host<int32_t>(o_c), up.host<int64_t>(o_off), &k);
   if (const int rc = up.send(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
-  d = {up.dev<float>(o_a), up.dev<float>(o_b)};
+  if (mono) d = {up.dev<float>(o_a), up.dev<float>(o_b)};
   HIPCHK(c, reg_scale_min_median(n, nc, d.a, d.b, up.dev<double>(o_u), up.dev<int32_t>(o_c), up.dev<int64_t>(o_off), dmed, dsc, down.dev<double>(d_out), c->stream));
   if (const int rc = down.receive(c)) return rc;
   *scale = (float)down.host<double>(d_out)[0];
@@ -133,7 +126,9 @@ void compose(const double* sim3, const float* Twc, double* s22_out, float* Tcw) 
   Tcw[12] = Tcw[13] = Tcw[14] = 0.f;
   Tcw[15] = 1.f;
 }
-}  // namespace
+}  // namespace dsh
+
+using namespace dsh;
 
 extern "C" {
 

@@ -1,6 +1,8 @@
 // The keyframe store dsh_kfdb as its translation units see it: dsh_mappoint.cpp (dsh_kfdb_*, dsh_mappoint_update), dsh_tmplswitch.cpp
 // (dsh_template_switch reads the descriptor rows, camera centres, octaves and scale factors of the reference keyframe) and
-// dsh_kfinsert.cpp (dsh_keyframe_process_new, dsh_point_store_upkeep: the upkeep of map points with every input on the device).
+// dsh_kfinsert.cpp (dsh_keyframe_process_new, dsh_point_store_upkeep: the upkeep of map points with every input on the device) and
+// dsh_surfreg.cpp (dsh_keyframe_register, dsh_keyframe_set_pose: the one writer of a stored camera centre, MpuSlot::Ow, after insertion;
+// the host keeps no copy of it).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -10,6 +10,7 @@
 //   dsh_pointerase.cpp    dsh_point_store_erase_observations, dsh_point_store_set_bad, dsh_point_store_cull and the read-backs of
 //                         observations and keyframe tables
 //   dsh_tracksft.cpp      dsh_track_sft_observations, dsh_track_sft
+//   dsh_surfreg.cpp       dsh_keyframe_snapshot_positions, dsh_keyframe_register and the keyframe pose of the keyframe store
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,10 @@ struct dsh_mpdb : dsh_store {
   int32_t* d_log_idx = nullptr;   // parallel to the log: the key point index of the observation in its keyframe, -1: not given
   LmKf* d_kf = nullptr;
   int32_t *d_table = nullptr, *d_local_kf = nullptr;
+  // DefKeyFrame's PosesKeyframes, parallel to d_table (dsh_keyframe_snapshot_positions): per table entry the point whose position was
+  // taken there (-1: none) and that position.  Keyed by point: later edits of the table do not touch it.
+  int32_t* d_snap_point = nullptr;
+  float* d_snap_xyz = nullptr;
   LmHdr* d_hdr = nullptr;
   // the resident last-frame list (dsh_track_end_frame): per key point of the last frame the id it holds or -1, and its octave (-1 there)
   int32_t *d_last_ids = nullptr, *d_last_oct = nullptr;
@@ -51,6 +56,7 @@ struct dsh_mpdb : dsh_store {
   std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
   std::unordered_set<uint64_t> unindexed;        // the live records without a key point index (dsh_mpdb_add_observations)
   std::vector<LmKf> kf;
+  std::vector<uint8_t> snapped;          // per keyframe: its snapshot has been taken (the reference takes it once, in the constructor)
   int32_t n_local_points = 0;
   int32_t n_ref_points = 0;            // length of d_ref_ids
   int32_t P_cnt = 0;                   // points d_cnt covers: the store's size at the last dsh_local_map_update
@@ -83,7 +89,7 @@ struct dsh_mpdb : dsh_store {
   void free_all() {
     for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
                     (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
-                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx})
+                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx, (void*)d_snap_point, (void*)d_snap_xyz})
       if (p) (void)hipFree(p);
   }
 };
@@ -131,6 +137,18 @@ inline hipError_t mpdb_reserve_last_frame(dsh_mpdb* db, int32_t N) {
   hipError_t e;
   if ((e = dsh_store_grow_array(&db->d_last_ids, used, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_last_oct, used, cap)) != hipSuccess) return e;
   db->last_cap = (int32_t)cap;
+  return hipSuccess;
+}
+
+// room for `need` table entries: the tables and the snapshot beside them
+inline hipError_t mpdb_reserve_table(dsh_mpdb* db, long long need) {
+  if (need <= db->Tcap && db->d_table && db->d_snap_point && db->d_snap_xyz) return hipSuccess;
+  const size_t cap = (size_t)std::max(need, db->d_table ? 2 * db->Tcap : db->Tcap), T = (size_t)db->T;
+  hipError_t e;
+  if ((e = dsh_store_grow_array(&db->d_table, T, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_snap_point, T, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_snap_xyz, 3 * T, 3 * cap)) != hipSuccess)
+    return e;
+  db->Tcap = (long long)cap;
   return hipSuccess;
 }
 

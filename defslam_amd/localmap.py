@@ -18,7 +18,11 @@
     dsh_point_store_upkeep): AddObservation, UpdateNormalAndDepth, ComputeDistinctiveDescriptors, results written into the store;
   * MapPoint::EraseObservation (MapPoint.cc:122-148), DefMapPoint::setBadFlag (DefMapPoint.cc:76-94) and LocalMapping::MapPointCulling
     (LocalMapping.cc:173-199) in full on the store's log and tables (dsh_point_store_erase_observations, dsh_point_store_set_bad,
-    dsh_point_store_cull), with the read-backs of a point's observations and a keyframe's table.
+    dsh_point_store_cull), with the read-backs of a point's observations and a keyframe's table;
+  * DefKeyFrame's PosesKeyframes snapshot (Modules/Common/DefKeyFrame.cc:60-74) and SurfaceRegistration::registerSurfaces
+    (Modules/Mapping/SurfaceRegistration.cc:48-153) with the clouds selected from the store and the snapshot, Surface::applyScale and the
+    camera centre of KeyFrame::SetPose written into the keyframe store (dsh_keyframe_snapshot_positions, dsh_keyframe_register,
+    dsh_keyframe_set_pose).
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -293,6 +297,39 @@ class PointObservations:
         """mObservations of the i-th id asked for: {slot: idx} in slot order."""
         s = slice(self.ptr[i], self.ptr[i + 1])
         return dict(zip(self.slots[s].tolist(), self.idx[s].tolist()))
+
+
+@dataclass
+class KeyframeClouds:
+    """What dsh_keyframe_register_clouds returns: the pairs of SurfaceRegistration.cc:60-104 in ascending entry order."""
+    pair_idx: np.ndarray                # (n_pairs,) the table entry of each pair
+    cloud_surface: np.ndarray           # (n_pairs,3) float32 cloud2pc: the surface points in world coordinates
+    cloud_map: np.ndarray               # (n_pairs,3) float32 cloud1pc: PosesKeyframes of the points
+    n_pairs: int
+    n_empty: int                        # entries without a point
+    n_bad: int                          # entries whose point is bad
+    n_no_facet: int                     # entries whose point has no facet now
+    n_no_snapshot: int                  # entries whose point has no snapshot for this keyframe
+
+
+@dataclass
+class KeyframeRegistration:
+    """What dsh_keyframe_register returns (SurfaceRegistration::registerSurfaces from the stores)."""
+    pair_idx: np.ndarray
+    n_pairs: int
+    n_empty: int
+    n_bad: int
+    n_no_facet: int
+    n_no_snapshot: int
+    registered: bool
+    stream_status: int                  # 1: the stream u is shorter than the reference's draws
+    consumed: int                       # draws of u the reference makes
+    sim3: np.ndarray                    # (8,) qx qy qz qw tx ty tz s
+    s22: float                          # the recovered scale
+    info: np.ndarray                    # (8,) as dsh_surface_register
+    Tcw_new: np.ndarray                 # (4,4) float32: the pose SetPose receives
+    Ow_new: np.ndarray                  # (3,) float32: its camera centre
+    surface_scaled: Optional[np.ndarray]   # (N,3) float32 Surface::applyScale of the surface points; None when not registered
 
 
 # dsh_point_store_erase_observations: what became of a pair
@@ -795,6 +832,88 @@ class MapPointStore:
                 continue
             self._ctx._check(rc, "dsh_point_store_get_observations")
             return PointObservations(ptr=ptr, slots=sl[:total.value].copy(), idx=ix[:total.value].copy())
+
+    # ---- the mapping thread: surface registration of a keyframe ----
+    def _kf_len(self, slot: int) -> int:
+        return self._kf_n[slot] if 0 <= int(slot) < len(self._kf_n) else 0
+
+    def snapshot_positions(self, slot: int) -> int:
+        """DefKeyFrame's constructor loop (DefKeyFrame.cc:60-74) for keyframe `slot`: the position of every point it holds that is not
+        bad and has a facet is kept as PosesKeyframes; returns how many entries were taken.  Once per keyframe."""
+        n = C.c_int32(0)
+        self._call("dsh_keyframe_snapshot_positions", int(slot), C.byref(n))
+        return int(n.value)
+
+    def get_snapshot(self, slot: int):
+        """(point (N,) int32, xyz (N,3) float32) of keyframe `slot`: per table entry the point whose position was taken, or -1."""
+        N = self._kf_len(slot)
+        pt, x = np.full(max(N, 1), -1, np.int32), np.zeros((max(N, 1), 3), np.float32)
+        self._call("dsh_keyframe_get_snapshot", int(slot), N, _ptr(pt, C.c_int32), _ptr(x, C.c_float))
+        return pt[:N], x[:N]
+
+    def _register_input(self, kf_store, slot, surface_pts, Twc, u, chi_limit, check_chi, keep: list) -> _lib.KeyframeRegisterInputC:
+        sp = np.ascontiguousarray(surface_pts, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(Twc, np.float32).reshape(16)
+        uu = None if u is None else np.ascontiguousarray(u, np.float64).reshape(-1)
+        keep += [sp, T, uu]
+        return _lib.KeyframeRegisterInputC(kf_store._h if kf_store is not None else None, int(slot), int(sp.shape[0]), _ptr(sp, C.c_float),
+                                           _ptr(T, C.c_float), _ptr(uu, C.c_double), 0 if uu is None else uu.shape[0], float(chi_limit),
+                                           int(bool(check_chi)))
+
+    @staticmethod
+    def _register_counts(r) -> dict:
+        return {n: int(getattr(r, n)) for n in ("n_pairs", "n_empty", "n_bad", "n_no_facet", "n_no_snapshot")}
+
+    def register_clouds(self, slot: int, surface_pts, Twc) -> KeyframeClouds:
+        """The two clouds of SurfaceRegistration::registerSurfaces (:60-104) for keyframe `slot`: surface_pts (N,3) float32 is
+        Surface::get3DSurfacePoint per key point, Twc (4,4) float32 the keyframe's GetPoseInverse().  Nothing changes."""
+        keep: list = []
+        inp = self._register_input(None, slot, surface_pts, Twc, None, 0.0, True, keep)
+        m = max(int(inp.N), 1)
+        idx, a, b = np.zeros(m, np.int32), np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32)
+        r = _lib.KeyframeRegisterResultC()
+        self._call("dsh_keyframe_register_clouds", C.byref(inp), _ptr(idx, C.c_int32), _ptr(a, C.c_float), _ptr(b, C.c_float), C.byref(r))
+        n = int(r.n_pairs)
+        return KeyframeClouds(pair_idx=idx[:n].copy(), cloud_surface=a[:n].copy(), cloud_map=b[:n].copy(), **self._register_counts(r))
+
+    def register_surface(self, kf_store, slot: int, surface_pts, Twc, u, chi_limit: float, check_chi: bool = True) -> KeyframeRegistration:
+        """SurfaceRegistration::registerSurfaces for keyframe `slot` from the stores: the clouds of register_clouds, the registration of
+        register.registerSurfaces on them (u: the rand() stream), and when it registers Surface::applyScale of surface_pts and the new
+        camera centre written into kf_store (a mappoint.KeyFrameStore, or None).  A refusal that still reports the counts (more than
+        8000 pairs, a stream that is too short) raises DshError with them in its `result` attribute."""
+        keep: list = []
+        inp = self._register_input(kf_store, slot, surface_pts, Twc, u, chi_limit, check_chi, keep)
+        N = int(inp.N)
+        idx, sc = np.zeros(max(N, 1), np.int32), np.zeros((max(N, 1), 3), np.float32)
+        r = _lib.KeyframeRegisterResultC()
+        rc = self._ctx._L.dsh_keyframe_register(self._h, C.byref(inp), _ptr(idx, C.c_int32), _ptr(sc, C.c_float), C.byref(r))
+        reg = bool(r.registered)
+        info = np.array(r.info, float)
+        res = KeyframeRegistration(pair_idx=idx[:int(r.n_pairs)].copy() if rc == _lib.DSH_OK else np.zeros(0, np.int32), registered=reg,
+                                   stream_status=int(r.stream_status), consumed=int(r.consumed), sim3=np.array(r.sim3, float), s22=float(r.s22),
+                                   info=info, Tcw_new=np.array(r.Tcw_new, np.float32).reshape(4, 4), Ow_new=np.array(r.Ow_new, np.float32),
+                                   surface_scaled=sc[:N].copy() if reg else None, **self._register_counts(r))
+        try:
+            self._ctx._check(rc, "dsh_keyframe_register")
+        except Exception as e:
+            e.result = res
+            raise
+        return res
+
+    def set_keyframe_pose(self, kf_store, slot: int, Tcw) -> np.ndarray:
+        """KeyFrame::SetPose for keyframe `slot` of kf_store: its camera centre becomes that of Tcw (4,4) float32; returns the centre."""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        inp = _lib.KeyframePoseInputC(kf_store._h if kf_store is not None else None, int(slot), _ptr(T, C.c_float))
+        Ow = np.zeros(3, np.float32)
+        self._call("dsh_keyframe_set_pose", C.byref(inp), _ptr(Ow, C.c_float))
+        return Ow
+
+    def keyframe_centre(self, kf_store, slot: int) -> np.ndarray:
+        """The camera centre kf_store holds for keyframe `slot`."""
+        inp = _lib.KeyframePoseInputC(kf_store._h if kf_store is not None else None, int(slot), None)
+        Ow = np.zeros(3, np.float32)
+        self._call("dsh_keyframe_get_centre", C.byref(inp), _ptr(Ow, C.c_float))
+        return Ow
 
     def keyframe_table(self, slot: int) -> np.ndarray:
         """KeyFrame::GetMapPointMatches of keyframe `slot` as ids or -1."""

@@ -497,8 +497,10 @@ int dsh_search_by_projection_local(dsh_ctx* ctx, const dsh_track_frame* frame, i
  * TriangularMesh.cc:192: normal and depth only).
  * dsh_kfdb keeps what these read of every keyframe resident in HBM: the descriptor rows, the octaves of mvKeysUn, the camera centre,
  * the scale pyramid and the bad flag (descriptor rows, octaves, centre and pyramid on the device; the bad flag of this store stays on
- * the host, where dsh_mappoint_update lists the election rows).  A keyframe is copied up once, when it is added; keyframe poses do not change after insertion in
- * DefSLAM (there is no keyframe bundle adjustment), so the store has no pose update.  Lifetime as dsh_diffdb: a store belongs to the
+ * the host, where dsh_mappoint_update lists the election rows).  A keyframe is copied up once, when it is added.  Keyframe poses change in exactly one place after
+ * insertion in DefSLAM (there is no keyframe bundle adjustment): the surface registration calls refKF->SetPose
+ * (Modules/Mapping/SurfaceRegistration.cc:150), which moves the camera centre.  dsh_keyframe_register writes the new centre into this
+ * store itself, and dsh_keyframe_set_pose is the call for any other caller of SetPose.  Lifetime as dsh_diffdb: a store belongs to the
  * context it was created on; dsh_destroy of that context detaches it -- every call on it then returns DSH_ERR_ARG -- and
  * dsh_kfdb_destroy works before or after dsh_destroy. */
 typedef struct dsh_kfdb dsh_kfdb;
@@ -1183,6 +1185,96 @@ int dsh_point_store_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t*
 int dsh_point_store_get_observations(dsh_mpdb* db, int n, const int32_t* ids, int32_t* obs_ptr, int32_t capacity, int32_t* slots,
                                      int32_t* idx, int32_t* n_total);
 int dsh_point_store_get_keyframe_table(dsh_mpdb* db, int32_t slot, int32_t capacity, int32_t* points);
+
+/* ---- mapping: surface registration of a keyframe from the resident stores ------------------------------------------------------
+ * SurfaceRegistration::registerSurfaces (Modules/Mapping/SurfaceRegistration.cc:48-153) with its inputs taken from the stores: the
+ * walk over GetMapPoint, isBad, getFacet and PosesKeyframes[refKF] that builds the two clouds, the registration of
+ * dsh_surface_register on them, Surface::applyScale (Modules/Mapping/Surface.cc:107-121) and refKF->SetPose (:150).  Every entry takes
+ * the point store alone; the keyframe store travels in the input struct, as for dsh_keyframe_process_new.
+ *
+ * THE SNAPSHOT.  The map cloud is not the points' current position: it is the position each point had when the keyframe was
+ * constructed (Modules/Common/DefKeyFrame.cc:60-74: for every key point whose point exists, is not bad and has a facet,
+ * PosesKeyframes[this] = GetWorldPos).  The store keeps it beside the keyframe tables: snap_point (int32, -1: none) and snap_xyz (three
+ * float32) per table entry.  A new keyframe starts with -1 everywhere; dsh_mpdb_clear forgets it.
+ *   PosesKeyframes[kf] of point p is non-empty exactly when some entry j of kf has snap_point[j] == p, and its value is that entry's
+ *   snap_xyz.  Entries naming the same point hold the same bytes: they were taken in one instant.  Later edits of the table --
+ *   dsh_mpdb_set_keyframe_point, the template switch, the erase calls -- do not touch the snapshot: it is keyed by point, as the
+ *   reference's unordered_map is.
+ * dsh_keyframe_snapshot_positions takes it for keyframe `slot`: one launch, nothing goes up, one small block comes down; *n_taken (may
+ * be NULL) = the entries taken.  The reference takes the snapshot once, in the constructor: a second call on the same keyframe returns
+ * DSH_ERR_STATE (the host mirror keeps a flag per keyframe).  dsh_keyframe_get_snapshot reads it back: point[N] and xyz[N x 3] of the
+ * keyframe's N entries, capacity >= N; an entry without a snapshot reads -1 and zeros.
+ *
+ * THE CLOUDS (SurfaceRegistration.cc:60-104), for table entry i ascending with p = table[i], the first matching case:
+ *   p == -1                                  n_empty
+ *   p bad                                    n_bad
+ *   p without a facet now                    n_no_facet
+ *   p without a snapshot for this keyframe   n_no_snapshot
+ *   otherwise                                pair k = the number of pairs before i: cloud_map[k] = the snapshot of p, cloud_surface[k] =
+ *                                            rows 0..2 of Twc * (s_i, 1), pair_idx[k] = i
+ * covNorm is an array address in the reference and always true.  The product is the float32 one stated for dsh_template_switch: four
+ * products per row, summed left to right, no contraction.  One launch, pairs in entry order; a keyframe has at most 8192 key points.
+ * dsh_keyframe_register_clouds is the selection alone (u, nu, chi_limit and check_chi are not read; pair_idx, cloud_surface and
+ * cloud_map hold N entries each and may be NULL): a caller who wants the reference's lazy rand() learns n_pairs from it.
+ *
+ * THE REGISTRATION.  Fewer than 15 pairs: registered = 0 and nothing else runs (:106-107).  More than 8000 pairs: DSH_ERR_ARG with the
+ * counts set (the limit of dsh_surface_register).  Otherwise the stages of dsh_surface_register run on the clouds where the selection
+ * left them, with the same n in the same order, so sim3, s22, Tcw_new and info are the bytes dsh_surface_register gives for the same
+ * clouds; consumed = the draws of the stream the reference makes.  The counts are read back once between the selection and the first
+ * stage: the host's walk of the stream needs n.  A stream that is too short is DSH_ERR_ARG with stream_status = 1 and the counts set;
+ * nothing is mutated.
+ * When registered, one finishing launch
+ *   - writes surface_scaled[i] = (float)((double)s_i * s22) per component for all N entries (may be NULL): Surface::applyScale on a
+ *     cv::Vec3f, a reading of OpenCV's Vec * double (no OpenCV build to check against); nodesDepth_ stays with the caller;
+ *   - with a keyframe store given, makes the keyframe's camera centre there the centre of Tcw_new by KeyFrame::SetPose
+ *     (Thirdparty/ORBSLAM_2/src/KeyFrame.cc:97-111): Ow[i] = -((R[0][i] * t[0] + R[1][i] * t[1]) + R[2][i] * t[2]) in float32.  It is
+ *     returned in Ow_new either way.  dsh_template_switch and dsh_point_store_upkeep, which run next, read that centre.
+ * When not registered nothing in either store changes and surface_scaled is not written.
+ *
+ * THE KEYFRAME POSE.  dsh_keyframe_set_pose is KeyFrame::SetPose for any other caller: the centre of Tcw goes into the keyframe store
+ * (and into Ow, which may be NULL); dsh_keyframe_get_centre reads the stored centre back (Tcw is not read).
+ *
+ * Refusals follow the store's rules: arguments first, DSH_ERR_ARG with a message that names the entry (a keyframe store, where one is
+ * given, must belong to the same context and hold the slot with the same N); a host-only context then gives DSH_ERR_NO_DEVICE; a
+ * detached store gives DSH_ERR_ARG.  A refused call writes nothing but the counts named above.  Every entry here names a keyframe of
+ * the store, and the store of a host-only context stays empty (dsh_mpdb_add_keyframe needs the device), so there the argument check
+ * "slot outside the store" always comes first and DSH_ERR_NO_DEVICE cannot be observed through these entries.  The keyframe store's
+ * handle is looked up among the stores attached to the context before it is read: a store of another context, a detached one and a
+ * pointer that is no store are all DSH_ERR_ARG.  Twc and the Tcw of dsh_keyframe_set_pose must be finite (DSH_ERR_ARG), as the centre
+ * of dsh_kfdb_add must; a registration whose composed pose is not finite (a degenerate alignment, which the reference would hand to
+ * SetPose) returns DSH_ERR_STATE with the counts, sim3 and info set, registered = 0 and nothing written. */
+int dsh_keyframe_snapshot_positions(dsh_mpdb* db, int32_t slot, int32_t* n_taken);
+int dsh_keyframe_get_snapshot(dsh_mpdb* db, int32_t slot, int32_t capacity, int32_t* point, float* xyz);
+
+typedef struct dsh_keyframe_register_input {
+  dsh_kfdb* kfdb;                   /* may be NULL: then no camera centre is written */
+  int32_t slot, N;                  /* N == the N the keyframe has in the store */
+  const float* surface_pts;         /* N x 3: Surface::get3DSurfacePoint per key point, camera frame */
+  const float* Twc;                 /* 16, row major: refKF->GetPoseInverse before the registration */
+  const double* u;                  /* the rand stream, as for dsh_surface_register */
+  int64_t nu;
+  double chi_limit;
+  int32_t check_chi;
+} dsh_keyframe_register_input;
+typedef struct dsh_keyframe_register_result {
+  int32_t n_pairs, n_empty, n_bad, n_no_facet, n_no_snapshot;   /* per table entry */
+  int32_t registered, stream_status;
+  int64_t consumed;
+  double sim3[8], s22, info[8];     /* as dsh_surface_register */
+  float Tcw_new[16], Ow_new[3];
+} dsh_keyframe_register_result;
+int dsh_keyframe_register_clouds(dsh_mpdb* db, const dsh_keyframe_register_input* in, int32_t* pair_idx, float* cloud_surface, float* cloud_map,
+                                 dsh_keyframe_register_result* out);
+int dsh_keyframe_register(dsh_mpdb* db, const dsh_keyframe_register_input* in, int32_t* pair_idx, float* surface_scaled,
+                          dsh_keyframe_register_result* out);
+
+typedef struct dsh_keyframe_pose_input {
+  dsh_kfdb* kfdb;                   /* of the same context */
+  int32_t slot;
+  const float* Tcw;                 /* 16, row major */
+} dsh_keyframe_pose_input;
+int dsh_keyframe_set_pose(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float* Ow /* 3, may be NULL: the centre written */);
+int dsh_keyframe_get_centre(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float* Ow /* 3 */);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -2,6 +2,7 @@
 // integration/local_map_hip.h, integration/track_close_hip.h and integration/anchor_pairs_hip.h touch
 // (reference declaration behind each), for the repository's CI: OpenCV is not in the build image.  Inside DefSLAM these are not used.
 #pragma once
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -81,6 +82,8 @@ class LmMapPoint {                             // Thirdparty/ORBSLAM_2/include/M
   void EraseObservation(LmKeyFrame* kf) {                               // :58 (MapPoint.cc:99-133, without the bad-flag rule)
     if (mObservations.erase(kf)) nObs--;
   }
+  // what DefKeyFrame's constructor and SurfaceRegistration::registerSurfaces touch (surface_register_store_hip.h)
+  std::map<LmKeyFrame*, std::array<float, 3>> PosesKeyframes;           // DefMapPoint.h:104 (unordered_map<KeyFrame*, cv::Mat>)
 };
 
 class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/KeyFrame.h
@@ -108,6 +111,16 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
   float Twc[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPoseInverse() :61 (cv::Mat 4x4 float)
   int rows = 0, cols = 0;                                               // imGray.rows, imGray.cols :228
   std::vector<float> surface_points;                                    // DefKeyFrame::surface->get3DSurfacePoint(i, x3c): 3 per key point
+  // what SurfaceRegistration::registerSurfaces writes (surface_register_store_hip.h)
+  float Tcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPose() :60
+  void SetPose(const float* T) {                                        // :59 (KeyFrame.cc:97-111: Tcw, Ow = -Rwc * tcw, Twc)
+    for (int i = 0; i < 16; i++) Tcw[i] = T[i];
+    for (int i = 0; i < 3; i++) Ow[i] = -(Tcw[i] * Tcw[3] + Tcw[4 + i] * Tcw[7] + Tcw[8 + i] * Tcw[11]);
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) Twc[4 * r + c] = Tcw[4 * c + r];
+      Twc[4 * r + 3] = Ow[r];
+    }
+  }
 };
 
 class LmFrame {                                // Thirdparty/ORBSLAM_2/include/Frame.h
