@@ -214,6 +214,22 @@ class KeyframePoseInputC(C.Structure):
     _fields_ = [("kfdb", C.c_void_p), ("slot", C.c_int32), ("Tcw", c_float_p)]
 
 
+class KeyframeSurfaceInfoC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "n_normals", "enough_normals", "has_depth")] + [("grid", BbsC)]
+
+
+class SurfaceTakeInputC(C.Structure):
+    _fields_ = [("ddb", C.c_void_p), ("n", C.c_int32), ("sel", c_i32_p), ("slot", c_i32_p), ("idx", c_i32_p)]
+
+
+class KeyframeSfnInputC(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("slot", C.c_int32), ("bbs", C.POINTER(BbsC)), ("bending_weight", C.c_double), ("mean_depth", C.c_double)]
+
+
+class KeyframeSfnResultC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_sites", "n_empty", "n_bad", "n_no_normal", "n_nan", "ok")]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -248,6 +264,9 @@ EXPORTED_SYMBOLS = [
     "dsh_point_store_get_keyframe_table",
     "dsh_keyframe_snapshot_positions", "dsh_keyframe_get_snapshot", "dsh_keyframe_register_clouds", "dsh_keyframe_register",
     "dsh_keyframe_set_pose", "dsh_keyframe_get_centre",
+    "dsh_keyframe_surface_init", "dsh_keyframe_surface_set_depth", "dsh_keyframe_surface_set_points", "dsh_keyframe_surface_set_normals",
+    "dsh_keyframe_surface_take_normals", "dsh_keyframe_surface_gather", "dsh_keyframe_surface_get", "dsh_keyframe_surface_vertices",
+    "dsh_keyframe_sfn", "dsh_keyframe_surface_state",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -407,6 +426,16 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_keyframe_register.argtypes = [vp, C.POINTER(KeyframeRegisterInputC), c_i32_p, c_float_p, C.POINTER(KeyframeRegisterResultC)]
     L.dsh_keyframe_set_pose.argtypes = [vp, C.POINTER(KeyframePoseInputC), c_float_p]
     L.dsh_keyframe_get_centre.argtypes = [vp, C.POINTER(KeyframePoseInputC), c_float_p]
+    L.dsh_keyframe_surface_init.argtypes = [vp, i32, i32, c_float_p]
+    L.dsh_keyframe_surface_set_depth.argtypes = [vp, i32, C.POINTER(BbsC), c_double_p]
+    L.dsh_keyframe_surface_set_points.argtypes = [vp, i32, i32, c_i32_p, c_float_p]
+    L.dsh_keyframe_surface_set_normals.argtypes = [vp, i32, c_i32_p, c_i32_p, c_float_p, c_i32_p]
+    L.dsh_keyframe_surface_take_normals.argtypes = [vp, C.POINTER(SurfaceTakeInputC), c_i32_p]
+    L.dsh_keyframe_surface_gather.argtypes = [vp, i32, c_i32_p, c_i32_p, c_float_p, c_u8_p, c_float_p]
+    L.dsh_keyframe_surface_get.argtypes = [vp, i32, i32, c_float_p, c_u8_p, c_float_p, c_float_p, c_double_p, C.POINTER(KeyframeSurfaceInfoC)]
+    L.dsh_keyframe_surface_vertices.argtypes = [vp, i32, c_float_p, i32, i32, c_double_p]
+    L.dsh_keyframe_surface_state.argtypes = [vp, i32]
+    L.dsh_keyframe_sfn.argtypes = [vp, C.POINTER(KeyframeSfnInputC), c_double_p, c_double_p, c_float_p, C.POINTER(KeyframeSfnResultC)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

@@ -321,4 +321,8 @@ struct NormalsOut {
   int32_t* rec_list[3];
 };
 int normals_stage(dsh_ctx_base* c, int P, int R, const NormalsIn& in, const NormalsOut& out);
+
+// dsh_tmplswitch.cpp: the body of dsh_surface_vertices behind its checks and its device gate; ctrl_dev: the depth spline on the device
+// (dsh_keyframe_surface_vertices), or null for grid->depth_ctrl.
+int surface_vertices_run(dsh_ctx_base* c, const dsh_surface_grid* grid, const double* ctrl_dev, double* nodes_xyz);
 }  // namespace dsh

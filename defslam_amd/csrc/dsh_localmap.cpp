@@ -130,6 +130,7 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->unindexed.clear();
   db->kf.clear();
   db->snapped.clear();
+  db->surf.clear();
   return DSH_OK;
 }
 
@@ -283,6 +284,7 @@ int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_
   HIPCHK(c, hipStreamSynchronize(c->stream));
   db->kf.push_back(k);
   db->snapped.push_back(0);
+  db->surf.emplace_back();
   if (slot) *slot = db->K;
   db->K++;
   db->T += N;

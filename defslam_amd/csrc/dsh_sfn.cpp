@@ -15,6 +15,7 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
+#include "dsh_sfn.h"
 #include "mapping_launch.h"
 #include "schwarp_problem.h"
 
@@ -90,8 +91,7 @@ int dsh_bbs_bending(const dsh_bbs* bbs, double lambda, double* bending) {
 
 }  // extern "C"
 
-// The body of dsh_sfn_estimate / dsh_sfn_estimate_db: the normals come from the host (normals) or are picked on the device out of the
-// last normal solve of a database (db, sel).  Two pairs of blocks: the control points come down before the surface points are evaluated.
+// The checks of dsh_sfn_estimate / dsh_sfn_estimate_db behind the device gate, then the stages.
 static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u, const double* v, const float* normals, const dsh_diffdb* ndb, const int32_t* sel,
                         double bending_weight, double mean_depth, int n_all, const double* u_all, const double* v_all, double* ctrl_raw, double* ctrl, float* pts,
                         int32_t* ok) {
@@ -108,14 +108,24 @@ static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u
   }
   const int N = bbs->nptsu * bbs->nptsv;
   if (N > 512) return dsh_fail(c, DSH_ERR_ARG, "dsh_sfn_estimate: more than 512 control points (one-workgroup solve)");
+  return dsh::sfn_stages(c, bbs, n, u, v, normals, ndb, sel, bending_weight, mean_depth, n_all, u_all, v_all, nullptr, ctrl_raw, ctrl, pts, ok);
+}
+
+// The body of dsh_sfn_estimate / dsh_sfn_estimate_db / dsh_keyframe_sfn: the normals come from the host (normals), are picked on the
+// device out of the last normal solve of a database (ndb, sel), or lie on the device with the sites (dev).  Two pairs of blocks: the
+// control points come down before the surface points are evaluated.
+int dsh::sfn_stages(dsh_ctx_base* c, const dsh_bbs* bbs, int n, const double* u, const double* v, const float* normals, const dsh_diffdb* ndb, const int32_t* sel,
+                    double bending_weight, double mean_depth, int n_all, const double* u_all, const double* v_all, const SfnDevice* dev, double* ctrl_raw,
+                    double* ctrl, float* pts, int32_t* ok) {
+  const int N = bbs->nptsu * bbs->nptsv;
   *ok = 0;
   hipStream_t st = c->stream;
   const int m = 2 * n + N + 1, np = nrsfm_swp_solve_np(N);
   const size_t nz = (size_t)n, Nz = (size_t)N, rows = 8 * 2 * nz * Nz;   // rows: bytes of the normal rows of A, which sfn_rows_kernel fills
   // the constant rows lead the block up and land right behind the normal rows: the device side of the block continues A
   UpBlock up;
-  const size_t o_tail = up.take(8 * (Nz + 1) * Nz), o_b = up.take(8 * (size_t)m), o_ones = up.take(8 * Nz), o_u = up.copy_of(u, 8 * nz), o_v = up.copy_of(v, 8 * nz),
-               o_n = ndb ? up.copy_of(sel, 4 * nz) : up.copy_of(normals, 12 * nz);
+  const size_t o_tail = up.take(8 * (Nz + 1) * Nz), o_b = up.take(8 * (size_t)m), o_ones = up.take(8 * Nz), o_u = up.copy_of(dev ? nullptr : u, 8 * nz),
+               o_v = up.copy_of(dev ? nullptr : v, 8 * nz), o_n = dev ? up.take(0) : ndb ? up.copy_of(sel, 4 * nz) : up.copy_of(normals, 12 * nz);
   Arena ws;   // x and the scalars of the solve are neighbours: one memset, and the block down lies on them
   const size_t o_A = ws.take(rows + up.size), o_r = ws.take(8 * (size_t)m), o_ddx = ws.take(8 * Nz), o_G = ws.take(8 * Nz * Nz), o_g = ws.take(8 * Nz),
                o_M = ws.take(8 * (size_t)np * np), o_W = ws.take(8 * (size_t)np * 16), o_x = ws.take(8 * Nz), o_scal = ws.take(256), o_pick = ws.take(ndb ? 12 * nz : 0);
@@ -128,13 +138,14 @@ static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u
   if (const int rc = up.send(c)) return rc;
   HIPCHK(c, hipMemsetAsync(w + o_A, 0, rows, st));
   HIPCHK(c, hipMemsetAsync(w + o_x, 0, o_scal + 256 - o_x, st));
-  const float* dn = up.dev<float>(o_n);
-  if (ndb && n > 0) {
+  const float* dn = dev ? dev->normals : up.dev<float>(o_n);
+  const double *du = dev ? dev->u : up.dev<double>(o_u), *dv = dev ? dev->v : up.dev<double>(o_v);
+  if (!dev && ndb && n > 0) {
     dn = reinterpret_cast<float*>(w + o_pick);
     HIPCHK(c, ddb_pick_normals(n, up.dev<int32_t>(o_n), ndb->last_normals, ndb->last_normals + 3 * (size_t)ndb->last_P, reinterpret_cast<float*>(w + o_pick), st));
   }
   double *dA = f64(o_A), *dx = f64(o_x), *db = up.dev<double>(o_b), *dones = up.dev<double>(o_ones);
-  HIPCHK(c, nrsfm_sfn_rows(bbs_par(bbs, 1), n, up.dev<double>(o_u), up.dev<double>(o_v), dn, dA, st));
+  HIPCHK(c, nrsfm_sfn_rows(bbs_par(bbs, 1), n, du, dv, dn, dA, st));
   // x0: G x = A^T b  (the solve kernel returns M dx = -g, so it is fed g = A^T (-(b - A x)))
   for (int it = 0; it < 3; it++) {
     HIPCHK(c, nrsfm_sfn_residual(m, N, dA, dx, db, -1.0, f64(o_r), st));
@@ -162,12 +173,19 @@ static int sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u
   // second pair (x is not read past this point: the blocks reuse the page-locked buffers)
   const size_t na = (size_t)n_all;
   UpBlock up2;
-  const size_t o_ctrl = up2.copy_of(ctrl, 8 * Nz), o_ua = up2.copy_of(u_all, 8 * na), o_va = up2.copy_of(v_all, 8 * na);
+  const size_t o_ctrl = up2.copy_of(ctrl, 8 * Nz), o_ua = up2.copy_of(dev ? nullptr : u_all, 8 * na), o_va = up2.copy_of(dev ? nullptr : v_all, 8 * na);
   DownBlock down2;
   const size_t d_pts = down2.copy_to(pts, 12 * na);
   if (const int rc = up2.copy(c)) return rc;
-  if (const int rc = down2.alloc(c)) return rc;
-  HIPCHK(c, nrsfm_sfn_points(bbs_par(bbs, 1), up2.dev<double>(o_ctrl), n_all, up2.dev<double>(o_ua), up2.dev<double>(o_va), down2.dev<float>(d_pts), st));
+  if (dev) {
+    // the surface points are evaluated into the place the caller keeps them in and come down from there; the control points follow
+    if (const int rc = down2.at(c, dev->pts)) return rc;
+    HIPCHK(c, nrsfm_sfn_points(bbs_par(bbs, 1), up2.dev<double>(o_ctrl), n_all, dev->u_all, dev->v_all, dev->pts, st));
+    HIPCHK(c, hipMemcpyAsync(dev->ctrl, up2.dev<double>(o_ctrl), 8 * Nz, hipMemcpyDeviceToDevice, st));
+  } else {
+    if (const int rc = down2.alloc(c)) return rc;
+    HIPCHK(c, nrsfm_sfn_points(bbs_par(bbs, 1), up2.dev<double>(o_ctrl), n_all, up2.dev<double>(o_ua), up2.dev<double>(o_va), down2.dev<float>(d_pts), st));
+  }
   if (const int rc = down2.receive(c)) return rc;
   *ok = 1;
   return DSH_OK;

@@ -51,7 +51,8 @@ std::string input_error(const dsh_mpdb* db, const dsh_keyframe_register_input* i
   const int32_t N = db->kf[in->slot].N;
   if (in->N != N) return "N (" + std::to_string(in->N) + ") is not the N of keyframe " + std::to_string(in->slot) + " in the store (" + std::to_string(N) + ")";
   if (N > SR_MAX_KEYPOINTS) return "the keyframe has more than 8192 key points";
-  if (!in->Twc || (N > 0 && !in->surface_pts)) return "Twc or surface_pts is NULL";
+  // a NULL surface_pts names the keyframe's resident surface points (dsh_keyframe_surface_init); without them it is the refusal it was
+  if (!in->Twc || (N > 0 && !in->surface_pts && !db->surf[in->slot].has_surface)) return "Twc or surface_pts is NULL";
   if (!pose_finite(in->Twc)) return "Twc is not finite";
   if (with_stream && (in->nu < 0 || (in->nu > 0 && !in->u))) return "nu < 0, or u is NULL";
   if (in->kfdb) {
@@ -62,8 +63,9 @@ std::string input_error(const dsh_mpdb* db, const dsh_keyframe_register_input* i
   return "";
 }
 
-// The selection: surface points and Twc go up, the launch leaves the clouds in scratch (or, when `clouds` asks for them, in the block
-// down) and the counts and pair_idx come down; synchronised on return.  pairs receives pair_idx; *surface_dev: the uploaded surface points.
+// The selection: surface points (unless the keyframe's resident ones are read) and Twc go up, the launch leaves the clouds in scratch
+// (or, when `clouds` asks for them, in the block down) and the counts and pair_idx come down; synchronised on return.  pairs receives
+// pair_idx; *surface_dev: the surface points on the device, uploaded or resident.
 // LIFETIME: d and *surface_dev point into slices of the context's scratch that outlive the UpBlock / DownBlock objects of this function.
 // The scratch only grows within a call and is reset by dsh_enter alone, which an entry point calls once, at its start; the stages of
 // dsh_register.h take further slices and never enter.  So the pointers hold until the caller returns, and no longer: nothing that calls
@@ -73,18 +75,19 @@ int select_clouds(dsh_mpdb* db, const dsh_keyframe_register_input* in, bool clou
   dsh_ctx_base* c = db->ctx;
   const size_t N = (size_t)in->N;
   UpBlock up;
-  const size_t o_T = up.take(64), o_surf = up.take_exact(12 * N);
+  const bool resident = !in->surface_pts && db->surf[in->slot].has_surface;
+  const size_t o_T = up.take(64), o_surf = up.take_exact(resident ? 0 : 12 * N);
   DownBlock down;
   const size_t d_cnt = down.take(sizeof(SrCounts)), d_idx = down.take(4 * N), d_a = down.take(clouds ? 12 * N : 0), d_b = down.take_exact(clouds ? 12 * N : 0);
   if (const int rc = up.stage(c)) return rc;
   std::memcpy(up.host<float>(o_T), in->Twc, 64);
-  if (N > 0) std::memcpy(up.host<float>(o_surf), in->surface_pts, 12 * N);
+  if (N > 0 && !resident) std::memcpy(up.host<float>(o_surf), in->surface_pts, 12 * N);
   if (const int rc = up.send(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   SrSelect k;
   k.kf = keyframe_slice(db, in->slot);
   k.P = db->P;
-  k.surface = up.dev<const float>(o_surf);
+  k.surface = resident ? db->d_surf_pts + 3 * (size_t)k.kf.tab_off : up.dev<const float>(o_surf);
   k.Twc = up.dev<const float>(o_T);
   k.pair_idx = down.dev<int32_t>(d_idx);
   k.counts = down.dev<SrCounts>(d_cnt);
@@ -113,8 +116,10 @@ void put_counts(dsh_keyframe_register_result* out, const SrCounts& s) {
   out->n_pairs = s.n_pairs; out->n_empty = s.n_empty; out->n_bad = s.n_bad; out->n_no_facet = s.n_no_facet; out->n_no_snapshot = s.n_no_snapshot;
 }
 
-// the finishing launch: surface_scaled (N > 0) and the centre come down; kfdb: the store whose centre is written, or null
-int finish(dsh_ctx_base* c, int32_t N, const float* surface_dev, double s22, const float* Tcw, dsh_kfdb* kfdb, int32_t slot, float* surface_scaled, float* Ow) {
+// the finishing launch: surface_scaled (N > 0) and the centre come down; kfdb: the store whose centre is written, or null; db: the point
+// store when keyframe `slot` of it is the one being registered (its resident Surface, where it has one, is scaled too), or null
+int finish(dsh_ctx_base* c, int32_t N, const float* surface_dev, double s22, const float* Tcw, dsh_kfdb* kfdb, int32_t slot, float* surface_scaled, float* Ow,
+           dsh_mpdb* db) {
   DownBlock down;
   const size_t d_Ow = down.take(12), d_s = down.take_exact(12 * (size_t)N);
   if (const int rc = down.alloc(c)) return rc;
@@ -126,6 +131,15 @@ int finish(dsh_ctx_base* c, int32_t N, const float* surface_dev, double s22, con
   k.kf_slot = kfdb ? kfdb->d_slots + slot : nullptr;
   k.surface_scaled = down.dev<float>(d_s);
   k.Ow = down.dev<float>(d_Ow);
+  k.resident_pts = nullptr; k.resident_depth = nullptr; k.n_depth = 0;
+  if (db && db->surf[slot].has_surface) {   // Surface::applyScale of the copy the store holds (Surface.cc:107-121)
+    const dsh_mpdb::SurfKf& sk = db->surf[slot];
+    k.resident_pts = db->d_surf_pts + 3 * (size_t)db->kf[slot].tab_off;
+    if (sk.has_depth) {
+      k.resident_depth = db->d_surf_depth + (size_t)dsh_mpdb::SURF_MAX_CTRL * slot;
+      k.n_depth = sk.grid.nptsu * sk.grid.nptsv;
+    }
+  }
   HIPCHK(c, sr_finish_launch(k, c->stream));
   if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -232,7 +246,7 @@ int dsh_keyframe_register(dsh_mpdb* db, const dsh_keyframe_register_input* in, i
         return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_register: the registration composed a pose that is not finite; nothing was written");
       }
       // Surface::applyScale of the surface points, KeyFrame::SetPose's centre into the keyframe store
-      if (const int rc = finish(c, in->N, surface_dev, r.s22, r.Tcw_new, in->kfdb, in->slot, surface_scaled, r.Ow_new)) return rc;
+      if (const int rc = finish(c, in->N, surface_dev, r.s22, r.Tcw_new, in->kfdb, in->slot, surface_scaled, r.Ow_new, db)) return rc;
       r.registered = 1;
     }
   }
@@ -250,7 +264,7 @@ int dsh_keyframe_set_pose(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float
   const std::string ke = centre_error(c, in->kfdb, in->slot);
   if (!ke.empty()) return bad(ke);
   if (const int rc = dsh_enter(c, "dsh_keyframe_set_pose")) return rc;
-  return finish(c, 0, nullptr, 1.0, in->Tcw, in->kfdb, in->slot, nullptr, Ow);
+  return finish(c, 0, nullptr, 1.0, in->Tcw, in->kfdb, in->slot, nullptr, Ow, nullptr);
 }
 
 int dsh_keyframe_get_centre(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float* Ow) {

@@ -50,6 +50,43 @@ void fill_keypoints(TsSwitch& k, const dsh_mpdb* db, int32_t slot, const dsh_kf_
 
 }  // namespace
 
+namespace dsh {
+// The body of dsh_surface_vertices and dsh_keyframe_surface_vertices, after the checks and the device gate: ctrl_dev, when given, is the
+// depth spline where it lies on the device and grid->depth_ctrl is not read (its slice of the block up stays empty).
+int surface_vertices_run(dsh_ctx_base* c, const dsh_surface_grid* grid, const double* ctrl_dev, double* nodes_xyz) {
+  const dsh_bbs* b = grid->bbs;
+  const size_t n = (size_t)grid->xs * grid->ys, nctrl = (size_t)b->nptsu * b->nptsv;
+  UpBlock up;
+  const size_t o_T = up.take(64), o_ctrl = up.take(ctrl_dev ? 0 : 8 * nctrl), o_u = up.take(8 * n), o_v = up.take(8 * n);
+  DownBlock down;
+  const size_t d_xyz = down.take_exact(24 * n);
+  if (const int rc = up.stage(c)) return rc;
+  std::memcpy(up.host<float>(o_T), grid->Twc, 64);
+  if (!ctrl_dev) std::memcpy(up.host<double>(o_ctrl), grid->depth_ctrl, 8 * nctrl);
+  double *u = up.host<double>(o_u), *v = up.host<double>(o_v);
+  const unsigned int xs = (unsigned)grid->xs, ys = (unsigned)grid->ys;
+  const double t = 0.03;
+  size_t us = 0;
+  for (unsigned int x = 0; x < xs; x++)
+    for (unsigned int j = 0; j < ys; j++, us++) {   // Surface.cc:136-146
+      u[us] = double((b->umax - b->umin - 2 * t) * x) / (xs - 1) + (b->umin + t);
+      v[us] = double((b->vmax - b->vmin - 2 * t) * j) / (ys - 1) + (b->vmin + t);
+    }
+  if (const int rc = up.send(c)) return rc;
+  if (const int rc = down.alloc(c)) return rc;
+  double* d_val = nullptr;
+  HIPCHK(c, dsh_scratch_array(c, &d_val, n));
+  HIPCHK(c, nrsfm_launch_bbs_eval(bbs_par(b, 1), ctrl_dev ? ctrl_dev : up.dev<const double>(o_ctrl), up.dev<const double>(o_u),
+                                  up.dev<const double>(o_v), (int)n, 0, 0, d_val, nullptr, c->stream));
+  HIPCHK(c, ts_vertices_launch(up.dev<const double>(o_u), up.dev<const double>(o_v), d_val, up.dev<const float>(o_T), (int)n, down.dev<double>(d_xyz),
+                               c->stream));
+  if (const int rc = down.fetch(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(nodes_xyz, down.host<double>(d_xyz), 24 * n);
+  return DSH_OK;
+}
+}  // namespace dsh
+
 extern "C" {
 
 int dsh_surface_vertices(const dsh_surface_grid* grid, double* nodes_xyz) {
@@ -64,36 +101,7 @@ int dsh_surface_vertices(const dsh_surface_grid* grid, double* nodes_xyz) {
   if (grid->xs < 2 || grid->ys < 2) return bad("xs and ys must be at least 2");
   if ((long long)grid->xs * grid->ys > (1 << 24)) return bad("more than 2^24 vertices");
   if (const int rc = dsh_enter(c, "dsh_surface_vertices")) return rc;
-
-  const size_t n = (size_t)grid->xs * grid->ys, nctrl = (size_t)b->nptsu * b->nptsv;
-  UpBlock up;
-  const size_t o_T = up.take(64), o_ctrl = up.take(8 * nctrl), o_u = up.take(8 * n), o_v = up.take(8 * n);
-  DownBlock down;
-  const size_t d_xyz = down.take_exact(24 * n);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<float>(o_T), grid->Twc, 64);
-  std::memcpy(up.host<double>(o_ctrl), grid->depth_ctrl, 8 * nctrl);
-  double *u = up.host<double>(o_u), *v = up.host<double>(o_v);
-  const unsigned int xs = (unsigned)grid->xs, ys = (unsigned)grid->ys;
-  const double t = 0.03;
-  size_t us = 0;
-  for (unsigned int x = 0; x < xs; x++)
-    for (unsigned int j = 0; j < ys; j++, us++) {   // Surface.cc:136-146
-      u[us] = double((b->umax - b->umin - 2 * t) * x) / (xs - 1) + (b->umin + t);
-      v[us] = double((b->vmax - b->vmin - 2 * t) * j) / (ys - 1) + (b->vmin + t);
-    }
-  if (const int rc = up.send(c)) return rc;
-  if (const int rc = down.alloc(c)) return rc;
-  double* d_val = nullptr;
-  HIPCHK(c, dsh_scratch_array(c, &d_val, n));
-  HIPCHK(c, nrsfm_launch_bbs_eval(bbs_par(b, 1), up.dev<const double>(o_ctrl), up.dev<const double>(o_u),
-                                  up.dev<const double>(o_v), (int)n, 0, 0, d_val, nullptr, c->stream));
-  HIPCHK(c, ts_vertices_launch(up.dev<const double>(o_u), up.dev<const double>(o_v), d_val, up.dev<const float>(o_T), (int)n, down.dev<double>(d_xyz),
-                               c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(nodes_xyz, down.host<double>(d_xyz), 24 * n);
-  return DSH_OK;
+  return dsh::surface_vertices_run(c, grid, nullptr, nodes_xyz);
 }
 
 int dsh_need_new_template(dsh_mpdb* db, int32_t slot, const dsh_kf_keypoints* kf, int32_t* n_candidates, uint8_t* candidate) {
@@ -144,7 +152,9 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   if (hk.N != kf.N) return bad("kf->N is not the N of keyframe " + std::to_string(in->slot) + " in the keyframe store");
   for (int i = 0; i < kf.N; i++)
     if (hk.octave[i] >= hk.levels) return bad("key point " + std::to_string(i) + " has an octave >= levels in the keyframe store");
-  if (!in->Twc || (kf.N > 0 && !in->surface_pts)) return bad("Twc or surface_pts is NULL");
+  // a NULL surface_pts names the keyframe's resident surface points (dsh_keyframe_surface_init); without them it is the refusal it was
+  const bool resident = !in->surface_pts && db->surf[in->slot].has_surface;
+  if (!in->Twc || (kf.N > 0 && !in->surface_pts && !resident)) return bad("Twc or surface_pts is NULL");
   if (!out) return bad("out is NULL");
   if ((long long)db->P + kf.N > INT32_MAX) return bad("store full");
   const dsh::TemplateHost* t = dsh_facet_template(c);
@@ -158,7 +168,7 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
 
   // up: the counts (zero), Twc, the key points, the surface points, the octaves and scale factors, the template
   UpBlock up;
-  const size_t o_cnt = up.take(sizeof(TsCounts)), o_T = up.take(64), o_kp = up.take(8 * N), o_surf = up.take(12 * N), o_oct = up.take(N),
+  const size_t o_cnt = up.take(sizeof(TsCounts)), o_T = up.take(64), o_kp = up.take(8 * N), o_surf = up.take(resident ? 0 : 12 * N), o_oct = up.take(N),
                o_sf = up.take(4 * MPU_MAX_LEVELS), o_xyz0 = up.take(24 * (size_t)t->n), o_fac = up.take(12 * (size_t)t->F),
                o_nfp = up.take(4 * (size_t)(t->n + 1)), o_nfi = up.take(4 * t->nf_idx.size());
   DownBlock down;   // the counts start as a copy of the uploaded zeros
@@ -170,7 +180,7 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   std::memcpy(up.host<float>(o_T), in->Twc, 64);
   if (N > 0) {
     std::memcpy(up.host<float>(o_kp), kf.kp, 8 * N);
-    std::memcpy(up.host<float>(o_surf), in->surface_pts, 12 * N);
+    if (!resident) std::memcpy(up.host<float>(o_surf), in->surface_pts, 12 * N);
     std::memcpy(up.host<int8_t>(o_oct), hk.octave.data(), N);
   }
   std::memcpy(up.host<float>(o_sf), hk.sf, 4 * MPU_MAX_LEVELS);
@@ -184,7 +194,7 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   TsSwitch k;
   fill_keypoints(k, db, in->slot, kf);
   k.kp = up.dev<const float>(o_kp);
-  k.surface = up.dev<const float>(o_surf);
+  k.surface = resident ? db->d_surf_pts + 3 * (size_t)db->kf[in->slot].tab_off : up.dev<const float>(o_surf);
   k.Twc = up.dev<const float>(o_T);
   k.octave = up.dev<const int8_t>(o_oct);
   k.sf = up.dev<const float>(o_sf);

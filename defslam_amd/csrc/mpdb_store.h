@@ -11,6 +11,7 @@
 //                         observations and keyframe tables
 //   dsh_tracksft.cpp      dsh_track_sft_observations, dsh_track_sft
 //   dsh_surfreg.cpp       dsh_keyframe_snapshot_positions, dsh_keyframe_register and the keyframe pose of the keyframe store
+//   dsh_surfstore.cpp     dsh_keyframe_surface_*, dsh_keyframe_sfn: the resident Surface of a keyframe
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,6 +49,13 @@ struct dsh_mpdb : dsh_store {
   // taken there (-1: none) and that position.  Keyed by point: later edits of the table do not touch it.
   int32_t* d_snap_point = nullptr;
   float* d_snap_xyz = nullptr;
+  // defSLAM::Surface of a keyframe (dsh_keyframe_surface_*), parallel to d_table: per table entry SurfacePoint::Normal, NormalOn and
+  // x3D, and mpKeypointNorm[i].pt.  Per keyframe, parallel to d_kf: numberofNormals_ and the SURF_MAX_CTRL doubles of nodesDepth_.
+  // An entry's four fields mean something from dsh_keyframe_surface_init of its keyframe on (surf[slot].has_surface).
+  float *d_surf_normal = nullptr, *d_surf_pts = nullptr, *d_surf_kpn = nullptr;
+  uint8_t* d_surf_has = nullptr;
+  int32_t* d_surf_nn = nullptr;
+  double* d_surf_depth = nullptr;
   LmHdr* d_hdr = nullptr;
   // the resident last-frame list (dsh_track_end_frame): per key point of the last frame the id it holds or -1, and its octave (-1 there)
   int32_t *d_last_ids = nullptr, *d_last_oct = nullptr;
@@ -57,6 +65,13 @@ struct dsh_mpdb : dsh_store {
   std::unordered_set<uint64_t> unindexed;        // the live records without a key point index (dsh_mpdb_add_observations)
   std::vector<LmKf> kf;
   std::vector<uint8_t> snapped;          // per keyframe: its snapshot has been taken (the reference takes it once, in the constructor)
+  static constexpr int SURF_MAX_CTRL = 512;   // control points of a resident depth spline: the limit of dsh_sfn_estimate
+  struct SurfKf {                        // per keyframe: what the host knows of its resident Surface
+    uint8_t has_surface = 0, has_depth = 0;
+    int32_t n_normals = 0;               // numberofNormals_, as d_surf_nn holds it
+    dsh_bbs grid{};                      // of the depth spline, valdim 1
+  };
+  std::vector<SurfKf> surf;
   int32_t n_local_points = 0;
   int32_t n_ref_points = 0;            // length of d_ref_ids
   int32_t P_cnt = 0;                   // points d_cnt covers: the store's size at the last dsh_local_map_update
@@ -89,7 +104,8 @@ struct dsh_mpdb : dsh_store {
   void free_all() {
     for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
                     (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
-                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx, (void*)d_snap_point, (void*)d_snap_xyz})
+                    (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx, (void*)d_snap_point, (void*)d_snap_xyz,
+                    (void*)d_surf_normal, (void*)d_surf_pts, (void*)d_surf_kpn, (void*)d_surf_has, (void*)d_surf_nn, (void*)d_surf_depth})
       if (p) (void)hipFree(p);
   }
 };
@@ -140,13 +156,16 @@ inline hipError_t mpdb_reserve_last_frame(dsh_mpdb* db, int32_t N) {
   return hipSuccess;
 }
 
-// room for `need` table entries: the tables and the snapshot beside them
+// room for `need` table entries: the tables, the snapshot and the surface points beside them
 inline hipError_t mpdb_reserve_table(dsh_mpdb* db, long long need) {
-  if (need <= db->Tcap && db->d_table && db->d_snap_point && db->d_snap_xyz) return hipSuccess;
+  if (need <= db->Tcap && db->d_table && db->d_snap_point && db->d_snap_xyz && db->d_surf_normal && db->d_surf_pts && db->d_surf_kpn && db->d_surf_has)
+    return hipSuccess;
   const size_t cap = (size_t)std::max(need, db->d_table ? 2 * db->Tcap : db->Tcap), T = (size_t)db->T;
   hipError_t e;
   if ((e = dsh_store_grow_array(&db->d_table, T, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_snap_point, T, cap)) != hipSuccess ||
-      (e = dsh_store_grow_array(&db->d_snap_xyz, 3 * T, 3 * cap)) != hipSuccess)
+      (e = dsh_store_grow_array(&db->d_snap_xyz, 3 * T, 3 * cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_surf_normal, 3 * T, 3 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_surf_pts, 3 * T, 3 * cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_surf_kpn, 2 * T, 2 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_surf_has, T, cap)) != hipSuccess)
     return e;
   db->Tcap = (long long)cap;
   return hipSuccess;
@@ -156,7 +175,10 @@ inline hipError_t mpdb_reserve_keyframes(dsh_mpdb* db, long long need) {
   if (need <= db->Kcap) return hipSuccess;
   const size_t cap = (size_t)std::min<long long>(std::max(need, 2ll * db->Kcap), INT32_MAX), K = (size_t)db->K;
   hipError_t e;
-  if ((e = dsh_store_grow_array(&db->d_kf, K, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_local_kf, K, cap)) != hipSuccess) return e;
+  if ((e = dsh_store_grow_array(&db->d_kf, K, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_local_kf, K, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_surf_nn, K, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_surf_depth, (size_t)dsh_mpdb::SURF_MAX_CTRL * K, (size_t)dsh_mpdb::SURF_MAX_CTRL * cap)) != hipSuccess)
+    return e;
   db->Kcap = (int32_t)cap;
   return hipSuccess;
 }

@@ -105,7 +105,12 @@ __global__ __launch_bounds__(SR_BLOCK) void sr_select_kernel(TcState s, SrSelect
 __global__ __launch_bounds__(SR_FINISH_BLOCK) void sr_finish_kernel(SrFinish k) {
   const int i = blockIdx.x * SR_FINISH_BLOCK + threadIdx.x;
   // Surface::applyScale on a cv::Vec3f: Vec * double, rounded to float32 per component
-  if (i < 3 * k.N) k.surface_scaled[i] = (float)((double)k.surface[i] * k.s22);
+  if (i < 3 * k.N) {
+    k.surface_scaled[i] = (float)((double)k.surface[i] * k.s22);
+    if (k.resident_pts) k.resident_pts[i] = (float)((double)k.resident_pts[i] * k.s22);
+  }
+  // Surface.cc:117-120: nodesDepth_[i] = s22 * nodesDepth_[i]
+  if (k.resident_depth && i < k.n_depth) k.resident_depth[i] = k.s22 * k.resident_depth[i];
   if (blockIdx.x == 0 && threadIdx.x < 3) {
     // KeyFrame::SetPose: Ow = -Rcw.t() * tcw, the three products of a row summed left to right in float32
     const float* T = k.Tcw;
@@ -131,6 +136,7 @@ extern "C" hipError_t sr_select_launch(const TcState& s, const SrSelect& k, hipS
 }
 
 extern "C" hipError_t sr_finish_launch(const SrFinish& k, hipStream_t st) {
-  hipLaunchKernelGGL(sr_finish_kernel, blocks_for(3 * (long long)k.N > 0 ? 3 * (long long)k.N : 1, SR_FINISH_BLOCK), dim3(SR_FINISH_BLOCK), 0, st, k);
+  const long long work = 3 * (long long)k.N > (k.resident_depth ? k.n_depth : 0) ? 3 * (long long)k.N : (k.resident_depth ? k.n_depth : 0);
+  hipLaunchKernelGGL(sr_finish_kernel, blocks_for(work > 0 ? work : 1, SR_FINISH_BLOCK), dim3(SR_FINISH_BLOCK), 0, st, k);
   return hipGetLastError();
 }

@@ -47,11 +47,15 @@ struct SrFinish {
   MpuSlot* kf_slot;          // the keyframe's record in dsh_kfdb, or null
   float* surface_scaled;     // N x 3
   float* Ow;                 // 3: the centre, always written
+  // the keyframe's resident Surface (dsh_keyframe_surface_init), or nulls: Surface::applyScale of the copy the store holds, in place
+  float* resident_pts;       // N x 3; may be `surface` itself
+  double* resident_depth;    // n_depth control points of nodesDepth_, or null
+  int32_t n_depth;
 };
 
 // one launch, one workgroup: snap_point / snap_xyz of the entries whose point is not bad and has a facet; *n_taken = their number
 extern "C" hipError_t sr_snapshot_launch(const TcState& s, const SrKeyframe& k, int32_t* n_taken, hipStream_t st);
 // one launch, one workgroup: the pairs of SurfaceRegistration.cc:60-104 in ascending entry order, and the counts
 extern "C" hipError_t sr_select_launch(const TcState& s, const SrSelect& k, hipStream_t st);
-// one launch: Surface::applyScale of the surface points and KeyFrame::SetPose's camera centre
+// one launch: Surface::applyScale of the surface points (and of the resident Surface) and KeyFrame::SetPose's camera centre
 extern "C" hipError_t sr_finish_launch(const SrFinish& k, hipStream_t st);

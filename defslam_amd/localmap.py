@@ -332,6 +332,41 @@ class KeyframeRegistration:
     surface_scaled: Optional[np.ndarray]   # (N,3) float32 Surface::applyScale of the surface points; None when not registered
 
 
+@dataclass
+class KeyframeSurface:
+    """What dsh_keyframe_surface_get returns: the resident defSLAM::Surface of a keyframe."""
+    normals: np.ndarray                 # (N,3) float32 SurfacePoint::Normal, zeros where none was set
+    has_normal: np.ndarray              # (N,) bool SurfacePoint::NormalOn
+    pts: np.ndarray                     # (N,3) float32 SurfacePoint::x3D
+    kpn: np.ndarray                     # (N,2) float32 mpKeypointNorm
+    ctrl: Optional[np.ndarray]          # (nptsu * nptsv,) float64 nodesDepth_; None without a depth spline
+    bbs: object                         # nrsfm.Bbs of the depth spline; None without one
+    n_normals: int                      # numberofNormals_
+    enough_normals: bool                # Surface::enoughNormals
+
+
+@dataclass
+class SurfaceGather:
+    """What dsh_keyframe_surface_gather returns: x0 / has_x0 / ref_uv of a normal solve."""
+    normal_xy: np.ndarray               # (n,2) float32 Ni(0), Ni(1); zeros without a normal
+    has: np.ndarray                     # (n,) uint8 Surface::getNormalSurfacePoint's return value
+    uv: np.ndarray                      # (n,2) float32 mpKeypointNorm
+
+
+@dataclass
+class KeyframeSfn:
+    """What dsh_keyframe_sfn returns (ShapeFromNormals::estimate of a keyframe from the store)."""
+    ok: bool
+    n_sites: int
+    n_empty: int                        # entries without a point
+    n_bad: int                          # entries whose point is bad
+    n_no_normal: int                    # entries without a normal
+    n_nan: int                          # entries whose normal has a NaN component
+    ctrl_raw: np.ndarray                # (nptsu * nptsv,) float64 the control points before the scaling
+    ctrl: Optional[np.ndarray]          # the scaled control points, None when not ok
+    pts: Optional[np.ndarray]           # (N,3) float32 the surface points, None when not ok
+
+
 # dsh_point_store_erase_observations: what became of a pair
 ERASE_NOT_STORED, ERASE_DONE, ERASE_SET_BAD = 0, 1, 2
 
@@ -729,7 +764,7 @@ class MapPointStore:
         Surface::get3DSurfacePoint per key point, Twc (4,4) float32 the keyframe's GetPoseInverse()."""
         keep = []
         k = kf.c(keep)
-        sp = np.ascontiguousarray(surface_pts, np.float32).reshape(-1, 3)
+        sp = None if surface_pts is None else np.ascontiguousarray(surface_pts, np.float32).reshape(-1, 3)   # None: the resident ones
         T = np.ascontiguousarray(Twc, np.float32).reshape(16)
         inp = _lib.TemplateSwitchInputC(kf_store._h if kf_store is not None else None, int(slot), C.pointer(k), _ptr(sp, C.c_float), _ptr(T, C.c_float))
         idx = np.zeros(max(k.N, 1), np.int32)
@@ -852,11 +887,12 @@ class MapPointStore:
         return pt[:N], x[:N]
 
     def _register_input(self, kf_store, slot, surface_pts, Twc, u, chi_limit, check_chi, keep: list) -> _lib.KeyframeRegisterInputC:
-        sp = np.ascontiguousarray(surface_pts, np.float32).reshape(-1, 3)
+        # surface_pts None: the keyframe's resident surface points (surface_init)
+        sp = None if surface_pts is None else np.ascontiguousarray(surface_pts, np.float32).reshape(-1, 3)
         T = np.ascontiguousarray(Twc, np.float32).reshape(16)
         uu = None if u is None else np.ascontiguousarray(u, np.float64).reshape(-1)
         keep += [sp, T, uu]
-        return _lib.KeyframeRegisterInputC(kf_store._h if kf_store is not None else None, int(slot), int(sp.shape[0]), _ptr(sp, C.c_float),
+        return _lib.KeyframeRegisterInputC(kf_store._h if kf_store is not None else None, int(slot), self._kf_len(slot) if sp is None else int(sp.shape[0]), _ptr(sp, C.c_float),
                                            _ptr(T, C.c_float), _ptr(uu, C.c_double), 0 if uu is None else uu.shape[0], float(chi_limit),
                                            int(bool(check_chi)))
 
@@ -914,6 +950,99 @@ class MapPointStore:
         Ow = np.zeros(3, np.float32)
         self._call("dsh_keyframe_get_centre", C.byref(inp), _ptr(Ow, C.c_float))
         return Ow
+
+    # ---- the mapping thread: the resident Surface of a keyframe ----
+    def surface_init(self, slot: int, kpn):
+        """Surface(N) of DefKeyFrame's constructor for keyframe `slot`, with mpKeypointNorm kpn (N,2) float32.  Once per keyframe."""
+        k = np.ascontiguousarray(kpn, np.float32).reshape(-1, 2)
+        self._call("dsh_keyframe_surface_init", int(slot), int(k.shape[0]), _ptr(k, C.c_float))
+
+    def surface_set_depth(self, slot: int, bbs, ctrl):
+        """Surface::saveArray: the depth spline of keyframe `slot` (bbs: nrsfm.Bbs, ctrl (nptsu * nptsv,) float64)."""
+        b = bbs.c()
+        x = np.ascontiguousarray(ctrl, np.float64).reshape(-1)
+        if x.shape[0] != bbs.nptsu * bbs.nptsv:
+            raise ValueError("ctrl does not have nptsu * nptsv entries")
+        self._call("dsh_keyframe_surface_set_depth", int(slot), C.byref(b), _ptr(x, C.c_double))
+
+    def surface_set_points(self, slot: int, idx, pts):
+        """Surface::set3DSurfacePoint from the host: pts (n,3) float32 for the distinct key points idx of keyframe `slot`."""
+        i, x = _i32(idx), np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        if i.shape[0] != x.shape[0]:
+            raise ValueError("idx and pts differ in length")
+        self._call("dsh_keyframe_surface_set_points", int(slot), i.shape[0], _ptr(i, C.c_int32), _ptr(x, C.c_float))
+
+    def surface_set_normals(self, slots, idx, normals) -> np.ndarray:
+        """Surface::setNormalSurfacePoint in call order for the targets (slots[j], idx[j]) with normals (n,3) float32; returns each target
+        keyframe's n_normals after the call."""
+        s, i, x = _i32(slots), _i32(idx), np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if not s.shape[0] == i.shape[0] == x.shape[0]:
+            raise ValueError("slots, idx and normals differ in length")
+        nn = np.zeros(max(s.shape[0], 1), np.int32)
+        self._call("dsh_keyframe_surface_set_normals", s.shape[0], _ptr(s, C.c_int32), _ptr(i, C.c_int32), _ptr(x, C.c_float), _ptr(nn, C.c_int32))
+        return nn[:s.shape[0]]
+
+    def surface_take_normals(self, diff_db, sel, slots, idx) -> np.ndarray:
+        """The same with normal j picked on the device from the last normal solve of diff_db (nrsfm.DiffDatabase): sel >= 0 is normal_ref
+        of that point, sel < 0 record -1 - sel."""
+        q, s, i = _i32(sel), _i32(slots), _i32(idx)
+        if not q.shape[0] == s.shape[0] == i.shape[0]:
+            raise ValueError("sel, slots and idx differ in length")
+        nn = np.zeros(max(s.shape[0], 1), np.int32)
+        inp = _lib.SurfaceTakeInputC(diff_db._h if diff_db is not None else None, s.shape[0], _ptr(q, C.c_int32), _ptr(s, C.c_int32), _ptr(i, C.c_int32))
+        self._call("dsh_keyframe_surface_take_normals", C.byref(inp), _ptr(nn, C.c_int32))
+        return nn[:s.shape[0]]
+
+    def surface_gather(self, slots, idx) -> SurfaceGather:
+        """x0 / has_x0 / ref_uv of a normal solve for the targets (slots[j], idx[j])."""
+        s, i = _i32(slots), _i32(idx)
+        if s.shape[0] != i.shape[0]:
+            raise ValueError("slots and idx differ in length")
+        n = s.shape[0]
+        m = max(n, 1)
+        nxy, has, uv = np.zeros((m, 2), np.float32), np.zeros(m, np.uint8), np.zeros((m, 2), np.float32)
+        self._call("dsh_keyframe_surface_gather", n, _ptr(s, C.c_int32), _ptr(i, C.c_int32), _ptr(nxy, C.c_float), _ptr(has, C.c_uint8), _ptr(uv, C.c_float))
+        return SurfaceGather(normal_xy=nxy[:n], has=has[:n], uv=uv[:n])
+
+    def surface_get(self, slot: int) -> KeyframeSurface:
+        """The resident Surface of keyframe `slot`, read back."""
+        from .nrsfm import Bbs
+        N = self._kf_len(slot)
+        m = max(N, 1)
+        nr, has, pts, kpn = np.zeros((m, 3), np.float32), np.zeros(m, np.uint8), np.zeros((m, 3), np.float32), np.zeros((m, 2), np.float32)
+        ctrl = np.zeros(512, np.float64)
+        info = _lib.KeyframeSurfaceInfoC()
+        self._call("dsh_keyframe_surface_get", int(slot), N, _ptr(nr, C.c_float), _ptr(has, C.c_uint8), _ptr(pts, C.c_float), _ptr(kpn, C.c_float),
+                   _ptr(ctrl, C.c_double), C.byref(info))
+        g = info.grid
+        bbs = Bbs(g.umin, g.umax, g.nptsu, g.vmin, g.vmax, g.nptsv, g.valdim) if info.has_depth else None
+        return KeyframeSurface(normals=nr[:N], has_normal=has[:N].astype(bool), pts=pts[:N], kpn=kpn[:N],
+                               ctrl=ctrl[:g.nptsu * g.nptsv].copy() if info.has_depth else None, bbs=bbs, n_normals=int(info.n_normals),
+                               enough_normals=bool(info.enough_normals))
+
+    def sfn(self, slot: int, bbs, bending_weight: float, mean_depth: float) -> KeyframeSfn:
+        """ShapeFromNormals::estimate of keyframe `slot` from the store: obtainM's selection on the device, the stages of
+        nrsfm.ShapeFromNormals on its sites; when ok the surface points and the depth spline of the keyframe are the new ones."""
+        b = bbs.c()
+        N, Nc = self._kf_len(slot), bbs.nptsu * bbs.nptsv
+        raw, ctrl, pts = np.zeros(Nc, np.float64), np.zeros(Nc, np.float64), np.zeros((max(N, 1), 3), np.float32)
+        inp = _lib.KeyframeSfnInputC(self._ctx._h, int(slot), C.pointer(b), float(bending_weight), float(mean_depth))
+        r = _lib.KeyframeSfnResultC()
+        self._call("dsh_keyframe_sfn", C.byref(inp), _ptr(raw, C.c_double), _ptr(ctrl, C.c_double), _ptr(pts, C.c_float), C.byref(r))
+        ok = bool(r.ok)
+        return KeyframeSfn(ok=ok, ctrl_raw=raw, ctrl=ctrl if ok else None, pts=pts[:N] if ok else None,
+                           **{n: int(getattr(r, n)) for n in ("n_sites", "n_empty", "n_bad", "n_no_normal", "n_nan")})
+
+    def surface_state(self, slot: int) -> int:
+        """0: keyframe `slot` has no resident Surface, 1: a Surface, 2: a Surface with a depth spline; -1: no such keyframe."""
+        return int(self._ctx._L.dsh_keyframe_surface_state(self._h, int(slot)))
+
+    def surface_vertices(self, slot: int, Twc, xs: int, ys: int) -> np.ndarray:
+        """Surface::getVertex of keyframe `slot` with its resident depth spline: (xs * ys, 3) float64 in world coordinates."""
+        T = np.ascontiguousarray(Twc, np.float32).reshape(16)
+        out = np.zeros((max(int(xs) * int(ys), 1), 3), np.float64)
+        self._call("dsh_keyframe_surface_vertices", int(slot), _ptr(T, C.c_float), int(xs), int(ys), _ptr(out, C.c_double))
+        return out[:int(xs) * int(ys)]
 
     def keyframe_table(self, slot: int) -> np.ndarray:
         """KeyFrame::GetMapPointMatches of keyframe `slot` as ids or -1."""

@@ -1225,7 +1225,8 @@ int dsh_point_store_get_keyframe_table(dsh_mpdb* db, int32_t slot, int32_t capac
  * nothing is mutated.
  * When registered, one finishing launch
  *   - writes surface_scaled[i] = (float)((double)s_i * s22) per component for all N entries (may be NULL): Surface::applyScale on a
- *     cv::Vec3f, a reading of OpenCV's Vec * double (no OpenCV build to check against); nodesDepth_ stays with the caller;
+ *     cv::Vec3f, a reading of OpenCV's Vec * double (no OpenCV build to check against); nodesDepth_ stays with the caller unless the
+ *     keyframe has a resident Surface (below), which is scaled in the same launch;
  *   - with a keyframe store given, makes the keyframe's camera centre there the centre of Tcw_new by KeyFrame::SetPose
  *     (Thirdparty/ORBSLAM_2/src/KeyFrame.cc:97-111): Ow[i] = -((R[0][i] * t[0] + R[1][i] * t[1]) + R[2][i] * t[2]) in float32.  It is
  *     returned in Ow_new either way.  dsh_template_switch and dsh_point_store_upkeep, which run next, read that centre.
@@ -1275,6 +1276,101 @@ typedef struct dsh_keyframe_pose_input {
 } dsh_keyframe_pose_input;
 int dsh_keyframe_set_pose(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float* Ow /* 3, may be NULL: the centre written */);
 int dsh_keyframe_get_centre(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float* Ow /* 3 */);
+
+/* ---- the resident Surface of a keyframe ----------------------------------------------------------------------------------
+ * defSLAM::Surface (Modules/Mapping/Surface.cc) holds, per key point of a keyframe, SurfacePoint::Normal with NormalOn and
+ * SurfacePoint::x3D, and per keyframe numberofNormals_ and the depth spline nodesDepth_ with its grid.  The store keeps it beside the
+ * keyframe tables, with DefKeyFrame::mpKeypointNorm[i].pt: per table entry a normal (three float32, zeros), a has-normal flag (0), a
+ * surface point (three float32, zeros as a default cv::Vec3f) and the normalised key point (two float32); per keyframe, with a host
+ * mirror, "has a surface", n_normals, "has a depth spline", its grid and at most 512 doubles of control points.  dsh_mpdb_clear forgets
+ * all of it.  A keyframe has no resident Surface until dsh_keyframe_surface_init, and every other entry here refuses such a keyframe.
+ *
+ * dsh_keyframe_surface_init      Surface(N) in DefKeyFrame's constructor plus mpKeypointNorm (Surface.cc:31-37): N must be the N of the
+ *                                keyframe, kpn[N x 2] finite; once per keyframe, a second call is DSH_ERR_STATE.  The bounding box stays
+ *                                with the caller.
+ * dsh_keyframe_surface_set_depth Surface::saveArray (Surface.cc:50-56): bbs with at most 512 control points, ctrl[nptsu * nptsv].  Serves the
+ *                                plane of ones of MonocularInitialization (DefTracking.cc:617-633) and any host-made spline.
+ * dsh_keyframe_surface_set_points Surface::set3DSurfacePoint (Surface.cc:94-97) from the host: n distinct idx of the keyframe, pts[n x 3].
+ * dsh_keyframe_surface_set_normals Surface::setNormalSurfacePoint (Surface.cc:76-85) for normals the host holds: target j is key point
+ *                                idx[j] of keyframe slot[j], in CALL ORDER -- a target named twice keeps the later normal -- and a
+ *                                keyframe's n_normals goes up once per entry that had no normal before.  The largest j per target is
+ *                                elected with an integer atomic and writes in a second pass, which also counts: the result does not
+ *                                depend on the schedule.  n_normals_out[n] (may be NULL) = each target keyframe's count after the call.
+ * dsh_keyframe_surface_take_normals the same with normal j picked on the device from the last dsh_normals_estimate_db of in->ddb, by sel's
+ *                                convention of dsh_sfn_estimate_db (>= 0: normal_ref of that point, < 0: record -1 - sel).  The normals
+ *                                never visit the host; the caller chooses the entries from the status / rec_written / rec_tag /
+ *                                rec_idx2 the solve returned (NormalEstimator.cc:170, :223).
+ * dsh_keyframe_surface_gather    per target Ni(0), Ni(1) and the return value of Surface::getNormalSurfacePoint (zeros where there is no
+ *                                normal) and mpKeypointNorm: x0 / has_x0 / ref_uv of dsh_normals_estimate[_db], first_n / has_fn of
+ *                                the host-record route (NormalEstimator.cc:60-110).  One launch, one download.
+ * dsh_keyframe_surface_get       reads everything back, each output may be NULL: normals[N x 3], has_normal[N], pts[N x 3], kpn[N x 2],
+ *                                ctrl (the control points of the depth spline, when there is one; room for 512), info.
+ * dsh_keyframe_surface_vertices  dsh_surface_vertices with the resident depth spline; DSH_ERR_STATE without one.
+ * dsh_keyframe_surface_state     0 / 1 / 2 from the host mirror: no resident Surface, a Surface, a Surface with a depth spline.
+ *
+ * dsh_keyframe_sfn is ShapeFromNormals::ShapeFromNormals + ::estimate (ShapeFromNormals.cc:38-171) of keyframe in->slot.  The selection
+ * is obtainM's (:190-210), for table entry i ascending with p = table[i], the first matching case:
+ *   p == -1                               n_empty
+ *   p bad                                 n_bad
+ *   no normal                             n_no_normal
+ *   a normal with a NaN component         n_nan      (Normal == Normal on a cv::Vec3f: an infinite component passes)
+ *   otherwise                             site k = the number of sites before i, at ((double)kpn.x, (double)kpn.y) with that normal
+ * One launch over at most 8192 entries, sites in entry order; the site count is read back once and sizes the launches that follow: the
+ * stages of dsh_sfn_estimate on the sites where the selection left them, with u_all / v_all the keyframe's resident key points widened.
+ * For the same sites ctrl_raw, ctrl and pts are the bytes dsh_sfn_estimate gives.  When ok, the surface points are evaluated into the
+ * store and the scaled control points become the keyframe's depth spline (set3DSurfacePoint, saveArray, :158-167), and ctrl_raw
+ * [nptsu * nptsv], ctrl [nptsu * nptsv] and pts [N x 3] (each may be NULL) come down.  When not ok nothing in the store changes.  A
+ * keyframe without a site is not ok and nothing is solved or written, ctrl_raw included: the bending rows and the mean-depth row alone
+ * have rank nptsu * nptsv - 2 (the affine depth maps are the null space of the bending energy), which a factorisation in floating
+ * point can miss.  At most 512 control points.
+ *
+ * A NULL surface_pts in dsh_keyframe_register_clouds, dsh_keyframe_register and dsh_template_switch means the resident surface points of
+ * the keyframe; for a keyframe without a resident Surface it stays the DSH_ERR_ARG it was.  When dsh_keyframe_register registers a
+ * keyframe that has a resident Surface, its finishing launch also applies Surface::applyScale to the resident copy, whichever way
+ * surface_pts was given: the points as (float)((double)s * s22), the depth spline as nodesDepth_[i] = s22 * nodesDepth_[i] in double
+ * (Surface.cc:107-121).  A keyframe without one behaves as before.
+ *
+ * Refusals follow the store's rules: arguments on the host mirror first (DSH_ERR_ARG, the message names the entry, nothing is written),
+ * then a host-only context is DSH_ERR_NO_DEVICE; a detached store is DSH_ERR_ARG. */
+typedef struct dsh_keyframe_surface_info {
+  int32_t N, n_normals;             /* numberofNormals_ */
+  int32_t enough_normals;           /* Surface::enoughNormals: n_normals >= 10 (Surface.cc:62-67) */
+  int32_t has_depth;
+  dsh_bbs grid;                     /* of the depth spline; zeros without one */
+} dsh_keyframe_surface_info;
+int dsh_keyframe_surface_init(dsh_mpdb* db, int32_t slot, int32_t N, const float* kpn /* N x 2 */);
+int dsh_keyframe_surface_set_depth(dsh_mpdb* db, int32_t slot, const dsh_bbs* bbs, const double* ctrl);
+int dsh_keyframe_surface_set_points(dsh_mpdb* db, int32_t slot, int32_t n, const int32_t* idx, const float* pts);
+int dsh_keyframe_surface_set_normals(dsh_mpdb* db, int32_t n, const int32_t* slot, const int32_t* idx, const float* normals /* 3 n */, int32_t* n_normals_out);
+typedef struct dsh_surface_take_input {   /* the database travels in the input struct, as the keyframe store of dsh_keyframe_register does */
+  const dsh_diffdb* ddb;            /* of the same context; its last dsh_normals_estimate_db is read */
+  int32_t n;
+  const int32_t* sel;               /* n */
+  const int32_t* slot;              /* n */
+  const int32_t* idx;               /* n */
+} dsh_surface_take_input;
+int dsh_keyframe_surface_take_normals(dsh_mpdb* db, const dsh_surface_take_input* in, int32_t* n_normals_out);
+int dsh_keyframe_surface_gather(dsh_mpdb* db, int32_t n, const int32_t* slot, const int32_t* idx, float* normal_xy /* 2 n */, uint8_t* has /* n */,
+                                float* uv /* 2 n */);
+int dsh_keyframe_surface_get(dsh_mpdb* db, int32_t slot, int32_t capacity, float* normals, uint8_t* has_normal, float* pts, float* kpn, double* ctrl,
+                             dsh_keyframe_surface_info* info);
+int dsh_keyframe_surface_vertices(dsh_mpdb* db, int32_t slot, const float* Twc, int32_t xs, int32_t ys, double* nodes_xyz);
+/* What the host mirror knows of keyframe `slot`, without touching the device: 0 no resident Surface, 1 a Surface, 2 a Surface with a
+ * depth spline; -1 for a slot outside the store or a detached store.  The call sites that serve keyframes with and without a resident
+ * Surface (integration/surface_register_store_hip.h, template_switch_hip.h) ask it before they choose surface_pts. */
+int32_t dsh_keyframe_surface_state(const dsh_mpdb* db, int32_t slot);
+
+typedef struct dsh_keyframe_sfn_input {
+  dsh_ctx* ctx;                     /* the context of the store */
+  int32_t slot;
+  const dsh_bbs* bbs;               /* the grid of the depth spline to estimate */
+  double bending_weight, mean_depth;
+} dsh_keyframe_sfn_input;
+typedef struct dsh_keyframe_sfn_result {
+  int32_t n_sites, n_empty, n_bad, n_no_normal, n_nan;   /* per table entry */
+  int32_t ok;                       /* ShapeFromNormals::estimate's return value */
+} dsh_keyframe_sfn_result;
+int dsh_keyframe_sfn(dsh_mpdb* db, const dsh_keyframe_sfn_input* in, double* ctrl_raw, double* ctrl, float* pts, dsh_keyframe_sfn_result* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -111,6 +111,7 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
   float Twc[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPoseInverse() :61 (cv::Mat 4x4 float)
   int rows = 0, cols = 0;                                               // imGray.rows, imGray.cols :228
   std::vector<float> surface_points;                                    // DefKeyFrame::surface->get3DSurfacePoint(i, x3c): 3 per key point
+  std::vector<KeyPoint> mpKeypointNorm;                                 // DefKeyFrame.h: the normalised key points (surface_store_hip.h)
   // what SurfaceRegistration::registerSurfaces writes (surface_register_store_hip.h)
   float Tcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPose() :60
   void SetPose(const float* T) {                                        // :59 (KeyFrame.cc:97-111: Tcw, Ow = -Rwc * tcw, Twc)

@@ -13,6 +13,9 @@
 //         refKF->surface->applyScale(s22)   the scaled surface points come back from the device and replace the keyframe's (:145)
 //         refKF->SetPose(mScw)              with the new pose (:150); the keyframe store's camera centre has been written by the call
 //       Returns the reference's return value; *ok (may be null) is false when the library failed (dsh_last_error has the text).
+//       A keyframe whose Surface is resident in the store (surface_store_hip.h, InitSurfaceStoreHIP) has no surface points on the host:
+//       the call then passes surface_pts = NULL, the finishing launch scales the resident points and depth spline, and applyScale's
+//       host write-back is skipped; SetPose is done as before.
 //
 // Templates over the reference's classes; the type-specific accessors are RegisterAccess<KeyFrameT>: cv::Mat and Surface in DefSLAM
 // (GetPoseInverse(), surface->get3DSurfacePoint, a setter of the Surface's points, SetPose(cv::Mat)), plain members in the stand-ins
@@ -53,19 +56,20 @@ bool RegisterSurfacesStoreHIP(MapPointStoreHIP<KeyFrameT, MapPointT>& store, Key
   const int32_t slot = store.slot(refKF);
   if (slot < 0 || kfstore.Slot(refKF, &rc) != slot) return false;                 // the two stores number the keyframes alike
   const int N = A::key_points(refKF);
+  const bool resident = dsh_keyframe_surface_state(store.handle(), slot) > 0;     // the Surface lives in the store: nothing of it on the host
   std::vector<float> surf(3 * (size_t)(N > 0 ? N : 1)), scaled(surf.size());
-  for (int i = 0; i < N; i++) A::surface_point(refKF, i, &surf[3 * (size_t)i]);
+  for (int i = 0; !resident && i < N; i++) A::surface_point(refKF, i, &surf[3 * (size_t)i]);
   float Twc[16];
   A::pose_inverse(refKF, Twc);
   dsh_keyframe_register_input in;
-  in.kfdb = kfstore.db(); in.slot = slot; in.N = N; in.surface_pts = surf.data(); in.Twc = Twc;
+  in.kfdb = kfstore.db(); in.slot = slot; in.N = N; in.surface_pts = resident ? nullptr : surf.data(); in.Twc = Twc;
   in.u = u; in.nu = nu; in.chi_limit = chiLimit; in.check_chi = check_chi ? 1 : 0;
   dsh_keyframe_register_result r;
-  if (dsh_keyframe_register(store.handle(), &in, nullptr, scaled.data(), &r) != DSH_OK) return false;
+  if (dsh_keyframe_register(store.handle(), &in, nullptr, resident ? nullptr : scaled.data(), &r) != DSH_OK) return false;
   if (ok) *ok = true;
   if (result) *result = r;
   if (!r.registered) return false;
-  for (int i = 0; i < N; i++) A::set_surface_point(refKF, i, &scaled[3 * (size_t)i]);   // surface->applyScale(s22), :145
+  for (int i = 0; !resident && i < N; i++) A::set_surface_point(refKF, i, &scaled[3 * (size_t)i]);   // surface->applyScale(s22), :145
   A::set_pose(refKF, r.Tcw_new);                                                  // :150
   return true;
 }

@@ -15,6 +15,7 @@
 //         every good point  SetWorldPos with its position after the switch; SetFacet(facet_of(n0, n1, n2)) -- null without a facet --
 //                           and SetCoordinates with the barycentrics (TriangularMesh.cc:186-190)
 //       Returns false when the library fails (dsh_last_error of the store's context has the text).
+//       A keyframe whose Surface is resident in the store (surface_store_hip.h) has no surface points on the host: surface_pts = NULL.
 // Not done here: DefMapPoint::Repose's UpdateNormalAndDepth of the embedded points (UpdateMapPointsHIP of mappoint_upkeep_hip.h with
 // DSH_MP_NORMAL_DEPTH, as before), DefKeyFrame::assignTemplate, the textures, lastincorporasion.
 //
@@ -77,12 +78,13 @@ bool UpdateTemplateHIP(MapPointStoreHIP<KeyFrameT, MapPointT>& store, KeyFrameSt
   dsh_kf_keypoints k;
   switch_keypoints(referenceKF, A::rows(referenceKF), A::cols(referenceKF), kp, k);
   const int N = k.N;
+  const bool resident = dsh_keyframe_surface_state(store.handle(), slot) > 0;
   std::vector<float> surf(3 * (size_t)N);
-  for (int i = 0; i < N; i++) A::surface_point(referenceKF, i, &surf[3 * (size_t)i]);
+  for (int i = 0; !resident && i < N; i++) A::surface_point(referenceKF, i, &surf[3 * (size_t)i]);
   float Twc[16];
   A::pose_inverse(referenceKF, Twc);
   dsh_template_switch_input in;
-  in.kfdb = kfstore.db(); in.slot = slot; in.kf = &k; in.surface_pts = surf.data(); in.Twc = Twc;
+  in.kfdb = kfstore.db(); in.slot = slot; in.kf = &k; in.surface_pts = resident ? nullptr : surf.data(); in.Twc = Twc;
   std::vector<int32_t> new_idx(N > 0 ? N : 1);
   dsh_template_switch_counts c;
   if (dsh_template_switch(store.handle(), &in, new_idx.data(), &c) != DSH_OK) return false;
