@@ -230,6 +230,18 @@ class KeyframeSfnResultC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_sites", "n_empty", "n_bad", "n_no_normal", "n_nan", "ok")]
 
 
+class KeyframeCreateInputC(C.Structure):
+    _fields_ = [("kfdb", C.c_void_p), ("kf", C.POINTER(MpKeyFrameC)), ("Tcw", c_float_p), ("points", c_i32_p), ("kpn", c_float_p)]
+
+
+class KeyframeCreateResultC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("slot", "n_held", "n_snapshot")] + [("Ow", C.c_float * 3)]
+
+
+class KeyframeConnectionsC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_counted", "n_connected", "parent", "parent_set", "max_weight", "max_kf")]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -267,6 +279,7 @@ EXPORTED_SYMBOLS = [
     "dsh_keyframe_surface_init", "dsh_keyframe_surface_set_depth", "dsh_keyframe_surface_set_points", "dsh_keyframe_surface_set_normals",
     "dsh_keyframe_surface_take_normals", "dsh_keyframe_surface_gather", "dsh_keyframe_surface_get", "dsh_keyframe_surface_vertices",
     "dsh_keyframe_sfn", "dsh_keyframe_surface_state",
+    "dsh_track_keyframe_candidate", "dsh_keyframe_create", "dsh_keyframe_update_connections",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -436,6 +449,9 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_keyframe_surface_vertices.argtypes = [vp, i32, c_float_p, i32, i32, c_double_p]
     L.dsh_keyframe_surface_state.argtypes = [vp, i32]
     L.dsh_keyframe_sfn.argtypes = [vp, C.POINTER(KeyframeSfnInputC), c_double_p, c_double_p, c_float_p, C.POINTER(KeyframeSfnResultC)]
+    L.dsh_track_keyframe_candidate.argtypes = [vp, i32, c_i32_p, c_i32_p]
+    L.dsh_keyframe_create.argtypes = [vp, C.POINTER(KeyframeCreateInputC), C.POINTER(KeyframeCreateResultC)]
+    L.dsh_keyframe_update_connections.argtypes = [vp, i32, i32, i32, c_i32_p, c_i32_p, c_i32_p, c_i32_p, C.POINTER(KeyframeConnectionsC)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

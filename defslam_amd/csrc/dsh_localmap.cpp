@@ -123,7 +123,7 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->max_node = -1;
   db->max_node_stale = false;
   db->top_on_device = false;
-  db->last_N = -1;
+  db->last_N = db->cand_N = -1;
   db->last_kept = 0;
   db->last_max_octave = -1;
   db->obs.clear();
@@ -131,6 +131,7 @@ int dsh_mpdb_clear(dsh_mpdb* db) {
   db->kf.clear();
   db->snapped.clear();
   db->surf.clear();
+  db->first_conn.clear();
   return DSH_OK;
 }
 
@@ -285,6 +286,7 @@ int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_
   db->kf.push_back(k);
   db->snapped.push_back(0);
   db->surf.emplace_back();
+  db->first_conn.push_back(1);
   if (slot) *slot = db->K;
   db->K++;
   db->T += N;

@@ -80,38 +80,11 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
   if (!kf) return bad("keyframe is NULL");
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(kf->Ow[k])) return bad("camera centre not finite");
-  if (const char* ne = dsh_keypoint_count_error(kf->N)) return bad(ne);
-  if (kf->N > 0 && (!kf->desc || !kf->octave)) return bad("key point arrays are NULL");
-  if (kf->levels <= 0 || kf->levels > MPU_MAX_LEVELS || !kf->scale_factors) return bad("levels outside 1 .. 32 or no scale factors");
-  for (int j = 0; j < kf->N; j++)
-    if (kf->octave[j] < 0 || kf->octave[j] > 127) return bad("key point octave outside 0 .. 127");
-  if (db->count == INT32_MAX || db->rows + kf->N > INT32_MAX) return bad("store full");
+  const std::string ke = kfdb_keyframe_error(db, kf);
+  if (!ke.empty()) return bad(ke);
   if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: hipSetDevice failed");
-  if (db->count + 1 > db->cap) {
-    const int32_t ncap = (int32_t)std::min<long long>(2ll * db->cap, INT32_MAX);
-    if (dsh_store_grow_array(&db->d_slots, (size_t)db->count, (size_t)ncap) != hipSuccess ||
-        dsh_store_grow_array(&db->d_levels, (size_t)db->count, (size_t)ncap) != hipSuccess ||
-        dsh_store_grow_array(&db->d_sf, MPU_MAX_LEVELS * (size_t)db->count, MPU_MAX_LEVELS * (size_t)ncap) != hipSuccess)
-      return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
-    db->cap = ncap;
-  }
-  if (db->rows + kf->N > db->row_cap) {
-    const long long ncap = std::max(db->rows + kf->N, 2 * db->row_cap);
-    if (dsh_store_grow_array(&db->d_rows, 2 * (size_t)db->rows, 2 * (size_t)ncap) != hipSuccess ||
-        dsh_store_grow_array(&db->d_oct, (size_t)db->rows, (size_t)ncap) != hipSuccess)
-      return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: out of device memory while growing the store");
-    db->row_cap = ncap;
-  }
-  dsh_kfdb::Kf h;
-  h.row_off = db->rows;
-  h.N = kf->N;
-  h.levels = kf->levels;
-  h.bad = kf->bad ? 1 : 0;
-  h.octave_over = false;
-  std::memset(h.sf, 0, sizeof(h.sf));
-  for (int l = 0; l < kf->levels; l++) h.sf[l] = kf->scale_factors[l];
-  h.octave.assign(kf->octave, kf->octave + kf->N);
-  for (const int8_t o : h.octave) h.octave_over = h.octave_over || o >= kf->levels;
+  HIPCHK(c, kfdb_reserve(db, kf->N));
+  dsh_kfdb::Kf h = kfdb_mirror(db, kf, kf->bad != 0);
   MpuSlot s;
   s.Ow[0] = kf->Ow[0]; s.Ow[1] = kf->Ow[1]; s.Ow[2] = kf->Ow[2];
   s.row_off = (int32_t)db->rows;
@@ -124,11 +97,8 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
     HIPCHK(c, hipMemcpyAsync(db->d_oct + db->rows, h.octave.data(), (size_t)kf->N, hipMemcpyHostToDevice, st));
   }
   HIPCHK(c, hipStreamSynchronize(st));
-  db->n_octave_over += h.octave_over ? 1 : 0;
-  db->kf.push_back(std::move(h));
-  if (slot) *slot = db->count;
-  db->count++;
-  db->rows += kf->N;
+  const int32_t at = kfdb_push(db, std::move(h));
+  if (slot) *slot = at;
   return DSH_OK;
 }
 

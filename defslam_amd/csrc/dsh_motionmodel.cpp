@@ -49,16 +49,17 @@ int dsh_track_end_frame(dsh_mpdb* db, int N, const int32_t* frame_points, const 
   e.nobs = db->d_nobs;
   e.last_ids = db->d_last_ids;
   e.last_oct = db->d_last_oct;
+  e.cand_ids = db->d_cand_ids;
   e.points_out = down.dev<int32_t>(d_pts);
   e.outlier_out = down.dev<uint8_t>(d_flag);
   e.counts = down.dev<int32_t>(d_cnt);
-  db->last_N = -1;   // the list is being overwritten: it counts again once the call has succeeded
+  db->last_N = db->cand_N = -1;   // the list and the candidate are being overwritten: they count again once the call has succeeded
   HIPCHK(c, mm_end_frame_launch(e, c->stream));
   if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
 
   const int32_t* cnt = down.host<int32_t>(d_cnt);
-  db->last_N = N;
+  db->last_N = db->cand_N = N;
   db->last_kept = cnt[2];
   db->last_max_octave = cnt[3];
   if (points_out && N > 0) std::memcpy(points_out, down.host<int32_t>(d_pts), 4 * n);

@@ -31,3 +31,59 @@ struct dsh_kfdb : dsh_store {
   };
   std::vector<Kf> kf;
 };
+
+// What the two calls that append a keyframe share (dsh_kfdb_add; dsh_keyframe_create, which writes the device side in its own launch).
+// Everything dsh_kfdb_add refuses of a keyframe but its camera centre: "" or what is wrong.
+inline std::string kfdb_keyframe_error(const dsh_kfdb* db, const dsh_mp_keyframe* kf) {
+  if (const char* ne = dsh_keypoint_count_error(kf->N)) return ne;
+  if (kf->N > 0 && (!kf->desc || !kf->octave)) return "key point arrays are NULL";
+  if (kf->levels <= 0 || kf->levels > MPU_MAX_LEVELS || !kf->scale_factors) return "levels outside 1 .. 32 or no scale factors";
+  for (int j = 0; j < kf->N; j++)
+    if (kf->octave[j] < 0 || kf->octave[j] > 127) return "key point octave outside 0 .. 127";
+  if (db->count == INT32_MAX || db->rows + kf->N > INT32_MAX) return "store full";
+  return "";
+}
+
+// room for one more keyframe with N descriptor rows
+inline hipError_t kfdb_reserve(dsh_kfdb* db, int32_t N) {
+  hipError_t e;
+  if (db->count + 1 > db->cap) {
+    const int32_t ncap = (int32_t)std::min<long long>(2ll * db->cap, INT32_MAX);
+    if ((e = dsh_store_grow_array(&db->d_slots, (size_t)db->count, (size_t)ncap)) != hipSuccess ||
+        (e = dsh_store_grow_array(&db->d_levels, (size_t)db->count, (size_t)ncap)) != hipSuccess ||
+        (e = dsh_store_grow_array(&db->d_sf, MPU_MAX_LEVELS * (size_t)db->count, MPU_MAX_LEVELS * (size_t)ncap)) != hipSuccess)
+      return e;
+    db->cap = ncap;
+  }
+  if (db->rows + N > db->row_cap) {
+    const long long ncap = std::max(db->rows + N, 2 * db->row_cap);
+    if ((e = dsh_store_grow_array(&db->d_rows, 2 * (size_t)db->rows, 2 * (size_t)ncap)) != hipSuccess ||
+        (e = dsh_store_grow_array(&db->d_oct, (size_t)db->rows, (size_t)ncap)) != hipSuccess)
+      return e;
+    db->row_cap = ncap;
+  }
+  return hipSuccess;
+}
+
+// the host mirror of a keyframe that goes in at the end of the store
+inline dsh_kfdb::Kf kfdb_mirror(const dsh_kfdb* db, const dsh_mp_keyframe* kf, bool bad) {
+  dsh_kfdb::Kf h;
+  h.row_off = db->rows;
+  h.N = kf->N;
+  h.levels = kf->levels;
+  h.bad = bad ? 1 : 0;
+  h.octave_over = false;
+  std::memset(h.sf, 0, sizeof(h.sf));
+  for (int l = 0; l < kf->levels; l++) h.sf[l] = kf->scale_factors[l];
+  h.octave.assign(kf->octave, kf->octave + kf->N);
+  for (const int8_t o : h.octave) h.octave_over = h.octave_over || o >= kf->levels;
+  return h;
+}
+
+// the mirror joins the store once the device side is written; returns the slot
+inline int32_t kfdb_push(dsh_kfdb* db, dsh_kfdb::Kf&& h) {
+  db->n_octave_over += h.octave_over ? 1 : 0;
+  db->rows += h.N;
+  db->kf.push_back(std::move(h));
+  return db->count++;
+}

@@ -26,35 +26,12 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_clear_kernel(LmBufs b) {
 __global__ __launch_bounds__(LM_BLOCK) void lm_scatter_kernel(LmBufs b) {
   const int i = blockIdx.x * LM_BLOCK + threadIdx.x;
   if (i >= b.N) return;
-  const int p = b.frame_points[i];
-  uint8_t fb = 0;
-  if (p >= 0) {
-    if (b.bad[p]) fb = 1;   // Tracking.cc:1527-1530
-    else atomicAdd(&b.cnt[p], 1);
-  }
-  b.out_frame_bad[i] = fb;
+  b.out_frame_bad[i] = vote_scatter(b.bad, b.cnt, b.frame_points[i]) ? 1 : 0;   // Tracking.cc:1527-1530
 }
 
 __global__ __launch_bounds__(LM_BLOCK) void lm_votes_kernel(LmBufs b) {
   __shared__ int hist[LM_BINS];
-  for (int base = 0; base < b.K; base += LM_BINS) {
-    const int bins = min(LM_BINS, b.K - base);
-    for (int k = threadIdx.x; k < bins; k += LM_BLOCK) hist[k] = 0;
-    __syncthreads();
-    for (long long r = (long long)blockIdx.x * LM_BLOCK + threadIdx.x; r < b.R; r += (long long)gridDim.x * LM_BLOCK) {
-      const int2 rec = b.log[r];
-      if (rec.x < 0) continue;   // erased
-      const int w = b.cnt[rec.x];
-      const int k = rec.y - base;
-      if (w > 0 && k >= 0 && k < bins) atomicAdd(&hist[k], w);
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < bins; k += LM_BLOCK) {
-      const int v = hist[k];
-      if (v) atomicAdd(&b.votes[base + k], v);
-    }
-    __syncthreads();
-  }
+  vote_sweep<LM_BLOCK, LM_BINS>(b.log, b.R, b.cnt, b.votes, b.K, -1, hist);   // a frame is no keyframe: nobody is left out
 }
 
 // first slot k in [from, K) that is not bad, not marked and (parent < 0 or a child of `parent`); -1: none.  Wave-uniform.

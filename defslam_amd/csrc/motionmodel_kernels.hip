@@ -2,7 +2,7 @@
 // (dsh_track_end_frame, dsh_motion_model_search; gfx950).
 //   DefTracking::CleanMatches, the outlier drop, mLastFrame = Frame(*mCurrentFrame)   Modules/Tracking/DefTracking.cc:667-679, :185-191, :211
 //   the query filter of DefORBmatcher::SearchByProjection                               Modules/Matching/DefORBmatcher.cc:321-332
-// mm_end_frame_kernel   ONE workgroup over the frame's key points (at most 8192): the two loops, the resident list, the counts
+// mm_end_frame_kernel   ONE workgroup over the frame's key points (at most 8192): the two loops, the resident list and keyframe candidate, the counts
 // mm_gather_kernel      the entries of the resident list that hold a point that is not bad and has a facet become the queries of
 //                       track_kernels.hip, compacted IN INDEX ORDER: the queries interact in that order.  One launch, no scratch and no
 //                       second pass: a workgroup counts the kept entries in front of its own MM_BLOCK entries itself (the list has at
@@ -31,6 +31,7 @@ __global__ __launch_bounds__(MM_END_BLOCK) void mm_end_frame_kernel(MmEnd e) {
       cleaned++;
     }
     e.points_out[i] = p;             // what CreateNewKeyFrame sees (:175-178)
+    e.cand_ids[i] = p;               // and keeps resident for it
     e.outlier_out[i] = out;
     if (p >= 0 && out) {             // :185-191
       p = -1;

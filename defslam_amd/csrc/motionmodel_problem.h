@@ -18,6 +18,7 @@ struct MmEnd {
   const int32_t* nobs;           // the store's MapPoint::nObs
   int32_t* last_ids;             // N, resident: the id after CleanMatches and the outlier drop, or -1
   int32_t* last_oct;             // N, resident: the octave of an entry that holds a point, else -1
+  int32_t* cand_ids;             // N, resident: the id after CleanMatches alone -- the keyframe candidate (dsh_keyframe_create)
   // the download block
   int32_t* points_out;           // N: after CleanMatches
   uint8_t* outlier_out;          // N

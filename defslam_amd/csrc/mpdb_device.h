@@ -71,6 +71,42 @@ __device__ __forceinline__ int block_sums(const bool (&flags)[NC]) {
   return s;
 }
 
+// The vote of a list of point ids on the keyframes that observe them, as Tracking::UpdateLocalKeyFrames (Tracking.cc:1519-1532) casts it
+// for a frame and KeyFrame::UpdateConnections (KeyFrame.cc:335-357) for a keyframe's own table: first the list's multiplicities, then
+// one coalesced pass over the observation log.
+// vote_scatter: entry p of the list into cnt[p]; a bad point does not vote and is reported.
+__device__ __forceinline__ bool vote_scatter(const int32_t* bad, int32_t* cnt, int p) {
+  if (p < 0) return false;
+  if (bad[p]) return true;
+  atomicAdd(&cnt[p], 1);
+  return false;
+}
+
+// vote_sweep: votes[k] += cnt[point] for every live record (point, k) with k != skip.  The votes accumulate in hist[BINS] in LDS and
+// leave with one global atomic per workgroup and touched keyframe (the records of a map concentrate on few keyframes: an atomic per
+// record would serialise on them); more than BINS keyframes take more passes over the log.  Every thread of the workgroup calls it.
+template <int BLOCK, int BINS>
+__device__ __forceinline__ void vote_sweep(const int2* log, long long R, const int32_t* cnt, int32_t* votes, int K, int skip, int* hist) {
+  for (int base = 0; base < K; base += BINS) {
+    const int bins = min(BINS, K - base);
+    for (int k = threadIdx.x; k < bins; k += BLOCK) hist[k] = 0;
+    __syncthreads();
+    for (long long r = (long long)blockIdx.x * BLOCK + threadIdx.x; r < R; r += (long long)gridDim.x * BLOCK) {
+      const int2 rec = log[r];
+      if (rec.x < 0 || rec.y == skip) continue;   // erased; the voter itself
+      const int w = cnt[rec.x];
+      const int k = rec.y - base;
+      if (w > 0 && k >= 0 && k < bins) atomicAdd(&hist[k], w);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < bins; k += BLOCK) {
+      const int v = hist[k];
+      if (v) atomicAdd(&votes[base + k], v);
+    }
+    __syncthreads();
+  }
+}
+
 // workgroups of `block` threads, one element per thread
 inline int blocks_for(long long n, int block) { return (int)((n + block - 1) / block); }
 

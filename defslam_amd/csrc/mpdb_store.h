@@ -12,6 +12,8 @@
 //   dsh_tracksft.cpp      dsh_track_sft_observations, dsh_track_sft
 //   dsh_surfreg.cpp       dsh_keyframe_snapshot_positions, dsh_keyframe_register and the keyframe pose of the keyframe store
 //   dsh_surfstore.cpp     dsh_keyframe_surface_*, dsh_keyframe_sfn: the resident Surface of a keyframe
+//   dsh_keyframe_create.cpp  dsh_track_keyframe_candidate, dsh_keyframe_create, dsh_keyframe_update_connections (keyframe_create_problem.h,
+//                         keyframe_create_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +61,9 @@ struct dsh_mpdb : dsh_store {
   LmHdr* d_hdr = nullptr;
   // the resident last-frame list (dsh_track_end_frame): per key point of the last frame the id it holds or -1, and its octave (-1 there)
   int32_t *d_last_ids = nullptr, *d_last_oct = nullptr;
+  // the resident keyframe candidate beside it: the same frame's ids after CleanMatches alone, outliers still held -- the table
+  // DefTracking::CreateNewKeyFrame copies (dsh_keyframe_create with points == NULL)
+  int32_t* d_cand_ids = nullptr;
   int32_t last_cap = 0;
   // host mirror
   std::unordered_map<uint64_t, long long> obs;   // (point, keyframe) -> its record in the log
@@ -82,6 +87,8 @@ struct dsh_mpdb : dsh_store {
   int32_t last_N = -1;                 // length of the resident last-frame list, -1: there is none
   int32_t last_kept = 0;               // its entries that hold a point
   int32_t last_max_octave = -1;        // the largest octave among them
+  int32_t cand_N = -1;                 // length of the resident keyframe candidate, -1: there is none
+  std::vector<uint8_t> first_conn;     // per keyframe: KeyFrame::mbFirstConnection (dsh_keyframe_update_connections)
 
   // INT32_MAX, which refuses every template, when the device cannot be asked
   int32_t largest_node() {
@@ -105,7 +112,7 @@ struct dsh_mpdb : dsh_store {
     for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
                     (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
                     (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx, (void*)d_snap_point, (void*)d_snap_xyz,
-                    (void*)d_surf_normal, (void*)d_surf_pts, (void*)d_surf_kpn, (void*)d_surf_has, (void*)d_surf_nn, (void*)d_surf_depth})
+                    (void*)d_cand_ids, (void*)d_surf_normal, (void*)d_surf_pts, (void*)d_surf_kpn, (void*)d_surf_has, (void*)d_surf_nn, (void*)d_surf_depth})
       if (p) (void)hipFree(p);
   }
 };
@@ -146,12 +153,14 @@ inline hipError_t mpdb_reserve_log(dsh_mpdb* db, long long need) {
   return hipSuccess;
 }
 
-// room for a last-frame list of N entries (the list it holds stays until the call that grows it writes the new one)
+// room for a last-frame list and a keyframe candidate of N entries (the list it holds stays until the call that grows it writes the new one)
 inline hipError_t mpdb_reserve_last_frame(dsh_mpdb* db, int32_t N) {
   if (N <= db->last_cap) return hipSuccess;
   const size_t cap = (size_t)std::max(N, 2 * db->last_cap), used = (size_t)std::max(db->last_N, 0);
   hipError_t e;
-  if ((e = dsh_store_grow_array(&db->d_last_ids, used, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_last_oct, used, cap)) != hipSuccess) return e;
+  if ((e = dsh_store_grow_array(&db->d_last_ids, used, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_last_oct, used, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_cand_ids, (size_t)std::max(db->cand_N, 0), cap)) != hipSuccess)
+    return e;
   db->last_cap = (int32_t)cap;
   return hipSuccess;
 }

@@ -112,10 +112,8 @@ __global__ __launch_bounds__(SR_FINISH_BLOCK) void sr_finish_kernel(SrFinish k) 
   // Surface.cc:117-120: nodesDepth_[i] = s22 * nodesDepth_[i]
   if (k.resident_depth && i < k.n_depth) k.resident_depth[i] = k.s22 * k.resident_depth[i];
   if (blockIdx.x == 0 && threadIdx.x < 3) {
-    // KeyFrame::SetPose: Ow = -Rcw.t() * tcw, the three products of a row summed left to right in float32
-    const float* T = k.Tcw;
     const int c = threadIdx.x;
-    const float o = -((T[c] * T[3] + T[4 + c] * T[7]) + T[8 + c] * T[11]);
+    const float o = sr_camera_centre(k.Tcw, c);
     if (k.kf_slot) k.kf_slot->Ow[c] = o;
     k.Ow[c] = o;
   }

@@ -53,6 +53,11 @@ struct SrFinish {
   int32_t n_depth;
 };
 
+// KeyFrame::SetPose (KeyFrame.cc:97-111): component c of Ow = -Rcw.t() * tcw of a row-major Tcw, the three products of a row summed left
+// to right in float32.  The one statement of it: the finishing launch here and dsh_keyframe_create's (keyframe_create_kernels.hip) call
+// it, both compiled without FMA contraction; the host calls it only to refuse a centre that is not finite.
+__host__ __device__ __forceinline__ float sr_camera_centre(const float* T, int c) { return -((T[c] * T[3] + T[4 + c] * T[7]) + T[8 + c] * T[11]); }
+
 // one launch, one workgroup: snap_point / snap_xyz of the entries whose point is not bad and has a facet; *n_taken = their number
 extern "C" hipError_t sr_snapshot_launch(const TcState& s, const SrKeyframe& k, int32_t* n_taken, hipStream_t st);
 // one launch, one workgroup: the pairs of SurfaceRegistration.cc:60-104 in ascending entry order, and the counts

@@ -22,7 +22,11 @@
   * DefKeyFrame's PosesKeyframes snapshot (Modules/Common/DefKeyFrame.cc:60-74) and SurfaceRegistration::registerSurfaces
     (Modules/Mapping/SurfaceRegistration.cc:48-153) with the clouds selected from the store and the snapshot, Surface::applyScale and the
     camera centre of KeyFrame::SetPose written into the keyframe store (dsh_keyframe_snapshot_positions, dsh_keyframe_register,
-    dsh_keyframe_set_pose).
+    dsh_keyframe_set_pose);
+  * DefTracking::CreateNewKeyFrame (Modules/Tracking/DefTracking.cc:696-707) in one call on both stores, with the table taken on the
+    device from the keyframe candidate the end of the frame left there, and KeyFrame::UpdateConnections
+    (Thirdparty/ORBSLAM_2/src/KeyFrame.cc:326-419) over the observation log, which gives the keyframe its parent
+    (dsh_track_keyframe_candidate, dsh_keyframe_create, dsh_keyframe_update_connections).
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -381,6 +385,28 @@ UPKEEP_NO_OBS, UPKEEP_NO_GOOD_DESC, UPKEEP_NO_REF, UPKEEP_SKIPPED_BAD = (_lib.DS
 CULL_STAYS, CULL_WAS_BAD, CULL_SET_BAD, CULL_OLD = 0, 1, 2, 3
 
 
+@dataclass
+class KeyframeCreation:
+    """What dsh_keyframe_create returns (DefTracking::CreateNewKeyFrame on the two stores)."""
+    slot: int                           # of the new keyframe, in both stores
+    n_held: int                         # table entries that hold a point
+    n_snapshot: int                     # entries whose position was taken (DefKeyFrame.cc:60-74)
+    Ow: np.ndarray                      # (3,) float32 the camera centre written
+
+
+@dataclass
+class KeyframeConnections:
+    """What dsh_keyframe_update_connections returns (KeyFrame::UpdateConnections, KeyFrame.cc:326-419)."""
+    counted_kf: np.ndarray              # mConnectedKeyFrameWeights: the keyframes with a weight > 0 by ascending slot
+    counted_w: np.ndarray               # their weights
+    ordered_kf: np.ndarray              # mvpOrderedConnectedKeyFrames: descending weight, among equals descending slot
+    ordered_w: np.ndarray               # mvOrderedWeights
+    parent: int                         # the keyframe's parent after the call, -1: none
+    parent_set: bool                    # this call set it (the first connection)
+    max_weight: int                     # nmax
+    max_kf: int                         # pKFmax, -1 when no weight is positive
+
+
 def _i32(a):
     return np.ascontiguousarray(a, np.int32).reshape(-1)
 
@@ -609,6 +635,14 @@ class MapPointStore:
         n = C.c_int32(0)
         self._call("dsh_track_last_frame", int(capacity), _ptr(ids, C.c_int32), _ptr(oc, C.c_int32), C.byref(n))
         return LastFrame(ids=ids[:n.value].copy(), octave=oc[:n.value].copy())
+
+    def keyframe_candidate(self, capacity: int = 8192) -> np.ndarray:
+        """The resident keyframe candidate: the ids of the last end_frame after CleanMatches alone, outliers still held."""
+        m = max(int(capacity), 1)
+        ids = np.full(m, -1, np.int32)
+        n = C.c_int32(0)
+        self._call("dsh_track_keyframe_candidate", int(capacity), _ptr(ids, C.c_int32), C.byref(n))
+        return ids[:n.value].copy()
 
     def motion_model_search(self, frame: TrackFrame, th: float = 20.0, th_wide: float = 25.0, min_matches: int = 20) -> MotionModelSearch:
         """DefTracking::TrackWithMotionModel after SetPose, with the resident last-frame list (of the preceding end_frame) as LastFrame;
@@ -1050,3 +1084,44 @@ class MapPointStore:
         t = np.full(max(N, 1), -1, np.int32)
         self._call("dsh_point_store_get_keyframe_table", int(slot), N, _ptr(t, C.c_int32))
         return t[:N]
+
+    # ---- a new keyframe: creation and covisibility connections ----
+    def create_keyframe(self, kf_store, kf, Tcw, points=None, kpn=None) -> KeyframeCreation:
+        """DefTracking::CreateNewKeyFrame on both stores in one call: kf (a mappoint.MpKeyFrame; Ow and bad are not read) goes into
+        kf_store with the camera centre of Tcw (4,4) float32, the table `points` (ids or -1; None: the resident keyframe candidate of
+        the last end_frame) into this store, the PosesKeyframes snapshot is taken, and with kpn (N,2) float32 the Surface is
+        initialised.  The state afterwards is that of kf_store.add, add_keyframe, snapshot_positions and surface_init."""
+        desc = np.ascontiguousarray(kf.desc, np.uint8).reshape(-1, 32)
+        octave = _i32(kf.octave)
+        sf = np.ascontiguousarray(kf.scale_factors, np.float32).reshape(-1)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        N = int(desc.shape[0])
+        t = None if points is None else _i32(points)
+        k = None if kpn is None else np.ascontiguousarray(kpn, np.float32).reshape(-1, 2)
+        if octave.shape[0] != N or (t is not None and t.shape[0] != N) or (k is not None and k.shape[0] != N):
+            raise ValueError("desc, octave, points and kpn differ in length")
+        if N == 0:   # an empty array has no address: give the call one it does not read
+            t = None if t is None else np.full(1, -1, np.int32)
+            k = None if k is None else np.zeros((1, 2), np.float32)
+        c = _lib.MpKeyFrameC()
+        c.N = N
+        c.desc, c.octave = _ptr(desc, C.c_uint8), _ptr(octave, C.c_int32)
+        c.levels, c.scale_factors = int(sf.shape[0]), _ptr(sf, C.c_float)
+        inp = _lib.KeyframeCreateInputC(kf_store._h if kf_store is not None else None, C.pointer(c), _ptr(T, C.c_float), _ptr(t, C.c_int32),
+                                        _ptr(k, C.c_float))
+        r = _lib.KeyframeCreateResultC()
+        self._call("dsh_keyframe_create", C.byref(inp), C.byref(r))
+        self._kf_n.append(N)
+        return KeyframeCreation(slot=int(r.slot), n_held=int(r.n_held), n_snapshot=int(r.n_snapshot), Ow=np.array(r.Ow, np.float32))
+
+    def update_connections(self, slot: int, th: int = 100) -> KeyframeConnections:
+        """KeyFrame::UpdateConnections of keyframe `slot` from the observation log; on the first call that finds a connection the
+        keyframe's parent in the store becomes the first ordered keyframe (not for slot 0)."""
+        K = max(self.n_keyframes, 1)
+        ck, cw, ok, ow = (np.zeros(K, np.int32) for _ in range(4))
+        r = _lib.KeyframeConnectionsC()
+        self._call("dsh_keyframe_update_connections", int(slot), int(th), K, _ptr(ck, C.c_int32), _ptr(cw, C.c_int32), _ptr(ok, C.c_int32),
+                   _ptr(ow, C.c_int32), C.byref(r))
+        nc, no = int(r.n_counted), int(r.n_connected)
+        return KeyframeConnections(counted_kf=ck[:nc].copy(), counted_w=cw[:nc].copy(), ordered_kf=ok[:no].copy(), ordered_w=ow[:no].copy(),
+                                   parent=int(r.parent), parent_set=bool(r.parent_set), max_weight=int(r.max_weight), max_kf=int(r.max_kf))

@@ -757,6 +757,12 @@ int dsh_track_end_frame(dsh_mpdb* db, int N, const int32_t* frame_points, const 
 /* The resident last-frame list read back: ids[capacity] and octave[capacity] (each may be NULL) receive its *n entries, the id or -1
  * and the octave (-1 where the entry is empty).  DSH_ERR_ARG when capacity is smaller or when there is no list. */
 int dsh_track_last_frame(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* octave, int32_t* n);
+/* THE KEYFRAME CANDIDATE.  dsh_track_end_frame also keeps the state after its step 1 resident, beside the last-frame list: the N ids
+ * it writes to points_out, outliers still held, cleaned entries -1.  It is the table DefTracking::CreateNewKeyFrame copies into a new
+ * keyframe (:175-178, :696-707), and dsh_keyframe_create reads it on the device when it is given no table.  It is replaced by the next
+ * dsh_track_end_frame, is not consumed by a keyframe made from it, and dsh_mpdb_clear forgets it with the last-frame list.  This reads
+ * it back: ids[capacity] (may be NULL) receives its *n entries; DSH_ERR_ARG when capacity is smaller or when there is no candidate. */
+int dsh_track_keyframe_candidate(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* n);
 /* DefTracking::TrackWithMotionModel (:342-375) after SetPose: DefORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, true)
  * (Modules/Matching/DefORBmatcher.cc:296-424) with the resident last-frame list as LastFrame, and again with th_wide on cleared
  * mvpMapPoints when the first search finds fewer than min_matches (:364-370).  The reference passes th = 20, th_wide = 25,
@@ -1371,6 +1377,84 @@ typedef struct dsh_keyframe_sfn_result {
   int32_t ok;                       /* ShapeFromNormals::estimate's return value */
 } dsh_keyframe_sfn_result;
 int dsh_keyframe_sfn(dsh_mpdb* db, const dsh_keyframe_sfn_input* in, double* ctrl_raw, double* ctrl, float* pts, dsh_keyframe_sfn_result* out);
+
+/* ---- a new keyframe on the resident stores: creation and covisibility connections -------------------------------------------------
+ * The two steps of a keyframe's life cycle that come before and after the map point upkeep of dsh_keyframe_process_new.  Both take the
+ * point store alone; the keyframe store travels in the input struct.
+ *
+ * CREATION.  DefTracking::CreateNewKeyFrame (Modules/Tracking/DefTracking.cc:696-707), that is KeyFrame::KeyFrame from a Frame
+ * (Thirdparty/ORBSLAM_2/src/KeyFrame.cc:37-75) and DefKeyFrame::DefKeyFrame (Modules/Common/DefKeyFrame.cc:42-77), on the tracking
+ * thread at every tenth frame (DefTracking.cc:175-178).  dsh_keyframe_create leaves both stores, host mirrors included, in the state
+ * these four calls leave them in, in this order:
+ *   1. dsh_kfdb_add with the camera centre of Tcw and bad = 0.  The centre is KeyFrame::SetPose's, computed by the one function that
+ *      serves dsh_keyframe_set_pose; kf->Ow and kf->bad are not read.
+ *   2. dsh_mpdb_add_keyframe with the table, parent -1 and bad = 0.  The table is points[N], or with points == NULL the resident
+ *      keyframe candidate of the last dsh_track_end_frame, copied device to device; the candidate is not consumed.
+ *   3. dsh_keyframe_snapshot_positions of the new slot (DefKeyFrame.cc:60-74: point held, not bad, has a facet).
+ *   4. dsh_keyframe_surface_init with kpn, when kpn is given.  NormaliseKeypoints (DefKeyFrame.cc:94-133) and the bounding box stay
+ *      with the caller, as they do for dsh_keyframe_surface_init.
+ * One block goes up, two launches run (the block into the arrays of both stores, then the snapshot) and one result block comes down;
+ * the tables, rows and keyframe arrays grow inside the call when they must.  No observation is added: the reference adds them later,
+ * in ProcessNewKeyFrame (dsh_keyframe_process_new).  ComputeBoW, the grid and the images have no counterpart in the stores.
+ * Refusals are decided on the host mirrors before any device work and leave neither store changed, DSH_ERR_ARG each: a NULL points
+ * without a candidate, or with one whose length is not kf->N; a table entry that is neither -1 nor a point of the store; a keyframe
+ * store that is NULL, of another context or detached, or that holds another number of keyframes than the point store (the new slot is
+ * the same in both); everything dsh_kfdb_add refuses (an octave outside 0 .. 127, levels outside 1 .. 32, a centre that is not
+ * finite); a Tcw or kpn that is not finite; N > 8192; a store that holds 65535 keyframes already.  Then a host-only context is
+ * DSH_ERR_NO_DEVICE.
+ *
+ * CONNECTIONS.  dsh_keyframe_update_connections is KeyFrame::UpdateConnections (KeyFrame.cc:326-419), which
+ * LocalMapping::ProcessNewKeyFrame calls right after its loop (LocalMapping.cc:167), for keyframe `slot`.  Index order stands for
+ * pointer order; every value is an integer and every output exact.
+ *   weights     for every table entry of the keyframe that holds a point p that is not bad, every live record (p, k) of the log with
+ *               k != slot adds 1 to w[k] (:335-357).  A point held by m entries counts m times; erased records do not count; there
+ *               is no bad test on keyframe k.  counted_kf / counted_w: the n_counted keyframes with w > 0, by ascending slot
+ *               (mConnectedKeyFrameWeights).
+ *   empty       no positive weight (:361): nothing changes, n_counted = n_connected = 0, parent_set = 0, max_kf = -1.
+ *   pKFmax      max_weight / max_kf: the first keyframe in ascending slot order with a strictly larger weight (:373-381) -- the LOWEST
+ *               slot among the maxima.
+ *   connected   every keyframe with w >= th; if there is none, the single pair (max_weight, max_kf) (:382-393).
+ *   order       ordered_kf / ordered_w, n_connected entries: descending weight and, among equal weights, DESCENDING slot -- sort on
+ *               (weight, pointer) and push_front (:395-402).  The tie rule is the opposite of pKFmax's; both are the reference's.
+ *   parent      the store keeps mbFirstConnection per keyframe in its host mirror: true from dsh_mpdb_add_keyframe and
+ *               dsh_keyframe_create on.  When it is true and slot != 0, the keyframe's parent in the store becomes ordered_kf[0] and the
+ *               flag clears (:412-417, parent_set = 1).  Slot 0 (mnId == 0) never gets a parent here and keeps its flag.  A parent given
+ *               to dsh_mpdb_add_keyframe or set by dsh_mpdb_set_keyframe_parent does not clear the flag -- KeyFrame::ChangeParent does
+ *               not touch mbFirstConnection either -- so the first call with a positive weight OVERWRITES such a parent, as the
+ *               reference would.  `parent` is the keyframe's parent after the call, -1 for none.
+ * Not kept in the store: AddConnection on the OTHER keyframes and their re-sorted lists (KeyFrame.cc:149-185), which no module of
+ * DefSLAM reads but the viewer; the caller applies them to its host objects from ordered_kf / ordered_w.
+ * At most four launches and no host read between them: a clear, the table's multiplicities, one coalesced sweep over the log with a
+ * histogram in LDS (the vote of dsh_local_map_update with the table as the frame and the own slot left out), and the ordering, which
+ * is exact for as many keyframes as the store may hold: (w << 16) | slot is a unique key, w <= 8192, slot < 65535.  One block down.
+ * The call reads no key point index, so records added without one are fine.  th is 100 in the reference (KeyFrame.cc:369).
+ * DSH_ERR_ARG: slot outside the store; th < 1; a list given and capacity smaller than the store's keyframe count; a keyframe with more
+ * than 8192 key points; a store with more than 65535 keyframes.  Then a host-only context is DSH_ERR_NO_DEVICE. */
+typedef struct dsh_keyframe_create_input {
+  dsh_kfdb* kfdb;               /* of the same context; must hold exactly as many keyframes as the point store */
+  const dsh_mp_keyframe* kf;    /* N, descriptor rows, octaves, levels, scale factors as for dsh_kfdb_add; Ow and bad are not read */
+  const float* Tcw;             /* 16, row major: F.mTcw */
+  const int32_t* points;        /* N ids or -1, or NULL: the resident keyframe candidate, whose length must equal kf->N */
+  const float* kpn;             /* N x 2 mpKeypointNorm, or NULL: no Surface is initialised */
+} dsh_keyframe_create_input;
+typedef struct dsh_keyframe_create_result {
+  int32_t slot;                 /* of the new keyframe, in both stores */
+  int32_t n_held;               /* table entries that hold a point */
+  int32_t n_snapshot;           /* entries whose position was taken */
+  float Ow[3];                  /* the camera centre written */
+} dsh_keyframe_create_result;
+int dsh_keyframe_create(dsh_mpdb* db, const dsh_keyframe_create_input* in, dsh_keyframe_create_result* out);
+
+typedef struct dsh_keyframe_connections {
+  int32_t n_counted;            /* keyframes with a weight > 0 */
+  int32_t n_connected;          /* length of mvpOrderedConnectedKeyFrames */
+  int32_t parent;               /* the keyframe's parent after the call, -1: none */
+  int32_t parent_set;           /* 1: this call set it, the first connection */
+  int32_t max_weight, max_kf;   /* nmax, pKFmax */
+} dsh_keyframe_connections;
+/* counted_kf, counted_w, ordered_kf, ordered_w: capacity entries each, each may be NULL; out may be NULL */
+int dsh_keyframe_update_connections(dsh_mpdb* db, int32_t slot, int32_t th, int32_t capacity, int32_t* counted_kf, int32_t* counted_w,
+                                    int32_t* ordered_kf, int32_t* ordered_w, dsh_keyframe_connections* out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

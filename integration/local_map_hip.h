@@ -120,11 +120,19 @@ class MapPointStoreHIP {
     return dsh_trackstate_seed_local_points(db_, (int)ids.size(), ids.data()) == DSH_OK;
   }
   int point_count() const { return (int)points_.size(); }
+  int keyframe_count() const { return (int)kfs_.size(); }
   // a point the store created itself (dsh_template_switch): the host object made for it takes the id; ids arrive in order
   bool AdoptPoint(MapPointT* p, int id) {
     if (id != (int)points_.size()) return false;
     ids_[p] = id;
     points_.push_back(p);
+    return true;
+  }
+  // a keyframe the library put into the store itself (dsh_keyframe_create): its host object takes the slot; slots arrive in order
+  bool AdoptKeyFrame(KeyFrameT* kf, int slot) {
+    if (slot != (int)kfs_.size()) return false;
+    slots_[kf] = slot;
+    kfs_.push_back(kf);
     return true;
   }
   // DefPoseOptimization moved these points (DefMapPoint::RecalculatePosition)

@@ -59,6 +59,8 @@ class KeyFrameStoreHIP {
     slots_.clear();
     return dsh_kfdb_clear(db_);
   }
+  // a keyframe the library put into the store itself (dsh_keyframe_create): its host object takes the slot
+  void Adopt(KeyFrameT* kf, int32_t slot) { slots_[kf] = slot; }
   // the keyframe's slot, added on first sight; its bad flag refreshed.  -1 on failure (*rc has the status).
   int32_t Slot(KeyFrameT* kf, int* rc) {
     typename std::map<KeyFrameT*, int32_t>::iterator it = slots_.find(kf);

@@ -2,11 +2,13 @@
 // integration/local_map_hip.h, integration/track_close_hip.h and integration/anchor_pairs_hip.h touch
 // (reference declaration behind each), for the repository's CI: OpenCV is not in the build image.  Inside DefSLAM these are not used.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstddef>
 #include <cstdint>
 #include <map>
 #include <set>
+#include <utility>
 #include <vector>
 
 #include "standin_types.h"   // standin::KeyPoint (cv::KeyPoint: pt, octave)
@@ -112,6 +114,26 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
   int rows = 0, cols = 0;                                               // imGray.rows, imGray.cols :228
   std::vector<float> surface_points;                                    // DefKeyFrame::surface->get3DSurfacePoint(i, x3c): 3 per key point
   std::vector<KeyPoint> mpKeypointNorm;                                 // DefKeyFrame.h: the normalised key points (surface_store_hip.h)
+  // what KeyFrame::UpdateConnections touches (keyframe_create_hip.h)
+  std::map<LmKeyFrame*, int> mConnectedKeyFrameWeights;                 // :237
+  std::vector<LmKeyFrame*> mvpOrderedConnectedKeyFrames;                // :238
+  std::vector<int> mvOrderedWeights;                                    // :239
+  bool mbFirstConnection = true;                                        // :242
+  void AddChild(LmKeyFrame* kf) { mspChildrens.insert(kf); }            // :77
+  void AddConnection(LmKeyFrame* kf, int weight) {                      // :66 (KeyFrame.cc:149-185, with UpdateBestCovisibles)
+    std::map<LmKeyFrame*, int>::iterator it = mConnectedKeyFrameWeights.find(kf);
+    if (it != mConnectedKeyFrameWeights.end() && it->second == weight) return;
+    mConnectedKeyFrameWeights[kf] = weight;
+    std::vector<std::pair<int, LmKeyFrame*>> by_weight;
+    for (const auto& kv : mConnectedKeyFrameWeights) by_weight.push_back(std::make_pair(kv.second, kv.first));
+    std::sort(by_weight.begin(), by_weight.end());
+    mvpOrderedConnectedKeyFrames.clear();
+    mvOrderedWeights.clear();
+    for (size_t i = by_weight.size(); i-- > 0;) {
+      mvpOrderedConnectedKeyFrames.push_back(by_weight[i].second);
+      mvOrderedWeights.push_back(by_weight[i].first);
+    }
+  }
   // what SurfaceRegistration::registerSurfaces writes (surface_register_store_hip.h)
   float Tcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPose() :60
   void SetPose(const float* T) {                                        // :59 (KeyFrame.cc:97-111: Tcw, Ow = -Rwc * tcw, Twc)
