@@ -242,6 +242,26 @@ class KeyframeConnectionsC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_counted", "n_connected", "parent", "parent_set", "max_weight", "max_kf")]
 
 
+class KeyframeViewC(C.Structure):
+    _fields_ = ([("N", C.c_int32), ("kp_px", c_float_p)] +
+                [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mnMinX", "mnMaxX", "mnMinY", "mnMaxY")] +
+                [("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("warp_grid", BbsC)])
+
+
+class WarpPairInputC(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("kfdb", C.c_void_p), ("ddb", C.c_void_p), ("slot", C.c_int32), ("anchor", C.c_int32), ("tag", C.c_int32),
+                ("lam", C.c_double), ("min_pairs", C.c_int32), ("max_iters", C.c_int32), ("radius", C.c_float), ("th_low", C.c_int32),
+                ("n_pairs", C.c_int32), ("pair_idx1", c_i32_p), ("pair_idx2", c_i32_p), ("n_queries", C.c_int32), ("query_idx1", c_i32_p)]
+
+
+class WarpPairResultC(C.Structure):
+    _fields_ = ([("x", c_double_p), ("pair_state", c_u8_p), ("query_state", c_u8_p), ("query_match", c_i32_p), ("query_point", c_i32_p),
+                 ("query_added", c_u8_p), ("init_ok", C.c_int32), ("fitted", C.c_int32), ("info", C.c_int32 * 2), ("costs", C.c_double * 2),
+                 ("first_record", C.c_int64)] +
+                [(n, C.c_int32) for n in ("n_filtered", "n_matched", "n_appended", "n_list", "n_skipped", "n_dropped", "n_kept", "n_stored", "rounds")] +
+                [("erase", PointEraseCountsC)])
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -280,6 +300,7 @@ EXPORTED_SYMBOLS = [
     "dsh_keyframe_surface_take_normals", "dsh_keyframe_surface_gather", "dsh_keyframe_surface_get", "dsh_keyframe_surface_vertices",
     "dsh_keyframe_sfn", "dsh_keyframe_surface_state",
     "dsh_track_keyframe_candidate", "dsh_keyframe_create", "dsh_keyframe_update_connections",
+    "dsh_keyframe_set_view", "dsh_keyframe_get_view", "dsh_keyframe_warp_pair",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -452,6 +473,9 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_track_keyframe_candidate.argtypes = [vp, i32, c_i32_p, c_i32_p]
     L.dsh_keyframe_create.argtypes = [vp, C.POINTER(KeyframeCreateInputC), C.POINTER(KeyframeCreateResultC)]
     L.dsh_keyframe_update_connections.argtypes = [vp, i32, i32, i32, c_i32_p, c_i32_p, c_i32_p, c_i32_p, C.POINTER(KeyframeConnectionsC)]
+    L.dsh_keyframe_set_view.argtypes = [vp, i32, C.POINTER(KeyframeViewC)]
+    L.dsh_keyframe_get_view.argtypes = [vp, i32, C.POINTER(KeyframeViewC), c_float_p]
+    L.dsh_keyframe_warp_pair.argtypes = [vp, C.POINTER(WarpPairInputC), C.POINTER(WarpPairResultC)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

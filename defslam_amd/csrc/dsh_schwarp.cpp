@@ -12,6 +12,7 @@
 #include "../../include/defslam_hip.h"
 #include "dsh_ctx.h"
 #include "dsh_diffdb.h"
+#include "dsh_schwarp.h"
 #include "mapping_launch.h"
 #include "schwarp_problem.h"
 
@@ -48,7 +49,7 @@ int dsh_schwarp_eval(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp1, 
 // The batched fit: every problem's inputs go up in ONE copy, the fits advance together through a fixed sequence of launches
 // with the trust-region control on the device (nrsfm_kernels.hip: nrsfm_swp_fit_batch), every result comes back in ONE copy.
 // stores / db (both or neither): the DiffProp records of the matches that are kept go into the device-resident database instead of
-// (or besides) the host -- dsh_schwarp_fit_batch_store.
+// (or besides) the host -- dsh_schwarp_fit_batch_store.  fit_batch: the checks; dsh::swp_fit_stages (dsh_schwarp.h): the stages.
 static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_schwarp_store* stores, dsh_diffdb* db) {
   dsh_ctx_base* c = dsh_base(ctx);
   if (!c) return DSH_ERR_ARG;
@@ -60,7 +61,6 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     for (int b = 0; b < B; b++) worst += std::max(probs[b].P, 0);
     if (ddb_reserve(db, db->count + worst) != 0) return dsh_fail(c, DSH_ERR_HIP, "dsh_schwarp_fit_batch_store: out of device memory while growing the database");
   }
-  int maxP = 0, maxN = 0, max_it = 0;
   for (int b = 0; b < B; b++) {
     const dsh_schwarp_problem& q = probs[b];
     if (!args_ok(&q.bbs, q.P, q.kp1, q.kp2, q.invsig, q.x) || q.max_iters < 0 || q.max_iters > 1000) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit_batch: bad argument in problem " + std::to_string(b));
@@ -68,6 +68,14 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
       return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit: more than 256 control points (the one-workgroup solve handles 2N <= 512 unknowns; the reference uses 13 x 15 = 195)");
     if (!db && (q.diff == nullptr) != (q.drop == nullptr)) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit_batch: diff and drop go together");
     if (db && !stores[b].point_id) return dsh_fail(c, DSH_ERR_ARG, "dsh_schwarp_fit_batch_store: point_id missing in problem " + std::to_string(b));
+  }
+  return dsh::swp_fit_stages(c, B, probs, stores, db, nullptr);
+}
+
+int dsh::swp_fit_stages(dsh_ctx_base* c, int B, dsh_schwarp_problem* probs, const dsh_schwarp_store* stores, dsh_diffdb* db, SwpDevice* dev) {
+  int maxP = 0, maxN = 0, max_it = 0;
+  for (int b = 0; b < B; b++) {
+    const dsh_schwarp_problem& q = probs[b];
     maxP = std::max(maxP, q.P); maxN = std::max(maxN, q.bbs.nptsu * q.bbs.nptsv); max_it = std::max(max_it, q.max_iters);
   }
   hipStream_t st = c->stream;
@@ -89,9 +97,9 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     const dsh_schwarp_problem& q = probs[b];
     const size_t n2 = (size_t)sizes[b].n2;
     Off& o = off[b];
-    o.kp1 = in.take(8 * (size_t)q.P);
-    o.kp2 = in.take(8 * (size_t)q.P);
-    o.isg = in.take(4 * (size_t)q.P);
+    o.kp1 = in.take(dev ? 0 : 8 * (size_t)q.P);   // dev: the matches lie on the device already
+    o.kp2 = in.take(dev ? 0 : 8 * (size_t)q.P);
+    o.isg = in.take(dev ? 0 : 4 * (size_t)q.P);
     o.cs = in.take(8 * n2);
     // bending matrix of the Warp::initialize stage: one per run of problems with the same grid and weight
     o.bend = 0;
@@ -144,12 +152,14 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     const Off& o = off[b];
     const SwpSizes& s = sizes[b];
     const bool init = q.init_lambda > 0.0;
-    std::memcpy(in.host<float>(o.kp1), q.kp1, 8 * (size_t)q.P); std::memcpy(in.host<float>(o.kp2), q.kp2, 8 * (size_t)q.P);
-    std::memcpy(in.host<float>(o.isg), q.invsig, 4 * (size_t)q.P);
+    if (!dev) {
+      std::memcpy(in.host<float>(o.kp1), q.kp1, 8 * (size_t)q.P); std::memcpy(in.host<float>(o.kp2), q.kp2, 8 * (size_t)q.P);
+      std::memcpy(in.host<float>(o.isg), q.invsig, 4 * (size_t)q.P);
+    }
     std::fill_n(in.host<double>(o.cs), s.n2, 1.0);
     if (init) {
       if (b == 0 || off[b - 1].bend != o.bend) dsh::bbs_bending_dense(&q.bbs, q.init_lambda, in.host<double>(o.bend));
-    } else {
+    } else if (!dev) {
       std::memcpy(hx + o.xo, q.x, 8 * (size_t)s.n2);
     }
     SwpFit f{};
@@ -157,12 +167,12 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
     f.fx = q.fx; f.fy = q.fy;
     f.n2 = s.n2; f.m = s.m; f.np = s.np; f.il = s.il; f.bwt = s.bwt; f.npi = s.npi; f.bwti = s.bwti;
     f.max_iters = q.max_iters;
-    f.kp1 = in.dev<float>(o.kp1); f.kp2 = in.dev<float>(o.kp2); f.isg = in.dev<float>(o.isg);
+    f.kp1 = dev ? dev->kp1 : in.dev<float>(o.kp1); f.kp2 = dev ? dev->kp2 : in.dev<float>(o.kp2); f.isg = dev ? dev->isg : in.dev<float>(o.isg);
     f.cs = in.dev<double>(o.cs);
     f.bend = init ? in.dev<double>(o.bend) : nullptr;
     f.x = out.dev<double>(o.xo);
-    f.diff = db ? sdiff + 18 * (size_t)b * maxP : (q.diff ? out.dev<float>(o.diff) : nullptr);
-    f.drop = db ? sdrop + (size_t)b * maxP : (q.drop ? out.dev<uint8_t>(o.drop) : nullptr);
+    f.diff = dev ? dev->diff : db ? sdiff + 18 * (size_t)b * maxP : (q.diff ? out.dev<float>(o.diff) : nullptr);
+    f.drop = dev ? dev->drop : db ? sdrop + (size_t)b * maxP : (q.drop ? out.dev<uint8_t>(o.drop) : nullptr);
     f.info = out.dev<int32_t>(o.info);
     f.costs = out.dev<double>(o.costs);
     f.scal = reinterpret_cast<double*>(dzero.as<char>() + zoff);
@@ -193,9 +203,14 @@ static int fit_batch(dsh_ctx* ctx, int B, dsh_schwarp_problem* probs, const dsh_
       }
   }
   if (const int rc = in.send(c)) return rc;
-  HIPCHK(c, hipMemcpyAsync(out.d, hx, x_bytes, hipMemcpyHostToDevice, st));
+  if (dev) HIPCHK(c, hipMemcpyAsync(out.d + off[0].xo, dev->x0, 8 * (size_t)sizes[0].n2, hipMemcpyDeviceToDevice, st));
+  else HIPCHK(c, hipMemcpyAsync(out.d, hx, x_bytes, hipMemcpyHostToDevice, st));
   if (fits_end > x_bytes) HIPCHK(c, hipMemsetAsync(out.d + x_bytes, 0, fits_end - x_bytes, st));
   HIPCHK(c, nrsfm_swp_fit_batch(in.dev<SwpFit>(o_fits), B, maxP, maxN, max_it, with_init, st));
+  if (dev) {   // the results stay where they are; the caller's block brings them down
+    dev->x = out.dev<double>(off[0].xo); dev->info = out.dev<int32_t>(off[0].info); dev->costs = out.dev<double>(off[0].costs);
+    return DSH_OK;
+  }
   if (db) {   // kept records -> the database, in (fit, match) order; records added = exclusive scan position + keep flag of the last entry
     HIPCHK(c, ddb_append((int)nall, sdrop, sdiff, in.dev<int32_t>(o_pid), in.dev<int32_t>(o_tag), in.dev<int32_t>(o_idx2), skeep.as<int32_t>(), spos.as<int32_t>(),
                          stmp.p, ddb_scan_tmp_bytes((int)nall), db->count, db->cap, db->rec, db->pid, db->tag, db->idx2, st));

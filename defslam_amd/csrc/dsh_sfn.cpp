@@ -191,6 +191,56 @@ int dsh::sfn_stages(dsh_ctx_base* c, const dsh_bbs* bbs, int n, const double* u,
   return DSH_OK;
 }
 
+// The body of dsh_warp_initialize / the second stage of dsh_keyframe_warp_pair: the matches come from the host (kp1, kp2) or lie on the
+// device with the constant operands (dev).
+int dsh::warp_init_stages(dsh_ctx_base* c, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, double lambda, WarpInitDevice* dev, double* x, int32_t* ok) {
+  const int N = bbs->nptsu * bbs->nptsv;
+  if (!dev) *ok = 0;
+  hipStream_t st = c->stream;
+  const int np = nrsfm_swp_solve_np(N), kd = 3 * bbs->nptsv + 3;   // colocation and bending couple a 4 x 4 patch: banded
+  const size_t Nz = (size_t)N, Pz = (size_t)P;
+  UpBlock up;
+  const size_t o_B = up.take(dev ? 0 : 8 * Nz * Nz), o_ones = up.take(dev ? 0 : 8 * Nz), o_k1 = up.copy_of(dev ? nullptr : kp1, 8 * Pz),
+               o_k2 = up.copy_of(dev ? nullptr : kp2, 8 * Pz);
+  Arena ws;   // x and the scalars of the solve are neighbours: the block down lies on them
+  const size_t o_C = ws.take(8 * Pz * Nz), o_r0 = ws.take(8 * Pz), o_r1 = ws.take(8 * Pz), o_G = ws.take(8 * Nz * Nz), o_g0 = ws.take(8 * Nz), o_g1 = ws.take(8 * Nz),
+               o_M = ws.take(8 * (size_t)np * np), o_W = ws.take(8 * (size_t)np * 16), o_x = ws.take(8 * 2 * Nz), o_scal = ws.take(256);
+  char* w = nullptr;
+  HIPCHK(c, c->scratch.take(ws.size, (void**)&w));
+  auto f64 = [&](size_t off) { return reinterpret_cast<double*>(w + off); };
+  if (!dev) {
+    if (const int rc = up.stage(c)) return rc;
+    bending_dense(bbs, lambda, up.host<double>(o_B));
+    std::fill_n(up.host<double>(o_ones), Nz, 1.0);
+    if (const int rc = up.send(c)) return rc;
+  }
+  const float *dk1 = dev ? dev->kp1 : up.dev<float>(o_k1), *dk2 = dev ? dev->kp2 : up.dev<float>(o_k2);
+  const double *dB = dev ? dev->bend : up.dev<double>(o_B), *dones = dev ? dev->ones : up.dev<double>(o_ones);
+  HIPCHK(c, hipMemsetAsync(w + o_C, 0, 8 * Pz * Nz, st));
+  HIPCHK(c, hipMemsetAsync(w + o_scal, 0, 256, st));
+  HIPCHK(c, nrsfm_warp_coloc(bbs_par(bbs, 1), P, dk1, dk2, f64(o_C), f64(o_r0), f64(o_r1), st));
+  // g1 = C^T (-q2y) first (G is rebuilt by the second call), then G = C^T C, g0 = C^T (-q2x); G += Bending
+  HIPCHK(c, nrsfm_swp_normal(P, N, f64(o_C), f64(o_r1), dones, f64(o_G), f64(o_g1), st));
+  HIPCHK(c, nrsfm_swp_normal(P, N, f64(o_C), f64(o_r0), dones, f64(o_G), f64(o_g0), st));
+  HIPCHK(c, nrsfm_mat_add(Nz * Nz, dB, f64(o_G), st));
+  HIPCHK(c, nrsfm_swp_solve(N, f64(o_G), f64(o_g0), 1e300, f64(o_M), f64(o_W), f64(o_x), f64(o_scal) + 2, 0, kd, st));
+  HIPCHK(c, nrsfm_swp_resolve(N, f64(o_g1), f64(o_M), f64(o_W), f64(o_x) + N, 0, kd, st));
+  if (dev) {   // x and the scalars stay where they are
+    dev->x = f64(o_x); dev->scal = f64(o_scal);
+    return DSH_OK;
+  }
+  DownBlock down;
+  down.copy_to(x, 8 * 2 * Nz);
+  const size_t d_s = down.take_exact(64);
+  if (const int rc = down.at(c, w + o_x)) return rc;
+  if (const int rc = down.receive(c)) return rc;
+  const double* s8 = down.host<double>(d_s);
+  bool finite = true;
+  for (int i = 0; i < 2 * N; i++) finite = finite && std::isfinite(x[i]);
+  *ok = ((s8[2] != 0.0 || s8[3] != 0.0) && finite) ? 1 : 0;
+  return DSH_OK;
+}
+
 extern "C" {
 
 int dsh_sfn_estimate(dsh_ctx* ctx, const dsh_bbs* bbs, int n, const double* u, const double* v, const float* normals, double bending_weight,
@@ -213,41 +263,7 @@ int dsh_warp_initialize(dsh_ctx* ctx, const dsh_bbs* bbs, int P, const float* kp
   if (!bbs_grid_ok(bbs) || P <= 0 || !kp1 || !kp2 || !x || !ok) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: bad argument");
   const int N = bbs->nptsu * bbs->nptsv;
   if (N > 512) return dsh_fail(c, DSH_ERR_ARG, "dsh_warp_initialize: more than 512 control points (one-workgroup solve)");
-  *ok = 0;
-  hipStream_t st = c->stream;
-  const int np = nrsfm_swp_solve_np(N), kd = 3 * bbs->nptsv + 3;   // colocation and bending couple a 4 x 4 patch: banded
-  const size_t Nz = (size_t)N, Pz = (size_t)P;
-  UpBlock up;
-  const size_t o_B = up.take(8 * Nz * Nz), o_ones = up.take(8 * Nz), o_k1 = up.copy_of(kp1, 8 * Pz), o_k2 = up.copy_of(kp2, 8 * Pz);
-  Arena ws;   // x and the scalars of the solve are neighbours: the block down lies on them
-  const size_t o_C = ws.take(8 * Pz * Nz), o_r0 = ws.take(8 * Pz), o_r1 = ws.take(8 * Pz), o_G = ws.take(8 * Nz * Nz), o_g0 = ws.take(8 * Nz), o_g1 = ws.take(8 * Nz),
-               o_M = ws.take(8 * (size_t)np * np), o_W = ws.take(8 * (size_t)np * 16), o_x = ws.take(8 * 2 * Nz), o_scal = ws.take(256);
-  char* w = nullptr;
-  HIPCHK(c, c->scratch.take(ws.size, (void**)&w));
-  auto f64 = [&](size_t off) { return reinterpret_cast<double*>(w + off); };
-  if (const int rc = up.stage(c)) return rc;
-  bending_dense(bbs, lambda, up.host<double>(o_B));
-  std::fill_n(up.host<double>(o_ones), Nz, 1.0);
-  if (const int rc = up.send(c)) return rc;
-  HIPCHK(c, hipMemsetAsync(w + o_C, 0, 8 * Pz * Nz, st));
-  HIPCHK(c, hipMemsetAsync(w + o_scal, 0, 256, st));
-  HIPCHK(c, nrsfm_warp_coloc(bbs_par(bbs, 1), P, up.dev<float>(o_k1), up.dev<float>(o_k2), f64(o_C), f64(o_r0), f64(o_r1), st));
-  // g1 = C^T (-q2y) first (G is rebuilt by the second call), then G = C^T C, g0 = C^T (-q2x); G += Bending
-  HIPCHK(c, nrsfm_swp_normal(P, N, f64(o_C), f64(o_r1), up.dev<double>(o_ones), f64(o_G), f64(o_g1), st));
-  HIPCHK(c, nrsfm_swp_normal(P, N, f64(o_C), f64(o_r0), up.dev<double>(o_ones), f64(o_G), f64(o_g0), st));
-  HIPCHK(c, nrsfm_mat_add(Nz * Nz, up.dev<double>(o_B), f64(o_G), st));
-  HIPCHK(c, nrsfm_swp_solve(N, f64(o_G), f64(o_g0), 1e300, f64(o_M), f64(o_W), f64(o_x), f64(o_scal) + 2, 0, kd, st));
-  HIPCHK(c, nrsfm_swp_resolve(N, f64(o_g1), f64(o_M), f64(o_W), f64(o_x) + N, 0, kd, st));
-  DownBlock down;
-  down.copy_to(x, 8 * 2 * Nz);
-  const size_t d_s = down.take_exact(64);
-  if (const int rc = down.at(c, w + o_x)) return rc;
-  if (const int rc = down.receive(c)) return rc;
-  const double* s8 = down.host<double>(d_s);
-  bool finite = true;
-  for (int i = 0; i < 2 * N; i++) finite = finite && std::isfinite(x[i]);
-  *ok = ((s8[2] != 0.0 || s8[3] != 0.0) && finite) ? 1 : 0;
-  return DSH_OK;
+  return dsh::warp_init_stages(c, bbs, P, kp1, kp2, lambda, nullptr, x, ok);
 }
 
 int dsh_search_by_schwarp(dsh_ctx* ctx, const dsh_bbs* bbs, const double* x, int Q, const float* kp1, const uint8_t* desc1, const float* cam2,

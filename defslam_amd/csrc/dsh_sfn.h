@@ -28,4 +28,18 @@ int sfn_stages(dsh_ctx_base* c, const dsh_bbs* bbs, int n, const double* u, cons
                double bending_weight, double mean_depth, int n_all, const double* u_all, const double* v_all, const SfnDevice* dev, double* ctrl_raw,
                double* ctrl, float* pts, int32_t* ok);
 
+// The same for Warps::Warp::initialize: dsh_keyframe_warp_pair (dsh_warppair.cpp) initialises on the matches its gather left on the
+// device.  The constant operands travel in the caller's own upload block (a call stages one block between two synchronisations):
+// bend = the N x N matrix of bbs_bending_dense(bbs, lambda), ones = N ones.
+struct WarpInitDevice {
+  const float *kp1, *kp2;       // P x 2 each
+  const double *bend, *ones;
+  // set by the stages: x (2 N control points) and the 32 scalars of the solve behind it; nothing comes down, nothing is waited for
+  double *x, *scal;
+};
+
+// The body of dsh_warp_initialize behind its checks and the device gate (nptsu * nptsv <= 512, P > 0).  With dev, kp1, kp2, lambda, x
+// and ok are not read or written.  Without dev, the calls, their order and their operands are what they were.
+int warp_init_stages(dsh_ctx_base* c, const dsh_bbs* bbs, int P, const float* kp1, const float* kp2, double lambda, WarpInitDevice* dev, double* x, int32_t* ok);
+
 }  // namespace dsh

@@ -12,6 +12,7 @@
 //   dsh_tracksft.cpp      dsh_track_sft_observations, dsh_track_sft
 //   dsh_surfreg.cpp       dsh_keyframe_snapshot_positions, dsh_keyframe_register and the keyframe pose of the keyframe store
 //   dsh_surfstore.cpp     dsh_keyframe_surface_*, dsh_keyframe_sfn: the resident Surface of a keyframe
+//   dsh_warppair.cpp      dsh_keyframe_set_view, dsh_keyframe_get_view, dsh_keyframe_warp_pair (warppair_problem.h, warppair_kernels.hip)
 //   dsh_keyframe_create.cpp  dsh_track_keyframe_candidate, dsh_keyframe_create, dsh_keyframe_update_connections (keyframe_create_problem.h,
 //                         keyframe_create_kernels.hip)
 #pragma once
@@ -58,6 +59,9 @@ struct dsh_mpdb : dsh_store {
   uint8_t* d_surf_has = nullptr;
   int32_t* d_surf_nn = nullptr;
   double* d_surf_depth = nullptr;
+  // the view of a keyframe (dsh_keyframe_set_view), parallel to d_table: per table entry the pixel key point mvKeysUn[i].pt; its
+  // scalars live in surf[slot].  An entry means something from dsh_keyframe_set_view of its keyframe on (surf[slot].has_view).
+  float* d_view_px = nullptr;
   LmHdr* d_hdr = nullptr;
   // the resident last-frame list (dsh_track_end_frame): per key point of the last frame the id it holds or -1, and its octave (-1 there)
   int32_t *d_last_ids = nullptr, *d_last_oct = nullptr;
@@ -75,6 +79,11 @@ struct dsh_mpdb : dsh_store {
     uint8_t has_surface = 0, has_depth = 0;
     int32_t n_normals = 0;               // numberofNormals_, as d_surf_nn holds it
     dsh_bbs grid{};                      // of the depth spline, valdim 1
+    // dsh_keyframe_set_view: camera (fx, fy, cx, cy), image bounds (mnMinX, mnMaxX, mnMinY, mnMaxY), image grid, warp grid
+    uint8_t has_view = 0;
+    float cam[4] = {0, 0, 0, 0}, bounds[4] = {0, 0, 0, 0};
+    int32_t grid_cols = 0, grid_rows = 0;
+    dsh_bbs warp{};
   };
   std::vector<SurfKf> surf;
   int32_t n_local_points = 0;
@@ -112,7 +121,7 @@ struct dsh_mpdb : dsh_store {
     for (void* p : {(void*)d_xyz, (void*)d_nrm, (void*)d_maxd, (void*)d_desc, (void*)d_bad, (void*)d_cnt, (void*)d_local_ids, (void*)d_visible,
                     (void*)d_found, (void*)d_nobs, (void*)d_nodes, (void*)d_ref_ids, (void*)d_bary, (void*)d_log, (void*)d_kf, (void*)d_table,
                     (void*)d_local_kf, (void*)d_hdr, (void*)d_last_ids, (void*)d_last_oct, (void*)d_ref_kf, (void*)d_log_idx, (void*)d_snap_point, (void*)d_snap_xyz,
-                    (void*)d_cand_ids, (void*)d_surf_normal, (void*)d_surf_pts, (void*)d_surf_kpn, (void*)d_surf_has, (void*)d_surf_nn, (void*)d_surf_depth})
+                    (void*)d_cand_ids, (void*)d_surf_normal, (void*)d_surf_pts, (void*)d_surf_kpn, (void*)d_surf_has, (void*)d_surf_nn, (void*)d_surf_depth, (void*)d_view_px})
       if (p) (void)hipFree(p);
   }
 };
@@ -167,14 +176,16 @@ inline hipError_t mpdb_reserve_last_frame(dsh_mpdb* db, int32_t N) {
 
 // room for `need` table entries: the tables, the snapshot and the surface points beside them
 inline hipError_t mpdb_reserve_table(dsh_mpdb* db, long long need) {
-  if (need <= db->Tcap && db->d_table && db->d_snap_point && db->d_snap_xyz && db->d_surf_normal && db->d_surf_pts && db->d_surf_kpn && db->d_surf_has)
+  if (need <= db->Tcap && db->d_table && db->d_snap_point && db->d_snap_xyz && db->d_surf_normal && db->d_surf_pts && db->d_surf_kpn && db->d_surf_has &&
+      db->d_view_px)
     return hipSuccess;
   const size_t cap = (size_t)std::max(need, db->d_table ? 2 * db->Tcap : db->Tcap), T = (size_t)db->T;
   hipError_t e;
   if ((e = dsh_store_grow_array(&db->d_table, T, cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_snap_point, T, cap)) != hipSuccess ||
       (e = dsh_store_grow_array(&db->d_snap_xyz, 3 * T, 3 * cap)) != hipSuccess ||
       (e = dsh_store_grow_array(&db->d_surf_normal, 3 * T, 3 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_surf_pts, 3 * T, 3 * cap)) != hipSuccess ||
-      (e = dsh_store_grow_array(&db->d_surf_kpn, 2 * T, 2 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_surf_has, T, cap)) != hipSuccess)
+      (e = dsh_store_grow_array(&db->d_surf_kpn, 2 * T, 2 * cap)) != hipSuccess || (e = dsh_store_grow_array(&db->d_surf_has, T, cap)) != hipSuccess ||
+      (e = dsh_store_grow_array(&db->d_view_px, 2 * T, 2 * cap)) != hipSuccess)
     return e;
   db->Tcap = (long long)cap;
   return hipSuccess;

@@ -26,7 +26,10 @@
   * DefTracking::CreateNewKeyFrame (Modules/Tracking/DefTracking.cc:696-707) in one call on both stores, with the table taken on the
     device from the keyframe candidate the end of the frame left there, and KeyFrame::UpdateConnections
     (Thirdparty/ORBSLAM_2/src/KeyFrame.cc:326-419) over the observation log, which gives the keyframe its parent
-    (dsh_track_keyframe_candidate, dsh_keyframe_create, dsh_keyframe_update_connections).
+    (dsh_track_keyframe_candidate, dsh_keyframe_create, dsh_keyframe_update_connections);
+  * the per-anchor body of SchwarpDatabase::add (SchwarpDatabase.cc:107-117): DefORBmatcher::findbyWarp and
+    SchwarpDatabase::calculateSchwarps with the key points, descriptor rows and tables read from the stores
+    (dsh_keyframe_set_view, dsh_keyframe_warp_pair).
 
 The map points, who observes whom, and the keyframes' point tables and spanning tree stay in HBM (MapPointStore); the work runs on the
 device (localmap_kernels.hip, track_kernels.hip), there is no CPU fallback.  Where the reference iterates pointer-ordered containers the
@@ -405,6 +408,38 @@ class KeyframeConnections:
     parent_set: bool                    # this call set it (the first connection)
     max_weight: int                     # nmax
     max_kf: int                         # pKFmax, -1 when no weight is positive
+
+
+@dataclass
+class KeyframeView:
+    """What warp_pair reads of a keyframe beyond its Surface (dsh_keyframe_view)."""
+    kp_px: np.ndarray                   # (N,2) float32 mvKeysUn[i].pt
+    K: tuple                            # fx, fy, cx, cy
+    bounds: tuple                       # mnMinX, mnMaxX, mnMinY, mnMaxY
+    grid_cols: int
+    grid_rows: int
+    warp_grid: object                   # nrsfm.Bbs: umin, umax, NCu, vmin, vmax, NCv, valdim
+
+
+WARP_NO_MATCH, WARP_FILTERED, WARP_UNFITTED, WARP_SKIPPED, WARP_DROPPED, WARP_KEPT, WARP_STORED = range(7)
+
+
+@dataclass
+class WarpPair:
+    """One anchor of SchwarpDatabase::add (dsh_keyframe_warp_pair)."""
+    x: np.ndarray                       # (2 NCu NCv,) the fitted warp, or the initialisation when not fitted
+    init_ok: bool
+    fitted: bool
+    info: np.ndarray                    # iterations, accepted steps
+    costs: np.ndarray                   # initial, final
+    pair_state: np.ndarray              # WARP_* per pair
+    query_state: np.ndarray             # WARP_* per query
+    query_match: np.ndarray             # idx2 or -1
+    query_point: np.ndarray             # the point a matched query registered, -1: none
+    query_added: np.ndarray             # bool: the query's observation record was appended
+    first_record: int
+    counts: dict                        # n_filtered, n_matched, n_appended, n_list, n_skipped, n_dropped, n_kept, n_stored, rounds
+    erase: dict                         # n_found, n_ref_moved, n_set_bad, n_records, n_entries
 
 
 def _i32(a):
@@ -1125,3 +1160,50 @@ class MapPointStore:
         nc, no = int(r.n_counted), int(r.n_connected)
         return KeyframeConnections(counted_kf=ck[:nc].copy(), counted_w=cw[:nc].copy(), ordered_kf=ok[:no].copy(), ordered_w=ow[:no].copy(),
                                    parent=int(r.parent), parent_set=bool(r.parent_set), max_weight=int(r.max_weight), max_kf=int(r.max_kf))
+
+    # ---- the mapping thread: one anchor of SchwarpDatabase::add ----
+    def set_view(self, slot: int, view: KeyframeView):
+        """The pixel key points, camera, image bounds, image grid and warp grid of keyframe `slot`.  Once per keyframe, after surface_init."""
+        px = np.ascontiguousarray(view.kp_px, np.float32).reshape(-1, 2)
+        v = _lib.KeyframeViewC(int(px.shape[0]), _ptr(px if px.shape[0] else np.zeros((1, 2), np.float32), C.c_float), *[float(a) for a in view.K],
+                               *[float(a) for a in view.bounds], int(view.grid_cols), int(view.grid_rows), view.warp_grid.c())
+        self._call("dsh_keyframe_set_view", int(slot), C.byref(v))
+
+    def get_view(self, slot: int) -> KeyframeView:
+        from .nrsfm import Bbs
+        N = self._kf_len(slot)
+        px = np.zeros((max(N, 1), 2), np.float32)
+        v = _lib.KeyframeViewC()
+        self._call("dsh_keyframe_get_view", int(slot), C.byref(v), _ptr(px, C.c_float))
+        g = v.warp_grid
+        return KeyframeView(kp_px=px[:N], K=(v.fx, v.fy, v.cx, v.cy), bounds=(v.mnMinX, v.mnMaxX, v.mnMinY, v.mnMaxY), grid_cols=int(v.grid_cols),
+                            grid_rows=int(v.grid_rows), warp_grid=Bbs(g.umin, g.umax, g.nptsu, g.vmin, g.vmax, g.nptsv, g.valdim))
+
+    def warp_pair(self, kf_store, diff_db, slot: int, anchor: int, pair_idx1, pair_idx2, query_idx1, lam: float, tag: Optional[int] = None,
+                  min_pairs: int = 20, max_iters: int = 3, radius: float = 2.0, th_low: int = 50) -> WarpPair:
+        """DefORBmatcher::findbyWarp and SchwarpDatabase::calculateSchwarps for new keyframe `slot` and anchor keyframe `anchor`, every
+        key point array read from the stores: pair_idx1 / pair_idx2 are the matched key points (anchor, slot) as anchors() lists them,
+        query_idx1 the anchor's key points to search for, ascending.  The DiffProp records go into diff_db (nrsfm.DiffDatabase) under
+        the point ids of the store with `tag` (default: slot).  x has the 2 NCu NCv entries of the anchor's warp grid."""
+        i1, i2, q1 = _i32(pair_idx1), _i32(pair_idx2), _i32(query_idx1)
+        if i1.shape[0] != i2.shape[0]:
+            raise ValueError("pair_idx1 and pair_idx2 differ in length")
+        P, Q = int(i1.shape[0]), int(q1.shape[0])
+        m = max(Q, 1)
+        x = np.zeros(512, np.float64)                             # room for the 256 control points the call accepts
+        ps, qs, qa = np.zeros(max(P, 1), np.uint8), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+        qm, qp = np.full(m, -1, np.int32), np.full(m, -1, np.int32)
+        inp = _lib.WarpPairInputC(self._ctx._h, kf_store._h if kf_store is not None else None, diff_db._h if diff_db is not None else None, int(slot),
+                                  int(anchor), int(slot if tag is None else tag), float(lam), int(min_pairs), int(max_iters), float(radius), int(th_low),
+                                  P, _ptr(i1 if P else np.zeros(1, np.int32), C.c_int32), _ptr(i2 if P else np.zeros(1, np.int32), C.c_int32), Q,
+                                  _ptr(q1 if Q else np.zeros(1, np.int32), C.c_int32))
+        r = _lib.WarpPairResultC(_ptr(x, C.c_double), _ptr(ps, C.c_uint8), _ptr(qs, C.c_uint8), _ptr(qm, C.c_int32), _ptr(qp, C.c_int32), _ptr(qa, C.c_uint8))
+        self._call("dsh_keyframe_warp_pair", C.byref(inp), C.byref(r))
+        v = _lib.KeyframeViewC()
+        self._call("dsh_keyframe_get_view", int(anchor), C.byref(v), None)   # the anchor's grid, from the host mirror
+        x = x[:2 * v.warp_grid.nptsu * v.warp_grid.nptsv].copy()
+        return WarpPair(x=x, init_ok=bool(r.init_ok), fitted=bool(r.fitted), info=np.array(r.info, np.int32), costs=np.array(r.costs, np.float64),
+                        pair_state=ps[:P], query_state=qs[:Q], query_match=qm[:Q], query_point=qp[:Q], query_added=qa[:Q].astype(bool),
+                        first_record=int(r.first_record),
+                        counts={n: int(getattr(r, n)) for n in ("n_filtered", "n_matched", "n_appended", "n_list", "n_skipped", "n_dropped", "n_kept", "n_stored", "rounds")},
+                        erase={n: int(getattr(r.erase, n)) for n in ("n_found", "n_ref_moved", "n_set_bad", "n_records", "n_entries")})

@@ -387,6 +387,49 @@ def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2, nu: 
     return dict(bbs=bbs, x=x, kp1=kp1, desc1=desc1, cam2=cam2, bounds2=bounds2, kp2=kp2, desc2=desc2, has_mp2=has_mp2)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# One anchor of SchwarpDatabase::add with every array keyed by key point index: a new keyframe (normalised and pixel key points,
+# descriptor rows, octaves) and anchor keyframes whose matched key points (pairs) and searched key points (queries) have a counterpart
+# among the new keyframe's key points, placed by make_warp_problem's motion.
+def make_warp_pair_scene(n_kp: int = 200, n_pairs: int = 64, n_queries: int = 65, n_anchors: int = 1, seed: int = 0, nu: int = 13, nv: int = 15,
+                         outliers: float = 0.0, lost_queries: float = 0.2):
+    """Per anchor: kpn (n_kp,2) float32, desc, octave, the warp grid bbs (nu x nv over the bounding box of its key points +- 0.10),
+    pair_idx1 / pair_idx2 and query_idx1 (ascending).  The new keyframe: kpn2, px2 = kpn2 * (fx, fy) + (cx, cy) in float32, desc2,
+    octave2; the key points nobody names are distractors.  outliers: share of the pairs whose second key point is moved away;
+    lost_queries: share of the queries whose counterpart carries a foreign descriptor."""
+    rng = np.random.default_rng(seed)
+    assert n_pairs + n_queries <= n_kp and n_anchors * (n_pairs + n_queries) <= n_kp
+    K = (520.0, 515.0, 322.5, 241.25)
+    f, c0 = np.array(K[:2], np.float32), np.array(K[2:], np.float32)
+    px2 = np.stack([rng.uniform(5, 635, n_kp), rng.uniform(5, 475, n_kp)], 1).astype(np.float32)
+    kpn2 = ((px2 - c0) / f).astype(np.float32)
+    desc2 = rng.integers(0, 256, (n_kp, 32), dtype=np.uint8)
+    free = list(rng.permutation(n_kp))
+    anchors = []
+    for a in range(n_anchors):
+        kpn = np.stack([rng.uniform(-0.55, 0.55, n_kp), rng.uniform(-0.42, 0.42, n_kp)], 1).astype(np.float32)
+        pr = make_warp_problem(seed=seed + 10 * a + 1, nu=nu, nv=nv, kp1=kpn.astype(np.float64),
+                               motion=(np.array([0.02, -0.05, 0.03]) * (1 + a), np.array([0.06, -0.04, 0.02]) * (1 - 0.5 * a)))
+        desc = rng.integers(0, 256, (n_kp, 32), dtype=np.uint8)
+        sel = rng.permutation(n_kp)[:n_pairs + n_queries]
+        idx2 = np.array([free.pop() for _ in sel], np.int32)
+        tgt = pr["kp2"][sel].astype(np.float32)
+        moved = rng.uniform(size=len(sel)) < outliers
+        moved[n_pairs:] = False
+        tgt[moved] += rng.uniform(-0.2, 0.2, size=(int(moved.sum()), 2)).astype(np.float32)
+        kpn2[idx2] = tgt
+        px2[idx2] = (tgt * f + c0).astype(np.float32)
+        for k, (i1, i2) in enumerate(zip(sel, idx2)):
+            lost = k >= n_pairs and rng.uniform() < lost_queries
+            desc2[i2] = rng.integers(0, 256, 32, dtype=np.uint8) if lost else _flip_bits(rng, desc[i1], rng.integers(0, 40))
+        order = np.argsort(sel[n_pairs:])
+        anchors.append(dict(kpn=kpn, desc=desc, octave=rng.integers(0, 8, n_kp).astype(np.int32), bbs=pr["bbs"][:6] + (2,),
+                            pair_idx1=sel[:n_pairs].astype(np.int32), pair_idx2=idx2[:n_pairs].copy(),
+                            query_idx1=sel[n_pairs:][order].astype(np.int32), query_idx2=idx2[n_pairs:][order].copy()))
+    return dict(seed=seed, K=K, bounds=(0.0, 640.0, 0.0, 480.0), grid=(64, 48), scale_factors=(1.2 ** np.arange(8)).astype(np.float32), anchors=anchors,
+                kpn2=kpn2, px2=px2, desc2=desc2, octave2=rng.integers(0, 8, n_kp).astype(np.int32), lam=1e-2)
+
+
 def make_register_scene(n: int = 600, seed: int = 5, noise: float = 2e-3, outliers: float = 0.05, scale: float = 1.35):
     """Surface registration (SurfaceRegistration::registerSurfaces): a keyframe surface (up to scale, in world coordinates) and
     the map points it has to be aligned with, the keyframe's inverse pose and a stream of uniform numbers for scaleMinMedian."""

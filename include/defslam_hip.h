@@ -1456,6 +1456,134 @@ typedef struct dsh_keyframe_connections {
 int dsh_keyframe_update_connections(dsh_mpdb* db, int32_t slot, int32_t th, int32_t capacity, int32_t* counted_kf, int32_t* counted_w,
                                     int32_t* ordered_kf, int32_t* ordered_w, dsh_keyframe_connections* out);
 
+/* ---- one anchor of SchwarpDatabase::add on the resident stores -----------------------------------------------------------------------
+ * The per-anchor body of SchwarpDatabase::add (Modules/Mapping/SchwarpDatabase.cc:107-117): DefORBmatcher::findbyWarp
+ * (Modules/Matching/DefORBmatcher.cc:47-71) and SchwarpDatabase::calculateSchwarps (SchwarpDatabase.cc:145-349) for a new keyframe
+ * `slot` (KF2) and one anchor keyframe `anchor` (KF1), with every per-key-point array read where the stores hold it.  Both entries take
+ * the point store alone; the context, the keyframe store and the DiffProp database travel in the input struct.
+ *
+ * dsh_keyframe_set_view keeps what the pair call needs of a keyframe beyond its Surface: the pixel key points mvKeysUn[i].pt beside
+ * the keyframe tables (two float32 per table entry, parallel to the Surface arrays) and, in the store's host mirror, the camera, the
+ * image bounds, the image grid and the warp grid of the keyframe.  One upload and no launch beyond the copy.  DSH_ERR_ARG: slot
+ * outside the store; view->N not the keyframe's N; a NULL kp_px with N > 0; a value that is not finite; mnMaxX <= mnMinX or
+ * mnMaxY <= mnMinY; grid_cols or grid_rows < 1 or grid_cols * grid_rows > 8192; a warp grid with fewer than 4 control points along an
+ * axis or an empty domain.  DSH_ERR_STATE: a keyframe without a resident Surface (dsh_keyframe_surface_init); a second call for the
+ * keyframe.  Then a host-only context is DSH_ERR_NO_DEVICE.  dsh_mpdb_clear forgets the views.  dsh_keyframe_get_view reads one back
+ * (kp_px with room for N x 2 floats, may be NULL; view->kp_px is left NULL); DSH_ERR_STATE without a view.
+ *
+ * dsh_keyframe_warp_pair runs the stages below.  The index lists go up in one block; the count of stage 5 is the one value read back
+ * before the result block.  With N = NCu * NCv control points of the ANCHOR's warp grid and P = n_pairs:
+ *   1 GATHER    kp1[i] = kpn[anchor][pair_idx1[i]], kp2[i] = kpn[slot][pair_idx2[i]] (the resident mpKeypointNorm), invsig[i] =
+ *               sqrtf(1.0f / (sf * sf)) in float32, every operation rounded, sf the anchor's scale factor at the octave of key point
+ *               pair_idx1[i] (ORBextractor.cc:422,430 and DefORBmatcher.cc:133-135).  For query j the key point kpn[anchor][query_idx1[j]]
+ *               and the anchor's 32-byte descriptor row.  KF2's descriptor rows and pixel key points are read in place.
+ *   2 INITIALISE  Warp::initialize (DefORBmatcher.cc:138-153): the launches of dsh_warp_initialize on the gathered arrays, same kernels
+ *               and operands; init_ok is that call's verdict.  Then NaN entries among the first min(2N, 2 * NCu * NCu) values of x
+ *               become 0 (the reference's loop bound, :139-152).
+ *   3 FILTER    (:155-186) the residuals of dsh_schwarp_eval with the anchor's (fx, fy) in the slots and lambda 0; the block of 2P
+ *               residuals is corrected as Ceres' HuberLoss(5.77) corrector does: s = the sum of their squares in ascending index
+ *               order in double without contraction (one lane adds them, so the bytes are those of a host loop), and when
+ *               s > 5.77 * 5.77 every residual is multiplied by sqrt(5.77 / sqrt(s)).  Match i is FILTERED when r[2i]^2 + r[2i+1]^2 >
+ *               20, two products and one sum without contraction: entries 2i and 2i+1 of [x_0 .. x_{P-1}, y_0 .. y_{P-1}], two
+ *               neighbouring x- (or y-) residuals, as the reference pairs them.  A filtered match clears table[slot][pair_idx2[i]]
+ *               (EraseMapPointMatch); its observation record stays.  The kept matches are compacted in order.
+ *   4 SEARCH AND REGISTER  (:57-70, :189-294) dsh_search_by_schwarp's kernels with the gathered queries against KF2 in place; a key
+ *               point of KF2 is taken when its table entry is not -1 AFTER the clears of stage 3.  For query j in ascending order that
+ *               found idx2, with p = table[anchor][query_idx1[j]] != -1: the first such query of a point without a live record
+ *               (p, slot) appends (p, slot, idx2) to the log and n_obs[p] += 1 (AddObservation with its early return); and
+ *               table[slot][idx2] = p, where of several queries that found one key point the LAST in query order holds the entry.
+ *               Records are appended in ascending query order.  No UpdateNormalAndDepth and no descriptor election: the reference
+ *               makes none here.  The kept list becomes the kept pairs followed by the matched queries (p == -1 included).
+ *   5 COUNT     the length L of the kept list is read back and sizes the fit.  L < min_pairs ends the call with fitted = 0: the
+ *               kept entries are UNFITTED, the DiffProp database is untouched.
+ *   6 FIT       (SchwarpDatabase.cc:145-264) the stages of dsh_schwarp_fit_batch for one problem on the kept arrays where they lie:
+ *               slots (fy, fx) of the anchor, fx and fy of the anchor for the drop test, max_iters iterations, start value the x of
+ *               stage 2.  x, info and costs are that call's bytes for the same arrays.
+ *   7 RECORDS AND DROPS  (:268-346) the kept list in list order, entry j with (idx1, idx2), p1 = table[anchor][idx1] and
+ *               p2 = table[slot][idx2] as they are when the loop reaches j; the first matching case:
+ *                 p1 or p2 is -1 or bad                SKIPPED
+ *                 the fit's drop flag (error > 10 px)  DROPPED: MapPoint::EraseObservation(p2, slot) in full -- the record (p2, slot) is
+ *                                                      blanked when it is live, n_obs goes down, a reference keyframe that was `slot`
+ *                                                      moves to the lowest remaining slot, and at n_obs <= 2 DefMapPoint::setBadFlag
+ *                                                      blanks the point's records and clears the table entries they name -- then
+ *                                                      table[slot][idx2] = -1
+ *                 ref_kf[p1] != anchor                 KEPT, nothing stored
+ *                 otherwise                            STORED: the DiffProp record goes into in->ddb under point id p1 with in->tag and
+ *                                                      idx2, in list order; p1 is the caller's newInformation_
+ *               The loop is sequential in the reference.  Its entries interact in three ways, all through DROPPED entries that are
+ *               reached alive: a later entry with the same idx2 finds p2 == -1; a later entry that names a point the drop set bad
+ *               (as p1 or p2) is skipped; a later entry whose idx1 is the key point index of a blanked record of the anchor finds
+ *               p1 == -1.  (A point that lost its record and moved its reference keyframe to the anchor is read with the new one.)
+ *               The device resolves this with integer elections -- atomicMin of the list position per idx2, per point and per anchor
+ *               entry over the alive dropped entries -- repeated until the alive flags stop changing: entry j depends on entries
+ *               before j alone, so the fixed point is the sequential result whatever the schedule; a list without chains settles
+ *               in two rounds.  A counting second pass writes.
+ * After the call both stores, their host mirrors and in->ddb are what the reference's objects are when calculateSchwarps returns.
+ *
+ * Results: out->x[2N] (the fit's, or stage 2's when fitted == 0), pair_state[n_pairs], query_state[n_queries] (DSH_WARP_*),
+ * query_match[n_queries] (idx2 or -1), query_point[n_queries] (p of stage 4, -1: none) and query_added[n_queries] (1: this query's
+ * record was appended; the records follow first_record in ascending query order); each array may be NULL.  Counts as named; `erase` as
+ * dsh_point_store_erase_observations reports them (n_entries counts the entries the cascade cleared).
+ *
+ * DSH_ERR_ARG, decided on the host mirrors before any device work, nothing written: in or out NULL; in->ctx not the context of the
+ * store; a keyframe store or database that is NULL, of another context or detached; a keyframe store that does not hold the point
+ * store's keyframes or holds an octave >= levels; slot or anchor outside the store; anchor == slot (the reference cannot reach it: no
+ * point is anchored in the keyframe being added); a keyframe with more than 8192 key points; n_pairs < 1 or n_queries < 0; an index
+ * outside its keyframe; a repeated pair_idx2 or query_idx1; more than 256 control points in the anchor's warp grid; max_iters outside
+ * 0 .. 1000, min_pairs < 1, a radius that is not positive and finite, th_low > 256.  DSH_ERR_STATE: a keyframe without a view; a live
+ * record without a key point index.  Then a host-only context is DSH_ERR_NO_DEVICE.  DSH_ERR_HIP after the first append leaves the
+ * store unusable, as for dsh_keyframe_process_new. */
+typedef struct dsh_keyframe_view {
+  int32_t N;
+  const float* kp_px;               /* N x 2: mvKeysUn[i].pt */
+  float fx, fy, cx, cy;
+  float mnMinX, mnMaxX, mnMinY, mnMaxY;
+  int32_t grid_cols, grid_rows;     /* FRAME_GRID_COLS, FRAME_GRID_ROWS */
+  dsh_bbs warp_grid;                /* umin, umax, NCu, vmin, vmax, NCv, valdim of the keyframe */
+} dsh_keyframe_view;
+int dsh_keyframe_set_view(dsh_mpdb* db, int32_t slot, const dsh_keyframe_view* view);
+int dsh_keyframe_get_view(dsh_mpdb* db, int32_t slot, dsh_keyframe_view* view, float* kp_px);
+
+#define DSH_WARP_NO_MATCH 0         /* a query that found no key point */
+#define DSH_WARP_FILTERED 1         /* a pair stage 3 removed */
+#define DSH_WARP_UNFITTED 2         /* on the kept list of a call that ended at stage 5 */
+#define DSH_WARP_SKIPPED 3
+#define DSH_WARP_DROPPED 4
+#define DSH_WARP_KEPT 5
+#define DSH_WARP_STORED 6
+typedef struct dsh_warp_pair_input {
+  dsh_ctx* ctx;                     /* the context of the store */
+  dsh_kfdb* kfdb;                   /* descriptor rows, octaves, scale factors */
+  dsh_diffdb* ddb;                  /* receives the DiffProp records */
+  int32_t slot, anchor, tag;        /* tag is stored with the records */
+  double lambda;
+  int32_t min_pairs, max_iters;     /* 20, 3 in the reference */
+  float radius;                     /* 2 */
+  int32_t th_low;                   /* 50 */
+  int32_t n_pairs;
+  const int32_t* pair_idx1;         /* key point of the anchor */
+  const int32_t* pair_idx2;         /* key point of the new keyframe, distinct */
+  int32_t n_queries;
+  const int32_t* query_idx1;        /* key points of the anchor, ascending and distinct */
+} dsh_warp_pair_input;
+typedef struct dsh_warp_pair_result {
+  double* x;                        /* 2 NCu NCv */
+  uint8_t* pair_state;              /* n_pairs */
+  uint8_t* query_state;             /* n_queries */
+  int32_t* query_match;             /* n_queries */
+  int32_t* query_point;             /* n_queries */
+  uint8_t* query_added;             /* n_queries */
+  int32_t init_ok, fitted;
+  int32_t info[2];                  /* iterations, accepted steps; zeros when fitted == 0 */
+  double costs[2];                  /* initial, final cost */
+  int64_t first_record;             /* log position of the first record stage 4 appended */
+  int32_t n_filtered, n_matched, n_appended, n_list;   /* stage 3, stage 4, records appended, L */
+  int32_t n_skipped, n_dropped, n_kept, n_stored;      /* stage 7 */
+  int32_t rounds;                   /* of the election of stage 7 */
+  dsh_point_erase_counts erase;
+} dsh_warp_pair_result;
+int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp_pair_result* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

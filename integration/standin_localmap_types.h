@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <set>
 #include <utility>
 #include <vector>
@@ -134,6 +135,15 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
       mvOrderedWeights.push_back(by_weight[i].first);
     }
   }
+  // what SchwarpDatabase::add, DefORBmatcher::findbyWarp and SchwarpDatabase::calculateSchwarps touch of a DefKeyFrame
+  // (schwarp_database_hip.h, schwarp_store_hip.h)
+  const uint8_t* descriptor(size_t i) const { return &mDescriptors[32 * i]; }   // mDescriptors.ptr(i)
+  int gridCols() const { return 64; }                                   // FRAME_GRID_COLS
+  int gridRows() const { return 48; }                                   // FRAME_GRID_ROWS
+  int NCu = 0, NCv = 0, valdim = 2, KeyframesRelated = 0;               // DefKeyFrame.h
+  double umin = 0, umax = 0, vmin = 0, vmax = 0;
+  float fx = 0, fy = 0, cx = 0, cy = 0, mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;   // KeyFrame.h:152, :210-213
+  std::vector<float> mvInvLevelSigma2;                                  // :190
   // what SurfaceRegistration::registerSurfaces writes (surface_register_store_hip.h)
   float Tcw[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // GetPose() :60
   void SetPose(const float* T) {                                        // :59 (KeyFrame.cc:97-111: Tcw, Ow = -Rwc * tcw, Twc)
@@ -144,6 +154,27 @@ class LmKeyFrame {                             // Thirdparty/ORBSLAM_2/include/K
       Twc[4 * r + 3] = Ow[r];
     }
   }
+};
+
+struct LmDiffProp {                            // Modules/Mapping/diffProp.h:52-83
+  std::pair<LmKeyFrame*, LmKeyFrame*> KFToKF;
+  size_t idx1 = 0, idx2 = 0;
+  float I1u, I1v, I2u, I2v, J12a, J12b, J12c, J12d, J21a, J21b, J21c, J21d, H12uux, H12uuy, H12uvx, H12uvy, H12vvx, H12vvy;
+};
+
+class LmWarpDatabase {                         // Modules/Mapping/WarpDatabase.h:39-72
+ public:
+  typedef std::vector<std::shared_ptr<LmDiffProp>> kr2krdata;
+  virtual ~LmWarpDatabase() = default;
+  virtual void add(LmKeyFrame* kf) = 0;
+  virtual void erase(LmKeyFrame* kf) = 0;
+  virtual void clear() = 0;
+  std::map<LmMapPoint*, kr2krdata>& getDiffDatabase() { return mapPointsDB_; }
+  std::map<LmMapPoint*, bool>& getToProccess() { return newInformation_; }
+
+ protected:
+  std::map<LmMapPoint*, bool> newInformation_;
+  std::map<LmMapPoint*, kr2krdata> mapPointsDB_;
 };
 
 class LmFrame {                                // Thirdparty/ORBSLAM_2/include/Frame.h
