@@ -103,8 +103,8 @@ def pose_to_f32_matrix(pose):
     return T
 
 
-def exp_times(d, pose):
-    """SE3Quat::exp(d) * pose, d = [omega, upsilon]."""
+def exp_times(d, pose, stats=None):
+    """SE3Quat::exp(d) * pose, d = [omega, upsilon].  stats: a dict whose "product_flips" counts the products that come out with w < 0."""
     om0, om1, om2 = d[0], d[1], d[2]
     theta = math.sqrt(om0 * om0 + om1 * om1 + om2 * om2)
     Om = [0.0, -om2, om1, om2, 0.0, -om0, -om1, om0, 0.0]
@@ -133,6 +133,8 @@ def exp_times(d, pose):
           qd[3] * q[1] + qd[1] * q[3] + qd[2] * q[0] - qd[0] * q[2],
           qd[3] * q[2] + qd[2] * q[3] + qd[0] * q[1] - qd[1] * q[0],
           qd[3] * q[3] - qd[0] * q[0] - qd[1] * q[1] - qd[2] * q[2]]
+    if stats is not None and nq[3] < 0:
+        stats["product_flips"] += 1
     return [td[0] + r0, td[1] + r1, td[2] + r2] + quat_unit_pos(nq)
 
 
@@ -303,6 +305,8 @@ class Result:
     n_bad: int
     n_good: int
     rounds: list
+    # what ran, for the coverage tests (tests/test_pose_only_points_cpu.py); nothing of the computation reads it
+    stats: dict = field(default_factory=dict)
 
 
 def positions(model, ids):
@@ -322,8 +326,12 @@ def solve(model, fr, order="sequential", outlier=None, xyz=None, block=BLOCK):
     uv = np.asarray(fr.kp, np.float32).reshape(N, 2)[idx].astype(float)
     w = np.asarray(fr.inv_level_sigma2, np.float32)[np.asarray(fr.octave).reshape(N)[idx]].astype(float)
     start = pose_from_f32_matrix(fr.Tcw)
+    T = [float(v) for v in np.asarray(fr.Tcw, np.float32).reshape(16)]
+    # start_raw_w: w as the conversion of the frame's pose leaves it, before normalizeRotation's flip
+    stats = dict(start_raw_w=quat_from_R([T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]])[3], product_flips=0, huber_below=0, huber_above=0,
+                 pivoted_solves=0, solves=0)
     if n_initial < 3:
-        return Result(flags, np.asarray(fr.Tcw, np.float32).reshape(4, 4).copy(), np.array(start), n_initial, 0, 0, [])
+        return Result(flags, np.asarray(fr.Tcw, np.float32).reshape(4, 4).copy(), np.array(start), n_initial, 0, 0, [], stats)
     level1 = np.zeros(n_initial, bool)
     rounds, est, n_bad = [], start, 0
     for rnd in range(4):
@@ -341,6 +349,10 @@ def solve(model, fr, order="sequential", outlier=None, xyz=None, block=BLOCK):
                 e0, e1, c, px, py, pz = edge_error(pose, K, Xa, uva, wa)
                 chi_last[act] = c
                 rho0, rho1 = huber(c) if robust else (c, np.ones_like(c))
+                if robust:
+                    below = int((c <= DELTA * DELTA).sum())
+                    stats["huber_below"] += below
+                    stats["huber_above"] += len(c) - below
                 return e0, e1, rho0, rho1, px, py, pz
 
             lam = ni = 0.0
@@ -376,9 +388,11 @@ def solve(model, fr, order="sequential", outlier=None, xyz=None, block=BLOCK):
                     for r in range(6):
                         Hs[7 * r] += lam
                     perm, ok = ldlt(Hs, 6)
+                    stats["solves"] += 1
+                    stats["pivoted_solves"] += perm != list(range(6))
                     if ok:
                         x = ldlt_solve(Hs, perm, b, 6)
-                    trial = exp_times(x, est)
+                    trial = exp_times(x, est, stats)
                     R.trial = trial
                     with np.errstate(all="ignore"):
                         tmp = float(ordered_sum(robust_chi2(trial)[2].reshape(-1, 1), ia, N, order, block)[0]) if ok else DBL_MAX
@@ -428,7 +442,7 @@ def solve(model, fr, order="sequential", outlier=None, xyz=None, block=BLOCK):
         rounds.append(R)
         if n_initial < 10:
             break
-    return Result(flags, pose_to_f32_matrix(est), np.array(est), n_initial, n_bad, n_initial - n_bad, rounds)
+    return Result(flags, pose_to_f32_matrix(est), np.array(est), n_initial, n_bad, n_initial - n_bad, rounds, stats)
 
 
 def classify(level1, chi_held, chi_fresh):
@@ -463,15 +477,31 @@ def true_pose(rng):
     return exp_times([float(v) for v in d], [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0])
 
 
-def make_case(seed, N, held, outlier_share=0.0, noise=0.5, perturb=0.02, n_bad_points=3, extra_points=17):
-    """A store model and a frame: `held` of N key points hold a point (the others are holes), octaves over LEVELS levels, a few bad points
-    that still take part, one id held by two key points (when held >= 4), outlier_share of the held key points displaced grossly, the
-    start pose `perturb` away from the pose that generated the key points."""
+def make_case(seed, N, held, outlier_share=0.0, noise=0.5, perturb=0.02, n_bad_points=3, extra_points=17, camera=None, sigma=None, behind=0,
+              top_octave=False):
+    """A store model and a frame: `held` of N key points hold a point (the others are holes), octaves over the levels of the sigma table,
+    a few bad points that still take part, one id held by two key points (when held >= 4), outlier_share of the held key points displaced
+    grossly, the start pose `perturb` away from the pose that generated the key points.
+
+    camera: (fx, fy, cx, cy, width, height); the points then fill that camera's own frustum at depths 3 to 8 (None: FX, FY, CX, CY and
+    the box they have always been drawn from).  sigma: the frame's mvInvLevelSigma2 (None: sigma_table()).  behind: that many held
+    points are mirrored to a negative depth, their key points being the projections they have there.  top_octave: every held key point
+    is at the table's last level.  The defaults draw exactly what this function drew before it had these arguments."""
     from store_model import MapModel
     rng = np.random.default_rng(seed)
     model = MapModel()
     P = max(held, 1) + extra_points
-    pts = np.stack([rng.uniform(-2, 2, P), rng.uniform(-1.5, 1.5, P), rng.uniform(3, 8, P)], 1).astype(np.float32)
+    sigma = sigma_table() if sigma is None else np.asarray(sigma, np.float32).reshape(-1)
+    levels = len(sigma)
+    if camera is None:
+        K = np.array([FX, FY, CX, CY], np.float32)
+        width, height = 640.0, 640.0                 # the range the holes' key points have always been drawn from
+        pts = np.stack([rng.uniform(-2, 2, P), rng.uniform(-1.5, 1.5, P), rng.uniform(3, 8, P)], 1).astype(np.float32)
+    else:
+        K = np.array(camera[:4], np.float32)
+        width, height = float(camera[4]), float(camera[5])
+        u, v, z = rng.uniform(0.05 * width, 0.95 * width, P), rng.uniform(0.05 * height, 0.95 * height, P), rng.uniform(3, 8, P)
+        pts = np.stack([(u - float(K[2])) / float(K[0]) * z, (v - float(K[3])) / float(K[1]) * z, z], 1).astype(np.float32)
     for p in range(P):
         model.add_point(xyz=pts[p], bad=False)
     for p in rng.choice(P, min(n_bad_points, P), replace=False):
@@ -483,13 +513,17 @@ def make_case(seed, N, held, outlier_share=0.0, noise=0.5, perturb=0.02, n_bad_p
     if held >= 4:
         ids[-1] = ids[0]                             # one id held by two key points
     fp[slots] = ids
-    octave = rng.integers(0, LEVELS, N).astype(np.int32)
-    kp = rng.uniform(0, 640, (N, 2)).astype(np.float32)
-    K = np.array([FX, FY, CX, CY], np.float32)
+    octave = rng.integers(0, levels, N).astype(np.int32)
+    if top_octave:
+        octave[slots] = levels - 1
+    kp = (rng.uniform(0, 640, (N, 2)) * np.array([width / 640.0, height / 640.0])).astype(np.float32)
+    for p in ids[1:1 + behind]:                      # behind the camera: the ray's mirror image at half the depth (not the id held twice)
+        pts[p] = np.float32(-0.5) * pts[p]
+        model.points[int(p)].xyz[:] = pts[p]
     if held:
         e0, e1, _, _, _, _ = edge_error(pose, [float(v) for v in K], pts[ids].astype(float), np.zeros((held, 2)), np.ones(held))
         proj = -np.stack([e0, e1], 1)
-        sig = np.sqrt(1.0 / sigma_table()[octave[slots]].astype(float))
+        sig = np.sqrt(1.0 / sigma[octave[slots]].astype(float))
         proj += rng.normal(0, noise, (held, 2)) * sig[:, None]
         n_out = int(round(outlier_share * held))
         if n_out:
@@ -499,7 +533,7 @@ def make_case(seed, N, held, outlier_share=0.0, noise=0.5, perturb=0.02, n_bad_p
     d = rng.normal(0, perturb, 6)
     start = exp_times([float(v) for v in d], pose)
     Tcw = pose_to_f32_matrix(start)
-    return model, Frame(Tcw, K, kp, octave, sigma_table(), fp), pose
+    return model, Frame(Tcw, K, kp, octave, sigma.copy(), fp), pose
 
 
 # name -> arguments of make_case.  The seeds are fixed so that the "sequential" and the "device" restatement agree on every decision

@@ -35,18 +35,19 @@ def frame_of(fr, outlier=None):
     return localmap.PoseOnlyFrame(fr.Tcw, fr.K, fr.kp, fr.octave, fr.inv_level_sigma2, fr.frame_points, outlier)
 
 
-def check(g, ref, name):
+def check(g, ref, name, pose_tol=R.POSE_TOL, chi2_rtol=R.CHI2_RTOL):
+    """A result against the restatement's; tests/test_pose_only_points_gpu.py passes the tolerances measured for its points."""
     print(f"{name}: n_initial {g.n_initial} rounds {g.rounds} iters {g.iters.tolist()} trials {g.trials.tolist()} bad {g.bad.tolist()} | "
-          f"pose diff {np.abs(g.pose - ref.pose).max():.3e} (tol {R.POSE_TOL:.3e})")
+          f"pose diff {np.abs(g.pose - ref.pose).max():.3e} (tol {pose_tol:.3e})")
     nr = len(ref.rounds)
     assert (g.n_initial, g.n_bad, g.n_good, g.rounds) == (ref.n_initial, ref.n_bad, ref.n_good, nr), name
     assert g.iters.tolist() == [r.iters for r in ref.rounds] + [0] * (4 - nr), name
     assert g.trials.tolist() == [r.trials for r in ref.rounds] + [0] * (4 - nr), name
     assert g.bad.tolist() == [r.bad for r in ref.rounds] + [0] * (4 - nr), name
     assert np.array_equal(g.outlier, ref.outlier), name
-    assert np.abs(g.pose - ref.pose).max() <= R.POSE_TOL, (name, np.abs(g.pose - ref.pose).max())
+    assert np.abs(g.pose - ref.pose).max() <= pose_tol, (name, np.abs(g.pose - ref.pose).max())
     for k, r in enumerate(ref.rounds):
-        assert abs(g.chi2[k] - r.chi2) <= R.CHI2_RTOL * max(r.chi2, 1.0), (name, k, g.chi2[k], r.chi2)
+        assert abs(g.chi2[k] - r.chi2) <= chi2_rtol * max(r.chi2, 1.0), (name, k, g.chi2[k], r.chi2)
     assert (g.chi2[nr:] == 0).all(), name
     assert np.abs(g.Tcw.view(np.int32).astype(np.int64) - ref.Tcw.view(np.int32)).max() <= 1, name
     if nr == 0:
