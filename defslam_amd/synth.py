@@ -277,12 +277,14 @@ def _coloc_dense(umin, umax, nu, vmin, vmax, nv, u, v):
     return A
 
 
-def make_warp_problem(n_matches: int = 400, seed: int = 3, nu: int = 13, nv: int = 15, noise: float = 5e-4, outliers: float = 0.0, kp1=None, motion=None):
+def make_warp_problem(n_matches: int = 400, seed: int = 3, nu: int = 13, nv: int = 15, noise: float = 5e-4, outliers: float = 0.0, kp1=None, motion=None,
+                      fx: float = 520.0, fy: float = 515.0, box=(0.55, 0.42), margin: float = 0.10):
     """One keyframe pair: matches kp1 -> kp2 under a plane-induced homography plus a ripple.  kp1 (given key points of the first keyframe,
-    e.g. a subset of one pool shared by several pairs) and motion (rotation vector, translation of the second camera) are optional."""
+    e.g. a subset of one pool shared by several pairs) and motion (rotation vector, translation of the second camera) are optional.
+    fx, fy: the focal lengths handed on; box: half extent of the key points drawn here; margin: the domain beyond the key points."""
     rng = np.random.default_rng(seed)
     if kp1 is None:
-        kp1 = np.stack([rng.uniform(-0.55, 0.55, n_matches), rng.uniform(-0.42, 0.42, n_matches)], 1)
+        kp1 = np.stack([rng.uniform(-box[0], box[0], n_matches), rng.uniform(-box[1], box[1], n_matches)], 1)
     else:
         kp1 = np.asarray(kp1, np.float64).reshape(-1, 2)
         n_matches = kp1.shape[0]
@@ -297,8 +299,8 @@ def make_warp_problem(n_matches: int = 400, seed: int = 3, nu: int = 13, nv: int
         bad = rng.uniform(size=n_matches) < outliers
         kp2[bad] += rng.uniform(-0.2, 0.2, size=(int(bad.sum()), 2))
     # domain: bounding box of the key points +- 0.10 (DefKeyFrame.cc:116-131)
-    umin, umax = float(kp1[:, 0].min() - 0.10), float(kp1[:, 0].max() + 0.10)
-    vmin, vmax = float(kp1[:, 1].min() - 0.10), float(kp1[:, 1].max() + 0.10)
+    umin, umax = float(kp1[:, 0].min() - margin), float(kp1[:, 0].max() + margin)
+    vmin, vmax = float(kp1[:, 1].min() - margin), float(kp1[:, 1].max() + margin)
     octave = rng.integers(0, 6, n_matches)
     invsig = np.sqrt((1.2 ** (-2.0 * octave)).astype(np.float32)).astype(np.float32)
     # start: what Warp::initialize hands over (Schwarp.cc:99-160) -- a regularised linear least-squares fit of the control
@@ -311,7 +313,7 @@ def make_warp_problem(n_matches: int = 400, seed: int = 3, nu: int = 13, nv: int
     cp = np.linalg.solve(C.T @ C + mu * np.eye(nu * nv), C.T @ kp2 + mu * ident)
     x0 = np.concatenate([cp[:, 0], cp[:, 1]])
     return dict(bbs=(umin, umax, nu, vmin, vmax, nv, 2), kp1=kp1.astype(np.float32), kp2=kp2.astype(np.float32), invsig=invsig, x0=x0,
-                fx=520.0, fy=515.0)
+                fx=float(fx), fy=float(fy))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -349,14 +351,19 @@ def make_sfn_scene(n_points: int = 600, seed: int = 4, noise: float = 0.01, with
 # Warp-guided match search: keyframe 1 key points (normalised) with ORB-like 256-bit descriptors, a warp, and keyframe 2
 # key points scattered around the predictions (pixels) with noisy copies of the descriptors, distractors, exact duplicates
 # (distance ties), points that already carry a map point and points outside the image / the grid.
-def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2, nu: int = 13, nv: int = 15):
-    """nu x nv: the control grid of the warp that predicts the matches."""
+def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2, nu: int = 13, nv: int = 15, cam2=(520.0, 515.0, 322.5, 241.25),
+                     bounds2=(0.0, 640.0, 0.0, 480.0), radius: float = 2.0, box=(0.55, 0.42), near: float = 1.3, twin: float = 0.2, around: float = 20.0):
+    """nu x nv: the control grid of the warp that predicts the matches.  cam2, bounds2: the view of keyframe 2; radius: the search radius the
+    scene is made for -- candidates lie within near * radius of their prediction, a duplicate within twin * radius of its original;
+    box: half extent of the warp's key points (its domain is that + 0.10); around: how far beyond the image the distractors reach."""
     rng = np.random.default_rng(seed)
-    pr = make_warp_problem(400, seed + 1, nu, nv)
+    pr = make_warp_problem(400, seed + 1, nu, nv, box=box)
     bbs = pr["bbs"][:6] + (2,)
     x = pr["x0"]
-    cam2 = np.array([520.0, 515.0, 322.5, 241.25], np.float32)
-    bounds2 = np.array([0.0, 640.0, 0.0, 480.0], np.float32)
+    cam2 = np.array(cam2, np.float32)
+    bounds2 = np.array(bounds2, np.float32)
+    near, twin = near * radius, twin * radius
+    lo, hi = bounds2[[0, 2]].astype(np.float64) - around, bounds2[[1, 3]].astype(np.float64) + around
     kp1 = np.stack([rng.uniform(bbs[0] + 0.02, bbs[1] - 0.02, n_query), rng.uniform(bbs[3] + 0.02, bbs[4] - 0.02, n_query)], 1).astype(np.float32)
     # predictions with numpy (double) only to PLACE key points of keyframe 2; the tests compare device and oracle, not this
     C = _coloc_dense(bbs[0], bbs[1], bbs[2], bbs[3], bbs[4], bbs[5], kp1[:, 0].astype(float), kp1[:, 1].astype(float))
@@ -368,16 +375,16 @@ def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2, nu: 
     for q in range(n_query):
         k = int(rng.integers(0, 4))                       # 0..3 candidates near the prediction
         for _ in range(k):
-            kp2.append(pix[q] + rng.uniform(-2.6, 2.6, 2))
+            kp2.append(pix[q] + rng.uniform(-near, near, 2))
             d = desc1[q].copy()
             flips = rng.integers(0, 256, int(rng.integers(0, 70)))
             for f in flips:
                 d[f // 8] ^= np.uint8(1 << (f % 8))
             desc2.append(d)
         if k and rng.uniform() < 0.25:                    # exact duplicate of the last candidate close by: a distance tie
-            kp2.append(kp2[-1] + rng.uniform(-0.4, 0.4, 2))
+            kp2.append(kp2[-1] + rng.uniform(-twin, twin, 2))
             desc2.append(desc2[-1].copy())
-    kp2 += list(np.stack([rng.uniform(-20, 660, n_extra), rng.uniform(-20, 500, n_extra)], 1))
+    kp2 += list(np.stack([rng.uniform(lo[0], hi[0], n_extra), rng.uniform(lo[1], hi[1], n_extra)], 1))
     desc2 += list(rng.integers(0, 256, (n_extra, 32), dtype=np.uint8))
     kp2 = np.asarray(kp2, np.float32)
     desc2 = np.asarray(desc2, np.uint8)
@@ -392,22 +399,28 @@ def make_match_scene(n_query: int = 600, n_extra: int = 900, seed: int = 2, nu: 
 # descriptor rows, octaves) and anchor keyframes whose matched key points (pairs) and searched key points (queries) have a counterpart
 # among the new keyframe's key points, placed by make_warp_problem's motion.
 def make_warp_pair_scene(n_kp: int = 200, n_pairs: int = 64, n_queries: int = 65, n_anchors: int = 1, seed: int = 0, nu: int = 13, nv: int = 15,
-                         outliers: float = 0.0, lost_queries: float = 0.2):
+                         outliers: float = 0.0, lost_queries: float = 0.2, views=None):
     """Per anchor: kpn (n_kp,2) float32, desc, octave, the warp grid bbs (nu x nv over the bounding box of its key points +- 0.10),
     pair_idx1 / pair_idx2 and query_idx1 (ascending).  The new keyframe: kpn2, px2 = kpn2 * (fx, fy) + (cx, cy) in float32, desc2,
     octave2; the key points nobody names are distractors.  outliers: share of the pairs whose second key point is moved away;
-    lost_queries: share of the queries whose counterpart carries a foreign descriptor."""
+    lost_queries: share of the queries whose counterpart carries a foreign descriptor.  views: one (K, bounds, grid, scale_factors) per
+    anchor and a last one for the new keyframe, instead of one view for all; they come back under "views", the new keyframe's also under
+    K, bounds, grid and scale_factors, and every keyframe's octaves lie inside its own table."""
     rng = np.random.default_rng(seed)
     assert n_pairs + n_queries <= n_kp and n_anchors * (n_pairs + n_queries) <= n_kp
-    K = (520.0, 515.0, 322.5, 241.25)
+    one = ((520.0, 515.0, 322.5, 241.25), (0.0, 640.0, 0.0, 480.0), (64, 48), (1.2 ** np.arange(8)).astype(np.float32))
+    assert views is None or len(views) == n_anchors + 1
+    K, bounds, grid, sf2 = one if views is None else views[-1]
     f, c0 = np.array(K[:2], np.float32), np.array(K[2:], np.float32)
-    px2 = np.stack([rng.uniform(5, 635, n_kp), rng.uniform(5, 475, n_kp)], 1).astype(np.float32)
+    px2 = np.stack([rng.uniform(bounds[0] + 5, bounds[1] - 5, n_kp), rng.uniform(bounds[2] + 5, bounds[3] - 5, n_kp)], 1).astype(np.float32)
+    # the anchors' key points: the usual box, or with views what the new keyframe sees of it (a little more: some predictions leave its image)
+    box = (0.55, 0.42) if views is None else tuple(float(0.5 * (bounds[2 * i + 1] - bounds[2 * i]) / K[i]) for i in range(2))
     kpn2 = ((px2 - c0) / f).astype(np.float32)
     desc2 = rng.integers(0, 256, (n_kp, 32), dtype=np.uint8)
     free = list(rng.permutation(n_kp))
     anchors = []
     for a in range(n_anchors):
-        kpn = np.stack([rng.uniform(-0.55, 0.55, n_kp), rng.uniform(-0.42, 0.42, n_kp)], 1).astype(np.float32)
+        kpn = np.stack([rng.uniform(-box[0], box[0], n_kp), rng.uniform(-box[1], box[1], n_kp)], 1).astype(np.float32)
         pr = make_warp_problem(seed=seed + 10 * a + 1, nu=nu, nv=nv, kp1=kpn.astype(np.float64),
                                motion=(np.array([0.02, -0.05, 0.03]) * (1 + a), np.array([0.06, -0.04, 0.02]) * (1 - 0.5 * a)))
         desc = rng.integers(0, 256, (n_kp, 32), dtype=np.uint8)
@@ -423,11 +436,15 @@ def make_warp_pair_scene(n_kp: int = 200, n_pairs: int = 64, n_queries: int = 65
             lost = k >= n_pairs and rng.uniform() < lost_queries
             desc2[i2] = rng.integers(0, 256, 32, dtype=np.uint8) if lost else _flip_bits(rng, desc[i1], rng.integers(0, 40))
         order = np.argsort(sel[n_pairs:])
-        anchors.append(dict(kpn=kpn, desc=desc, octave=rng.integers(0, 8, n_kp).astype(np.int32), bbs=pr["bbs"][:6] + (2,),
+        levels = 8 if views is None else len(views[a][3])
+        anchors.append(dict(kpn=kpn, desc=desc, octave=rng.integers(0, levels, n_kp).astype(np.int32), bbs=pr["bbs"][:6] + (2,),
                             pair_idx1=sel[:n_pairs].astype(np.int32), pair_idx2=idx2[:n_pairs].copy(),
                             query_idx1=sel[n_pairs:][order].astype(np.int32), query_idx2=idx2[n_pairs:][order].copy()))
-    return dict(seed=seed, K=K, bounds=(0.0, 640.0, 0.0, 480.0), grid=(64, 48), scale_factors=(1.2 ** np.arange(8)).astype(np.float32), anchors=anchors,
-                kpn2=kpn2, px2=px2, desc2=desc2, octave2=rng.integers(0, 8, n_kp).astype(np.int32), lam=1e-2)
+    sc = dict(seed=seed, K=K, bounds=bounds, grid=grid, scale_factors=np.asarray(sf2, np.float32), anchors=anchors,
+              kpn2=kpn2, px2=px2, desc2=desc2, octave2=rng.integers(0, len(sf2), n_kp).astype(np.int32), lam=1e-2)
+    if views is not None:
+        sc["views"] = [(tuple(float(v) for v in k), tuple(float(v) for v in b), tuple(g), np.asarray(t, np.float32)) for k, b, g, t in views]
+    return sc
 
 
 def make_register_scene(n: int = 600, seed: int = 5, noise: float = 2e-3, outliers: float = 0.05, scale: float = 1.35):

@@ -44,15 +44,13 @@ def _assert_same_bits(a, b):
     np.testing.assert_array_equal(a[4], b[4])
 
 
-@pytest.mark.parametrize("grid", gc.FIT_GRIDS, ids=gc.gid)
-def test_schwarp_eval_matches_oracle_on_every_grid(gpu_ctx, oracle_mod, grid):
-    """Warps::Warp::Evaluate + Warps::Schwarzian::Evaluate: residuals and the dense Jacobian, as test_schwarp_residuals_and_jacobian_match_oracle."""
+def _assert_eval_follows_oracle(ctx, oracle, pr, x, lam):
+    """The assertions of test_schwarp_residuals_and_jacobian_match_oracle, for any problem of synth.make_warp_problem."""
     from defslam_amd import nrsfm
-    pr, x, lam = gc.eval_problem(grid)
-    P, N = pr["kp1"].shape[0], grid[0] * grid[1]
+    P, N = pr["kp1"].shape[0], pr["bbs"][2] * pr["bbs"][5]
     b = _bbs(pr["bbs"])
-    ro, Jo = oracle_mod.schwarp_eval(pr["bbs"], pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x)
-    rg, Jg = nrsfm.schwarp_eval(gpu_ctx, b, pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x)
+    ro, Jo = oracle.schwarp_eval(pr["bbs"], pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x)
+    rg, Jg = nrsfm.schwarp_eval(ctx, b, pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x)
     np.testing.assert_array_equal(Jg != 0, Jo != 0)                       # sparsity: bit-exact tap indexing
     np.testing.assert_allclose(rg, ro, rtol=1e-13, atol=1e-15)
     np.testing.assert_allclose(Jg, Jo, rtol=1e-13, atol=1e-15)
@@ -62,9 +60,16 @@ def test_schwarp_eval_matches_oracle_on_every_grid(gpu_ctx, oracle_mod, grid):
     for k in [N // 5, N + N // 2, 2 * N - 1]:
         d = np.zeros_like(x)
         d[k] = 1e-6
-        fd = (nrsfm.schwarp_eval(gpu_ctx, b, pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x + d, False)[0] -
-              nrsfm.schwarp_eval(gpu_ctx, b, pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x - d, False)[0]) / 2e-6
+        fd = (nrsfm.schwarp_eval(ctx, b, pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x + d, False)[0] -
+              nrsfm.schwarp_eval(ctx, b, pr["kp1"], pr["kp2"], pr["invsig"], pr["fy"], pr["fx"], lam, x - d, False)[0]) / 2e-6
         np.testing.assert_allclose(fd[2 * P:], Jg[2 * P:, k], rtol=1e-5, atol=1e-7)
+
+
+@pytest.mark.parametrize("grid", gc.FIT_GRIDS, ids=gc.gid)
+def test_schwarp_eval_matches_oracle_on_every_grid(gpu_ctx, oracle_mod, grid):
+    """Warps::Warp::Evaluate + Warps::Schwarzian::Evaluate: residuals and the dense Jacobian, as test_schwarp_residuals_and_jacobian_match_oracle."""
+    pr, x, lam = gc.eval_problem(grid)
+    _assert_eval_follows_oracle(gpu_ctx, oracle_mod, pr, x, lam)
 
 
 @pytest.mark.parametrize("grid,k", gc.FIT_PARAMS, ids=gc.FIT_IDS)

@@ -184,6 +184,29 @@ def states_of(state, kept, P, pair_state, query_state):
 
 # ---- the map of a synth.make_warp_pair_scene ------------------------------------------------------------------------------------------
 
+def view_of(sc, a=None):
+    """(K, bounds, grid, scale factors) of anchor a, or of the new keyframe (a is None).  A scene made without `views` has one for all.
+    The reference takes KF->fx, KF->fy and KF->mvInvLevelSigma2 from the anchor (DefORBmatcher.cc:133-135, SchwarpDatabase.cc:200-201,
+    :284-285) and dKF2->fx, cx, IsInImage and GetFeaturesInArea from the new keyframe (DefORBmatcher.cc:229-247)."""
+    if "views" not in sc:
+        return sc["K"], sc["bounds"], sc["grid"], sc["scale_factors"]
+    return sc["views"][-1 if a is None else a]
+
+
+def exchanged(sc):
+    """The scene with every anchor's view and the new keyframe's trading places: what a call computes that reads the wrong keyframe's
+    camera, bounds, grid or scale factors.  The key points stay where they are."""
+    out = dict(sc)
+    out["exchange"] = True
+    return out
+
+
+def _views(sc, a):
+    """(the view the gather, filter and fit read, the view the search reads)."""
+    v1, v2 = view_of(sc, a), view_of(sc)
+    return (v2, v1) if sc.get("exchange") else (v1, v2)
+
+
 def build_model(sc, few_obs=(), other_ref=()):
     """The anchors at slots 0 .. A-1, two keyframes that only lend observations at A and A+1, the new keyframe at A+2.  Every pair and
     every query of every anchor is a point anchored in its anchor and observed there, in both lending keyframes (not for the points in
@@ -193,7 +216,6 @@ def build_model(sc, few_obs=(), other_ref=()):
     m = WarpPairRef()
     A = len(sc["anchors"])
     n_pts = sum(len(a["pair_idx1"]) + len(a["query_idx1"]) for a in sc["anchors"])
-    sf = sc["scale_factors"]
     tables = [[-1] * a["kpn"].shape[0] for a in sc["anchors"]] + [[-1] * n_pts, [-1] * n_pts, [-1] * sc["kpn2"].shape[0]]
     obs, p = [], 0
     for s, a in enumerate(sc["anchors"]):
@@ -210,7 +232,8 @@ def build_model(sc, few_obs=(), other_ref=()):
                 obs.append((p, A + 2, int(i2)))
             p += 1
     for s, a in enumerate(sc["anchors"]):
-        m.add_keyframe(tables[s], Ow=np.zeros(3), desc=a["desc"], octave=a["octave"], scale_factors=sf)
+        m.add_keyframe(tables[s], Ow=np.zeros(3), desc=a["desc"], octave=a["octave"], scale_factors=view_of(sc, s)[3])
+    sf = view_of(sc)[3]
     for k in (A, A + 1):
         m.add_keyframe(tables[k], Ow=np.zeros(3), desc=rng.integers(0, 256, (n_pts, 32), dtype=np.uint8), octave=np.zeros(n_pts, np.int32), scale_factors=sf)
     m.add_keyframe(tables[A + 2], Ow=np.zeros(3), desc=sc["desc2"], octave=sc["octave2"], scale_factors=sf)
@@ -231,15 +254,17 @@ def stores(ctx, sc, m, observations=None, views=True):
     st = localmap.MapPointStore(ctx, points=max(len(m.points), 1), keyframes=len(m.kfs), observations=observations or max(4 * len(m.log), 16))
     ks = mappoint.KeyFrameStore(ctx, 2)
     m.fill(st, ks)
-    f, c0 = np.array(sc["K"][:2], np.float32), np.array(sc["K"][2:], np.float32)
     new = len(m.kfs) - 1
     for s, a in enumerate(sc["anchors"]):
         st.surface_init(s, a["kpn"])
         if views:
-            st.set_view(s, localmap.KeyframeView((a["kpn"] * f + c0).astype(np.float32), sc["K"], sc["bounds"], *sc["grid"], bbs_of(a["bbs"])))
+            K, bounds, grid, _ = view_of(sc, s)
+            f, c0 = np.array(K[:2], np.float32), np.array(K[2:], np.float32)
+            st.set_view(s, localmap.KeyframeView((a["kpn"] * f + c0).astype(np.float32), K, bounds, *grid, bbs_of(a["bbs"])))
     st.surface_init(new, sc["kpn2"])
     if views:
-        st.set_view(new, localmap.KeyframeView(sc["px2"], sc["K"], sc["bounds"], *sc["grid"], bbs_of(sc["anchors"][0]["bbs"])))
+        K, bounds, grid, _ = view_of(sc)
+        st.set_view(new, localmap.KeyframeView(sc["px2"], K, bounds, *grid, bbs_of(sc["anchors"][0]["bbs"])))
     return st, ks
 
 
@@ -247,8 +272,9 @@ def initial(ctx, sc, a, i1, i2):
     """Stages 2 and 3 by the one-shot calls: (init_ok, x with the NaN rule applied, the filter's flags)."""
     from defslam_amd import nrsfm
     A = sc["anchors"][a]
-    bbs, (fx, fy) = bbs_of(A["bbs"]), sc["K"][:2]
-    kp1, kp2, isg = A["kpn"][i1], sc["kpn2"][i2], inv_sigma(sc["scale_factors"], A["octave"][i1])
+    (K1, _, _, sf), _ = _views(sc, a)
+    bbs, (fx, fy) = bbs_of(A["bbs"]), K1[:2]
+    kp1, kp2, isg = A["kpn"][i1], sc["kpn2"][i2], inv_sigma(sf, A["octave"][i1])
     init_ok, x = nrsfm.WarpInitialize(ctx, bbs, kp1, kp2, sc["lam"])
     nz = min(x.size, 2 * bbs.nptsu * bbs.nptsu)
     x[:nz][np.isnan(x[:nz])] = 0.0
@@ -256,22 +282,23 @@ def initial(ctx, sc, a, i1, i2):
     return init_ok, x, filter_flags(res, len(i1))
 
 
-def host_route(ctx, m, sc, a, i1, i2, q1, ddb, tag, min_pairs=20, max_iters=3):
+def host_route(ctx, m, sc, a, i1, i2, q1, ddb, tag, min_pairs=20, max_iters=3, radius=2.0, th_low=50):
     """The explicit-array sequence for one anchor (integration/schwarp_database_hip.h: the four one-shot calls on host-gathered arrays) on
-    the model m, which is mutated; the records into ddb."""
+    the model m, which is mutated; the records into ddb.  The gather, the filter and the fit read the anchor's camera and scale factors,
+    the search the new keyframe's camera, bounds, grid and pixel key points (view_of)."""
     from defslam_amd import nrsfm
     A, new = sc["anchors"][a], len(m.kfs) - 1
-    bbs, lam, (fx, fy) = bbs_of(A["bbs"]), sc["lam"], sc["K"][:2]
-    sf = sc["scale_factors"]
+    (K1, _, _, sf), (K2, bounds2, grid2, _) = _views(sc, a)
+    bbs, lam, (fx, fy) = bbs_of(A["bbs"]), sc["lam"], K1[:2]
     i1, i2, q1 = (np.asarray(v, np.int64) for v in (i1, i2, q1))
     P, Q = len(i1), len(q1)
     init_ok, x, filt = initial(ctx, sc, a, i1, i2)
     has = np.array(m.kfs[new].table) != -1
     has[i2[filt]] = False
-    match = (nrsfm.searchBySchwarp(ctx, bbs, x, A["kpn"][q1], A["desc"][q1], sc["K"], sc["bounds"], sc["px2"], sc["desc2"], has, 2.0, 50, sc["grid"])
+    match = (nrsfm.searchBySchwarp(ctx, bbs, x, A["kpn"][q1], A["desc"][q1], K2, bounds2, sc["px2"], sc["desc2"], has, radius, th_low, grid2)
              if Q else np.zeros(0, np.int32))
     kept, ps, qs, qp, qa = m.filter_register_seq(a, new, i1, i2, filt, q1, match)
-    out = dict(x=x, init_ok=init_ok, fitted=False, info=np.zeros(2, np.int32), costs=np.zeros(2), match=match, query_point=qp, query_added=qa,
+    out = dict(x=x, x_start=x, has=has, init_ok=init_ok, fitted=False, info=np.zeros(2, np.int32), costs=np.zeros(2), match=match, query_point=qp, query_added=qa,
                n_list=len(kept), stored=[], counts=zero_counts())
     if len(kept) >= min_pairs:
         k1 = A["kpn"][[e[0] for e in kept]]
