@@ -22,19 +22,15 @@ extern "C" {
 
 int dsh_point_store_set_reference_keyframes(dsh_mpdb* db, int n, const int32_t* ids, const int32_t* slots) {
   DSH_STORE_ENTER("dsh_point_store_set_reference_keyframes");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id"));
   if (n > 0 && !slots) return bad("slots is NULL");
   for (int i = 0; i < n; i++)
     if (slots[i] < -1 || slots[i] >= db->K) return bad("slots[" + std::to_string(i) + "] is neither -1 nor a slot of the store");
-  if (const int rc = dsh_enter(c, "dsh_point_store_set_reference_keyframes")) return rc;
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
-  const size_t m = (size_t)n, o_ids = up.take(4 * m), o_val = up.take(4 * m);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  std::memcpy(up.host<int32_t>(o_val), slots, 4 * m);
-  if (const int rc = up.send(c)) return rc;
+  const size_t m = (size_t)n, o_ids = up.copy_of(ids, 4 * m), o_val = up.copy_of(slots, 4 * m);
+  if (const int rc = up.copy(c)) return rc;
   HIPCHK(c, lm_scatter_i32_launch(db->d_ref_kf, up.dev<const int32_t>(o_ids), up.dev<const int32_t>(o_val), 0, n, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return DSH_OK;
@@ -42,24 +38,18 @@ int dsh_point_store_set_reference_keyframes(dsh_mpdb* db, int n, const int32_t* 
 
 int dsh_point_store_get_reference_keyframes(dsh_mpdb* db, int n, const int32_t* ids, int32_t* slots_out) {
   DSH_STORE_ENTER("dsh_point_store_get_reference_keyframes");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id"));
   if (n > 0 && !slots_out) return bad("slots_out is NULL");
-  if (const int rc = dsh_enter(c, "dsh_point_store_get_reference_keyframes")) return rc;
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
-  const size_t m = (size_t)n, o_ids = up.take(4 * m);
+  const size_t m = (size_t)n, o_ids = up.copy_of(ids, 4 * m);
   DownBlock down;
-  const size_t d_val = down.take(4 * m);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  if (const int rc = up.send(c)) return rc;
+  const size_t d_val = down.copy_to(slots_out, 4 * m);
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   HIPCHK(c, an_gather_i32_launch(db->d_ref_kf, up.dev<const int32_t>(o_ids), n, down.dev<int32_t>(d_val), c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(slots_out, down.host<int32_t>(d_val), 4 * m);
-  return DSH_OK;
+  return down.receive(c);
 }
 
 int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anchor_lists* out) {
@@ -76,8 +66,8 @@ int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anch
   if (out->anchor_capacity > 0 && (!out->anchor_slot || !out->anchor_count || !out->anchor_pairs)) return bad("an anchor array is NULL");
   if (out->pair_capacity > 0 && (!out->pair_idx1 || !out->pair_idx2 || !out->pair_point || !out->pair_own)) return bad("a pair array is NULL");
   if (out->query_capacity > 0 && (!out->query_idx1 || !out->query_point)) return bad("a query array is NULL");
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_keyframe_anchors");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_anchors")) return rc;
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
 
   // what the host knows of the sizes: an anchor takes a vote of an entry, a pair an entry per anchor, a query an entry of a table
   const long long N = nk.N, Amax = std::min<long long>(db->K, N);
@@ -91,6 +81,7 @@ int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anch
   const size_t d_hdr = down.take(sizeof(AnHdr)), d_slot = down.take(4 * ca), d_count = down.take(4 * ca), d_np = down.take(4 * ca),
                d_pptr = down.take(4 * (ca + 1)), d_qptr = down.take(4 * (ca + 1)), d_i1 = down.take(4 * cp), d_i2 = down.take(4 * cp),
                d_pt = down.take(4 * cp), d_own = down.take(cp), d_q1 = down.take(4 * cq), d_qp = down.take(4 * cq), d_has = down.take((size_t)N);
+  down.copy_to(d_has, out->has, (size_t)N);   // the kernel writes it whether the caller wants it or not
   if (const int rc = down.alloc(c)) return rc;
   AnBufs b;
   std::memset(&b, 0, sizeof(b));
@@ -125,9 +116,11 @@ int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anch
 
   const AnHdr h = *down.host<AnHdr>(d_hdr);
   out->n_anchors = h.n_anchors; out->n_pairs = h.n_pairs; out->n_queries = h.n_queries; out->n_no_ref = h.n_no_ref;
-  if (h.n_anchors > out->anchor_capacity || h.n_pairs > out->pair_capacity || h.n_queries > out->query_capacity)
+  if (h.n_anchors > out->anchor_capacity || h.n_pairs > out->pair_capacity || h.n_queries > out->query_capacity)   // leaves the caller's arrays
     return bad("the lists do not fit: " + std::to_string(h.n_anchors) + " anchors, " + std::to_string(h.n_pairs) + " pairs and " +
                std::to_string(h.n_queries) + " queries are needed (n_anchors, n_pairs, n_queries of out)");
+  down.hand_out();
+  // the lists: their lengths came down with them
   const size_t A = (size_t)h.n_anchors, np = (size_t)h.n_pairs, nq = (size_t)h.n_queries;
   if (A > 0) {
     std::memcpy(out->anchor_slot, down.host<int32_t>(d_slot), 4 * A);
@@ -146,7 +139,6 @@ int dsh_keyframe_anchors(dsh_mpdb* db, int32_t slot, int32_t min_pairs, dsh_anch
     std::memcpy(out->query_idx1, down.host<int32_t>(d_q1), 4 * nq);
     std::memcpy(out->query_point, down.host<int32_t>(d_qp), 4 * nq);
   }
-  if (out->has && N > 0) std::memcpy(out->has, down.host<uint8_t>(d_has), (size_t)N);
   return DSH_OK;
 }
 

@@ -1,7 +1,21 @@
 // Internal definition of the opaque dsh_ctx (shared by the translation units of libdefslam_hip.so) and the host-side plumbing every
 // C ABI module uses: error reporting (dsh_fail, HIPCHK), the device gate (dsh_enter), scratch slices (DevBuf), block layout (Arena),
 // page-locked host buffers (HostBuf), the one-copy blocks of a call (UpBlock, DownBlock), the life cycle of the device-resident
-// stores (dsh_store, DSH_STORE_ENTER, dsh_store_grow) and what the mapping calls share across files (namespace dsh).
+// stores (dsh_store, DSH_STORE_ENTER / DSH_STORE_GATE / DSH_CHECK, dsh_store_grow) and what the mapping calls share across files
+// (namespace dsh).
+//
+// How a call moves its arrays.  An array of the caller whose byte count is known before the copy is a bound slice: up.copy_of(src, bytes)
+// on the way up, down.copy_to(dst, bytes) on the way down; a null array or no bytes is an empty slice, and dev_if() hands the kernel null
+// for it.  A call whose blocks hold bound slices alone is up.copy(c), launches, down.receive(c).  Three kinds of slice stay by hand, each
+// with a one-line comment where it is filled or read:
+//   - what the host computes or converts: zeroed counters, packed records (TrkProb), widened or merged flags, in_view (int32 on the
+//     device, uint8 for the caller), fields of a result record;
+//   - an output whose length comes down with it (local_kf, the anchor lists, slots / idx, new_idx): the caller gets exactly that many
+//     entries, never the capacity that was fetched;
+//   - a call that can refuse after the download (TRK_REFUSED, lists that do not fit): fetch and synchronise by hand, check, then
+//     hand_out(), so a refused call leaves the caller's arrays untouched.
+// A slice the kernels write whether the caller asked for it or not keeps its bytes: take() it and bind it with copy_to(off, dst, bytes).
+// A DownBlock placed with at() over an array of a store ends in take_exact(): a padded last slice would read past the allocation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -198,14 +212,21 @@ struct CopyBlock : Arena {   // size: what the copy moves
   }
   template <class T> T* host(size_t off) const { return reinterpret_cast<T*>(h + off); }
   template <class T> T* dev(size_t off) const { return reinterpret_cast<T*>(d + off); }
+  // the device side of a slice whose caller's array p is optional: null for an output or an input nobody passed
+  template <class T> T* dev_if(const void* p, size_t off) const { return p ? dev<T>(off) : nullptr; }
   // slices that are plain copies of arrays of the caller (UpBlock::copy_of, DownBlock::copy_to): the block moves them itself; a null array
   // or one without bytes is an empty slice
   struct Bound { size_t off, bytes; void* p; };
   std::vector<Bound> bound;
   size_t bind(void* p, size_t bytes) {
     const size_t off = take(p ? bytes : 0);
-    if (p && bytes) bound.push_back({off, bytes, p});
+    bind_at(off, p, bytes);
     return off;
+  }
+  // the same for a slice laid out by take() / take_exact(): one that keeps its bytes when the array is null because the kernels write it
+  // in any case, or the unpadded last slice of a block that lies over an array of a store
+  void bind_at(size_t off, void* p, size_t bytes) {
+    if (p && bytes) bound.push_back({off, bytes, p});
   }
 };
 
@@ -222,6 +243,12 @@ struct UpBlock : CopyBlock {
   }
   // a slice that stage() fills from src
   size_t copy_of(const void* src, size_t bytes) { return bind(const_cast<void*>(src), bytes); }
+  // the same at `off` of a slice laid out by hand, also for a part of one (a problem's share of a batch's slice); once the block is staged
+  // the bytes are copied at once
+  void copy_of(size_t off, const void* src, size_t bytes) {
+    if (h && src && bytes) std::memcpy(h + off, src, bytes);
+    else bind_at(off, const_cast<void*>(src), bytes);
+  }
   // stage and send in one: for a block that holds bound slices alone
   int copy(dsh_ctx_base* c) {
     if (const int rc = stage(c)) return rc;
@@ -260,6 +287,7 @@ struct DownBlock : CopyBlock {
   }
   // a slice that hand_out() copies to dst after the caller's hipStreamSynchronize (null: an optional output nobody asked for)
   size_t copy_to(void* dst, size_t bytes) { return bind(dst, bytes); }
+  void copy_to(size_t off, void* dst, size_t bytes) { bind_at(off, dst, bytes); }
   void hand_out() const {
     for (const Bound& b : bound) std::memcpy(b.p, h + b.off, b.bytes);
   }
@@ -272,12 +300,26 @@ struct DownBlock : CopyBlock {
   }
 };
 
-// The first checks of every entry point on a device-resident store `db`: a store that is alive and attached.  Leaves its context in c
-// and bad(message), which refuses with DSH_ERR_ARG and "who: message".
-#define DSH_STORE_ENTER(who)                            \
-  if (!db || !db->ctx) return DSH_ERR_ARG;              \
-  [[maybe_unused]] dsh_ctx_base* c = db->ctx;           \
-  [[maybe_unused]] auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, std::string(who) + ": " + m); }
+// The first checks of every entry point on a device-resident store `db`: a store that is alive and attached.  Leaves its context in c,
+// the entry point's name (spelled here and nowhere else in its body) and two refusals with "who: message": bad(message) is DSH_ERR_ARG,
+// refuse(code, message) any other code.
+#define DSH_STORE_ENTER(who)                                                                  \
+  if (!db || !db->ctx) return DSH_ERR_ARG;                                                    \
+  [[maybe_unused]] dsh_ctx_base* c = db->ctx;                                                 \
+  [[maybe_unused]] const char* const who__ = (who);                                           \
+  [[maybe_unused]] auto refuse = [&](int code, const std::string& m) { return dsh_fail(c, code, std::string(who__) + ": " + m); }; \
+  [[maybe_unused]] auto bad = [&](const std::string& m) { return refuse(DSH_ERR_ARG, m); }
+// The device gate (dsh_enter) of that entry point, under the same name: it stays where the host-only check belongs in the order of checks.
+#define DSH_STORE_GATE() \
+  if (const int rc__ = dsh_enter(c, who__)) return rc__
+// A validator that returns what is wrong as a std::string ("": nothing) or as a const char* (null: nothing): refuse with it through bad().
+inline std::string dsh_check_text(std::string e) { return e; }
+inline std::string dsh_check_text(const char* e) { return e ? e : ""; }
+#define DSH_CHECK(expr)                               \
+  do {                                                \
+    const std::string e__ = dsh_check_text(expr);     \
+    if (!e__.empty()) return bad(e__);                \
+  } while (0)
 
 // The key point count of a frame or a keyframe: what is wrong with it, or null.
 inline const char* dsh_keypoint_count_error(long long N) { return N < 0 || N > (1 << 20) ? "N outside 0 .. 2^20" : nullptr; }

@@ -85,12 +85,11 @@ int dsh_diffdb_clear(dsh_diffdb* db) {
 int64_t dsh_diffdb_count(const dsh_diffdb* db) { return db ? (int64_t)db->count : -1; }
 
 int dsh_diffdb_append(dsh_diffdb* db, int n, const dsh_diffprop* recs, const int32_t* point_id, const int32_t* tag, const int32_t* idx2) {
-  if (!db || !db->ctx) return DSH_ERR_ARG;
-  dsh_ctx_base* c = db->ctx;
-  if (n < 0 || (n > 0 && (!recs || !point_id))) return dsh_fail(c, DSH_ERR_ARG, "dsh_diffdb_append: bad argument");
+  DSH_STORE_ENTER("dsh_diffdb_append");
+  if (n < 0 || (n > 0 && (!recs || !point_id))) return bad("bad argument");
   if (n == 0) return DSH_OK;
   (void)hipSetDevice(c->device);
-  if (ddb_reserve(db, db->count + n) != 0) return dsh_fail(c, DSH_ERR_HIP, "dsh_diffdb_append: out of device memory while growing the database");
+  if (ddb_reserve(db, db->count + n) != 0) return refuse(DSH_ERR_HIP, "out of device memory while growing the database");
   hipStream_t st = c->stream;
   std::vector<int32_t> fill;
   const std::vector<int32_t> zeros(tag ? 0 : (size_t)n, 0);   // lives until the stream synchronisation below

@@ -61,7 +61,7 @@ extern "C" {
 int dsh_track_keyframe_candidate(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* n) {
   DSH_STORE_ENTER("dsh_track_keyframe_candidate");
   if (capacity < 0) return bad("capacity < 0");
-  if (const int rc = dsh_enter(c, "dsh_track_keyframe_candidate")) return rc;
+  DSH_STORE_GATE();
   if (db->cand_N < 0) return bad("no resident keyframe candidate (dsh_track_end_frame has not run since the store was created or cleared)");
   if (capacity < db->cand_N) return bad("capacity is smaller than the keyframe candidate");
   if (db->cand_N > 0 && ids) {
@@ -74,9 +74,8 @@ int dsh_track_keyframe_candidate(dsh_mpdb* db, int32_t capacity, int32_t* ids, i
 
 int dsh_keyframe_create(dsh_mpdb* db, const dsh_keyframe_create_input* in, dsh_keyframe_create_result* out) {
   DSH_STORE_ENTER("dsh_keyframe_create");
-  const std::string ie = create_error(db, in, out);
-  if (!ie.empty()) return bad(ie);
-  if (const int rc = dsh_enter(c, "dsh_keyframe_create")) return rc;
+  DSH_CHECK(create_error(db, in, out));
+  DSH_STORE_GATE();
   dsh_kfdb* kfdb = in->kfdb;
   const dsh_mp_keyframe& kf = *in->kf;
   const size_t N = (size_t)kf.N;
@@ -88,20 +87,13 @@ int dsh_keyframe_create(dsh_mpdb* db, const dsh_keyframe_create_input* in, dsh_k
 
   // one block up; its last slice goes up as zeros and comes down as the result
   UpBlock up;
-  const size_t o_rows = up.take(32 * N), o_oct = up.take(N), o_sf = up.take(sizeof(mirror.sf)), o_T = up.take(64), o_pts = up.take(in->points ? 4 * N : 0),
-               o_kpn = up.take(in->kpn ? 8 * N : 0), o_out = up.take_exact(sizeof(KcCreateOut));
+  const size_t o_rows = up.copy_of(kf.desc, 32 * N), o_oct = up.copy_of(mirror.octave.data(), N), o_sf = up.copy_of(mirror.sf, sizeof(mirror.sf)),
+               o_T = up.copy_of(in->Tcw, 64), o_pts = up.copy_of(in->points, 4 * N), o_kpn = up.copy_of(in->kpn, 8 * N),
+               o_out = up.take_exact(sizeof(KcCreateOut));
   DownBlock down;
   const size_t d_out = down.take_exact(sizeof(KcCreateOut));
   if (const int rc = up.stage(c)) return rc;
-  if (N > 0) {
-    std::memcpy(up.host<uint8_t>(o_rows), kf.desc, 32 * N);
-    std::memcpy(up.host<int8_t>(o_oct), mirror.octave.data(), N);
-    if (in->points) std::memcpy(up.host<int32_t>(o_pts), in->points, 4 * N);
-    if (in->kpn) std::memcpy(up.host<float>(o_kpn), in->kpn, 8 * N);
-  }
-  std::memcpy(up.host<float>(o_sf), mirror.sf, sizeof(mirror.sf));
-  std::memcpy(up.host<float>(o_T), in->Tcw, 64);
-  std::memset(up.host<KcCreateOut>(o_out), 0, sizeof(KcCreateOut));
+  std::memset(up.host<KcCreateOut>(o_out), 0, sizeof(KcCreateOut));   // the result goes up as zeros
   if (const int rc = up.send(c)) return rc;
   if (const int rc = down.at(c, up.dev<KcCreateOut>(o_out))) return rc;
 
@@ -113,7 +105,7 @@ int dsh_keyframe_create(dsh_mpdb* db, const dsh_keyframe_create_input* in, dsh_k
   k.src_sf = up.dev<const float>(o_sf);
   k.Tcw = up.dev<const float>(o_T);
   k.src_points = in->points ? up.dev<const int32_t>(o_pts) : db->d_cand_ids;   // device to device: the host mirror holds no table contents
-  k.src_kpn = in->kpn ? up.dev<const float>(o_kpn) : nullptr;
+  k.src_kpn = up.dev_if<const float>(in->kpn, o_kpn);
   k.kf_slot = kfdb->d_slots + slot;
   k.row_off = (int32_t)kfdb->rows;
   k.rows = kfdb->d_rows; k.oct = kfdb->d_oct;
@@ -145,7 +137,7 @@ int dsh_keyframe_create(dsh_mpdb* db, const dsh_keyframe_create_input* in, dsh_k
   db->T += kf.N;
   const KcCreateOut& r = *down.host<KcCreateOut>(d_out);
   out->slot = slot; out->n_held = r.n_held; out->n_snapshot = r.n_snapshot;
-  std::memcpy(out->Ow, r.Ow, 12);
+  std::memcpy(out->Ow, r.Ow, 12);   // a field of the result record
   return DSH_OK;
 }
 
@@ -157,7 +149,7 @@ int dsh_keyframe_update_connections(dsh_mpdb* db, int32_t slot, int32_t th, int3
   if ((counted_kf || counted_w || ordered_kf || ordered_w) && capacity < db->K) return bad("capacity is smaller than the store's keyframe count");
   if (db->kf[slot].N > KC_MAX_KEYPOINTS) return bad("the keyframe has more than 8192 key points");
   if (db->K > KC_MAX_KEYFRAMES) return bad("the store holds more than 65535 keyframes");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_update_connections")) return rc;
+  DSH_STORE_GATE();
 
   const size_t K = (size_t)db->K;
   DownBlock down;
@@ -181,6 +173,7 @@ int dsh_keyframe_update_connections(dsh_mpdb* db, int32_t slot, int32_t th, int3
     db->kf[slot].parent = h.parent;
     db->first_conn[slot] = 0;
   }
+  // the lists: their lengths came down with them
   if (counted_kf) std::memcpy(counted_kf, down.host<int32_t>(d_ck), 4 * (size_t)h.n_counted);
   if (counted_w) std::memcpy(counted_w, down.host<int32_t>(d_cw), 4 * (size_t)h.n_counted);
   if (ordered_kf) std::memcpy(ordered_kf, down.host<int32_t>(d_ok), 4 * (size_t)h.n_connected);

@@ -63,13 +63,12 @@ int dsh_keyframe_process_new(dsh_mpdb* db, const dsh_keyframe_process_input* in,
   if (!in) return bad("in is NULL");
   if (!out) return bad("out is NULL");
   if (in->slot < 0 || in->slot >= db->K) return bad("slot outside the store");
-  const std::string ke = kfdb_error(db, in->kfdb);
-  if (!ke.empty()) return bad(ke);
+  DSH_CHECK(kfdb_error(db, in->kfdb));
   const LmKf nk = db->kf[in->slot];
   const long long cap_obs = (long long)db->obs.size() + nk.N;
   if (cap_obs > INT32_MAX || db->R + nk.N > INT32_MAX) return bad("store full");
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_keyframe_process_new");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_process_new")) return rc;
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
   std::memset(out, 0, sizeof(*out));   // a refused call leaves the caller's counts as they were
   out->first_record = db->R;
 
@@ -78,6 +77,7 @@ int dsh_keyframe_process_new(dsh_mpdb* db, const dsh_keyframe_process_input* in,
   HIPCHK(c, mpdb_reserve_log(db, db->R + nk.N));
   DownBlock down;
   const size_t d_hdr = down.take(sizeof(KiHdr)), d_added = down.take(4 * N), d_action = down.take_exact(N);
+  down.copy_to(d_action, action, N);   // the kernel writes the actions whether the caller wants them or not
   if (const int rc = down.alloc(c)) return rc;
   KiBufs b;
   if (const int rc = fill_bufs(c, b, db, in->kfdb, nk.N, cap_obs)) return rc;
@@ -89,8 +89,7 @@ int dsh_keyframe_process_new(dsh_mpdb* db, const dsh_keyframe_process_input* in,
   b.out_added = down.dev<int32_t>(d_added);
   b.out_action = down.dev<uint8_t>(d_action);
   HIPCHK(c, ki_process_new_launch(b, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (const int rc = down.receive(c)) return rc;
 
   // the host mirror follows: the records the device appended, as dsh_point_store_add_observations_indexed leaves them
   const KiHdr& h = *down.host<KiHdr>(d_hdr);
@@ -99,8 +98,7 @@ int dsh_keyframe_process_new(dsh_mpdb* db, const dsh_keyframe_process_input* in,
   db->R += h.n_appended;
   out->n_empty = h.n_empty; out->n_bad = h.n_bad; out->n_added = h.n_appended; out->n_recent = h.n_recent;
   out->n_no_good_desc = h.n_no_good_desc; out->n_no_ref = h.n_no_ref;
-  if (action && N > 0) std::memcpy(action, down.host<uint8_t>(d_action), N);
-  if (added_point && h.n_appended > 0) std::memcpy(added_point, added, 4 * (size_t)h.n_appended);
+  if (added_point && h.n_appended > 0) std::memcpy(added_point, added, 4 * (size_t)h.n_appended);   // its length came down with it
   return DSH_OK;
 }
 
@@ -113,25 +111,23 @@ int dsh_point_store_upkeep(dsh_mpdb* db, const dsh_point_upkeep_input* in, int32
   if (in->select != DSH_UPKEEP_IDS && in->select != DSH_UPKEEP_EMBEDDED) return bad("select is neither DSH_UPKEEP_IDS nor DSH_UPKEEP_EMBEDDED");
   const bool embedded = in->select == DSH_UPKEEP_EMBEDDED;
   if (!embedded) {
-    const std::string ie = mpdb_ids_error(in->n, in->ids, db->P, "point id");
-    if (!ie.empty()) return bad(ie);
+    DSH_CHECK(mpdb_ids_error(in->n, in->ids, db->P, "point id"));
   }
-  const std::string ke = kfdb_error(db, in->kfdb);
-  if (!ke.empty()) return bad(ke);
+  DSH_CHECK(kfdb_error(db, in->kfdb));
   if (db->obs.size() > (size_t)INT32_MAX) return bad("store full");
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_upkeep");
-  if (const int rc = dsh_enter(c, "dsh_point_store_upkeep")) return rc;
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
   std::memset(out, 0, sizeof(*out));   // a refused call leaves the caller's counts as they were
   const int32_t S = embedded ? db->P : in->n;
   if (S == 0) return DSH_OK;
 
   UpBlock up;
   const size_t o_ids = up.take_exact(embedded ? 0 : 4 * (size_t)S);
+  up.copy_of(o_ids, embedded ? nullptr : in->ids, 4 * (size_t)S);
   DownBlock down;
   const size_t d_hdr = down.take(sizeof(KiHdr)), d_status = down.take_exact(embedded ? 0 : 4 * (size_t)S);
-  if (const int rc = up.stage(c)) return rc;
-  if (!embedded) std::memcpy(up.host<int32_t>(o_ids), in->ids, 4 * (size_t)S);
-  if (const int rc = up.send(c)) return rc;
+  down.copy_to(d_status, embedded ? nullptr : status, 4 * (size_t)S);   // the kernel writes the status whether the caller wants it or not
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   KiBufs b;
   if (const int rc = fill_bufs(c, b, db, in->kfdb, S, (long long)db->obs.size())) return rc;
@@ -141,13 +137,11 @@ int dsh_point_store_upkeep(dsh_mpdb* db, const dsh_point_upkeep_input* in, int32
   b.hdr = b.out_hdr = down.dev<KiHdr>(d_hdr);
   b.out_status = embedded ? nullptr : down.dev<int32_t>(d_status);
   HIPCHK(c, ki_upkeep_launch(b, embedded ? 1 : 0, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (const int rc = down.receive(c)) return rc;
 
   const KiHdr& h = *down.host<KiHdr>(d_hdr);
   out->n_selected = h.n_sel - h.n_skipped_bad; out->n_no_obs = h.n_no_obs; out->n_no_good_desc = h.n_no_good_desc; out->n_no_ref = h.n_no_ref;
   out->n_bad = h.n_skipped_bad;
-  if (status && !embedded) std::memcpy(status, down.host<int32_t>(d_status), 4 * (size_t)S);
   return DSH_OK;
 }
 

@@ -43,17 +43,16 @@ int add_observations(dsh_mpdb* db, const char* who, int n, const int32_t* point_
     if (db->obs.count(mpdb_obs_key(p, s))) return bad(at + "the point already observes this keyframe");
     if (!batch.insert(mpdb_obs_key(p, s)).second) return bad(at + "repeated in the batch");
   }
-  if (const int rc = dsh_enter(c, who)) return rc;
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   HIPCHK(c, mpdb_reserve_log(db, db->R + n));
   UpBlock up;   // staged here, copied to the end of the log and of the indices beside it
-  const size_t o_rec = up.take(8 * (size_t)n), o_idx = up.take_exact(indexed ? 4 * (size_t)n : 0);
+  const size_t o_rec = up.take(8 * (size_t)n), o_idx = up.copy_of(indexed ? idx : nullptr, 4 * (size_t)n);
   if (const int rc = up.stage(c)) return rc;
-  int2* h = up.host<int2>(o_rec);
+  int2* h = up.host<int2>(o_rec);   // the records are interleaved from the two arrays
   for (int i = 0; i < n; i++) h[i] = make_int2(point_ids[i], keyframe_slots[i]);
   HIPCHK(c, hipMemcpyAsync(db->d_log + db->R, h, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   if (indexed) {
-    std::memcpy(up.host<int32_t>(o_idx), idx, 4 * (size_t)n);
     HIPCHK(c, hipMemcpyAsync(db->d_log_idx + db->R, up.host<int32_t>(o_idx), 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   } else {
     HIPCHK(c, hipMemsetAsync(db->d_log_idx + db->R, 0xff, 4 * (size_t)n, c->stream));   // -1: no index
@@ -112,7 +111,7 @@ int dsh_mpdb_destroy(dsh_mpdb* db) {
 int dsh_mpdb_clear(dsh_mpdb* db) {
   DSH_STORE_ENTER("dsh_mpdb_clear");
   if (db->d_hdr) {
-    if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_mpdb_clear: hipSetDevice failed");
+    if (hipSetDevice(c->device) != hipSuccess) return refuse(DSH_ERR_HIP, "hipSetDevice failed");
     HIPCHK(c, hipMemsetAsync(db->d_hdr, 0, sizeof(LmHdr), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -144,7 +143,7 @@ int dsh_mpdb_add_points(dsh_mpdb* db, int n, const float* xyz, const float* norm
   if (n < 0) return bad("n < 0");
   if (n > 0 && (!xyz || !normal || !max_distance || !desc)) return bad("a point array is NULL");
   if ((long long)db->P + n > INT32_MAX) return bad("store full");
-  if (const int rc = dsh_enter(c, "dsh_mpdb_add_points")) return rc;
+  DSH_STORE_GATE();
   if (first_id) *first_id = db->P;
   if (n == 0) return DSH_OK;
   HIPCHK(c, mpdb_reserve_points(db, (long long)db->P + n));
@@ -171,21 +170,15 @@ int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what
   DSH_STORE_ENTER("dsh_mpdb_update_points");
   if (what < 1 || what > (DSH_MPDB_POSITION | DSH_MPDB_NORMAL_DEPTH | DSH_MPDB_DESCRIPTOR))
     return bad("what is not a non-empty mask of DSH_MPDB_POSITION, DSH_MPDB_NORMAL_DEPTH, DSH_MPDB_DESCRIPTOR");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id"));
   const bool wp = (what & DSH_MPDB_POSITION) != 0, wn = (what & DSH_MPDB_NORMAL_DEPTH) != 0, wd = (what & DSH_MPDB_DESCRIPTOR) != 0;
   if (n > 0 && ((wp && !xyz) || (wn && (!normal || !max_distance)) || (wd && !desc))) return bad("an array that `what` selects is NULL");
-  if (const int rc = dsh_enter(c, "dsh_mpdb_update_points")) return rc;
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
-  UpBlock up;
-  const size_t m = (size_t)n, o_ids = up.take(4 * m), o_xyz = up.take(wp ? 12 * m : 0), o_nrm = up.take(wn ? 12 * m : 0), o_maxd = up.take(wn ? 4 * m : 0),
-               o_desc = up.take(wd ? 32 * m : 0);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  if (wp) std::memcpy(up.host<float>(o_xyz), xyz, 12 * m);
-  if (wn) { std::memcpy(up.host<float>(o_nrm), normal, 12 * m); std::memcpy(up.host<float>(o_maxd), max_distance, 4 * m); }
-  if (wd) std::memcpy(up.host<uint4>(o_desc), desc, 32 * m);
-  if (const int rc = up.send(c)) return rc;
+  UpBlock up;   // an array that `what` does not select is not read: an empty slice
+  const size_t m = (size_t)n, o_ids = up.copy_of(ids, 4 * m), o_xyz = up.copy_of(wp ? xyz : nullptr, 12 * m), o_nrm = up.copy_of(wn ? normal : nullptr, 12 * m),
+               o_maxd = up.copy_of(wn ? max_distance : nullptr, 4 * m), o_desc = up.copy_of(wd ? desc : nullptr, 32 * m);
+  if (const int rc = up.copy(c)) return rc;
   hipStream_t st = c->stream;
   LmWriteBufs w;
   w.ids = up.dev<const int32_t>(o_ids);
@@ -201,15 +194,13 @@ int dsh_mpdb_update_points(dsh_mpdb* db, int n, const int32_t* ids, int32_t what
 
 int dsh_mpdb_set_points_bad(dsh_mpdb* db, int n, const int32_t* ids, const uint8_t* bad_flags) {
   DSH_STORE_ENTER("dsh_mpdb_set_points_bad");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
-  if (!ie.empty()) return bad(ie);
-  if (const int rc = dsh_enter(c, "dsh_mpdb_set_points_bad")) return rc;
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id"));
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
-  const size_t m = (size_t)n, o_ids = up.take(4 * m), o_val = up.take(4 * m);
+  const size_t m = (size_t)n, o_ids = up.copy_of(ids, 4 * m), o_val = up.take(4 * m);
   if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  int32_t* v = up.host<int32_t>(o_val);
+  int32_t* v = up.host<int32_t>(o_val);   // the flags widen to int32, and a null array means all
   for (int i = 0; i < n; i++) v[i] = !bad_flags || bad_flags[i] ? 1 : 0;
   if (const int rc = up.send(c)) return rc;
   hipStream_t st = c->stream;
@@ -234,7 +225,7 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
     const std::string pe = mpdb_pair_error(db, point_ids[i], keyframe_slots[i]);
     if (!pe.empty()) return bad("pair " + std::to_string(i) + ": " + pe);
   }
-  if (const int rc = dsh_enter(c, "dsh_mpdb_erase_observations")) return rc;
+  DSH_STORE_GATE();
   // the records to blank: 2 * record is the point field of the log seen as int32 pairs
   std::vector<int32_t> idx;
   std::vector<uint64_t> keys;
@@ -249,9 +240,8 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
   if (idx.empty()) return DSH_OK;
   UpBlock up;
   const size_t o_idx = up.take_exact(4 * idx.size());
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_idx), idx.data(), up.size);
-  if (const int rc = up.send(c)) return rc;
+  up.copy_of(o_idx, idx.data(), up.size);
+  if (const int rc = up.copy(c)) return rc;
   const int32_t* didx = up.dev<const int32_t>(o_idx);
   // nObs-- of every pair that was found (MapPoint.cc:114-133), read from the records before they are blanked
   HIPCHK(c, tc_add_by_record_launch(db->d_nobs, reinterpret_cast<const int32_t*>(db->d_log), didx, -1, (int)idx.size(), c->stream));
@@ -266,13 +256,12 @@ int dsh_mpdb_erase_observations(dsh_mpdb* db, int n, const int32_t* point_ids, c
 
 int dsh_mpdb_add_keyframe(dsh_mpdb* db, int32_t N, const int32_t* points, int32_t parent, int32_t bad_flag, int32_t* slot) {
   DSH_STORE_ENTER("dsh_mpdb_add_keyframe");
-  if (const char* ne = dsh_keypoint_count_error(N)) return bad(ne);
+  DSH_CHECK(dsh_keypoint_count_error(N));
   if (N > 0 && !points) return bad("the table is NULL");
-  const std::string te = mpdb_table_error(db, N, points, "table entry ", "");
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(mpdb_table_error(db, N, points, "table entry ", ""));
   if (parent < -1 || parent >= db->K) return bad("parent is neither -1 nor a slot of the store");
   if (db->K == INT32_MAX || db->T + N > INT32_MAX) return bad("store full");
-  if (const int rc = dsh_enter(c, "dsh_mpdb_add_keyframe")) return rc;
+  DSH_STORE_GATE();
   HIPCHK(c, mpdb_reserve_keyframes(db, (long long)db->K + 1));
   HIPCHK(c, mpdb_reserve_table(db, db->T + N));
   LmKf k;
@@ -298,7 +287,7 @@ int dsh_mpdb_set_keyframe_point(dsh_mpdb* db, int32_t slot, int32_t idx, int32_t
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
   if (idx < 0 || idx >= db->kf[slot].N) return bad("index outside the keyframe's key points");
   if (point_id < -1 || point_id >= db->P) return bad("point_id is neither -1 nor a point of the store");
-  if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_point")) return rc;
+  DSH_STORE_GATE();
   return put_i32(c, db->d_table + db->kf[slot].tab_off + idx, point_id);
 }
 
@@ -306,7 +295,7 @@ int dsh_mpdb_set_keyframe_parent(dsh_mpdb* db, int32_t slot, int32_t parent) {
   DSH_STORE_ENTER("dsh_mpdb_set_keyframe_parent");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
   if (parent < -1 || parent >= db->K || parent == slot) return bad("parent is neither -1 nor another slot of the store");
-  if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_parent")) return rc;
+  DSH_STORE_GATE();
   db->kf[slot].parent = parent;
   return put_i32(c, &db->d_kf[slot].parent, parent);
 }
@@ -314,7 +303,7 @@ int dsh_mpdb_set_keyframe_parent(dsh_mpdb* db, int32_t slot, int32_t parent) {
 int dsh_mpdb_set_keyframe_bad(dsh_mpdb* db, int32_t slot, int32_t bad_flag) {
   DSH_STORE_ENTER("dsh_mpdb_set_keyframe_bad");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
-  if (const int rc = dsh_enter(c, "dsh_mpdb_set_keyframe_bad")) return rc;
+  DSH_STORE_GATE();
   db->kf[slot].bad = bad_flag ? 1 : 0;
   return put_i32(c, &db->d_kf[slot].bad, bad_flag ? 1 : 0);
 }
@@ -322,23 +311,22 @@ int dsh_mpdb_set_keyframe_bad(dsh_mpdb* db, int32_t slot, int32_t bad_flag) {
 int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8_t* frame_bad, int32_t kf_capacity, int32_t* local_kf,
                          int32_t* local_votes, int32_t* n_voted, int32_t* n_local_kf, int32_t* ref_kf, int32_t* n_local_points) {
   DSH_STORE_ENTER("dsh_local_map_update");
-  if (const char* ne = dsh_keypoint_count_error(N)) return bad(ne);
+  DSH_CHECK(dsh_keypoint_count_error(N));
   if (N > 0 && !frame_points) return bad("frame_points is NULL");
-  const std::string te = mpdb_table_error(db, N, frame_points, "frame_points[", "]");
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(mpdb_table_error(db, N, frame_points, "frame_points[", "]"));
   if ((local_kf || local_votes) && kf_capacity < db->K) return bad("kf_capacity is smaller than the store's keyframe count");
-  if (const int rc = dsh_enter(c, "dsh_local_map_update")) return rc;
+  DSH_STORE_GATE();
 
   const size_t P = (size_t)db->P, K = (size_t)db->K, nb = (P + LM_CHUNK - 1) / LM_CHUNK;
   UpBlock up;
   DownBlock down;
   const size_t o_fp = up.take_exact(4 * (size_t)N);
+  up.copy_of(o_fp, frame_points, 4 * (size_t)N);
   const size_t d_hdr = down.take(sizeof(LmHdr)), d_kf = down.take(4 * K), d_votes = down.take(4 * K), d_fbad = down.take((size_t)N);
-  if (const int rc = up.stage(c)) return rc;
-  if (N > 0) std::memcpy(up.host<int32_t>(o_fp), frame_points, 4 * (size_t)N);
+  down.copy_to(d_fbad, frame_bad, (size_t)N);   // the kernel writes the flags whether the caller wants them or not
   hipStream_t st = c->stream;
   LmBufs b;
-  if (const int rc = up.send(c)) return rc;
+  if (const int rc = up.copy(c)) return rc;
   HIPCHK(c, dsh_scratch_array(c, &b.votes, K));
   HIPCHK(c, dsh_scratch_array(c, &b.mark, K));
   HIPCHK(c, dsh_scratch_array(c, &b.flag, P));
@@ -359,12 +347,11 @@ int dsh_local_map_update(dsh_mpdb* db, int N, const int32_t* frame_points, uint8
   b.out_votes = down.dev<int32_t>(d_votes);
   b.out_frame_bad = down.dev<uint8_t>(d_fbad);
   HIPCHK(c, lm_update_launch(b, st));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(st));
+  if (const int rc = down.receive(c)) return rc;
 
   const LmHdr h = *down.host<LmHdr>(d_hdr);
   db->n_local_points = h.n_local_points;
-  if (frame_bad && N > 0) std::memcpy(frame_bad, down.host<uint8_t>(d_fbad), (size_t)N);
+  // the lists: their lengths came down with them
   if (local_kf) std::memcpy(local_kf, down.host<int32_t>(d_kf), 4 * (size_t)h.n_local_kf);
   if (local_votes) std::memcpy(local_votes, down.host<int32_t>(d_votes), 4 * (size_t)h.n_voted);
   if (n_voted) *n_voted = h.n_voted;
@@ -378,7 +365,7 @@ int dsh_local_map_points(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* 
   DSH_STORE_ENTER("dsh_local_map_points");
   if (capacity < db->n_local_points) return bad("capacity is smaller than the number of local points");
   if (db->n_local_points > 0 && !ids) return bad("ids is NULL");
-  if (const int rc = dsh_enter(c, "dsh_local_map_points")) return rc;
+  DSH_STORE_GATE();
   if (db->n_local_points > 0) {
     HIPCHK(c, hipMemcpyAsync(ids, db->d_local_ids, 4 * (size_t)db->n_local_points, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -391,14 +378,13 @@ int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, i
                          uint8_t* in_view, int32_t* level, float* uv, float* view_cos, int32_t* nmatches) {
   DSH_STORE_ENTER("dsh_local_map_search");
   if (!frame) return bad("frame is NULL");
-  const std::string fe = trk_frame_error(*frame);
-  if (!fe.empty()) return bad(fe);
+  DSH_CHECK(trk_frame_error(*frame));
   if (!(th > 0.0f) || !std::isfinite(th)) return bad("th must be a positive finite number");
   const int Q = db->n_local_points;
   if (capacity < Q) return bad("capacity is smaller than the number of local points");
   if (Q > 0 && !match) return bad("match is NULL");
   if (Q > (1 << 28)) return bad("too many local points");
-  if (const int rc = dsh_enter(c, "dsh_local_map_search")) return rc;
+  DSH_STORE_GATE();
   if (nmatches) *nmatches = 0;
   if (Q == 0) {
     // no query, but the frame's own points are still seen (Tracking.cc:1408-1425)
@@ -414,7 +400,12 @@ int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, i
   DownBlock down;
   TrkPlan pl;
   trk_plan_layout(pl, up, down, 1, (size_t)f.N, q, (size_t)f.grid_cols * f.grid_rows + 1);
-  const size_t d_ids = down.take(4 * q);
+  const size_t d_ids = down.take(4 * q);   // read by the visibility launch too, whether the caller wants the ids or not
+  down.copy_to(d_ids, local_ids, 4 * q);
+  down.copy_to(pl.d_match, match, 4 * q);
+  down.copy_to(pl.d_level, level, 4 * q);
+  down.copy_to(pl.d_uv, uv, 8 * q);
+  down.copy_to(pl.d_vcos, view_cos, 4 * q);
   if (const int rc = up.stage(c)) return rc;
   TrkProb pr;
   trk_fill_prob(pr, f, DSH_TRACK_LOCAL, th, Q);
@@ -440,16 +431,12 @@ int dsh_local_map_search(dsh_mpdb* db, const dsh_track_frame* frame, float th, i
   if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
 
-  if (trk_plan_refused(pl, down) >= 0) return bad(TRK_REFUSED);
-  std::memcpy(match, down.host<int32_t>(pl.d_match), 4 * q);
-  if (local_ids) std::memcpy(local_ids, down.host<int32_t>(d_ids), 4 * q);
-  if (in_view) {
+  if (trk_plan_refused(pl, down) >= 0) return bad(TRK_REFUSED);   // a refused search leaves the caller's arrays
+  down.hand_out();
+  if (in_view) {   // int32 on the device, uint8 for the caller
     const int32_t* iv = down.host<int32_t>(pl.d_inview);
     for (size_t i = 0; i < q; i++) in_view[i] = (uint8_t)iv[i];
   }
-  if (level) std::memcpy(level, down.host<int32_t>(pl.d_level), 4 * q);
-  if (uv) std::memcpy(uv, down.host<float>(pl.d_uv), 8 * q);
-  if (view_cos) std::memcpy(view_cos, down.host<float>(pl.d_vcos), 4 * q);
   if (nmatches) *nmatches = down.host<int32_t>(pl.d_pstat)[0];
   return DSH_OK;
 }

@@ -80,9 +80,8 @@ int dsh_kfdb_add(dsh_kfdb* db, const dsh_mp_keyframe* kf, int32_t* slot) {
   if (!kf) return bad("keyframe is NULL");
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(kf->Ow[k])) return bad("camera centre not finite");
-  const std::string ke = kfdb_keyframe_error(db, kf);
-  if (!ke.empty()) return bad(ke);
-  if (hipSetDevice(c->device) != hipSuccess) return dsh_fail(c, DSH_ERR_HIP, "dsh_kfdb_add: hipSetDevice failed");
+  DSH_CHECK(kfdb_keyframe_error(db, kf));
+  if (hipSetDevice(c->device) != hipSuccess) return refuse(DSH_ERR_HIP, "hipSetDevice failed");
   HIPCHK(c, kfdb_reserve(db, kf->N));
   dsh_kfdb::Kf h = kfdb_mirror(db, kf, kf->bad != 0);
   MpuSlot s;
@@ -206,20 +205,13 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   // one host buffer, one copy up
   UpBlock up;
   DownBlock down;
-  const size_t o_pts = up.take(sizeof(MpuPoint) * P), o_oslot = up.take(4 * (size_t)Mt), o_el = up.take(4 * Met), o_small = up.take(4 * small_order.size()),
-               o_blk = up.take(4 * blocks.size()), o_lpts = up.take(4 * (size_t)NL);
+  const size_t o_pts = up.copy_of(pts.data(), sizeof(MpuPoint) * P), o_oslot = up.copy_of(obs_kf, 4 * (size_t)Mt), o_el = up.copy_of(el_row.data(), 4 * Met),
+               o_small = up.copy_of(small_order.data(), 4 * small_order.size()), o_blk = up.copy_of(blocks.data(), 4 * blocks.size()),
+               o_lpts = up.copy_of(large_pts.data(), 4 * (size_t)NL);
   const size_t d_best = down.take(4 * (size_t)P), d_desc = down.take(32 * (size_t)P), d_nrm = down.take(12 * (size_t)P), d_dist = down.take(8 * (size_t)P);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<MpuPoint>(o_pts), pts.data(), sizeof(MpuPoint) * P);
-  if (Mt > 0) std::memcpy(up.host<int32_t>(o_oslot), obs_kf, 4 * (size_t)Mt);
-  if (Met > 0) std::memcpy(up.host<int32_t>(o_el), el_row.data(), 4 * Met);
-  if (!small_order.empty()) std::memcpy(up.host<int32_t>(o_small), small_order.data(), 4 * small_order.size());
-  if (!blocks.empty()) std::memcpy(up.host<int32_t>(o_blk), blocks.data(), 4 * blocks.size());
-  if (NL > 0) std::memcpy(up.host<int32_t>(o_lpts), large_pts.data(), 4 * (size_t)NL);
-
   hipStream_t st = c->stream;
   MpuBufs b;
-  if (const int rc = up.send(c)) return rc;
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   HIPCHK(c, dsh_scratch_array(c, &b.large_key, (size_t)P));
   if (NL > 0) HIPCHK(c, hipMemsetAsync(b.large_key, 0xFF, 4 * (size_t)P, st));
@@ -239,7 +231,7 @@ int dsh_mappoint_update(dsh_ctx* ctx, dsh_kfdb* db, int P, const float* xyz, con
   if (const int rc = down.fetch(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
 
-  // outputs: only what was asked for, only where the reference writes
+  // outputs by hand: only what was asked for, only where the reference writes, which the flags that came down decide per point
   const int32_t* obest = down.host<int32_t>(d_best);
   const float* onrm = down.host<float>(d_nrm);
   const float* odist = down.host<float>(d_dist);

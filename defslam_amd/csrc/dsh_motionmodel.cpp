@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -21,25 +20,20 @@ int dsh_track_end_frame(dsh_mpdb* db, int N, const int32_t* frame_points, const 
   DSH_STORE_ENTER("dsh_track_end_frame");
   if (N < 0 || N > TRK_MAX_KEYPOINTS) return bad("N outside 0 .. 8192");
   if (N > 0 && (!frame_points || !outlier || !octave)) return bad("frame_points, outlier or octave is NULL");
-  const std::string te = mpdb_table_error(db, N, frame_points, "frame_points[", "]");
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(mpdb_table_error(db, N, frame_points, "frame_points[", "]"));
   for (int i = 0; i < N; i++)
     if (octave[i] < 0 || octave[i] > 127) return bad("octave[" + std::to_string(i) + "] outside 0 .. 127");
-  if (const int rc = dsh_enter(c, "dsh_track_end_frame")) return rc;
+  DSH_STORE_GATE();
   HIPCHK(c, mpdb_reserve_last_frame(db, std::max(N, 1)));
 
   // up: the frame's ids, flags and octaves; down: the state after CleanMatches and the counts
   UpBlock up;
   DownBlock down;
-  const size_t n = (size_t)N, o_fp = up.take(4 * n), o_out = up.take(n), o_oct = up.take(4 * n);
+  const size_t n = (size_t)N, o_fp = up.copy_of(frame_points, 4 * n), o_out = up.copy_of(outlier, n), o_oct = up.copy_of(octave, 4 * n);
   const size_t d_cnt = down.take(16), d_pts = down.take(4 * n), d_flag = down.take(n);
-  if (const int rc = up.stage(c)) return rc;
-  if (N > 0) {
-    std::memcpy(up.host<int32_t>(o_fp), frame_points, 4 * n);
-    std::memcpy(up.host<uint8_t>(o_out), outlier, n);
-    std::memcpy(up.host<int32_t>(o_oct), octave, 4 * n);
-  }
-  if (const int rc = up.send(c)) return rc;
+  down.copy_to(d_pts, points_out, 4 * n);   // the kernel writes both whether the caller wants them or not
+  down.copy_to(d_flag, outlier_out, n);
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   MmEnd e;
   e.N = N;
@@ -55,15 +49,12 @@ int dsh_track_end_frame(dsh_mpdb* db, int N, const int32_t* frame_points, const 
   e.counts = down.dev<int32_t>(d_cnt);
   db->last_N = db->cand_N = -1;   // the list and the candidate are being overwritten: they count again once the call has succeeded
   HIPCHK(c, mm_end_frame_launch(e, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (const int rc = down.receive(c)) return rc;
 
   const int32_t* cnt = down.host<int32_t>(d_cnt);
   db->last_N = db->cand_N = N;
   db->last_kept = cnt[2];
   db->last_max_octave = cnt[3];
-  if (points_out && N > 0) std::memcpy(points_out, down.host<int32_t>(d_pts), 4 * n);
-  if (outlier_out && N > 0) std::memcpy(outlier_out, down.host<uint8_t>(d_flag), n);
   if (out) { out->cleaned = cnt[0]; out->dropped = cnt[1]; out->kept = cnt[2]; }
   return DSH_OK;
 }
@@ -71,7 +62,7 @@ int dsh_track_end_frame(dsh_mpdb* db, int N, const int32_t* frame_points, const 
 int dsh_track_last_frame(dsh_mpdb* db, int32_t capacity, int32_t* ids, int32_t* octave, int32_t* n) {
   DSH_STORE_ENTER("dsh_track_last_frame");
   if (capacity < 0) return bad("capacity < 0");
-  if (const int rc = dsh_enter(c, "dsh_track_last_frame")) return rc;
+  DSH_STORE_GATE();
   if (db->last_N < 0) return bad("no resident last-frame list (dsh_track_end_frame has not run since the store was created or cleared)");
   if (capacity < db->last_N) return bad("capacity is smaller than the last-frame list");
   const size_t bytes = 4 * (size_t)db->last_N;
@@ -93,12 +84,11 @@ int dsh_motion_model_search(dsh_mpdb* db, const dsh_track_frame* frame, float th
   const std::vector<uint8_t> empty((size_t)std::max(frame->N, 1), 0);
   dsh_track_frame f = *frame;
   f.state = empty.data();
-  const std::string fe = trk_frame_error(f);
-  if (!fe.empty()) return bad(fe);
+  DSH_CHECK(trk_frame_error(f));
   if (!(th > 0.0f) || !std::isfinite(th) || !(th_wide > 0.0f) || !std::isfinite(th_wide)) return bad("th and th_wide must be positive finite numbers");
   if (min_matches < 0) return bad("min_matches < 0");
   if (f.N > 0 && !frame_points) return bad("frame_points is NULL");
-  if (const int rc = dsh_enter(c, "dsh_motion_model_search")) return rc;
+  DSH_STORE_GATE();
   if (db->last_N < 0) return bad("no resident last-frame list (dsh_track_end_frame has not run since the store was created or cleared)");
   if (db->last_max_octave >= f.levels)
     return bad("the last-frame list holds octave " + std::to_string(db->last_max_octave) + ", which is outside 0 .. levels-1");

@@ -22,17 +22,15 @@ int run(dsh_mpdb* db, dsh_ctx_base* c, int mode, int n, const int32_t* ids, cons
   if (n == 0) return DSH_OK;
   const size_t m = (size_t)n, cap = db->obs.size();   // the sweep erases live records only, and the mirror knows how many there are
   UpBlock up;
-  const size_t o_ids = up.take(4 * m), o_slots = up.take(mode == PE_ERASE ? 4 * m : 0), o_first = up.take(mode == PE_CULL ? 4 * m : 0),
-               o_rec = up.take_exact(mode == PE_ERASE ? 8 * m : 0);
+  const size_t o_ids = up.copy_of(ids, 4 * m), o_slots = up.copy_of(mode == PE_ERASE ? slots : nullptr, 4 * m),
+               o_first = up.copy_of(mode == PE_CULL ? first_kf : nullptr, 4 * m), o_rec = up.take_exact(mode == PE_ERASE ? 8 * m : 0);
   DownBlock down;
   const size_t d_hdr = down.take(sizeof(PeHdr)), d_code = down.take(mode == PE_SET_BAD ? 0 : m);
+  down.copy_to(d_code, mode == PE_SET_BAD ? nullptr : code, m);   // the kernel writes the codes whether the caller wants them or not
   const size_t head = down.size;                      // what every call fetches; the erased list lies behind it
   const size_t d_erased = down.take_exact(8 * cap);
   if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  if (mode == PE_CULL) std::memcpy(up.host<int32_t>(o_first), first_kf, 4 * m);
   if (mode == PE_ERASE) {
-    std::memcpy(up.host<int32_t>(o_slots), slots, 4 * m);
     long long* rec = up.host<long long>(o_rec);       // 64-bit positions: a log of any length
     for (int i = 0; i < n; i++) {
       const auto it = db->obs.find(mpdb_obs_key(ids[i], slots[i]));
@@ -75,7 +73,7 @@ int run(dsh_mpdb* db, dsh_ctx_base* c, int mode, int n, const int32_t* ids, cons
   out->n_found = h.n_found; out->n_ref_moved = h.n_ref_moved; out->n_set_bad = h.n_set_bad;
   out->n_records = h.n_found + h.n_erased;
   out->n_entries = (erase_match ? h.n_found : 0) + h.n_erased;
-  if (code && mode != PE_SET_BAD) std::memcpy(code, down.host<uint8_t>(d_code), m);
+  down.hand_out();
   return DSH_OK;
 }
 
@@ -88,22 +86,20 @@ int dsh_point_store_erase_observations(dsh_mpdb* db, int n, const int32_t* point
   DSH_STORE_ENTER("dsh_point_store_erase_observations");
   if (!out) return bad("out is NULL");
   if (n > 0 && !keyframe_slots) return bad("keyframe_slots is NULL");
-  const std::string ie = mpdb_ids_error(n, point_ids, db->P, "point id", true);
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(mpdb_ids_error(n, point_ids, db->P, "point id", true));
   for (int i = 0; i < n; i++)
     if (keyframe_slots[i] < 0 || keyframe_slots[i] >= db->K) return bad("pair " + std::to_string(i) + ": keyframe slot outside the store");
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_erase_observations");
-  if (const int rc = dsh_enter(c, "dsh_point_store_erase_observations")) return rc;
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
   return run(db, c, PE_ERASE, n, point_ids, keyframe_slots, nullptr, erase_match ? 1 : 0, 0, status, out);
 }
 
 int dsh_point_store_set_bad(dsh_mpdb* db, int n, const int32_t* ids, dsh_point_erase_counts* out) {
   DSH_STORE_ENTER("dsh_point_store_set_bad");
   if (!out) return bad("out is NULL");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id", true);
-  if (!ie.empty()) return bad(ie);
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_set_bad");
-  if (const int rc = dsh_enter(c, "dsh_point_store_set_bad")) return rc;
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id", true));
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
   return run(db, c, PE_SET_BAD, n, ids, nullptr, nullptr, 0, 0, nullptr, out);
 }
 
@@ -111,33 +107,30 @@ int dsh_point_store_cull(dsh_mpdb* db, int n, const int32_t* ids, const int32_t*
                          dsh_point_erase_counts* out) {
   DSH_STORE_ENTER("dsh_point_store_cull");
   if (!out) return bad("out is NULL");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id", true);
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id", true));
   if (n > 0 && (!first_kf || !action)) return bad("first_kf or action is NULL");
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_point_store_cull");
-  if (const int rc = dsh_enter(c, "dsh_point_store_cull")) return rc;
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
   return run(db, c, PE_CULL, n, ids, nullptr, first_kf, 0, current_kf, action, out);
 }
 
 int dsh_point_store_get_observations(dsh_mpdb* db, int n, const int32_t* ids, int32_t* obs_ptr, int32_t capacity, int32_t* slots, int32_t* idx,
                                      int32_t* n_total) {
   DSH_STORE_ENTER("dsh_point_store_get_observations");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id", true);
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id", true));
   if (!obs_ptr || !n_total) return bad("obs_ptr or n_total is NULL");
   if (capacity < 0) return bad("capacity < 0");
   if (capacity > 0 && (!slots || !idx)) return bad("slots or idx is NULL");
   if (db->obs.size() > (size_t)INT32_MAX) return bad("store full");
-  if (const int rc = dsh_enter(c, "dsh_point_store_get_observations")) return rc;
+  DSH_STORE_GATE();
   *n_total = 0;
   const size_t m = (size_t)n, live = db->obs.size(), cap = std::min((size_t)capacity, live);
   UpBlock up;
   const size_t o_ids = up.take_exact(4 * m);
+  up.copy_of(o_ids, ids, 4 * m);
   DownBlock down;
-  const size_t d_hdr = down.take(sizeof(PeHdr)), d_ptr = down.take(4 * (m + 1)), d_slot = down.take(4 * cap), d_idx = down.take_exact(4 * cap);
-  if (const int rc = up.stage(c)) return rc;
-  if (n > 0) std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  if (const int rc = up.send(c)) return rc;
+  const size_t d_hdr = down.take(sizeof(PeHdr)), d_ptr = down.copy_to(obs_ptr, 4 * (m + 1)), d_slot = down.take(4 * cap), d_idx = down.take_exact(4 * cap);
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   PeObsBufs b;
   std::memset(&b, 0, sizeof(b));
@@ -150,10 +143,10 @@ int dsh_point_store_get_observations(dsh_mpdb* db, int n, const int32_t* ids, in
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int32_t total = down.host<PeHdr>(d_hdr)->total;
   *n_total = total;
-  if (total > capacity)
+  if (total > capacity)   // a refused call leaves the caller's arrays
     return bad("capacity " + std::to_string(capacity) + " is too small for the " + std::to_string(total) + " observations of the points");
-  std::memcpy(obs_ptr, down.host<int32_t>(d_ptr), 4 * (m + 1));
-  if (total > 0) {
+  down.hand_out();
+  if (total > 0) {   // the lists: their length came down with them
     std::memcpy(slots, down.host<int32_t>(d_slot), 4 * (size_t)total);
     std::memcpy(idx, down.host<int32_t>(d_idx), 4 * (size_t)total);
   }
@@ -166,15 +159,12 @@ int dsh_point_store_get_keyframe_table(dsh_mpdb* db, int32_t slot, int32_t capac
   const LmKf k = db->kf[slot];
   if (capacity < k.N) return bad("capacity " + std::to_string(capacity) + " is too small for the keyframe's " + std::to_string(k.N) + " key points");
   if (k.N > 0 && !points) return bad("points is NULL");
-  if (const int rc = dsh_enter(c, "dsh_point_store_get_keyframe_table")) return rc;
+  DSH_STORE_GATE();
   if (k.N == 0) return DSH_OK;
   DownBlock down;
-  const size_t d_tab = down.take_exact(4 * (size_t)k.N);
+  down.copy_to(down.take_exact(4 * (size_t)k.N), points, 4 * (size_t)k.N);   // an exact slice: the block lies over the store's table
   if (const int rc = down.at(c, db->d_table + k.tab_off)) return rc;
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(points, down.host<int32_t>(d_tab), 4 * (size_t)k.N);
-  return DSH_OK;
+  return down.receive(c);
 }
 
 }  // extern "C"

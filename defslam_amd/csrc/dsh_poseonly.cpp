@@ -39,7 +39,7 @@ int pose_only_run(dsh_mpdb* db, int B, dsh_pose_only_problem* problems, const ch
     n_kp += (size_t)p.N;
     n_sig += (size_t)p.levels;
   }
-  if (const int rc = dsh_enter(c, who)) return rc;
+  DSH_STORE_GATE();
   if (B == 0) return DSH_OK;
 
   // up: the poses, key points, octaves, sigma tables and ids of the whole batch; down: the flags and the result records
@@ -53,18 +53,16 @@ int pose_only_run(dsh_mpdb* db, int B, dsh_pose_only_problem* problems, const ch
   size_t kp0 = 0, sig0 = 0;
   for (int k = 0; k < B; k++) {
     const dsh_pose_only_problem& p = problems[k];
-    PoProb& r = up.host<PoProb>(o_prob)[k];
+    PoProb& r = up.host<PoProb>(o_prob)[k];   // the problem's record is packed from fields
     std::memcpy(r.Tcw, p.Tcw, sizeof r.Tcw);
     std::memcpy(r.K, p.K, sizeof r.K);
     r.N = p.N; r.levels = p.levels; r.kp0 = (int32_t)kp0; r.sig0 = (int32_t)sig0;
     const size_t n = (size_t)p.N;
-    if (n > 0) {
-      std::memcpy(up.host<float>(o_kp) + 2 * kp0, p.kp, 8 * n);
-      std::memcpy(up.host<int32_t>(o_ids) + kp0, p.frame_points, 4 * n);
-      int32_t* oct = up.host<int32_t>(o_oct) + kp0;
-      for (size_t i = 0; i < n; i++) oct[i] = p.frame_points[i] >= 0 ? p.octave[i] : 0;   // read only where a point is held
-    }
-    std::memcpy(up.host<float>(o_sig) + sig0, p.inv_level_sigma2, 4 * (size_t)p.levels);
+    up.copy_of(o_kp + 8 * kp0, p.kp, 8 * n);
+    up.copy_of(o_ids + 4 * kp0, p.frame_points, 4 * n);
+    int32_t* oct = up.host<int32_t>(o_oct) + kp0;
+    for (size_t i = 0; i < n; i++) oct[i] = p.frame_points[i] >= 0 ? p.octave[i] : 0;   // read only where a point is held
+    up.copy_of(o_sig + 4 * sig0, p.inv_level_sigma2, 4 * (size_t)p.levels);
     kp0 += n;
     sig0 += (size_t)p.levels;
   }
@@ -86,7 +84,7 @@ int pose_only_run(dsh_mpdb* db, int B, dsh_pose_only_problem* problems, const ch
   HIPCHK(c, hipStreamSynchronize(c->stream));
 
   kp0 = 0;
-  for (int k = 0; k < B; k++) {
+  for (int k = 0; k < B; k++) {   // the flags only where a point is held; the rest are fields of the problem's record
     dsh_pose_only_problem& p = problems[k];
     const PoResult& r = down.host<PoResult>(d_res)[k];
     const uint8_t* st = down.host<uint8_t>(d_state) + kp0;
@@ -112,13 +110,13 @@ int dsh_track_pose_only_batch(dsh_mpdb* db, int B, dsh_pose_only_problem* proble
   DSH_STORE_ENTER("dsh_track_pose_only_batch");
   if (B < 0 || B > PO_MAX_BATCH) return bad("B outside 0 .. 65536");
   if (B > 0 && !problems) return bad("problems is NULL");
-  return pose_only_run(db, B, problems, "dsh_track_pose_only_batch", false);
+  return pose_only_run(db, B, problems, who__, false);
 }
 
 int dsh_track_pose_only(dsh_mpdb* db, dsh_pose_only_problem* p) {
   DSH_STORE_ENTER("dsh_track_pose_only");
   if (!p) return bad("p is NULL");
-  return pose_only_run(db, 1, p, "dsh_track_pose_only", true);
+  return pose_only_run(db, 1, p, who__, true);
 }
 
 }  // extern "C"

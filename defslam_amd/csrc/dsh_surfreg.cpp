@@ -76,13 +76,11 @@ int select_clouds(dsh_mpdb* db, const dsh_keyframe_register_input* in, bool clou
   const size_t N = (size_t)in->N;
   UpBlock up;
   const bool resident = !in->surface_pts && db->surf[in->slot].has_surface;
-  const size_t o_T = up.take(64), o_surf = up.take_exact(resident ? 0 : 12 * N);
+  const size_t o_T = up.copy_of(in->Twc, 64), o_surf = up.take_exact(resident ? 0 : 12 * N);
+  up.copy_of(o_surf, resident ? nullptr : in->surface_pts, 12 * N);
   DownBlock down;
   const size_t d_cnt = down.take(sizeof(SrCounts)), d_idx = down.take(4 * N), d_a = down.take(clouds ? 12 * N : 0), d_b = down.take_exact(clouds ? 12 * N : 0);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<float>(o_T), in->Twc, 64);
-  if (N > 0 && !resident) std::memcpy(up.host<float>(o_surf), in->surface_pts, 12 * N);
-  if (const int rc = up.send(c)) return rc;
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   SrSelect k;
   k.kf = keyframe_slice(db, in->slot);
@@ -105,6 +103,7 @@ int select_clouds(dsh_mpdb* db, const dsh_keyframe_register_input* in, bool clou
   counts = *down.host<SrCounts>(d_cnt);
   const size_t n = (size_t)counts.n_pairs;
   pairs.assign(down.host<int32_t>(d_idx), down.host<int32_t>(d_idx) + n);
+  // the clouds: their length came down with them
   if (cloud_surface && n > 0) std::memcpy(cloud_surface, down.host<float>(d_a), 12 * n);
   if (cloud_map && n > 0) std::memcpy(cloud_map, down.host<float>(d_b), 12 * n);
   d = {k.cloud_surface, k.cloud_map};
@@ -122,12 +121,14 @@ int finish(dsh_ctx_base* c, int32_t N, const float* surface_dev, double s22, con
            dsh_mpdb* db) {
   DownBlock down;
   const size_t d_Ow = down.take(12), d_s = down.take_exact(12 * (size_t)N);
+  down.copy_to(d_Ow, Ow, 12);   // the kernel writes both whether the caller wants them or not
+  down.copy_to(d_s, surface_scaled, 12 * (size_t)N);
   if (const int rc = down.alloc(c)) return rc;
   SrFinish k;
   k.N = N;
   k.surface = surface_dev;
   k.s22 = s22;
-  std::memcpy(k.Tcw, Tcw, 64);
+  std::memcpy(k.Tcw, Tcw, 64);   // a kernel argument
   k.kf_slot = kfdb ? kfdb->d_slots + slot : nullptr;
   k.surface_scaled = down.dev<float>(d_s);
   k.Ow = down.dev<float>(d_Ow);
@@ -141,11 +142,7 @@ int finish(dsh_ctx_base* c, int32_t N, const float* surface_dev, double s22, con
     }
   }
   HIPCHK(c, sr_finish_launch(k, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (Ow) std::memcpy(Ow, down.host<float>(d_Ow), 12);
-  if (surface_scaled && N > 0) std::memcpy(surface_scaled, down.host<float>(d_s), 12 * (size_t)N);
-  return DSH_OK;
+  return down.receive(c);
 }
 
 }  // namespace
@@ -155,16 +152,15 @@ extern "C" {
 int dsh_keyframe_snapshot_positions(dsh_mpdb* db, int32_t slot, int32_t* n_taken) {
   DSH_STORE_ENTER("dsh_keyframe_snapshot_positions");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
-  if (db->snapped[slot]) return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_snapshot_positions: the snapshot of keyframe " + std::to_string(slot) + " has been taken already");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_snapshot_positions")) return rc;
+  if (db->snapped[slot]) return refuse(DSH_ERR_STATE, "the snapshot of keyframe " + std::to_string(slot) + " has been taken already");
+  DSH_STORE_GATE();
   DownBlock down;
   const size_t d_n = down.take_exact(4);
+  down.copy_to(d_n, n_taken, 4);   // the kernel counts whether the caller wants the count or not
   if (const int rc = down.alloc(c)) return rc;
   HIPCHK(c, sr_snapshot_launch(mpdb_state(db), keyframe_slice(db, slot), down.dev<int32_t>(d_n), c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (const int rc = down.receive(c)) return rc;
   db->snapped[slot] = 1;
-  if (n_taken) *n_taken = *down.host<int32_t>(d_n);
   return DSH_OK;
 }
 
@@ -174,7 +170,7 @@ int dsh_keyframe_get_snapshot(dsh_mpdb* db, int32_t slot, int32_t capacity, int3
   const LmKf k = db->kf[slot];
   if (capacity < k.N) return bad("capacity is smaller than the keyframe's N");
   if (k.N > 0 && (!point || !xyz)) return bad("point or xyz is NULL");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_get_snapshot")) return rc;
+  DSH_STORE_GATE();
   if (k.N == 0) return DSH_OK;
   HIPCHK(c, hipMemcpyAsync(point, db->d_snap_point + k.tab_off, 4 * (size_t)k.N, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(xyz, db->d_snap_xyz + 3 * (size_t)k.tab_off, 12 * (size_t)k.N, hipMemcpyDeviceToHost, c->stream));
@@ -188,9 +184,8 @@ int dsh_keyframe_get_snapshot(dsh_mpdb* db, int32_t slot, int32_t capacity, int3
 int dsh_keyframe_register_clouds(dsh_mpdb* db, const dsh_keyframe_register_input* in, int32_t* pair_idx, float* cloud_surface, float* cloud_map,
                                  dsh_keyframe_register_result* out) {
   DSH_STORE_ENTER("dsh_keyframe_register_clouds");
-  const std::string ie = input_error(db, in, out, false);
-  if (!ie.empty()) return bad(ie);
-  if (const int rc = dsh_enter(c, "dsh_keyframe_register_clouds")) return rc;
+  DSH_CHECK(input_error(db, in, out, false));
+  DSH_STORE_GATE();
   dsh::Clouds d;
   SrCounts counts;
   std::vector<int32_t> pairs;
@@ -203,9 +198,8 @@ int dsh_keyframe_register_clouds(dsh_mpdb* db, const dsh_keyframe_register_input
 
 int dsh_keyframe_register(dsh_mpdb* db, const dsh_keyframe_register_input* in, int32_t* pair_idx, float* surface_scaled, dsh_keyframe_register_result* out) {
   DSH_STORE_ENTER("dsh_keyframe_register");
-  const std::string ie = input_error(db, in, out, true);
-  if (!ie.empty()) return bad(ie);
-  if (const int rc = dsh_enter(c, "dsh_keyframe_register")) return rc;
+  DSH_CHECK(input_error(db, in, out, true));
+  DSH_STORE_GATE();
   dsh::Clouds d;
   SrCounts counts;
   std::vector<int32_t> pairs;
@@ -243,7 +237,7 @@ int dsh_keyframe_register(dsh_mpdb* db, const dsh_keyframe_register_input* in, i
       dsh::compose(r.sim3, in->Twc, &r.s22, r.Tcw_new);
       if (!pose_finite(r.Tcw_new) || !std::isfinite(r.s22)) {   // a degenerate alignment (scale 0): the reference would SetPose it; the stores keep finite centres
         *out = r;
-        return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_register: the registration composed a pose that is not finite; nothing was written");
+        return refuse(DSH_ERR_STATE, "the registration composed a pose that is not finite; nothing was written");
       }
       // Surface::applyScale of the surface points, KeyFrame::SetPose's centre into the keyframe store
       if (const int rc = finish(c, in->N, surface_dev, r.s22, r.Tcw_new, in->kfdb, in->slot, surface_scaled, r.Ow_new, db)) return rc;
@@ -261,9 +255,8 @@ int dsh_keyframe_set_pose(dsh_mpdb* db, const dsh_keyframe_pose_input* in, float
   if (!in->kfdb) return bad("kfdb is NULL");
   if (!in->Tcw) return bad("Tcw is NULL");
   if (!pose_finite(in->Tcw)) return bad("Tcw is not finite");
-  const std::string ke = centre_error(c, in->kfdb, in->slot);
-  if (!ke.empty()) return bad(ke);
-  if (const int rc = dsh_enter(c, "dsh_keyframe_set_pose")) return rc;
+  DSH_CHECK(centre_error(c, in->kfdb, in->slot));
+  DSH_STORE_GATE();
   return finish(c, 0, nullptr, 1.0, in->Tcw, in->kfdb, in->slot, nullptr, Ow, nullptr);
 }
 
@@ -272,9 +265,8 @@ int dsh_keyframe_get_centre(dsh_mpdb* db, const dsh_keyframe_pose_input* in, flo
   if (!in) return bad("in is NULL");
   if (!in->kfdb) return bad("kfdb is NULL");
   if (!Ow) return bad("Ow is NULL");
-  const std::string ke = centre_error(c, in->kfdb, in->slot);
-  if (!ke.empty()) return bad(ke);
-  if (const int rc = dsh_enter(c, "dsh_keyframe_get_centre")) return rc;
+  DSH_CHECK(centre_error(c, in->kfdb, in->slot));
+  DSH_STORE_GATE();
   HIPCHK(c, hipMemcpyAsync(Ow, in->kfdb->d_slots[in->slot].Ow, 12, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return DSH_OK;

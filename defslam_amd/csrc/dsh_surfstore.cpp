@@ -108,8 +108,8 @@ int dsh_keyframe_surface_init(dsh_mpdb* db, int32_t slot, int32_t N, const float
   if (N > 0 && !kpn) return bad("kpn is NULL");
   for (size_t i = 0; i < 2 * (size_t)N; i++)
     if (!std::isfinite(kpn[i])) return bad("key point " + std::to_string(i / 2) + " is not finite");
-  if (db->surf[slot].has_surface) return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_surface_init: keyframe " + std::to_string(slot) + " has a resident surface already");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_init")) return rc;
+  if (db->surf[slot].has_surface) return refuse(DSH_ERR_STATE, "keyframe " + std::to_string(slot) + " has a resident surface already");
+  DSH_STORE_GATE();
   // Surface(N): default SurfacePoints -- no normal, x3D zeros -- and numberofNormals_ = 0 (Surface.cc:31-37)
   const size_t n = (size_t)N, e = (size_t)k.tab_off;
   UpBlock up;
@@ -130,12 +130,11 @@ int dsh_keyframe_surface_init(dsh_mpdb* db, int32_t slot, int32_t N, const float
 
 int dsh_keyframe_surface_set_depth(dsh_mpdb* db, int32_t slot, const dsh_bbs* bbs, const double* ctrl) {
   DSH_STORE_ENTER("dsh_keyframe_surface_set_depth");
-  const std::string se = surface_error(db, slot);
-  if (!se.empty()) return bad(se);
+  DSH_CHECK(surface_error(db, slot));
   if (!bbs_grid_ok(bbs)) return bad("bad B-spline");
   if ((long long)bbs->nptsu * bbs->nptsv > dsh_mpdb::SURF_MAX_CTRL) return bad("more than 512 control points");
   if (!ctrl) return bad("ctrl is NULL");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_set_depth")) return rc;
+  DSH_STORE_GATE();
   const size_t Nz = (size_t)bbs->nptsu * bbs->nptsv;
   UpBlock up;
   const size_t o_ctrl = up.copy_of(ctrl, 8 * Nz);
@@ -150,12 +149,10 @@ int dsh_keyframe_surface_set_depth(dsh_mpdb* db, int32_t slot, const dsh_bbs* bb
 
 int dsh_keyframe_surface_set_points(dsh_mpdb* db, int32_t slot, int32_t n, const int32_t* idx, const float* pts) {
   DSH_STORE_ENTER("dsh_keyframe_surface_set_points");
-  const std::string se = surface_error(db, slot);
-  if (!se.empty()) return bad(se);
-  const std::string ie = mpdb_ids_error(n, idx, db->kf[slot].N, "idx");
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(surface_error(db, slot));
+  DSH_CHECK(mpdb_ids_error(n, idx, db->kf[slot].N, "idx"));
   if (n > 0 && !pts) return bad("pts is NULL");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_set_points")) return rc;
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
   const size_t o_idx = up.copy_of(idx, 4 * (size_t)n), o_pts = up.copy_of(pts, 12 * (size_t)n);
@@ -167,10 +164,9 @@ int dsh_keyframe_surface_set_points(dsh_mpdb* db, int32_t slot, int32_t n, const
 
 int dsh_keyframe_surface_set_normals(dsh_mpdb* db, int32_t n, const int32_t* slot, const int32_t* idx, const float* normals, int32_t* n_normals_out) {
   DSH_STORE_ENTER("dsh_keyframe_surface_set_normals");
-  const std::string te = targets_error(db, n, slot, idx);
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(targets_error(db, n, slot, idx));
   if (n > 0 && !normals) return bad("normals is NULL");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_set_normals")) return rc;
+  DSH_STORE_GATE();
   UpBlock up;
   Targets tg;
   tg.layout(up, n);
@@ -188,15 +184,14 @@ int dsh_keyframe_surface_take_normals(dsh_mpdb* db, const dsh_surface_take_input
   if (!in) return bad("in is NULL");
   const dsh_diffdb* ddb = in->ddb;
   const int32_t n = in->n, *sel = in->sel, *slot = in->slot, *idx = in->idx;
-  const std::string te = targets_error(db, n, slot, idx);
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(targets_error(db, n, slot, idx));
   if (!ddb) return bad("ddb is NULL");
   if (std::find(c->stores.begin(), c->stores.end(), static_cast<const dsh_store*>(ddb)) == c->stores.end())
     return bad("the database belongs to another context or was detached");
   if (n > 0 && !sel) return bad("sel is NULL");
   for (int j = 0; j < n; j++)
     if (sel[j] >= ddb->last_P || -1 - (long long)sel[j] >= ddb->last_R) return bad("sel[" + std::to_string(j) + "] is outside the last normal solve of the database");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_take_normals")) return rc;
+  DSH_STORE_GATE();
   UpBlock up;
   Targets tg;
   tg.layout(up, n);
@@ -212,10 +207,9 @@ int dsh_keyframe_surface_take_normals(dsh_mpdb* db, const dsh_surface_take_input
 
 int dsh_keyframe_surface_gather(dsh_mpdb* db, int32_t n, const int32_t* slot, const int32_t* idx, float* normal_xy, uint8_t* has, float* uv) {
   DSH_STORE_ENTER("dsh_keyframe_surface_gather");
-  const std::string te = targets_error(db, n, slot, idx);
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(targets_error(db, n, slot, idx));
   if (n > 0 && (!normal_xy || !has || !uv)) return bad("normal_xy, has or uv is NULL");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_gather")) return rc;
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
   Targets tg;
@@ -233,11 +227,10 @@ int dsh_keyframe_surface_gather(dsh_mpdb* db, int32_t n, const int32_t* slot, co
 int dsh_keyframe_surface_get(dsh_mpdb* db, int32_t slot, int32_t capacity, float* normals, uint8_t* has_normal, float* pts, float* kpn, double* ctrl,
                              dsh_keyframe_surface_info* info) {
   DSH_STORE_ENTER("dsh_keyframe_surface_get");
-  const std::string se = surface_error(db, slot);
-  if (!se.empty()) return bad(se);
+  DSH_CHECK(surface_error(db, slot));
   const LmKf k = db->kf[slot];
   if (capacity < k.N) return bad("capacity is smaller than the keyframe's N");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_get")) return rc;
+  DSH_STORE_GATE();
   const dsh_mpdb::SurfKf& sk = db->surf[slot];
   const size_t n = (size_t)k.N, e = (size_t)k.tab_off, Nz = sk.has_depth ? (size_t)sk.grid.nptsu * sk.grid.nptsv : 0;
   // one block down through the page-locked buffer: the arrays asked for are gathered into it device to device
@@ -273,14 +266,13 @@ int dsh_keyframe_sfn(dsh_mpdb* db, const dsh_keyframe_sfn_input* in, double* ctr
   if (!in) return bad("in is NULL");
   if (!out) return bad("out is NULL");
   if (dsh_base(in->ctx) != c) return bad("in->ctx is not the context of the store");
-  const std::string se = surface_error(db, in->slot);
-  if (!se.empty()) return bad(se);
+  DSH_CHECK(surface_error(db, in->slot));
   const LmKf k = db->kf[in->slot];
   if (k.N > SS_MAX_KEYPOINTS) return bad("the keyframe has more than 8192 key points");
   if (!bbs_grid_ok(in->bbs)) return bad("bad B-spline");
   const int Nc = in->bbs->nptsu * in->bbs->nptsv;
   if (Nc > dsh_mpdb::SURF_MAX_CTRL) return bad("more than 512 control points (one-workgroup solve)");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_sfn")) return rc;
+  DSH_STORE_GATE();
 
   // the selection: nothing goes up, the counts come down.  LIFETIME: the sites and the widened key points are slices of the context's
   // scratch, which only grows within a call and is reset by dsh_enter alone; the stages below take further slices and never enter.
@@ -332,14 +324,13 @@ int dsh_keyframe_sfn(dsh_mpdb* db, const dsh_keyframe_sfn_input* in, double* ctr
 
 int dsh_keyframe_surface_vertices(dsh_mpdb* db, int32_t slot, const float* Twc, int32_t xs, int32_t ys, double* nodes_xyz) {
   DSH_STORE_ENTER("dsh_keyframe_surface_vertices");
-  const std::string se = surface_error(db, slot);
-  if (!se.empty()) return bad(se);
+  DSH_CHECK(surface_error(db, slot));
   if (!Twc || !nodes_xyz) return bad("Twc or nodes_xyz is NULL");
   if (xs < 2 || ys < 2) return bad("xs and ys must be at least 2");
   if ((long long)xs * ys > (1 << 24)) return bad("more than 2^24 vertices");
   if (!db->surf[slot].has_depth)
-    return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_surface_vertices: keyframe " + std::to_string(slot) + " has no resident depth spline");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_surface_vertices")) return rc;
+    return refuse(DSH_ERR_STATE, "keyframe " + std::to_string(slot) + " has no resident depth spline");
+  DSH_STORE_GATE();
   dsh_surface_grid g;
   g.ctx = nullptr; g.bbs = &db->surf[slot].grid; g.depth_ctrl = nullptr; g.Twc = Twc; g.xs = xs; g.ys = ys;
   return dsh::surface_vertices_run(c, &g, depth_of(db, slot), nodes_xyz);

@@ -57,12 +57,11 @@ int surface_vertices_run(dsh_ctx_base* c, const dsh_surface_grid* grid, const do
   const dsh_bbs* b = grid->bbs;
   const size_t n = (size_t)grid->xs * grid->ys, nctrl = (size_t)b->nptsu * b->nptsv;
   UpBlock up;
-  const size_t o_T = up.take(64), o_ctrl = up.take(ctrl_dev ? 0 : 8 * nctrl), o_u = up.take(8 * n), o_v = up.take(8 * n);
+  const size_t o_T = up.copy_of(grid->Twc, 64), o_ctrl = up.copy_of(ctrl_dev ? nullptr : grid->depth_ctrl, 8 * nctrl), o_u = up.take(8 * n),
+               o_v = up.take(8 * n);
   DownBlock down;
-  const size_t d_xyz = down.take_exact(24 * n);
+  const size_t d_xyz = down.copy_to(nodes_xyz, 24 * n);
   if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<float>(o_T), grid->Twc, 64);
-  if (!ctrl_dev) std::memcpy(up.host<double>(o_ctrl), grid->depth_ctrl, 8 * nctrl);
   double *u = up.host<double>(o_u), *v = up.host<double>(o_v);
   const unsigned int xs = (unsigned)grid->xs, ys = (unsigned)grid->ys;
   const double t = 0.03;
@@ -80,10 +79,7 @@ int surface_vertices_run(dsh_ctx_base* c, const dsh_surface_grid* grid, const do
                                   up.dev<const double>(o_v), (int)n, 0, 0, d_val, nullptr, c->stream));
   HIPCHK(c, ts_vertices_launch(up.dev<const double>(o_u), up.dev<const double>(o_v), d_val, up.dev<const float>(o_T), (int)n, down.dev<double>(d_xyz),
                                c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(nodes_xyz, down.host<double>(d_xyz), 24 * n);
-  return DSH_OK;
+  return down.receive(c);
 }
 }  // namespace dsh
 
@@ -106,20 +102,19 @@ int dsh_surface_vertices(const dsh_surface_grid* grid, double* nodes_xyz) {
 
 int dsh_need_new_template(dsh_mpdb* db, int32_t slot, const dsh_kf_keypoints* kf, int32_t* n_candidates, uint8_t* candidate) {
   DSH_STORE_ENTER("dsh_need_new_template");
-  const std::string ke = keypoints_error(db, slot, kf);
-  if (!ke.empty()) return bad(ke);
+  DSH_CHECK(keypoints_error(db, slot, kf));
   if (!n_candidates) return bad("n_candidates is NULL");
-  if (const int rc = dsh_enter(c, "dsh_need_new_template")) return rc;
+  DSH_STORE_GATE();
   *n_candidates = 0;
   const size_t N = (size_t)kf->N;
   if (N == 0) return DSH_OK;
   UpBlock up;
-  const size_t o_cnt = up.take(sizeof(TsCounts)), o_kp = up.take(8 * N);
+  const size_t o_cnt = up.take(sizeof(TsCounts)), o_kp = up.copy_of(kf->kp, 8 * N);
   DownBlock down;
   const size_t d_cnt = down.take(sizeof(TsCounts)), d_cand = down.take_exact(N);
+  down.copy_to(d_cand, candidate, N);   // the kernel writes the flags whether the caller wants them or not
   if (const int rc = up.stage(c)) return rc;
-  std::memset(up.host<TsCounts>(o_cnt), 0, sizeof(TsCounts));
-  std::memcpy(up.host<float>(o_kp), kf->kp, 8 * N);
+  std::memset(up.host<TsCounts>(o_cnt), 0, sizeof(TsCounts));   // the counters go up as zeros
   if (const int rc = up.send(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   TsSwitch k;
@@ -131,18 +126,15 @@ int dsh_need_new_template(dsh_mpdb* db, int32_t slot, const dsh_kf_keypoints* kf
   HIPCHK(c, dsh_scratch_array(c, &k.block_new, (N + TS_BLOCK - 1) / TS_BLOCK));
   HIPCHK(c, hipMemcpyAsync(k.counts, up.dev<const TsCounts>(o_cnt), sizeof(TsCounts), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, ts_classify_launch(mpdb_state(db), k, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (const int rc = down.receive(c)) return rc;
   *n_candidates = down.host<TsCounts>(d_cnt)->c.n_new;
-  if (candidate) std::memcpy(candidate, down.host<uint8_t>(d_cand), N);
   return DSH_OK;
 }
 
 int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32_t* new_idx, dsh_template_switch_counts* out) {
   DSH_STORE_ENTER("dsh_template_switch");
   if (!in) return bad("in is NULL");
-  const std::string ke = keypoints_error(db, in->slot, in->kf);
-  if (!ke.empty()) return bad(ke);
+  DSH_CHECK(keypoints_error(db, in->slot, in->kf));
   const dsh_kf_keypoints& kf = *in->kf;
   const dsh_kfdb* kfdb = in->kfdb;
   if (!kfdb) return bad("kfdb is NULL");
@@ -158,8 +150,8 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   if (!out) return bad("out is NULL");
   if ((long long)db->P + kf.N > INT32_MAX) return bad("store full");
   const dsh::TemplateHost* t = dsh_facet_template(c);
-  if (!t) return dsh_fail(c, DSH_ERR_STATE, "dsh_template_switch: needs a template built from facets");
-  if (const int rc = dsh_enter(c, "dsh_template_switch")) return rc;
+  if (!t) return refuse(DSH_ERR_STATE, "needs a template built from facets");
+  DSH_STORE_GATE();
 
   // room for a new point per key point: how many are empty is known on the device only
   const size_t N = (size_t)kf.N;
@@ -168,26 +160,17 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
 
   // up: the counts (zero), Twc, the key points, the surface points, the octaves and scale factors, the template
   UpBlock up;
-  const size_t o_cnt = up.take(sizeof(TsCounts)), o_T = up.take(64), o_kp = up.take(8 * N), o_surf = up.take(resident ? 0 : 12 * N), o_oct = up.take(N),
-               o_sf = up.take(4 * MPU_MAX_LEVELS), o_xyz0 = up.take(24 * (size_t)t->n), o_fac = up.take(12 * (size_t)t->F),
-               o_nfp = up.take(4 * (size_t)(t->n + 1)), o_nfi = up.take(4 * t->nf_idx.size());
+  const size_t o_cnt = up.take(sizeof(TsCounts)), o_T = up.copy_of(in->Twc, 64), o_kp = up.copy_of(kf.kp, 8 * N),
+               o_surf = up.copy_of(resident ? nullptr : in->surface_pts, 12 * N), o_oct = up.copy_of(hk.octave.data(), N),
+               o_sf = up.copy_of(hk.sf, 4 * MPU_MAX_LEVELS), o_xyz0 = up.copy_of(t->xyz0.data(), 24 * (size_t)t->n),
+               o_fac = up.copy_of(t->facets.data(), 12 * (size_t)t->F), o_nfp = up.copy_of(t->nf_ptr.data(), 4 * (size_t)(t->n + 1)),
+               o_nfi = up.copy_of(t->nf_idx.data(), 4 * t->nf_idx.size());
   DownBlock down;   // the counts start as a copy of the uploaded zeros
   const size_t d_cnt = down.take(sizeof(TsCounts)), d_idx = down.take_exact(4 * N);
   if (const int rc = up.stage(c)) return rc;
-  TsCounts* hc = up.host<TsCounts>(o_cnt);
+  TsCounts* hc = up.host<TsCounts>(o_cnt);   // the counters go up as zeros, the largest node as none
   std::memset(hc, 0, sizeof(TsCounts));
   hc->max_node = -1;
-  std::memcpy(up.host<float>(o_T), in->Twc, 64);
-  if (N > 0) {
-    std::memcpy(up.host<float>(o_kp), kf.kp, 8 * N);
-    if (!resident) std::memcpy(up.host<float>(o_surf), in->surface_pts, 12 * N);
-    std::memcpy(up.host<int8_t>(o_oct), hk.octave.data(), N);
-  }
-  std::memcpy(up.host<float>(o_sf), hk.sf, 4 * MPU_MAX_LEVELS);
-  std::memcpy(up.host<double>(o_xyz0), t->xyz0.data(), 24 * (size_t)t->n);
-  std::memcpy(up.host<int32_t>(o_fac), t->facets.data(), 12 * (size_t)t->F);
-  std::memcpy(up.host<int32_t>(o_nfp), t->nf_ptr.data(), 4 * (size_t)(t->n + 1));
-  if (!t->nf_idx.empty()) std::memcpy(up.host<int32_t>(o_nfi), t->nf_idx.data(), 4 * t->nf_idx.size());
   if (const int rc = up.send(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   hipStream_t st = c->stream;
@@ -232,59 +215,42 @@ int dsh_template_switch(dsh_mpdb* db, const dsh_template_switch_input* in, int32
   *out = r.c;
   out->first_id = first;
   out->n_points = db->P;
-  if (new_idx && n_new > 0) std::memcpy(new_idx, down.host<int32_t>(d_idx), 4 * (size_t)n_new);
+  if (new_idx && n_new > 0) std::memcpy(new_idx, down.host<int32_t>(d_idx), 4 * (size_t)n_new);   // its length came down with it
   return DSH_OK;
 }
 
 int dsh_point_store_get_points(dsh_mpdb* db, int n, const int32_t* ids, float* xyz, float* normal, float* max_distance, uint8_t* desc, uint8_t* bad_flags) {
   DSH_STORE_ENTER("dsh_point_store_get_points");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
-  if (!ie.empty()) return bad(ie);
-  if (const int rc = dsh_enter(c, "dsh_point_store_get_points")) return rc;
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id"));
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
-  const size_t m = (size_t)n, o_ids = up.take(4 * m);
+  const size_t m = (size_t)n, o_ids = up.copy_of(ids, 4 * m);
   DownBlock down;
-  const size_t d_xyz = down.take(xyz ? 12 * m : 0), d_nrm = down.take(normal ? 12 * m : 0), d_maxd = down.take(max_distance ? 4 * m : 0),
-               d_desc = down.take(desc ? 32 * m : 0), d_bad = down.take(bad_flags ? m : 0);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  if (const int rc = up.send(c)) return rc;
+  const size_t d_xyz = down.copy_to(xyz, 12 * m), d_nrm = down.copy_to(normal, 12 * m), d_maxd = down.copy_to(max_distance, 4 * m),
+               d_desc = down.copy_to(desc, 32 * m), d_bad = down.copy_to(bad_flags, m);
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
-  HIPCHK(c, ts_get_points_launch(mpdb_state(db), db->d_nrm, db->d_maxd, db->d_desc, up.dev<const int32_t>(o_ids), n, xyz ? down.dev<float>(d_xyz) : nullptr,
-                                 normal ? down.dev<float>(d_nrm) : nullptr, max_distance ? down.dev<float>(d_maxd) : nullptr,
-                                 desc ? down.dev<uint4>(d_desc) : nullptr, bad_flags ? down.dev<uint8_t>(d_bad) : nullptr, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (xyz) std::memcpy(xyz, down.host<float>(d_xyz), 12 * m);
-  if (normal) std::memcpy(normal, down.host<float>(d_nrm), 12 * m);
-  if (max_distance) std::memcpy(max_distance, down.host<float>(d_maxd), 4 * m);
-  if (desc) std::memcpy(desc, down.host<uint8_t>(d_desc), 32 * m);
-  if (bad_flags) std::memcpy(bad_flags, down.host<uint8_t>(d_bad), m);
-  return DSH_OK;
+  HIPCHK(c, ts_get_points_launch(mpdb_state(db), db->d_nrm, db->d_maxd, db->d_desc, up.dev<const int32_t>(o_ids), n, down.dev_if<float>(xyz, d_xyz),
+                                 down.dev_if<float>(normal, d_nrm), down.dev_if<float>(max_distance, d_maxd), down.dev_if<uint4>(desc, d_desc),
+                                 down.dev_if<uint8_t>(bad_flags, d_bad), c->stream));
+  return down.receive(c);
 }
 
 int dsh_point_store_get_embedding(dsh_mpdb* db, int n, const int32_t* ids, int32_t* nodes, double* bary) {
   DSH_STORE_ENTER("dsh_point_store_get_embedding");
-  const std::string ie = mpdb_ids_error(n, ids, db->P, "point id");
-  if (!ie.empty()) return bad(ie);
-  if (const int rc = dsh_enter(c, "dsh_point_store_get_embedding")) return rc;
+  DSH_CHECK(mpdb_ids_error(n, ids, db->P, "point id"));
+  DSH_STORE_GATE();
   if (n == 0) return DSH_OK;
   UpBlock up;
-  const size_t m = (size_t)n, o_ids = up.take(4 * m);
+  const size_t m = (size_t)n, o_ids = up.copy_of(ids, 4 * m);
   DownBlock down;
-  const size_t d_nodes = down.take(nodes ? 12 * m : 0), d_bary = down.take(bary ? 24 * m : 0);
-  if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), ids, 4 * m);
-  if (const int rc = up.send(c)) return rc;
+  const size_t d_nodes = down.copy_to(nodes, 12 * m), d_bary = down.copy_to(bary, 24 * m);
+  if (const int rc = up.copy(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
-  HIPCHK(c, ts_get_embedding_launch(mpdb_state(db), up.dev<const int32_t>(o_ids), n, nodes ? down.dev<int32_t>(d_nodes) : nullptr,
-                                    bary ? down.dev<double>(d_bary) : nullptr, c->stream));
-  if (const int rc = down.fetch(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (nodes) std::memcpy(nodes, down.host<int32_t>(d_nodes), 12 * m);
-  if (bary) std::memcpy(bary, down.host<double>(d_bary), 24 * m);
-  return DSH_OK;
+  HIPCHK(c, ts_get_embedding_launch(mpdb_state(db), up.dev<const int32_t>(o_ids), n, down.dev_if<int32_t>(nodes, d_nodes), down.dev_if<double>(bary, d_bary),
+                                    c->stream));
+  return down.receive(c);
 }
 
 }  // extern "C"

@@ -65,10 +65,10 @@ void trk_plan_pack_frame(const TrkPlan& pl, UpBlock& up, int p, const TrkProb& P
   up.host<TrkProb>(pl.o_prob)[p] = P;
   if (f.N <= 0) return;
   const size_t N = (size_t)f.N, at = (size_t)P.kp_off;
-  std::memcpy(up.host<float2>(pl.o_kp) + at, f.kp, 8 * N);
-  int32_t* km = up.host<int32_t>(pl.o_km) + at;
+  up.copy_of(pl.o_kp + 8 * at, f.kp, 8 * N);
+  int32_t* km = up.host<int32_t>(pl.o_km) + at;   // octave and state share a word
   for (size_t j = 0; j < N; j++) km[j] = f.octave[j] | ((int32_t)f.state[j] << 8);
-  std::memcpy(up.host<uint4>(pl.o_kd) + 2 * at, f.desc, 32 * N);
+  up.copy_of(pl.o_kd + 32 * at, f.desc, 32 * N);
 }
 
 int trk_plan_device(dsh_ctx_base* c, const TrkPlan& pl, UpBlock& up, DownBlock& down, TrkBufs& b) {
@@ -112,9 +112,8 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   long long Nt = 0, Qt = 0, Ct = 0;
   for (int p = 0; p < B; p++) {
     dsh_track_problem& pr = problems[p];
-    const std::string fe = trk_frame_error(pr.frame);
     auto bad = [&](const std::string& m) { return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(p) + ": " + m); };
-    if (!fe.empty()) return bad(fe);
+    DSH_CHECK(trk_frame_error(pr.frame));
     if (pr.mode != DSH_TRACK_FRAME && pr.mode != DSH_TRACK_LOCAL) return bad("mode is neither DSH_TRACK_FRAME nor DSH_TRACK_LOCAL");
     if (!(pr.th > 0.0f) || !std::isfinite(pr.th)) return bad("th must be a positive finite number");
     if (pr.Q < 0) return bad("Q < 0");
@@ -151,20 +150,23 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
     trk_fill_prob(P, f, pr.mode, pr.th, pr.Q);
     P.kp_off = (int32_t)kp_off; P.q_off = (int32_t)q_off; P.cell_off = (int32_t)cell_off;
     trk_plan_pack_frame(pl, up, p, P, f);
-    if (pr.Q > 0) {
-      int32_t* qpid = up.host<int32_t>(o_qpid) + q_off;
-      int32_t* qmeta = up.host<int32_t>(o_qmeta) + q_off;
-      for (int q = 0; q < pr.Q; q++) {
-        qpid[q] = p;
-        qmeta[q] = pr.mode == DSH_TRACK_FRAME ? pr.octave[q] : (pr.skip && pr.skip[q] ? 1 : 0);
-      }
-      std::memcpy(up.host<float>(o_qxyz) + 3 * q_off, pr.xyz, 12 * (size_t)pr.Q);
-      if (pr.mode == DSH_TRACK_LOCAL) {
-        std::memcpy(up.host<float>(o_qnrm) + 3 * q_off, pr.normal, 12 * (size_t)pr.Q);
-        std::memcpy(up.host<float>(o_qmaxd) + q_off, pr.max_distance, 4 * (size_t)pr.Q);
-      }
-      std::memcpy(up.host<uint4>(o_qdesc) + 2 * q_off, pr.desc, 32 * (size_t)pr.Q);
+    const size_t Q = (size_t)pr.Q, q0 = (size_t)q_off;
+    const bool local = pr.mode == DSH_TRACK_LOCAL;
+    int32_t* qpid = up.host<int32_t>(o_qpid) + q_off;   // the problem of each query, and its octave or its skip flag
+    int32_t* qmeta = up.host<int32_t>(o_qmeta) + q_off;
+    for (int q = 0; q < pr.Q; q++) {
+      qpid[q] = p;
+      qmeta[q] = local ? (pr.skip && pr.skip[q] ? 1 : 0) : pr.octave[q];
     }
+    up.copy_of(o_qxyz + 12 * q0, pr.xyz, 12 * Q);
+    up.copy_of(o_qnrm + 12 * q0, local ? pr.normal : nullptr, 12 * Q);
+    up.copy_of(o_qmaxd + 4 * q0, local ? pr.max_distance : nullptr, 4 * Q);
+    up.copy_of(o_qdesc + 32 * q0, pr.desc, 32 * Q);
+    // down: the local map's extras only for a local search
+    down.copy_to(pl.d_match + 4 * q0, pr.match, 4 * Q);
+    down.copy_to(pl.d_level + 4 * q0, local ? pr.level : nullptr, 4 * Q);
+    down.copy_to(pl.d_uv + 8 * q0, local ? pr.uv : nullptr, 8 * Q);
+    down.copy_to(pl.d_vcos + 4 * q0, local ? pr.view_cos : nullptr, 4 * Q);
     kp_off += f.N;
     q_off += pr.Q;
     cell_off += (long long)f.grid_cols * f.grid_rows + 1;
@@ -184,22 +186,16 @@ int dsh_search_by_projection_batch(dsh_ctx* ctx, int B, dsh_track_problem* probl
   HIPCHK(c, hipStreamSynchronize(st));
 
   const int refused = trk_plan_refused(pl, down);
-  if (refused >= 0) return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(refused) + ": " TRK_REFUSED);
+  if (refused >= 0)   // a refused batch leaves the callers' arrays
+    return dsh_fail(c, DSH_ERR_ARG, "dsh_search_by_projection: problem " + std::to_string(refused) + ": " TRK_REFUSED);
+  down.hand_out();
   const int32_t* pstat = down.host<int32_t>(pl.d_pstat);
   q_off = 0;
   for (int p = 0; p < B; p++) {
     dsh_track_problem& pr = problems[p];
-    const size_t Q = (size_t)pr.Q;
-    if (Q > 0) {
-      std::memcpy(pr.match, down.host<int32_t>(pl.d_match) + q_off, 4 * Q);
-      if (pr.mode == DSH_TRACK_LOCAL) {
-        const int32_t* iv = down.host<int32_t>(pl.d_inview) + q_off;
-        if (pr.in_view)
-          for (size_t q = 0; q < Q; q++) pr.in_view[q] = (uint8_t)iv[q];
-        if (pr.level) std::memcpy(pr.level, down.host<int32_t>(pl.d_level) + q_off, 4 * Q);
-        if (pr.uv) std::memcpy(pr.uv, down.host<float>(pl.d_uv) + 2 * q_off, 8 * Q);
-        if (pr.view_cos) std::memcpy(pr.view_cos, down.host<float>(pl.d_vcos) + q_off, 4 * Q);
-      }
+    if (pr.mode == DSH_TRACK_LOCAL && pr.in_view) {   // int32 on the device, uint8 for the caller
+      const int32_t* iv = down.host<int32_t>(pl.d_inview) + q_off;
+      for (int q = 0; q < pr.Q; q++) pr.in_view[q] = (uint8_t)iv[q];
     }
     pr.nmatches = pstat[4 * p];
     pr.rescans = pstat[4 * p + 1];

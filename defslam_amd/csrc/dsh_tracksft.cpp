@@ -35,31 +35,27 @@ int select_rows(dsh_mpdb* db, const dsh_track_sft_frame* fp, bool solve, const c
   if (f.N > 0 && (!f.kp || !f.octave || !f.frame_points || !f.outlier)) return bad("kp, octave, frame_points or outlier is NULL");
   if (solve && (!f.Tcw || !f.xyz)) return bad("Tcw or xyz is NULL");
   if (solve && (f.max_iters < 0 || f.max_iters > DSH_MAX_ITERS)) return bad("max_iters outside 0 .. 64");
-  const std::string te = mpdb_table_error(db, f.N, f.frame_points, "frame_points[", "]");
-  if (!te.empty()) return bad(te);
+  DSH_CHECK(mpdb_table_error(db, f.N, f.frame_points, "frame_points[", "]"));
   for (int i = 0; i < f.N; i++)
     if (f.frame_points[i] >= 0 && (f.octave[i] < 0 || f.octave[i] >= f.levels)) return bad("octave[" + std::to_string(i) + "] outside 0 .. levels-1");
   const dsh_ctx* x = static_cast<const dsh_ctx*>(c);
-  if (!x->tmpl.valid) return dsh_fail(c, DSH_ERR_STATE, std::string(who) + ": no template");
+  if (!x->tmpl.valid) return refuse(DSH_ERR_STATE, "no template");
   if (db->largest_node() >= x->tmpl.n)
     return bad("a stored node index (" + std::to_string(db->largest_node()) + ") is >= the " + std::to_string(x->tmpl.n) + " nodes of the template");
-  if (const int rc = dsh_enter(c, who)) return rc;
+  DSH_STORE_GATE();
   t = TfTable{};
   if (f.N == 0) return DSH_OK;
 
   // up: the frame's ids, flags, octaves, key points and the sigma table; down: M and Points_Obs, then the table with room for N rows
   UpBlock up;
   const size_t n = (size_t)f.N;
-  const size_t o_ids = up.take(4 * n), o_out = up.take(n), o_oct = up.take(4 * n), o_kp = up.take(8 * n), o_sig = up.take(4 * (size_t)f.levels);
+  const size_t o_ids = up.copy_of(f.frame_points, 4 * n), o_out = up.copy_of(f.outlier, n), o_oct = up.take(4 * n), o_kp = up.copy_of(f.kp, 8 * n),
+               o_sig = up.copy_of(f.inv_level_sigma2, 4 * (size_t)f.levels);
   const size_t d_head = down.take(8), d_idx = down.take(4 * n), d_pid = down.take(4 * n), d_nodes = down.take(12 * n), d_bary = down.take(24 * n),
                d_uv = down.take(16 * n), d_sig = down.take_exact(8 * n);
   if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_ids), f.frame_points, 4 * n);
-  std::memcpy(up.host<uint8_t>(o_out), f.outlier, n);
   int32_t* oct = up.host<int32_t>(o_oct);
   for (size_t i = 0; i < n; i++) oct[i] = f.frame_points[i] >= 0 ? f.octave[i] : 0;   // read only where a point is held
-  std::memcpy(up.host<float>(o_kp), f.kp, 8 * n);
-  std::memcpy(up.host<float>(o_sig), f.inv_level_sigma2, 4 * (size_t)f.levels);
   if (const int rc = up.send(c)) return rc;
   if (const int rc = down.alloc(c)) return rc;
   TfSelect s;
@@ -88,7 +84,7 @@ int select_rows(dsh_mpdb* db, const dsh_track_sft_frame* fp, bool solve, const c
   t.bary = down.host<double>(d_bary);
   t.uv = down.host<double>(d_uv);
   t.invsig2 = down.host<double>(d_sig);
-  if (t.M < 0 || t.M > f.N) return dsh_fail(c, DSH_ERR_HIP, std::string(who) + ": the selection returned a row count outside 0 .. N");
+  if (t.M < 0 || t.M > f.N) return refuse(DSH_ERR_HIP, "the selection returned a row count outside 0 .. N");
   return DSH_OK;
 }
 
@@ -112,7 +108,7 @@ int dsh_track_sft_observations(dsh_mpdb* db, const dsh_track_sft_frame* f, dsh_t
   if (!out) return bad("t is NULL");
   DownBlock down;
   TfTable t;
-  if (const int rc = select_rows(db, f, false, "dsh_track_sft_observations", down, t)) return rc;
+  if (const int rc = select_rows(db, f, false, who__, down, t)) return rc;
   if (!tf_table_fits(t, *out)) return bad("capacity (" + std::to_string(out->capacity) + ") < M (" + std::to_string(t.M) + ")");
   tf_hand_out(t, out);
   return DSH_OK;
@@ -123,7 +119,7 @@ int dsh_track_sft(dsh_mpdb* db, const dsh_track_sft_frame* f, int32_t write_back
   if (!r) return bad("r is NULL");
   DownBlock down;
   TfTable t;
-  if (const int rc = select_rows(db, f, true, "dsh_track_sft", down, t)) return rc;
+  if (const int rc = select_rows(db, f, true, who__, down, t)) return rc;
   if (out && !tf_table_fits(t, *out)) return bad("capacity (" + std::to_string(out->capacity) + ") < M (" + std::to_string(t.M) + ")");
   dsh_ctx* x = static_cast<dsh_ctx*>(c);
   if (t.M == 0) {   // not the reference's numbers (an optimiser without observation edges): the input comes back
@@ -145,7 +141,7 @@ int dsh_track_sft(dsh_mpdb* db, const dsh_track_sft_frame* f, int32_t write_back
   }
   if (const int rc = dsh_sft_solve(x, &sf, &rr)) {
     const int m = rc == DSH_ERR_ARG ? refused_observation(c->err) : -1;
-    c->err = "dsh_track_sft: " + c->err;
+    c->err = std::string(who__) + ": " + c->err;
     if (m >= 0 && m < t.M) c->err += " (key point " + std::to_string(t.kp_index[m]) + ")";
     return rc;
   }

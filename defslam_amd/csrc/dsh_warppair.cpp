@@ -72,9 +72,9 @@ int dsh_keyframe_set_view(dsh_mpdb* db, int32_t slot, const dsh_keyframe_view* v
   const dsh_bbs& g = view->warp_grid;
   if (!std::isfinite(g.umin) || !std::isfinite(g.umax) || !std::isfinite(g.vmin) || !std::isfinite(g.vmax) || !bbs_grid_ok(&g)) return bad("bad warp grid");
   dsh_mpdb::SurfKf& sk = db->surf[slot];
-  if (!sk.has_surface) return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_set_view: keyframe " + std::to_string(slot) + " has no resident surface (dsh_keyframe_surface_init)");
-  if (sk.has_view) return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_set_view: keyframe " + std::to_string(slot) + " has a view already");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_set_view")) return rc;
+  if (!sk.has_surface) return refuse(DSH_ERR_STATE, "keyframe " + std::to_string(slot) + " has no resident surface (dsh_keyframe_surface_init)");
+  if (sk.has_view) return refuse(DSH_ERR_STATE, "keyframe " + std::to_string(slot) + " has a view already");
+  DSH_STORE_GATE();
   UpBlock up;
   const size_t o_px = up.copy_of(view->kp_px, 8 * (size_t)k.N);
   if (const int rc = up.copy(c)) return rc;
@@ -93,8 +93,8 @@ int dsh_keyframe_get_view(dsh_mpdb* db, int32_t slot, dsh_keyframe_view* view, f
   if (!view) return bad("view is NULL");
   if (slot < 0 || slot >= db->K) return bad("slot outside the store");
   const dsh_mpdb::SurfKf& sk = db->surf[slot];
-  if (!sk.has_view) return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_get_view: keyframe " + std::to_string(slot) + " has no view (dsh_keyframe_set_view)");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_get_view")) return rc;
+  if (!sk.has_view) return refuse(DSH_ERR_STATE, "keyframe " + std::to_string(slot) + " has no view (dsh_keyframe_set_view)");
+  DSH_STORE_GATE();
   const LmKf k = db->kf[slot];
   if (kp_px && k.N > 0) {
     DownBlock down;
@@ -120,8 +120,7 @@ int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp
   if (!same_context(c, in->ddb)) return bad("the database is NULL, belongs to another context or was detached");
   dsh_kfdb* kfdb = in->kfdb;
   dsh_diffdb* ddb = in->ddb;
-  const std::string ke = kfdb_error(db, kfdb);
-  if (!ke.empty()) return bad(ke);
+  DSH_CHECK(kfdb_error(db, kfdb));
   const int32_t slot = in->slot, anchor = in->anchor;
   if (slot < 0 || slot >= db->K || anchor < 0 || anchor >= db->K) return bad("slot or anchor outside the store");
   if (slot == anchor) return bad("anchor == slot: no point is anchored in the keyframe being added");
@@ -130,10 +129,9 @@ int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp
   if (kfdb->kf[anchor].octave_over) return bad("keyframe " + std::to_string(anchor) + " has an octave >= levels in the keyframe store");
   const int P0 = in->n_pairs, Q = in->n_queries;
   if (P0 < 1 || Q < 0) return bad("n_pairs < 1 or n_queries < 0");
-  std::string ie = index_error(P0, in->pair_idx1, k1.N, "pair_idx1", false);
-  if (ie.empty()) ie = index_error(P0, in->pair_idx2, k2.N, "pair_idx2", true);
-  if (ie.empty()) ie = index_error(Q, in->query_idx1, k1.N, "query_idx1", true);
-  if (!ie.empty()) return bad(ie);
+  DSH_CHECK(index_error(P0, in->pair_idx1, k1.N, "pair_idx1", false));
+  DSH_CHECK(index_error(P0, in->pair_idx2, k2.N, "pair_idx2", true));
+  DSH_CHECK(index_error(Q, in->query_idx1, k1.N, "query_idx1", true));
   if (in->max_iters < 0 || in->max_iters > 1000 || in->min_pairs < 1 || !(in->radius > 0.f) || !std::isfinite(in->radius) || in->th_low > 256 || !std::isfinite(in->lambda))
     return bad("max_iters outside 0 .. 1000, min_pairs < 1, a radius that is not positive and finite, th_low > 256 or a lambda that is not finite");
   const dsh_mpdb::SurfKf &s1 = db->surf[anchor], &s2 = db->surf[slot];
@@ -142,9 +140,9 @@ int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp
   const long long cap_erased = (long long)db->obs.size() + Q;
   if (db->R + Q > INT32_MAX || cap_erased > INT32_MAX) return bad("store full");
   if (!s1.has_view || !s2.has_view)
-    return dsh_fail(c, DSH_ERR_STATE, "dsh_keyframe_warp_pair: keyframe " + std::to_string(s1.has_view ? slot : anchor) + " has no view (dsh_keyframe_set_view)");
-  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, "dsh_keyframe_warp_pair");
-  if (const int rc = dsh_enter(c, "dsh_keyframe_warp_pair")) return rc;
+    return refuse(DSH_ERR_STATE, "keyframe " + std::to_string(s1.has_view ? slot : anchor) + " has no view (dsh_keyframe_set_view)");
+  if (!db->unindexed.empty()) return mpdb_unindexed_error(db, who__);
+  DSH_STORE_GATE();
 
   const dsh_bbs bbs = s1.warp;
   const int Nc = bbs.nptsu * bbs.nptsv, n2 = 2 * Nc, cap = P0 + Q;
@@ -152,21 +150,25 @@ int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp
   hipStream_t st = c->stream;
   // room for every record stage 4 and stage 7 can add, before anything is launched
   HIPCHK(c, mpdb_reserve_log(db, db->R + Q));
-  if (ddb_reserve(ddb, ddb->count + cap) != 0) return dsh_fail(c, DSH_ERR_HIP, "dsh_keyframe_warp_pair: out of device memory while growing the database");
+  if (ddb_reserve(ddb, ddb->count + cap) != 0) return refuse(DSH_ERR_HIP, "out of device memory while growing the database");
 
   // the one block up: the index lists, and the constant operands of the initialisation
   UpBlock up;
-  const size_t o_i1 = up.take(4 * P0z), o_i2 = up.take(4 * P0z), o_q1 = up.take(4 * Qz), o_bend = up.take(8 * Ncz * Ncz), o_ones = up.take_exact(8 * Ncz);
+  const size_t o_i1 = up.copy_of(in->pair_idx1, 4 * P0z), o_i2 = up.copy_of(in->pair_idx2, 4 * P0z), o_q1 = up.copy_of(in->query_idx1, 4 * Qz),
+               o_bend = up.take(8 * Ncz * Ncz), o_ones = up.take_exact(8 * Ncz);
   // the one block down; the erased list lies behind what every call fetches
   DownBlock down;
   const size_t d_hdr = down.take(sizeof(WpHdr)), d_x = down.take(8 * (size_t)n2), d_info = down.take(16), d_costs = down.take(16), d_qmatch = down.take(4 * Qz),
                d_qpoint = down.take(4 * Qz), d_pstate = down.take(P0z), d_qstate = down.take(Qz), d_qadded = down.take(Qz);
+  down.copy_to(d_x, out->x, 8 * (size_t)n2);   // the kernels write all of these whether the caller wants them or not
+  down.copy_to(d_pstate, out->pair_state, P0z);
+  down.copy_to(d_qstate, out->query_state, Qz);
+  down.copy_to(d_qmatch, out->query_match, 4 * Qz);
+  down.copy_to(d_qpoint, out->query_point, 4 * Qz);
+  down.copy_to(d_qadded, out->query_added, Qz);
   const size_t head = down.size;
   const size_t d_erased = down.take_exact(8 * (size_t)cap_erased);
   if (const int rc = up.stage(c)) return rc;
-  std::memcpy(up.host<int32_t>(o_i1), in->pair_idx1, 4 * P0z);
-  std::memcpy(up.host<int32_t>(o_i2), in->pair_idx2, 4 * P0z);
-  if (Q > 0) std::memcpy(up.host<int32_t>(o_q1), in->query_idx1, 4 * Qz);
   dsh::bbs_bending_dense(&bbs, in->lambda, up.host<double>(o_bend));
   std::fill_n(up.host<double>(o_ones), Ncz, 1.0);
   if (const int rc = up.send(c)) return rc;
@@ -279,17 +281,9 @@ int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp
     ddb->max_pid = std::max(ddb->max_pid, h.max_pid);
   }
 
-  dsh_warp_pair_result res_out = *out;   // the caller's arrays
-  if (res_out.x) std::memcpy(res_out.x, down.host<double>(d_x), 8 * (size_t)n2);
-  if (res_out.pair_state) std::memcpy(res_out.pair_state, down.host<uint8_t>(d_pstate), P0z);
-  if (Q > 0) {
-    if (res_out.query_state) std::memcpy(res_out.query_state, down.host<uint8_t>(d_qstate), Qz);
-    if (res_out.query_match) std::memcpy(res_out.query_match, down.host<int32_t>(d_qmatch), 4 * Qz);
-    if (res_out.query_point) std::memcpy(res_out.query_point, qpoint, 4 * Qz);
-    if (res_out.query_added) std::memcpy(res_out.query_added, qadded, Qz);
-  }
+  down.hand_out();
   out->init_ok = h.init_ok; out->fitted = fit ? 1 : 0;
-  std::memcpy(out->info, down.host<int32_t>(d_info), sizeof out->info);
+  std::memcpy(out->info, down.host<int32_t>(d_info), sizeof out->info);   // fields of the result record, not arrays of the caller
   std::memcpy(out->costs, down.host<double>(d_costs), sizeof out->costs);
   out->first_record = db->R - h.n_appended;
   out->n_filtered = h.n_filtered; out->n_matched = h.n_matched; out->n_appended = h.n_appended; out->n_list = h.n_list;
