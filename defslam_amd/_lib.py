@@ -262,6 +262,11 @@ class WarpPairResultC(C.Structure):
                 [("erase", PointEraseCountsC)])
 
 
+class OrbConfigC(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32), ("scale_factor", C.c_float),
+                ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32), ("capacity", C.c_int32), ("pattern", c_i32_p)]
+
+
 DIFFPROP_FIELDS = ["I1u", "I1v", "I2u", "I2v", "J12a", "J12b", "J12c", "J12d", "J21a", "J21b", "J21c", "J21d",
                    "H12uux", "H12uuy", "H12uvx", "H12uvy", "H12vvx", "H12vvy"]
 
@@ -301,6 +306,7 @@ EXPORTED_SYMBOLS = [
     "dsh_keyframe_sfn", "dsh_keyframe_surface_state",
     "dsh_track_keyframe_candidate", "dsh_keyframe_create", "dsh_keyframe_update_connections",
     "dsh_keyframe_set_view", "dsh_keyframe_get_view", "dsh_keyframe_warp_pair",
+    "dsh_orb_create", "dsh_orb_destroy", "dsh_orb_level_sizes", "dsh_orb_detect", "dsh_orb_describe", "dsh_orb_get_plane",
 ]
 DSH_COMM_ID_BYTES = 128
 
@@ -476,6 +482,12 @@ def _bind(path: str, lab: bool) -> C.CDLL:
     L.dsh_keyframe_set_view.argtypes = [vp, i32, C.POINTER(KeyframeViewC)]
     L.dsh_keyframe_get_view.argtypes = [vp, i32, C.POINTER(KeyframeViewC), c_float_p]
     L.dsh_keyframe_warp_pair.argtypes = [vp, C.POINTER(WarpPairInputC), C.POINTER(WarpPairResultC)]
+    L.dsh_orb_create.argtypes = [C.POINTER(OrbConfigC), C.POINTER(vp)]
+    L.dsh_orb_destroy.argtypes = [vp]
+    L.dsh_orb_level_sizes.argtypes = [vp, c_i32_p, c_float_p]
+    L.dsh_orb_detect.argtypes = [vp, c_u8_p, C.c_int64, c_i32_p, c_i32_p]
+    L.dsh_orb_describe.argtypes = [vp, i32, c_i32_p, c_float_p, c_float_p, c_u8_p]
+    L.dsh_orb_get_plane.argtypes = [vp, i32, i32, c_u8_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dsh_last_error", "dsh_stream"):

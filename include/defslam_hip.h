@@ -1584,6 +1584,70 @@ typedef struct dsh_warp_pair_result {
 } dsh_warp_pair_result;
 int dsh_keyframe_warp_pair(dsh_mpdb* db, const dsh_warp_pair_input* in, dsh_warp_pair_result* out);
 
+/* ---- ORB feature front end (ORB_SLAM2::ORBextractor::operator(), Thirdparty/ORBSLAM_2/src/ORBextractor.cc:1047-1118) ----------------
+ * Two device stages with the caller's selection between them, split where the reference splits:
+ *   detect    image up, pyramid (ComputePyramid, :1120-1145) built and kept resident with its blurred copy (:1098-1099), FAST corners per
+ *             30-pixel cell with the two-threshold rule (ComputeKeyPointsOctTree, :765-833), candidates down;
+ *   (host)    the caller's DistributeOctTree (:539-763): its sort compares pointers on ties, a few thousand points per frame;
+ *   describe  the selected key points up, IC_Angle (:77-104) and computeOrbDescriptor (:108-147) on the resident planes, angles and
+ *             descriptors down.
+ * Not covered: masks (ComputePyramid with a mask, runByPixelsMask), ComputeKeyPointsOld, DistributeOctTree, Frame's undistortion.
+ *
+ * READINGS, NOT VERIFIED AGAINST AN OPENCV BUILD.  The OpenCV steps of the reference are restated here in integers or single IEEE float32
+ * operations from OpenCV's documented behaviour; no OpenCV build was available to compare with.  Each reading and the behaviour it reads:
+ *   level sizes   sf[0] = 1, sf[l] = sf[l-1] * scale_factor in float; inv[l] = 1.0f / sf[l]; size = cvRound((float)W0 * inv[l]) per axis,
+ *                 cvRound = round half to even (:415-431, :1124-1125).
+ *   resize        cv::resize INTER_LINEAR on 8-bit data, the fixed-point path with INTER_RESIZE_COEF_BITS = 11.  Per axis, sc = (double)src / dst:
+ *                 f = (float)((d + 0.5) * sc - 0.5), s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= src - 1: s = src - 1, f = 0; the second tap
+ *                 index is clamped to src - 1; taps c0 = cvRound((1.f - f) * 2048), c1 = cvRound(f * 2048).  Horizontal h = S[s] * a0 + S[s+1] * a1,
+ *                 vertical D = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2.
+ *   frame         copyMakeBorder with BORDER_REFLECT_101, 19 pixels, made from the level itself (BORDER_ISOLATED) for every level.
+ *   blur          cv::GaussianBlur 7 x 7, sigma 2, 8-bit: weights q = cvRound(k * 256) of the normalised double Gaussian, (18, 34, 49, 55, 49,
+ *                 34, 18), sum 257, not renormalised; row pass then column pass in exact integers over the frame; min(255, (sum + 32768) >> 16).
+ *                 The blurred plane is defined 3 pixels beyond the level on every side, computed from the frame: inside the level this is the
+ *                 reference's blur of the cloned level, outside it replaces what the reference reads outside its cloned buffer.
+ *   FAST          cv::FAST 9/16 with non-maximum suppression on each cell's sub-image.  d_k = I(circle_k) - I(p) on the radius-3 circle of 16;
+ *                 M(p) = the maximum over the 16 arcs of 9 contiguous circle pixels and both signs of min_k(+-d_k); p is a corner at threshold t
+ *                 iff M(p) > t and its response is M(p) - 1 (cornerScore<16>).  Corners only at least 3 pixels inside the sub-image; a corner is
+ *                 kept iff its response is strictly greater than that of its 8 neighbours, where a neighbour that is no corner at the threshold
+ *                 in use or lies outside the cell's detection region counts 0.  A cell runs at ini_th_fast and, only if that leaves it empty,
+ *                 again at min_th_fast.  Cells as :773-806 computes them.
+ *   angle         cv::fastAtan2 as the scalar polynomial: c = min(ax, ay) / (max(ax, ay) + (float)DBL_EPSILON), a = (((p7 c^2 + p5) c^2 + p3) c^2 + p1) c
+ *                 with p1, p3, p5, p7 = 0.9997878412794807f, -0.3258083974640975f, 0.1555786518463281f, -0.04432655554792128f, each times
+ *                 (float)(180 / pi); 90 - a if ay > ax, 180 - a if x < 0, 360 - a if y < 0.  The moments are integers over the circular patch of
+ *                 the unblurred level centred at (cvRound(x), cvRound(y)).
+ *   descriptor    ang = angle * (float)(pi / 180.f); a = (float)cos((double)ang), b = (float)sin((double)ang); pattern point (px, py) samples the
+ *                 blurred plane at row cy + cvRound(px * b + py * a), column cx + cvRound(px * a - py * b); bit k of byte i is
+ *                 sample(16 i + 2 k) < sample(16 i + 2 k + 1).  All float arithmetic is float32, one rounding per operation.
+ * The sampling pattern (the reference's bit_pattern_31_) is an argument, as it is of computeOrbDescriptor.
+ *
+ * Candidates of a level come in the reference's order: cell row, cell column, then raster (y, then x) inside the cell; coordinates are
+ * level pixels (the reference's pt after :847-848), the response is M - 1.  The placement does not depend on scheduling.
+ * A context is named inside the configuration; the extractor is a device-resident object like the stores: destroying its context first
+ * is safe (every later call but the destroy returns DSH_ERR_ARG).  On a host-only context the create and the level sizes work, the three
+ * calls that need the device return DSH_ERR_NO_DEVICE after their argument checks. */
+typedef struct dsh_orb dsh_orb;
+typedef struct dsh_orb_config {
+  dsh_ctx* ctx;
+  int32_t width, height, levels;    /* 1 <= levels <= 32; every level at least 62 pixels in both dimensions */
+  float scale_factor;               /* > 1 */
+  int32_t ini_th_fast, min_th_fast; /* 1 <= min <= ini <= 255 */
+  int32_t capacity;                 /* candidates per level */
+  const int32_t* pattern;           /* 512 points: x, y, with x^2 + y^2 <= 342 */
+} dsh_orb_config;
+int dsh_orb_create(const dsh_orb_config* cfg, dsh_orb** out);
+int dsh_orb_destroy(dsh_orb* orb);
+int dsh_orb_level_sizes(const dsh_orb* orb, int32_t* wh /* levels*2: width, height */, float* scale /* levels: sf[l] */);
+/* counts[l]: the candidates of level l; cand[(l * capacity + i) * 3]: x, y, response.  A level with more candidates than capacity is
+ * DSH_ERR_ARG (the message names the level and the count), counts still holds the true counts and cand the first `capacity` of a level. */
+int dsh_orb_detect(dsh_orb* orb, const uint8_t* image, int64_t row_stride, int32_t* counts /* levels */, int32_t* cand /* levels*capacity*3 */);
+/* Key points of the last detected image: level and position in level pixels, the rounded position at least 16 pixels from every edge of
+ * the level.  DSH_ERR_STATE before the first detect. */
+int dsh_orb_describe(dsh_orb* orb, int32_t n, const int32_t* level, const float* xy /* n*2, level pixels */, float* angle /* n, degrees */,
+                     uint8_t* desc /* n*32 */);
+/* Tests, debugging.  blurred == 0: the level with its 19-pixel frame, (h + 38) rows of (w + 38); else the blurred plane, (h + 6) rows of (w + 6). */
+int dsh_orb_get_plane(dsh_orb* orb, int32_t level, int32_t blurred, uint8_t* out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
